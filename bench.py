@@ -9,9 +9,14 @@ AnimScripter.cpp:555-572), self-contact off: element assembly + sparse Cholesky 
 One "step" = one pass of the solveSub_IP loop (Optimizer.cpp:1829-2204) = one Newton iteration,
 time-step boundaries (scripted DBC motion, BE velocity update) included as they occur.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL: the direct solver sharded by subtrees, elements and contact-pair lists by the
 CSR rows those subtrees read -- no matrix value crosses ranks; the line's `comm_per_iter` says what does.  See DESIGN.md section 6.)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line used to carry: the roofline
+and solver figures, the model of DESIGN.md section 6 and the second workload (N > 1), and on one GPU the contact, scene and 1.12 M-tet
+sub-records and the CPU baselines (--no-contact / --no-large / --no-cpu-baseline leave parts of that out).  --dump-outputs DIR writes
+what the last timed step left for a caller (ipcgpu_opt_get_state) as DIR/<name>.npy, float64.
 """
 import argparse
 import json
@@ -181,12 +186,40 @@ def progress(msg):
     print(f"[bench {time.time() - _T0:7.1f} s] {msg}", file=sys.stderr, flush=True)
 
 
+STATE_SCALARS = ("E", "stepSize", "targetGRes", "innerIterAmt", "timestep", "alphaFeasible", "kappa", "dHat")
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: what the timed path hands a caller after its last step (ipcgpu_opt_get_state), float64, as <out_dir>/<name>.npy.  The nodal arrays are
+    written whole while they fit the budget (mat150: 3.2 MB); above it, the same fixed seeded sample of nodes from each (node ids in sample_nodes.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    s = ctx.state()
+    nodal = {"positions": np.asarray(s["V"], dtype=np.float64).reshape(-1, 3),
+             "search_direction": np.asarray(s["searchDir"], dtype=np.float64).reshape(-1, 3),
+             "gradient": np.asarray(s["gradient"], dtype=np.float64).reshape(-1, 3)}
+    n = nodal["positions"].shape[0]
+    arrays = {"state_scalars": np.array([float(s[k]) for k in STATE_SCALARS], dtype=np.float64)}
+    per_node = 8 * 3 * len(nodal)
+    if n * per_node > DUMP_BUDGET_BYTES - 4096:
+        keep = np.sort(np.random.default_rng(0).choice(n, (DUMP_BUDGET_BYTES - 4096) // (per_node + 8), replace=False))
+        nodal = {k: v[keep] for k, v in nodal.items()}
+        arrays["sample_nodes"] = keep.astype(np.float64)
+    arrays.update(nodal)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    progress(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--size", type=int, default=150, help="mat N (N x N x 2 nodes); 150 = BASELINE config[1]")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline / solver figures, the N > 1 model and "
+                    "second workload, the N = 1 sub-records and CPU baselines (each a run of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-contact", action="store_true", help="skip the contact sub-records (2 x mat100 stack with self-collision; BASELINE's contact "
                     "configurations as shipped: 4_rodsTwist, 12_sphereOnMat; N = 1 only)")
@@ -294,10 +327,12 @@ def main():
     xs1 = ctx.solver_exchange_stats()
 
     progress(f"timed region done: {args.steps / elapsed:.1f} it/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
     # collective when the solver is sharded: every rank takes part
-    f_ms, s_ms = ctx.bench_factor_solve(3)
+    f_ms, s_ms = ctx.bench_factor_solve(3) if args.full else (None, None)
     model = None
-    if distributed and solver_sharded:
+    if args.full and distributed and solver_sharded:
         cp = ctx.solver_critical_path()
         wait_ms = (xs1["wait_ms"] - xs0["wait_ms"]) / args.steps
         one_rank = single_rank_reference(args, ipc_amd, local_rank, args.size, max(20, args.steps // 4), 5)  # every rank, on its own GPU: no communication inside
@@ -314,11 +349,6 @@ def main():
             "backsolve_ms": 1e3 * timers[4] / K,
             "timestep_ms": 1e3 * timers[11] / K,
         }
-        # dominant HBM-bound kernel: fused element assembly (gradient + projected Hessian -> CSR)
-        ms_asm, bytes_asm = ctx.bench_assembly(0.04 ** 2, reps=20)
-        ach = bytes_asm / (ms_asm * 1e-3) / 1e9
-        stream_gbs = ctx.bench_stream(1 << 30, 10)
-        st = ctx.linsys_stats()
         out = {
             "metric": "newton_iterations_per_sec",
             "value": K / elapsed,
@@ -370,8 +400,16 @@ def main():
             "split_note": "factor_ms holds the numeric factorisation AND both triangular sweeps (the forward sweep of a level runs on its own stream beside the "
                           "factorisation of the levels above, MfNumeric::factorizeSolve); backsolve_ms is what follows them in the same bucket: the batched "
                           "read-back of |p|_inf, the inversion step filter and E -- and the first trial of the line search (step, inversion flag, E at the trial "
-                          "point), taken on the device behind the solve: ccd_linesearch_ms is what a rejected trial costs.  solver.factor_ms / solver.solve_ms below time the two separately "
-                          "(ipcgpu_bench_factor_solve, HIP events)",
+                          "point), taken on the device behind the solve: ccd_linesearch_ms is what a rejected trial costs.  With --full, solver.factor_ms / solver.solve_ms time the two "
+                          "separately (ipcgpu_bench_factor_solve, HIP events)",
+        }
+    if rank == 0 and args.full:
+        # dominant HBM-bound kernel: fused element assembly (gradient + projected Hessian -> CSR)
+        ms_asm, bytes_asm = ctx.bench_assembly(0.04 ** 2, reps=20)
+        ach = bytes_asm / (ms_asm * 1e-3) / 1e9
+        stream_gbs = ctx.bench_stream(1 << 30, 10)
+        st = ctx.linsys_stats()
+        out.update({
             "roofline": {
                 "kernel": "k_assemble_patch<true> (fused NH gradient + PSD-projected Hessian + mass/DBC diagonal -> symmetric-upper CSR, atomic-free)",
                 "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
@@ -399,9 +437,9 @@ def main():
             "solver": {"nnzL": st["nnzL"], "factor_gflop": st["flops"] / 1e9, "fronts": st["fronts"], "levels": st["levels"],
                        "factor_ms": f_ms, "solve_ms": s_ms, "factor_gflops_per_s": st["flops"] / 1e9 / (f_ms * 1e-3),
                        "precompute_s": t_pre},
-        }
+        })
     ctx.close()
-    if rank == 0 and world == 1 and not args.no_contact:
+    if rank == 0 and world == 1 and args.full and not args.no_contact:
         # the contact half of the path, timed by the same process: two stacked mat100 sheets with self-collision on (barrier terms,
         # constraint sets, CCD, pattern changes); BASELINE's metric is quoted on the contact-free matTwist above, this is a sub-record
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -413,7 +451,7 @@ def main():
                           "split_ms_per_iter": r["split_ms_per_iter"],
                           "active_constraints_per_step": [c["nActive"] for c in r["contact_state_per_step"]],
                           "pattern_changes": r["contact_state_per_step"][-1]["nPatternChanges"], "intersected_at_end": r["intersected_at_end"]}
-    if rank == 0 and world == 1 and not args.no_contact:
+    if rank == 0 and world == 1 and args.full and not args.no_contact:
         # BASELINE configs[1]'s scene AS SHIPPED: 14_matTwist.txt:15 says `selfCollisionOn` (the headline above follows BASELINE and strips it).  Two windows: the first
         # steps (contact machinery running, nothing active) and the steps after the sheet has wrapped onto itself (tools/bench_mat_twist.py)
         try:
@@ -422,7 +460,7 @@ def main():
             out["mat_twist_as_shipped"] = bench_mat_twist.run(args.size)
         except Exception as e:  # noqa: BLE001
             out["mat_twist_as_shipped"] = {"value": None, "note": f"not measured: {e!r}"[:300]}
-    if rank == 0 and world == 1 and not args.no_contact and not args.no_large:
+    if rank == 0 and world == 1 and args.full and not args.no_contact and not args.no_large:
         # BASELINE configs[4] scale ("~1M tets: full pipeline") on ONE GPU, SURVEY 8d item 5's stand-in: three mat250 sheets stacked with gaps < sqrt(dHat) --
         # 1.12 M tets, 1.36 M active constraints + 0.25 M mollified pairs at the first step.  Same split as `contact`.
         try:
@@ -438,7 +476,7 @@ def main():
                                     "solver": r.get("solver")}
         except Exception as e:  # noqa: BLE001
             out["contact_large"] = {"value": None, "note": f"not measured: {e!r}"[:300]}
-    if rank == 0 and world == 1 and not args.no_contact:
+    if rank == 0 and world == 1 and args.full and not args.no_contact:
         # BASELINE configs[3] and configs[2] AS SHIPPED, from the fixtures the reference's own main() produced (tests/golden/ref_scene_*.npz): timed, and the
         # Newton iteration count of every step compared with the reference's in the same record (tools/bench_scene.py)
         import bench_scene
@@ -451,14 +489,14 @@ def main():
                 out[name] = bench_scene.run(name, steps, first, what)
             except Exception as e:  # noqa: BLE001  (a sub-record must not take the bench line down)
                 out[name] = {"value": None, "note": f"not measured: {e!r}"[:300]}
-    if rank == 0 and world == 1 and not args.no_large and args.size != args.large_size and args.large_size:
+    if rank == 0 and world == 1 and args.full and not args.no_large and args.size != args.large_size and args.large_size:
         # the same twist scene at 1.12 M tets (mat433) on ONE GPU: where the latency-bound steps amortise, the fractions are what the kernels do when fed
         try:
             progress(f"roofline_large (mat{args.large_size})")
             out["roofline_large"] = large_single(args, ipc_amd)
         except Exception as e:  # noqa: BLE001
             out["roofline_large"] = {"value": None, "note": f"not measured: {e!r}"[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # The CPU baselines come LAST: their thread pools (OpenMP workers of the port, the std::thread pool behind the reference's parallel_for) stay alive in this
         # process, and with them in the background the host side of the contact sub-record above measured 1.0 ms per iteration slower (symbolic analysis 1.11 -> 1.52,
         # step bounds 0.63 -> 1.13 ms: profiles/r05_bench_line.json against r05_entry_lists_on_the_device_ab.txt).  Nothing on the GPU runs beside them.
@@ -466,7 +504,7 @@ def main():
         out["cpu_baseline"] = cpu_baseline(V, F, left, right, args.cpu_iters)
         progress("cpu_reference (the reference's sources, 16 threads)")
         out["cpu_reference"] = cpu_reference(V, F)
-    if distributed and args.large_size and args.size != args.large_size:
+    if distributed and args.full and args.large_size and args.size != args.large_size:
         # a second, >= 1 M-tet strong-scaling point for the curve (mat150's 2.9 ms iteration is mostly the dependent pivot chain of
         # its top separators, which does not shard): same script, same measurement, fewer steps
         big = large_workload(args, rank, local_rank, world, torch, dist, ipc_amd)

@@ -31,7 +31,9 @@ def build_exe():
 
 
 REF_SRC = "/root/reference/src"
-EXE_REF = os.path.join(BUILD, "test_adapters_ref")
+# executables built from the reference's sources lie beside libipcref.so under oracle/_ref/, with everything else built from them
+REF_BUILD = os.path.join(ROOT, "oracle", "_ref", "adapters")
+EXE_REF = os.path.join(REF_BUILD, "test_adapters_ref")
 LIB_REF = os.path.join(ROOT, "oracle", "_ref", "libipcref.so")
 
 
@@ -42,7 +44,7 @@ def build_exe_ref():
     LinSysSolverType::HIP is the one enum value a maintainer adds: the unmodified tree is given CHOLMOD's in its place."""
     from ipc_amd import build as b
     b.build()
-    os.makedirs(BUILD, exist_ok=True)
+    os.makedirs(REF_BUILD, exist_ok=True)
     src = os.path.join(ROOT, "tests", "adapters", "test_adapters.cpp")
     deps = [src, LIB_REF, os.path.join(ROOT, "include", "ipcgpu.h")] + [os.path.join(ROOT, "include", "adapters", f) for f in os.listdir(os.path.join(ROOT, "include", "adapters"))]
     if os.path.exists(EXE_REF) and all(os.path.getmtime(EXE_REF) >= os.path.getmtime(d) for d in deps):
@@ -58,7 +60,7 @@ def build_exe_ref():
     return EXE_REF
 
 
-MAIN_HIP = os.path.join(BUILD, "ipc_main_hip")
+MAIN_HIP = os.path.join(REF_BUILD, "ipc_main_hip")
 REF_OBJ = os.path.join(ROOT, "oracle", "_ref", "obj")
 
 
@@ -68,7 +70,7 @@ def _ref_includes():
 
 
 def build_main_hip():
-    """tests/adapters/_build/ipc_main_hip: the reference's OWN main.cpp (compiled where it lies, tests/adapters/main_hook.hpp
+    """oracle/_ref/adapters/ipc_main_hip: the reference's OWN main.cpp (compiled where it lies, tests/adapters/main_hook.hpp
     pre-included: the one `new Optimizer` of main.cpp:1397 becomes `new HipOptimizer`) + include/adapters/HipOptimizer.hpp +
     the reference's other compiled sources (the objects oracle/Makefile.ref built) + the factory line of
     tests/adapters/main_hip_plug.cpp.  Round 5: the reference's Optimizer.cpp is compiled once more for this executable, UNCHANGED, with
@@ -77,7 +79,7 @@ def build_main_hip():
     Build container only; the executable travels to the GPU box."""
     from ipc_amd import build as b
     b.build()
-    os.makedirs(BUILD, exist_ok=True)
+    os.makedirs(REF_BUILD, exist_ok=True)
     hook = os.path.join(ROOT, "tests", "adapters", "main_hook.hpp")
     plug = os.path.join(ROOT, "tests", "adapters", "main_hip_plug.cpp")
     ctcd = os.path.join(ROOT, "oracle", "ref_plug.cpp")
@@ -96,7 +98,7 @@ def build_main_hip():
             (plug, "main_hip_plug.o", []), (ctcd, "ctcd_plug.o", ["-DIPCREF_PLUG_CTCD_ONLY"])]
     procs = []
     for src, name, extra in jobs:
-        o = os.path.join(BUILD, name)
+        o = os.path.join(REF_BUILD, name)
         objs.append(o)
         procs.append(subprocess.Popen(["g++"] + flags + extra + ["-c", src, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     for pr in procs:
@@ -152,7 +154,7 @@ def test_adapters_run_on_the_gpu():
 
 @pytest.mark.gpu
 def test_adapters_built_on_the_reference_headers_run_on_the_gpu():
-    """tests/adapters/_build/test_adapters_ref: HipLinSysSolver / HipElasticEnergy deriving from the reference's own LinSysSolver /
+    """oracle/_ref/adapters/test_adapters_ref: HipLinSysSolver / HipElasticEnergy deriving from the reference's own LinSysSolver /
     Energy<3>, on a Mesh<3> of the reference's own Mesh.cpp -- built where /root/reference exists (__graft_entry__.build)."""
     if not (os.path.exists(EXE_REF) and os.path.exists(LIB_REF)):
         pytest.skip("built in the container that holds /root/reference")

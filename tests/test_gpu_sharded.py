@@ -371,7 +371,8 @@ def test_bench_line_at_two_ranks_on_one_device():
     import json
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29547",
-           os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--single-device-test", "--size", "60", "--large-size", "80"]
+           os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--single-device-test", "--size", "60", "--large-size", "80",
+           "--full"]
     r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

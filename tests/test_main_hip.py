@@ -1,4 +1,4 @@
-"""The reference's OWN main() on the HIP path: tests/adapters/_build/ipc_main_hip is src/main.cpp compiled where it lies (its one
+"""The reference's OWN main() on the HIP path: oracle/_ref/adapters/ipc_main_hip is src/main.cpp compiled where it lies (its one
 `new Optimizer<DIM>` at :1397 redirected to include/adapters/HipOptimizer.hpp by the pre-included tests/adapters/main_hook.hpp),
 linked with the reference's other compiled sources and libipcgpu.so (tests/test_adapters.py::build_main_hip; built in the
 container that holds /root/reference, the executable travels to the GPU box).  Scene scripts the reference itself ran
@@ -71,7 +71,7 @@ def run_main_hip(S, meshes, tmp, steps, mode="resident", extra_env=None):
     return read_run(out, steps) + (log,)
 
 
-needs_exe = pytest.mark.skipif(not os.path.exists(MAIN_HIP), reason="tests/adapters/_build/ipc_main_hip is built in the container that holds /root/reference")
+needs_exe = pytest.mark.skipif(not os.path.exists(MAIN_HIP), reason="oracle/_ref/adapters/ipc_main_hip is built only where the reference's sources are present")
 
 
 @pytest.mark.skipif(not (os.path.isdir(REF_SRC) and os.path.exists(LIB_REF)), reason="needs the reference-compiled library (build container)")

@@ -1,5 +1,6 @@
 """Tet-mesh files through the C ABI (IglUtils::readTetMesh / saveTetMesh, IglUtils.cpp:300-361, 451-584).
 Host-only code: runs without a GPU."""
+import gzip
 import os
 
 import numpy as np
@@ -8,7 +9,7 @@ import pytest
 from ipc_amd import lib as gl
 from ipc_amd import scene
 
-REF_MESHES = "/root/reference/input/tetMeshes"
+REF_MESHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_meshes")  # input/tetMeshes/*.msh as shipped, gzipped (tools/make_golden_inputs.py)
 
 
 def _mesh():
@@ -139,11 +140,12 @@ def _independent_parse_41(path):
     return np.array(V).reshape(-1, 3), np.array(T, dtype=np.int32)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MESHES), reason="the reference's meshes are only present in the build container")
 @pytest.mark.parametrize("name,nV,nT", [("bar-2523", 886, 2523), ("mat20x20", 800, None), ("cube", 8, None), ("sphere1K", None, 6851), ("mat40x40", None, 9126)])
-def test_reference_meshes(name, nV, nT):
+def test_reference_meshes(tmp_path, name, nV, nT):
     """Real paper-scene meshes (bar-2523 = 886 nodes / 2 523 tets, sphere1K = 6 851 tets, mat40x40 = 9 126 tets)."""
-    p = os.path.join(REF_MESHES, name + ".msh")
+    p = tmp_path / (name + ".msh")
+    with gzip.open(os.path.join(REF_MESHES, name + ".msh.gz"), "rb") as f:
+        p.write_bytes(f.read())
     V, T, SF = gl.read_tet_mesh(p)
     assert nV is None or V.shape[0] == nV
     assert nT is None or T.shape[0] == nT

@@ -1,6 +1,7 @@
 """Scene scripts (src/Config.cpp:97-620) driving the C ABI: grammar, shape assembly, and the tutorial
 scene run on the GPU beside the oracle through the same calls."""
 import os
+import tarfile
 
 import numpy as np
 import pytest
@@ -8,7 +9,7 @@ import pytest
 from ipc_amd import lib as gl
 from ipc_amd import scene, scene_script as ss
 
-REF_INPUT = "/root/reference/input"
+REF_SCRIPTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_scene_files.tar.gz")  # every input/**/*.txt (tools/make_golden_inputs.py)
 
 TUTORIAL = """
 shapes input 2
@@ -102,18 +103,16 @@ def test_dirichlet_and_neumann_boxes_follow_the_shape_through_its_transform():
     assert np.ptp(sel[:, 1]) < 1e-12 and np.ptp(sel[:, 0]) > 0.5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason="the reference's scene files are only present in the build container")
 def test_reference_scene_files_parse():
     ok, unsupported = [], {}
-    for root, _, files in os.walk(REF_INPUT):
-        for f in files:
-            if not f.endswith(".txt"):
+    with tarfile.open(REF_SCRIPTS) as tar:
+        for m in tar.getmembers():
+            if not (m.isfile() and m.name.endswith(".txt")):
                 continue
-            p = os.path.join(root, f)
             try:
-                c = ss.SceneConfig.parse(open(p, errors="replace").read(), "/root/reference")
+                c = ss.SceneConfig.parse(tar.extractfile(m).read().decode(errors="replace"), "reference")
                 if c.shapes:
-                    ok.append(os.path.relpath(p, REF_INPUT))
+                    ok.append(m.name)
             except ss.UnsupportedKeyword as e:
                 unsupported[str(e).split()[0]] = unsupported.get(str(e).split()[0], 0) + 1
             except (ValueError, IndexError):

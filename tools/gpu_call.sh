@@ -4,7 +4,7 @@
 #   CONTACT=1        tools/bench_contact.py (2 x mat100) plain + under rocprofv3 --kernel-trace --stats -> contact.json, contact_kernel_stats.md
 #   LARGE="250 3"    tools/bench_contact.py at that size (contact_large) + kernel stats                -> contact_large.json, contact_large_kernel_stats.md
 #   TWIST=1          tools/bench_mat_twist.py                                                          -> mat_twist.json
-#   BENCH="flags"    bench.py with those flags                                                         -> bench.json  (BENCH_PROF=1: also under rocprofv3)
+#   BENCH="flags"    bench.py --full with those flags                                                  -> bench.json  (BENCH_PROF=1: also under rocprofv3)
 #   CMD="..."        anything else, last
 # usage: gpurun --timeout 1500 -- 'NAME=r6_call1 TESTS=all CONTACT=1 bash tools/gpu_call.sh'
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -65,7 +65,7 @@ PY
 fi
 if [ -n "$BENCH" ]; then
   [ "$BENCH" = "default" ] && BENCH=""
-  timeout 900 python bench.py $BENCH > $out/bench.json 2>> $out/err.log
+  timeout 900 python bench.py --full $BENCH > $out/bench.json 2>> $out/err.log
   python - $out/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -75,7 +75,7 @@ for k in ("rods_twist", "sphere_on_mat", "roofline_large", "contact_large", "mat
     if k in d:
         print("  ", k, json.dumps(d[k])[:400])
 PY
-  if [ -n "$BENCH_PROF" ]; then prof bench python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-contact --no-large $BENCH; fi
+  if [ -n "$BENCH_PROF" ]; then prof bench python "$PWD/bench.py" --full --no-cpu-baseline --no-contact --no-large $BENCH; fi
 fi
 if [ -n "$CMD" ]; then bash -c "$CMD" 2>&1 | filt | tail -${CMD_TAIL:-40}; fi
 tail -5 $out/err.log 2>/dev/null || true

@@ -11,12 +11,12 @@ R=$GRAFT_REPO_ROOT
 if [ -z "$SKIP_TESTS" ]; then
   ( timeout 1500 python -m pytest tests -m gpu -q --tb=line -rf 2>&1 | grep -E "FAILED|passed|failed|assert" | cut -c1-400 | tail -12 ) > $out/gpu_tests.txt; cat $out/gpu_tests.txt
 fi
-timeout 400 python bench.py > $out/bench_line.json 2> $out/bench.err; grep bench $out/bench.err | tail -12
+timeout 400 python bench.py --full > $out/bench_line.json 2> $out/bench.err; grep bench $out/bench.err | tail -12
 rm -rf /tmp/prof_r05
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_r05 -o run -- python $R/bench.py --no-cpu-baseline --no-contact --no-large --steps 60 --warmup 10 > $R/$out/bench_line_under_rocprof.json 2> /dev/null )
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_r05 -o run -- python $R/bench.py --full --no-cpu-baseline --no-contact --no-large --steps 60 --warmup 10 > $R/$out/bench_line_under_rocprof.json 2> /dev/null )
 db=$(find /tmp/prof_r05 -name "*.db" | head -1)
 [ -n "$db" ] && python tools/rocprof_summary.py $db $out/kernel_stats.md > /dev/null && python tools/rocprof_timeline.py $db 12 > $out/timeline.txt 2>&1
-timeout 300 python bench.py --no-cpu-baseline --no-contact --no-large --size 433 --steps 12 --warmup 3 > $out/bench_mat433.json 2> /dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-contact --no-large --size 433 --steps 12 --warmup 3 > $out/bench_mat433.json 2> /dev/null
 rm -rf /tmp/profc_r05
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/profc_r05 -o run -- python $R/tools/bench_contact.py --n 100 --steps 12 > $R/$out/contact_bench_under_rocprof.json 2> /dev/null )
 db=$(find /tmp/profc_r05 -name "*.db" | head -1)

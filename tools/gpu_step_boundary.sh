@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-rm -rf /tmp/prof_b; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_b -o b -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-contact --no-large --steps 60 > /dev/null 2>&1 )
+R=$PWD; rm -rf /tmp/prof_b; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_b -o b -- python $R/bench.py --full --no-cpu-baseline --no-contact --no-large --steps 60 > /dev/null 2>&1 )
 db=$(find /tmp/prof_b -name "*.db" | head -1)
 python - $db <<'PY'
 import sqlite3, sys

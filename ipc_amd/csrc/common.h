@@ -79,6 +79,28 @@ struct DevBuf {
     }
 };
 
+// Counters that every pass run to its end leaves at zero: a count kernel adds to them, a scan turns them into offsets, and the fill kernel takes its slots by
+// counting them back down.  They are cleared when allocated and after a pass that was left between the two kernels (an exception), never on the way of a
+// pass that completes.
+struct ZeroKeptCounters {
+    DevBuf<int> buf;
+    bool dirty = false;
+    // before the count kernel: at least `count` counters, all zero.  A large enough array is neither shrunk nor cleared; one that grows is a new allocation
+    // and is cleared whole.
+    int* begin(size_t count, hipStream_t s)
+    {
+        if (buf.n < count) {
+            dirty = true;
+            buf.ensure(count);
+        }
+        if (dirty) buf.zero(s);
+        dirty = true;
+        return buf.p;
+    }
+    void done() { dirty = false; } // the kernel that counts back down is enqueued
+    void reset(hipStream_t s) { buf.zero(s); } // a pass that starts over behind its count kernel: cleared now
+};
+
 // pinned host scalar block for small readbacks
 template <class T>
 struct PinnedBuf {

@@ -20,6 +20,12 @@ namespace ipcgpu {
 class HipMesh;
 class HipLinSysSolver;
 
+// uniform grid of the broad phase (cell_of, hip_contact.hip): laid out on the host, taken by value by the kernels
+struct Grid {
+    double lo[3], h;
+    int dim[3];
+};
+
 class HipContact {
 public:
     explicit HipContact(hipStream_t s) : stream(s)
@@ -131,34 +137,39 @@ public:
     void frictionConnectivity(std::vector<std::pair<int, int>>& pairs) const; // appends
 
 private:
-    struct GridHost {
-        double lo[3], h;
-        int dim[3];
-        long long nCells;
-    };
-    GridHost makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell);
-    void buildCells(const GridHost& g, int nPrim, int nv, const int* prim_dev, const double* x_dev, const double* p_dev, double alpha, double infl,
+    // host side of the grids: the swept grid of ccdFull (own bounding box, two synchronisations), the grid of a build or check over box_ padded by two cells
+    // of size h (grown until the grid has at most 2^26 cells), and the box of the positions measured synchronously (first build or check of a surface)
+    Grid makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells);
+    Grid gridOverBox(double h, long long& nCells) const;
+    void measureBox(int nV, const double* x_dev);
+    void buildCells(const Grid& g, long long nCells, int nPrim, int nv, const int* prim_dev, const double* x_dev, const double* p_dev, double alpha,
         DevBuf<int>& cnt, DevBuf<int>& start, DevBuf<int>& items);
+    void* scanTmp(size_t bytes); // temporary storage of a hipcub call, grown on demand
+    template <class T>
+    void exclusiveSum(const T* in, T* out, int count);
     DevBuf<int> d_cand_, d_ids_;
     DevBuf<double> d_vals_;
     DevBuf<unsigned long long> ccdOut_, ccdHits_;
     DevBuf<int> d_codimPoints;
     DevBuf<int> cellCountT_, cellCountE_, cellStartT_, cellStartE_, cellItemsT_, cellItemsE_, outPT_, outEE_, counters_;
-    DevBuf<int> d_v2sv, refVbox_, refCount_, refStart_, refItems_; // reference-mode sweep: node -> surface index, index boxes, the three cell structures in one
+    DevBuf<int> d_v2sv, refVbox_, refStart_, refItems_; // reference-mode sweep: node -> surface index, index boxes, the three cell structures in one
+    ZeroKeptCounters refCount_;
     DevBuf<double> bboxPartial_;
-    bool haveBox_ = false; // box_: the bounding box the last constraint-set build measured (the next build's grid is laid over it)
+    bool haveBox_ = false; // box_: the bounding box the last constraint-set build or intersection check measured (the next grid is laid over it)
     double box_[6] = { 0, 0, 0, 0, 0, 0 };
-    DevBuf<int> gridCount_, gridStart_, gridItems_; // the narrow phase's grids, triangles and edges in one array of 2 nCells + 1 cells (k_grid_insert_both)
+    // the narrow phase's grids, triangles and edges in one array of 2 nCells + 1 cells (k_grid_insert_both); the intersection check uses nCells + 1 of them
+    ZeroKeptCounters gridCount_;
+    DevBuf<int> gridStart_, gridItems_;
     // on-device assembly of the sets (buildConstraintSet)
     int nActive_ = 0, nPara_ = 0, nCand_ = 0;
     mutable bool hostStale_ = false;
     DevBuf<unsigned long long> sortKeyIn_, sortKeyOut_, flags_, flagPos_;
     DevBuf<int> permPT_, dupTuple_, dupSorted_, closeIdx_;
     // counting sorts of the record lists (by first primitive) and of the duplicate candidates (by vertex): counters, bucket starts, bucket contents, runs
-    DevBuf<int> bucketCount_, bucketStart_, bucketSeg_, dupCount_, dupStart_, runs_, runPos_;
+    ZeroKeptCounters bucketCount_, dupCount_;
+    DevBuf<int> bucketStart_, bucketSeg_, dupStart_, runs_, runPos_;
     void readbackInit();
-    bool hessErrPending_ = false, refDirty_ = false;
-    bool countersDirty_ = false; // a build was left half-way (exception): the counters are cleared before the next one
+    bool hessErrPending_ = false;
     PinnedBuf<unsigned long long> readback_; // BuildReadback: what the host reads between the stages of a build (mapped memory, written by the kernels)
     DevBuf<double> closeVal_;
     DevBuf<char> scanTmp_;
@@ -166,8 +177,8 @@ private:
     // contents of the counting sort
     DevBuf<double> detVals_;
     DevBuf<unsigned> detKey_;
-    DevBuf<int> detCount_, detStart_, detSeg_, detSorted_, detRow_, hessPerm_; // hessPerm_: the two lists' indices binned by stencil kind (k_bin_stencils)
-    bool detDirty_ = false; // a pass was left between its kernel and its fill (exception): the counters are cleared before the next one
+    ZeroKeptCounters detCount_;
+    DevBuf<int> detStart_, detSeg_, detSorted_, detRow_, hessPerm_; // hessPerm_: the two lists' indices binned by stencil kind (k_bin_stencils)
     void detBegin(size_t nSlots, int valsPerSlot, bool withRow, bool fillKeys, size_t nKeys);
     void detBuckets(size_t nSlots, size_t nKeys, int div);
     void detReduce3(size_t nSlots, size_t nKeys, double* grad_dev);

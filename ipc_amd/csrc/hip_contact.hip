@@ -815,10 +815,6 @@ __global__ __launch_bounds__(BLOCK) void k_friction_hessian(FrictionView fv, Csr
 }
 
 // ---- broad phase: uniform grid by counting sort ---------------------------------------------------------------
-struct Grid {
-    double lo[3], h;
-    int dim[3];
-};
 __device__ __forceinline__ int cell_of(const Grid& g, double x, int c)
 {
     return min(g.dim[c] - 1, max(0, (int)floor((x - g.lo[c]) / g.h)));
@@ -833,13 +829,11 @@ __global__ void k_pair_flags(int nV, const int* __restrict__ dbc, const int* __r
     if (v < nV) flags[v] = (dbc[v] != 0 ? 1 : 0) | ((obst && obst[v]) ? 2 : 0) | (obstacleOnly ? 4 : 0);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_bbox_partial(int nV, const double* __restrict__ x, double* __restrict__ partial)
+// The box of a workgroup from the boxes (lo, hi) of its threads: wave shuffles, then the waves' boxes through LDS.  True in threads 0 .. 5, which receive
+// component threadIdx.x of (lo[3], hi[3]) in r.  All threads of the block call it.
+__device__ __forceinline__ bool block_box(double* lo, double* hi, double& r)
 {
     __shared__ double sm[6][BLOCK / 64];
-    const int v = blockIdx.x * BLOCK + threadIdx.x;
-    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
-    if (v < nV)
-        for (int c = 0; c < 3; ++c) lo[c] = hi[c] = x[3 * (size_t)v + c];
     for (int c = 0; c < 3; ++c) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -852,38 +846,32 @@ __global__ __launch_bounds__(BLOCK) void k_bbox_partial(int nV, const double* __
         }
     }
     __syncthreads();
-    if (threadIdx.x < 6) {
-        double r = sm[threadIdx.x][0];
-        for (int i = 1; i < BLOCK / 64; ++i) r = (threadIdx.x < 3) ? fmin(r, sm[threadIdx.x][i]) : fmax(r, sm[threadIdx.x][i]);
-        partial[6 * (size_t)blockIdx.x + threadIdx.x] = r;
-    }
+    if (threadIdx.x >= 6) return false;
+    r = sm[threadIdx.x][0];
+    for (int i = 1; i < BLOCK / 64; ++i) r = (threadIdx.x < 3) ? fmin(r, sm[threadIdx.x][i]) : fmax(r, sm[threadIdx.x][i]);
+    return true;
+}
+__global__ __launch_bounds__(BLOCK) void k_bbox_partial(int nV, const double* __restrict__ x, double* __restrict__ partial)
+{
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
+    if (v < nV)
+        for (int c = 0; c < 3; ++c) lo[c] = hi[c] = x[3 * (size_t)v + c];
+    double r;
+    if (block_box(lo, hi, r)) partial[6 * (size_t)blockIdx.x + threadIdx.x] = r;
 }
 // the box of the current positions; *stale = 1 when it leaves the grid `g` the host laid over the previous build's box (the kernels of the build then return at
 // once and the host repeats the build on a fresh grid: with everything clamped into the border cells one cell would hold the whole surface)
 __global__ __launch_bounds__(BLOCK) void k_bbox_final(int nb, const double* __restrict__ partial, double* __restrict__ box6, Grid g, int check, int* __restrict__ stale)
 {
-    __shared__ double sm[6][BLOCK / 64];
     double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
     for (int b = threadIdx.x; b < nb; b += BLOCK)
         for (int c = 0; c < 3; ++c) {
             lo[c] = fmin(lo[c], partial[6 * (size_t)b + c]);
             hi[c] = fmax(hi[c], partial[6 * (size_t)b + 3 + c]);
         }
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[c] = fmin(lo[c], __shfl_down(lo[c], off, 64));
-            hi[c] = fmax(hi[c], __shfl_down(hi[c], off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            sm[c][threadIdx.x >> 6] = lo[c];
-            sm[3 + c][threadIdx.x >> 6] = hi[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double r = sm[threadIdx.x][0];
-        for (int i = 1; i < BLOCK / 64; ++i) r = (threadIdx.x < 3) ? fmin(r, sm[threadIdx.x][i]) : fmax(r, sm[threadIdx.x][i]);
+    double r;
+    if (block_box(lo, hi, r)) {
         box6[threadIdx.x] = r;
         const int c = threadIdx.x % 3;
         if (check && (threadIdx.x < 3 ? r < g.lo[c] : r > g.lo[c] + g.h * g.dim[c])) atomicOr(stale, 1);
@@ -951,40 +939,6 @@ __device__ __forceinline__ VoxRec load_vox_rec(const int* __restrict__ recs, int
     const int4 r0 = reinterpret_cast<const int4*>(recs)[2 * (size_t)k], r1 = reinterpret_cast<const int4*>(recs)[2 * (size_t)k + 1];
     return VoxRec{ r0.x, { r0.y, r0.z, r0.w, r1.x, r1.y, r1.z } };
 }
-// mode 0: count, mode 1: fill (records, see above).  Primitive = triangle (isTri) or surface edge, bbox inflated by `infl`
-__global__ __launch_bounds__(BLOCK) void k_grid_insert(int nPrim, int isTri, const int* __restrict__ prim, const double* __restrict__ x, Grid g,
-    double infl, int mode, int* __restrict__ cellCount, const int* __restrict__ cellStart, int* __restrict__ cellItems)
-{
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nPrim) return;
-    const int nv = isTri ? 3 : 2;
-    double bl[3] = { 1e300, 1e300, 1e300 }, bh[3] = { -1e300, -1e300, -1e300 };
-    for (int k = 0; k < nv; ++k) {
-        const int v = prim[nv * (size_t)i + k];
-        for (int c = 0; c < 3; ++c) {
-            const double xv = x[3 * (size_t)v + c];
-            bl[c] = fmin(bl[c], xv - infl);
-            bh[c] = fmax(bh[c], xv + infl);
-        }
-    }
-    int a[3], b[3];
-    for (int c = 0; c < 3; ++c) {
-        a[c] = cell_of(g, bl[c], c);
-        b[c] = cell_of(g, bh[c], c);
-    }
-    for (int z = a[2]; z <= b[2]; ++z)
-        for (int y = a[1]; y <= b[1]; ++y)
-            for (int xx = a[0]; xx <= b[0]; ++xx) {
-                const int cell = xx + g.dim[0] * (y + g.dim[1] * z);
-                const int slot = atomicAdd(&cellCount[cell], 1);
-                if (mode == 1) {
-                    int4* r = reinterpret_cast<int4*>(cellItems) + 2 * (size_t)(cellStart[cell] + slot);
-                    r[0] = make_int4(i, __float_as_int(f_down(bl[0])), __float_as_int(f_down(bl[1])), __float_as_int(f_down(bl[2])));
-                    r[1] = make_int4(__float_as_int(f_up(bh[0])), __float_as_int(f_up(bh[1])), __float_as_int(f_up(bh[2])), 0);
-                }
-            }
-}
-
 // Triangles AND edges of the surface in one pass over one cell array of 2 nCells + 1 counters (round 6: the two grids of the narrow phase used to be built one
 // after the other -- fill, count, scan, read-back, fill, insert for each): thread i < nTri takes triangle i into cells [0, nCells), the others edge i - nTri
 // into [nCells, 2 nCells).  mode 0 counts; mode 1 fills and takes its slots by counting the cells' counters back DOWN to zero -- no second fill pass, and the
@@ -1580,7 +1534,6 @@ __global__ void k_ref_cap(int nb, const double* __restrict__ partial, double alp
 __global__ __launch_bounds__(BLOCK) void k_ref_bbox_swept_dev(int n, const int* __restrict__ SVI, const double* __restrict__ x, const double* __restrict__ p,
     const double* __restrict__ alphaPtr, double* __restrict__ partial)
 {
-    __shared__ double sm[6][BLOCK / 64];
     const double alpha = alphaPtr[0];
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
@@ -1588,29 +1541,13 @@ __global__ __launch_bounds__(BLOCK) void k_ref_bbox_swept_dev(int n, const int* 
         const size_t v = (size_t)SVI[i];
         for (int c = 0; c < 3; ++c) lo[c] = hi[c] = swept_pos(x[3 * v + c], alpha, p[3 * v + c]);
     }
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[c] = fmin(lo[c], __shfl_down(lo[c], off, 64));
-            hi[c] = fmax(hi[c], __shfl_down(hi[c], off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            sm[c][threadIdx.x >> 6] = lo[c];
-            sm[3 + c][threadIdx.x >> 6] = hi[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double r = sm[threadIdx.x][0];
-        for (int k = 1; k < BLOCK / 64; ++k) r = (threadIdx.x < 3) ? fmin(r, sm[threadIdx.x][k]) : fmax(r, sm[threadIdx.x][k]);
-        partial[6 * (size_t)blockIdx.x + threadIdx.x] = r;
-    }
+    double r;
+    if (block_box(lo, hi, r)) partial[6 * (size_t)blockIdx.x + threadIdx.x] = r;
 }
 // min / max over nA + nB partial boxes (6 doubles each: lo[3], hi[3]) -> out[1 .. 6]; out[0 .. 6] -> mapped host memory
 __global__ __launch_bounds__(BLOCK) void k_ref_box_final(int nA, const double* __restrict__ partA, int nB, const double* __restrict__ partB, double* __restrict__ out,
     double* __restrict__ mapped)
 {
-    __shared__ double sm[6][BLOCK / 64];
     double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
     for (int b = threadIdx.x; b < nA + nB; b += BLOCK) {
         const double* q = b < nA ? partA + 6 * (size_t)b : partB + 6 * (size_t)(b - nA);
@@ -1619,21 +1556,8 @@ __global__ __launch_bounds__(BLOCK) void k_ref_box_final(int nA, const double* _
             hi[c] = fmax(hi[c], q[3 + c]);
         }
     }
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[c] = fmin(lo[c], __shfl_down(lo[c], off, 64));
-            hi[c] = fmax(hi[c], __shfl_down(hi[c], off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            sm[c][threadIdx.x >> 6] = lo[c];
-            sm[3 + c][threadIdx.x >> 6] = hi[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double r = sm[threadIdx.x][0];
-        for (int k = 1; k < BLOCK / 64; ++k) r = (threadIdx.x < 3) ? fmin(r, sm[threadIdx.x][k]) : fmax(r, sm[threadIdx.x][k]);
+    double r;
+    if (block_box(lo, hi, r)) {
         out[1 + threadIdx.x] = r;
         mapped[1 + threadIdx.x] = r;
     }
@@ -2430,6 +2354,49 @@ void HipContact::readbackInit()
     static_assert(sizeof(BuildReadback) <= 16 * sizeof(unsigned long long), "read-back block too small");
 }
 
+void* HipContact::scanTmp(size_t bytes)
+{
+    if (scanTmp_.n < bytes) scanTmp_.alloc(bytes + bytes / 4);
+    return scanTmp_.p;
+}
+template <class T>
+void HipContact::exclusiveSum(const T* in, T* out, int count)
+{
+    size_t bytes = 0;
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, count, stream));
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp(bytes), bytes, in, out, count, stream));
+}
+
+// [lo, hi] padded by `pad` cells of size h on every side; h grows until the grid has at most 2^26 cells
+static Grid layGrid(const double* lo, const double* hi, double h, double pad, long long& nCells)
+{
+    Grid g;
+    g.h = h;
+    for (;;) {
+        nCells = 1;
+        for (int c = 0; c < 3; ++c) {
+            g.lo[c] = lo[c] - pad * g.h;
+            g.dim[c] = std::max(1, (int)std::floor((hi[c] + pad * g.h - g.lo[c]) / g.h) + 1);
+            nCells *= g.dim[c];
+        }
+        if (nCells <= (1LL << 26)) return g;
+        g.h *= 1.5;
+    }
+}
+Grid HipContact::gridOverBox(double h, long long& nCells) const { return layGrid(box_, box_ + 3, h, 2.0, nCells); }
+
+void HipContact::measureBox(int nV, const double* x_dev)
+{
+    const int nb = nblk(nV);
+    bboxPartial_.ensure(6 * (size_t)nb + 6);
+    double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
+    hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
+    hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, Grid{}, 0, (int*)nullptr);
+    HIP_CHECK(hipMemcpyAsync(box_, box_dev, sizeof(box_), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    haveBox_ = true;
+}
+
 #ifndef GRID_H_SCALE
 #define GRID_H_SCALE 1.0 // cell size of the narrow phase's grid in mean edge lengths
 #endif
@@ -2444,34 +2411,19 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     // sides of every pair): the box of this build is measured on the device and read back with the narrow phase's counts, the grid uses the box the PREVIOUS
     // build measured (padded by two cells).  Only the first build of a surface waits for its own box.  (Round 6: one synchronisation per build less; the second --
     // the total number of cell entries -- went the same way: the fill pass writes into the capacity the last build needed and the total comes back with the counts.)
+    if (!haveBox_) measureBox(nV, x_dev);
     const int nb = nblk(nV);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
     counters_.alloc(16);
     const int* stale = counters_.p + 2;
-    double boxNow[6];
-    if (!haveBox_) {
-        counters_.zero(stream);
-        hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
-        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, Grid{}, 0, counters_.p + 2);
-        HIP_CHECK(hipMemcpyAsync(boxNow, box_dev, sizeof(boxNow), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        for (int c = 0; c < 6; ++c) box_[c] = boxNow[c];
-        haveBox_ = true;
-    }
     int capPT = std::max<int>(1 << 14, (int)outPT_.n / 6), capEE = std::max<int>(1 << 14, (int)outEE_.n / 6);
     const int nPrim = nSF + nSFE;
     if (gridItems_.n < (size_t)REC * 16 * (size_t)nPrim) gridItems_.ensure((size_t)REC * 16 * (size_t)nPrim); // (a first guess: 16 cells per primitive)
-    // counters of the counting sorts (see "constraint-set assembly on the device"): cleared when allocated and after a build that did not run to its end;
-    // a build that does leaves them zero
+    // counters of the counting sorts (see "constraint-set assembly on the device")
     const int nB = nSVI + nSFE;
-    if (bucketCount_.n < (size_t)nB + 1 || dupCount_.n < (size_t)nV + 1 || countersDirty_) {
-        bucketCount_.ensure((size_t)nB + 1);
-        dupCount_.ensure((size_t)nV + 1);
-        bucketCount_.zero(stream);
-        dupCount_.zero(stream);
-    }
-    countersDirty_ = true;
+    int* bucketCount = bucketCount_.begin((size_t)nB + 1, stream);
+    int* dupCount = dupCount_.begin((size_t)nV + 1, stream);
     bucketStart_.ensure((size_t)nB + 1);
     dupStart_.ensure((size_t)nV + 1);
     runs_.ensure((size_t)nV + 1);
@@ -2479,35 +2431,16 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     readbackInit();
     BuildReadback* rb = reinterpret_cast<BuildReadback*>(readback_.p);
     BuildReadback* rbDev = reinterpret_cast<BuildReadback*>(readback_.dev);
-    auto scan = [&](auto* in, auto* out, int count) { // exclusive prefix sum, temporary storage grown on demand
-        size_t bytes = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, count, stream);
-        if (scanTmp_.n < bytes) scanTmp_.alloc(bytes + bytes / 4);
-        hipcub::DeviceScan::ExclusiveSum((void*)scanTmp_.p, bytes, in, out, count, stream);
-    };
     int nPT = 0, nEE = 0;
     Grid g;
     for (int attempt = 0;; ++attempt) {
         if (attempt > 8) throw StateError("constraint-set build: the grid does not settle");
-        g.h = std::max(GRID_H_SCALE * mesh.avgEdgeLen, 2.0 * infl);
         long long nCells;
-        for (;;) {
-            nCells = 1;
-            for (int c = 0; c < 3; ++c) {
-                g.lo[c] = box_[c] - 2.0 * g.h;
-                g.dim[c] = std::max(1, (int)std::floor((box_[3 + c] + 2.0 * g.h - g.lo[c]) / g.h) + 1);
-                nCells *= g.dim[c];
-            }
-            if (nCells <= (1LL << 26)) break;
-            g.h *= 1.5;
-        }
+        g = gridOverBox(std::max(GRID_H_SCALE * mesh.avgEdgeLen, 2.0 * infl), nCells);
         if (2 * nCells + 1 > (long long)INT_MAX) throw StateError("constraint-set build: grid too fine for 32-bit cell indices");
         // both grids in one pass: counters [0, nCells) of the triangles, [nCells, 2 nCells) of the edges, one scan (k_grid_insert_both)
         const size_t nC2 = 2 * (size_t)nCells + 1;
-        if (gridCount_.n < nC2) { // a fresh array is cleared once; every pass leaves it zero (the fill counts back down)
-            gridCount_.ensure(nC2);
-            gridCount_.zeroN(gridCount_.n, stream);
-        }
+        int* gridCount = gridCount_.begin(nC2, stream);
         gridStart_.ensure(nC2);
         const int* cellStartT = gridStart_.p;
         const int* cellStartE = gridStart_.p + nCells;
@@ -2518,16 +2451,17 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
         hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 0, capItems, stale,
-            gridCount_.p, (const int*)nullptr, (int*)nullptr);
-        scan(gridCount_.p, gridStart_.p, (int)nC2);
+            gridCount, (const int*)nullptr, (int*)nullptr);
+        exclusiveSum(gridCount, gridStart_.p, (int)nC2);
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 1, capItems, stale,
-            gridCount_.p, gridStart_.p, gridItems_.p);
+            gridCount, gridStart_.p, gridItems_.p);
+        gridCount_.done();
         hipLaunchKernelGGL(k_narrow_pt, dim3(nblk(COOP * nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, pf, g, cellStartT, gridItems_.p,
-            dHat, capPT, outPT_.p, counters_.p, capItems, stale, bucketCount_.p);
+            dHat, capPT, outPT_.p, counters_.p, capItems, stale, bucketCount);
         hipLaunchKernelGGL(k_narrow_ee_cells, dim3((int)std::min<long long>(nblk(64 * nCells), 4096)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, d_xRest.p, pf, g, (int)nCells, cellStartE,
-            gridItems_.p, dHat, infl, capEE, outEE_.p, counters_.p + 1, capItems, stale, bucketCount_.p + nSVI);
+            gridItems_.p, dHat, infl, capEE, outEE_.p, counters_.p + 1, capItems, stale, bucketCount + nSVI);
         // the buckets of the record sort: needed only when the build stands, enqueued before the host knows (one scan; the GPU would idle through the read-back)
-        scan(bucketCount_.p, bucketStart_.p, nB + 1);
+        exclusiveSum(bucketCount, bucketStart_.p, nB + 1);
         hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + (nC2 - 1), box_dev, rbDev);
         HIP_CHECK(hipStreamSynchronize(stream));
         const int total = rb->cnt[3];
@@ -2535,13 +2469,13 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
         if (rb->cnt[2]) continue; // the positions have left the old grid: nothing ran, once more on the fresh box
         if (total > capItems) { // the cell lists did not fit (the narrow phase walked truncated lists): grow and redo
             gridItems_.ensure((size_t)REC * ((size_t)total + (size_t)total / 4));
-            bucketCount_.zero(stream);
+            bucketCount_.reset(stream);
             continue;
         }
         if (rb->cnt[0] > capPT || rb->cnt[1] > capEE) { // overflow: grow and redo
             capPT = std::max(capPT, rb->cnt[0] + rb->cnt[0] / 4);
             capEE = std::max(capEE, rb->cnt[1] + rb->cnt[1] / 4);
-            bucketCount_.zero(stream);
+            bucketCount_.reset(stream);
             continue;
         }
         nPT = rb->cnt[0];
@@ -2555,7 +2489,8 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     d_csPTEE.ensure(2 * (size_t)std::max(n, 1));
     if (n == 0) {
         nActive_ = nPara_ = 0;
-        countersDirty_ = false;
+        bucketCount_.done(); // (no record, nothing counted)
+        dupCount_.done();
         return 0;
     }
     bucketSeg_.ensure(2 * (size_t)n);
@@ -2563,14 +2498,15 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     flags_.ensure((size_t)n + 1);
     flagPos_.ensure((size_t)n + 1);
     // by (svI, sfI) and (eI, eJ) -- the order a serial scan emits --, the point-triangle records first
-    hipLaunchKernelGGL(k_bucket_fill, dim3(nblk(n)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, outPT_.p, outEE_.p, bucketStart_.p, bucketCount_.p,
+    hipLaunchKernelGGL(k_bucket_fill, dim3(nblk(n)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, outPT_.p, outEE_.p, bucketStart_.p, bucketCount,
         reinterpret_cast<int2*>(bucketSeg_.p));
+    bucketCount_.done();
     hipLaunchKernelGGL(k_bucket_rank_classify, dim3(nblk(n + 1)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, nV, bucketStart_.p,
-        reinterpret_cast<const int2*>(bucketSeg_.p), outPT_.p, outEE_.p, permPT_.p, d_csPTEE.p, flags_.p, dupCount_.p);
+        reinterpret_cast<const int2*>(bucketSeg_.p), outPT_.p, outEE_.p, permPT_.p, d_csPTEE.p, flags_.p, dupCount);
     const int* permPT = permPT_.p;
     const int* permEE = permPT_.p + nPT;
-    scan(flags_.p, flagPos_.p, n + 1);
-    scan(dupCount_.p, dupStart_.p, nV + 1);
+    exclusiveSum(flags_.p, flagPos_.p, n + 1);
+    exclusiveSum(dupCount, dupStart_.p, nV + 1);
     // Everything below runs without the host knowing the category totals (round 6: two synchronisations per build less): the sets are sized for the
     // worst case -- every candidate in one category --, the kernels read the totals where they need them (flagPos_[n]), and the counts come back at the end.
     const unsigned long long* totalsDev = flagPos_.p + n;
@@ -2580,12 +2516,13 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     dupTuple_.ensure(4 * (size_t)n);
     dupSorted_.ensure(4 * (size_t)n);
     hipLaunchKernelGGL(k_scatter_sets, dim3(nblk(n)), dim3(BLOCK), 0, stream, nPT, nEE, nSFE, outPT_.p, permPT, outEE_.p, permEE, flagPos_.p,
-        d_active.p, dupTuple_.p, dupStart_.p, dupCount_.p, d_para.p, d_paraEIEJ.p, nV);
+        d_active.p, dupTuple_.p, dupStart_.p, dupCount, d_para.p, d_paraEIEJ.p, nV);
+    dupCount_.done();
     // lexicographic order of (id0, id1, id2) = the map's: buckets by id0, each ordered by (id1, id2); one tuple per run, its multiplicity in the last slot
     hipLaunchKernelGGL(k_dup_rank, dim3(nblk(n)), dim3(BLOCK), 0, stream, totalsDev, nV, dupStart_.p, reinterpret_cast<const int4*>(dupTuple_.p),
         reinterpret_cast<int4*>(dupSorted_.p));
     hipLaunchKernelGGL(k_dup_runs, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runs_.p);
-    scan(runs_.p, runPos_.p, nV + 1);
+    exclusiveSum(runs_.p, runPos_.p, nV + 1);
     hipLaunchKernelGGL(k_dup_emit, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, totalsDev, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runPos_.p,
         reinterpret_cast<int4*>(d_active.p), rbDev);
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -2593,7 +2530,6 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     const int nDirect = (int)(totals & 0xffffffffull), nDup = (int)(totals >> 32), nPar = n - nDirect - nDup;
     const int nUnique = rb->nUnique;
     (void)nDup;
-    countersDirty_ = false;
     nActive_ = nDirect + nUnique;
     nPara_ = nPar;
     return nActive_;
@@ -2684,7 +2620,7 @@ void HipContact::gradientAdd(const double* x_dev, const int* dbc_dev, int nV, do
     if (n) {
         ContactView cv{ nA, nP, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, x_dev, d_xRest.p, need_dev };
         detBegin(8 * (size_t)n, 3, false, /*fillKeys=*/false, (size_t)nV); // the kernel writes every key
-        hipLaunchKernelGGL(k_contact_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, cv, dHat, kappa, GradSink{ detVals_.p, detKey_.p, detCount_.p });
+        hipLaunchKernelGGL(k_contact_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, cv, dHat, kappa, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
         detReduce3(8 * (size_t)n, (size_t)nV, grad_dev);
     }
     hipLaunchKernelGGL(k_zero_projected, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dbc_dev, projectDBC, grad_dev);
@@ -2707,7 +2643,7 @@ void HipContact::hessianAdd(const double* x_dev, const int* dbc_dev, const HipLi
     detBegin(nSlots, 9, true, /*fillKeys=*/false, nKeys); // the kernel writes every key
     const HessBins bins{ counters_.p + 4, hessPerm_.p, n };
     hipLaunchKernelGGL(k_contact_hessian, dim3(nblk(n, HESS_W) + NBINS), dim3(HESS_W), 0, stream, cv, bins, m, dbc_dev, projectDBC, dHat, kappa,
-        BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.p }, counters_.p);
+        BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.buf.p }, counters_.p);
     detReduceBlocks(nSlots, nKeys, lin.d_ia.p, a_dev);
     if (deferCheck) { // the flag goes to mapped host memory behind the pass; the caller looks at it after its next synchronisation (takeHessianError)
         readbackInit();
@@ -2795,23 +2731,16 @@ void HipContact::detBegin(size_t nSlots, int valsPerSlot, bool withRow, bool fil
     detSeg_.ensure(nSlots);
     detSorted_.ensure(nSlots);
     if (withRow) detRow_.ensure(nSlots);
-    if (detCount_.n < nKeys + 1 || detDirty_) { // the counters return to zero with every pass that runs to its end (k_det_fill)
-        detCount_.ensure(nKeys + 1);
-        detCount_.zero(stream);
-    }
+    detCount_.begin(nKeys + 1, stream); // (counted back down by k_det_fill)
     detStart_.ensure(nKeys + 1);
-    detDirty_ = true;
     if (fillKeys) HIP_CHECK(hipMemsetAsync(detKey_.p, 0xFF, nSlots * sizeof(unsigned), stream)); // KEY_NONE: slots the kernel does not write
 }
 void HipContact::detBuckets(size_t nSlots, size_t nKeys, int div)
 {
-    size_t bytes = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, detCount_.p, detStart_.p, (int)nKeys + 1, stream);
-    if (scanTmp_.n < bytes) scanTmp_.alloc(bytes + bytes / 4);
-    hipcub::DeviceScan::ExclusiveSum((void*)scanTmp_.p, bytes, detCount_.p, detStart_.p, (int)nKeys + 1, stream);
-    hipLaunchKernelGGL(k_det_fill, dim3(nblk((int)nSlots)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, div, detStart_.p, detCount_.p, detSeg_.p);
+    exclusiveSum(detCount_.buf.p, detStart_.p, (int)nKeys + 1);
+    hipLaunchKernelGGL(k_det_fill, dim3(nblk((int)nSlots)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, div, detStart_.p, detCount_.buf.p, detSeg_.p);
+    detCount_.done();
     hipLaunchKernelGGL(k_det_rank, dim3(nblk((int)nSlots)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, div, detStart_.p, (int)nKeys, detSeg_.p, detSorted_.p);
-    detDirty_ = false;
 }
 void HipContact::detReduce3(size_t nSlots, size_t nKeys, double* grad_dev)
 {
@@ -2831,7 +2760,7 @@ void HipContact::frictionGradientAdd(const double* x_dev, const double* xt_dev, 
     if (!n) return;
     FrictionView fv{ n, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
     detBegin(8 * (size_t)n, 3, false, true, d_xRest.n / 3); // (d_xRest: three rest coordinates per node)
-    hipLaunchKernelGGL(k_friction_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, fv, x_dev, xt_dev, eps2, coef, GradSink{ detVals_.p, detKey_.p, detCount_.p });
+    hipLaunchKernelGGL(k_friction_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, fv, x_dev, xt_dev, eps2, coef, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
     detReduce3(8 * (size_t)n, d_xRest.n / 3, grad_dev);
 }
 
@@ -2847,7 +2776,7 @@ void HipContact::frictionHessianAdd(const double* x_dev, const double* xt_dev, c
     const size_t nKeys = lin.ja.size() / 3 + 1;
     detBegin(16 * (size_t)n, 9, true, true, nKeys);
     hipLaunchKernelGGL(k_friction_hessian, dim3(nblk(n)), dim3(BLOCK), 0, stream, fv, m, x_dev, xt_dev, dbc_dev, projectDBC, eps2, coef,
-        BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.p }, counters_.p);
+        BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.buf.p }, counters_.p);
     detReduceBlocks(16 * (size_t)n, nKeys, lin.d_ia.p, a_dev);
     int err[2];
     counters_.download(err, 2, stream);
@@ -2912,20 +2841,16 @@ void HipContact::candidateConnectivitySorted(std::vector<std::pair<int, int>>& p
     sortKeyIn_.ensure(m + 1);
     sortKeyOut_.ensure(m + 1);
     hipLaunchKernelGGL(k_cand_pair_keys, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, sortKeyIn_.p);
-    auto tmp = [&](size_t bytes) {
-        if (scanTmp_.n < bytes) scanTmp_.alloc(bytes + bytes / 4);
-        return (void*)scanTmp_.p;
-    };
     {
         size_t bytes = 0;
         hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, sortKeyIn_.p, sortKeyOut_.p, (int)m, 0, 64, stream);
-        hipcub::DeviceRadixSort::SortKeys(tmp(bytes), bytes, sortKeyIn_.p, sortKeyOut_.p, (int)m, 0, 64, stream);
+        hipcub::DeviceRadixSort::SortKeys(scanTmp(bytes), bytes, sortKeyIn_.p, sortKeyOut_.p, (int)m, 0, 64, stream);
     }
     unsigned long long* d_cnt = sortKeyOut_.p + m; // one spare slot behind the keys
     {
         size_t bytes = 0;
         hipcub::DeviceSelect::Unique(nullptr, bytes, sortKeyOut_.p, sortKeyIn_.p, reinterpret_cast<int*>(d_cnt), (int)m, stream);
-        hipcub::DeviceSelect::Unique(tmp(bytes), bytes, sortKeyOut_.p, sortKeyIn_.p, reinterpret_cast<int*>(d_cnt), (int)m, stream);
+        hipcub::DeviceSelect::Unique(scanTmp(bytes), bytes, sortKeyOut_.p, sortKeyIn_.p, reinterpret_cast<int*>(d_cnt), (int)m, stream);
     }
     int cnt = 0;
     HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -3040,7 +2965,8 @@ double HipContact::maxSurfaceSpeed(const double* p_dev)
     return v;
 }
 
-HipContact::GridHost HipContact::makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell)
+// the grid of the swept-box sweep (ccdFull): the box of the positions grown by what the step can reach, cells at least that large
+Grid HipContact::makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells)
 {
     const int nV = mesh.nV;
     const int nb = nblk(nV);
@@ -3048,76 +2974,46 @@ HipContact::GridHost HipContact::makeGrid(const HipMesh& mesh, const double* x_d
     hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
     std::vector<double> part(6 * (size_t)nb);
     bboxPartial_.download(part.data(), part.size(), stream);
-    GridHost g;
-    double hi[3];
-    for (int c = 0; c < 3; ++c) {
-        g.lo[c] = 1e300;
-        hi[c] = -1e300;
-    }
+    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
     for (int b = 0; b < nb; ++b)
         for (int c = 0; c < 3; ++c) {
-            g.lo[c] = std::min(g.lo[c], part[6 * (size_t)b + c]);
+            lo[c] = std::min(lo[c], part[6 * (size_t)b + c]);
             hi[c] = std::max(hi[c], part[6 * (size_t)b + 3 + c]);
         }
-    double reach = 0.0;
-    if (p_dev) { // swept boxes reach at most alpha * max |p| beyond the current bounding box
-        ccdOut_.alloc(4);
-        ccdOut_.zero(stream);
-        hipLaunchKernelGGL(k_max_speed, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, (const int*)nullptr, p_dev, ccdOut_.p);
-        unsigned long long bits = 0;
-        HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        double pm;
-        std::memcpy(&pm, &bits, sizeof(pm));
-        reach = alpha * pm;
-    }
+    // swept boxes reach at most alpha * max |p| beyond the current bounding box
+    ccdOut_.alloc(4);
+    ccdOut_.zero(stream);
+    hipLaunchKernelGGL(k_max_speed, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, (const int*)nullptr, p_dev, ccdOut_.p);
+    unsigned long long bits = 0;
+    HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    double pm;
+    std::memcpy(&pm, &bits, sizeof(pm));
+    const double reach = alpha * pm;
     for (int c = 0; c < 3; ++c) {
-        g.lo[c] -= reach;
+        lo[c] -= reach;
         hi[c] += reach;
     }
-    g.h = std::max(minCell, reach);
-    for (;;) {
-        g.nCells = 1;
-        for (int c = 0; c < 3; ++c) {
-            g.dim[c] = std::max(1, (int)std::floor((hi[c] - g.lo[c]) / g.h) + 1);
-            g.nCells *= g.dim[c];
-        }
-        if (g.nCells <= (1LL << 26)) break;
-        g.h *= 1.5;
-    }
-    return g;
+    return layGrid(lo, hi, std::max(minCell, reach), 0.0, nCells);
 }
 
-void HipContact::buildCells(const GridHost& gh, int nPrim, int nv, const int* prim, const double* x_dev, const double* p_dev, double alpha, double infl,
+// cell lists of primitive indices over swept boxes: count, scan, wait for the total, fill
+void HipContact::buildCells(const Grid& g, long long nCells, int nPrim, int nv, const int* prim, const double* x_dev, const double* p_dev, double alpha,
     DevBuf<int>& cnt, DevBuf<int>& start, DevBuf<int>& items)
 {
-    Grid g;
-    for (int c = 0; c < 3; ++c) {
-        g.lo[c] = gh.lo[c];
-        g.dim[c] = gh.dim[c];
-    }
-    g.h = gh.h;
-    const long long nCells = gh.nCells;
     cnt.ensure((size_t)nCells + 1);
     start.ensure((size_t)nCells + 1);
     auto insert = [&](int mode) {
         cnt.zeroN((size_t)nCells + 1, stream);
-        if (p_dev)
-            hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nPrim, nv, prim, x_dev, p_dev, alpha, g, mode, cnt.p,
-                start.p, items.p);
-        else
-            hipLaunchKernelGGL(k_grid_insert, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nPrim, nv == 3 ? 1 : 0, prim, x_dev, g, infl, mode, cnt.p, start.p,
-                items.p);
+        hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nPrim, nv, prim, x_dev, p_dev, alpha, g, mode, cnt.p, start.p,
+            items.p);
     };
     insert(0);
-    size_t tmpBytes = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, cnt.p, start.p, (int)nCells + 1, stream));
-    if (scanTmp_.n < tmpBytes) scanTmp_.alloc(tmpBytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp_.p, tmpBytes, cnt.p, start.p, (int)nCells + 1, stream));
+    exclusiveSum(cnt.p, start.p, (int)nCells + 1);
     int total = 0;
     HIP_CHECK(hipMemcpyAsync(&total, start.p + nCells, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    items.ensure((size_t)(p_dev ? 1 : REC) * std::max(1, total)); // k_grid_insert writes records, k_grid_insert_swept indices
+    items.ensure((size_t)std::max(1, total));
     insert(1);
 }
 
@@ -3187,15 +3083,10 @@ double HipContact::ccdFull(const HipMesh& mesh, const double* x_dev, const doubl
 {
     if (!surfaceSet) throw StateError("ccd before set_surface");
     const int* pf = pairFlags(mesh.nV, dbc_dev);
-    const GridHost gh = makeGrid(mesh, x_dev, p_dev, stepSize, mesh.avgEdgeLen);
-    buildCells(gh, nSF, 3, d_SF.p, x_dev, p_dev, stepSize, 0.0, cellCountT_, cellStartT_, cellItemsT_);
-    buildCells(gh, nSFE, 2, d_SFE.p, x_dev, p_dev, stepSize, 0.0, cellCountE_, cellStartE_, cellItemsE_);
-    Grid g;
-    for (int c = 0; c < 3; ++c) {
-        g.lo[c] = gh.lo[c];
-        g.dim[c] = gh.dim[c];
-    }
-    g.h = gh.h;
+    long long nCells;
+    const Grid g = makeGrid(mesh, x_dev, p_dev, stepSize, mesh.avgEdgeLen, nCells);
+    buildCells(g, nCells, nSF, 3, d_SF.p, x_dev, p_dev, stepSize, cellCountT_, cellStartT_, cellItemsT_);
+    buildCells(g, nCells, nSFE, 2, d_SFE.p, x_dev, p_dev, stepSize, cellCountE_, cellStartE_, cellItemsE_);
     ccdOut_.alloc(4);
     const unsigned long long init[2] = { ~0ull, ~0ull };
     HIP_CHECK(hipMemcpyAsync(ccdOut_.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
@@ -3282,24 +3173,15 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     // which the kernels took 0.9): the last entry of each third stays zero, the scan makes the offsets of the later thirds absolute, the fill counts the
     // counters back down (k_ref_insert), and the host waits once, for the total.
     const size_t nC1 = (size_t)nCells + 1;
-    if (refCount_.n < 3 * nC1 || refDirty_) { // (dirty: a sweep that was left between its count and its fill)
-        refCount_.ensure(3 * nC1);
-        refCount_.zero(stream);
-    }
-    refDirty_ = true;
+    int* refCount = refCount_.begin(3 * nC1, stream);
     refStart_.ensure(3 * nC1);
     const int nPrims[3] = { nSVI, nSFE, nSF }, nvs[3] = { 1, 2, 3 };
     const int* prims[3] = { d_SVI.p, d_SFE.p, d_SF.p };
     for (int q = 0; q < 3; ++q)
         if (nPrims[q])
             hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q])), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 0,
-                refCount_.p + q * nC1, (const int*)nullptr, (int*)nullptr);
-    {
-        size_t tmpBytes = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, refCount_.p, refStart_.p, (int)(3 * nC1), stream));
-        if (scanTmp_.n < tmpBytes) scanTmp_.alloc(tmpBytes + tmpBytes / 4);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp_.p, tmpBytes, refCount_.p, refStart_.p, (int)(3 * nC1), stream));
-    }
+                refCount + q * nC1, (const int*)nullptr, (int*)nullptr);
+    exclusiveSum(refCount, refStart_.p, (int)(3 * nC1));
     readbackInit();
     hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(1), 0, stream, (const int*)(refStart_.p + 3 * nC1 - 1), reinterpret_cast<int*>(readback_.dev));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -3308,8 +3190,8 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     for (int q = 0; q < 3; ++q)
         if (nPrims[q])
             hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q])), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 1,
-                refCount_.p + q * nC1, (const int*)(refStart_.p + q * nC1), refItems_.p);
-    refDirty_ = false;
+                refCount + q * nC1, (const int*)(refStart_.p + q * nC1), refItems_.p);
+    refCount_.done();
     ccdOut_.alloc(4);
     counters_.alloc(16);
     // counters_: [0] queried pairs, [1] pairs that returned a time inside the step (the hit list)
@@ -3373,49 +3255,44 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
             hipLaunchKernelGGL(k_points_in_tets<false>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
                 counters_.p);
     };
+    counters_.alloc(16);
+    if (nSF == 0 || nSFE == 0) {
+        // A surface without triangles (point clouds, segment-only shapes): no edge can pierce a triangle of it, and no grid is built.  What such a surface can
+        // still do is put a codimensional point inside a tetrahedron.
+        counters_.zero(stream);
+        pointsInTets();
+        int f = 0;
+        counters_.download(&f, 1, stream);
+        return f != 0;
+    }
     // Round 6: the check runs once or twice per Newton iteration of a contact scene and used to wait for the host three times (bounding box, number of cell
     // entries, result).  Like the constraint-set build it now lays its grid over the box the LAST build or check measured (a stale grid is detected on the
     // device and nothing runs), fills the edge cells into the capacity the last pass needed, and reads flag + stale flag + total + the fresh box back at once.
-    for (int attempt = 0; haveBox_ && nSF > 0 && nSFE > 0 && attempt < 3; ++attempt) {
-        const int nV = mesh.nV, nb = nblk(nV);
-        bboxPartial_.ensure(6 * (size_t)nb + 6);
-        double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
-        counters_.alloc(16);
-        Grid g;
-        g.h = mesh.avgEdgeLen;
+    // Only the first build or check of a surface waits for its own box.
+    const int nV = mesh.nV, nb = nblk(nV);
+    if (!haveBox_) measureBox(nV, x_dev);
+    bboxPartial_.ensure(6 * (size_t)nb + 6);
+    double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
+    const int* stale = counters_.p + 2;
+    readbackInit();
+    const BuildReadback* rb = reinterpret_cast<const BuildReadback*>(readback_.p);
+    for (int attempt = 0; attempt < 3; ++attempt) {
         long long nCells;
-        for (;;) {
-            nCells = 1;
-            for (int c = 0; c < 3; ++c) {
-                g.lo[c] = box_[c] - 2.0 * g.h;
-                g.dim[c] = std::max(1, (int)std::floor((box_[3 + c] + 2.0 * g.h - g.lo[c]) / g.h) + 1);
-                nCells *= g.dim[c];
-            }
-            if (nCells <= (1LL << 26)) break;
-            g.h *= 1.5;
-        }
-        if (gridCount_.n < (size_t)nCells + 1) { // (cleared once: every pass counts its cells up and back down)
-            gridCount_.ensure((size_t)nCells + 1);
-            gridCount_.zeroN(gridCount_.n, stream);
-        }
+        const Grid g = gridOverBox(mesh.avgEdgeLen, nCells);
+        int* gridCount = gridCount_.begin((size_t)nCells + 1, stream);
         gridStart_.ensure((size_t)nCells + 1);
         if (gridItems_.n < (size_t)REC * 8 * (size_t)nSFE) gridItems_.ensure((size_t)REC * 8 * (size_t)nSFE);
         const int capItems = (int)std::min<size_t>(gridItems_.n / REC, (size_t)INT_MAX);
-        const int* stale = counters_.p + 2;
-        readbackInit();
-        BuildReadback* rb = reinterpret_cast<BuildReadback*>(readback_.p);
         counters_.zero(stream);
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
         hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
         // (edges only, in cells [0, nCells): the kernel's offset of the edge cells is its nCells argument)
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 0, capItems, stale,
-            gridCount_.p, (const int*)nullptr, (int*)nullptr);
-        size_t tmpBytes = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, gridCount_.p, gridStart_.p, (int)nCells + 1, stream);
-        if (scanTmp_.n < tmpBytes) scanTmp_.alloc(tmpBytes + tmpBytes / 4);
-        hipcub::DeviceScan::ExclusiveSum((void*)scanTmp_.p, tmpBytes, gridCount_.p, gridStart_.p, (int)nCells + 1, stream);
+            gridCount, (const int*)nullptr, (int*)nullptr);
+        exclusiveSum(gridCount, gridStart_.p, (int)nCells + 1);
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 1, capItems, stale,
-            gridCount_.p, gridStart_.p, gridItems_.p);
+            gridCount, gridStart_.p, gridItems_.p);
+        gridCount_.done();
         if (exactPredicates)
             hipLaunchKernelGGL(k_intersect<true>, dim3(nblk(COOP * (long long)nSF)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
                 gridItems_.p, counters_.p, capItems);
@@ -3433,27 +3310,10 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
         }
         return rb->cnt[0] != 0;
     }
-    // the general path (first call on a surface, or a box that keeps moving): own bounding box, own cell arrays, three synchronisations
-    const GridHost gh = makeGrid(mesh, x_dev, nullptr, 0.0, mesh.avgEdgeLen);
-    buildCells(gh, nSFE, 2, d_SFE.p, x_dev, nullptr, 0.0, 0.0, cellCountE_, cellStartE_, cellItemsE_);
-    Grid g;
-    for (int c = 0; c < 3; ++c) {
-        g.lo[c] = gh.lo[c];
-        g.dim[c] = gh.dim[c];
-    }
-    g.h = gh.h;
-    counters_.alloc(16);
-    counters_.zero(stream);
-    if (exactPredicates)
-        hipLaunchKernelGGL(k_intersect<true>, dim3(nblk(COOP * (long long)nSF)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, cellStartE_.p,
-            cellItemsE_.p, counters_.p, INT_MAX);
-    else
-        hipLaunchKernelGGL(k_intersect<false>, dim3(nblk(COOP * (long long)nSF)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, cellStartE_.p,
-            cellItemsE_.p, counters_.p, INT_MAX);
-    pointsInTets();
-    int f[2];
-    counters_.download(f, 2, stream);
-    return f[0] != 0;
+    // Not reached: the positions do not change between the attempts, and every attempt leaves their box in box_.  From the second attempt on the grid is
+    // therefore laid over the box of these very positions: it is not stale and no longer changes, so if the second attempt's cell lists overflow, the
+    // third builds the same lists into a capacity grown past their total.
+    throw StateError("intersection check: the grid does not settle");
 }
 
 // stencils of the current active set closer than dTol, in set order, with their squared distances: evaluated and

@@ -63,6 +63,7 @@ protected:
     mutable std::vector<double> delta_, setVal_;
     mutable std::vector<unsigned char> isSet_;
     mutable bool dirty_ = false, anySet_ = false;
+    bool iterative_ = false;
 
     static void chk(int rc)
     {
@@ -92,7 +93,19 @@ public:
     HipLinSysSolver& operator=(const HipLinSysSolver&) = delete;
 
     ipcgpu_ctx* context() const { return ctx; }
-    LinSysSolverType type() const override { return IPCGPU_LINSYSSOLVER_TYPE; }
+    // the iterative choice (`linearSolver AMGCL`, Config.cpp:696-699; LinSysSolver.cpp:19-22 would create an AMGCLSolver): preconditioned CG in
+    // the library, see ipcgpu_linsys_set_iterative for what analyze_pattern / factorize / solve then mean
+    LinSysSolverType type() const override { return iterative_ ? LinSysSolverType::AMGCL : IPCGPU_LINSYSSOLVER_TYPE; }
+    void setIterative(bool on)
+    {
+        chk(ipcgpu_ctx_set_solver(ctx, on ? IPCGPU_SOLVER_PCG : IPCGPU_SOLVER_MULTIFRONTAL));
+        iterative_ = on;
+    }
+    // solver.tol / solver.maxiter (AMGCLSolver.cpp:24-25), the preconditioner (IPCGPU_PRECOND_*) and how many factorize() calls a lagged factor serves
+    void setIterativeParameters(double relTol, int maxIter, int precond, int maxFactorAge)
+    {
+        chk(ipcgpu_linsys_set_iterative(ctx, relTol, maxIter, precond, maxFactorAge));
+    }
 
     // host-side addCoeff / setCoeff since the last flush -> HBM (one pass over the values)
     void flush() const
@@ -135,7 +148,11 @@ public:
     void solve(Eigen::VectorXd& rhs, Eigen::VectorXd& result) override
     {
         result.conservativeResize(rhs.size());
-        chk(ipcgpu_linsys_solve(ctx, rhs.data(), result.data()));
+        const int rc = ipcgpu_linsys_solve(ctx, rhs.data(), result.data());
+        chk(rc);
+        // the iterative solver found a direction of non-positive curvature: solve() has no way to say so (LinSysSolver.hpp:229), so it hands out
+        // what the caller would compute after a failed factorize (Optimizer.cpp:2331-2348)
+        if (rc == IPCGPU_NOT_PD) chk(ipcgpu_linsys_precondition_diag(ctx, rhs.data(), result.data()));
     }
     void multiply(const Eigen::VectorXd& x, Eigen::VectorXd& Ax) override
     {

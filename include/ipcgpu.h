@@ -43,7 +43,9 @@ enum { IPCGPU_NOT_DBC = 0, IPCGPU_DBC_ZERO = 1, IPCGPU_DBC_NONZERO = 2 };
 
 /* linear-solver back ends selectable per context (the reference selects CHOLMOD / EIGEN /
  * AMGCL through LinSysSolver::create, LinSysSolver.cpp:10-28) */
-enum { IPCGPU_SOLVER_MULTIFRONTAL = 0, IPCGPU_SOLVER_ROCSOLVER_CSRRF = 1 };
+enum { IPCGPU_SOLVER_MULTIFRONTAL = 0, IPCGPU_SOLVER_ROCSOLVER_CSRRF = 1, IPCGPU_SOLVER_PCG = 2 };
+/* preconditioners of IPCGPU_SOLVER_PCG (ipcgpu_linsys_set_iterative) */
+enum { IPCGPU_PRECOND_BLOCK_JACOBI = 0, IPCGPU_PRECOND_LAGGED_CHOLESKY = 1 };
 
 const char* ipcgpu_last_error(void);
 int ipcgpu_version(void);
@@ -146,6 +148,30 @@ int ipcgpu_linsys_analyze_pattern(ipcgpu_ctx*); /* analyze_pattern, CHOLMODSolve
 int ipcgpu_linsys_factorize(ipcgpu_ctx*); /* factorize, :130-137; returns IPCGPU_NOT_PD */
 int ipcgpu_linsys_solve(ipcgpu_ctx*, const double* rhs, double* result); /* solve, :139-154 */
 int ipcgpu_linsys_precondition_diag(ipcgpu_ctx*, const double* in, double* out); /* :411-420 */
+/* IPCGPU_SOLVER_PCG: preconditioned conjugate gradients from x = 0, the reference's iterative choice (`linearSolver AMGCL`: CG to a relative
+ * residual, AMGCLSolver.cpp:24-25, 44, 201, 225-232; its algebraic multigrid hierarchy is not rebuilt).  Defaults when set_iterative is never
+ * called: rel_tol 1e-5, max_iter 1000 (solver.tol / solver.maxiter, :24-25), block Jacobi, max_factor_age 1 (the best of 1, 2, 4, 8, 16
+ * in a Newton run of the headline workload, profiles/pcg_bench.json).  The LinSysSolver calls then mean:
+ *   analyze_pattern  BLOCK_JACOBI: no symbolic analysis at all, only the index of the lower triangle the product needs (AMGCLSolver.hpp: the
+ *                    base class's no-op).  LAGGED_CHOLESKY: the multifrontal solver's analysis and set-up, as for IPCGPU_SOLVER_MULTIFRONTAL.
+ *   factorize        (AMGCLSolver.cpp:173-191 rebuilds the preconditioner and returns true.)  BLOCK_JACOBI: inverts the 3x3 diagonal node
+ *                    blocks (entries the pattern does not hold count as zero); IPCGPU_NOT_PD when one is not positive definite.
+ *                    LAGGED_CHOLESKY: factorises when there is no factor for the current analysis, when the kept factor would be serving its
+ *                    max_factor_age-th factorize() call (1 = always), or when the previous solve did not converge; otherwise keeps the
+ *                    factor and counts its age.  IPCGPU_NOT_PD as for the multifrontal solver.
+ *   solve            (AMGCLSolver.cpp:193-243.)  IPCGPU_NOT_PD when a search direction has p.Ap <= 0: the caller takes the diagonal fallback as
+ *                    after a failed factorize (Optimizer.cpp:2331-2348).  Not converged after max_iter with a factor of age > 0: the current
+ *                    values are factorised once and the solve runs again.  Still not converged: IPCGPU_OK with converged = 0 in the
+ *                    statistics, as the reference goes on with what AMGCL returned (:230-241).
+ * Together with ipcgpu_linsys_set_shard(world > 1): IPCGPU_ERR_UNSUPPORTED.
+ * ipcgpu_linsys_iter_stats, of the last solve: out6 = { iterations, |b - A x|_2 / |b|_2 at exit recomputed with one extra product, converged 0/1,
+ * numeric factorisations this context's iterative solver has done so far, age of the factor the solve used (in factorize() calls), host
+ * synchronisations the solve made }.
+ * ipcgpu_linsys_multiply_sym: the solver's product (LinSysSolver.hpp:238-253) -- the lower triangle read from the upper storage through a
+ * per-pattern index, no atomics, the same bits on every run; available with every solver type. */
+int ipcgpu_linsys_set_iterative(ipcgpu_ctx*, double rel_tol, int max_iter, int precond, int max_factor_age);
+int ipcgpu_linsys_iter_stats(ipcgpu_ctx*, double* out6);
+int ipcgpu_linsys_multiply_sym(ipcgpu_ctx*, const double* x, double* Ax);
 /* Multi-GPU direct solver (one process per GPU): the assembly tree is cut below its top separators; rank r factorises and solves
    the subtrees it owns; a front above the cut is executed by ONE rank (the one that holds its most expensive child), and the update
    matrices / vectors of children on other ranks and the solution entries of ancestors travel point to point through the exchange hook
@@ -482,6 +508,9 @@ int ipcgpu_bench_assembly(ipcgpu_ctx*, double dtSq, int reps, double* avg_ms, do
 int ipcgpu_bench_factor_solve(ipcgpu_ctx*, int reps, double* factor_ms, double* solve_ms);
 /* device streaming copy bandwidth (GB/s) measured here, the "STREAM" figure quoted beside the
  * nominal 8 TB/s */
+/* average time of one launch of the iterative solver's product (ipcgpu_linsys_multiply_sym) on device-resident vectors and its algorithmic bytes:
+ * 8 nnz values + 4 nnz columns + the two vectors, each once */
+int ipcgpu_bench_multiply_sym(ipcgpu_ctx*, int reps, double* avg_ms, double* algorithmic_bytes);
 int ipcgpu_bench_stream(ipcgpu_ctx*, long long bytes, int reps, double* gbps);
 
 #ifdef __cplusplus

@@ -157,7 +157,12 @@ int ipcgpu_ctx_set_solver(ipcgpu_ctx* c, int type)
 {
     specChanged(c);
     return guarded([&] {
-        needArg(c && (type == IPCGPU_SOLVER_MULTIFRONTAL || type == IPCGPU_SOLVER_ROCSOLVER_CSRRF), "unknown solver type"); // LinSysSolver.cpp:24-26
+        needArg(c && (type == IPCGPU_SOLVER_MULTIFRONTAL || type == IPCGPU_SOLVER_ROCSOLVER_CSRRF || type == IPCGPU_SOLVER_PCG), "unknown solver type"); // LinSysSolver.cpp:24-26
+        if (type == IPCGPU_SOLVER_PCG && c->lin->solverWorld() > 1) {
+            g_err = "the iterative solver is not sharded";
+            return IPCGPU_ERR_UNSUPPORTED;
+        }
+        if (type != c->lin->solverType) c->lin->invalidateAnalysis();
         c->lin->solverType = type;
         return IPCGPU_OK;
     });
@@ -581,6 +586,37 @@ int ipcgpu_linsys_multiply(ipcgpu_ctx* c, const double* x, double* y)
         return IPCGPU_OK;
     });
 }
+int ipcgpu_linsys_multiply_sym(ipcgpu_ctx* c, const double* x, double* y)
+{
+    return guarded([&] {
+        bind(c);
+        HipLinSysSolver& l = L(c);
+        need(l.numRows > 0, "no pattern");
+        needWholeMatrix(c);
+        DevBuf<double> dx, dy;
+        dx.upload(x, l.numRows, c->stream);
+        dy.alloc(l.numRows);
+        l.multiplySym(dx.p, dy.p);
+        dy.download(y, l.numRows, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_linsys_set_iterative(ipcgpu_ctx* c, double rel_tol, int max_iter, int precond, int max_factor_age)
+{
+    specChanged(c);
+    return guarded([&] {
+        L(c).setIterative(rel_tol, max_iter, precond, max_factor_age);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_linsys_iter_stats(ipcgpu_ctx* c, double* out6)
+{
+    return guarded([&] {
+        needArg(c && out6, "null argument");
+        L(c).iterStats(out6);
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_linsys_analyze_pattern(ipcgpu_ctx* c)
 {
     return guarded([&] {
@@ -604,9 +640,9 @@ int ipcgpu_linsys_solve(ipcgpu_ctx* c, const double* rhs, double* x)
         DevBuf<double> db, dx;
         db.upload(rhs, l.numRows, c->stream);
         dx.alloc(l.numRows);
-        l.solve(db.p, dx.p);
+        const bool ok = l.solve(db.p, dx.p);
         dx.download(x, l.numRows, c->stream);
-        return IPCGPU_OK;
+        return ok ? IPCGPU_OK : IPCGPU_NOT_PD;
     });
 }
 int ipcgpu_linsys_precondition_diag(ipcgpu_ctx* c, const double* in, double* out)
@@ -628,6 +664,10 @@ int ipcgpu_linsys_set_shard(ipcgpu_ctx* c, int rank, int world)
     specChanged(c);
     return guarded([&] {
         needArg(c && world >= 1 && rank >= 0 && rank < world, "bad shard");
+        if (world > 1 && c->lin->solverType == IPCGPU_SOLVER_PCG) {
+            g_err = "the iterative solver is not sharded";
+            return IPCGPU_ERR_UNSUPPORTED;
+        }
         need(world == 1 || c->opt->allreduce != nullptr || c->opt->allreduceStream != nullptr, "set the all-reduce hook first (ipcgpu_opt_set_allreduce)");
         need(world == 1 || c->lin->hasExchangeHook(), "set the exchange hook first (ipcgpu_opt_set_exchange / ipcgpu_opt_set_exchange_stream): the sharded solver sends point to point");
         c->lin->setShard(rank, world, c->opt->allreduce, c->opt->allreduceUser, c->opt->allreduceStream, c->opt->allreduceStreamUser);
@@ -1749,6 +1789,34 @@ int ipcgpu_bench_factor_solve(ipcgpu_ctx* c, int reps, double* fms, double* sms)
         (void)hipEventDestroy(e2);
         *fms = tf / reps;
         *sms = ts / reps;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_bench_multiply_sym(ipcgpu_ctx* c, int reps, double* avg_ms, double* bytes)
+{
+    return guarded([&] {
+        needArg(c && reps > 0 && avg_ms && bytes, "bad argument");
+        bind(c);
+        HipLinSysSolver& l = L(c);
+        need(l.numRows > 0, "no pattern");
+        DevBuf<double> x, y;
+        x.alloc(l.numRows);
+        y.alloc(l.numRows);
+        launch_fill(x.p, l.numRows, 1.0, c->stream);
+        l.multiplySym(x.p, y.p); // (builds the pattern's index; warm-up)
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        HIP_CHECK(hipEventRecord(e0, c->stream));
+        for (int r = 0; r < reps; ++r) l.multiplySym(x.p, y.p);
+        HIP_CHECK(hipEventRecord(e1, c->stream));
+        HIP_CHECK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        *avg_ms = ms / reps;
+        *bytes = 12.0 * (double)l.ja.size() + 16.0 * l.numRows; // values + columns + the two vectors, each once
         return IPCGPU_OK;
     });
 }

@@ -13,6 +13,7 @@
 #include "patch_assembly.h"
 #include "hip_contact.h"
 #include "hip_halfspace.h"
+#include "pcg.h"
 #include <map>
 #include <memory>
 #include <string>
@@ -81,12 +82,20 @@ public:
     int findEntry(int row, int col) const;
     void analyze_pattern(const HipMesh* meshForCoords);
     bool factorize();
-    void solve(const double* rhs_dev, double* x_dev);
+    bool solve(const double* rhs_dev, double* x_dev); // false: the iterative solver met p.Ap <= 0 (the exact solvers always return true)
     bool factorizeSolve(const double* rhs_dev, double* x_dev, bool wait = true); // factorize + solve, forward sweep overlapped with the factorisation
     bool lastPivotsOk() const; // after factorizeSolve(..., wait = false) and a synchronisation of the stream
     bool lastSyncOk_ = true;
     void multiply(const double* x_dev, double* y_dev);
     void precondition_diag(const double* in_dev, double* out_dev);
+    // Solver type 2: preconditioned CG (the reference's iterative choice, AMGCLSolver.cpp:24-25, 173-241).  precond 0: 3x3 block Jacobi, no symbolic
+    // analysis at all; 1: the multifrontal factor of an earlier matrix, kept for up to maxFactorAge factorize() calls.
+    double pcgRelTol = 1e-5; // solver.tol, AMGCLSolver.cpp:24
+    int pcgMaxIter = 1000; // solver.maxiter, :25
+    int pcgPrecond = 0, pcgMaxFactorAge = 1; // (the best of 1, 2, 4, 8, 16 on the headline workload: profiles/pcg_bench.json)
+    void setIterative(double relTol, int maxIter, int precond, int maxFactorAge);
+    void iterStats(double* out6) const;
+    void multiplySym(const double* x_dev, double* y_dev); // the atomic-free product of the iterative solver (any solver type)
     int getNumRows() const { return numRows; }
     int getNumNonzeros() const { return (int)ja.size(); }
     const MfSymbolic& symbolic() const { return sym_; }
@@ -112,12 +121,27 @@ public:
     int analysisVersion = 0; // bumped by every analyze_pattern (the owner-computes plan of the assembly follows the solver's cut)
     double sharedFlopFraction() const { return num_.sharedFlopFraction(); }
     bool analyzed() const { return analyzed_; }
+    void invalidateAnalysis() { analyzed_ = false; } // the solver type changed: what one back end set up is not what another needs
 
 private:
     MfSymbolic sym_;
     MfNumeric num_;
     bool analyzed_ = false;
     std::unique_ptr<struct RocsolverCsrrf> rs_;
+    // solver type 2
+    PcgPattern pcgPat_;
+    PcgWork pcgWork_;
+    int pcgPatVersion_ = -1;
+    void ensurePcgPattern();
+    int runPcg(const double* rhs_dev, double* x_dev, PcgState& out);
+    bool haveFactor_ = false, lastConverged_ = true;
+    int factorAge_ = 0; // factorize() calls since the factor was computed
+    long long nFactorizations_ = 0;
+    struct {
+        int iterations = 0, syncs = 0, factorAge = 0;
+        double residual = 0.0;
+        bool converged = false;
+    } pcgLast_;
     friend struct RocsolverCsrrf;
 };
 

@@ -3,6 +3,7 @@
 #include "hip_ipc.h"
 #include <rocsolver/rocsolver.h>
 #include <algorithm>
+#include <cmath>
 #include <thread>
 #include <cstdlib>
 
@@ -215,11 +216,22 @@ void HipLinSysSolver::analyze_pattern(const HipMesh* mesh)
     // leaf domains of at most 12 nodes (36 columns): one level less at the bottom of the tree than with 8 -- one launch less in the factorisation and in each sweep --
     // and still a single-workgroup front in 64 KB of LDS.  Measured (profiles/r04_nd_leaf_size_ab.txt): mat150 5: 382, 6: 384, 8: 393, 10: 396, 12: 406, 14: 406, 16: 394,
     // 20: 398 it/s; mat433 42.9 -> 43.7; contact bench 10.98 -> 10.78 ms per iteration.
+    if (solverType == 2) {
+        if (num_.world() > 1) throw StateError("the iterative solver is not sharded");
+        ensurePcgPattern();
+        haveFactor_ = false;
+        factorAge_ = 0;
+        lastConverged_ = true;
+        if (pcgPrecond == 0) { // block Jacobi: nothing of the exact solvers' symbolic phase (LinSysSolver::analyze_pattern is a no-op in AMGCLSolver.hpp too)
+            analyzed_ = true;
+            return;
+        }
+    }
     const int leaf = 12;
     // (the entries' destinations in the fronts are computed on the device by MfNumeric::setup; the rocSOLVER back end does not use them)
     mf_analyze(numRows, ia.data(), ja.data(), cptr, leaf, sym_, /*withEntryDestinations=*/false);
     ++analysisVersion;
-    if (solverType == 0) {
+    if (solverType == 0 || solverType == 2) {
         num_.setup(sym_, stream, d_ia.p, d_ja.p, (long long)ja.size());
     }
     else {
@@ -275,6 +287,28 @@ bool HipLinSysSolver::factorize()
 {
     if (!analyzed_) throw StateError("factorize before analyze_pattern");
     if (solverType == 0) return num_.factorize(d_a.p);
+    if (solverType == 2) {
+        if (pcgPrecond == 0) {
+            // AMGCLSolver::factorize rebuilds its preconditioner from the current values and always returns true (AMGCLSolver.cpp:173-191); here
+            // a diagonal block that is not positive definite is reported, since the matrix then is not either
+            pcgWork_.ensure(numRows);
+            pcgWork_.flag.zero(stream);
+            launch_pcg_invert_blocks(pcgPat_, d_a.p, pcgWork_.flag.p, stream);
+            int f = 0;
+            pcgWork_.flag.download(&f, 1, stream);
+            return f == 0;
+        }
+        // the factor of an earlier matrix goes on serving as the preconditioner: a factor is used by at most pcgMaxFactorAge factorize() calls
+        if (haveFactor_ && lastConverged_ && factorAge_ + 1 < pcgMaxFactorAge) {
+            ++factorAge_;
+            return true;
+        }
+        ++nFactorizations_;
+        haveFactor_ = num_.factorize(d_a.p);
+        factorAge_ = 0;
+        lastConverged_ = true;
+        return haveFactor_;
+    }
     RocsolverCsrrf& R = *rs_;
     hipLaunchKernelGGL(k_gather, dim3((R.nnzA + 255) / 256), dim3(256), 0, stream, R.nnzA, R.trans.p, d_a.p, R.valA.p);
     rocblas_status st = rocsolver_dcsrrf_refactchol(R.handle, R.n, R.nnzA, R.ptrA.p, R.indA.p, R.valA.p, R.nnzT, R.ptrT.p, R.indT.p,
@@ -299,23 +333,133 @@ bool HipLinSysSolver::factorizeSolve(const double* rhs_dev, double* x_dev, bool 
     lastSyncOk_ = true;
     if (solverType == 0) return lastSyncOk_ = num_.factorizeSolve(d_a.p, rhs_dev, x_dev, wait);
     const bool ok = factorize();
-    if (ok) solve(rhs_dev, x_dev);
-    return lastSyncOk_ = ok;
+    return lastSyncOk_ = ok && solve(rhs_dev, x_dev);
 }
 bool HipLinSysSolver::lastPivotsOk() const { return lastSyncOk_ && (solverType != 0 || num_.lastPivotsOk()); }
 
-void HipLinSysSolver::solve(const double* rhs_dev, double* x_dev)
+bool HipLinSysSolver::solve(const double* rhs_dev, double* x_dev)
 {
     if (!analyzed_) throw StateError("solve before analyze_pattern");
     if (solverType == 0) {
         num_.solve(rhs_dev, x_dev);
-        return;
+        return true;
+    }
+    if (solverType == 2) {
+        const bool jacobi = pcgPrecond == 0;
+        if (!jacobi && !haveFactor_) throw StateError("solve before factorize");
+        pcgLast_ = {};
+        pcgLast_.factorAge = jacobi ? 0 : factorAge_;
+        PcgState st;
+        int status = runPcg(rhs_dev, x_dev, st);
+        pcgLast_.iterations = st.iter;
+        if (status == PCG_MAXITER && !jacobi && factorAge_ > 0) {
+            // the stale factor did not get there: refactorise the current values once and solve again
+            ++nFactorizations_;
+            haveFactor_ = num_.factorize(d_a.p);
+            factorAge_ = 0;
+            if (!haveFactor_) return false;
+            pcgLast_.factorAge = 0;
+            status = runPcg(rhs_dev, x_dev, st);
+            pcgLast_.iterations += st.iter;
+        }
+        pcgLast_.residual = st.bb > 0.0 ? std::sqrt(st.trueRes2 / st.bb) : 0.0;
+        pcgLast_.converged = status == PCG_CONVERGED && st.trueRes2 <= st.tol2;
+        lastConverged_ = pcgLast_.converged;
+        // not converged: the caller goes on with what it got, as the reference does with AMGCL's answer (AMGCLSolver.cpp:230-241)
+        return status != PCG_BREAKDOWN;
     }
     RocsolverCsrrf& R = *rs_;
     HIP_CHECK(hipMemcpyAsync(x_dev, rhs_dev, sizeof(double) * R.n, hipMemcpyDeviceToDevice, stream));
     if (rocsolver_dcsrrf_solve(R.handle, R.n, 1, R.nnzT, R.ptrT.p, R.indT.p, R.valT.p, nullptr, R.pivQ.p, x_dev, R.n, R.info)
         != rocblas_status_success)
         throw HipError("rocsolver_dcsrrf_solve failed");
+    return true;
+}
+
+// ---- solver type 2 ------------------------------------------------------------------------------------------------------------------
+void HipLinSysSolver::setIterative(double relTol, int maxIter, int precond, int maxFactorAge)
+{
+    if (!(relTol > 0.0) || maxIter < 1 || (precond != 0 && precond != 1) || maxFactorAge < 1)
+        throw ArgError("set_iterative: rel_tol > 0, max_iter >= 1, precond 0 | 1, max_factor_age >= 1");
+    if (precond != pcgPrecond && solverType == 2) analyzed_ = false; // (the lagged factor needs the symbolic analysis block Jacobi skips)
+    pcgRelTol = relTol;
+    pcgMaxIter = maxIter;
+    pcgPrecond = precond;
+    pcgMaxFactorAge = maxFactorAge;
+}
+
+void HipLinSysSolver::iterStats(double* o) const
+{
+    o[0] = pcgLast_.iterations;
+    o[1] = pcgLast_.residual;
+    o[2] = pcgLast_.converged ? 1.0 : 0.0;
+    o[3] = (double)nFactorizations_;
+    o[4] = pcgLast_.factorAge;
+    o[5] = pcgLast_.syncs;
+}
+
+void HipLinSysSolver::ensurePcgPattern()
+{
+    if (!numRows) throw StateError("no pattern");
+    if (pcgPatVersion_ == patternVersion) return;
+    pcgPat_.build(numRows, ia, ja, rowBase, rowLen, stream);
+    pcgPatVersion_ = patternVersion;
+}
+
+void HipLinSysSolver::multiplySym(const double* x_dev, double* y_dev)
+{
+    ensurePcgPattern();
+    launch_pcg_symv(pcgPat_, d_ia.p, d_ja.p, d_rowBase.p, d_rowLen.p, d_a.p, x_dev, nullptr, nullptr, 0, y_dev, nullptr, nullptr, 0, stream);
+}
+
+// One CG run from x = 0.  The host enqueues batches of iterations and looks at the published state once per batch; a batch's launches behind the
+// iteration that ended the solve return at once on the device's flag.  Block Jacobi: batches of 16, 32, 64, 64, ... iterations.  Lagged factor: the
+// preconditioner is the multifrontal solver's own launch sequence, which knows nothing of the flag, so the host looks after every iteration, before
+// the sweeps (a synchronisation costs a tenth of them).  The true residual is computed behind the iteration that ended the solve, inside the same
+// batch; should it miss the tolerance the recurrence residual claims (rounding, after many iterations), CG restarts from the current x.
+int HipLinSysSolver::runPcg(const double* rhs_dev, double* x_dev, PcgState& out)
+{
+    const bool jacobi = pcgPrecond == 0;
+    PcgWork& W = pcgWork_;
+    W.ensure(numRows);
+    const int gAp = pcg_symv_grid(pcgPat_);
+    double* p[2] = { W.p0.p, W.p1.p };
+    int cur = 0, first = 1, restarts = 0, batch = jacobi ? 16 : 1;
+    auto precondition = [&](int firstRz) {
+        if (jacobi) return;
+        num_.solve(W.r.p, W.z.p);
+        launch_pcg_rz(numRows, W.r.p, W.z.p, W, firstRz, stream);
+    };
+    launch_pcg_begin(pcgPat_, jacobi, false, rhs_dev, nullptr, x_dev, W, pcgRelTol, pcgMaxIter, stream);
+    precondition(1);
+    for (;;) {
+        for (int i = 0; i < batch; ++i) {
+            launch_pcg_symv(pcgPat_, d_ia.p, d_ja.p, d_rowBase.p, d_rowLen.p, d_a.p, W.z.p, p[cur], p[1 - cur], first, W.Ap.p, W.partial.p, W.state.p, 1, stream);
+            cur = 1 - cur;
+            first = 0;
+            launch_pcg_alpha(W, gAp, stream);
+            launch_pcg_update(pcgPat_, jacobi, p[cur], W.Ap.p, x_dev, W, stream);
+        }
+        launch_pcg_symv(pcgPat_, d_ia.p, d_ja.p, d_rowBase.p, d_rowLen.p, d_a.p, x_dev, nullptr, nullptr, 0, W.Ap.p, nullptr, W.state.p, 2, stream);
+        launch_pcg_residual(numRows, rhs_dev, W.Ap.p, W, stream);
+        launch_pcg_publish(W, stream);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        ++pcgLast_.syncs;
+        out = *W.hState.p;
+        if (out.done == PCG_RUNNING) {
+            precondition(0);
+            if (jacobi) batch = std::min(64, 2 * batch);
+            continue;
+        }
+        if (out.done == PCG_CONVERGED && out.trueRes2 > out.tol2 && restarts < 3 && out.iter < out.maxIter) {
+            ++restarts;
+            launch_pcg_begin(pcgPat_, jacobi, true, rhs_dev, W.Ap.p, x_dev, W, pcgRelTol, pcgMaxIter, stream);
+            first = 1;
+            precondition(1);
+            continue;
+        }
+        return out.done;
+    }
 }
 
 void HipLinSysSolver::multiply(const double* x_dev, double* y_dev)

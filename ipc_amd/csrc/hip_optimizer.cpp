@@ -1258,7 +1258,8 @@ void HipOptimizer::computeSearchDir(bool projectDBC)
 
 bool HipOptimizer::fastPath() const
 {
-    return worldSize == 1 && !ipOn() && nbcGroups.empty() && !(dampingStiff > 0.0) && !(rhoDBC && !tpIds.empty());
+    // (the iterative solver synchronises inside its solve and may end in the diagonal fallback: the general branch of computeSearchDir)
+    return worldSize == 1 && !ipOn() && nbcGroups.empty() && !(dampingStiff > 0.0) && !(rhoDBC && !tpIds.empty()) && lin.solverType != 2;
 }
 
 void HipOptimizer::resolveEventTimers()

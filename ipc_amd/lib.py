@@ -24,6 +24,9 @@ IPCGPU_OK = 0
 IPCGPU_NOT_PD = 1
 SOLVER_MULTIFRONTAL = 0
 SOLVER_ROCSOLVER_CSRRF = 1
+SOLVER_PCG = 2  # the reference's `linearSolver AMGCL`: preconditioned CG (ipcgpu_linsys_set_iterative)
+PRECOND_BLOCK_JACOBI = 0
+PRECOND_LAGGED_CHOLESKY = 1
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int)
 
@@ -402,6 +405,23 @@ class Context:
         y = np.zeros_like(x)
         self._chk(self._L.ipcgpu_linsys_multiply(self.h, _dp(x), _dp(y)))
         return y
+
+    def multiply_sym(self, x):
+        """the iterative solver's product: no atomics, the same bits on every run (ipcgpu_linsys_multiply_sym)"""
+        x = _f64(x)
+        y = np.zeros_like(x)
+        self._chk(self._L.ipcgpu_linsys_multiply_sym(self.h, _dp(x), _dp(y)))
+        return y
+
+    def set_iterative(self, rel_tol=1e-5, max_iter=1000, precond=PRECOND_BLOCK_JACOBI, max_factor_age=1):
+        """parameters of solver type 2 (ipcgpu_linsys_set_iterative); the defaults are the library's"""
+        self._chk(self._L.ipcgpu_linsys_set_iterative(self.h, C.c_double(rel_tol), C.c_int(max_iter), C.c_int(precond), C.c_int(max_factor_age)))
+
+    def iter_stats(self):
+        """of the last solve of solver type 2 (ipcgpu_linsys_iter_stats)"""
+        o = np.zeros(6)
+        self._chk(self._L.ipcgpu_linsys_iter_stats(self.h, _dp(o)))
+        return dict(iterations=int(o[0]), residual=float(o[1]), converged=int(o[2]), factorizations=int(o[3]), factor_age=int(o[4]), syncs=int(o[5]))
 
     def analyze_pattern(self):
         self._chk(self._L.ipcgpu_linsys_analyze_pattern(self.h))
@@ -795,6 +815,11 @@ class Context:
         f, s = C.c_double(), C.c_double()
         self._chk(self._L.ipcgpu_bench_factor_solve(self.h, C.c_int(reps), C.byref(f), C.byref(s)))
         return f.value, s.value
+
+    def bench_multiply_sym(self, reps=50):
+        ms, by = C.c_double(), C.c_double()
+        self._chk(self._L.ipcgpu_bench_multiply_sym(self.h, C.c_int(reps), C.byref(ms), C.byref(by)))
+        return ms.value, by.value
 
     def bench_stream(self, nbytes=1 << 30, reps=10):
         g = C.c_double()

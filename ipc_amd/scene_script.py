@@ -12,6 +12,7 @@ anything else raises `UnsupportedKeyword` instead of being ignored silently.
 from dataclasses import dataclass, field
 import math
 import os
+import warnings
 
 import numpy as np
 
@@ -54,6 +55,7 @@ class Shape:
 class SceneConfig:
     energy: str = "NH"
     time_integration: str = "BE"
+    linear_solver: int = 0  # `linearSolver` (Config.cpp:120-124): the solver type of ipcgpu_ctx_set_solver, for the Context the caller creates
     beta: float = 0.25
     gamma: float = 0.5
     duration: float = 5.0
@@ -240,7 +242,15 @@ class SceneConfig:
                 if not 0 < cfg.handle_ratio < 0.5:
                     raise ValueError("handleRatio must lie in (0, 0.5) (Config.cpp:530)")
             elif k in ("linearSolver", "linSysSolver"):
-                pass  # Config.cpp:120-124 picks CHOLMOD / AMGCL / Eigen inside the reference; the library brings its own factorisation
+                # Config.cpp:120-124, 689-706: `amgcl | AMGCL` is the iterative choice (solver type 2 with the library's defaults); `cholmod | CHOLMOD`,
+                # `eigen | EIGEN | Eigen` are exact factorisations, and an unknown name falls back to one with a warning (:704-705): the multifrontal solver
+                name = a[0] if a else ""
+                if name in ("amgcl", "AMGCL"):
+                    cfg.linear_solver = 2
+                else:
+                    cfg.linear_solver = 0
+                    if name not in ("cholmod", "CHOLMOD", "eigen", "EIGEN", "Eigen"):
+                        warnings.warn(f"unknown linear system solver: {name}; using the default (multifrontal) solver")
             elif k in ("CCDTolerance", "ccdTolerance"):
                 pass  # Config.cpp:569-571: read by the TightInclusion back end only (Optimizer.cpp:1149, 1173); the default method takes none
             elif k == "DBCTimeRange":

@@ -22,7 +22,7 @@ root = args.root or os.path.dirname(os.path.abspath(args.scene))
 cfg = ss.SceneConfig.parse(open(args.scene).read(), root)
 sc = ss.assemble(cfg, lib.read_tet_mesh)
 print(f"{len(cfg.shapes)} shapes, {sc.V.shape[0]} nodes, {sc.T.shape[0]} tets, {sc.SF.shape[0]} surface triangles, dt = {cfg.dt}")
-c = ss.apply(sc, lib.Context(0))
+c = ss.apply(sc, lib.Context(0, solver=cfg.linear_solver))  # `linearSolver AMGCL` -> the iterative solver
 steps = args.steps if args.steps is not None else int(round(cfg.duration / cfg.dt))
 for step in range(steps):
     t0 = time.time()

@@ -126,12 +126,12 @@ void MfNumeric::criticalPath(double* out5) const
         for (int q = sym.levelPtr[l]; q < sym.levelPtr[l + 1]; ++q) {
             const int s = sym.levelFronts[q], st = (sym.nc(s) + 31) / 32;
             widest = std::max(widest, st);
-            const bool shared = world_ > 1 && owner_[s] < 0;
+            const bool shared = world_ > 1 && mp_.owner[s] < 0;
             if (shared) widestAbove = std::max(widestAbove, st);
             else {
                 const double N = sym.N(s), nc = sym.nc(s);
                 const double fl = nc * nc * nc / 3.0 + nc * nc * (N - nc) + nc * (N - nc) * (N - nc);
-                load[world_ > 1 ? owner_[s] : 0] += fl;
+                load[world_ > 1 ? mp_.owner[s] : 0] += fl;
                 below += fl;
             }
         }
@@ -150,22 +150,22 @@ void MfNumeric::criticalPath(double* out5) const
 // the parent's rank (a bad pivot anywhere reaches everybody with the one-double all-reduce behind the factorisation)
 void MfNumeric::exchangeUpdateMatrices(int l)
 {
-    const Xchg& X = xchg_[l];
+    const MfXchgLevel& X = mp_.xchg[l];
     if (X.opsM.empty()) return;
     TreeView tv{ frontOff_.p, idxPtr_.p, firstNode_.p, childPtr_.p, child_.p, invPtr_.p, inv_.p, idx_.p, dinvOff_.p };
     if (X.pack.cnt) hipLaunchKernelGGL(k_xchg_update, dim3(64, X.pack.cnt), dim3(256), 0, stream_, xchgDesc_.p + X.pack.off, tv, fronts_.p, xchgBuf_.p, 0);
-    exchange(X.opsM);
+    exchange(xchg_[l].opsM);
     if (X.unpack.cnt) hipLaunchKernelGGL(k_xchg_update, dim3(64, X.unpack.cnt), dim3(256), 0, stream_, xchgDesc_.p + X.unpack.off, tv, fronts_.p, xchgBuf_.p, 1);
 }
 
 // the same for the update vectors of the forward sweep
 void MfNumeric::exchangeUpdateVectors(int l)
 {
-    const Xchg& X = xchg_[l];
+    const MfXchgLevel& X = mp_.xchg[l];
     if (X.opsW.empty()) return;
     TreeView tv{ frontOff_.p, idxPtr_.p, firstNode_.p, childPtr_.p, child_.p, invPtr_.p, inv_.p, idx_.p, dinvOff_.p };
     if (X.pack.cnt) hipLaunchKernelGGL(k_xchg_w, dim3(4, X.pack.cnt), dim3(256), 0, stream_, xchgDesc_.p + X.pack.off, tv, wOff_.p, w_.p, xchgBuf_.p, 0);
-    exchange(X.opsW);
+    exchange(xchg_[l].opsW);
     if (X.unpack.cnt) hipLaunchKernelGGL(k_xchg_w, dim3(4, X.unpack.cnt), dim3(256), 0, stream_, xchgDesc_.p + X.unpack.off, tv, wOff_.p, w_.p, xchgBuf_.p, 1);
 }
 

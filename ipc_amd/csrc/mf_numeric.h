@@ -2,6 +2,7 @@
 // mf_symbolic.  Plays the role of cholmod_factorize / cholmod_solve (CHOLMODSolver.cpp:130-154).
 #pragma once
 #include "common.h"
+#include "mf_plan.h"
 #include "mf_symbolic.h"
 
 namespace ipcgpu {
@@ -44,8 +45,8 @@ public:
     // for the default threshold, so the tests force the path on through these
     void setBulkTuning(double minMB, int block)
     {
-        bulkMinMB_ = minMB;
-        bulkBlock_ = block < 64 ? 64 : (block / 32) * 32;
+        tune_.bulkMinMB = minMB;
+        tune_.bulkBlock = block < 64 ? 64 : (block / 32) * 32;
     }
     void setExchangeHooks(ExchangeFn fn, void* user, ExchangeStreamFn sfn, void* streamUser)
     {
@@ -79,7 +80,7 @@ public:
     // the same over the fronts above the cut only, the largest rank's share of the flops below the cut (1 / world when balanced), levels, levels that
     // hold a front above the cut }
     void criticalPath(double* out5) const;
-    double sharedFlopFraction() const { return sharedFlops_; } // share of the factorisation flops above the cut (executed once each since round 5, on the chain of the cut's levels)
+    double sharedFlopFraction() const { return mp_.sharedFlops; } // share of the factorisation flops above the cut (executed once each since round 5, on the chain of the cut's levels)
     // a_dev: CSR values (device).  Returns false when a non-positive pivot was met.
     bool factorize(const double* a_dev);
     // rhs_dev / x_dev: device vectors in the user's ordering
@@ -100,51 +101,25 @@ public:
 private:
     void enqueueFactor(const double* a_dev, bool overlapForward = false);
     void enqueueSolve(const double* rhs_dev, double* x_dev);
-    struct Range {
-        int off = 0, cnt = 0;
-    };
-    struct LevelPlan {
-        Range small; // into smallList_
-        size_t smallLds = 0, solveLds = 0, triLds = 0, bwdLds = 0;
-        int smallThreads = 256; // workgroup size of the fused kernel on this level
-        Range ea; // extend-add descriptors
-        Range bigFronts; // into bigList_
-        std::vector<Range> step; // fused factor steps: launch 0 factors panel 0, launch j+1 applies panel j / factors j+1
-        std::vector<Range> bulk; // per step launch: the bulk updates of the wide fronts that follow it (k_big_bulk; empty ranges elsewhere)
-        Range schur; // one-pass Schur complement tiles of the big fronts
-        bool schur64 = false; // ... as 64 x 64 tiles (k_big_schur64) instead of 32 x 32 with the columns split over the waves
-        bool stepTop = false; // the level's step launches carry role C, the explicit inverse growing by bordering (k_big_step<true>)
-        bool fuseEA = false; // the level's Schur kernel gathers the children of the update block itself (k_big_schur64_ea); the extend-add only writes own columns
-        Range fwdRect, bwdInit; // descriptors of the row-/column-parallel halves of the big-front solves
-        Range bigTri; // into triList_: big fronts whose triangle is swept by one workgroup (no explicit inverse)
-        Range xinvFwd, xinvBwd; // into xinvDesc_: row / column blocks of the fronts with an explicit inverse
-    };
+    typedef MfRange Range;
+    typedef MfLevelPlan LevelPlan;
+    typedef MfXinvLevel XinvLevel;
     int rank_ = 0, world_ = 1;
-    const long long schur64Min_ = 512; // levels with at least this many 32 x 32 Schur tiles take the 64 x 64 kernel (profiles/r03r_schur_tile_ab.txt)
-    double bulkMinMB_ = 48.0; // levels whose step launches read + write at least that many MB of own columns factor them in outer blocks (two-level blocking, k_big_bulk); ipcgpu_linsys_set_tuning "bulk_min_mb"
-    int bulkBlock_ = 256; // width of an outer block; ipcgpu_linsys_set_tuning "bulk_block"
-    bool xinvBorder_ = true; // X = L11^-1 by bordering inside the step launches (false: recursive doubling on the side stream, the round-4 scheme)
+    MfPlanTuning tune_; // what the next setup() plans with; setBulkTuning sets the only two fields a caller can change
+    MfPlan mp_; // the launch plan of the current pattern (mf_plan.h): which front takes which kernel, every descriptor range the launches below read
     AllreduceFn allreduce_ = nullptr;
     AllreduceStreamFn allreduceStream_ = nullptr;
     void* allreduceUser_ = nullptr;
     void* allreduceStreamUser_ = nullptr; // its own slot: attaching RCCL after a host hook must not replace that hook's user pointer
-    double sharedFlops_ = 0.0;
     ExchangeFn exchange_ = nullptr;
     ExchangeStreamFn exchangeStream_ = nullptr;
     void* exchangeUser_ = nullptr;
     void* exchangeStreamUser_ = nullptr;
-    std::vector<int> owner_; // per front: owning rank, -1 = above the cut
-    std::vector<int> exec_; // per front: the rank that factorises and solves it (== owner_ below the cut)
-    std::vector<unsigned long long> group_; // per front: ranks that execute a front of its subtree
     long long commBytes_ = 0, commCalls_ = 0, sentBytes_ = 0, recvBytes_ = 0;
     double waitMs_ = 0.0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> waitPending_, waitFree_; // event pairs around exchange groups not yet read / free for reuse
-    struct Xchg {
-        Range pack; // into xchgDesc_: (front, staging offset lo, hi, offset of its update vector) of the fronts of this level this rank SENDS to their parent's rank
-        Range unpack; // ... and of the children (of this level) of fronts this rank executes that it RECEIVES
-        std::vector<P2POp> opsM, opsW, opsX; // the level's groups: update matrices (factorisation), update vectors (forward sweep), solution segments (backward sweep)
-        long long count = 0; // doubles exchanged after the level's factorisation (update matrices)
-        long long countW = 0; // ... and after its forward sweep (update vectors)
+    struct Xchg { // the level's groups (MfXchgLevel) with the offsets resolved to pointers
+        std::vector<P2POp> opsM, opsW, opsX;
     };
     std::vector<Xchg> xchg_;
     DevBuf<int4> xchgDesc_;
@@ -163,22 +138,13 @@ private:
     const MfSymbolic* sym_ = nullptr;
     hipStream_t stream_ = nullptr;
     int ns_ = 0, nLevels_ = 0;
-    long long nDiagBlocks_ = 0;
-    std::vector<LevelPlan> plan_;
     DevBuf<double> fronts_, w_, yperm_, bperm_, xsol_;
     // explicit inverses X = L11^-1 of the widest fronts (and the scratch T of their recursive doubling)
     DevBuf<double> xinvX_, xinvT_;
     DevBuf<long long> xinvOff_;
     DevBuf<int4> xinvDesc_;
     DevBuf<int> triList_;
-    struct XinvLevel {
-        Range blocks; // diagonal blocks of the level's inverse fronts (cnt > 0: the level has inverses to form by recursive doubling)
-        Range init; // into xinvDesc_
-        std::vector<std::pair<Range, Range>> rounds; // per doubling: the two GEMM launches (descriptor pairs)
-    };
-    std::vector<XinvLevel> xinvLevel_;
     hipStream_t side_ = nullptr; // inverses are formed here, beside the chain of the upper levels
-    bool xcdOrder_ = true; // Schur tiles dealt to the XCDs front by front (false: front after front over all XCDs, as before round 5; profiles/r05_solver_ab_xcd_occupancy.txt)
     int fwdStride_ = 4; // levels handed to the forward stream per event (1 = every level, as before round 4; profiles/r05_knob_sweep.txt)
     bool fwdJoined_ = false; // the root's forward sweep went onto the main stream (factorizeSolve)
     // factorizeSolve(): the forward sweep of a level is enqueued on its own stream as soon as that level's factor kernels are, so that it
@@ -192,15 +158,12 @@ private:
     std::vector<hipEvent_t> evLevel_, evInvDone_;
     bool sidePending_ = false; // the last factorisation left work on the side stream that nothing has waited for yet
     void enqueueInverses(int level, hipStream_t st);
-    size_t xinvLds_ = 8;
     DevBuf<double> dinv_; // explicit inverses of the 32x32 diagonal blocks of L, 1024 doubles each
     DevBuf<int> idx_, idxPtr_, firstNode_, childPtr_, child_, invPtr_, inv_, newOf_, flag_;
     DevBuf<long long> frontOff_, wOff_, dinvOff_;
-    std::vector<long long> hDinvOff_; // host copy: the step records carry a front's first inverse block
     DevBuf<int> aSrc_, aLoc_; // entries of A per fused front: CSR source index, offset inside the LDS panel
     DevBuf<double> aPerm_; // values of A gathered into fused-front order at the start of every factorisation
     int nFusedA_ = 0;
-    std::vector<int> aPtrHost_; // front -> first entry (goes into the packed descriptors)
     DevBuf<int> bigFd_; // packed records of the other fronts (k_extend_add)
     DevBuf<int> fdesc_; // packed descriptors of the fused fronts (64 ints each, launch order)
     DevBuf<int> bigASrc_; // entries of A of the other fronts, grouped by extend-add tile: source index ...

@@ -157,8 +157,8 @@ __global__ __launch_bounds__(WG) void k_extend_add(const int4* __restrict__ desc
     const int* __restrict__ invMap, double* __restrict__ fronts, int ownOnly, const int* __restrict__ aPtr, const int* __restrict__ aSrc,
     const long long* __restrict__ aDst, const double* __restrict__ a)
 {
-    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE_EA];
-    __shared__ int rmap[FUSED_MAX_KIDS_EA][TS], cmap[FUSED_MAX_KIDS_EA][TS];
+    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE];
+    __shared__ int rmap[FUSED_MAX_KIDS][TS], cmap[FUSED_MAX_KIDS][TS];
     const int4 d = desc[blockIdx.x];
     const int i0 = TS * d.y, j0 = TS * d.z;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(WG) void k_extend_add(const int4* __restrict__ desc
     double* F = nullptr;
     for (int rec = d.x; rec >= 0;) {
         __syncthreads();
-        if (tid < FD_STRIDE_EA) fd[tid] = bigFd[(size_t)rec * FD_STRIDE_EA + tid];
+        if (tid < FD_STRIDE) fd[tid] = bigFd[(size_t)rec * FD_STRIDE + tid];
         __syncthreads();
         N = fd[2];
         ncOwn = fd[3];
@@ -403,12 +403,7 @@ __device__ __forceinline__ bool wave_potrf_inv32_mfma(const double* blk, int ld,
 // the tree.)
 //   P[k * N + r] = column k (< nc) of the front, rows 0..N (k-major: a wave reads 64 consecutive rows)
 //   cm[q * N + I] = scalar index of parent-local row I inside child q's front, or -1
-constexpr int FUSED_MAX_KIDS = FUSED_MAX_KIDS_EA;
-// Host-packed descriptor of a fused front, 64 ints: everything the kernel would otherwise chase through five rounds of
-// dependent loads (front list -> index pointers -> child list -> child pointers -> inverse maps) arrives in one.
-//   [0,1] front offset  [2] N  [3] nc  [4,5] first dinv block  [6] aBeg  [7] aEnd  [8] #children
-//   child q at 16 + 6 q: [0,1] front offset  [2] N  [3] nc  [4] offset of its inverse map
-constexpr int FD_STRIDE = FD_STRIDE_EA;
+// (the host-packed 64-int descriptor of a front: FD_STRIDE in mf_plan.h)
 // Diagnosis build only (-DMF_FUSED_PROBE, tools/gpu_r5_call11.sh): thread 0 of every fused front stamps the phases of its workgroup with the 100 MHz wall clock;
 // MfNumeric::factorize prints the level averages once.  Expands to nothing in the product build.
 #ifndef MF_FUSED_SCHUR_GROUP
@@ -757,7 +752,6 @@ __global__ __launch_bounds__(NT, 3) void k_front_fused(const int* __restrict__ f
 // D(j, i): the 16 lanes of an accumulator row hold 16 consecutive rows i of one column j, which makes the read-modify-write
 // of the column-major front 128-byte contiguous.  v_mfma_f64_16x16x4_f64: A[l & 15][l >> 4], B[l >> 4][l & 15],
 // D column = l & 15, row = (l >> 4) + 4 reg.
-constexpr int TQ = 32; // Schur tile
 // [cLo, cHi): the columns of L of this pass (multiples of 32).  One pass over all columns behind the chain (k_big_schur) on most levels; on the top
 // levels, where the pivot chain is what the level takes, the update rides on the chain's own launches in passes of a few panels (role S of k_big_step,
 // round 4): only the last pass is left behind the chain.  red: 4096 doubles of LDS, [wave][16 x 16 tile][D layout: 64 lanes x 4].
@@ -860,7 +854,6 @@ __global__ __launch_bounds__(WG, MF_SCHUR_OCC) void k_big_schur(const int4* __re
 // 32 x 32 version (a workgroup reads 128 rows of L for 4096 entries of S instead of 64 for 1024).  The fronts of those levels have nc of
 // 100-450: split four ways a wave ran two or three chunks between its prologue and the LDS reduction.  Upper levels keep the 32 x 32 kernel: they
 // have a handful of fronts and need the tiles for parallelism.  desc as above with 64 x 64 tile indices.
-constexpr int TQ64 = 64;
 // LOAD_OLD = false: `old` arrives filled (the children's sums gathered by the caller: k_big_schur64_ea) and the tile is WRITTEN, not read-modify-written.
 // (Round 5: parking `old` in LDS over the product loop -- 32 registers less, a third wave per SIMD -- changed nothing, measured at 45 K and 375 K nodes:
 // the kernel is not occupancy-bound.  profiles/r05_solver_ab_xcd_occupancy.txt.)
@@ -980,8 +973,8 @@ __global__ __launch_bounds__(WG, MF_SCHUR_OCC) void k_big_bulk(const int4* __res
 __global__ __launch_bounds__(WG) void k_big_schur64_ea(const int4* __restrict__ desc, const int* __restrict__ bigFd, const int* __restrict__ invMap,
     double* __restrict__ fronts)
 {
-    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE_EA];
-    __shared__ int rmap[FUSED_MAX_KIDS_EA][TQ64], cmap[FUSED_MAX_KIDS_EA][TQ64];
+    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE];
+    __shared__ int rmap[FUSED_MAX_KIDS][TQ64], cmap[FUSED_MAX_KIDS][TQ64];
     const int4 d = desc[2 * blockIdx.x];
     const int4 d2 = desc[2 * blockIdx.x + 1];
     const int N = d2.x, nc = d2.y;
@@ -999,7 +992,7 @@ __global__ __launch_bounds__(WG) void k_big_schur64_ea(const int4* __restrict__ 
             for (int r = 0; r < 4; ++r) old[nj][mi][r] = 0.0;
     for (int rec = d.w; rec >= 0;) {
         __syncthreads();
-        if (tid < FD_STRIDE_EA) fd[tid] = bigFd[(size_t)rec * FD_STRIDE_EA + tid];
+        if (tid < FD_STRIDE) fd[tid] = bigFd[(size_t)rec * FD_STRIDE + tid];
         __syncthreads();
         const int nk = fd[8];
         rec = fd[9];
@@ -1533,6 +1526,15 @@ __global__ __launch_bounds__(256) void k_xinv_gemm(const int4* __restrict__ desc
 
 } // namespace
 
+namespace {
+
+static_assert(sizeof(MfRec4) == sizeof(int4) && alignof(MfRec4) <= alignof(int4), "the plan's records are uploaded as int4");
+void uploadRecs(DevBuf<int4>& buf, const std::vector<MfRec4>& recs, hipStream_t stream) { buf.upload(reinterpret_cast<const int4*>(recs.data()), recs.size(), stream); }
+
+} // namespace
+
+// Set-up for one pattern: buffers, the tree in HBM, the launch plan (mf_plan.cpp: host only, two steps around the one round trip of the device entry sort)
+// and its upload.
 void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_dev, const int* ja_dev, long long nnzPattern)
 {
     if (side_) HIP_CHECK(hipStreamSynchronize(side_)); // buffers are about to be replaced
@@ -1545,6 +1547,7 @@ void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_d
         fprintf(stderr, "mf setup %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tSetup).count());
         tSetup = now;
     };
+    if (world_ > 64) throw StateError("the sharded solver supports at most 64 ranks");
     sym_ = &sym;
     stream_ = stream;
     ns_ = sym.ns;
@@ -1563,576 +1566,113 @@ void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_d
     invPtr_.upload(sym.invPtr, stream);
     inv_.upload(sym.inv.empty() ? std::vector<int>{ 0 } : sym.inv, stream);
     newOf_.upload(sym.newOf, stream);
-    {
-        std::vector<long long> t(sym.frontOff.begin(), sym.frontOff.end());
-        frontOff_.upload(t, stream);
-        std::vector<long long> u(sym.wOff.begin(), sym.wOff.end());
-        wOff_.upload(u, stream);
-        std::vector<long long> di(ns_ + 1, 0);
-        for (int s = 0; s < ns_; ++s) di[s + 1] = di[s] + (sym.nc(s) + NB - 1) / NB;
-        dinvOff_.upload(di, stream);
-        hDinvOff_ = di;
-        nDiagBlocks_ = di[ns_];
-        dinv_.alloc((size_t)di[ns_] * NB * NB);
-    }
+    frontOff_.upload(std::vector<long long>(sym.frontOff.begin(), sym.frontOff.end()), stream);
+    wOff_.upload(std::vector<long long>(sym.wOff.begin(), sym.wOff.end()), stream);
     lap("buffers + tree uploads");
     flag_.alloc(1);
     hflag_.alloc(4);
+    auto newEvent = [] {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return e;
+    };
     if (!side_) {
         HIP_CHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&evSide_, hipEventDisableTiming));
+        evSide_ = newEvent();
     }
     if (!fwd_) {
         HIP_CHECK(hipStreamCreateWithFlags(&fwd_, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&evRhs_, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&evFwdDone_, hipEventDisableTiming));
+        evRhs_ = newEvent();
+        evFwdDone_ = newEvent();
     }
-    while ((int)evFactLevel_.size() < nLevels_) {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        evFactLevel_.push_back(e);
-    }
+    while ((int)evFactLevel_.size() < nLevels_) evFactLevel_.push_back(newEvent());
     while ((int)evLevel_.size() < nLevels_) {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        evLevel_.push_back(e);
-        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        evInvDone_.push_back(e);
+        evLevel_.push_back(newEvent());
+        evInvDone_.push_back(newEvent());
     }
     sidePending_ = false;
 
-    // A front whose nc own columns (plus the index maps of its children) fit into LDS takes the fused single-workgroup path;
-    // the others go through the level-batched multi-workgroup kernels.
-    size_t fusedLds = 64 * 1024;
-    // Fixed since round 6 (each was an environment switch while it was being measured; the sweeps are profiles/r05_knob_sweep*.txt, r05_two_level_blocking_ab.txt,
-    // r03r_schur_tile_ab.txt, r04_nd_leaf_size_ab.txt): levels with >= 512 Schur tiles of 32 x 32 take the 64 x 64 kernel (schur64Min_); levels whose step launches
-    // move >= 48 MB of own columns factor them in outer blocks of 256 columns (bulkMinMB_, bulkBlock_: members with these defaults -- the only two a caller can set,
-    // ipcgpu_linsys_set_tuning, because no mesh of the test suite reaches 48 MB and the path has to be forced to be tested; swept at 375 K nodes: 4, 16, 64 MB the
-    // same, factorisation 17.58 -> 16.9 ms; block 128 the same, 512 half the gain); 64 KB of LDS per fused front.
-    auto ldsOf = [&](int s) {
-        const size_t kids = (size_t)(sym.childPtr[s + 1] - sym.childPtr[s]);
-        return ((size_t)sym.nc(s) * sym.N(s) + 64) * sizeof(double) + kids * sym.N(s) * sizeof(int);
+    // plan, step 1: which front takes which kernel, the order inside the levels, the extend-add tiles, the cut of the tree between the ranks
+    auto planning = [](auto&& step) {
+        try {
+            step();
+        }
+        catch (const MfPlanError& e) {
+            throw StateError(e.what());
+        }
     };
-    const int ntSmallN = 0, ntBigN = 200;
-    // ... unless its level has fronts of the second kind anyway and only a few of the first (round 5): the single-workgroup kernel of such a level is a launch of
-    // its own IN FRONT of the level's batched kernels -- 57 us for the 93 widest fused fronts of level 4 of a 45 K-node sheet, one workgroup each at the limit of
-    // what LDS holds -- while as members of the batched launches the same fronts cost next to nothing (those launches are latency-bound and far from full).
-    // (profiles/r05_mixed_levels_ab_and_p2p_bytes.txt)
-    std::vector<char> fusedFront(ns_, 0);
-    {
-        const bool mixedOk = false;
-        std::vector<int> nFit(nLevels_, 0), nBigL(nLevels_, 0);
-        for (int s = 0; s < ns_; ++s) {
-            fusedFront[s] = sym.childPtr[s + 1] - sym.childPtr[s] <= FUSED_MAX_KIDS && ldsOf(s) <= fusedLds;
-            (fusedFront[s] ? nFit : nBigL)[sym.level[s]]++;
-        }
-        if (!mixedOk)
-            for (int s = 0; s < ns_; ++s) {
-                const int l = sym.level[s];
-                if (fusedFront[s] && nBigL[l] > 0 && nFit[l] <= std::max(64, nBigL[l])) fusedFront[s] = 0;
-            }
-    }
-    auto isFused = [&](int s) { return fusedFront[s] != 0; };
-    // explicit triangle inverses (see k_xinv_*): fronts of the multi-workgroup path with nc >= xinvMin
-    const int xinvMin = 192;
-    xinvBorder_ = true; // the inverse grows by bordering inside the step launches (step_border); false = recursive doubling on the side stream, as before round 4 (profiles/r05_permlane_and_border_ab.txt)
-#ifndef MF_BORDER_MAX_NC
-#define MF_BORDER_MAX_NC 1536 // (1024 until round 6: the 1 440-column root of the two-sheet contact stack keeps 0.17 ms of doubling rounds behind its factorisation, profiles/r06_border_max_nc_ab.txt)
-#endif
-    const int borderMaxNc = MF_BORDER_MAX_NC; // wider separators (a root of 2 600 columns at 1.12 M tets) keep the recursive doubling: a bordering workgroup is as long as the
-                            // front is wide, and at that width it stretches every step launch (measured at mat433: factorisation 20.0 -> 20.8 ms)
-    auto hasXinv = [&](int s) { return !isFused(s) && sym.nc(s) >= xinvMin; };
-    auto hasBorder = [&](int s) { return xinvBorder_ && hasXinv(s) && sym.nc(s) <= borderMaxNc; };
-    // ---- multi-GPU: cut the assembly tree below its top separators (see mf_numeric.h)
-    owner_.assign(ns_, rank_);
-    exec_.assign(ns_, rank_);
-    sharedFlops_ = 0.0;
-    if (world_ > 1) {
-        if (world_ > 64) throw StateError("the sharded solver supports at most 64 ranks");
-        sharedFlops_ = mf_assign_owners(sym, world_, owner_); // host logic, shared with the CPU tests of the protocol (mf_symbolic.cpp)
-        mf_assign_executors(sym, owner_, exec_, group_);
-        // exchange lists, by level (mf_exchange_plan: fronts whose parent another rank executes, solution segments of the fronts above the cut).  Every
-        // rank computes the same staging layout; it packs what it sends and unpacks what it receives.
-        std::vector<MfExchangeLevel> plan;
-        mf_exchange_plan(sym, owner_, exec_, group_, rank_, world_, plan);
-        xchg_.assign(nLevels_, Xchg());
-        std::vector<int4> xd;
-        long long maxCount = 1;
-        for (const MfExchangeLevel& E : plan) {
-            maxCount = std::max(maxCount, E.count + E.countW);
-            // the device descriptor of an update vector carries its offset (matrix area + offW) in ONE 32-bit word (k_xchg_w), the matrices' in two
-            if ((long long)E.count + (long long)E.countW > (long long)INT_MAX)
-                throw StateError("solver exchange: a level's staging area exceeds 2^31 doubles (the update-vector offsets are 32-bit)");
-        }
-        xchgBuf_.ensure((size_t)maxCount + 1);
-        for (int l = 0; l < nLevels_; ++l) {
-            Xchg& X = xchg_[l];
-            const MfExchangeLevel& E = plan[l];
-            X.count = E.count;
-            X.countW = E.countW;
-            auto emit = [&](const std::vector<MfExchangeItem>& items, Range& R, int sendFlag) {
-                R.off = (int)xd.size();
-                for (const MfExchangeItem& it : items) {
-                    xd.push_back(make_int4(it.front, (int)(unsigned)(it.off & 0xffffffffLL), (int)(it.off >> 32), (int)(E.count + it.offW))); // vectors sit behind the matrices
-                    const long long m = sym.N(it.front) - sym.nc(it.front);
-                    X.opsM.push_back(P2POp{ xchgBuf_.p + it.off, m * (m + 1) / 2, it.peer, sendFlag });
-                    X.opsW.push_back(P2POp{ xchgBuf_.p + E.count + it.offW, m, it.peer, sendFlag });
-                }
-                R.cnt = (int)xd.size() - R.off;
-            };
-            emit(E.send, X.pack, 1);
-            emit(E.recv, X.unpack, 0);
-            for (const MfExchangeItem& it : E.xsSend) X.opsX.push_back(P2POp{ xsol_.p + 3 * (long long)sym.firstNode[it.front], (long long)sym.nc(it.front), it.peer, 1 });
-            for (const MfExchangeItem& it : E.xsRecv) X.opsX.push_back(P2POp{ xsol_.p + 3 * (long long)sym.firstNode[it.front], (long long)sym.nc(it.front), it.peer, 0 });
-        }
-        if (xd.empty()) xd.push_back(make_int4(0, 0, 0, 0));
-        xchgDesc_.upload(xd.data(), xd.size(), stream);
-        std::vector<int> ne(std::max(sym.nn, 1), 0);
-        for (int s = 0; s < ns_; ++s)
-            for (int v = sym.firstNode[s]; v < sym.firstNode[s + 1]; ++v) ne[v] = exec_[s];
-        nodeExec_.upload(ne, stream);
-    }
-    auto mine = [&](int s) { return world_ == 1 || exec_[s] == rank_; };
-    // The fronts of every level in the order the plans below use them (heaviest first, so that the tail of a level is made of short jobs), the levels whose
-    // Schur kernel gathers the update block itself (k_big_schur64_ea: their extend-add only writes own columns), and the numbering of the extend-add tiles
-    // (64 x 64, lower triangle, front after front): the entries of A are sorted by the tile they land in, because the extend-add kernel adds them (round 5).
-    std::vector<std::vector<int>> smallByLevel(nLevels_), bigByLevel(nLevels_);
-    std::vector<char> levelFuseEA(nLevels_, 0);
-    std::vector<int> eaTileBase(ns_, -1), eaColTiles(ns_, 0); // first tile of a front; tiles kept per tile row: min(ti + 1, eaColTiles)
-    int nEaTiles = 0;
-    for (int l = 0; l < nLevels_; ++l) {
-        std::vector<int>&small = smallByLevel[l], &big = bigByLevel[l];
-        for (int i = sym.levelPtr[l]; i < sym.levelPtr[l + 1]; ++i) {
-            const int s = sym.levelFronts[i];
-            if (!mine(s)) continue; // factorised and solved by the rank that executes it
-            (isFused(s) ? small : big).push_back(s);
-        }
-        std::sort(small.begin(), small.end(), [&](int a, int b) { return sym.N(a) > sym.N(b) || (sym.N(a) == sym.N(b) && a < b); });
-        std::sort(big.begin(), big.end(), [&](int a, int b) { return sym.nc(a) > sym.nc(b) || (sym.nc(a) == sym.nc(b) && a < b); });
-        long long tiles32 = 0;
-        for (int s : big) {
-            const long long nt = (sym.N(s) - sym.nc(s) + TQ - 1) / TQ;
-            tiles32 += nt * (nt + 1) / 2;
-        }
-        levelFuseEA[l] = tiles32 >= schur64Min_;
-        for (int s : big) {
-            const int nt = (sym.N(s) + TS - 1) / TS;
-            eaColTiles[s] = levelFuseEA[l] ? (sym.nc(s) + TS - 1) / TS : nt;
-            eaTileBase[s] = nEaTiles;
-            for (int ti = 0; ti < nt; ++ti) nEaTiles += std::min(ti + 1, eaColTiles[s]);
-        }
-    }
-    auto eaTileOf = [&](int s, int ti, int tj) { // index of tile (ti, tj) of front s among the extend-add tiles
-        const int c = eaColTiles[s];
-        return eaTileBase[s] + (ti <= c ? ti * (ti + 1) / 2 : c * (c + 1) / 2 + (ti - c) * c) + tj;
-    };
+    mp_.rank = rank_;
+    mp_.world = world_;
+    mp_.tune = tune_;
+    planning([&] { mf_plan_fronts(sym, mp_); });
+    dinvOff_.upload(mp_.dinvOff, stream);
+    dinv_.alloc((size_t)mp_.dinvOff[ns_] * NB * NB);
     // entries of A grouped by where they go: (source index, offset inside the LDS panel) for the single-workgroup fronts, per front; (source index, offset in
     // the front buffer) for the others, per extend-add tile -- computed and sorted on the device from the pattern in HBM (k_entry_dst, k_scan_exclusive,
     // k_entry_scatter above).  What comes back to the host: the bucket starts (the packed descriptors of the single-workgroup fronts carry their entry range).
-    {
-        const size_t nnz = (size_t)nnzPattern;
-        const int nBuckets = ns_ + nEaTiles;
-        std::vector<int4> info(std::max(ns_, 1));
-        for (int s = 0; s < ns_; ++s) info[s] = make_int4(!mine(s) ? -1 : (isFused(s) ? 0 : 1), eaTileBase[s], eaColTiles[s], 0);
-        std::vector<int> nodeFront(std::max(sym.nn, 1));
-        for (int s = 0; s < ns_; ++s)
-            for (int v = sym.firstNode[s]; v < sym.firstNode[s + 1]; ++v) nodeFront[v] = s;
-        frontInfo_.upload(info.data(), info.size(), stream);
-        nodeFront_.upload(nodeFront, stream);
-        entryDst_.ensure(nnz + 1);
-        entryBucket_.ensure(nnz + 1);
-        bucketHist_.ensure(2 * (size_t)nBuckets + 2); // counts, then the tickets of the scatter
-        bucketStart_.ensure((size_t)nBuckets + 2);
-        bucketHist_.zeroN(2 * (size_t)nBuckets + 2, stream);
-        EntryView ev{ ia_dev, ja_dev, sym.n, ns_, newOf_.p, nodeFront_.p, firstNode_.p, idxPtr_.p, idx_.p, frontOff_.p, frontInfo_.p };
-        hipLaunchKernelGGL(k_entry_dst, dim3((sym.n + 3) / 4), dim3(256), 0, stream, ev, entryDst_.p, entryBucket_.p, bucketHist_.p);
-        hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, nBuckets, bucketHist_.p, bucketStart_.p);
-        std::vector<int> start((size_t)nBuckets + 1);
-        bucketStart_.download(start.data(), start.size(), stream); // (synchronises)
-        const size_t nFused = (size_t)start[ns_], nBig = (size_t)(start[nBuckets] - start[ns_]);
-        aPtrHost_.assign(start.begin(), start.begin() + ns_ + 1);
-        nFusedA_ = (int)nFused;
-        aPerm_.ensure(std::max<size_t>(nFused, 1));
-        aSrc_.ensure(nFused + 1);
-        aLoc_.ensure(nFused + 1);
-        bigASrc_.ensure(nBig + 1);
-        bigADst_.ensure(nBig + 1);
-        if (nnz)
-            hipLaunchKernelGGL(k_entry_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, (int)nnz, ns_, entryDst_.p, entryBucket_.p, bucketStart_.p,
-                bucketHist_.p + nBuckets + 1, frontOff_.p, aSrc_.p, aLoc_.p, bigASrc_.p, bigADst_.p);
-        std::vector<int> eaPtr((size_t)nEaTiles + 1);
-        for (int t = 0; t <= nEaTiles; ++t) eaPtr[t] = start[ns_ + t] - start[ns_];
-        eaAPtr_.upload(eaPtr, stream); // per extend-add tile: its range in bigASrc_ / bigADst_
-    }
+    const size_t nnz = (size_t)nnzPattern;
+    const int nBuckets = ns_ + mp_.nEaTiles;
+    uploadRecs(frontInfo_, mp_.frontInfo, stream);
+    nodeFront_.upload(mp_.nodeFront, stream);
+    entryDst_.ensure(nnz + 1);
+    entryBucket_.ensure(nnz + 1);
+    bucketHist_.ensure(2 * (size_t)nBuckets + 2); // counts, then the tickets of the scatter
+    bucketStart_.ensure((size_t)nBuckets + 2);
+    bucketHist_.zeroN(2 * (size_t)nBuckets + 2, stream);
+    EntryView ev{ ia_dev, ja_dev, sym.n, ns_, newOf_.p, nodeFront_.p, firstNode_.p, idxPtr_.p, idx_.p, frontOff_.p, frontInfo_.p };
+    hipLaunchKernelGGL(k_entry_dst, dim3((sym.n + 3) / 4), dim3(256), 0, stream, ev, entryDst_.p, entryBucket_.p, bucketHist_.p);
+    hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, nBuckets, bucketHist_.p, bucketStart_.p);
+    std::vector<int> start((size_t)nBuckets + 1);
+    bucketStart_.download(start.data(), start.size(), stream); // (synchronises)
+    const size_t nFused = (size_t)start[ns_], nBig = (size_t)(start[nBuckets] - start[ns_]);
+    nFusedA_ = (int)nFused;
+    aPerm_.ensure(std::max<size_t>(nFused, 1));
+    aSrc_.ensure(nFused + 1);
+    aLoc_.ensure(nFused + 1);
+    bigASrc_.ensure(nBig + 1);
+    bigADst_.ensure(nBig + 1);
+    if (nnz)
+        hipLaunchKernelGGL(k_entry_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, (int)nnz, ns_, entryDst_.p, entryBucket_.p, bucketStart_.p,
+            bucketHist_.p + nBuckets + 1, frontOff_.p, aSrc_.p, aLoc_.p, bigASrc_.p, bigADst_.p);
     lap("A-entry lists");
-    plan_.assign(nLevels_, LevelPlan());
-    std::vector<int> smallList, bigList;
-    std::vector<int4> ea;
-    std::vector<int> bigFd; // packed records of the fronts of the multi-workgroup path (k_extend_add)
-    std::vector<int> eaRecOf(ns_, -1); // front -> its first record
-    std::vector<int4> desc;
-    size_t maxSmallLds = 0, maxSolveLds = 0, maxTriLds = 0, maxBwdLds = 0;
-    for (int l = 0; l < nLevels_; ++l) {
-        LevelPlan& P = plan_[l];
-        const std::vector<int>&small = smallByLevel[l], &big = bigByLevel[l];
-        P.small.off = (int)smallList.size();
-        P.small.cnt = (int)small.size();
-        int maxN = 0, maxNc = 0;
-        for (int s : small) maxN = std::max(maxN, sym.N(s));
-        for (int s : big) maxNc = std::max(maxNc, sym.nc(s));
-        smallList.insert(smallList.end(), small.begin(), small.end());
-        P.bigFronts.off = (int)bigList.size();
-        P.bigFronts.cnt = (int)big.size();
-        bigList.insert(bigList.end(), big.begin(), big.end());
-        P.smallLds = 0;
-        for (int s : small) P.smallLds = std::max(P.smallLds, ldsOf(s));
-        // narrow fronts: two waves per workgroup, twice as many workgroups per CU (every phase of the kernel is latency-bound)
-        P.smallThreads = (maxN <= ntSmallN) ? 128 : (maxN >= ntBigN ? 512 : 256); // wide fronts: one workgroup per CU anyway (LDS)
-        P.solveLds = (size_t)std::max(maxN, 1) * sizeof(double);
-        P.triLds = (size_t)std::max(maxNc, 1) * sizeof(double);
-        {
-            int maxBelow = 1;
-            for (int s : big) maxBelow = std::max(maxBelow, sym.N(s) - sym.nc(s));
-            P.bwdLds = (size_t)maxBelow * sizeof(double);
-            maxBwdLds = std::max(maxBwdLds, P.bwdLds);
-        }
-        maxSmallLds = std::max(maxSmallLds, P.smallLds);
-        maxSolveLds = std::max(maxSolveLds, P.solveLds);
-        maxTriLds = std::max(maxTriLds, P.triLds);
-        // extend-add descriptors: lower-triangular 64 x 64 tiles of the parent, each pointing at the parent's packed record
-        P.ea.off = (int)ea.size();
-        P.schur64 = P.fuseEA = levelFuseEA[l] != 0; // (decided above: it thins out the extend-add's tiles and numbers them)
-        for (int s : big) { // every lower-triangle tile is written (children sums or zeros): the fronts are never zero-filled
-            const int first = (int)(bigFd.size() / FD_STRIDE);
-            eaRecOf[s] = first;
-            const int nkAll = sym.childPtr[s + 1] - sym.childPtr[s];
-            for (int k0 = 0; k0 == 0 || k0 < nkAll; k0 += FUSED_MAX_KIDS) {
-                const size_t base = bigFd.size();
-                bigFd.resize(base + FD_STRIDE, 0);
-                int* d = bigFd.data() + base;
-                const long long off = sym.frontOff[s];
-                std::memcpy(d, &off, 8);
-                d[2] = sym.N(s);
-                d[3] = sym.nc(s);
-                const int nk = std::min(FUSED_MAX_KIDS, nkAll - k0);
-                d[8] = std::max(nk, 0);
-                d[9] = (k0 + FUSED_MAX_KIDS < nkAll) ? (int)(base / FD_STRIDE) + 1 : -1;
-                for (int q = 0; q < nk; ++q) {
-                    const int c = sym.child[sym.childPtr[s] + k0 + q];
-                    int* k = d + 16 + 6 * q;
-                    const long long coff = sym.frontOff[c];
-                    std::memcpy(k, &coff, 8);
-                    k[2] = sym.N(c);
-                    k[3] = sym.nc(c);
-                    k[4] = sym.invPtr[c];
-                }
-            }
-            const int nt = (sym.N(s) + TS - 1) / TS;
-            for (int ti = 0; ti < nt; ++ti)
-                for (int tj = 0; tj <= ti; ++tj) {
-                    if (P.fuseEA && TS * tj >= sym.nc(s)) continue; // a tile of the update block alone: the Schur kernel's
-                    if ((int)ea.size() != eaTileOf(s, ti, tj)) throw StateError("internal: extend-add tiles are not numbered in emission order");
-                    ea.push_back(make_int4(first, ti, tj, eaTileOf(s, ti, tj)));
-                }
-        }
-        P.ea.cnt = (int)ea.size() - P.ea.off;
-        // big-front step descriptors: launch 0 factors panel 0, launch j + 1 applies panel j and factors panel j + 1
-        int steps = 0;
-        for (int s : big) steps = std::max(steps, (sym.nc(s) + NB - 1) / NB);
-        P.step.assign(big.empty() ? 0 : steps + 1, Range());
-        P.bulk.assign(P.step.size(), Range());
-        // two-level blocking (k_big_bulk) for the fronts of this level?  What a step launch's rank-32 update reads and writes: the own columns of every front, all rows
-        const int OBW = bulkBlock_;
-        double stepMB = 0.0;
-        for (int s : big) stepMB += 8.0e-6 * (double)sym.N(s) * sym.nc(s);
-        const bool levelWide = stepMB >= bulkMinMB_;
-        for (int j = -1; j < steps && !big.empty(); ++j) {
-            Range& R = P.step[j + 1];
-            R.off = (int)desc.size();
-            for (int s : big) {
-                const int N = sym.N(s), nc = sym.nc(s);
-                const int kb = j * NB;
-                if (j >= 0 && kb >= nc) continue;
-                const int w = (j >= 0) ? std::min(NB, nc - kb) : 0;
-                const int kb1 = (j >= 0) ? kb + w : 0;
-                const int w1 = (kb1 < nc) ? std::min(NB, nc - kb1) : 0;
-                const long long foff = sym.frontOff[s];
-                const int4 rec2 = make_int4(N, nc, (int)(unsigned)(foff & 0xffffffffll), (int)(unsigned)(foff >> 32));
-                // wide fronts (two-level blocking, k_big_bulk): E = the end of the outer block panel kb belongs to; when the next panel opens a new block, the
-                // bulk update launched in front of this step has applied panel kb already
-                const bool wide = levelWide && nc >= 2 * OBW;
-                const int E = (wide && j >= 0) ? std::min(nc, (kb / OBW + 1) * OBW) : nc;
-                const bool applied = wide && j >= 0 && kb1 >= E && kb1 < nc;
-                if (w1 > 0)
-                    for (int r0 = 0; r0 < N - kb1; r0 += ROWS_B) {
-                        desc.push_back(make_int4((int)hDinvOff_[s], j < 0 ? -1 : (applied ? -2 - kb1 : kb), r0, -2));
-                        desc.push_back(rec2);
-                    }
-                if (j >= 0 && hasBorder(s)) { // role C: the rows of panel j of X = L11^-1, one workgroup per column tile up to the diagonal block
-                    P.stepTop = true;
-                    // 16-column tiles (32 wide ones made the late steps of the root 20 us long: one CU per tile, k up to nc); c0 == kb: the diagonal block, one copy
-                    for (int c0 = 0; c0 <= kb; c0 += 16) {
-                        desc.push_back(make_int4(s, kb, c0, -6));
-                        desc.push_back(rec2);
-                    }
-                }
-                if (j >= 0 && !applied) {
-                    // trailing tiles inside the front's own columns (of a wide front: inside the panel's outer block -- the records carry E in place of nc, which is
-                    // all role A reads nc for); the Schur complement (columns >= nc) waits for k_big_schur
-                    const int M0 = kb1 + w1;
-                    const int ntr = (N - M0 + TS - 1) / TS, ntc = (E - M0 + TS - 1) / TS;
-                    const int4 recA = make_int4(N, E, rec2.z, rec2.w);
-                    for (int ti = 0; ti < ntr; ++ti)
-                        for (int tj = 0; tj <= ti && tj < ntc; ++tj) {
-                            desc.push_back(make_int4((int)hDinvOff_[s], kb, ti, tj));
-                            desc.push_back(recA);
-                        }
-                }
-            }
-            R.cnt = ((int)desc.size() - R.off) / 2; // workgroups: two records each
-            // the bulk updates that have to run BEHIND this launch (it factored panel j + 1): of every wide front whose outer block ends with that panel
-            Range& U = P.bulk[j + 1];
-            U.off = (int)desc.size();
-            for (int s : big) {
-                const int N = sym.N(s), nc = sym.nc(s);
-                const int p0 = (j + 1) * NB, Eb = p0 + NB; // the panel just factored and its end
-                if (!levelWide || nc < 2 * OBW || Eb % OBW != 0 || Eb >= nc) continue;
-                const long long foff = sym.frontOff[s];
-                const int4 rec2 = make_int4(N, nc, (int)(unsigned)(foff & 0xffffffffll), (int)(unsigned)(foff >> 32));
-                const int ntr = (N - Eb + TQ64 - 1) / TQ64, ntc = (nc - Eb + TQ64 - 1) / TQ64;
-                for (int ti = 0; ti < ntr; ++ti)
-                    for (int tj = 0; tj <= ti && tj < ntc; ++tj) {
-                        desc.push_back(make_int4(OBW, Eb - OBW, ti, tj));
-                        desc.push_back(rec2);
-                    }
-            }
-            U.cnt = ((int)desc.size() - U.off) / 2;
-        }
-        // Schur complement: one pass behind the chain (k_big_schur / k_big_schur64 / k_big_schur64_ea).
-        // XCD-aware order (round 5): workgroup b of a launch runs on XCD b % 8 (observed, MI355X_MICROARCH.md; a speed assumption only -- any placement is
-        // correct) and every XCD has its own 4 MB L2.  In front-after-front order the tiles of one front land on all eight XCDs, so each L2 sees the factor
-        // panels L21 of ALL fronts of the level (25 MB on the 64-front level of a 45 K-node sheet) and every operand load is an L2 miss.  Here the tile rows of
-        // a front form groups of about total / 8 tiles, the groups are dealt to eight bins (largest first onto the least loaded bin) and slot b of the
-        // launch takes the next tile of bin b % 8: an XCD works through whole fronts and reads their panels from memory once.
-        P.schur.off = (int)desc.size();
-        {
-            const int TQl = P.schur64 ? TQ64 : TQ;
-            struct Tile {
-                int4 a, b;
-            };
-            std::vector<std::vector<Tile>> groups;
-            long long total = 0;
-            for (int s : big) {
-                const long long nt = (sym.N(s) - sym.nc(s) + TQl - 1) / TQl;
-                total += nt * (nt + 1) / 2;
-            }
-            const long long target = std::max<long long>(1, (total + XCDS - 1) / XCDS);
-            for (int s : big) {
-                const int nt = (sym.N(s) - sym.nc(s) + TQl - 1) / TQl;
-                const long long foff = sym.frontOff[s];
-                const int4 rec2 = make_int4(sym.N(s), sym.nc(s), (int)(unsigned)(foff & 0xffffffffll), (int)(unsigned)(foff >> 32));
-                groups.emplace_back();
-                for (int ti = 0; ti < nt; ++ti) {
-                    if (xcdOrder_ && (long long)groups.back().size() + ti + 1 > target && !groups.back().empty()) groups.emplace_back(); // next row range of a front too large for one bin
-                    for (int tj = 0; tj <= ti; ++tj) groups.back().push_back(Tile{ make_int4(s, ti, tj, P.fuseEA ? eaRecOf[s] : 0), rec2 });
-                }
-            }
-            if (!xcdOrder_) {
-                for (const auto& g : groups)
-                    for (const Tile& t : g) {
-                        desc.push_back(t.a);
-                        desc.push_back(t.b);
-                    }
-            }
-            else {
-                std::vector<int> order(groups.size());
-                for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return groups[a].size() > groups[b].size(); });
-                std::vector<std::vector<Tile>> bins(XCDS);
-                for (int g : order) {
-                    int best = 0;
-                    for (int x = 1; x < XCDS; ++x)
-                        if (bins[x].size() < bins[best].size()) best = x;
-                    bins[best].insert(bins[best].end(), groups[g].begin(), groups[g].end());
-                }
-                std::vector<size_t> head(XCDS, 0), tail(XCDS);
-                for (int x = 0; x < XCDS; ++x) tail[x] = bins[x].size();
-                for (long long left = total; left > 0;)
-                    for (int x = 0; x < XCDS && left > 0; ++x, --left) {
-                        int from = x;
-                        if (head[x] >= tail[x]) { // this bin has run dry: take from the END of the fullest one (its head keeps its order)
-                            for (int y = 0; y < XCDS; ++y)
-                                if (tail[y] - head[y] > tail[from] - head[from]) from = y;
-                        }
-                        const Tile& t = (from == x) ? bins[x][head[x]++] : bins[from][--tail[from]];
-                        desc.push_back(t.a);
-                        desc.push_back(t.b);
-                    }
-            }
-        }
-        P.schur.cnt = ((int)desc.size() - P.schur.off) / 2; // workgroups: two records each
-        P.fwdRect.off = (int)desc.size();
-        for (int s : big)
-            for (int r0 = 0; r0 < sym.N(s) - sym.nc(s); r0 += MV_ROWS) desc.push_back(make_int4(s, r0, 0, 0));
-        P.fwdRect.cnt = (int)desc.size() - P.fwdRect.off;
-        P.bwdInit.off = (int)desc.size();
-        for (int s : big)
-            if (sym.N(s) > sym.nc(s))
-                for (int c0 = 0; c0 < sym.nc(s); c0 += 16) desc.push_back(make_int4(s, c0, 0, 0));
-        P.bwdInit.cnt = (int)desc.size() - P.bwdInit.off;
-    }
+    // plan, step 2 (beside the scatter kernel): every descriptor of the factorisation and of the sweeps
+    planning([&] { mf_plan_launches(sym, start.data(), mp_); });
     lap("level plans");
-    {
-        // packed descriptors of the fused fronts, in launch order
-        std::vector<int> fd((std::max<size_t>(smallList.size(), 1)) * FD_STRIDE, 0);
-        std::vector<long long> di(ns_ + 1, 0);
-        for (int s = 0; s < ns_; ++s) di[s + 1] = di[s] + (sym.nc(s) + NB - 1) / NB;
-        for (size_t i = 0; i < smallList.size(); ++i) {
-            const int s = smallList[i];
-            int* d = fd.data() + i * FD_STRIDE;
-            const long long off = sym.frontOff[s];
-            std::memcpy(d, &off, 8);
-            d[2] = sym.N(s);
-            d[3] = sym.nc(s);
-            std::memcpy(d + 4, &di[s], 8);
-            d[6] = aPtrHost_[s];
-            d[7] = aPtrHost_[s + 1];
-            const int nk = sym.childPtr[s + 1] - sym.childPtr[s];
-            d[8] = nk;
-            for (int q = 0; q < nk; ++q) {
-                const int c = sym.child[sym.childPtr[s] + q];
-                int* k = d + 16 + 6 * q;
-                const long long coff = sym.frontOff[c];
-                std::memcpy(k, &coff, 8);
-                k[2] = sym.N(c);
-                k[3] = sym.nc(c);
-                k[4] = sym.invPtr[c];
-            }
-        }
-        fdesc_.uploadGrow(fd, stream);
-    }
+    eaAPtr_.upload(mp_.eaAPtr, stream); // per extend-add tile: its range in bigASrc_ / bigADst_
+    fdesc_.uploadGrow(mp_.fdesc, stream);
     lap("fused descriptors");
-    {
-        std::vector<long long> xOff(ns_, -1);
-        long long xTot = 0;
-        std::vector<int4> xd; // all descriptors of the inverse machinery
-        std::vector<int> invFronts;
-        size_t maxInvNc = 0;
-        for (int l = 0; l < nLevels_; ++l)
-            for (int i = plan_[l].bigFronts.off; i < plan_[l].bigFronts.off + plan_[l].bigFronts.cnt; ++i) {
-                const int s = bigList[i];
-                if (!hasXinv(s)) continue;
-                xOff[s] = xTot;
-                xTot += (long long)sym.nc(s) * sym.nc(s);
-                invFronts.push_back(s);
-                maxInvNc = std::max<size_t>(maxInvNc, sym.nc(s));
-            }
-        // per level (the inverses of a level are formed on a side stream while the levels above factorise): the diagonal
-        // blocks to invert, the copies into X and the doubling rounds
-        std::vector<int> blockList;
-        std::vector<long long> di(ns_ + 1, 0);
-        for (int s = 0; s < ns_; ++s) di[s + 1] = di[s] + (sym.nc(s) + NB - 1) / NB;
-        xinvLevel_.assign(nLevels_, XinvLevel());
-        for (int l = 0; l < nLevels_; ++l) {
-            XinvLevel& XL = xinvLevel_[l];
-            std::vector<int> lf;
-            for (int s : invFronts)
-                if (sym.level[s] == l) lf.push_back(s);
-            XL.blocks.off = (int)blockList.size();
-            XL.init.off = (int)xd.size();
-            lf.erase(std::remove_if(lf.begin(), lf.end(), [&](int s) { return hasBorder(s); }), lf.end()); // the step launches build those inverses (step_border)
-            for (int s : lf)
-                for (int b = 0; b < (sym.nc(s) + NB - 1) / NB; ++b) {
-                    blockList.push_back((int)(di[s] + b));
-                    xd.push_back(make_int4(s, b, 0, 0));
-                }
-            XL.blocks.cnt = (int)blockList.size() - XL.blocks.off;
-            XL.init.cnt = (int)xd.size() - XL.init.off;
-            if ((xd.size() & 1) != 0) xd.push_back(make_int4(0, 0, 0, 0)); // GEMM descriptors are pairs: keep them pair-aligned
-            int lvlMax = 0;
-            for (int s : lf) lvlMax = std::max(lvlMax, sym.nc(s));
-            for (int sz = NB; sz < lvlMax; sz *= 2) {
-                // pairs (A, C) of this doubling: A = [2 p sz, 2 p sz + sz), C = [2 p sz + sz, min(2 p sz + 2 sz, nc))
-                Range g1, g2;
-                for (int mode = 1; mode <= 2; ++mode) {
-                    Range& g = (mode == 1) ? g1 : g2;
-                    g.off = (int)xd.size() / 2;
-                    for (int s : lf) {
-                        const int nc = sym.nc(s);
-                        for (int a0 = 0; a0 + sz < nc; a0 += 2 * sz) {
-                            const int c0 = a0 + sz, cEnd = std::min(a0 + 2 * sz, nc);
-                            for (int r = c0; r < cEnd; r += 32)
-                                for (int c = a0; c < a0 + sz; c += 32) {
-                                    xd.push_back(make_int4(s, r, c, mode));
-                                    // mode 1 sums over the columns of A, mode 2 over the rows of C
-                                    xd.push_back(mode == 1 ? make_int4(cEnd, a0 + sz, a0, a0 + sz) : make_int4(cEnd, a0 + sz, c0, cEnd));
-                                }
-                        }
-                    }
-                    g.cnt = (int)xd.size() / 2 - g.off;
-                }
-                XL.rounds.push_back({ g1, g2 });
-            }
-        }
-        // solve: per level the fronts swept by one workgroup (no inverse) and the row / column blocks of the others
-        std::vector<int> triList;
-        for (int l = 0; l < nLevels_; ++l) {
-            LevelPlan& P = plan_[l];
-            P.bigTri.off = (int)triList.size();
-            size_t triMax = 1;
-            std::vector<int4> fw, bw;
-            for (int i = P.bigFronts.off; i < P.bigFronts.off + P.bigFronts.cnt; ++i) {
-                const int s = bigList[i];
-                if (xOff[s] < 0) {
-                    triList.push_back(s);
-                    triMax = std::max<size_t>(triMax, sym.nc(s));
-                    continue;
-                }
-                for (int r0 = 0; r0 < sym.nc(s); r0 += MV_ROWS) fw.push_back(make_int4(s, r0, 0, 0));
-                for (int c0 = 0; c0 < sym.nc(s); c0 += 16) bw.push_back(make_int4(s, c0, 0, 0));
-            }
-            P.bigTri.cnt = (int)triList.size() - P.bigTri.off;
-            P.triLds = triMax * sizeof(double);
-            if ((xd.size() & 1) != 0) xd.push_back(make_int4(0, 0, 0, 0));
-            P.xinvFwd.off = (int)xd.size();
-            xd.insert(xd.end(), fw.begin(), fw.end());
-            P.xinvFwd.cnt = (int)fw.size();
-            P.xinvBwd.off = (int)xd.size();
-            xd.insert(xd.end(), bw.begin(), bw.end());
-            P.xinvBwd.cnt = (int)bw.size();
-        }
-        maxTriLds = 0;
-        for (int l = 0; l < nLevels_; ++l) maxTriLds = std::max(maxTriLds, plan_[l].triLds);
-        xinvLds_ = std::max<size_t>(maxInvNc, 1) * sizeof(double);
-        if (xinvLds_ > 150 * 1024) throw StateError("a separator front is too wide for the inverse-based triangular solve");
-        if (triList.empty()) triList.push_back(0);
-        triList_.upload(triList, stream);
-        if (xd.empty()) xd.push_back(make_int4(0, 0, 0, 0));
-        xinvDesc_.upload(xd.data(), xd.size(), stream);
-        xinvOff_.upload(xOff.empty() ? std::vector<long long>{ -1 } : xOff, stream);
-        xinvX_.alloc((size_t)std::max<long long>(xTot, 1));
-        xinvT_.alloc((size_t)std::max<long long>(xTot, 1));
-        xinvX_.zero(stream);
-        xinvT_.zero(stream);
-    }
+    triList_.upload(mp_.triList, stream);
+    uploadRecs(xinvDesc_, mp_.xinvDesc, stream);
+    xinvOff_.upload(mp_.xinvOff, stream);
+    xinvX_.alloc((size_t)std::max<long long>(mp_.xTot, 1));
+    xinvT_.alloc((size_t)std::max<long long>(mp_.xTot, 1));
+    xinvX_.zero(stream);
+    xinvT_.zero(stream);
     lap("inverse plan + buffers");
-    if (smallList.empty()) smallList.push_back(0);
-    smallList_.upload(smallList, stream);
-    if (bigList.empty()) bigList.push_back(0);
-    bigList_.upload(bigList, stream);
-    if (ea.empty()) ea.push_back(make_int4(0, 0, 0, 0));
-    eaDesc_.upload(ea.data(), ea.size(), stream);
-    if (bigFd.empty()) bigFd.resize(FD_STRIDE, 0);
-    bigFd_.uploadGrow(bigFd, stream);
-    if (desc.empty()) desc.push_back(make_int4(0, 0, 0, 0));
-    desc_.upload(desc.data(), desc.size(), stream);
-    if (maxSmallLds > 48 * 1024)
-    {
-        HIP_CHECK(hipFuncSetAttribute((const void*)k_front_fused<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxSmallLds));
-        HIP_CHECK(hipFuncSetAttribute((const void*)k_front_fused<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxSmallLds));
-        HIP_CHECK(hipFuncSetAttribute((const void*)k_front_fused<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxSmallLds));
+    smallList_.upload(mp_.smallList, stream);
+    bigList_.upload(mp_.bigList, stream);
+    uploadRecs(eaDesc_, mp_.ea, stream);
+    bigFd_.uploadGrow(mp_.bigFd, stream);
+    uploadRecs(desc_, mp_.desc, stream);
+    if (world_ > 1) { // the exchange groups: the plan's offsets into the staging buffer and the solution vector become pointers
+        xchgBuf_.ensure((size_t)mp_.xchgStaging + 1);
+        uploadRecs(xchgDesc_, mp_.xchgDesc, stream);
+        nodeExec_.upload(mp_.nodeExec, stream);
+        auto resolve = [](const std::vector<MfXchgOp>& ops, double* base, std::vector<P2POp>& out) {
+            for (const MfXchgOp& o : ops) out.push_back(P2POp{ base + o.off, o.count, o.peer, o.send });
+        };
+        xchg_.assign(nLevels_, Xchg());
+        for (int l = 0; l < nLevels_; ++l) {
+            resolve(mp_.xchg[l].opsM, xchgBuf_.p, xchg_[l].opsM);
+            resolve(mp_.xchg[l].opsW, xchgBuf_.p, xchg_[l].opsW);
+            resolve(mp_.xchg[l].opsX, xsol_.p, xchg_[l].opsX);
+        }
     }
-    configureSweepKernels(maxSolveLds, maxBwdLds, maxTriLds); // the dynamic-LDS limits of the sweep kernels (mf_sweeps.hip)
+    if (mp_.maxSmallLds > 48 * 1024) {
+        HIP_CHECK(hipFuncSetAttribute((const void*)k_front_fused<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp_.maxSmallLds));
+        HIP_CHECK(hipFuncSetAttribute((const void*)k_front_fused<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp_.maxSmallLds));
+    }
+    configureSweepKernels(mp_.maxSolveLds, mp_.maxBwdLds, mp_.maxTriLds); // the dynamic-LDS limits of the sweep kernels (mf_sweeps.hip)
     HIP_CHECK(hipStreamSynchronize(stream));
     lap("uploads + attributes");
 }
@@ -2145,7 +1685,7 @@ void MfNumeric::nodeOwners(std::vector<int>& ownerOfNode) const
     if (world_ <= 1) return;
     std::vector<int> perm(sym.nn, -1); // owner per permuted node
     for (int s = 0; s < ns_; ++s)
-        for (int v = sym.firstNode[s]; v < sym.firstNode[s + 1]; ++v) perm[v] = owner_[s];
+        for (int v = sym.firstNode[s]; v < sym.firstNode[s + 1]; ++v) perm[v] = mp_.owner[s];
     for (int v = 0; v < sym.nn; ++v) ownerOfNode[v] = perm[sym.newOf[v]];
 }
 
@@ -2181,7 +1721,7 @@ bool MfNumeric::factorize(const double* a_dev)
             HIP_CHECK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_probe), h.size() * sizeof(unsigned long long)));
             const char* names[7] = { "maps", "children", "A", "panels", "store", "schur", "total" };
             for (int l = 0; l < nLevels_; ++l) {
-                const LevelPlan& P = plan_[l];
+                const LevelPlan& P = mp_.level[l];
                 if (!P.small.cnt) continue;
                 double sum[16] = { 0 }, mx = 0;
                 for (int b = 0; b < P.small.cnt; ++b) {
@@ -2250,14 +1790,11 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
     if (nFusedA_) hipLaunchKernelGGL(k_gather_a, dim3((nFusedA_ + 255) / 256), dim3(256), 0, stream_, nFusedA_, aSrc_.p, a_dev, aPerm_.p, flag_.p);
     else flag_.zero(stream_);
     for (int l = 0; l < nLevels_; ++l) {
-        const LevelPlan& P = plan_[l];
+        const LevelPlan& P = mp_.level[l];
         if (P.small.cnt)
         {
             const int* fd = fdesc_.p + (size_t)P.small.off * FD_STRIDE;
-            if (P.smallThreads == 128)
-                hipLaunchKernelGGL(k_front_fused<128>, dim3(P.small.cnt), dim3(128), P.smallLds, stream_, fd, inv_.p, aLoc_.p, aPerm_.p, fronts_.p,
-                    dinv_.p, flag_.p);
-            else if (P.smallThreads == 512)
+            if (P.smallThreads == 512)
                 hipLaunchKernelGGL(k_front_fused<512>, dim3(P.small.cnt), dim3(512), P.smallLds, stream_, fd, inv_.p, aLoc_.p, aPerm_.p, fronts_.p,
                     dinv_.p, flag_.p);
             else
@@ -2281,7 +1818,7 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
             else hipLaunchKernelGGL(k_big_schur, dim3(P.schur.cnt), dim3(WG), 0, stream_, desc_.p + P.schur.off, fronts_.p);
         }
         if (world_ > 1) exchangeUpdateMatrices(l); // update matrices whose parent front another rank executes (mf_exchange.hip)
-        if (xinvLevel_[l].blocks.cnt) {
+        if (mp_.xinvLevel[l].blocks.cnt) {
             // the factor panels and pivot blocks of this level are final: form the triangle inverses of its fronts beside the
             // latency-bound chain of the levels above
             if (side_) {
@@ -2312,7 +1849,7 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
                 HIP_CHECK(hipEventRecord(evFactLevel_[l], stream_));
                 HIP_CHECK(hipStreamWaitEvent(fwd_, evFactLevel_[l], 0));
                 for (; fwdNext <= l; ++fwdNext) {
-                    if (plan_[fwdNext].xinvFwd.cnt && sideUsed) HIP_CHECK(hipStreamWaitEvent(fwd_, evInvDone_[fwdNext], 0));
+                    if (mp_.level[fwdNext].xinvFwd.cnt && sideUsed) HIP_CHECK(hipStreamWaitEvent(fwd_, evInvDone_[fwdNext], 0));
                     enqueueForwardLevel(fwdNext, fwd_);
                 }
             }
@@ -2327,7 +1864,7 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
 // X = L11^-1 of the fronts of one level (see k_xinv_*), enqueued on `st`
 void MfNumeric::enqueueInverses(int l, hipStream_t st)
 {
-    const XinvLevel& XL = xinvLevel_[l];
+    const XinvLevel& XL = mp_.xinvLevel[l];
     TreeView tv{ frontOff_.p, idxPtr_.p, firstNode_.p, childPtr_.p, child_.p, invPtr_.p, inv_.p, idx_.p, dinvOff_.p };
     XinvView xv{ xinvOff_.p, xinvX_.p, xinvT_.p };
     hipLaunchKernelGGL(k_xinv_init, dim3(XL.init.cnt), dim3(256), 0, st, xinvDesc_.p + XL.init.off, tv, xv, dinv_.p);

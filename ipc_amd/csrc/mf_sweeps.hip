@@ -495,9 +495,9 @@ __global__ __launch_bounds__(WG) void k_xinv_bwd(const int4* __restrict__ desc, 
 // the dynamic-LDS limits of the sweep kernels (called by setup(), which knows the widest front of every kind)
 void MfNumeric::configureSweepKernels(size_t maxSolveLds, size_t maxBwdLds, size_t maxTriLds)
 {
-    if (xinvLds_ > 48 * 1024) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)k_xinv_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xinvLds_));
-        HIP_CHECK(hipFuncSetAttribute((const void*)k_xinv_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xinvLds_));
+    if (mp_.xinvLds > 48 * 1024) {
+        HIP_CHECK(hipFuncSetAttribute((const void*)k_xinv_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp_.xinvLds));
+        HIP_CHECK(hipFuncSetAttribute((const void*)k_xinv_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp_.xinvLds));
     }
     if (maxSolveLds > 48 * 1024) {
         HIP_CHECK(hipFuncSetAttribute((const void*)k_fwd_level<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxSolveLds));
@@ -533,7 +533,7 @@ void MfNumeric::enqueueSolve(const double* rhs_dev, double* x_dev)
     // workgroups of the same launch still gather right-hand-side entries
     enqueuePermuteRhs(rhs_dev, stream_);
     for (int l = 0; l < nLevels_; ++l) {
-        const LevelPlan& P = plan_[l];
+        const LevelPlan& P = mp_.level[l];
         if (P.xinvFwd.cnt && sidePending_) HIP_CHECK(hipStreamWaitEvent(stream_, evInvDone_[l], 0));
         enqueueForwardLevel(l, stream_);
         if (world_ > 1) exchangeUpdateVectors(l); // update vectors of this level's fronts -> the rank that executes their parent (mf_exchange.hip)
@@ -545,7 +545,7 @@ void MfNumeric::enqueueForwardLevel(int l, hipStream_t st)
 {
     TreeView tv{ frontOff_.p, idxPtr_.p, firstNode_.p, childPtr_.p, child_.p, invPtr_.p, inv_.p, idx_.p, dinvOff_.p };
     XinvView xv{ xinvOff_.p, xinvX_.p, xinvT_.p };
-    const LevelPlan& P = plan_[l];
+    const LevelPlan& P = mp_.level[l];
     if (P.small.cnt)
     {
         if (FWD_NARROW && P.solveLds <= BWD_NARROW_MAX_N * sizeof(double))
@@ -559,7 +559,7 @@ void MfNumeric::enqueueForwardLevel(int l, hipStream_t st)
         hipLaunchKernelGGL(k_big_fwd_tri, dim3(P.bigTri.cnt), dim3(WGT), P.triLds, st, triList_.p + P.bigTri.off, tv, wOff_.p, fronts_.p, dinv_.p, w_.p,
             bperm_.p, yperm_.p);
     if (P.xinvFwd.cnt)
-        hipLaunchKernelGGL(k_xinv_fwd, dim3(P.xinvFwd.cnt), dim3(WG), xinvLds_, st, xinvDesc_.p + P.xinvFwd.off, tv, xv, wOff_.p, w_.p, bperm_.p, yperm_.p);
+        hipLaunchKernelGGL(k_xinv_fwd, dim3(P.xinvFwd.cnt), dim3(WG), mp_.xinvLds, st, xinvDesc_.p + P.xinvFwd.off, tv, xv, wOff_.p, w_.p, bperm_.p, yperm_.p);
     if (P.fwdRect.cnt)
         hipLaunchKernelGGL(k_big_fwd_rect, dim3(P.fwdRect.cnt), dim3(WG), 0, st, desc_.p + P.fwdRect.off, tv, wOff_.p, fronts_.p, w_.p, yperm_.p);
 }
@@ -588,7 +588,7 @@ void MfNumeric::enqueueBackward(double* x_dev)
     auto mark = [](const char*, int) {};
 #endif
     for (int l = nLevels_ - 1; l >= 0; --l) {
-        const LevelPlan& P = plan_[l];
+        const LevelPlan& P = mp_.level[l];
         if (P.bwdInit.cnt)
             hipLaunchKernelGGL(k_big_bwd_init, dim3(P.bwdInit.cnt), dim3(WG), P.bwdLds, stream_, desc_.p + P.bwdInit.off, tv, fronts_.p, yperm_.p,
                 xsol_.p);
@@ -598,7 +598,7 @@ void MfNumeric::enqueueBackward(double* x_dev)
                 dinv_.p, yperm_.p, xsol_.p);
         if (P.bigTri.cnt) mark("bwd_tri", l);
         if (P.xinvBwd.cnt)
-            hipLaunchKernelGGL(k_xinv_bwd, dim3(P.xinvBwd.cnt), dim3(WG), xinvLds_, stream_, xinvDesc_.p + P.xinvBwd.off, tv, xv, yperm_.p,
+            hipLaunchKernelGGL(k_xinv_bwd, dim3(P.xinvBwd.cnt), dim3(WG), mp_.xinvLds, stream_, xinvDesc_.p + P.xinvBwd.off, tv, xv, yperm_.p,
                 xsol_.p);
         if (P.small.cnt) {
             if (P.solveLds <= BWD_NARROW_MAX_N * sizeof(double))

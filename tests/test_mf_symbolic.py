@@ -21,7 +21,8 @@ ROOT = os.path.dirname(HERE)
 @pytest.fixture(scope="module")
 def shim():
     so = os.path.join(HERE, "mf_symbolic", "_build", "libmfsym.so")
-    srcs = [os.path.join(HERE, "mf_symbolic", "shim.cpp"), os.path.join(ROOT, "ipc_amd", "csrc", "mf_symbolic.cpp")]
+    srcs = [os.path.join(HERE, "mf_symbolic", "shim.cpp"), os.path.join(ROOT, "ipc_amd", "csrc", "mf_symbolic.cpp"),
+            os.path.join(ROOT, "ipc_amd", "csrc", "mf_plan.cpp")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread"] + srcs + ["-o", so])

@@ -104,7 +104,8 @@ def _shim_lib():
     import subprocess
     here = os.path.dirname(os.path.abspath(__file__))
     so = os.path.join(here, "mf_symbolic", "_build", "libmfsym.so")
-    srcs = [os.path.join(here, "mf_symbolic", "shim.cpp"), os.path.join(os.path.dirname(here), "ipc_amd", "csrc", "mf_symbolic.cpp")]
+    srcs = [os.path.join(here, "mf_symbolic", "shim.cpp"), os.path.join(os.path.dirname(here), "ipc_amd", "csrc", "mf_symbolic.cpp"),
+            os.path.join(os.path.dirname(here), "ipc_amd", "csrc", "mf_plan.cpp")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread"] + srcs + ["-o", so])

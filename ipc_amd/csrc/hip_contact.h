@@ -1,12 +1,12 @@
 // HipContact: the self-collision handler of the hot path (SelfCollisionHandler<3> statics,
 // src/CollisionObject/SelfCollisionHandler.hpp:21-250) with its state in HBM.
-//   computeConstraintSet      SelfCollisionHandler.cpp:2149-2478  -> buildConstraintSet (grid broad phase + typing on the GPU,
-//                                                                   duplicate merge on the host like the reference's std::map)
+//   computeConstraintSet      SelfCollisionHandler.cpp:2149-2478  -> buildConstraintSet (grid broad phase, typing and the merge of
+//                                                                   duplicate tuples on the GPU, in the order of the reference's std::map)
 //   evaluateConstraints + b   :38-81, Optimizer.cpp:3252-3353     -> energy
 //   leftMultiplyConstraintJacobianT / augmentParaEEGradient  :84-148, 2990-3036   -> gradientAdd
 //   augmentIPHessian / augmentParaEEHessian   :418-561, 3039-3201 -> hessianAdd
 //   augmentConnectivity       :330-415                            -> connectivity
-//   largestFeasibleStepSize[_CCD]  :564-686, 982-1366             -> ccdStepBound (conservative additive CCD)
+//   largestFeasibleStepSize[_CCD]  :564-686, 982-1366             -> ccdPartial / ccdFull / ccdFullReference (conservative additive CCD)
 #pragma once
 #include <cstdlib>
 #include "common.h"
@@ -147,7 +147,7 @@ private:
     void* scanTmp(size_t bytes); // temporary storage of a hipcub call, grown on demand
     template <class T>
     void exclusiveSum(const T* in, T* out, int count);
-    DevBuf<int> d_cand_, d_ids_;
+    DevBuf<int> d_ids_;
     DevBuf<double> d_vals_;
     DevBuf<unsigned long long> ccdOut_, ccdHits_;
     DevBuf<int> d_codimPoints;

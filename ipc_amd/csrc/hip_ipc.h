@@ -7,6 +7,7 @@
 // one-line forwards.  Everything here is reached through the C ABI of include/ipcgpu.h.
 #pragma once
 #include "common.h"
+#include "contact_pattern.h"
 #include "mf_numeric.h"
 #include "mf_symbolic.h"
 #include "nh_kernels.h"
@@ -162,7 +163,10 @@ public:
     double computeEnergyVal();
     void computeGradient(bool projectDBC);
     void penaltyGradientAdd(bool projectDBC);
-    void computePrecondMtr(bool projectDBC, bool withGradient);
+    void computePrecondMtr(bool projectDBC, bool withGradient); // its three steps follow
+    bool patternCoversContact(); // does the solver's pattern hold every block of the current contact sets
+    void growPattern(const std::function<void(const char*)>& lap); // new pattern + analysis where ContactPattern asks for them (lap: IPCGPU_PATTERN_TIMES)
+    void assembleSystem(bool projectDBC, bool withGradient); // matrix (and gradient) on the current pattern, one sequence for every sharding scheme
     // lagged stiffness-proportional damping (Optimizer.cpp:3381-3400, 3519-3540, 3707-3709, 3723-3735; Config.cpp:141-157, 614-616):
     // D = projected elastic Hessian at the state the last time step ended in, times dampingStiff / dt, on the solver's pattern
     double dampingStiff = 0.0;
@@ -174,9 +178,11 @@ public:
     void assembleDampingMtr(); // (re)builds the values at the remembered positions on the current pattern
     double dampingEnergy();
     void dampingGradientAdd(bool projectDBC, double* grad_dev);
-    void computeSearchDir(bool projectDBC);
+    void computeSearchDir();
+    void enqueueDirNorm();
     void lineSearch(double& stepSize);
     void stepForward(const double* x0_dev, double alpha);
+    void stepFeasible(double& stepSize);
     double filterStepSize(const double* p_dev, double stepSize);
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion();
@@ -269,7 +275,7 @@ public:
     bool fastPath() const;
     bool cachedDistValid = false, cachedE0Valid = false;
     double cachedDist = 0, cachedE0 = 0, cachedFilter = 0;
-    // ... and, second step (IPCGPU_NO_TRIAL_AHEAD restores the above): the first trial of the line search is taken on the device behind the solve
+    // ... and, second step: the first trial of the line search is taken on the device behind the solve
     // as well -- its step size, inversion flag and energy arrive with the same synchronisation, ONE per Newton iteration
     bool cachedTrialValid = false, cachedTrialInverted = false;
     double cachedTrialE = 0, cachedAlpha = 1.0;
@@ -279,7 +285,7 @@ public:
     // Nothing is skipped and nothing observable moves: d_gradient and the solver's values keep describing the iterate the search direction came from
     // until the swap; a rejected trial, a converged pass (one assembly per time step goes unused), a bad pivot or a time-step call drop the buffers' content.
     DevBuf<double> d_aSpec, d_gradSpec;
-    bool specAsmValid = false, specAsmOn = true; // IPCGPU_NO_SPEC_ASSEMBLY=1
+    bool specAsmValid = false;
     void speculativeAssembly();
     hipEvent_t evAsm0 = nullptr, evAsm1 = nullptr, evTail = nullptr;
     bool evAsmPending = false;
@@ -310,6 +316,7 @@ public:
     long long ownerNeededNodes = 0;
     bool matrixComplete = true; // false after an owner-mode assembly: a[] holds this rank's rows only
     void maskAndReduceGradient(double* g);
+    void ownerGradientTail(bool projectDBC); // stencils part 1, the exchange, Neumann, part 2, penalty: what computeGradient and assembleSystem share
     void completeMatrix(); // sum of the designated rows over the ranks: for the consumers of the WHOLE matrix on a sharded context (diagonal fallback, get_a)
     long long commBytes = 0, commCalls = 0; // all-reduced through the hook by the optimizer itself (the solver counts its own: HipLinSysSolver::exchangedBytes)
     // self-contact, interior point (fullyImplicit_IP with isSelfCollision, Optimizer.cpp:1518-1819)
@@ -319,7 +326,7 @@ public:
     bool absParameters = false; // useAbsParameters: lengths of `tuning` and the tolerance are absolute (Config.cpp:553-555)
     double dTolRel = 1.0e-9, kappaMinMultiplier = 1.0e11; // tuning[3] (Optimizer.cpp:102-106), Config.hpp:139
     double lenScale2() const { return absParameters ? 1.0 : mesh.bboxDiag2; }
-    std::vector<std::pair<int, int>> curExtra; // contact connectivity inside the current pattern (vNeighbor_IP)
+    ContactPattern contactPattern; // contact connectivity inside the current pattern (vNeighbor_IP)
     std::vector<std::array<int, 4>> closeID; // closeMConstraintID / Val (Optimizer.cpp:2396-2440)
     std::vector<double> closeVal;
     int lastCCDPair[2] = { 0, 0 }, nFullCCD = 0, nPatternChanges = 0, dbcIncomplete = 0;

@@ -436,9 +436,8 @@ bool HipOptimizer::nextSubproblem()
     if (fric && fricDHat <= fricDHatTarget) { // :1717 (the target equals the start value unless `tuning` gives a sixth entry)
         // tangent-space convergence test: one Newton direction with the refreshed lag (:1717-1731)
         computePrecondMtr(true, true);
-        computeSearchDir(true);
-        launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-        launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+        computeSearchDir();
+        enqueueDirNorm();
         if (readScalar(d_scalar.p + 3) < targetGRes) updateFricDHat = false;
         if (fricIterAmt > 0 && fricIterI >= fricIterAmt) updateFricDHat = false;
     }
@@ -863,16 +862,21 @@ void HipOptimizer::computeGradient(bool projectDBC)
     const bool owner = ownerMode() && !lin.rowBase.empty();
     elasticInertiaGradient(projectDBC, !owner);
     if (owner) {
-        // owner-computes: elastic + inertia forces of this rank's patches, its share of the self-contact stencils (those that touch a node it owns rows
-        // of), then ONE exchange in which every node is contributed by its designated rank; what is evaluated identically everywhere follows
-        if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 1);
-        maskAndReduceGradient(d_gradient.p);
-        neumannGradientAdd(d_gradient.p);
-        if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 2);
-        penaltyGradientAdd(projectDBC);
+        ownerGradientTail(projectDBC);
         return;
     }
     if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p);
+    penaltyGradientAdd(projectDBC);
+}
+
+// owner-computes: d_gradient holds the elastic + inertia forces of this rank's patches; its share of the self-contact stencils (those that touch a node it owns
+// rows of) goes on top, then ONE exchange in which every node is contributed by its designated rank; what is evaluated identically everywhere follows
+void HipOptimizer::ownerGradientTail(bool projectDBC)
+{
+    if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 1);
+    maskAndReduceGradient(d_gradient.p);
+    neumannGradientAdd(d_gradient.p);
+    if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 2);
     penaltyGradientAdd(projectDBC);
 }
 
@@ -889,10 +893,6 @@ void HipOptimizer::penaltyGradientAdd(bool projectDBC)
 void HipOptimizer::computePrecondMtr(bool projectDBC, bool withGradient)
 {
     if (lin.rowBase.empty()) throw StateError("computePrecondMtr needs a pattern built by set_pattern");
-    // The common case by far: the pattern already holds every block the current sets need (it only grows, and it is built with
-    // look-ahead).  One small kernel answers that; the host-side connectivity (hundreds of thousands of pairs to build, filter
-    // and sort) runs only when a pair is missing.  Lagged friction keeps its own set: always the host path there.
-    const bool frictionPairs = fricDHat > 0.0 && selfFric > 0.0;
     static const bool timeIt = std::getenv("IPCGPU_PATTERN_TIMES") != nullptr; // stderr: where a pattern change spends its time
     auto tLap = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -902,163 +902,141 @@ void HipOptimizer::computePrecondMtr(bool projectDBC, bool withGradient)
         fprintf(stderr, "pattern change: %-34s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tLap).count());
         tLap = now;
     };
-    // (the coverage answer usually arrived with the close-stencil bookkeeping at the end of the last iteration, postLineSearch: same sets, same pattern)
-    const bool coverCached = selfCollision && coverSets == contact->setsVersion && coverPattern == lin.patternVersion;
-    if (selfCollision && (frictionPairs || !(coverCached ? coverAnswer : contact->patternCovers(lin)))) {
+    if (!patternCoversContact()) {
         lap("coverage check");
-        // the pattern follows the contact connectivity (augmentConnectivity into vNeighbor_IP, Optimizer.cpp:3560-3612);
-        // only pairs that are not mesh edges change it
-        std::vector<std::pair<int, int>> extra, fresh;
-        // The connectivity of the live sets on the host (read-back of the tuples, node pairs, filter, sort: 1-2 ms at 40 K nodes) is needed only for the lagged
-        // friction set and for a look-ahead below 1.  Otherwise (round 6) the device has already said that the pattern lacks a block of the live sets -- a new
-        // analysis is certain --, and the look-ahead list below, the FULL stencils of every candidate within lookahead() x dHat >= dHat, contains every node pair
-        // of the live sets: their stencils are sub-stencils of candidates, the mollified pairs' four nodes are their candidates' four nodes.
-        const bool liveOnHost = frictionPairs || lookahead() < 1.0;
-        if (liveOnHost) {
-            if (contact->nActive() + contact->nPara()) contact->connectivity(extra);
-            if (fricDHat > 0.0 && selfFric > 0.0) contact->frictionConnectivity(extra); // lagged set (:3565-3566)
-            for (const auto& e : extra) {
-                const int* b = mesh.nb.data() + mesh.nbPtr[e.first];
-                const int* en = mesh.nb.data() + mesh.nbPtr[e.first + 1];
-                if (!std::binary_search(b, en, e.second)) fresh.push_back(e);
-            }
-            std::sort(fresh.begin(), fresh.end());
-            fresh.erase(std::unique(fresh.begin(), fresh.end()), fresh.end());
-        }
-        lap("connectivity of the live sets");
-        // The reference rebuilds pattern + symbolic analysis whenever the contact graph changes (:3570-3592).  Here the pattern
-        // only ever GROWS inside the stepper: pairs that left the constraint set keep their (zero) slots, so a new analysis is
-        // needed only when a pair shows up that no earlier iteration had.  Same matrix, fewer host-side analyses; the
-        // union is dropped again once it has grown far beyond the live set.
-        if (!liveOnHost || !std::includes(curExtra.begin(), curExtra.end(), fresh.begin(), fresh.end())) {
-            // Look-ahead: contact spreads, so the next iterations bring pairs that are a little farther apart now.  The new
-            // pattern is built from the constraint set at a larger distance (lookahead() * dHat, squared distances): its
-            // blocks hold explicit zeros until the pairs become active, and pattern + symbolic analysis (tens of ms on the
-            // host) are needed far less often.  Costs two extra constraint-set builds per analysis.
-            std::vector<std::pair<int, int>> padded = fresh;
-            const double pad = lookahead();
-            if (pad >= 1.0) {
-                std::vector<std::pair<int, int>> ahead;
-                if (pad > 1.0) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, pad * dHat);
-                contact->candidateConnectivitySorted(ahead); // full stencils: closest-feature changes need no new blocks; sorted, unique
-                if (pad > 1.0) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, dHat); // back to the real sets
-                std::vector<std::pair<int, int>> aheadNew;
-                aheadNew.reserve(ahead.size());
-                for (const auto& e : ahead) {
-                    const int* b = mesh.nb.data() + mesh.nbPtr[e.first];
-                    const int* en = mesh.nb.data() + mesh.nbPtr[e.first + 1];
-                    if (!std::binary_search(b, en, e.second)) aheadNew.push_back(e);
-                }
-                padded.clear(); // fresh and aheadNew are both sorted and unique: their union is one linear merge
-                std::set_union(fresh.begin(), fresh.end(), aheadNew.begin(), aheadNew.end(), std::back_inserter(padded));
-            }
-            lap("look-ahead sets + connectivity");
-            std::vector<std::pair<int, int>> merged;
-            std::set_union(curExtra.begin(), curExtra.end(), padded.begin(), padded.end(), std::back_inserter(merged));
-            if (merged.size() > 3 * padded.size() + 4096) merged = padded;
-            curExtra.swap(merged);
-            nPatternChanges++;
-            std::vector<int> flat;
-            flat.reserve(2 * curExtra.size());
-            for (const auto& e : curExtra) {
-                flat.push_back(e.first);
-                flat.push_back(e.second);
-            }
-            lap("union + flatten");
-            {
-                Tic t(timers[1], stream);
-                lin.set_pattern(mesh, (int)curExtra.size(), flat.data());
-            }
-            lap("set_pattern");
-            {
-                // the assembly plan of the new pattern is built on a second host thread while this one runs the symbolic analysis:
-                // both only read the pattern, and the GPU is idle either way
-                int dev = 0;
-                HIP_CHECK(hipGetDevice(&dev));
-                std::exception_ptr planErr;
-                std::thread planThread([&] {
-                    try {
-                        HIP_CHECK(hipSetDevice(dev));
-                        ensurePatchPlan();
-                    }
-                    catch (...) {
-                        planErr = std::current_exception();
-                    }
-                });
-                std::exception_ptr anaErr;
-                try {
-                    Tic t(timers[2], stream);
-                    lin.analyze_pattern(&mesh);
-                }
-                catch (...) {
-                    anaErr = std::current_exception();
-                }
-                planThread.join();
-                if (anaErr) std::rethrow_exception(anaErr);
-                if (planErr) std::rethrow_exception(planErr);
-            }
-            lap("analyze_pattern + patch plan");
-        }
+        growPattern(lap);
     }
-    // setZero (Optimizer.cpp:3616), elastic Hessian (:3619-3623) and the mass / DBC diagonal (:3638-3668) are one
-    // pass: every owned CSR row is written exactly once by the patch that owns its node
     const bool planStale = !(patchVersion == lin.patternVersion && patch.valid);
     ensurePatchPlan();
     if (planStale) lap("patch plan");
-    if (ownerMode()) {
-        // Owner-computes (round 4): this rank's patches write the complete CSR rows of the nodes it owns or shares, its share of the contact stencils adds
-        // their blocks to those rows -- and that is all its fronts ever read (an entry belongs to the front of whichever of its two nodes is eliminated
-        // first; the other node then sits in the same subtree or above the cut).  No matrix value crosses ranks.  The rows of other ranks' nodes stay zero.
-        ensureOwnerPlan();
-        lin.setZero();
-        if (withGradient) d_gradient.zero(stream);
-        launch_assemble_patches(view(), patch, 0, nOwnerPatches, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p, stream,
-            d_ownerPatches.p);
-        matrixComplete = false;
-        if (ipOn() && selfCollision) contact->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin, dHat, kappa, projectDBC, lin.d_a.p, d_need.p, /*deferCheck=*/true);
-        if (withGradient) {
-            if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 1);
-            maskAndReduceGradient(d_gradient.p);
-            neumannGradientAdd(d_gradient.p);
-            if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p, 2);
+    assembleSystem(projectDBC, withGradient);
+}
+
+bool HipOptimizer::patternCoversContact()
+{
+    // The common case by far: the pattern already holds every block the current sets need (it only grows, and it is built with
+    // look-ahead).  One small kernel answers that; the host-side connectivity (hundreds of thousands of pairs to build, filter
+    // and sort) runs only when a pair is missing.  Lagged friction keeps its own set: always the host path there.
+    if (!selfCollision) return true;
+    if (fricDHat > 0.0 && selfFric > 0.0) return false;
+    // (the coverage answer usually arrived with the close-stencil bookkeeping at the end of the last iteration, postLineSearch: same sets, same pattern)
+    const bool cached = coverSets == contact->setsVersion && coverPattern == lin.patternVersion;
+    return cached ? coverAnswer : contact->patternCovers(lin);
+}
+
+// the pattern follows the contact connectivity (augmentConnectivity into vNeighbor_IP, Optimizer.cpp:3560-3612); which pairs make it grow, and to what:
+// ContactPattern (contact_pattern.h)
+void HipOptimizer::growPattern(const std::function<void(const char*)>& lap)
+{
+    // The connectivity of the live sets on the host (read-back of the tuples, node pairs, filter, sort: 1-2 ms at 40 K nodes) is needed only for the lagged
+    // friction set and for a look-ahead below 1.  Otherwise (round 6) the device has already said that the pattern lacks a block of the live sets -- a new
+    // analysis is certain --, and the look-ahead list below, the FULL stencils of every candidate within lookahead() x dHat >= dHat, contains every node pair
+    // of the live sets: their stencils are sub-stencils of candidates, the mollified pairs' four nodes are their candidates' four nodes.
+    const bool frictionPairs = fricDHat > 0.0 && selfFric > 0.0;
+    const bool liveOnHost = frictionPairs || lookahead() < 1.0;
+    NodePairs live;
+    if (liveOnHost) {
+        if (contact->nActive() + contact->nPara()) contact->connectivity(live);
+        if (frictionPairs) contact->frictionConnectivity(live); // lagged set (:3565-3566)
+        live = nonMeshPairs(live, mesh.nbPtr.data(), mesh.nb.data());
+    }
+    lap("connectivity of the live sets");
+    // Look-ahead: contact spreads, so the next iterations bring pairs that are a little farther apart now.  The new
+    // pattern is built from the constraint set at a larger distance (lookahead() * dHat, squared distances): its
+    // blocks hold explicit zeros until the pairs become active, and pattern + symbolic analysis (tens of ms on the
+    // host) are needed far less often.  Costs two extra constraint-set builds per analysis.
+    auto lookAheadPairs = [&] {
+        NodePairs ahead;
+        const double pad = lookahead();
+        if (pad >= 1.0) {
+            if (pad > 1.0) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, pad * dHat);
+            contact->candidateConnectivitySorted(ahead); // full stencils: closest-feature changes need no new blocks; sorted, unique
+            if (pad > 1.0) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, dHat); // back to the real sets
+            ahead = nonMeshPairs(ahead, mesh.nbPtr.data(), mesh.nb.data());
         }
-        if (ipOn()) { // evaluated alike on every rank (vertex-wise diagonal blocks / the lagged friction set): added to the rows each rank holds
-            for (auto& h : planes)
-                h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
-            if (fricDHat > 0.0) {
-                for (auto& h : planes)
-                    if (h->friction > 0.0)
-                        h->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, fricDHat, projectDBC, lin.d_a.p);
-                if (selfCollision && selfFric > 0.0)
-                    contact->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin, fricDHat, selfFric, projectDBC, lin.d_a.p);
+        lap("look-ahead sets + connectivity");
+        return ahead;
+    };
+    if (!contactPattern.grow(liveOnHost ? &live : nullptr, lookAheadPairs)) return;
+    nPatternChanges++;
+    lap("union + flatten");
+    {
+        Tic t(timers[1], stream);
+        lin.set_pattern(mesh, (int)contactPattern.pairs().size(), contactPattern.flat().data());
+    }
+    lap("set_pattern");
+    {
+        // the assembly plan of the new pattern is built on a second host thread while this one runs the symbolic analysis:
+        // both only read the pattern, and the GPU is idle either way
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        std::exception_ptr planErr;
+        std::thread planThread([&] {
+            try {
+                HIP_CHECK(hipSetDevice(dev));
+                ensurePatchPlan();
             }
+            catch (...) {
+                planErr = std::current_exception();
+            }
+        });
+        std::exception_ptr anaErr;
+        try {
+            Tic t(timers[2], stream);
+            lin.analyze_pattern(&mesh);
         }
-        if (withGradient) penaltyGradientAdd(projectDBC);
-        if (!projectDBC && rhoDBC && !tpIds.empty()) launch_mdbc_hessian(mdbc(), lin.d_ia.p, rhoDBC, lin.d_a.p, stream);
-        return;
+        catch (...) {
+            anaErr = std::current_exception();
+        }
+        planThread.join();
+        if (anaErr) std::rethrow_exception(anaErr);
+        if (planErr) std::rethrow_exception(planErr);
     }
-    int pb, pe;
-    patchShard(pb, pe);
+    lap("analyze_pattern + patch plan");
+}
+
+// setZero (Optimizer.cpp:3616), elastic Hessian (:3619-3623) and the mass / DBC diagonal (:3638-3668) are one pass: every owned CSR row is written exactly
+// once by the patch that owns its node; the barrier, friction, damping and penalty terms go on top.  Two schemes for several ranks:
+// Owner-computes (round 4): this rank's patches write the complete CSR rows of the nodes it owns or shares, its share of the contact stencils adds their
+// blocks to those rows -- and that is all its fronts ever read (an entry belongs to the front of whichever of its two nodes is eliminated first; the other
+// node then sits in the same subtree or above the cut).  No matrix value crosses ranks.  The rows of other ranks' nodes stay zero.
+// The older scheme, kept for contexts whose solver is not sharded: a slice of the patches per rank, partial matrices summed by one all-reduce of the values;
+// the contact stencils are then evaluated alike on every rank, after the exchange.
+void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
+{
+    const bool owner = ownerMode();
+    int pb = 0, pe = 0;
+    if (owner) {
+        ensureOwnerPlan();
+        pe = nOwnerPatches;
+    }
+    else patchShard(pb, pe);
     if (worldSize > 1) {
         lin.setZero();
         if (withGradient) d_gradient.zero(stream);
     }
-    launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr,
-        lin.d_a.p, stream);
-    matrixComplete = true;
-    // (the older scheme, kept for contexts whose solver is not sharded: partial matrices summed by one all-reduce of the values; the contact stencils are
-    // then evaluated alike on every rank, after the exchange)
-    const bool contactSharded = false;
-    if (worldSize > 1) {
-        reduceSum(lin.d_a.p, (long long)lin.ja.size());
-        if (withGradient) reduceSum(d_gradient.p, 3LL * mesh.nV);
+    launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p, stream,
+        owner ? d_ownerPatches.p : nullptr);
+    matrixComplete = !owner;
+    if (owner) {
+        if (withGradient) ownerGradientTail(projectDBC);
     }
-    if (withGradient) neumannGradientAdd(d_gradient.p);
+    else {
+        if (worldSize > 1) {
+            reduceSum(lin.d_a.p, (long long)lin.ja.size());
+            if (withGradient) reduceSum(d_gradient.p, 3LL * mesh.nV);
+        }
+        if (withGradient) {
+            neumannGradientAdd(d_gradient.p);
+            if (ipOn()) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p);
+        }
+    }
     if (ipOn()) { // barrier blocks, PSD-projected per stencil (Optimizer.cpp:3625-3636, 3670-3676)
-        if (withGradient) barrierGradientAdd(projectDBC, kappa, false, d_gradient.p);
+        // (half-spaces and lagged friction: vertex-wise diagonal blocks / one set, evaluated alike on every rank and added to the rows each rank holds)
         for (auto& h : planes)
             h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
-        if (selfCollision && !contactSharded) contact->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin, dHat, kappa, projectDBC, lin.d_a.p, nullptr, /*deferCheck=*/true);
+        if (selfCollision) // owner-computes: the stencils that touch a row this rank needs
+            contact->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin, dHat, kappa, projectDBC, lin.d_a.p, owner ? d_need.p : nullptr, /*deferCheck=*/true);
         if (fricDHat > 0.0) { // Optimizer.cpp:3677-3702
             for (auto& h : planes)
                 if (h->friction > 0.0)
@@ -1067,11 +1045,11 @@ void HipOptimizer::computePrecondMtr(bool projectDBC, bool withGradient)
                 contact->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin, fricDHat, selfFric, projectDBC, lin.d_a.p);
         }
     }
-    if (dampingStiff > 0.0) { // addCoeff(dampingMtr, 1.0), Optimizer.cpp:3707-3709
+    if (dampingStiff > 0.0) { // addCoeff(dampingMtr, 1.0), Optimizer.cpp:3707-3709 (never in owner mode: ownerMode())
         if (dampPatternVersion != lin.patternVersion) assembleDampingMtr();
         launch_axpy((long long)lin.ja.size(), 1.0, d_damp.p, lin.d_a.p, stream);
     }
-    if (withGradient) penaltyGradientAdd(projectDBC);
+    if (withGradient && !owner) penaltyGradientAdd(projectDBC); // (the owner's came with its gradient tail)
     if (!projectDBC && rhoDBC && !tpIds.empty()) launch_mdbc_hessian(mdbc(), lin.d_ia.p, rhoDBC, lin.d_a.p, stream); // :3711-3713
 }
 
@@ -1127,7 +1105,7 @@ void HipOptimizer::stepForward(const double* x0_dev, double alpha)
 void HipOptimizer::speculativeAssembly()
 {
     specAsmValid = false;
-    if (!specAsmOn || !fastPath() || !projDBC || lin.rowBase.empty()) return;
+    if (!fastPath() || !projDBC || lin.rowBase.empty()) return;
     ensurePatchPlan();
     d_aSpec.alloc(lin.d_a.n); // same capacity as the solver's value array: the two are swapped
     d_gradSpec.alloc(d_gradient.n);
@@ -1147,16 +1125,20 @@ void HipOptimizer::speculativeAssembly()
     specAsmValid = true;
 }
 
-void HipOptimizer::computeSearchDir(bool projectDBC)
+// |p|_inf of the search direction into d_scalar[3] (convergence test of the next pass, Optimizer.cpp:1869-1879): enqueued, the caller publishes or reads it
+void HipOptimizer::enqueueDirNorm()
 {
-    (void)projectDBC;
+    launch_fill(d_scalar.p + 3, 1, 0.0, stream);
+    launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+}
+
+void HipOptimizer::computeSearchDir()
+{
     bool ok;
-    const bool twoCalls = false; // (factorize(), then solve(): the A/B of profiles/r03h_bench_line_*forward_overlap.json)
     launch_negate(3 * mesh.nV, d_gradient.p, d_minusG.p, stream);
-    const bool noSpec = false; // (synchronise after the solve, again after the trial step: profiles/r03t_trial_ahead_ab.txt)
     cachedTrialValid = false;
     cachedDistValid = false; // (|p|_inf of the direction this call replaces)
-    if (fastPath() && !twoCalls && !noSpec) {
+    if (fastPath()) {
         // ONE synchronisation per Newton iteration.  Behind factorisation + sweeps, on the same stream and without the host in between: |p|_inf
         // (convergence test of the next pass, Optimizer.cpp:1869-1879), the inversion step filter (:1887), E at the iterate (:2681), then the
         // first trial of the line search -- step size decided on the device from the filter's result, the step, its inversion flag
@@ -1166,7 +1148,7 @@ void HipOptimizer::computeSearchDir(bool projectDBC)
         const size_t bytes = 3 * (size_t)mesh.nV * sizeof(double);
         if (lin.factorizeSolve(d_minusG.p, d_searchDir.p, /*wait=*/false)) {
             // ten launches (fifteen before round 4: the resets, the copy + step-size + step and the two read-backs are one launch each now)
-            launch_iter_reset(d_scalar.p, d_flag.p, stream);
+            launch_iter_reset(d_scalar.p, d_flag.p, stream); // (zeroes the slot of |p|_inf with the others: no enqueueDirNorm(), whose fill would be one launch more)
             launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
             if (mesh.energyType != 1) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
             launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
@@ -1200,14 +1182,12 @@ void HipOptimizer::computeSearchDir(bool projectDBC)
         // the right-hand side is known before the factorisation starts: the forward sweep of each level runs beside the pivot chain of
         // the levels above (MfNumeric::factorizeSolve); this bucket then holds factorisation + both sweeps
         Tic t(timers[3], stream);
-        if (twoCalls) ok = lin.factorize();
-        else if (worldSize == 1) {
+        if (worldSize == 1) {
             // one process: nothing waits inside the solver; |p|_inf for the convergence test of the next pass (Optimizer.cpp:1869-1879) is enqueued behind
             // the sweeps and the pivot flag comes back with it -- one synchronisation (round 6; two before, and a third at the head of the next pass)
             ok = lin.factorizeSolve(d_minusG.p, d_searchDir.p, /*wait=*/false);
             if (ok) {
-                launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-                launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+                enqueueDirNorm();
                 launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
                 HIP_CHECK(hipStreamSynchronize(stream));
                 ok = lin.lastPivotsOk();
@@ -1224,13 +1204,11 @@ void HipOptimizer::computeSearchDir(bool projectDBC)
         completeMatrix(); // (owner-computes sharding: the diagonal of the rows other ranks hold)
         lin.precondition_diag(d_minusG.p, d_searchDir.p); // Optimizer.cpp:2331-2348
     }
-    else if (twoCalls) lin.solve(d_minusG.p, d_searchDir.p);
     if (fastPath()) {
         // everything the host needs next, behind the solve on the same stream, read back with ONE synchronisation (the Tic's): |p|_inf
         // (convergence test of the next pass, Optimizer.cpp:1869-1879), the inversion step filter (:1887) and E at the current iterate
         // (line search entry, :2681)
-        launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-        launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+        enqueueDirNorm();
         launch_fill(d_scalar.p + 2, 1, 1e20, stream);
         if (mesh.energyType != 1) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
         launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
@@ -1245,8 +1223,7 @@ void HipOptimizer::computeSearchDir(bool projectDBC)
         // the barrier Hessian's deferred "pair outside the pattern" flag has arrived with the solve's synchronisation; |p|_inf as above where it has not
         // come back yet (several processes, or the diagonal fallback just replaced the direction)
         if (!cachedDistValid) {
-            launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-            launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+            enqueueDirNorm();
             launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
             HIP_CHECK(hipStreamSynchronize(stream));
             cachedDist = h_scalar.p[3];
@@ -1270,6 +1247,22 @@ void HipOptimizer::resolveEventTimers()
     HIP_CHECK(hipEventElapsedTime(&ms, evAsm0, evAsm1));
     timers[0] += 1.0e-3 * (double)ms * evAsmWeight;
     evAsmPending = false;
+}
+
+// x = x0 + stepSize p from d_x0, stepSize halved while an element is inverted there, then, with contact, while the surface intersects itself or an obstacle
+// (AnimScripter.cpp:2172-2180; Optimizer.cpp:1117-1215)
+void HipOptimizer::stepFeasible(double& stepSize)
+{
+    stepForward(d_x0.p, stepSize);
+    while (!checkInversion()) {
+        stepSize /= 2.0;
+        stepForward(d_x0.p, stepSize);
+    }
+    if (ipOn())
+        while (anyIntersection()) {
+            stepSize /= 2.0;
+            stepForward(d_x0.p, stepSize);
+        }
 }
 
 void HipOptimizer::lineSearch(double& stepSize)
@@ -1324,6 +1317,7 @@ void HipOptimizer::lineSearch(double& stepSize)
         Tic t(timers[5], stream);
         HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, bytes, hipMemcpyDeviceToDevice, stream));
         stepForward(d_x0.p, stepSize);
+        // (not stepFeasible(): a step size halved down to zero ends this loop with the positions at the last non-zero step, not back at d_x0)
         while (!checkInversion()) { // Optimizer.cpp:2710-2717
             stepSize /= 2.0;
             if (stepSize == 0.0) break;
@@ -1375,7 +1369,7 @@ void HipOptimizer::precompute()
     {
         Tic t(timers[1], stream);
         lin.set_pattern(mesh, 0, nullptr);
-        curExtra.clear();
+        contactPattern = ContactPattern();
     }
     computeConstraintSets();
     computeDampingMtr(); // computePrecondMtr(..., updateDamping): Optimizer.cpp:470, 3598-3612
@@ -1423,10 +1417,8 @@ void HipOptimizer::beginTimestep()
         bool energyKnown = true;
         if (h_flag.p[1]) { // inverted behind the filtered step: the halving loop (AnimScripter.cpp:2172-2180) from here
             energyKnown = false;
-            do {
-                stepSize /= 2.0;
-                stepForward(d_x0.p, stepSize);
-            } while (!checkInversion());
+            stepSize /= 2.0;
+            stepFeasible(stepSize);
         }
         if (stepSize < 1.0) dbcIncomplete++;
         completedStep = stepSize;
@@ -1451,16 +1443,7 @@ void HipOptimizer::beginTimestep()
         if (selfCollision) // CCD of the scripted motion with slackness 0.5 (AnimScripter.cpp:2158-2171)
             stepSize = fullCcd(0.5, stepSize);
         HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, 3 * (size_t)mesh.nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        stepForward(d_x0.p, stepSize);
-        while (!checkInversion()) {
-            stepSize /= 2.0;
-            stepForward(d_x0.p, stepSize);
-        }
-        if (ipOn())
-            while (anyIntersection()) {
-                stepSize /= 2.0;
-                stepForward(d_x0.p, stepSize);
-            }
+        stepFeasible(stepSize);
         if (stepSize < 1.0) dbcIncomplete++; // the penalty solve of newtonIter() takes the nodes the rest of the way
         completedStep = stepSize; // AnimScripter::getCompletedStepSize
         d_searchDir.zero(stream); // initX(0), Optimizer.cpp:930-934
@@ -1490,16 +1473,7 @@ void HipOptimizer::beginTimestep()
             if (selfCollision) stepSize = fullCcd(0.8, stepSize);
         }
         HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, 3 * (size_t)mesh.nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        stepForward(d_x0.p, stepSize);
-        while (!checkInversion()) {
-            stepSize /= 2.0;
-            stepForward(d_x0.p, stepSize);
-        }
-        if (ipOn())
-            while (anyIntersection()) {
-                stepSize /= 2.0;
-                stepForward(d_x0.p, stepSize);
-            }
+        stepFeasible(stepSize);
         warmStepSize = stepSize;
     }
     if (ipOn()) {
@@ -1599,8 +1573,7 @@ void HipOptimizer::dirichletPenaltyUpdate()
     if (completed > 1.0 - 1.0e-3) projDBC = true; // penalty solve finished
     else if (completed < lastMove && rhoDBC < 1.0e8) rhoDBC *= 2.0;
     else {
-        launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-        launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+        enqueueDirNorm();
         if (readScalar(d_scalar.p + 3) < CN_MBC) { // safeToPull
             if (completed < 0.99 && rhoDBC < 1.0e8) rhoDBC *= 2.0;
             else launch_mdbc_lambda(mdbc(), mesh.d_x.p, rhoDBC, stream); // updateLambda (AnimScripter.cpp:2339-2346)
@@ -1614,8 +1587,7 @@ bool HipOptimizer::newtonIter()
     double distToOpt_PN;
     if (k && cachedDistValid) distToOpt_PN = cachedDist; // read back with the last solve
     else if (k) {
-        launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-        launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+        enqueueDirNorm();
         distToOpt_PN = readScalar(d_scalar.p + 3);
     }
     else distToOpt_PN = 0.0; // (the test needs k > 0: nothing to measure in the first pass of a time step)
@@ -1657,7 +1629,7 @@ bool HipOptimizer::newtonIter()
         computePrecondMtr(projDBC, true);
     }
     cachedE0Valid = false;
-    computeSearchDir(projDBC);
+    computeSearchDir();
     double alpha = 1.0;
     {
         Tic t(timers[13], stream);

@@ -188,11 +188,36 @@ def drop_scene(orc, gpu_lib, n=2, gap=0.03, dHatEps=1e-2, dt=0.01, speed=-1.5, j
     return m, o, c, nA
 
 
-@pytest.mark.parametrize("n,speed,dt", [(2, -1.5, 0.01), (3, -6.0, 0.02)])
-def test_contact_newton_iterates_track_the_oracle(orc, gpu_lib, n, speed, dt):
+@pytest.fixture(scope="module")
+def iterate_runs(orc, gpu_lib):
+    """Runs of _contact_newton_iterates by (n, speed, dt, look-ahead), each made once: the look-ahead 0 case compares itself with the default run whether or
+    not that case ran before it (a run that fails an assertion is not kept and fails again where it is asked for)."""
+    done = {}
+
+    def run(*key):
+        if key not in done:
+            done[key] = _contact_newton_iterates(orc, gpu_lib, *key)
+        return done[key]
+    return run
+
+
+@pytest.mark.parametrize("n,speed,dt,lookahead", [
+    pytest.param(2, -1.5, 0.01, None, id="2--1.5-0.01"), pytest.param(2, -1.5, 0.01, 1.0, id="2--1.5-0.01-lookahead1"),
+    pytest.param(2, -1.5, 0.01, 0.0, id="2--1.5-0.01-lookahead0"), pytest.param(3, -6.0, 0.02, None, id="3--6.0-0.02")])
+def test_contact_newton_iterates_track_the_oracle(iterate_runs, n, speed, dt, lookahead):
     """The whole contact-aware stepper (constraint sets per trial, barrier terms, adaptive kappa, partial / CFL / full CCD,
-    intersection-checked line search, pattern growth + re-analysis) iterate by iterate against the oracle."""
+    intersection-checked line search, pattern growth + re-analysis) iterate by iterate against the oracle.
+    lookahead: the pattern's look-ahead in units of dHat (None: the library's default, 4; 1: the candidates' stencils at dHat itself;
+    0: the exact pattern, live pairs formed on the host) -- the pattern only decides where explicit zeros sit, so every bound holds for each."""
+    changes = iterate_runs(n, speed, dt, lookahead)
+    if lookahead == 0.0:  # an exact pattern cannot change less often than one built ahead
+        assert changes >= iterate_runs(n, speed, dt, None)
+
+
+def _contact_newton_iterates(orc, gpu_lib, n, speed, dt, lookahead):
     m, o, c, nA = drop_scene(orc, gpu_lib, n=n, speed=speed, dt=dt)
+    if lookahead is not None:
+        c.set_pattern_lookahead(lookahead)
     o.precompute()
     c.precompute()
     seen, worst = 0, 0.0
@@ -227,7 +252,9 @@ def test_contact_newton_iterates_track_the_oracle(orc, gpu_lib, n, speed, dt):
     assert worst < 1e-8
     Vn = c.state()["V"]
     assert Vn[nA:, 1].mean() > Vn[:nA, 1].mean() + 0.2
+    changes = c.contact_state()["nPatternChanges"]
     c.close()
+    return changes
 
 
 def test_barrier_energy_gradient_hessian(orc, pair):

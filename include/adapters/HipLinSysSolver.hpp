@@ -101,11 +101,15 @@ public:
         chk(ipcgpu_ctx_set_solver(ctx, on ? IPCGPU_SOLVER_PCG : IPCGPU_SOLVER_MULTIFRONTAL));
         iterative_ = on;
     }
-    // solver.tol / solver.maxiter (AMGCLSolver.cpp:24-25), the preconditioner (IPCGPU_PRECOND_*) and how many factorize() calls a lagged factor serves
+    // solver.tol / solver.maxiter (AMGCLSolver.cpp:24-25), the preconditioner (IPCGPU_PRECOND_BLOCK_JACOBI | _LAGGED_CHOLESKY | _TWO_LEVEL) and how many
+    // factorize() calls a lagged factor serves.  _TWO_LEVEL reads the positions and Dirichlet types of this context's mesh at every factorize().
     void setIterativeParameters(double relTol, int maxIter, int precond, int maxFactorAge)
     {
         chk(ipcgpu_linsys_set_iterative(ctx, relTol, maxIter, precond, maxFactorAge));
     }
+
+    // the coarse level of IPCGPU_PRECOND_TWO_LEVEL: { aggregates, coarse rows, coarse nnz, coarse factorisations, block-Jacobi-only fall-backs }
+    void coarseStats(double* out5) const { chk(ipcgpu_linsys_coarse_stats(ctx, out5)); }
 
     // host-side addCoeff / setCoeff since the last flush -> HBM (one pass over the values)
     void flush() const

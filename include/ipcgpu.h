@@ -45,7 +45,7 @@ enum { IPCGPU_NOT_DBC = 0, IPCGPU_DBC_ZERO = 1, IPCGPU_DBC_NONZERO = 2 };
  * AMGCL through LinSysSolver::create, LinSysSolver.cpp:10-28) */
 enum { IPCGPU_SOLVER_MULTIFRONTAL = 0, IPCGPU_SOLVER_ROCSOLVER_CSRRF = 1, IPCGPU_SOLVER_PCG = 2 };
 /* preconditioners of IPCGPU_SOLVER_PCG (ipcgpu_linsys_set_iterative) */
-enum { IPCGPU_PRECOND_BLOCK_JACOBI = 0, IPCGPU_PRECOND_LAGGED_CHOLESKY = 1 };
+enum { IPCGPU_PRECOND_BLOCK_JACOBI = 0, IPCGPU_PRECOND_LAGGED_CHOLESKY = 1, IPCGPU_PRECOND_TWO_LEVEL = 2 };
 
 const char* ipcgpu_last_error(void);
 int ipcgpu_version(void);
@@ -149,7 +149,8 @@ int ipcgpu_linsys_factorize(ipcgpu_ctx*); /* factorize, :130-137; returns IPCGPU
 int ipcgpu_linsys_solve(ipcgpu_ctx*, const double* rhs, double* result); /* solve, :139-154 */
 int ipcgpu_linsys_precondition_diag(ipcgpu_ctx*, const double* in, double* out); /* :411-420 */
 /* IPCGPU_SOLVER_PCG: preconditioned conjugate gradients from x = 0, the reference's iterative choice (`linearSolver AMGCL`: CG to a relative
- * residual, AMGCLSolver.cpp:24-25, 44, 201, 225-232; its algebraic multigrid hierarchy is not rebuilt).  Defaults when set_iterative is never
+ * residual, AMGCLSolver.cpp:24-25, 44, 201, 225-232; its smoothed-aggregation hierarchy is not rebuilt: IPCGPU_PRECOND_TWO_LEVEL is a two-level
+ * method with a coarse space of its own).  Defaults when set_iterative is never
  * called: rel_tol 1e-5, max_iter 1000 (solver.tol / solver.maxiter, :24-25), block Jacobi, max_factor_age 1 (the best of 1, 2, 4, 8, 16
  * in a Newton run of the headline workload, profiles/pcg_bench.json).  The LinSysSolver calls then mean:
  *   analyze_pattern  BLOCK_JACOBI: no symbolic analysis at all, only the index of the lower triangle the product needs (AMGCLSolver.hpp: the
@@ -163,6 +164,17 @@ int ipcgpu_linsys_precondition_diag(ipcgpu_ctx*, const double* in, double* out);
  *                    after a failed factorize (Optimizer.cpp:2331-2348).  Not converged after max_iter with a factor of age > 0: the current
  *                    values are factorised once and the solve runs again.  Still not converged: IPCGPU_OK with converged = 0 in the
  *                    statistics, as the reference goes on with what AMGCL returned (:230-241).
+ * IPCGPU_PRECOND_TWO_LEVEL: z = D^-1 r + P Ac^-1 P^T r, block Jacobi plus an exact solve on a coarse space of six rigid-body modes per aggregate of
+ * nodes (additive, so symmetric positive definite whenever A is; max_factor_age is ignored).  Node i of aggregate I contributes the 3x6 block
+ * [ I | S(x_i - c_I) ] to P, S(d) w = d x w, c_I the centroid of the aggregate's free nodes; nodes with a Dirichlet type (ipcgpu_set_dbc) contribute
+ * nothing; an aggregate with fewer than 4 free nodes gets translations only and an identity in its rotation block of Ac = P^T A P.
+ *   analyze_pattern  aggregates the node graph of the pattern (greedy, in index order: deterministic) and analyses the coarse pattern with the
+ *                    multifrontal solver; the fine matrix gets no symbolic analysis.  Needs a node pattern on the context's mesh
+ *                    (ipcgpu_linsys_set_pattern): IPCGPU_ERR_UNSUPPORTED on an ipcgpu_linsys_set_pattern_csr pattern.
+ *   factorize        inverts the diagonal blocks (IPCGPU_NOT_PD as for BLOCK_JACOBI), then builds P from the positions and Dirichlet types the
+ *                    context holds at this call, assembles Ac on the device and factorises it.  An Ac that is not positive definite although every
+ *                    diagonal block is leaves this matrix to block Jacobi alone: IPCGPU_OK, counted in ipcgpu_linsys_coarse_stats.
+ *   solve            as for BLOCK_JACOBI; the coarse solver's sweeps run once per iteration.
  * Together with ipcgpu_linsys_set_shard(world > 1): IPCGPU_ERR_UNSUPPORTED.
  * ipcgpu_linsys_iter_stats, of the last solve: out6 = { iterations, |b - A x|_2 / |b|_2 at exit recomputed with one extra product, converged 0/1,
  * numeric factorisations this context's iterative solver has done so far, age of the factor the solve used (in factorize() calls), host
@@ -171,6 +183,14 @@ int ipcgpu_linsys_precondition_diag(ipcgpu_ctx*, const double* in, double* out);
  * per-pattern index, no atomics, the same bits on every run; available with every solver type. */
 int ipcgpu_linsys_set_iterative(ipcgpu_ctx*, double rel_tol, int max_iter, int precond, int max_factor_age);
 int ipcgpu_linsys_iter_stats(ipcgpu_ctx*, double* out6);
+/* The coarse level of IPCGPU_PRECOND_TWO_LEVEL.  coarse_stats: out5 = { aggregates, coarse rows (6 per aggregate), entries of the coarse upper CSR,
+ * coarse factorisations this context has done so far, factorize() calls that fell back to block Jacobi alone }; the first three are 0 without a coarse
+ * level.  coarse_dims: the same three sizes (0 without a coarse level).  coarse_get, after analyze_pattern: agg_of_node[n_nodes], the coarse
+ * symmetric-upper CSR coarse_ia[rows + 1] / coarse_ja[nnz] (aggregate I owns rows 6 I .. 6 I + 2, translations, and 6 I + 3 .. 6 I + 5, rotations) and,
+ * after factorize, its values coarse_a[nnz] as assembled on the device; any pointer may be NULL. */
+int ipcgpu_linsys_coarse_stats(ipcgpu_ctx*, double* out5);
+int ipcgpu_linsys_coarse_dims(ipcgpu_ctx*, int* n_aggregates, int* n_rows, int* nnz);
+int ipcgpu_linsys_coarse_get(ipcgpu_ctx*, int* agg_of_node, int* coarse_ia, int* coarse_ja, double* coarse_a);
 int ipcgpu_linsys_multiply_sym(ipcgpu_ctx*, const double* x, double* Ax);
 /* Multi-GPU direct solver (one process per GPU): the assembly tree is cut below its top separators; rank r factorises and solves
    the subtrees it owns; a front above the cut is executed by ONE rank (the one that holds its most expensive child), and the update

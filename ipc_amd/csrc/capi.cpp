@@ -25,6 +25,10 @@ int guarded(Fn&& fn)
         g_err = e.what();
         return IPCGPU_ERR_STATE;
     }
+    catch (const UnsupportedError& e) {
+        g_err = e.what();
+        return IPCGPU_ERR_UNSUPPORTED;
+    }
     catch (const HipError& e) {
         g_err = e.what();
         return IPCGPU_ERR_HIP;
@@ -614,6 +618,29 @@ int ipcgpu_linsys_iter_stats(ipcgpu_ctx* c, double* out6)
     return guarded([&] {
         needArg(c && out6, "null argument");
         L(c).iterStats(out6);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_linsys_coarse_stats(ipcgpu_ctx* c, double* out5)
+{
+    return guarded([&] {
+        needArg(c && out5, "null argument");
+        L(c).coarseStats(out5);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_linsys_coarse_dims(ipcgpu_ctx* c, int* n_agg, int* n_rows, int* nnz)
+{
+    return guarded([&] {
+        L(c).coarseDims(n_agg, n_rows, nnz);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_linsys_coarse_get(ipcgpu_ctx* c, int* agg_of_node, int* coarse_ia, int* coarse_ja, double* coarse_a)
+{
+    return guarded([&] {
+        bind(c);
+        L(c).coarseGet(agg_of_node, coarse_ia, coarse_ja, coarse_a);
         return IPCGPU_OK;
     });
 }

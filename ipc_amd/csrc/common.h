@@ -18,6 +18,9 @@ struct ArgError : std::runtime_error {
 struct StateError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+struct UnsupportedError : std::runtime_error { // a combination the library does not implement (IPCGPU_ERR_UNSUPPORTED)
+    using std::runtime_error::runtime_error;
+};
 
 #define HIP_CHECK(expr)                                                                               \
     do {                                                                                              \

@@ -15,6 +15,7 @@
 #include "hip_contact.h"
 #include "hip_halfspace.h"
 #include "pcg.h"
+#include "pcg_coarse.h"
 #include <map>
 #include <memory>
 #include <string>
@@ -90,12 +91,18 @@ public:
     void multiply(const double* x_dev, double* y_dev);
     void precondition_diag(const double* in_dev, double* out_dev);
     // Solver type 2: preconditioned CG (the reference's iterative choice, AMGCLSolver.cpp:24-25, 173-241).  precond 0: 3x3 block Jacobi, no symbolic
-    // analysis at all; 1: the multifrontal factor of an earlier matrix, kept for up to maxFactorAge factorize() calls.
+    // analysis at all; 1: the multifrontal factor of an earlier matrix, kept for up to maxFactorAge factorize() calls; 2: block Jacobi plus the exact solve
+    // of a coarse matrix of six rigid-body modes per node aggregate (pcg_coarse.h), rebuilt and factorised by every factorize() (maxFactorAge is ignored).
     double pcgRelTol = 1e-5; // solver.tol, AMGCLSolver.cpp:24
     int pcgMaxIter = 1000; // solver.maxiter, :25
     int pcgPrecond = 0, pcgMaxFactorAge = 1; // (the best of 1, 2, 4, 8, 16 on the headline workload: profiles/pcg_bench.json)
     void setIterative(double relTol, int maxIter, int precond, int maxFactorAge);
     void iterStats(double* out6) const;
+    // two-level preconditioner, after analyze_pattern: { aggregates, coarse rows, coarse nnz, coarse factorisations so far, factorize() calls whose coarse
+    // matrix was not positive definite (those matrices were served by block Jacobi alone) }
+    void coarseStats(double* out5) const;
+    bool coarseDims(int* nAgg, int* rows, int* nnz) const; // false: there is no coarse level (another preconditioner, or before analyze_pattern)
+    void coarseGet(int* aggOfNode, int* cia, int* cja, double* ca); // the hierarchy as the last analyze_pattern / factorize left it
     void multiplySym(const double* x_dev, double* y_dev); // the atomic-free product of the iterative solver (any solver type)
     int getNumRows() const { return numRows; }
     int getNumNonzeros() const { return (int)ja.size(); }
@@ -138,6 +145,14 @@ private:
     bool haveFactor_ = false, lastConverged_ = true;
     int factorAge_ = 0; // factorize() calls since the factor was computed
     long long nFactorizations_ = 0;
+    // two-level preconditioner: the aggregation (rebuilt when the pattern changes), its device copy, and a second solver (multifrontal, same stream) for Ac
+    PcgCoarse coarseHost_;
+    PcgCoarseDev coarseDev_;
+    std::unique_ptr<HipLinSysSolver> coarse_;
+    const HipMesh* coarseMesh_ = nullptr; // positions and Dirichlet types are read from it at every factorize()
+    int coarseVersion_ = -1;
+    bool coarseBuilt_ = false, coarseOk_ = false; // Ac assembled for the current values; its factorisation succeeded
+    long long nCoarseFactorizations_ = 0, nCoarseFallbacks_ = 0;
     struct {
         int iterations = 0, syncs = 0, factorAge = 0;
         double residual = 0.0;

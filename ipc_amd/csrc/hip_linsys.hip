@@ -226,6 +226,24 @@ void HipLinSysSolver::analyze_pattern(const HipMesh* mesh)
             analyzed_ = true;
             return;
         }
+        if (pcgPrecond == 2) { // two levels: the fine matrix gets no symbolic analysis either, the coarse one the multifrontal solver's
+            if (rowBase.empty()) throw UnsupportedError("the two-level preconditioner needs a node pattern (ipcgpu_linsys_set_pattern): a set_pattern_csr pattern has no nodes");
+            if (!mesh || 3 * mesh->nV != numRows) throw UnsupportedError("the two-level preconditioner needs the mesh whose nodes the pattern was built on");
+            coarseMesh_ = mesh;
+            if (coarseVersion_ != patternVersion) {
+                std::vector<unsigned char> fixed(mesh->nV);
+                for (int v = 0; v < mesh->nV; ++v) fixed[v] = mesh->dbcType[v] != 0;
+                coarseHost_.build(mesh->nV, ja.data(), rowBase.data(), rowLen.data(), fixed.data());
+                coarseDev_.upload(coarseHost_, stream);
+                if (!coarse_) coarse_.reset(new HipLinSysSolver(stream));
+                coarse_->set_pattern_csr(6 * coarseHost_.nAgg, coarseHost_.cia.data(), coarseHost_.cja.data());
+                coarseVersion_ = patternVersion;
+            }
+            if (!coarse_->analyzed()) coarse_->analyze_pattern(nullptr);
+            coarseBuilt_ = coarseOk_ = false;
+            analyzed_ = true;
+            return;
+        }
     }
     const int leaf = 12;
     // (the entries' destinations in the fronts are computed on the device by MfNumeric::setup; the rocSOLVER back end does not use them)
@@ -288,7 +306,7 @@ bool HipLinSysSolver::factorize()
     if (!analyzed_) throw StateError("factorize before analyze_pattern");
     if (solverType == 0) return num_.factorize(d_a.p);
     if (solverType == 2) {
-        if (pcgPrecond == 0) {
+        if (pcgPrecond == 0 || pcgPrecond == 2) {
             // AMGCLSolver::factorize rebuilds its preconditioner from the current values and always returns true (AMGCLSolver.cpp:173-191); here
             // a diagonal block that is not positive definite is reported, since the matrix then is not either
             pcgWork_.ensure(numRows);
@@ -296,7 +314,18 @@ bool HipLinSysSolver::factorize()
             launch_pcg_invert_blocks(pcgPat_, d_a.p, pcgWork_.flag.p, stream);
             int f = 0;
             pcgWork_.flag.download(&f, 1, stream);
-            return f == 0;
+            if (f || pcgPrecond == 0) return f == 0;
+            // two levels: Ac = P^T A P for the positions and constraints the context holds now, assembled into the coarse solver's values and factorised.
+            // A coarse matrix that is not positive definite although every diagonal block is (P lost rank: an aggregate whose free nodes lie on a line)
+            // leaves this matrix to block Jacobi alone.
+            if (!coarseMesh_->d_x.p || !coarseMesh_->d_dbc.p || 3 * coarseMesh_->nV != numRows) throw StateError("factorize: the mesh of the two-level preconditioner has no positions");
+            launch_pcg_coarse_geometry(coarseDev_, coarseMesh_->d_x.p, coarseMesh_->d_dbc.p, stream);
+            launch_pcg_galerkin(coarseDev_, d_rowLen.p, d_a.p, coarse_->d_a.p, stream);
+            coarseBuilt_ = true;
+            ++nCoarseFactorizations_;
+            coarseOk_ = coarse_->factorize();
+            if (!coarseOk_) ++nCoarseFallbacks_;
+            return true;
         }
         // the factor of an earlier matrix goes on serving as the preconditioner: a factor is used by at most pcgMaxFactorAge factorize() calls
         if (haveFactor_ && lastConverged_ && factorAge_ + 1 < pcgMaxFactorAge) {
@@ -345,8 +374,10 @@ bool HipLinSysSolver::solve(const double* rhs_dev, double* x_dev)
         return true;
     }
     if (solverType == 2) {
-        const bool jacobi = pcgPrecond == 0;
-        if (!jacobi && !haveFactor_) throw StateError("solve before factorize");
+        const bool lagged = pcgPrecond == 1;
+        const bool jacobi = !lagged; // (the point-wise part of the two-level preconditioner is block Jacobi's)
+        if (lagged && !haveFactor_) throw StateError("solve before factorize");
+        if (pcgPrecond == 2 && !coarseBuilt_) throw StateError("solve before factorize");
         pcgLast_ = {};
         pcgLast_.factorAge = jacobi ? 0 : factorAge_;
         PcgState st;
@@ -379,9 +410,9 @@ bool HipLinSysSolver::solve(const double* rhs_dev, double* x_dev)
 // ---- solver type 2 ------------------------------------------------------------------------------------------------------------------
 void HipLinSysSolver::setIterative(double relTol, int maxIter, int precond, int maxFactorAge)
 {
-    if (!(relTol > 0.0) || maxIter < 1 || (precond != 0 && precond != 1) || maxFactorAge < 1)
-        throw ArgError("set_iterative: rel_tol > 0, max_iter >= 1, precond 0 | 1, max_factor_age >= 1");
-    if (precond != pcgPrecond && solverType == 2) analyzed_ = false; // (the lagged factor needs the symbolic analysis block Jacobi skips)
+    if (!(relTol > 0.0) || maxIter < 1 || precond < 0 || precond > 2 || maxFactorAge < 1)
+        throw ArgError("set_iterative: rel_tol > 0, max_iter >= 1, precond 0 | 1 | 2, max_factor_age >= 1");
+    if (precond != pcgPrecond && solverType == 2) analyzed_ = false; // (the lagged factor needs the symbolic analysis block Jacobi skips, two levels the aggregation)
     pcgRelTol = relTol;
     pcgMaxIter = maxIter;
     pcgPrecond = precond;
@@ -396,6 +427,35 @@ void HipLinSysSolver::iterStats(double* o) const
     o[3] = (double)nFactorizations_;
     o[4] = pcgLast_.factorAge;
     o[5] = pcgLast_.syncs;
+}
+
+void HipLinSysSolver::coarseStats(double* o) const
+{
+    const bool have = coarseVersion_ == patternVersion && coarse_;
+    o[0] = have ? coarseHost_.nAgg : 0;
+    o[1] = have ? 6.0 * coarseHost_.nAgg : 0;
+    o[2] = have ? (double)coarseHost_.cja.size() : 0;
+    o[3] = (double)nCoarseFactorizations_;
+    o[4] = (double)nCoarseFallbacks_;
+}
+bool HipLinSysSolver::coarseDims(int* nAgg, int* rows, int* nnz) const
+{
+    const bool have = solverType == 2 && pcgPrecond == 2 && analyzed_ && coarse_ && coarseVersion_ == patternVersion;
+    if (nAgg) *nAgg = have ? coarseHost_.nAgg : 0;
+    if (rows) *rows = have ? 6 * coarseHost_.nAgg : 0;
+    if (nnz) *nnz = have ? (int)coarseHost_.cja.size() : 0;
+    return have;
+}
+void HipLinSysSolver::coarseGet(int* aggOfNode, int* cia, int* cja, double* ca)
+{
+    if (!coarseDims(nullptr, nullptr, nullptr)) throw StateError("no coarse level: set the two-level preconditioner and call analyze_pattern first");
+    if (aggOfNode) std::copy(coarseHost_.aggOf.begin(), coarseHost_.aggOf.end(), aggOfNode);
+    if (cia) std::copy(coarseHost_.cia.begin(), coarseHost_.cia.end(), cia);
+    if (cja) std::copy(coarseHost_.cja.begin(), coarseHost_.cja.end(), cja);
+    if (ca) {
+        if (!coarseBuilt_) throw StateError("the coarse values exist after factorize");
+        coarse_->d_a.download(ca, coarseHost_.cja.size(), stream);
+    }
 }
 
 void HipLinSysSolver::ensurePcgPattern()
@@ -417,16 +477,28 @@ void HipLinSysSolver::multiplySym(const double* x_dev, double* y_dev)
 // preconditioner is the multifrontal solver's own launch sequence, which knows nothing of the flag, so the host looks after every iteration, before
 // the sweeps (a synchronisation costs a tenth of them).  The true residual is computed behind the iteration that ended the solve, inside the same
 // batch; should it miss the tolerance the recurrence residual claims (rounding, after many iterations), CG restarts from the current x.
+// Two levels: restriction and prolongation honour the flag, the coarse solver's sweeps between them do not; they are small (6 rows per aggregate), so
+// they run ungated inside batches of PCG_TWO_LEVEL_BATCH iterations (1: the host looks after every iteration, as with the lagged factor).
+#ifndef PCG_TWO_LEVEL_BATCH
+#define PCG_TWO_LEVEL_BATCH 8
+#endif
 int HipLinSysSolver::runPcg(const double* rhs_dev, double* x_dev, PcgState& out)
 {
-    const bool jacobi = pcgPrecond == 0;
+    const bool twoLevel = pcgPrecond == 2 && coarseOk_;
+    const bool jacobi = pcgPrecond == 0 || (pcgPrecond == 2 && !coarseOk_); // (z and r.z come out of the update kernel itself)
     PcgWork& W = pcgWork_;
     W.ensure(numRows);
     const int gAp = pcg_symv_grid(pcgPat_);
     double* p[2] = { W.p0.p, W.p1.p };
-    int cur = 0, first = 1, restarts = 0, batch = jacobi ? 16 : 1;
+    int cur = 0, first = 1, restarts = 0, batch = jacobi ? 16 : (twoLevel ? PCG_TWO_LEVEL_BATCH : 1);
     auto precondition = [&](int firstRz) {
         if (jacobi) return;
+        if (twoLevel) {
+            launch_pcg_restrict(coarseDev_, W.r.p, coarseDev_.rc.p, W.state.p, 1, stream);
+            coarse_->solve(coarseDev_.rc.p, coarseDev_.xc.p);
+            launch_pcg_prolong(pcgPat_, coarseDev_, coarseDev_.xc.p, W, firstRz, 1, stream);
+            return;
+        }
         num_.solve(W.r.p, W.z.p);
         launch_pcg_rz(numRows, W.r.p, W.z.p, W, firstRz, stream);
     };
@@ -439,6 +511,7 @@ int HipLinSysSolver::runPcg(const double* rhs_dev, double* x_dev, PcgState& out)
             first = 0;
             launch_pcg_alpha(W, gAp, stream);
             launch_pcg_update(pcgPat_, jacobi, p[cur], W.Ap.p, x_dev, W, stream);
+            if (twoLevel && i + 1 < batch) precondition(0);
         }
         launch_pcg_symv(pcgPat_, d_ia.p, d_ja.p, d_rowBase.p, d_rowLen.p, d_a.p, x_dev, nullptr, nullptr, 0, W.Ap.p, nullptr, W.state.p, 2, stream);
         launch_pcg_residual(numRows, rhs_dev, W.Ap.p, W, stream);

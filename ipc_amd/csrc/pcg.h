@@ -65,4 +65,27 @@ void launch_pcg_update(const PcgPattern& P, bool jacobi, const double* p, const 
 void launch_pcg_residual(int n, const double* b, const double* y, PcgWork& W, hipStream_t s);
 void launch_pcg_publish(PcgWork& W, hipStream_t s);
 
+// ---- two-level preconditioner (IPCGPU_PRECOND_TWO_LEVEL): z = Dinv r + P Ac^-1 P^T r with Ac = P^T A P -------------------------------------------
+// The device copy of a PcgCoarse (pcg_coarse.h) and what factorize() computes from the current positions.  Node i of aggregate I contributes the 3x6
+// block [ I | S(x_i - c_I) ] to P (S(d) w = d x w, c_I the centroid of the aggregate's free nodes); a fixed node contributes nothing; an aggregate with
+// fewer than 4 free nodes has no rotation columns and an identity in its rotation block of Ac.
+struct PcgCoarseDev {
+    int nNodes = 0, nAgg = 0, nPairs = 0;
+    DevBuf<int> aggOf, aggPtr, aggNodes, pairIJ, pairPtr, pairSlot, cRowLen;
+    DevBuf<int> ent; // [4 per list entry] slot, row node, column node, transposed
+    DevBuf<double> geo; // [4][nNodes]: x_i - c_I (zero where the aggregate has no rotation columns or the node is fixed), and the weight 1 (free) / 0 (fixed)
+    DevBuf<int> aggFlags; // per aggregate: bit 0 it has a free node (translation columns), bit 1 it has 4 or more (rotation columns)
+    DevBuf<double> rc, xc; // [6 nAgg] restricted residual, coarse solution
+    void upload(const struct PcgCoarse& C, hipStream_t s);
+};
+// once per factorize(): centroids, offsets and flags from the positions (xyz per node) and the Dirichlet types (0 = free) the context holds
+void launch_pcg_coarse_geometry(PcgCoarseDev& C, const double* x, const int* dbcType, hipStream_t s);
+// Ac = P^T A P from the fine values a (upper storage, node block rows) into the coarse solver's value array ca: one lane group per aggregate pair walks
+// the pair's list, the 36 sums are reduced over the group in a fixed order, every coarse slot is written exactly once
+void launch_pcg_galerkin(const PcgCoarseDev& C, const int* rowLen, const double* a, double* ca, hipStream_t s);
+// rc = P^T r, one lane group per aggregate over its node list (gate as launch_pcg_symv)
+void launch_pcg_restrict(const PcgCoarseDev& C, const double* r, double* rc, const PcgState* st, int gate, hipStream_t s);
+// z = Dinv r + P xc and r.z (first = 1: the initial r.z; else beta = rz_new / rz), as launch_pcg_rz for the lagged factor
+void launch_pcg_prolong(const PcgPattern& P, const PcgCoarseDev& C, const double* xc, PcgWork& W, int first, int gate, hipStream_t s);
+
 } // namespace ipcgpu

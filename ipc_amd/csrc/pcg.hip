@@ -2,6 +2,7 @@
 // (8 B value + 4 B column per stored entry; the lower half comes from the same storage through a per-pattern index), the vectors once per
 // pass, the scalars never leave the device, and nothing is accumulated with atomics -- two runs give the same bits.
 #include "pcg.h"
+#include "pcg_coarse.h"
 #include <algorithm>
 
 namespace ipcgpu {
@@ -333,6 +334,202 @@ __global__ void k_pcg_publish(const unsigned* __restrict__ src, unsigned* __rest
     if (i < n) dst[i] = src[i];
 }
 
+// ---- two-level preconditioner -------------------------------------------------------------------------------------------------------------------
+// GROUP lanes share one aggregate (geometry, restriction) or one aggregate pair (Galerkin product): the lanes stride over the item's list, the sums are
+// combined by the xor butterfly below -- a fixed order, the same bits on every run -- and lane 0 writes.
+__device__ __forceinline__ double group_sum(double x)
+{
+#pragma unroll
+    for (int off = GROUP / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, GROUP);
+    return x;
+}
+// out = M S(d) and out = S(d)^T M for row-major 3x3 M, S(d) w = d x w
+__device__ __forceinline__ void times_S(const double* M, double dx, double dy, double dz, double* out)
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        out[3 * r + 0] = M[3 * r + 1] * dz - M[3 * r + 2] * dy;
+        out[3 * r + 1] = M[3 * r + 2] * dx - M[3 * r + 0] * dz;
+        out[3 * r + 2] = M[3 * r + 0] * dy - M[3 * r + 1] * dx;
+    }
+}
+__device__ __forceinline__ void St_times(const double* M, double dx, double dy, double dz, double* out)
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out[0 + c] = dz * M[3 + c] - dy * M[6 + c];
+        out[3 + c] = dx * M[6 + c] - dz * M[0 + c];
+        out[6 + c] = dy * M[0 + c] - dx * M[3 + c];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_pcg_coarse_geometry(int nAgg, int nNodes, const int* __restrict__ aggPtr, const int* __restrict__ aggNodes,
+    const double* __restrict__ x, const int* __restrict__ dbcType, double* __restrict__ geo, int* __restrict__ aggFlags)
+{
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int I = blockIdx.x * NODES_PER_BLOCK + (threadIdx.x / GROUP);
+    const int b = I < nAgg ? aggPtr[I] : 0, e = I < nAgg ? aggPtr[I + 1] : 0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    for (int k = b + lane; k < e; k += GROUP) {
+        const int v = aggNodes[k];
+        if (dbcType[v] == 0) {
+            const size_t o = 3 * (size_t)v;
+            s0 += x[o], s1 += x[o + 1], s2 += x[o + 2];
+            cnt += 1.0;
+        }
+    }
+    s0 = group_sum(s0), s1 = group_sum(s1), s2 = group_sum(s2), cnt = group_sum(cnt);
+    if (I >= nAgg) return;
+    const bool rot = cnt >= 4.0;
+    const double inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
+    const double c0 = s0 * inv, c1 = s1 * inv, c2 = s2 * inv;
+    for (int k = b + lane; k < e; k += GROUP) {
+        const int v = aggNodes[k];
+        const bool free_ = dbcType[v] == 0;
+        const size_t o = 3 * (size_t)v;
+        const bool arm = rot && free_;
+        geo[v] = arm ? x[o] - c0 : 0.0;
+        geo[(size_t)nNodes + v] = arm ? x[o + 1] - c1 : 0.0;
+        geo[2 * (size_t)nNodes + v] = arm ? x[o + 2] - c2 : 0.0;
+        geo[3 * (size_t)nNodes + v] = free_ ? 1.0 : 0.0;
+    }
+    if (lane == 0) aggFlags[I] = (cnt >= 1.0 ? 1 : 0) | (rot ? 2 : 0);
+}
+
+// One lane group per aggregate pair (I <= J).  For an entry (i in I, j in J) with fine block B the pair receives P_i^T B P_j =
+// [ B, B S_j ; S_i^T B, S_i^T B S_j ]; an off-diagonal fine block inside one aggregate stands for its mirror image too (M + M^T).
+__global__ __launch_bounds__(BLOCK) void k_pcg_galerkin(int nPairs, int nNodes, const int* __restrict__ pairIJ, const int* __restrict__ pairPtr,
+    const int* __restrict__ pairSlot, const int4* __restrict__ ent, const int* __restrict__ rowLen, const int* __restrict__ cRowLen,
+    const double* __restrict__ geo, const int* __restrict__ aggFlags, const double* __restrict__ a, double* __restrict__ ca)
+{
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int p = blockIdx.x * NODES_PER_BLOCK + (threadIdx.x / GROUP);
+    const bool live = p < nPairs;
+    const int I = live ? pairIJ[2 * p] : 0, J = live ? pairIJ[2 * p + 1] : 0;
+    const int b = live ? pairPtr[p] : 0, e = live ? pairPtr[p + 1] : 0;
+    double TT[9], TR[9], RT[9], RR[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) TT[q] = TR[q] = RT[q] = RR[q] = 0.0;
+    for (int k = b + lane; k < e; k += GROUP) {
+        const int4 en = ent[k]; // slot, row node u, column node w, transposed
+        const int u = en.y, w = en.z;
+        if (geo[3 * (size_t)nNodes + u] * geo[3 * (size_t)nNodes + w] == 0.0) continue; // a fixed node has no entries in P
+        const int len = rowLen[u], s0 = en.x;
+        double B[9];
+        if (u == w) {
+            B[0] = a[s0], B[1] = B[3] = a[s0 + 1], B[2] = B[6] = a[s0 + 2];
+            B[4] = a[s0 + len], B[5] = B[7] = a[s0 + len + 1], B[8] = a[s0 + 2 * len - 1];
+        }
+        else {
+            const int s1 = s0 + len - 1, s2 = s0 + 2 * len - 3;
+            if (en.w) {
+                B[0] = a[s0], B[3] = a[s0 + 1], B[6] = a[s0 + 2];
+                B[1] = a[s1], B[4] = a[s1 + 1], B[7] = a[s1 + 2];
+                B[2] = a[s2], B[5] = a[s2 + 1], B[8] = a[s2 + 2];
+            }
+            else {
+                B[0] = a[s0], B[1] = a[s0 + 1], B[2] = a[s0 + 2];
+                B[3] = a[s1], B[4] = a[s1 + 1], B[5] = a[s1 + 2];
+                B[6] = a[s2], B[7] = a[s2 + 1], B[8] = a[s2 + 2];
+            }
+        }
+        const int i = en.w ? w : u, j = en.w ? u : w;
+        const double ix = geo[i], iy = geo[(size_t)nNodes + i], iz = geo[2 * (size_t)nNodes + i];
+        const double jx = geo[j], jy = geo[(size_t)nNodes + j], jz = geo[2 * (size_t)nNodes + j];
+        double tr[9], rt[9], rr[9];
+        times_S(B, jx, jy, jz, tr);
+        St_times(B, ix, iy, iz, rt);
+        St_times(tr, ix, iy, iz, rr);
+        if (I == J && u != w) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    TT[3 * r + c] += B[3 * r + c] + B[3 * c + r];
+                    TR[3 * r + c] += tr[3 * r + c] + rt[3 * c + r];
+                    RR[3 * r + c] += rr[3 * r + c] + rr[3 * c + r];
+                }
+        }
+        else {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) TT[q] += B[q], TR[q] += tr[q], RT[q] += rt[q], RR[q] += rr[q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) TT[q] = group_sum(TT[q]), TR[q] = group_sum(TR[q]), RT[q] = group_sum(RT[q]), RR[q] = group_sum(RR[q]);
+    if (!live || lane) return;
+    const int lt = cRowLen[2 * I], lr = cRowLen[2 * I + 1];
+    const int sTT = pairSlot[4 * p], sTR = pairSlot[4 * p + 1], sRT = pairSlot[4 * p + 2], sRR = pairSlot[4 * p + 3];
+    auto full = [&](const double* M, int s, int len) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ca[s + c] = M[c], ca[s + len - 1 + c] = M[3 + c], ca[s + 2 * len - 3 + c] = M[6 + c];
+    };
+    auto diag = [&](const double* M, int s, int len, bool identity) {
+        ca[s] = identity ? 1.0 : M[0], ca[s + 1] = identity ? 0.0 : M[1], ca[s + 2] = identity ? 0.0 : M[2];
+        ca[s + len] = identity ? 1.0 : M[4], ca[s + len + 1] = identity ? 0.0 : M[5], ca[s + 2 * len - 1] = identity ? 1.0 : M[8];
+    };
+    if (I == J) {
+        const int f = aggFlags[I];
+        diag(TT, sTT, lt, !(f & 1));
+        full(TR, sTR, lt);
+        diag(RR, sRR, lr, !(f & 2));
+    }
+    else {
+        full(TT, sTT, lt);
+        full(TR, sTR, lt);
+        full(RT, sRT, lr);
+        full(RR, sRR, lr);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_pcg_restrict(int nAgg, int nNodes, const int* __restrict__ aggPtr, const int* __restrict__ aggNodes,
+    const double* __restrict__ geo, const double* __restrict__ r, double* __restrict__ rc, const PcgState* __restrict__ st, int gate)
+{
+    if (gated_out(st, gate)) return;
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int I = blockIdx.x * NODES_PER_BLOCK + (threadIdx.x / GROUP);
+    const int b = I < nAgg ? aggPtr[I] : 0, e = I < nAgg ? aggPtr[I + 1] : 0;
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    for (int k = b + lane; k < e; k += GROUP) {
+        const int v = aggNodes[k];
+        const size_t o = 3 * (size_t)v;
+        const double w = geo[3 * (size_t)nNodes + v];
+        const double dx = geo[v], dy = geo[(size_t)nNodes + v], dz = geo[2 * (size_t)nNodes + v]; // (zero for a fixed node)
+        const double r0 = r[o], r1 = r[o + 1], r2 = r[o + 2];
+        t0 += w * r0, t1 += w * r1, t2 += w * r2;
+        q0 += r1 * dz - r2 * dy, q1 += r2 * dx - r0 * dz, q2 += r0 * dy - r1 * dx; // S(d)^T r = r x d
+    }
+    t0 = group_sum(t0), t1 = group_sum(t1), t2 = group_sum(t2), q0 = group_sum(q0), q1 = group_sum(q1), q2 = group_sum(q2);
+    if (I < nAgg && lane == 0) {
+        double* o = rc + 6 * (size_t)I;
+        o[0] = t0, o[1] = t1, o[2] = t2, o[3] = q0, o[4] = q1, o[5] = q2;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_pcg_prolong(int nNodes, const int* __restrict__ aggOf, const double* __restrict__ geo, const double* __restrict__ dinv,
+    const double* __restrict__ r, const double* __restrict__ xc, double* __restrict__ z, double* __restrict__ pRz, const PcgState* __restrict__ st, int gate)
+{
+    __shared__ double sm[BLOCK / 64];
+    if (gated_out(st, gate)) return;
+    double rz = 0.0;
+    for (int v = blockIdx.x * BLOCK + threadIdx.x; v < nNodes; v += gridDim.x * BLOCK) {
+        const size_t o = 3 * (size_t)v;
+        const double r0 = r[o], r1 = r[o + 1], r2 = r[o + 2];
+        double z0, z1, z2;
+        apply_dinv(dinv, nNodes, v, r0, r1, r2, z0, z1, z2);
+        const double* c = xc + 6 * (size_t)aggOf[v];
+        const double w = geo[3 * (size_t)nNodes + v];
+        const double dx = geo[v], dy = geo[(size_t)nNodes + v], dz = geo[2 * (size_t)nNodes + v];
+        z0 += w * c[0] + (dy * c[5] - dz * c[4]); // S(d) w = d x w
+        z1 += w * c[1] + (dz * c[3] - dx * c[5]);
+        z2 += w * c[2] + (dx * c[4] - dy * c[3]);
+        z[o] = z0, z[o + 1] = z1, z[o + 2] = z2;
+        rz += r0 * z0 + r1 * z1 + r2 * z2;
+    }
+    const double s = block_sum(rz, sm);
+    if (threadIdx.x == 0) pRz[blockIdx.x] = s;
+}
+
 inline int vec_grid(long long n) { return (int)std::max<long long>(1, std::min<long long>(MAX_VEC_BLOCKS, (n + BLOCK - 1) / BLOCK)); }
 } // namespace
 
@@ -478,6 +675,45 @@ void launch_pcg_update(const PcgPattern& P, bool jacobi, const double* p, const 
     double* pRr = W.partial.p + 2 * (size_t)W.nPartial;
     hipLaunchKernelGGL(k_pcg_update, dim3(g), dim3(BLOCK), 0, s, P.nNodes, (int)jacobi, p, Ap, P.dinv.p, x, W.r.p, W.z.p, pRz, pRr, W.state.p);
     hipLaunchKernelGGL(k_pcg_update_state, dim3(1), dim3(BLOCK), 0, s, g, (int)jacobi, pRz, pRr, W.state.p);
+}
+
+void PcgCoarseDev::upload(const PcgCoarse& C, hipStream_t s)
+{
+    nNodes = C.nNodes, nAgg = C.nAgg, nPairs = (int)C.pairI.size();
+    std::vector<int> ij(2 * (size_t)nPairs), e4(4 * C.entSlot.size());
+    for (int p = 0; p < nPairs; ++p) ij[2 * p] = C.pairI[p], ij[2 * p + 1] = C.pairJ[p];
+    for (size_t k = 0; k < C.entSlot.size(); ++k) e4[4 * k] = C.entSlot[k], e4[4 * k + 1] = C.entRow[k], e4[4 * k + 2] = C.entCol[k], e4[4 * k + 3] = C.entTrans[k];
+    aggOf.uploadGrow(C.aggOf, s), aggPtr.uploadGrow(C.aggPtr, s), aggNodes.uploadGrow(C.aggNodes, s);
+    pairIJ.uploadGrow(ij, s), pairPtr.uploadGrow(C.pairPtr, s), pairSlot.uploadGrow(C.pairSlot, s), cRowLen.uploadGrow(C.cRowLen, s);
+    ent.uploadGrow(e4, s);
+    geo.ensure(4 * (size_t)nNodes), aggFlags.ensure(nAgg), rc.ensure(6 * (size_t)nAgg), xc.ensure(6 * (size_t)nAgg);
+    HIP_CHECK(hipStreamSynchronize(s)); // the host vectors go out of scope
+}
+
+void launch_pcg_coarse_geometry(PcgCoarseDev& C, const double* x, const int* dbcType, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pcg_coarse_geometry, dim3((C.nAgg + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK), dim3(BLOCK), 0, s, C.nAgg, C.nNodes, C.aggPtr.p, C.aggNodes.p, x,
+        dbcType, C.geo.p, C.aggFlags.p);
+}
+
+void launch_pcg_galerkin(const PcgCoarseDev& C, const int* rowLen, const double* a, double* ca, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pcg_galerkin, dim3((C.nPairs + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK), dim3(BLOCK), 0, s, C.nPairs, C.nNodes, C.pairIJ.p, C.pairPtr.p,
+        C.pairSlot.p, (const int4*)C.ent.p, rowLen, C.cRowLen.p, C.geo.p, C.aggFlags.p, a, ca);
+}
+
+void launch_pcg_restrict(const PcgCoarseDev& C, const double* r, double* rc, const PcgState* st, int gate, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pcg_restrict, dim3((C.nAgg + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK), dim3(BLOCK), 0, s, C.nAgg, C.nNodes, C.aggPtr.p, C.aggNodes.p, C.geo.p, r,
+        rc, st, gate);
+}
+
+void launch_pcg_prolong(const PcgPattern& P, const PcgCoarseDev& C, const double* xc, PcgWork& W, int first, int gate, hipStream_t s)
+{
+    const int g = vec_grid(P.nNodes);
+    double* pRz = W.partial.p + W.nPartial;
+    hipLaunchKernelGGL(k_pcg_prolong, dim3(g), dim3(BLOCK), 0, s, P.nNodes, C.aggOf.p, C.geo.p, P.dinv.p, W.r.p, xc, W.z.p, pRz, W.state.p, gate);
+    hipLaunchKernelGGL(k_pcg_rz_state, dim3(1), dim3(BLOCK), 0, s, g, first, pRz, W.state.p);
 }
 
 void launch_pcg_residual(int n, const double* b, const double* y, PcgWork& W, hipStream_t s)

@@ -27,6 +27,7 @@ SOLVER_ROCSOLVER_CSRRF = 1
 SOLVER_PCG = 2  # the reference's `linearSolver AMGCL`: preconditioned CG (ipcgpu_linsys_set_iterative)
 PRECOND_BLOCK_JACOBI = 0
 PRECOND_LAGGED_CHOLESKY = 1
+PRECOND_TWO_LEVEL = 2  # block Jacobi + an exact coarse solve on six rigid-body modes per node aggregate
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int)
 
@@ -422,6 +423,29 @@ class Context:
         o = np.zeros(6)
         self._chk(self._L.ipcgpu_linsys_iter_stats(self.h, _dp(o)))
         return dict(iterations=int(o[0]), residual=float(o[1]), converged=int(o[2]), factorizations=int(o[3]), factor_age=int(o[4]), syncs=int(o[5]))
+
+    def coarse_stats(self):
+        """the coarse level of PRECOND_TWO_LEVEL (ipcgpu_linsys_coarse_stats)"""
+        o = np.zeros(5)
+        self._chk(self._L.ipcgpu_linsys_coarse_stats(self.h, _dp(o)))
+        return dict(aggregates=int(o[0]), coarse_rows=int(o[1]), coarse_nnz=int(o[2]), coarse_factorizations=int(o[3]), jacobi_fallbacks=int(o[4]))
+
+    def coarse_dims(self):
+        """(aggregates, coarse rows, coarse nnz); zeros without a coarse level"""
+        a, r, z = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self._L.ipcgpu_linsys_coarse_dims(self.h, C.byref(a), C.byref(r), C.byref(z)))
+        return a.value, r.value, z.value
+
+    def coarse_get(self, values=True):
+        """(aggregate of every node, coarse ia, coarse ja, coarse values or None): the hierarchy of PRECOND_TWO_LEVEL as the last analyze_pattern /
+        factorize left it (ipcgpu_linsys_coarse_get)"""
+        _, rows, nnz = self.coarse_dims()
+        n, _ = self.get_dims()
+        agg = np.zeros(n // 3, dtype=np.int32)
+        cia, cja = np.zeros(rows + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32)
+        ca = np.zeros(nnz) if values else None
+        self._chk(self._L.ipcgpu_linsys_coarse_get(self.h, _ip(agg), _ip(cia), _ip(cja), _dp(ca)))
+        return agg, cia, cja, ca
 
     def analyze_pattern(self):
         self._chk(self._L.ipcgpu_linsys_analyze_pattern(self.h))

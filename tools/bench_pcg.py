@@ -6,6 +6,9 @@ the headline workload's (mat150 twist, bench.py) and the contact bench's (tools/
   the product kernel's achieved bytes/s against its algorithmic bytes (8 nnz values + 4 nnz columns + the two vectors, each once)
 
 usage: python tools/bench_pcg.py [--n 150] [--contact-n 60] [--newton 40] [--out profiles/pcg_bench.json]
+       python tools/bench_pcg.py --two-level [--n 150] [--contact-n 60] [--large-n 0] [--out profiles/pcg_two_level_bench.json]
+--two-level: the two-level preconditioner (precond 2) beside block Jacobi and the multifrontal solve, per solve, on the same matrices (and on the
+3 x mat<large-n> stack of contact_large when --large-n is given); per row iterations, ms per solve, ms per factorize(), aggregates, host synchronisations.
 Times are HIP-event times around factorize() / solve() on device-resident vectors (ipcgpu_bench_factor_solve, ipcgpu_bench_multiply_sym)."""
 import argparse
 import json
@@ -19,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ipc_amd import lib, scene  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E
-BJ, LAG = lib.PRECOND_BLOCK_JACOBI, lib.PRECOND_LAGGED_CHOLESKY
+BJ, LAG, TWO = lib.PRECOND_BLOCK_JACOBI, lib.PRECOND_LAGGED_CHOLESKY, lib.PRECOND_TWO_LEVEL
 
 
 def twist_ctx(n, solver, iterative=None):
@@ -35,8 +38,8 @@ def twist_ctx(n, solver, iterative=None):
     return c
 
 
-def contact_ctx(n, solver, iterative=None):
-    V, F, nA = scene.make_mat_stack(n, 2, gap=1.2e-3)
+def contact_ctx(n, solver, iterative=None, layers=2):
+    V, F, nA = scene.make_mat_stack(n, layers, gap=1.2e-3)
     Vs = scene.jitter(V, F, rel=2e-3)
     SF = scene.surface_tris(F)
     c = lib.Context(0, solver=solver)
@@ -104,6 +107,38 @@ def per_solve(make, warm_iters, reps):
     return out
 
 
+def two_level(make, warm_iters, reps):
+    """per_solve's protocol for the multifrontal solve, block Jacobi and the two-level preconditioner at 1e-5 and 1e-10"""
+    out = {}
+    variants = [("multifrontal", 0, None)]
+    for tol in (1e-5, 1e-10):
+        variants.append((f"pcg_block_jacobi_{tol:g}", 2, (tol, 100000, BJ, 1)))
+        variants.append((f"pcg_two_level_{tol:g}", 2, (tol, 100000, TWO, 1)))
+    for name, solver, it in variants:
+        c = make(0)
+        newton(c, warm_iters)
+        n_rows, nnz = c.get_dims()
+        t_analyze = None
+        if solver == 2:
+            c.set_solver(2)
+            c.set_iterative(*it)
+            t0 = time.perf_counter()
+            c.analyze_pattern()
+            t_analyze = 1e3 * (time.perf_counter() - t0)
+        c.bench_factor_solve(1)
+        f_ms, s_ms = c.bench_factor_solve(reps)
+        rec = {"factorize_ms": f_ms, "solve_ms": s_ms, "total_ms": f_ms + s_ms, "rows": n_rows, "nnz": nnz}
+        if solver == 2:
+            rec.update(c.iter_stats())
+            rec["analyze_pattern_wall_ms"] = t_analyze
+            if it[2] == TWO:
+                rec.update(c.coarse_stats())
+        out[name] = rec
+        c.close()
+        print(name, json.dumps(rec), flush=True)
+    return out
+
+
 def lagged_ages(n, iters):
     out = {}
     c = twist_ctx(n, 0)
@@ -131,8 +166,24 @@ if __name__ == "__main__":
     ap.add_argument("--contact-n", type=int, default=60)
     ap.add_argument("--newton", type=int, default=40)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join("profiles", "pcg_bench.json"))
+    ap.add_argument("--two-level", action="store_true")
+    ap.add_argument("--large-n", type=int, default=0)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.two_level:
+        a.out = a.out or os.path.join("profiles", "pcg_two_level_bench.json")
+        rec = {"device": "MI355X", "headline_matrix": {"workload": f"mat{a.n} twist after 10 Newton iterations", **two_level(lambda s: twist_ctx(a.n, s), 10, a.reps)},
+               "contact_matrix": {"workload": f"2 x mat{a.contact_n} stack after 8 Newton iterations", **two_level(lambda s: contact_ctx(a.contact_n, s), 8, a.reps)}}
+        if a.large_n:
+            rec["contact_large_matrix"] = {"workload": f"3 x mat{a.large_n} stack after 2 Newton iterations", **two_level(lambda s: contact_ctx(a.large_n, s, layers=3), 2, a.reps)}
+        else:
+            rec["contact_large_matrix"] = "not measured"
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print(json.dumps(rec))
+        sys.exit(0)
+    a.out = a.out or os.path.join("profiles", "pcg_bench.json")
     rec = {"device": "MI355X", "headline_matrix": {"workload": f"mat{a.n} twist after 10 Newton iterations", **per_solve(lambda s: twist_ctx(a.n, s), 10, a.reps)},
            "contact_matrix": {"workload": f"2 x mat{a.contact_n} stack after 8 Newton iterations", **per_solve(lambda s: contact_ctx(a.contact_n, s), 8, a.reps)},
            "lagged_factor_newton_run": {"workload": f"mat{a.n} twist, {a.newton} Newton iterations, rel_tol 1e-5", **lagged_ages(a.n, a.newton)}}

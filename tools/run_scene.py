@@ -1,7 +1,7 @@
 """Run one of the reference's scene scripts (src/Config.cpp grammar) on the GPU through the C ABI.
-usage: python tools/run_scene.py <scene.txt> [--root DIR] [--steps N] [--status-every K] [--out DIR]
+usage: python tools/run_scene.py <scene.txt> [--root DIR] [--steps N] [--status-every K] [--out DIR] [--precond {0,1,2}]
 `--root` is the directory the script's relative mesh paths are resolved against (the reference resolves them against its
-repository root).  Prints one line per time step; writes `status<N>` checkpoints in the reference's format."""
+repository root).  `--precond` chooses the preconditioner of a `linearSolver AMGCL` scene (0 block Jacobi, the default; 1 lagged Cholesky; 2 two-level).  Prints one line per time step; writes `status<N>` checkpoints in the reference's format."""
 import argparse
 import os
 import sys
@@ -16,13 +16,19 @@ ap.add_argument("--root", default=None)
 ap.add_argument("--steps", type=int, default=None)
 ap.add_argument("--status-every", type=int, default=0)
 ap.add_argument("--out", default=".")
+ap.add_argument("--precond", type=int, choices=(0, 1, 2), default=None)
 args = ap.parse_args()
 
 root = args.root or os.path.dirname(os.path.abspath(args.scene))
 cfg = ss.SceneConfig.parse(open(args.scene).read(), root)
 sc = ss.assemble(cfg, lib.read_tet_mesh)
 print(f"{len(cfg.shapes)} shapes, {sc.V.shape[0]} nodes, {sc.T.shape[0]} tets, {sc.SF.shape[0]} surface triangles, dt = {cfg.dt}")
-c = ss.apply(sc, lib.Context(0, solver=cfg.linear_solver))  # `linearSolver AMGCL` -> the iterative solver
+ctx = lib.Context(0, solver=cfg.linear_solver)  # `linearSolver AMGCL` -> the iterative solver
+if args.precond is not None:
+    if cfg.linear_solver != lib.SOLVER_PCG:
+        sys.exit("--precond needs a scene with `linearSolver AMGCL`")
+    ctx.set_iterative(precond=args.precond)
+c = ss.apply(sc, ctx)
 steps = args.steps if args.steps is not None else int(round(cfg.duration / cfg.dt))
 for step in range(steps):
     t0 = time.time()

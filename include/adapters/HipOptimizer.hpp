@@ -40,6 +40,11 @@
 #include <string>
 #include <vector>
 
+// the component table and the output folder of the reference's main.cpp (:91-92, 1111-1112; Optimizer.cpp:62-63 declares them the same way)
+extern std::vector<int> compVAccSize;
+extern std::vector<int> compFAccSize;
+extern std::string outputFolderPath;
+
 namespace IPC {
 
 enum HipOptimizerMode {
@@ -158,6 +163,7 @@ protected:
     std::vector<std::array<double, 3>> plateVel; // DCOSquash / DCOSquash6: current velocity of every plate
     std::vector<unsigned char> dbcMirror_; // vertexDBCType as last handed to the device (percall)
     std::vector<double> bufV_, bufA_, bufB_, bufC_;
+    int nReportComps = 0; // components handed to the device: those of Mesh<3>, then the mesh collision objects as one more
 
     using Parts::chk;
 
@@ -244,6 +250,7 @@ public:
         double sc[8];
         chk(ipcgpu_opt_get_state(Parts::ctx, nullptr, nullptr, nullptr, sc));
         Base::lastEnergyVal = sc[0];
+        writeSystemReport(true); // Optimizer.cpp:484-506
     }
 
     // Optimizer::solve (Optimizer.cpp:509-602): maxIter time steps; 1 = the animation is over, 0 otherwise
@@ -260,6 +267,7 @@ public:
             Base::innerIterAmt += n;
             Base::globalIterNum++;
             mirrorState();
+            writeSystemReport(false); // Optimizer.cpp:1495-1512, 1799-1816
         }
         return 0;
     }
@@ -284,6 +292,49 @@ public:
     }
 
 protected:
+    // Optimizer::computeSystemEnergy (Optimizer.cpp:3746-3778).  Resident: one deterministic reduction on the device over the state of the last finished
+    // time step (ipcgpu_opt_system_report; result.V_prev of the host mirror already equals result.V then).  Percall: the host arrays are the state.
+    void computeSystemEnergy(std::vector<double>& sysE, std::vector<Eigen::Matrix<double, 1, dim>>& sysM,
+        std::vector<Eigen::Matrix<double, 1, dim>>& sysL) override
+    {
+        if (!resident() || !uploaded) {
+            Base::computeSystemEnergy(sysE, sysM, sysL);
+            return;
+        }
+        bufA_.resize((size_t)nReportComps);
+        bufB_.resize(3 * (size_t)nReportComps);
+        bufC_.resize(3 * (size_t)nReportComps);
+        chk(ipcgpu_opt_system_report(Parts::ctx, bufA_.data(), bufB_.data(), bufC_.data()));
+        const size_t n = nObst ? (size_t)nReportComps - 1 : (size_t)nReportComps; // the reference's files end with the last component of Mesh<3>
+        sysE.assign(bufA_.begin(), bufA_.begin() + n);
+        sysM.resize(n);
+        sysL.resize(n);
+        for (size_t c = 0; c < n; ++c)
+            for (int i = 0; i < 3; ++i) {
+                sysM[c][i] = bufB_[3 * c + i];
+                sysL[c][i] = bufC_[3 * c + i];
+            }
+    }
+
+    // the three files of the reference's precompute() and fullyImplicit[_IP](), neither of which runs in resident mode
+    void writeSystemReport(bool open)
+    {
+        std::vector<double> sysE;
+        std::vector<Eigen::Matrix<double, 1, dim>> sysM, sysL;
+        computeSystemEnergy(sysE, sysM, sysL);
+        if (open) {
+            Base::file_sysE.open(outputFolderPath + "sysE.txt");
+            Base::file_sysM.open(outputFolderPath + "sysM.txt");
+            Base::file_sysL.open(outputFolderPath + "sysL.txt");
+        }
+        for (const auto& i : sysE) Base::file_sysE << i << " ";
+        Base::file_sysE << std::endl;
+        for (const auto& i : sysM) Base::file_sysM << i << " ";
+        Base::file_sysM << std::endl;
+        for (const auto& i : sysL) Base::file_sysL << i << " ";
+        Base::file_sysL << std::endl;
+    }
+
     void mirrorDBC(const Mesh<dim>* data = nullptr)
     {
         const Mesh<dim>& m = data ? *data : Base::result;
@@ -408,6 +459,20 @@ protected:
             fOff += (int)mco->F.rows();
         }
         chk(ipcgpu_set_mesh(ctx, nAll, nT, Vrest.data(), m.F.data(), m.m_YM, m.m_PR, m.density));
+        {
+            // components of the system report: the accumulated sizes main.cpp keeps, then the nodes of the mesh collision objects
+            std::vector<int> nodeEnd(compVAccSize), tetEnd(compFAccSize);
+            if (nodeEnd.empty() || nodeEnd.size() != tetEnd.size() || nodeEnd.back() != nSim || tetEnd.back() != nT) {
+                nodeEnd.assign(1, nSim);
+                tetEnd.assign(1, nT);
+            }
+            if (nObst) {
+                nodeEnd.push_back(nAll);
+                tetEnd.push_back(nT);
+            }
+            chk(ipcgpu_opt_set_components(ctx, (int)nodeEnd.size(), nodeEnd.data(), tetEnd.data()));
+            nReportComps = (int)nodeEnd.size();
+        }
         // components of codimension 2 / 1 / 0 (triangle meshes, `.seg` segments, `.pt` points under `shapes`, main.cpp:948-1005): nodes of no
         // tetrahedron with the masses Mesh<3> gave them (Mesh.cpp:279-345, 405-411)
         std::vector<int> codim;

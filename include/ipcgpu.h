@@ -467,6 +467,21 @@ int ipcgpu_opt_get_dbc_state(ipcgpu_ctx*, double* out4);
 /* Optimizer::velocity (xyz-interleaved), acceleration and dx_Elastic = V - xTilta of the last finished time step
  * (Optimizer.cpp:574-586); any pointer may be null */
 int ipcgpu_opt_get_kinematics(ipcgpu_ctx*, double* vel_3nV, double* acc_3nV, double* dx_elastic_3nV);
+/* The system report, Optimizer::computeSystemEnergy (Optimizer.cpp:3746-3778; written to sysE.txt / sysM.txt / sysL.txt after precompute, :488-506, and
+ * after every time step, :1497-1512, 1801-1816), reduced on the device.  Per mesh component c with nodes [v0, v1) and elements [t0, t1):
+ *   sysE[c] = sum_t vol_t psi(F_t) + sum_v m_v (|x_v - xprev_v|^2 / (2 dt^2) - g . x_v)
+ *   sysM[c] = sum_v p_v,  p_v = m_v (x_v - xprev_v) / dt          sysL[c] = sum_v x_v x p_v
+ * psi: the configured energy (the per-element values of ipcgpu_elastic_energy_per_elem), m_v: the lumped mass (ipcgpu_get_features), g: the gravity of
+ * ipcgpu_opt_init, xprev: the positions the last finished time step started from (result.V_prev at the reference's call sites; equal to x after
+ * ipcgpu_opt_init / ipcgpu_opt_precompute / ipcgpu_opt_load_status, where the kinetic part and the momenta are exactly zero).  Every node of a range
+ * counts (Dirichlet, obstacle and codimensional nodes too).  fp64, no atomics, a fixed summation order: the same state gives the same bits.
+ * ipcgpu_opt_set_components: the accumulated ends of the components as the reference keeps them (compVAccSize / compFAccSize, main.cpp:91-92,
+ * 1111-1112): non-decreasing, the last ones equal to nV / nT (else IPCGPU_ERR_ARG); empty ranges are legal.  Call after ipcgpu_set_mesh (which goes
+ * back to the default: one component, the whole mesh).
+ * ipcgpu_opt_system_report: sysE[nComp], sysM / sysL[3 nComp] component-major, xyz interleaved; any pointer may be null.  After ipcgpu_opt_init
+ * (before: IPCGPU_ERR_STATE); changes no state.  On a sharded context (ipcgpu_ctx_set_shard, world > 1): IPCGPU_ERR_UNSUPPORTED. */
+int ipcgpu_opt_set_components(ipcgpu_ctx*, int nComp, const int* nodeEnd_nComp, const int* tetEnd_nComp);
+int ipcgpu_opt_system_report(ipcgpu_ctx*, double* sysE_nComp, double* sysM_3nComp, double* sysL_3nComp);
 /* Optimizer::saveStatus (Optimizer.cpp:2964-3011) and the `restart <status file>` branch of the Optimizer constructor
  * (Optimizer.cpp:179-248, Config.cpp:513-516): the reference's text checkpoint (timestep / position / velocity / acceleration /
  * dx_Elastic), written with 20 significant digits so that doubles round-trip; files are interchangeable with the reference's.

@@ -198,6 +198,9 @@ int ipcgpu_set_mesh(ipcgpu_ctx* c, int nV, int nT, const double* Vr, const int* 
         c->opt->tetBegin = (int)((long long)nT * c->rank / c->worldSize);
         c->opt->tetEnd = (int)((long long)nT * (c->rank + 1) / c->worldSize);
         c->opt->initialised = false;
+        c->opt->compNodeEnd.clear(); // the component table belongs to the previous mesh: back to one component
+        c->opt->compTetEnd.clear();
+        c->opt->reportPlanValid = false;
         c->opt->selfCollision = false; // surface + contact state belong to the previous mesh
         c->opt->contact = nullptr;
         c->opt->planes.clear();
@@ -1579,6 +1582,25 @@ int ipcgpu_opt_get_kinematics(ipcgpu_ctx* c, double* vel, double* acc, double* d
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
         o.getKinematics(vel, acc, dx);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_opt_set_components(ipcgpu_ctx* c, int nComp, const int* nodeEnd, const int* tetEnd)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        needArg(nComp >= 1 && nodeEnd && tetEnd, "set_components: at least one component and both tables");
+        o.setComponents(nComp, nodeEnd, tetEnd);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* sysL)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        need(o.initialised, "call ipcgpu_opt_init first");
+        o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });
 }

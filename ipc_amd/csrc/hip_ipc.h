@@ -16,6 +16,7 @@
 #include "hip_halfspace.h"
 #include "pcg.h"
 #include "pcg_coarse.h"
+#include "report_plan.h"
 #include <map>
 #include <memory>
 #include <string>
@@ -218,6 +219,18 @@ public:
     void setTimeIntegration(int type, double beta, double gamma);
     void getKinematics(double* vel, double* acc, double* dxElastic);
     void getDbcState(double* out4) const;
+    // Optimizer::computeSystemEnergy (Optimizer.cpp:3746-3778): per component the energy, the linear and the angular momentum, reduced on the device.
+    // d_xStepStart is result.V_prev as the reference's call sites see it (:1497, 1801 run BEFORE V_prev = V of :578 / :588): the positions the last
+    // finished time step started from -- endTimestep swaps it with d_xPrev instead of overwriting x^t in place.  Without setComponents: one component.
+    std::vector<int> compNodeEnd, compTetEnd; // accumulated ends (compVAccSize / compFAccSize, main.cpp:1111-1112)
+    DevBuf<double> d_xStepStart, d_reportRec;
+    DevBuf<int> d_reportSlices, d_reportNodeStart, d_reportTetStart;
+    PinnedBuf<double> h_report;
+    bool reportPlanValid = false;
+    int nReportNodeSlices = 0, nReportSlices = 0;
+    void setComponents(int nComp, const int* nodeEnd, const int* tetEnd);
+    void ensureReportPlan();
+    void systemReport(double* sysE, double* sysM_3, double* sysL_3); // any pointer may be null; changes no state
     void saveStatus(const std::string& path); // Optimizer::saveStatus, Optimizer.cpp:2964-3011
     void loadStatus(const std::string& path); // restart, Optimizer.cpp:179-248
     DevBuf<double> d_vel, d_xPrev, d_searchDir, d_gradient, d_minusG, d_x0, d_partial, d_scalar;

@@ -85,6 +85,7 @@ void HipOptimizer::init(double dt_, bool withGravity)
     d_dxElastic.alloc(n3);
     d_dxElastic.zero(stream);
     d_xPrev.alloc(n3);
+    d_xStepStart.alloc(n3);
     d_searchDir.alloc(n3);
     d_searchDir.zero(stream);
     d_gradient.alloc(n3);
@@ -97,6 +98,7 @@ void HipOptimizer::init(double dt_, bool withGravity)
     h_scalar.alloc(8);
     h_flag.alloc(2);
     HIP_CHECK(hipMemcpyAsync(d_xPrev.p, mesh.d_x.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_xStepStart.p, mesh.d_x.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(mesh.d_xTilde.p, mesh.d_x.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
     for (int c = 0; c < 3; ++c) rotCenter[c] = 0.5 * (mesh.bboxLo[c] + mesh.bboxHi[c]);
     // element shard of this rank (contiguous blocks of the caller's tet order)
@@ -612,6 +614,7 @@ void HipOptimizer::loadStatus(const std::string& path)
     if (in.bad()) throw StateError("read error on status file " + path);
     mesh.d_x.upload(x, stream);
     d_xPrev.upload(x, stream);
+    d_xStepStart.upload(x, stream); // V_prev = V (Optimizer.cpp:247): a report right after a restart has no kinetic part
     d_vel.upload(vel, stream);
     d_acc.upload(acc, stream);
     d_dxElastic.upload(dx, stream);
@@ -1685,14 +1688,71 @@ void HipOptimizer::endTimestep()
     specAsmValid = false;
     Tic t(timers[11], stream);
     t.nosync = fastPath(); // (the update is one kernel on the stream; the next time step's batch synchronises)
+    // the update writes x^t of the next step into the second array: what d_xPrev held, the positions this step started from, stays for the system report
+    std::swap(d_xPrev.p, d_xStepStart.p);
     if (timeIntegration == 1)
         launch_nm_update(mesh.nV, mesh.d_dbc.p, mesh.d_x.p, d_xPrev.p, d_vel.p, d_acc.p, d_dxElastic.p, mesh.d_xTilde.p, dt, betaNM, gammaNM,
             gravity[0], gravity[1], gravity[2], stream);
     else
-        launch_be_update(mesh.nV, mesh.d_dbc.p, mesh.d_x.p, d_xPrev.p, d_vel.p, d_acc.p, d_dxElastic.p, mesh.d_xTilde.p, dt, gravity[0],
+        launch_be_update(mesh.nV, mesh.d_dbc.p, mesh.d_x.p, d_xStepStart.p, d_xPrev.p, d_vel.p, d_acc.p, d_dxElastic.p, mesh.d_xTilde.p, dt, gravity[0],
             gravity[1], gravity[2], stream);
     computeDampingMtr(); // Optimizer.cpp:593-595
     globalIterNum++;
+}
+
+// ---- system report (Optimizer::computeSystemEnergy, Optimizer.cpp:3746-3778) ----------------------------------------------------
+void HipOptimizer::setComponents(int nComp, const int* nodeEnd, const int* tetEnd_)
+{
+    if (!reportEndsValid(nComp, nodeEnd, mesh.nV) || !reportEndsValid(nComp, tetEnd_, mesh.nT))
+        throw ArgError("set_components: the accumulated ends must be non-decreasing and end at the node / element count");
+    compNodeEnd.assign(nodeEnd, nodeEnd + nComp);
+    compTetEnd.assign(tetEnd_, tetEnd_ + nComp);
+    reportPlanValid = false;
+}
+
+void HipOptimizer::ensureReportPlan()
+{
+    if (reportPlanValid) return;
+    if (compNodeEnd.empty() || compNodeEnd.back() != mesh.nV || compTetEnd.back() != mesh.nT) { // no table (or one of another mesh): the whole mesh
+        compNodeEnd.assign(1, mesh.nV);
+        compTetEnd.assign(1, mesh.nT);
+    }
+    const int nComp = (int)compNodeEnd.size();
+    std::vector<ReportSlice> slices;
+    std::vector<int> nodeStart, tetStart;
+    buildReportSlices(nComp, compNodeEnd.data(), 256, slices, nodeStart);
+    nReportNodeSlices = (int)slices.size();
+    buildReportSlices(nComp, compTetEnd.data(), 256, slices, tetStart);
+    nReportSlices = (int)slices.size();
+    static_assert(sizeof(ReportSlice) == 3 * sizeof(int), "the kernel reads the list as int triples");
+    std::vector<int> flat(3 * slices.size() + 1);
+    std::memcpy(flat.data(), slices.data(), slices.size() * sizeof(ReportSlice));
+    d_reportSlices.upload(flat, stream);
+    d_reportNodeStart.upload(nodeStart, stream);
+    d_reportTetStart.upload(tetStart, stream);
+    d_reportRec.alloc(7 * slices.size() + 1);
+    h_report.alloc(7 * (size_t)nComp);
+    HIP_CHECK(hipStreamSynchronize(stream)); // the staging vectors go out of scope
+    reportPlanValid = true;
+}
+
+void HipOptimizer::systemReport(double* sysE, double* sysM, double* sysL)
+{
+    if (worldSize > 1) throw UnsupportedError("system report on a sharded context (multi-rank reports are not implemented)");
+    ensureReportPlan();
+    const int nComp = (int)compNodeEnd.size();
+    launch_system_report(view(), d_xStepStart.p, d_reportSlices.p, nReportNodeSlices, nReportSlices, d_reportNodeStart.p, d_reportTetStart.p, nComp, dt,
+        gravity, d_reportRec.p, h_report.dev, stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (int c = 0; c < nComp; ++c) {
+        const double* r = h_report.p + 7 * (size_t)c;
+        if (sysE) sysE[c] = r[0];
+        for (int i = 0; i < 3; ++i) {
+            if (sysM) sysM[3 * (size_t)c + i] = r[1 + i];
+            if (sysL) sysL[3 * (size_t)c + i] = r[4 + i];
+        }
+    }
 }
 
 int HipOptimizer::solveTimestep(int maxIter)

@@ -38,6 +38,12 @@ const char* assemble_kernel_name();
 void launch_energy(const ElemView& v, double coef, bool withInertia, bool ownerRank, double* partial, int partialCap,
     double* out, hipStream_t s);
 void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s);
+// System report (Optimizer::computeSystemEnergy, Optimizer.cpp:3746-3778): out[7 c + (0 | 1..3 | 4..6)] = energy | linear | angular momentum of
+// component c, sum_t vol psi + sum_v m (|x - xStart|^2 / (2 dt^2) - g . x), p_v = m (x - xStart) / dt, x_v x p_v.  slices: (component, begin, end)
+// triples of report_plan.h, the nNodeSlices node slices first; nodeStart / tetStart[nComp + 1]: a component's slices in that list; rec: 7 nSlices
+// doubles of scratch.  Deterministic: fixed slices, fixed summation order, no atomics.
+void launch_system_report(const ElemView& v, const double* xStart, const int* slices, int nNodeSlices, int nSlices, const int* nodeStart,
+    const int* tetStart, int nComp, double dt, const double* g3, double* rec, double* out, hipStream_t s);
 
 // inversion: flag[0] |= any det < 0 ; step bound: per-shard min written to *outMin (must be preset to +inf bits)
 void launch_check_inversion(const ElemView& v, int* flag, hipStream_t s);
@@ -65,11 +71,12 @@ void launch_csr_symv(int nRows, const int* ia, const int* ja, const double* a, c
 void launch_apply_host_updates(long long nnz, const double* delta, const unsigned char* mask, const double* setVal, double* a, hipStream_t s);
 void launch_precond_diag(int nRows, const int* ia, const double* a, const double* in, double* out, hipStream_t s);
 // BE update (Optimizer.cpp:570-580, 1236-1257): dxElastic = x - xTilde; acc = (vel_new - vel) / dt; vel = (x - xPrev) / dt;
-// xPrev = x; xTilde = xPrev + dt vel + dt^2 g (DBC: xPrev)
-void launch_be_update(int nV, const int* dbc, const double* x, double* xPrev, double* vel, double* acc, double* dxElastic, double* xTilde,
+// xPrevOut = x; xTilde = x + dt vel + dt^2 g (DBC: x).  xPrevOut is a second array (never xPrev itself): the caller swaps the two and
+// so keeps the positions the step started from for the system report without a copy
+void launch_be_update(int nV, const int* dbc, const double* x, const double* xPrev, double* xPrevOut, double* vel, double* acc, double* dxElastic, double* xTilde,
     double dt, double gx, double gy, double gz, hipStream_t s);
 // Newmark update (Optimizer.cpp:582-590, 1259-1277)
-void launch_nm_update(int nV, const int* dbc, const double* x, double* xPrev, double* vel, double* acc, double* dxElastic, double* xTilde,
+void launch_nm_update(int nV, const int* dbc, const double* x, double* xPrevOut, double* vel, double* acc, double* dxElastic, double* xTilde,
     double dt, double beta, double gamma, double gx, double gy, double gz, hipStream_t s);
 // scripted Dirichlet groups (Mesh::DirichletBCs / scripted component velocities, AnimScripter.cpp:1413-1462)
 struct DbcMotion {

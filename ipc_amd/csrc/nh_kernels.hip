@@ -180,6 +180,82 @@ __global__ __launch_bounds__(BLOCK) void k_energy_per_elem(ElemView v, double* _
     out[t] = v.vol[t] * elem_psi(v, F, v.mu[t], v.lam[t]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// System report (Optimizer::computeSystemEnergy, Optimizer.cpp:3746-3778): per component the energy, the linear momentum and the angular momentum about
+// the origin -- seven doubles.  No atomics, every sum in a fixed order: two calls on one state give the same bits.
+//   pass 1  workgroup b takes slice b of the host-built list (report_plan.h: at most BLOCK consecutive nodes, or elements, of ONE component; the node
+//           slices come first) and writes one record of REPORT_Q partial sums -- an element slice only entry 0 of it
+//   pass 2  one wave per component sums the records of its slices: lane l takes slices l, l + 64, ... in index order, then the shuffle tree
+constexpr int REPORT_Q = 7; // E, M xyz, L xyz
+
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_report_slices(ElemView v, const double* __restrict__ xStart, const int* __restrict__ slices, int nNodeSlices,
+    double dt, double gx, double gy, double gz, double* __restrict__ rec)
+{
+    __shared__ double sm[REPORT_Q][BLOCK / 64];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = slices[3 * b + 1] + threadIdx.x;
+    const bool live = i < slices[3 * b + 2];
+    const int nq = b < nNodeSlices ? REPORT_Q : 1; // uniform over the workgroup
+    double q[REPORT_Q] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    if (live && b < nNodeSlices) {
+        const d3 x = ld3(v.x, i), x0 = ld3(xStart, i);
+        const double m = v.mass[i];
+        const double dx = x.x - x0.x, dy = x.y - x0.y, dz = x.z - x0.z;
+        q[0] = m * ((dx * dx + dy * dy + dz * dz) / (dt * dt) / 2.0 - (gx * x.x + gy * x.y + gz * x.z)); // Optimizer.cpp:3765
+        const double mdt = m / dt; // :3767
+        q[1] = mdt * dx;
+        q[2] = mdt * dy;
+        q[3] = mdt * dz;
+        q[4] = x.y * q[3] - x.z * q[2]; // :3771
+        q[5] = x.z * q[1] - x.x * q[3];
+        q[6] = x.x * q[2] - x.y * q[1];
+    }
+    else if (live) {
+        const int4 tv = v.tet[i];
+        double A[9], F[9];
+        load_A(v, i, A);
+        deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
+        q[0] = v.vol[i] * elem_psi(v, F, v.mu[i], v.lam[i]); // the value of k_energy_per_elem (:3751, 3762)
+    }
+#pragma unroll
+    for (int k = 0; k < REPORT_Q; ++k)
+        if (k < nq) {
+            const double r = wave_sum(q[k]);
+            if (lane == 0) sm[k][wv] = r;
+        }
+    __syncthreads();
+    if (threadIdx.x < nq) {
+        double r = 0.0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) r += sm[threadIdx.x][w];
+        rec[REPORT_Q * (size_t)b + threadIdx.x] = r;
+    }
+}
+
+// nodeStart / tetStart[nComp + 1]: the slices of component c in the list of pass 1; out: REPORT_Q doubles per component
+__global__ __launch_bounds__(64) void k_report_components(const double* __restrict__ rec, const int* __restrict__ nodeStart,
+    const int* __restrict__ tetStart, double* __restrict__ out)
+{
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int n0 = nodeStart[c], n1 = nodeStart[c + 1], t0 = tetStart[c], t1 = tetStart[c + 1];
+#pragma unroll
+    for (int k = 0; k < REPORT_Q; ++k) {
+        double a = 0.0;
+        for (int j = n0 + lane; j < n1; j += 64) a += rec[REPORT_Q * (size_t)j + k];
+        if (k == 0)
+            for (int j = t0 + lane; j < t1; j += 64) a += rec[REPORT_Q * (size_t)j];
+        a = wave_sum(a);
+        if (lane == 0) out[REPORT_Q * (size_t)c + k] = a;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_check_inversion(ElemView v, int* flag)
 {
     const int t = v.tetBegin + blockIdx.x * BLOCK + threadIdx.x;
@@ -426,7 +502,7 @@ __global__ void k_precond_diag(int nRows, const int* __restrict__ ia, const doub
 }
 // Newmark update (Optimizer.cpp:582-590, 1259-1277): vel += dt (1 - gamma) acc; acc = (x - xTilde) / (dt^2 beta) + g;
 // vel += dt gamma acc; xPrev = x; xTilde = xPrev + dt vel + beta dt^2 g + (1/2 - beta) dt^2 acc (DBC: xPrev)
-__global__ void k_nm_update(int nV, const int* __restrict__ dbc, const double* __restrict__ x, double* __restrict__ xPrev,
+__global__ void k_nm_update(int nV, const int* __restrict__ dbc, const double* __restrict__ x, double* __restrict__ xPrevOut,
     double* __restrict__ vel, double* __restrict__ acc, double* __restrict__ dxElastic, double* __restrict__ xTilde, double dt, double beta,
     double gamma, double gx, double gy, double gz)
 {
@@ -444,11 +520,11 @@ __global__ void k_nm_update(int nV, const int* __restrict__ dbc, const double* _
     vel[i] = vl;
     acc[i] = a;
     const double xp = x[i];
-    xPrev[i] = xp;
+    xPrevOut[i] = xp;
     xTilde[i] = dbc[v] != 0 ? xp : xp + (vl * dt + beta * (dtSq * g) + (0.5 - beta) * (dtSq * a));
 }
-__global__ void k_be_update(int nV, const int* __restrict__ dbc, const double* __restrict__ x, double* __restrict__ xPrev,
-    double* __restrict__ vel, double* __restrict__ acc, double* __restrict__ dxElastic, double* __restrict__ xTilde, double dt, double gx,
+__global__ void k_be_update(int nV, const int* __restrict__ dbc, const double* __restrict__ x, const double* __restrict__ xPrev,
+    double* __restrict__ xPrevOut, double* __restrict__ vel, double* __restrict__ acc, double* __restrict__ dxElastic, double* __restrict__ xTilde, double dt, double gx,
     double gy, double gz)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -460,7 +536,7 @@ __global__ void k_be_update(int nV, const int* __restrict__ dbc, const double* _
     dxElastic[i] = xi - xTilde[i]; // Optimizer.cpp:574
     acc[i] = (vi - vel[i]) / dt; // :577
     vel[i] = vi;
-    xPrev[i] = xi;
+    xPrevOut[i] = xi;
     xTilde[i] = (dbc[v] != 0) ? xi : (xi + (vi * dt + dt * dt * g));
 }
 __global__ void k_twist_dir(int nH, const int* __restrict__ ids, const double* __restrict__ ang, double cy, double cz,
@@ -714,6 +790,13 @@ void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s)
 {
     if (v.nT) hipLaunchKernelGGL(k_energy_per_elem, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
 }
+void launch_system_report(const ElemView& v, const double* xStart, const int* slices, int nNodeSlices, int nSlices, const int* nodeStart,
+    const int* tetStart, int nComp, double dt, const double* g3, double* rec, double* out, hipStream_t s)
+{
+    if (nSlices)
+        hipLaunchKernelGGL(k_report_slices, dim3(nSlices), dim3(BLOCK), 0, s, v, xStart, slices, nNodeSlices, dt, g3[0], g3[1], g3[2], rec);
+    hipLaunchKernelGGL(k_report_components, dim3(nComp), dim3(64), 0, s, rec, nodeStart, tetStart, out);
+}
 void launch_check_inversion(const ElemView& v, int* flag, hipStream_t s)
 {
     const int n = v.tetEnd - v.tetBegin;
@@ -783,17 +866,17 @@ void launch_precond_diag(int nRows, const int* ia, const double* a, const double
 {
     if (nRows) hipLaunchKernelGGL(k_precond_diag, dim3(nblk(nRows)), dim3(BLOCK), 0, s, nRows, ia, a, in, out);
 }
-void launch_nm_update(int nV, const int* dbc, const double* x, double* xPrev, double* vel, double* acc, double* dxElastic, double* xTilde,
+void launch_nm_update(int nV, const int* dbc, const double* x, double* xPrevOut, double* vel, double* acc, double* dxElastic, double* xTilde,
     double dt, double beta, double gamma, double gx, double gy, double gz, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_nm_update, dim3((3 * nV + 255) / 256), dim3(256), 0, s, nV, dbc, x, xPrev, vel, acc, dxElastic, xTilde, dt, beta, gamma,
+    hipLaunchKernelGGL(k_nm_update, dim3((3 * nV + 255) / 256), dim3(256), 0, s, nV, dbc, x, xPrevOut, vel, acc, dxElastic, xTilde, dt, beta, gamma,
         gx, gy, gz);
 }
-void launch_be_update(int nV, const int* dbc, const double* x, double* xPrev, double* vel, double* acc, double* dxElastic, double* xTilde,
+void launch_be_update(int nV, const int* dbc, const double* x, const double* xPrev, double* xPrevOut, double* vel, double* acc, double* dxElastic, double* xTilde,
     double dt, double gx, double gy, double gz, hipStream_t s)
 {
     if (nV)
-        hipLaunchKernelGGL(k_be_update, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, x, xPrev, vel, acc, dxElastic, xTilde, dt, gx, gy,
+        hipLaunchKernelGGL(k_be_update, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, x, xPrev, xPrevOut, vel, acc, dxElastic, xTilde, dt, gx, gy,
             gz);
 }
 void launch_warm_dir(int nV, const int* dbc, const double* vel, const double* dx, double dt, const double* cgDtSqG3, double ce, double* p,

@@ -287,6 +287,7 @@ class Context:
         V = np.asfortranarray(V, dtype=np.float64)
         F = np.asfortranarray(F, dtype=np.int32)
         self.nV, self.nT = V.shape[0], F.shape[0]
+        self._ncomp = 1  # a new mesh is one component until set_components
         self._chk(self._L.ipcgpu_set_mesh(self.h, C.c_int(self.nV), C.c_int(self.nT), _dp(V), _ip(F),
                                           C.c_double(YM), C.c_double(PR), C.c_double(density)))
 
@@ -297,6 +298,22 @@ class Context:
     def set_component_material(self, node_range, tet_range, density, YM, PR):
         self._chk(self._L.ipcgpu_set_component_material(self.h, C.c_int(node_range[0]), C.c_int(node_range[1]), C.c_int(tet_range[0]),
                                                         C.c_int(tet_range[1]), C.c_double(density), C.c_double(YM), C.c_double(PR)))
+
+    def set_components(self, node_end, tet_end):
+        """The mesh components of the system report: accumulated node / element ends (the reference's compVAccSize / compFAccSize)."""
+        node_end, tet_end = _i32(node_end).ravel(), _i32(tet_end).ravel()
+        if len(node_end) != len(tet_end):
+            raise ValueError("set_components: one node end and one element end per component")
+        self._chk(self._L.ipcgpu_opt_set_components(self.h, C.c_int(len(node_end)), _ip(node_end), _ip(tet_end)))
+        self._ncomp = len(node_end)
+
+    def system_report(self):
+        """Optimizer::computeSystemEnergy on the device: (E[nComp], M[nComp, 3], L[nComp, 3]) -- energy, linear momentum and angular momentum about
+        the origin per component, for the state after precompute() or the last finished time step."""
+        n = getattr(self, "_ncomp", 1)
+        E, M, L = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
+        self._chk(self._L.ipcgpu_opt_system_report(self.h, _dp(E), _dp(M), _dp(L)))
+        return E, M, L
 
     def set_energy_type(self, name):
         """Scene-script `energy NH|FCR`."""

@@ -1024,6 +1024,10 @@ def apply(sc, be):
     """Drive a backend (the ctypes `Context` of ipc_amd/lib.py, or an adapter over the oracle with the same method names)."""
     cfg = sc.cfg
     be.set_mesh(sc.V, sc.T, YM=cfg.YM, PR=cfg.PR, density=cfg.rho)
+    if hasattr(be, "set_components"):
+        # the components of the system report (compVAccSize / compFAccSize, main.cpp:1111-1112): the shapes in script order, then every mesh
+        # collision object as a component of its own (they are not part of the reference's Mesh<3>: its files end with the last shape)
+        be.set_components(sc.node_ranges[1:], sc.tet_ranges[1:])
     if sc.codim_nodes is not None:
         be.set_codim_nodes(sc.codim_nodes, sc.codim_mass)
     be.set_energy_type(cfg.energy)
@@ -1101,3 +1105,20 @@ def apply(sc, be):
         be.load_status(cfg.restart)
     be.precompute()
     return be
+
+
+class ReportWriter:
+    """The reference's system report files (Optimizer.cpp:488-506, 1497-1512, 1801-1816): `sysE.txt`, `sysM.txt`, `sysL.txt` in `folder`, one line per
+    call of write() -- after precompute() and after every time step.  Values in the reference's order (components in sequence, a component's x y z
+    adjacent), space separated; the digits are `%.17g`, which reads back to the same doubles, not the reference's 6 significant digits."""
+
+    def __init__(self, folder):
+        os.makedirs(folder, exist_ok=True)
+        self.paths = {k: os.path.join(folder, f"sys{k}.txt") for k in "EML"}
+        for p in self.paths.values():
+            open(p, "w").close()
+
+    def write(self, be):
+        for k, a in zip("EML", be.system_report()):
+            with open(self.paths[k], "a") as f:
+                f.write(" ".join("%.17g" % x for x in np.asarray(a, dtype=np.float64).ravel()) + "\n")

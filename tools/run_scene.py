@@ -1,7 +1,8 @@
 """Run one of the reference's scene scripts (src/Config.cpp grammar) on the GPU through the C ABI.
-usage: python tools/run_scene.py <scene.txt> [--root DIR] [--steps N] [--status-every K] [--out DIR] [--precond {0,1,2}]
+usage: python tools/run_scene.py <scene.txt> [--root DIR] [--steps N] [--status-every K] [--out DIR] [--precond {0,1,2}] [--report DIR]
 `--root` is the directory the script's relative mesh paths are resolved against (the reference resolves them against its
-repository root).  `--precond` chooses the preconditioner of a `linearSolver AMGCL` scene (0 block Jacobi, the default; 1 lagged Cholesky; 2 two-level).  Prints one line per time step; writes `status<N>` checkpoints in the reference's format."""
+repository root).  `--precond` chooses the preconditioner of a `linearSolver AMGCL` scene (0 block Jacobi, the default; 1 lagged Cholesky; 2 two-level).  `--report DIR` writes the reference's system report, `DIR/sysE.txt`, `sysM.txt` and `sysL.txt`: energy, linear and angular momentum per mesh component, one line
+after precompute() and one per time step (17 significant digits).  Prints one line per time step; writes `status<N>` checkpoints in the reference's format."""
 import argparse
 import os
 import sys
@@ -17,6 +18,7 @@ ap.add_argument("--steps", type=int, default=None)
 ap.add_argument("--status-every", type=int, default=0)
 ap.add_argument("--out", default=".")
 ap.add_argument("--precond", type=int, choices=(0, 1, 2), default=None)
+ap.add_argument("--report", default=None)
 args = ap.parse_args()
 
 root = args.root or os.path.dirname(os.path.abspath(args.scene))
@@ -29,6 +31,9 @@ if args.precond is not None:
         sys.exit("--precond needs a scene with `linearSolver AMGCL`")
     ctx.set_iterative(precond=args.precond)
 c = ss.apply(sc, ctx)
+report = ss.ReportWriter(args.report) if args.report else None
+if report:
+    report.write(c)
 steps = args.steps if args.steps is not None else int(round(cfg.duration / cfg.dt))
 for step in range(steps):
     t0 = time.time()
@@ -37,6 +42,8 @@ for step in range(steps):
     st = c.state()
     cs = c.contact_state() if cfg.self_collision or cfg.half_spaces else {}
     print(f"step {st['timestep']:5d}  {it:4d} Newton iterations  {1e3 * (time.time() - t0):8.1f} ms  E = {st['E']:.6e}  active = {cs.get('nActive', 0)}", flush=True)
+    if report:
+        report.write(c)
     if args.status_every and st["timestep"] % args.status_every == 0:
         c.save_status(os.path.join(args.out, f"status{st['timestep']}"))
 c.close()

@@ -117,6 +117,22 @@ int ipcgpu_check_inversion(ipcgpu_ctx*, int* ok);
 int ipcgpu_elastic_energy(ipcgpu_ctx*, double coef, double* energy);
 /* Energy::getEnergyValPerElemBySVD (Energy.hpp:66) */
 int ipcgpu_elastic_energy_per_elem(ipcgpu_ctx*, double* perElem_nT);
+/* Stress fields of the positions the context holds (no counterpart in the reference, which writes positions and energies only).  Per element the
+ * Cauchy stress sigma = P F^T / J of the configured energy (ipcgpu_set_energy_type), P the first Piola-Kirchhoff stress the gradient is built from,
+ * F the deformation gradient, J = det F, mu / lam the element's Lame parameters:
+ *   NH   sigma = (mu (F F^T - I) + lam ln J I) / J
+ *   FCR  sigma = 2 mu (F - R) F^T / J + lam (J - 1) I,  R = U V^T the rotation of the SVD F = U diag(s) V^T (only s_2 may be negative)
+ * perElem: column-major nT x 8 -- sxx, syy, szz, sxy, syz, sxz (the symmetric-tensor order of VTK), the von Mises stress sqrt(3/2 dev sigma : dev
+ * sigma), J.  An element without stiffness (mu = lam = 0) gets zeros and its J.  An NH element with J <= 0 has no stress: NaN in all eight entries,
+ * and *nInvalid counts such elements; FCR is finite for inverted elements (nInvalid = 0) as long as J != 0 -- at J = 0 exactly P F^T / J is inf or
+ * NaN, uncounted.
+ * perNode: column-major nV x 8 -- the mean of the tensors of the node's elements weighted by their rest volumes (summed in ascending element
+ * index), the von Mises stress OF THAT MEAN TENSOR (not the mean of the elements' von Mises stresses), the sum of those rest volumes (a sum that is exactly zero has no mean: NaN).  A node without
+ * an element (surface-only and codimensional nodes) gets zeros; a NaN element makes the seven stress entries of its four nodes NaN (the volume sum stays).
+ * Any pointer may be null; the nodal pass is skipped when perNode is null.  Valid after ipcgpu_set_mesh (positions: ipcgpu_set_positions) and at
+ * any point between time steps after ipcgpu_opt_init (before a mesh is set: IPCGPU_ERR_STATE); changes no state.  fp64, a fixed summation order, no
+ * floating-point atomics: the same state gives the same bits.  On a sharded context (ipcgpu_ctx_set_shard, world > 1): IPCGPU_ERR_UNSUPPORTED. */
+int ipcgpu_elastic_stress(ipcgpu_ctx*, double* perElem_nTx8, double* perNode_nVx8, int* n_invalid);
 /* Energy::computeGradient (Energy.hpp:47, Energy.cpp:245-289) */
 int ipcgpu_elastic_gradient(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 /* Energy::computeHessian (Energy.hpp:53, Energy.cpp:292-331) into the context's CSR values:

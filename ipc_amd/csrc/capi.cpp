@@ -149,6 +149,7 @@ int ipcgpu_ctx_destroy(ipcgpu_ctx* c)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         c->contact.reset();
+        c->stress.reset();
         c->opt.reset();
         c->lin.reset();
         c->mesh.reset();
@@ -205,6 +206,7 @@ int ipcgpu_set_mesh(ipcgpu_ctx* c, int nV, int nT, const double* Vr, const int* 
         c->opt->contact = nullptr;
         c->opt->planes.clear();
         c->contact.reset();
+        c->stress.reset(); // the incidence list belongs to the previous mesh
         return IPCGPU_OK;
     });
 }
@@ -430,6 +432,43 @@ int ipcgpu_elastic_energy_per_elem(ipcgpu_ctx* c, double* out)
         tmp.alloc(c->mesh->nT);
         launch_energy_per_elem(o.view(), tmp.p, c->stream);
         tmp.download(out, c->mesh->nT, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_elastic_stress(ipcgpu_ctx* c, double* perElem, double* perNode, int* nInvalid)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (c->worldSize > 1) throw UnsupportedError("stress fields on a sharded context (multi-rank fields are not implemented)");
+        if (!c->stress) {
+            c->stress.reset(new StressFields);
+            c->stress->d_invalid.alloc(1);
+            c->stress->h_invalid.alloc(1);
+        }
+        StressFields& sf = *c->stress;
+        const size_t nT = (size_t)m.nT, nV = (size_t)m.nV;
+        sf.d_elem.alloc(8 * nT);
+        sf.d_invalid.zero(c->stream);
+        launch_stress_elements(c->opt->view(), sf.d_elem.p, sf.d_invalid.p, c->stream);
+        launch_publish(sf.d_invalid.p, sf.h_invalid.dev, 1, c->stream);
+        if (perNode) {
+            if (!sf.planValid) {
+                std::vector<int> ptr, elems;
+                if (!buildNodeElementIncidence(m.nV, m.nT, m.F.data(), ptr, elems)) throw StateError("the mesh has an element index out of range");
+                sf.d_ptr.upload(ptr, c->stream);
+                sf.d_elems.upload(elems, c->stream);
+                HIP_CHECK(hipStreamSynchronize(c->stream)); // the staging vectors go out of scope
+                sf.planValid = true;
+            }
+            sf.d_node.alloc(8 * nV);
+            launch_stress_nodes(m.nV, m.nT, sf.d_ptr.p, sf.d_elems.p, m.d_vol.p, sf.d_elem.p, sf.d_node.p, c->stream);
+        }
+        HIP_CHECK(hipGetLastError());
+        if (perElem && nT) HIP_CHECK(hipMemcpyAsync(perElem, sf.d_elem.p, 8 * nT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (perNode) HIP_CHECK(hipMemcpyAsync(perNode, sf.d_node.p, 8 * nV * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (nInvalid) *nInvalid = sf.h_invalid.p[0];
         return IPCGPU_OK;
     });
 }

@@ -17,6 +17,7 @@
 #include "pcg.h"
 #include "pcg_coarse.h"
 #include "report_plan.h"
+#include "stress_plan.h"
 #include <map>
 #include <memory>
 #include <string>
@@ -399,6 +400,15 @@ public:
     void computeXTilta();
 };
 
+// Buffers of ipcgpu_elastic_stress: the incidence list of the current mesh (built at the first call that asks for nodal values, dropped with the
+// mesh), the two record arrays, and the count of invalid elements with its mapped host copy
+struct StressFields {
+    bool planValid = false;
+    DevBuf<int> d_ptr, d_elems, d_invalid;
+    DevBuf<double> d_elem, d_node;
+    PinnedBuf<int> h_invalid;
+};
+
 } // namespace ipcgpu
 
 struct ipcgpu_ctx {
@@ -408,6 +418,7 @@ struct ipcgpu_ctx {
     std::unique_ptr<ipcgpu::HipLinSysSolver> lin;
     std::unique_ptr<ipcgpu::HipOptimizer> opt;
     std::unique_ptr<ipcgpu::HipContact> contact;
+    std::unique_ptr<ipcgpu::StressFields> stress;
     int rank = 0, worldSize = 1;
     // point-to-point exchange hooks of the sharded solver (ipcgpu_opt_set_exchange[_stream]); stored here as opaque pointers of the C ABI's types
     void* exchange = nullptr;

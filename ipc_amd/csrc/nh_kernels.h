@@ -38,6 +38,13 @@ const char* assemble_kernel_name();
 void launch_energy(const ElemView& v, double coef, bool withInertia, bool ownerRank, double* partial, int partialCap,
     double* out, hipStream_t s);
 void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s);
+// Stress fields (ipcgpu_elastic_stress; no counterpart in the reference).  rec: 8 nT doubles, rec[k * nT + t] with k = sxx, syy, szz, sxy, syz, sxz of
+// the Cauchy stress P F^T / J of the configured energy, the von Mises stress, J = det F; an element without stiffness gets zeros and its J, an NH element
+// with J <= 0 eight NaN and one count in *nInvalid (device memory, zeroed by the caller).  launch_stress_nodes: out[k * nV + v] = the rest-volume-weighted
+// mean of the records of node v's elements (ptr / elems: stress_plan.h, ascending), the von Mises stress of that mean, the sum of the volumes; zeros for
+// a node without an element.  Deterministic: fixed order, no floating-point atomics.
+void launch_stress_elements(const ElemView& v, double* rec, int* nInvalid, hipStream_t s);
+void launch_stress_nodes(int nV, int nT, const int* ptr, const int* elems, const double* vol, const double* rec, double* out, hipStream_t s);
 // System report (Optimizer::computeSystemEnergy, Optimizer.cpp:3746-3778): out[7 c + (0 | 1..3 | 4..6)] = energy | linear | angular momentum of
 // component c, sum_t vol psi + sum_v m (|x - xStart|^2 / (2 dt^2) - g . x), p_v = m (x - xStart) / dt, x_v x p_v.  slices: (component, begin, end)
 // triples of report_plan.h, the nNodeSlices node slices first; nodeStart / tetStart[nComp + 1]: a component's slices in that list; rec: 7 nSlices

@@ -181,6 +181,112 @@ __global__ __launch_bounds__(BLOCK) void k_energy_per_elem(ElemView v, double* _
 }
 
 // ------------------------------------------------------------------------------------------------
+// Stress fields (ipcgpu_elastic_stress; the reference has no counterpart).  Records of STRESS_Q doubles, SoA: out[k * n + i] with
+// k = sxx, syy, szz, sxy, syz, sxz (VTK's symmetric-tensor order), von Mises, and J (elements) or sum of rest volumes (nodes).
+//   pass 1  one lane per element: F as the energy kernels form it, the Cauchy stress sigma = P F^T / J of the configured energy in the closed forms
+//             NH   sigma = (mu (F F^T - I) + lam ln J I) / J                       (P = mu (F - F^-T) + lam ln J F^-T, F^-T F^T = I)
+//             FCR  sigma = 2 mu (F - R) F^T / J + lam (J - 1) I,  R = U V^T        (P = 2 mu (F - R) + lam (J - 1) cof F, cof F F^T = J I)
+//           which never form F^-T or cof F.  (F - R) F^T is symmetric up to round-off only: the mean of the two off-diagonal entries is stored.
+//           An element without stiffness (mu = lam = 0, the convention of piola) gets zeros and its J; an NH element with J <= 0 has no logarithm:
+//           NaN in all eight slots, and it is counted.  FCR is finite for every F with J != 0, inverted ones included (at J = 0 exactly the division by J
+//           gives inf / NaN like any other evaluation of P F^T / J; such an element is not counted).
+//   pass 2  one lane per node: the rest-volume-weighted mean of the records of its elements, walked in ascending element index (stress_plan.h), the
+//           von Mises stress OF THAT MEAN, and the volume sum.  A NaN record makes the stress entries of its four nodes NaN; a node without an element gets zeros.
+// No atomics on any floating-point value and a fixed order everywhere: the same state gives the same bits.
+constexpr int STRESS_Q = 8; // entries of a record: six tensor components, von Mises, J | volume sum
+
+__device__ __forceinline__ double von_mises(double sxx, double syy, double szz, double sxy, double syz, double sxz)
+{
+    // sqrt(3/2 dev : dev) without forming the mean: 1/2 ((sxx - syy)^2 + (syy - szz)^2 + (szz - sxx)^2) + 3 (sxy^2 + syz^2 + sxz^2)
+    const double a = sxx - syy, b = syy - szz, c = szz - sxx;
+    return sqrt(0.5 * (a * a + b * b + c * c) + 3.0 * (sxy * sxy + syz * syz + sxz * sxz));
+}
+
+template <bool FCR>
+__global__ __launch_bounds__(BLOCK) void k_stress_elements(ElemView v, double* __restrict__ out, int* __restrict__ nInvalid)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    bool invalid = false;
+    if (t < v.nT) {
+        const int4 tv = v.tet[t];
+        double A[9], F[9];
+        load_A(v, t, A);
+        deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
+        const double mu = v.mu[t], lam = v.lam[t];
+        const double J = det3(F);
+        double s[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, vm = 0.0, Jout = J; // {xx, yy, zz, xy, yz, xz}
+        if (!(mu == 0.0 && lam == 0.0)) {
+            if (!FCR && !(J > 0.0)) {
+                invalid = true;
+                const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) s[k] = nan;
+                vm = Jout = nan;
+            }
+            else {
+                double G[9]; // NH: F;  FCR: 2 (F - R)
+                double isoJ, iso; // the isotropic part: (isoJ / J + iso) I
+                if (FCR) {
+                    double U[9], sv[3], V[9];
+                    svd3(F, U, sv, V);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) G[i + 3 * j] = 2.0 * (F[i + 3 * j] - (U[i] * V[j] + U[i + 3] * V[j + 3] + U[i + 6] * V[j + 6]));
+                    isoJ = 0.0;
+                    iso = lam * (J - 1.0); // lam (J - 1) J / J
+                }
+                else {
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) G[i] = F[i];
+                    isoJ = lam * log(J) - mu;
+                    iso = 0.0;
+                }
+                auto gft = [&](int i, int j) { return G[i] * F[j] + G[i + 3] * F[j + 3] + G[i + 6] * F[j + 6]; }; // (G F^T)_ij
+                s[0] = (mu * gft(0, 0) + isoJ) / J + iso;
+                s[1] = (mu * gft(1, 1) + isoJ) / J + iso;
+                s[2] = (mu * gft(2, 2) + isoJ) / J + iso;
+                s[3] = mu * (0.5 * (gft(0, 1) + gft(1, 0))) / J;
+                s[4] = mu * (0.5 * (gft(1, 2) + gft(2, 1))) / J;
+                s[5] = mu * (0.5 * (gft(0, 2) + gft(2, 0))) / J;
+                vm = von_mises(s[0], s[1], s[2], s[3], s[4], s[5]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out[(size_t)k * v.nT + t] = s[k];
+        out[(size_t)(STRESS_Q - 2) * v.nT + t] = vm;
+        out[(size_t)(STRESS_Q - 1) * v.nT + t] = Jout;
+    }
+    // the count is an integer: one add per wave that has such an element, in any order the same number
+    const unsigned long long m = __ballot(invalid);
+    if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(nInvalid, __popcll(m));
+}
+
+__global__ __launch_bounds__(BLOCK) void k_stress_nodes(int nV, int nT, const int* __restrict__ ptr, const int* __restrict__ elems,
+    const double* __restrict__ vol, const double* __restrict__ rec, double* __restrict__ out)
+{
+    const int n = blockIdx.x * BLOCK + threadIdx.x;
+    if (n >= nV) return;
+    double s[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, w = 0.0;
+    const int k1 = ptr[n + 1];
+    for (int k = ptr[n]; k < k1; ++k) {
+        const int e = elems[k];
+        const double ve = vol[e];
+        w += ve;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s[c] += ve * rec[(size_t)c * nT + e];
+    }
+    if (k1 > ptr[n]) { // (elements whose rest volumes sum to exactly zero give NaN here: there is no mean)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s[c] /= w;
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) out[(size_t)c * nV + n] = s[c];
+    out[(size_t)(STRESS_Q - 2) * nV + n] = von_mises(s[0], s[1], s[2], s[3], s[4], s[5]);
+    out[(size_t)(STRESS_Q - 1) * nV + n] = w;
+}
+
+// ------------------------------------------------------------------------------------------------
 // System report (Optimizer::computeSystemEnergy, Optimizer.cpp:3746-3778): per component the energy, the linear momentum and the angular momentum about
 // the origin -- seven doubles.  No atomics, every sum in a fixed order: two calls on one state give the same bits.
 //   pass 1  workgroup b takes slice b of the host-built list (report_plan.h: at most BLOCK consecutive nodes, or elements, of ONE component; the node
@@ -789,6 +895,16 @@ void launch_energy(const ElemView& v, double coef, bool withInertia, bool ownerR
 void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s)
 {
     if (v.nT) hipLaunchKernelGGL(k_energy_per_elem, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
+}
+void launch_stress_elements(const ElemView& v, double* rec, int* nInvalid, hipStream_t s)
+{
+    if (!v.nT) return;
+    if (v.energyType == 1) hipLaunchKernelGGL(k_stress_elements<true>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    else hipLaunchKernelGGL(k_stress_elements<false>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+}
+void launch_stress_nodes(int nV, int nT, const int* ptr, const int* elems, const double* vol, const double* rec, double* out, hipStream_t s)
+{
+    if (nV) hipLaunchKernelGGL(k_stress_nodes, dim3(nblk(nV)), dim3(BLOCK), 0, s, nV, nT, ptr, elems, vol, rec, out);
 }
 void launch_system_report(const ElemView& v, const double* xStart, const int* slices, int nNodeSlices, int nSlices, const int* nodeStart,
     const int* tetStart, int nComp, double dt, const double* g3, double* rec, double* out, hipStream_t s)

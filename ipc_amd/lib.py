@@ -361,6 +361,16 @@ class Context:
         self._chk(self._L.ipcgpu_elastic_energy_per_elem(self.h, _dp(out)))
         return out
 
+    def elastic_stress(self, nodal=True):
+        """Cauchy stress fields of the current positions (ipcgpu_elastic_stress): (elem[nT, 8], node[nV, 8] or None, n_invalid).  Columns: sxx, syy,
+        szz, sxy, syz, sxz, von Mises, then J per element / the sum of the incident rest volumes per node.  An NH element with J <= 0 is NaN and
+        counted in n_invalid; the stress entries of its four nodes are NaN too."""
+        elem = np.zeros((self.nT, 8), order="F")
+        node = np.zeros((self.nV, 8), order="F") if nodal else None
+        n = C.c_int()
+        self._chk(self._L.ipcgpu_elastic_stress(self.h, _dp(elem), _dp(node), C.byref(n)))
+        return elem, node, n.value
+
     def elastic_gradient(self, coef=1.0, projectDBC=True):
         g = np.zeros(3 * self.nV)
         self._chk(self._L.ipcgpu_elastic_gradient(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))

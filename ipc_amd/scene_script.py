@@ -1122,3 +1122,39 @@ class ReportWriter:
         for k, a in zip("EML", be.system_report()):
             with open(self.paths[k], "a") as f:
                 f.write(" ".join("%.17g" % x for x in np.asarray(a, dtype=np.float64).ravel()) + "\n")
+
+
+class FieldsWriter:
+    """`fields<N>.vtu` files in `folder` (tools/run_scene.py --fields): an ASCII VTK unstructured grid of the tetrahedra at the state the backend holds.
+    Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()`.  Point data: the nodal
+    `stress` (rest-volume-weighted mean of the incident elements), `von_mises` of that mean, `velocity`; with self-contact on, `contact_force` -- minus the
+    barrier gradient of the constraint set rebuilt at these positions with the step's dHat and kappa, Dirichlet rows kept -- and, when the lagged friction
+    set is not empty, `friction_force` -- minus the lagged friction gradient of the step from `x_prev` to here.  The reference writes no such file.
+    The stress call changes no state.  The two force fields do: `contact_build` replaces the context's constraint set by the one of the written positions, and the
+    gradient calls use the stepper's gradient and line-search buffers as scratch.  Every time step rebuilds the set and both buffers before it reads them, so a run
+    with the writer takes the steps of a run without it (tests/test_gpu_fields_tool.py) -- except under `warmStart 5`, whose first iterate reads the set the previous
+    step left."""
+
+    def __init__(self, folder, sc, contact=False, self_fric=0.0):
+        from . import vtu_io
+        os.makedirs(folder, exist_ok=True)
+        self.folder, self.sc, self.contact, self.self_fric, self._io = folder, sc, contact, self_fric, vtu_io
+
+    def write(self, be, step, x_prev=None):
+        elem, node, n_invalid = be.elastic_stress()
+        X = np.asarray(be.get_positions())
+        nV = X.shape[0]
+        cell = {"stress": elem[:, :6], "von_mises": elem[:, 6], "J": elem[:, 7]}
+        point = {"stress": node[:, :6], "von_mises": node[:, 6], "velocity": be.kinematics()["velocity"].reshape(nV, 3)}
+        if self.contact:
+            fs = be.friction_state()  # (the lagged set first: rebuilding the constraint set below is not to touch what it is read from)
+            fric = np.zeros((nV, 3))
+            if self.self_fric > 0 and x_prev is not None and fs["n_lagged"] > 0 and fs["fricDHat"] > 0:
+                fric = -be.friction_gradient_add(x_prev, fs["fricDHat"], self.self_fric).reshape(nV, 3)
+            st = be.state()
+            be.contact_build(st["dHat"])
+            point["contact_force"] = -be.contact_gradient_add(st["dHat"], st["kappa"], projectDBC=False).reshape(nV, 3)
+            point["friction_force"] = fric
+        path = os.path.join(self.folder, f"fields{step}.vtu")
+        self._io.write_vtu(path, X, self.sc.T, cell, point)
+        return path, n_invalid

@@ -309,6 +309,39 @@ int ipcgpu_contact_jt_multiply(ipcgpu_ctx*, int n, const int* mmcvid_4n, const d
 /* grad += kappa J^T b'  (leftMultiplyConstraintJacobianT + augmentParaEEGradient, SelfCollisionHandler.cpp:84-148,
  * 2990-3036), then rows of projected Dirichlet nodes zeroed (Optimizer.cpp:3512-3516) */
 int ipcgpu_contact_gradient_add(ipcgpu_ctx*, double dHat, double kappa, int projectDBC, double* grad_3nV_inout);
+/* The contact report: what happens BETWEEN bodies (it extends the reference's `min distance^2` log of a converged solve, Optimizer.cpp:2402-2442, and the
+ * per-object counts of outputCollStats, :3070-3087), reduced on the device.  It evaluates the sets the context HOLDS at the positions it holds -- the
+ * active and the mollified set of the last ipcgpu_contact_build / _set or of the stepper's last build, every half-space's vertex set, the lagged
+ * self-friction set of ipcgpu_friction_update or of the stepper -- in buffers of its own and CHANGES NO STATE.  Components: ipcgpu_opt_set_components
+ * (default: one).
+ * A row is one unordered pair with at least one contributing tuple: two components (a, b), a <= b, or component a and half-space h, written
+ * (a, -1 - h).  Rows ascend by (a, b), the half-space rows of a behind its component rows, ascending in h.
+ * Sides: primitive 1 of a decoded tuple is node 0 (PP, PE, PT) or nodes 0 and 1 (EE), primitive 2 the other nodes; of a mollified tuple the primitives
+ * are the edges eI and eJ of paraEEeIeJ, whose four nodes all carry force.  A primitive's component is that of its first node.  Side A is the primitive
+ * whose component is a (primitive 1 when a == b).  A half-space row has side A only.
+ * Barrier part, over the tuples with d < dHat at the current positions (a held tuple at or beyond dHat contributes nothing and is not counted); the
+ * force on node k is minus the node's term of ipcgpu_contact_gradient_add(projectDBC = 0) resp. ipcgpu_halfspace_gradient_add, Dirichlet rows kept:
+ *   active      f_k = -kappa mult b'(d) grad_k d        mollified   f_k = -kappa (b e' grad_k c + e b' grad_k d)
+ * rowsI[8 r ..]: a, b, nPP, nPE, nPT, nEE (active tuples by kind -- tuples, not multiplicities; the vertex count of a half-space row goes into nPP),
+ *   nMollified, argmin (index into the list active | mollified, resp. the node id in a half-space row, of the first tuple in list order that attains
+ *   minD2; -1 in a row without barrier tuples).
+ * rowsD[20 r ..]: minD2 (the squared distance as ipcgpu_contact_evaluate returns it), FA[3], FB[3] (sum of f_k over the nodes of side A / B), TA[3],
+ *   TB[3] (sum of x_k x f_k), RA[3], RB[3], W.
+ * Friction part, only with Vt != NULL, coef > 0 and a non-empty lagged self-contact set: per lagged tuple the force on node k is minus what
+ * ipcgpu_friction_gradient_add(Vt, eps2, coef) adds (self / obstacle scales included), summed by side into RA / RB; W = sum_k f_k . (x_k - Vt_k), the
+ * work of the lagged friction forces over the step (<= 0 up to round-off).  A row that exists through friction alone has zero counts and minD2 = +inf.
+ * After ipcgpu_opt_solve_timestep the lagged set is the one ipcgpu_opt_next_subproblem took at the CONVERGED positions (the lag is renewed before the
+ * stepper decides whether another friction sub-problem follows): the friction columns then are the forces of that fresh lag over the step's motion, not
+ * the friction terms the step's last Newton solve balanced.
+ * HALF-SPACE FRICTION IS NOT REPORTED (no entry point exposes its per-node terms): the friction columns of half-space rows are 0.
+ * capacity < number of rows: IPCGPU_ERR_ARG with *nRows set (capacity = 0 with null arrays asks for the size); no row: *nRows = 0, IPCGPU_OK.  Before
+ * ipcgpu_set_surface: IPCGPU_ERR_STATE.  Sharded context: IPCGPU_ERR_UNSUPPORTED; so are more than 2^22 keys nComp (nComp + 1) / 2 + nComp nHalfSpaces
+ * (the histogram over the pairs is dense; about 2 890 components).  Cost: linear in the number of held tuples except for the pass that orders a row's
+ * records, which compares every record of a row with every other -- quadratic in the LONGEST row (3.4 ms for one row of 22 K tuples on an MI355X; rows of a
+ * few hundred thousand tuples, e.g. two large bodies or the default single component of a large scene, take seconds).  fp64, no floating-point atomics, a fixed summation order (records of a row in the
+ * order active, mollified, half-spaces by id, friction, then set order): the same state gives the same bits. */
+int ipcgpu_contact_report(ipcgpu_ctx*, double dHat, double kappa, const double* Vt_colmajor /*nullable*/, double eps2, double coef, int capacity, int* nRows,
+    int* rowsI_8n, double* rowsD_20n);
 /* a += PSD-projected barrier Hessians (augmentIPHessian + augmentParaEEHessian, SelfCollisionHandler.cpp:418-561,
  * 3039-3201).  The pattern must already contain the contact connectivity (ipcgpu_contact_connectivity ->
  * ipcgpu_linsys_set_pattern); otherwise IPCGPU_ERR_STATE. */

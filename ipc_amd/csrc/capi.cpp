@@ -1028,6 +1028,26 @@ int ipcgpu_contact_gradient_add(ipcgpu_ctx* c, double dHat, double kappa, int pr
         return IPCGPU_OK;
     });
 }
+int ipcgpu_contact_report(ipcgpu_ctx* c, double dHat, double kappa, const double* Vt, double eps2, double coef, int capacity, int* nRows, int* rowsI,
+    double* rowsD)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        need(c->contact && c->contact->surfaceSet, "call ipcgpu_set_surface first");
+        if (c->worldSize > 1) throw UnsupportedError("contact report on a sharded context (multi-rank reports are not implemented)");
+        needArg(nRows != nullptr && capacity >= 0 && (capacity == 0 || (rowsI && rowsD)), "contact report: null output");
+        needArg(dHat > 0.0 && (!Vt || coef <= 0.0 || eps2 > 0.0), "contact report: dHat and eps2 must be positive");
+        const int nV = c->mesh->nV;
+        std::vector<int> ends = o.compNodeEnd; // no table (or one of another mesh): the whole mesh, as the system report has it
+        if (ends.empty() || ends.back() != nV) ends.assign(1, nV);
+        std::vector<HipContact::ReportPlane> planes;
+        for (const auto& h : o.planes) planes.push_back({ { h->n[0], h->n[1], h->n[2] }, h->D, h->d_set.p, (int)h->set.size() });
+        *nRows = c->contact->contactReport(c->mesh->d_x.p, nV, ends, planes, dHat, kappa, Vt, eps2, coef, capacity, rowsI, rowsD);
+        needArg(capacity >= *nRows, "contact report: capacity is smaller than the number of rows (*nRows is set)");
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_contact_hessian_add(ipcgpu_ctx* c, double dHat, double kappa, int projectDBC)
 {
     return guarded([&] {

@@ -135,8 +135,33 @@ public:
     void frictionHessianAdd(const double* x_dev, const double* xt_dev, const int* dbc_dev, const HipLinSysSolver& lin, double eps2, double coef,
         int projectDBC, double* a_dev);
     void frictionConnectivity(std::vector<std::pair<int, int>>& pairs) const; // appends
+    // Contact report (ipcgpu_contact_report, include/ipcgpu.h): per pair of components, or component and half-space, the smallest squared distance, the
+    // constraint counts by kind, the barrier forces and torques on either side, the lagged friction forces and their work.  Evaluates the sets held
+    // (active, mollified, every plane's vertex set, the lagged friction set) at x_dev in buffers of its own: no state of the handler changes.
+    // compNodeEnd: accumulated node ends of the components; Vt_colmajor null or coef <= 0: no friction part.  Returns the number of rows; rowsI / rowsD
+    // are filled when capacity >= that number.
+    struct ReportPlane {
+        double n[3], D;
+        const int* set_dev;
+        int count;
+    };
+    int contactReport(const double* x_dev, int nV, const std::vector<int>& compNodeEnd, const std::vector<ReportPlane>& planes, double dHat, double kappa,
+        const double* Vt_colmajor, double eps2, double coef, int capacity, int* rowsI_8n, double* rowsD_20n);
 
 private:
+    // contact report: node -> component, the previous positions, the records (key, kind, index, 13 values, SoA), the counting sort of the records by
+    // key, the slice list with its partial sums, and the mapped host block the row keys, ends and finished rows come back through
+    struct ReportScratch {
+        std::vector<int> compNodeEnd;
+        DevBuf<int> nodeComp, kind, idx, seg, sorted, slices, sliceStart, sliceI;
+        DevBuf<unsigned> key;
+        DevBuf<double> xt, val, sliceD;
+        ZeroKeptCounters count;
+        DevBuf<unsigned long long> start;
+        DevBuf<char> scanTmp;
+        PinnedBuf<int> hostI;
+        PinnedBuf<double> hostD;
+    } report_;
     // host side of the grids: the swept grid of ccdFull (own bounding box, two synchronisations), the grid of a build or check over box_ padded by two cells
     // of size h (grown until the grid has at most 2^26 cells), and the box of the positions measured synchronously (first build or check of a surface)
     Grid makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells);

@@ -2,6 +2,8 @@
 #include <climits>
 #include "hip_contact.h"
 #include "contact_device.h"
+#include "contact_report_plan.h"
+#include "halfspace_device.h"
 #include "stencil_hessian_device.h"
 #include "orient3d_exact.h"
 #include "hip_ipc.h"
@@ -3380,6 +3382,486 @@ void HipContact::evalStencils(const std::vector<std::array<int, 4>>& ids, const 
     d_vals_.ensure(n);
     hipLaunchKernelGGL(k_eval_stencils, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_ids_.p, x_dev, d_vals_.p);
     d_vals_.download(d2.data(), n, stream);
+}
+
+// ---- contact report (ipcgpu_contact_report) ---------------------------------------------------------------------------------------------------
+// What happens BETWEEN bodies: per pair of components (or component and half-space) the smallest squared distance with the tuple that attains it, the
+// counts by kind, the barrier forces and torques on either side, the lagged friction forces and their work.  Off the Newton iteration, in buffers of
+// its own, no floating-point atomics, every sum in a fixed order:
+//   records  one lane per tuple of each source (active | mollified, the planes' vertices, the lagged friction set): the row key, the kind, the index
+//            argmin reports and CR_V values, SoA; a tuple at or beyond dHat gets KEY_NONE.  The per-node terms are those of k_contact_gradient, the
+//            half-space gradient kernel and k_friction_gradient, negated, formed by the same device functions in the same order.
+//   sort     the counting sort of the deterministic scatter over the dense row keys (contact_report_plan.h): histogram (the record kernels bump the
+//            counters), ONE scan -- of count | present << 32, so that it lays out the buckets and numbers the rows at once --, fill (counts the counters
+//            back down), rank: a row's records in ascending record index = source order, then set order
+//   publish  the present keys with their accumulated ends into mapped host memory; the host cuts every row into slices of at most BLOCK records
+//   slices   one workgroup per slice: wave shuffles, then LDS;  rows: one wave per row over its slice partials in index order, into mapped host memory
+namespace {
+
+constexpr int CR_V = 13; // record values: d | FA FB TA TB (barrier) resp. +inf | RA RB W (friction)
+constexpr int CR_Q = 20; // row values: minD2 FA FB TA TB RA RB W
+constexpr int CR_MOLL = 4, CR_FRIC = 5; // record kinds beside K_PP .. K_EE (a half-space vertex counts as K_PP)
+
+struct ReportRec {
+    int n; // records of all sources
+    const int* nodeComp;
+    int nComp, nHalf;
+    unsigned* key;
+    int* kind;
+    int* idx;
+    double* val; // val[q * n + r]
+    int* count;
+};
+__device__ __forceinline__ void cr_add(const double* x, const double* f, double* F, double* T)
+{
+    for (int c = 0; c < 3; ++c) F[c] += f[c];
+    T[0] += x[1] * f[2] - x[2] * f[1];
+    T[1] += x[2] * f[0] - x[0] * f[2];
+    T[2] += x[0] * f[1] - x[1] * f[0];
+}
+// the row of two primitives' components; swap: primitive 2 is side A
+__device__ __forceinline__ int cr_pair_key(const ReportRec& o, int node1, int node2, bool* swap)
+{
+    const int c1 = o.nodeComp[node1], c2 = o.nodeComp[node2];
+    *swap = c1 > c2;
+    return contactReportKey(o.nComp, o.nHalf, min(c1, c2), max(c1, c2));
+}
+__device__ __forceinline__ void cr_store(const ReportRec& o, int r, int key, int kind, int idx)
+{
+    o.key[r] = (unsigned)key;
+    o.kind[r] = kind;
+    o.idx[r] = idx;
+    atomicAdd(o.count + key, 1);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_creport_contact(ContactView cv, double dHat, double kappa, ReportRec o)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= cv.nA + cv.nP) return;
+    double S0[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, S1[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }; // force, torque of primitive 1 / primitive 2
+    double d; // (every loop over nodes below is unrolled with the node count as a predicate: all array indices are compile-time constants)
+    int key, kind;
+    bool swap;
+    if (i < cv.nA) {
+        const Stencil s = decode(cv.active + 4 * (size_t)i);
+        double X[4][3], g[12], b, gb, Hb;
+        gatherX(cv.x, s.node, s.n, X);
+        d = stencil_distance(s.kind, X, g, nullptr);
+        if (!(d < dHat)) {
+            o.key[i] = KEY_NONE;
+            return;
+        }
+        barrier(d, dHat, &b, &gb, &Hb);
+        const double coef = kappa * s.mult * gb;
+        const int n1 = s.kind == K_EE ? 2 : 1; // nodes of primitive 1
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < s.n) {
+                const double f[3] = { -(coef * g[3 * k]), -(coef * g[3 * k + 1]), -(coef * g[3 * k + 2]) };
+                if (k < n1) cr_add(X[k], f, S0, S0 + 3);
+                else cr_add(X[k], f, S1, S1 + 3);
+            }
+        kind = s.kind;
+        key = cr_pair_key(o, s.node[0], n1 == 2 ? s.node[2] : s.node[1], &swap);
+    }
+    else {
+        const int j = i - cv.nA;
+        const Stencil s = decode(cv.para + 4 * (size_t)j);
+        int en[4];
+        paraNodes(cv, j, en);
+        double X[4][3], g[12], b, gb, Hb;
+        gatherX(cv.x, s.node, s.n, X);
+        d = stencil_distance(s.kind, X, g, nullptr);
+        if (!(d < dHat)) {
+            o.key[i] = KEY_NONE;
+            return;
+        }
+        barrier(d, dHat, &b, &gb, &Hb);
+        double XE[4][3], cg[12], e, eg, eH;
+        gatherX(cv.x, en, 4, XE);
+        const double c = cross_sqnorm_derivs(XE, cg, nullptr);
+        mollifier(c, eps_x_of(cv.xRest, en[0], en[1], en[2], en[3]), &e, &eg, &eH);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { // edge eI = primitive 1, edge eJ = primitive 2
+            const double f[3] = { -(kappa * b * eg * cg[3 * k]), -(kappa * b * eg * cg[3 * k + 1]), -(kappa * b * eg * cg[3 * k + 2]) };
+            if (k < 2) cr_add(XE[k], f, S0, S0 + 3);
+            else cr_add(XE[k], f, S1, S1 + 3);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) // the distance stencil's nodes are among the four edge nodes
+            if (k < s.n) {
+                const double f[3] = { -(kappa * e * gb * g[3 * k]), -(kappa * e * gb * g[3 * k + 1]), -(kappa * e * gb * g[3 * k + 2]) };
+                if (s.node[k] == en[0] || s.node[k] == en[1]) cr_add(X[k], f, S0, S0 + 3);
+                else cr_add(X[k], f, S1, S1 + 3);
+            }
+        kind = CR_MOLL;
+        key = cr_pair_key(o, en[0], en[2], &swap);
+    }
+    o.val[i] = d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { // side A is primitive 2 when the sides are swapped
+        o.val[(size_t)(1 + c) * o.n + i] = swap ? S1[c] : S0[c];
+        o.val[(size_t)(4 + c) * o.n + i] = swap ? S0[c] : S1[c];
+        o.val[(size_t)(7 + c) * o.n + i] = swap ? S1[3 + c] : S0[3 + c];
+        o.val[(size_t)(10 + c) * o.n + i] = swap ? S0[3 + c] : S1[3 + c];
+    }
+    cr_store(o, i, key, kind, i);
+}
+// the vertex set of half-space h: records [r0, r0 + n)
+__global__ __launch_bounds__(BLOCK) void k_creport_halfspace(int n, const int* __restrict__ set, const double* __restrict__ x, hsdev::Plane h, int hsId, int r0,
+    double dHat, double kappa, ReportRec o)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int r = r0 + i, v = set[i];
+    const double dist = hsdev::plane_dist(h, x, v), d = dist * dist;
+    if (!(d < dHat)) {
+        o.key[r] = KEY_NONE;
+        return;
+    }
+    double b, gb, Hb;
+    barrier(d, dHat, &b, &gb, &Hb);
+    const double f[3] = { -(kappa * gb * 2.0 * dist * h.n0), -(kappa * gb * 2.0 * dist * h.n1), -(kappa * gb * 2.0 * dist * h.n2) };
+    const double xv[3] = { x[3 * (size_t)v], x[3 * (size_t)v + 1], x[3 * (size_t)v + 2] };
+    double S[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    cr_add(xv, f, S, S + 3);
+    o.val[r] = d;
+    for (int c = 0; c < 3; ++c) {
+        o.val[(size_t)(1 + c) * o.n + r] = S[c];
+        o.val[(size_t)(4 + c) * o.n + r] = 0.0;
+        o.val[(size_t)(7 + c) * o.n + r] = S[3 + c];
+        o.val[(size_t)(10 + c) * o.n + r] = 0.0;
+    }
+    cr_store(o, r, contactReportKey(o.nComp, o.nHalf, o.nodeComp[v], -1 - hsId), K_PP, v);
+}
+// the lagged friction set: records [r0, r0 + fv.n)
+__global__ __launch_bounds__(BLOCK) void k_creport_friction(FrictionView fv, const double* __restrict__ x, const double* __restrict__ xt, double eps2, double coef,
+    int r0, ReportRec o)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= fv.n) return;
+    const int r = r0 + i;
+    const Stencil s = decode(fv.set + 4 * (size_t)i);
+    const double* B = fv.basis + 6 * (size_t)i;
+    double wt[4], u[2];
+    fr_weights(s.kind, fv.coord + 2 * (size_t)i, wt);
+    fr_slide(x, xt, s, wt, B, u);
+    const double x2 = u[0] * u[0] + u[1] * u[1], eps = sqrt(eps2);
+    const double sc = (x2 > eps2) ? 1.0 / sqrt(x2) : (-sqrt(x2) + 2.0 * eps) / (eps * eps); // f1 / |u|
+    double t3[3];
+    for (int c = 0; c < 3; ++c) t3[c] = B[c] * (u[0] * sc) + B[3 + c] * (u[1] * sc);
+    const int n1 = s.kind == K_EE ? 2 : 1;
+    double R0[3] = { 0.0, 0.0, 0.0 }, R1[3] = { 0.0, 0.0, 0.0 }, W = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < s.n) {
+            const double f[3] = { -(coef * fv.lambda[i] * wt[k] * t3[0]), -(coef * fv.lambda[i] * wt[k] * t3[1]), -(coef * fv.lambda[i] * wt[k] * t3[2]) };
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (k < n1) R0[c] += f[c];
+                else R1[c] += f[c];
+                W += f[c] * (x[3 * (size_t)s.node[k] + c] - xt[3 * (size_t)s.node[k] + c]);
+            }
+        }
+    bool swap;
+    const int key = cr_pair_key(o, s.node[0], n1 == 2 ? s.node[2] : s.node[1], &swap);
+    o.val[r] = INFINITY;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o.val[(size_t)(1 + c) * o.n + r] = swap ? R1[c] : R0[c];
+        o.val[(size_t)(4 + c) * o.n + r] = swap ? R0[c] : R1[c];
+    }
+    o.val[(size_t)7 * o.n + r] = W;
+    cr_store(o, r, key, CR_FRIC, -1);
+}
+
+// the scan's input: a key's count, and in the upper word whether it has any -- the exclusive sum is (rows before the key) << 32 | records before the key
+struct ReportScanIn {
+    __host__ __device__ unsigned long long operator()(int c) const { return c > 0 ? ((1ull << 32) | (unsigned)c) : 0ull; }
+};
+__device__ __forceinline__ int cr_lo(unsigned long long s) { return (int)(s & 0xFFFFFFFFull); }
+__device__ __forceinline__ int cr_hi(unsigned long long s) { return (int)(s >> 32); }
+__global__ __launch_bounds__(BLOCK) void k_creport_fill(int n, const unsigned* __restrict__ keys, const unsigned long long* __restrict__ start, int* __restrict__ count,
+    int* __restrict__ seg)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const unsigned key = keys[t];
+    if (key == KEY_NONE) return;
+    seg[cr_lo(start[key]) + atomicSub(count + key, 1) - 1] = t;
+}
+// k_det_rank over the packed starts: every bucket into ascending record order
+__global__ __launch_bounds__(BLOCK) void k_creport_rank(int n, const unsigned* __restrict__ keys, const unsigned long long* __restrict__ start, int nKeys,
+    const int* __restrict__ seg, int* __restrict__ sorted)
+{
+    const int u = blockIdx.x * BLOCK + threadIdx.x;
+    if (u >= n || u >= cr_lo(start[nKeys])) return;
+    const int rec = seg[u];
+    const unsigned b = keys[rec];
+    const int s0 = cr_lo(start[b]), s1 = cr_lo(start[b + 1]);
+    int rank = 0;
+    for (int w = s0; w < s1; ++w) rank += seg[w] < rec ? 1 : 0;
+    sorted[s0 + rank] = rec;
+}
+// out (mapped host memory): [0] rows, [1] contributing records, then key and accumulated end per row (at most maxRows of them fit)
+__global__ __launch_bounds__(BLOCK) void k_creport_publish(int nKeys, const unsigned long long* __restrict__ start, int maxRows, int* __restrict__ out)
+{
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= nKeys) return;
+    const unsigned long long s = start[k], e = start[k + 1];
+    if (cr_hi(e) > cr_hi(s) && cr_hi(s) < maxRows) {
+        out[2 + 2 * (size_t)cr_hi(s)] = k;
+        out[3 + 2 * (size_t)cr_hi(s)] = cr_lo(e);
+    }
+    if (k == nKeys - 1) {
+        out[0] = cr_hi(e);
+        out[1] = cr_lo(e);
+    }
+}
+
+__device__ __forceinline__ bool cr_before(double d, int p, double d0, int p0) { return d < d0 || (d == d0 && p < p0); }
+__device__ __forceinline__ void cr_wave_min(double& d, int& p, int& id)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_down(d, off, 64);
+        const int op = __shfl_down(p, off, 64), oi = __shfl_down(id, off, 64);
+        if (cr_before(od, op, d, p)) {
+            d = od;
+            p = op;
+            id = oi;
+        }
+    }
+}
+__device__ __forceinline__ double cr_wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
+// slices: int triples (row, begin, end) into `sorted`.  outD: CR_Q doubles per slice ([0]: the smallest d), outI: 8 ints per slice -- five counts, the
+// index of the tuple that attains the minimum (-1: none) and its position in `sorted`
+__global__ __launch_bounds__(BLOCK) void k_creport_slices(int n, const int* __restrict__ slices, const int* __restrict__ sorted, const int* __restrict__ kind,
+    const int* __restrict__ idx, const double* __restrict__ val, double* __restrict__ outD, int* __restrict__ outI)
+{
+    __shared__ double sm[CR_Q][BLOCK / 64];
+    __shared__ int smI[7][BLOCK / 64];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int pos = slices[3 * b + 1] + threadIdx.x;
+    const bool live = pos < slices[3 * b + 2];
+    double q[CR_Q];
+#pragma unroll
+    for (int k = 0; k < CR_Q; ++k) q[k] = 0.0;
+    q[0] = INFINITY;
+    int kd = -1, id = -1;
+    if (live) {
+        const int r = sorted[pos];
+        kd = kind[r];
+        id = idx[r];
+        if (kd == CR_FRIC) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) q[13 + k] = val[(size_t)(1 + k) * n + r];
+        }
+        else {
+#pragma unroll
+            for (int k = 0; k < CR_V; ++k) q[k] = val[(size_t)k * n + r];
+        }
+    }
+#pragma unroll
+    for (int k = 1; k < CR_Q; ++k) {
+        const double r = cr_wave_sum(q[k]);
+        if (lane == 0) sm[k][wv] = r;
+    }
+    double d = q[0];
+    cr_wave_min(d, pos, id);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64(kd == k));
+        if (lane == 0) smI[k][wv] = c;
+    }
+    if (lane == 0) {
+        sm[0][wv] = d;
+        smI[5][wv] = id;
+        smI[6][wv] = pos;
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t == 0) {
+        double d0 = sm[0][0];
+        int id0 = smI[5][0], p0 = smI[6][0];
+        for (int w = 1; w < BLOCK / 64; ++w)
+            if (cr_before(sm[0][w], smI[6][w], d0, p0)) {
+                d0 = sm[0][w];
+                id0 = smI[5][w];
+                p0 = smI[6][w];
+            }
+        outD[CR_Q * (size_t)b] = d0;
+        outI[8 * (size_t)b + 5] = d0 < INFINITY ? id0 : -1;
+        outI[8 * (size_t)b + 6] = p0;
+        outI[8 * (size_t)b + 7] = 0;
+    }
+    else if (t < CR_Q) {
+        double r = 0.0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) r += sm[t][w];
+        outD[CR_Q * (size_t)b + t] = r;
+    }
+    else if (t < CR_Q + 5) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) c += smI[t - CR_Q][w];
+        outI[8 * (size_t)b + (t - CR_Q)] = c;
+    }
+}
+// one wave per row: lane l takes the row's slices l, l + 64, ... in index order, then the shuffle tree.  rowsD: CR_Q doubles per row; rowsI: 8 ints per
+// row, of which [2 .. 7] are written here (counts and argmin; the pair is the host's)
+__global__ __launch_bounds__(64) void k_creport_rows(const int* __restrict__ sliceStart, const double* __restrict__ sliceD, const int* __restrict__ sliceI,
+    double* __restrict__ rowsD, int* __restrict__ rowsI)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int s0 = sliceStart[r], s1 = sliceStart[r + 1];
+#pragma unroll
+    for (int k = 1; k < CR_Q; ++k) {
+        double a = 0.0;
+        for (int j = s0 + lane; j < s1; j += 64) a += sliceD[CR_Q * (size_t)j + k];
+        a = cr_wave_sum(a);
+        if (lane == 0) rowsD[CR_Q * (size_t)r + k] = a;
+    }
+    double d = INFINITY;
+    int p = INT_MAX, id = -1;
+    for (int j = s0 + lane; j < s1; j += 64) {
+        const double dj = sliceD[CR_Q * (size_t)j];
+        if (dj < d) { // (a lane's slices ascend: the earlier one keeps a tie)
+            d = dj;
+            id = sliceI[8 * (size_t)j + 5];
+            p = sliceI[8 * (size_t)j + 6];
+        }
+    }
+    cr_wave_min(d, p, id);
+    if (lane == 0) {
+        rowsD[CR_Q * (size_t)r] = d;
+        rowsI[8 * (size_t)r + 7] = id;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        int c = 0;
+        for (int j = s0 + lane; j < s1; j += 64) c += sliceI[8 * (size_t)j + k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        if (lane == 0) rowsI[8 * (size_t)r + 2 + k] = c;
+    }
+}
+} // namespace
+
+int HipContact::contactReport(const double* x_dev, int nV, const std::vector<int>& compNodeEnd, const std::vector<ReportPlane>& planes, double dHat,
+    double kappa, const double* Vt, double eps2, double coef, int capacity, int* rowsI, double* rowsD)
+{
+    ReportScratch& w = report_;
+    const int nComp = (int)compNodeEnd.size(), nHalf = (int)planes.size();
+    if (nComp < 1 || compNodeEnd.back() != nV) throw ArgError("contact report: the component table does not end at the node count");
+    const long long nKeysLL = contactReportKeyCount(nComp, nHalf);
+    if (nKeysLL > CONTACT_REPORT_MAX_KEYS)
+        throw UnsupportedError("contact report: more than 2^22 pairs of components and half-spaces (the histogram over the pairs is dense)");
+    const int nKeys = (int)nKeysLL;
+    const int nA = nActive_, nP = nPara_;
+    const int nF = (Vt && coef > 0.0) ? (int)fricSet.size() : 0;
+    long long nRecLL = (long long)nA + nP + nF;
+    for (const ReportPlane& h : planes) nRecLL += h.count;
+    if (nRecLL > (long long)INT_MAX / CR_V) throw StateError("too many contact tuples for one report");
+    const int nRec = (int)nRecLL;
+    if (!nRec) return 0;
+
+    std::vector<int> nodeComp; // staging vectors live until the first synchronisation below
+    std::vector<double> xt;
+    if (w.compNodeEnd != compNodeEnd || w.nodeComp.n < (size_t)nV) {
+        nodeComp.resize(nV);
+        for (int c = 0, v = 0; c < nComp; ++c)
+            for (; v < compNodeEnd[c]; ++v) nodeComp[v] = c;
+        w.nodeComp.uploadGrow(nodeComp, stream);
+        w.compNodeEnd = compNodeEnd;
+    }
+    if (nF) {
+        xt.resize(3 * (size_t)nV);
+        for (int v = 0; v < nV; ++v)
+            for (int k = 0; k < 3; ++k) xt[3 * (size_t)v + k] = Vt[v + (size_t)nV * k];
+        w.xt.uploadGrow(xt, stream);
+    }
+    w.key.ensure(nRec);
+    w.kind.ensure(nRec);
+    w.idx.ensure(nRec);
+    w.seg.ensure(nRec);
+    w.sorted.ensure(nRec);
+    w.val.ensure((size_t)CR_V * nRec);
+    w.start.ensure((size_t)nKeys + 1);
+    const int maxRows = std::min(nKeys, nRec);
+    if (w.hostI.n < 2 + 2 * (size_t)maxRows) w.hostI.alloc(2 + 2 * (size_t)maxRows + maxRows / 2);
+    int* count = w.count.begin((size_t)nKeys + 1, stream);
+    const ReportRec o{ nRec, w.nodeComp.p, nComp, nHalf, w.key.p, w.kind.p, w.idx.p, w.val.p, count };
+
+    if (nA + nP) {
+        const ContactView cv{ nA, nP, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, x_dev, d_xRest.p };
+        hipLaunchKernelGGL(k_creport_contact, dim3(nblk(nA + nP)), dim3(BLOCK), 0, stream, cv, dHat, kappa, o);
+    }
+    int r0 = nA + nP;
+    for (int h = 0; h < nHalf; ++h) {
+        const ReportPlane& pl = planes[h];
+        if (pl.count)
+            hipLaunchKernelGGL(k_creport_halfspace, dim3(nblk(pl.count)), dim3(BLOCK), 0, stream, pl.count, pl.set_dev, x_dev,
+                hsdev::Plane{ pl.n[0], pl.n[1], pl.n[2], pl.D }, h, r0, dHat, kappa, o);
+        r0 += pl.count;
+    }
+    if (nF) {
+        const FrictionView fv{ nF, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
+        hipLaunchKernelGGL(k_creport_friction, dim3(nblk(nF)), dim3(BLOCK), 0, stream, fv, x_dev, w.xt.p, eps2, coef, r0, o);
+    }
+    {
+        hipcub::TransformInputIterator<unsigned long long, ReportScanIn, const int*> in(count, ReportScanIn());
+        size_t bytes = 0;
+        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, w.start.p, nKeys + 1, stream));
+        if (w.scanTmp.n < bytes) w.scanTmp.alloc(bytes + bytes / 4);
+        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.scanTmp.p, bytes, in, w.start.p, nKeys + 1, stream));
+    }
+    hipLaunchKernelGGL(k_creport_fill, dim3(nblk(nRec)), dim3(BLOCK), 0, stream, nRec, w.key.p, w.start.p, count, w.seg.p);
+    w.count.done();
+    hipLaunchKernelGGL(k_creport_rank, dim3(nblk(nRec)), dim3(BLOCK), 0, stream, nRec, w.key.p, w.start.p, nKeys, w.seg.p, w.sorted.p);
+    hipLaunchKernelGGL(k_creport_publish, dim3(nblk(nKeys)), dim3(BLOCK), 0, stream, nKeys, w.start.p, maxRows, w.hostI.dev);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream)); // the one read-back: the rows present and where their records end
+
+    const int nRows = w.hostI.p[0];
+    const int* rowKey2 = w.hostI.p + 2; // (key, end) pairs
+    if (nRows < 0 || nRows > maxRows) throw StateError("contact report: inconsistent row count");
+    if (!nRows || capacity < nRows) return nRows;
+    std::vector<int> rowKey(nRows), rowEnd(nRows), pairs, sliceStart;
+    for (int r = 0; r < nRows; ++r) {
+        rowKey[r] = rowKey2[2 * (size_t)r];
+        rowEnd[r] = rowKey2[2 * (size_t)r + 1];
+    }
+    if (!contactReportRowsValid(nKeys, nRows, rowKey.data(), rowEnd.data()) || rowEnd.back() != w.hostI.p[1] || rowEnd.back() > nRec)
+        throw StateError("contact report: inconsistent row table");
+    std::vector<ReportSlice> slices;
+    buildContactReportPlan(nComp, nHalf, nRows, rowKey.data(), rowEnd.data(), BLOCK, pairs, slices, sliceStart);
+    static_assert(sizeof(ReportSlice) == 3 * sizeof(int), "the kernel reads the list as int triples");
+    const int nSlices = (int)slices.size();
+    std::vector<int> flat(3 * (size_t)nSlices);
+    std::memcpy(flat.data(), slices.data(), slices.size() * sizeof(ReportSlice));
+    w.slices.uploadGrow(flat, stream);
+    w.sliceStart.uploadGrow(sliceStart, stream);
+    w.sliceD.ensure((size_t)CR_Q * nSlices);
+    w.sliceI.ensure(8 * (size_t)nSlices);
+    if (w.hostD.n < (size_t)CR_Q * nRows) w.hostD.alloc((size_t)CR_Q * nRows + 64);
+    if (w.hostI.n < 8 * (size_t)nRows) w.hostI.alloc(8 * (size_t)nRows + 64); // (the row table was copied out above)
+    hipLaunchKernelGGL(k_creport_slices, dim3(nSlices), dim3(BLOCK), 0, stream, nRec, w.slices.p, w.sorted.p, w.kind.p, w.idx.p, w.val.p, w.sliceD.p, w.sliceI.p);
+    hipLaunchKernelGGL(k_creport_rows, dim3(nRows), dim3(64), 0, stream, w.sliceStart.p, w.sliceD.p, w.sliceI.p, w.hostD.dev, w.hostI.dev);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::memcpy(rowsD, w.hostD.p, (size_t)CR_Q * nRows * sizeof(double));
+    for (int r = 0; r < nRows; ++r) {
+        rowsI[8 * (size_t)r] = pairs[2 * (size_t)r];
+        rowsI[8 * (size_t)r + 1] = pairs[2 * (size_t)r + 1];
+        for (int k = 2; k < 8; ++k) rowsI[8 * (size_t)r + k] = w.hostI.p[8 * (size_t)r + k];
+    }
+    return nRows;
 }
 
 } // namespace ipcgpu

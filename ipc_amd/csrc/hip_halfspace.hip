@@ -3,6 +3,7 @@
 // the sizes of the hot path (<= 45 K surface vertices at mat150).  Reference lines are cited in hip_halfspace.h.
 #include "hip_halfspace.h"
 #include "contact_device.h"
+#include "halfspace_device.h"
 #include <cmath>
 #include <cstring>
 #include <hipcub/hipcub.hpp>
@@ -12,13 +13,8 @@ namespace {
 constexpr int BLOCK = 256;
 inline int nblk(int n) { return (n + BLOCK - 1) / BLOCK; }
 
-struct Plane {
-    double n0, n1, n2, D;
-};
-__device__ __forceinline__ double plane_dist(const Plane& h, const double* __restrict__ x, int v)
-{
-    return h.n0 * x[3 * (size_t)v] + h.n1 * x[3 * (size_t)v + 1] + h.n2 * x[3 * (size_t)v + 2] + h.D;
-}
+using hsdev::Plane;
+using hsdev::plane_dist;
 __device__ __forceinline__ double block_sum(double x, double* sm)
 {
 #pragma unroll

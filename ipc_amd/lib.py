@@ -99,6 +99,11 @@ def load_library():
     return _lib
 
 
+# one row of Context.contact_report (ipcgpu_contact_report: rowsI[8], rowsD[20])
+CONTACT_REPORT_DTYPE = np.dtype([(k, np.int32) for k in ("a", "b", "nPP", "nPE", "nPT", "nEE", "nMollified", "argmin")] + [("minD2", np.float64)]
+                                + [(k, np.float64, (3,)) for k in ("FA", "FB", "TA", "TB", "RA", "RB")] + [("W", np.float64)])
+
+
 def _dp(a):
     return a.ctypes.data_as(c_dp) if a is not None else None
 
@@ -559,6 +564,58 @@ class Context:
         g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
         self._chk(self._L.ipcgpu_contact_gradient_add(self.h, C.c_double(dHat), C.c_double(kappa), C.c_int(int(projectDBC)), _dp(g)))
         return g
+
+    def contact_held(self):
+        """The constraint sets the context holds (of the last contact_build / contact_set or of the stepper's last build), without rebuilding them."""
+        n = np.zeros(3, dtype=np.int32)
+        self._chk(self._L.ipcgpu_contact_counts(self.h, _ip(n)))
+        a, p, q = np.zeros((n[0], 4), dtype=np.int32), np.zeros((n[1], 4), dtype=np.int32), np.zeros((n[1], 2), dtype=np.int32)
+        self._chk(self._L.ipcgpu_contact_get(self.h, _ip(a), _ip(p), _ip(q), None))
+        return dict(active=a, para=p, para_eiej=q)
+
+    def contact_evaluate(self, tuples):
+        """Squared distances of MMCVID tuples at the positions the context holds (ipcgpu_contact_evaluate)."""
+        t = np.ascontiguousarray(tuples, dtype=np.int32).reshape(-1, 4)
+        val = np.zeros(t.shape[0])
+        self._chk(self._L.ipcgpu_contact_evaluate(self.h, C.c_int(t.shape[0]), _ip(t), _dp(val)))
+        return val
+
+    def contact_report(self, dHat=None, kappa=None, x_prev=None, eps2=None, coef=None):
+        """Contact report of the sets the context holds at the positions it holds (ipcgpu_contact_report; changes no state): a structured array with
+        one entry per pair of components `(a, b)`, a <= b, or component and half-space `(a, -1 - h)`, that has a contributing tuple -- fields `a`, `b`,
+        `nPP`, `nPE`, `nPT`, `nEE`, `nMollified`, `argmin`, `minD2`, `FA`, `FB`, `TA`, `TB` (barrier force and torque on either side), `RA`, `RB`, `W`
+        (lagged friction forces and their work over the step from `x_prev`).  Missing dHat / kappa come from state().  The friction fields need `x_prev`
+        AND `coef`, the friction coefficient the lagged terms are scaled with (the scene's selfFric: the library keeps no copy the caller could ask for);
+        a missing eps2 comes from friction_state().  Without them the friction fields are zero."""
+        if dHat is None or kappa is None:
+            st = self.state()
+            dHat = st["dHat"] if dHat is None else dHat
+            kappa = st["kappa"] if kappa is None else kappa
+        Vt = None
+        if x_prev is not None:
+            coef = 0.0 if coef is None else coef
+            if coef > 0 and eps2 is None:
+                eps2 = self.friction_state()["fricDHat"]
+            if coef > 0 and eps2 > 0:
+                Vt = np.asfortranarray(x_prev, dtype=np.float64)
+                assert Vt.shape == (self.nV, 3)
+        call = lambda cap, ri, rd, n: self._L.ipcgpu_contact_report(self.h, C.c_double(dHat), C.c_double(kappa), _dp(Vt), C.c_double(eps2 or 0.0),
+                                                                    C.c_double(coef or 0.0), C.c_int(cap), C.byref(n), _ip(ri), _dp(rd))
+        n = C.c_int(0)
+        rc = call(0, None, None, n)
+        if rc != IPCGPU_OK and n.value == 0:
+            self._chk(rc)
+        rows_i, rows_d = np.zeros((n.value, 8), dtype=np.int32), np.zeros((n.value, 20))
+        if n.value:
+            self._chk(call(n.value, rows_i, rows_d, n))
+        out = np.zeros(n.value, dtype=CONTACT_REPORT_DTYPE)
+        for k, name in enumerate(("a", "b", "nPP", "nPE", "nPT", "nEE", "nMollified", "argmin")):
+            out[name] = rows_i[:, k]
+        out["minD2"] = rows_d[:, 0]
+        for k, name in enumerate(("FA", "FB", "TA", "TB", "RA", "RB")):
+            out[name] = rows_d[:, 1 + 3 * k:4 + 3 * k]
+        out["W"] = rows_d[:, 19]
+        return out
 
     def contact_hessian_add(self, dHat, kappa, projectDBC=True):
         self._chk(self._L.ipcgpu_contact_hessian_add(self.h, C.c_double(dHat), C.c_double(kappa), C.c_int(int(projectDBC))))

@@ -1124,6 +1124,37 @@ class ReportWriter:
                 f.write(" ".join("%.17g" % x for x in np.asarray(a, dtype=np.float64).ravel()) + "\n")
 
 
+class ContactReportWriter:
+    """`contact.txt` in `folder` (tools/run_scene.py --contact-report): one line per row of `contact_report()` per call of write() --
+    `step a b nPP nPE nPT nEE nMoll argmin minD2 FA.. FB.. TA.. TB.. RA.. RB.. W`, 29 columns, doubles as `%.17g` (they read back to the same doubles).  A row
+    is a pair of components `(a, b)` or a component and half-space `(a, -1 - h)`; see `ipcgpu_contact_report` in include/ipcgpu.h.  The reference logs only
+    the smallest distance of a converged solve (Optimizer.cpp:2402-2442) and per-object counts (:3070-3087).
+    The report is taken on the sets the stepper HOLDS when solve_timestep returns and changes no state, so a run with the writer takes the steps of a run
+    without it.  Those sets are the ones of the final positions: with contact on, every trial of a line search rebuilds them at the trial positions
+    (HipOptimizer::lineSearch -> computeConstraintSets), at the step's current dHat, and nothing moves between the last line search and the return; the converged
+    pass only evaluates the gradient.  The friction set is NOT the one the solve balanced: when a sub-problem has converged, HipOptimizer::nextSubproblem lags
+    friction anew at the converged positions before it decides whether another sub-problem follows, so the lag held at the return was taken at the FINAL
+    positions.  RA, RB and W are the forces of that fresh lag (the normal forces and tangent frames of the end of the step) over the step's motion from
+    `x_prev` -- an estimate of the friction acting at the end of the step, not the terms of the step's last Newton solve.  `self_fric`: the scene's selfFric,
+    the coefficient the lagged terms are scaled with (0: no friction columns)."""
+
+    COLUMNS = ("a", "b", "nPP", "nPE", "nPT", "nEE", "nMollified", "argmin")
+
+    def __init__(self, folder, self_fric=0.0):
+        os.makedirs(folder, exist_ok=True)
+        self.self_fric = self_fric
+        self.path = os.path.join(folder, "contact.txt")
+        open(self.path, "w").close()
+
+    def write(self, be, step, x_prev=None):
+        rows = be.contact_report(x_prev=x_prev if self.self_fric > 0 else None, coef=self.self_fric)
+        with open(self.path, "a") as f:
+            for r in rows:
+                vals = [float(r["minD2"])] + [float(v) for k in ("FA", "FB", "TA", "TB", "RA", "RB") for v in r[k]] + [float(r["W"])]
+                f.write(" ".join([str(int(step))] + [str(int(r[k])) for k in self.COLUMNS] + ["%.17g" % v for v in vals]) + "\n")
+        return len(rows)
+
+
 class FieldsWriter:
     """`fields<N>.vtu` files in `folder` (tools/run_scene.py --fields): an ASCII VTK unstructured grid of the tetrahedra at the state the backend holds.
     Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()`.  Point data: the nodal

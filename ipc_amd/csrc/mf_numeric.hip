@@ -859,6 +859,19 @@ __global__ __launch_bounds__(WG, MF_SCHUR_OCC) void k_big_schur(const int4* __re
 // the kernel is not occupancy-bound.  profiles/r05_solver_ab_xcd_occupancy.txt.)
 // orig: first row / column of tile (0, 0); colEnd: columns from here on are not this pass's (the Schur passes: orig = nc, colEnd = N; the bulk update of the wide
 // fronts' own columns, k_big_bulk: orig = the end of the outer block, colEnd = nc); [cLo, nc): the columns of L of this pass.
+// The 64 x 64 kernels' full chunks (every column below nc: all but the last two or three of a pass) take a loop without the column clamp of the loads and without the selects on the
+// operands -- per pair of chunks, 32 v_cndmask, the v_min clamps and a 64-bit multiply-add per load group beside 32 MFMAs, on a wave whose VALU and address work
+// does not overlap with its own MFMAs (profiles/r05_schur_tile_experiments.txt).  An operand's address is split into a wave-uniform part -- column 0 of the group of
+// four columns, advanced by scalar adds of N * CW -- and a per-lane part that never changes: the lane's (clamped) row and its column ak within the group, in bytes, at
+// most 32 N: 32 bits.  The masked products were products with exact zeros and the order of the MFMAs is the same: the factor keeps its bits.
+__device__ __forceinline__ unsigned lane_bytes(const double* rowPtr, const double* F, const int N, const int ak)
+{
+    return 8u * ((unsigned)(rowPtr - F) + (unsigned)N * (unsigned)ak);
+}
+__device__ __forceinline__ double load_uniform_plus_lane(const double* uniformBase, const unsigned laneBytes)
+{
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(uniformBase) + laneBytes);
+}
 template <bool LOAD_OLD>
 __device__ __forceinline__ void schur_tile64_core(const int N, const int orig, const int colEnd, const int nc, double* __restrict__ F, const int ti, const int tj,
     const int cLo, double (&old)[2][2][4])
@@ -915,16 +928,51 @@ __device__ __forceinline__ void schur_tile64_core(const int N, const int orig, c
     // ping-pong register sets, unconditional fetches behind scheduling fences: see k_big_schur
     const int ch0 = cLo / CW;
     fetch(ch0, a0, a1, b0, b1);
-    for (int ch = ch0; ch < nch; ch += 2) {
-        fetch(ch + 1, na0, na1, nb0, nb1);
+    int ch = ch0;
+    // main loop: the two chunks it multiplies and the two it fetches all lie below nc (lane_bytes above)
+    const unsigned va0 = lane_bytes(pa0, F, N, ak), va1 = lane_bytes(pa1, F, N, ak), vb0 = lane_bytes(pb0, F, N, ak), vb1 = lane_bytes(pb1, F, N, ak);
+    const long long cstride = (long long)N * CW;
+    const double* cb = F + cstride * (ch0 + 1); // column 0 of the chunk fetched next
+    auto fetchFull = [&](const double* c, double* x0, double* x1, double* y0, double* y1) {
+#pragma unroll
+        for (int ks = 0; ks < CS; ++ks) {
+            const double* g = c + (long long)N * (4 * ks);
+            x0[ks] = load_uniform_plus_lane(g, va0);
+            x1[ks] = load_uniform_plus_lane(g, va1);
+            y0[ks] = load_uniform_plus_lane(g, vb0);
+            y1[ks] = load_uniform_plus_lane(g, vb1);
+        }
+    };
+    auto multFull = [&](const double* x0, const double* x1, const double* y0, const double* y1) {
+#pragma unroll
+        for (int ks = 0; ks < CS; ++ks) {
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(y0[ks], x0[ks], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(y0[ks], x1[ks], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(y1[ks], x0[ks], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(y1[ks], x1[ks], acc[1][1], 0, 0, 0);
+        }
+    };
+    for (const int nFull = nc / CW; ch + 2 < nFull; ch += 2, cb += 2 * cstride) {
+        fetchFull(cb, na0, na1, nb0, nb1);
         __builtin_amdgcn_sched_barrier(0);
-        mult(ch, a0, a1, b0, b1);
+        multFull(a0, a1, b0, b1);
         __builtin_amdgcn_sched_barrier(0);
-        fetch(ch + 2, a0, a1, b0, b1);
+        fetchFull(cb + cstride, a0, a1, b0, b1);
         __builtin_amdgcn_sched_barrier(0);
-        if (ch + 1 < nch) mult(ch + 1, na0, na1, nb0, nb1);
+        multFull(na0, na1, nb0, nb1);
         __builtin_amdgcn_sched_barrier(0);
     }
+    // tail: chunk ch (its operands are in a0 .. b1) and at most two more, clamped and masked.  Straight-line code: as a second loop it made the register
+    // allocator carry the accumulators of the main loop in VGPRs and copy all 32 to and from the AGPRs in every iteration.
+    fetch(ch + 1, na0, na1, nb0, nb1);
+    __builtin_amdgcn_sched_barrier(0);
+    mult(ch, a0, a1, b0, b1);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(ch + 2, a0, a1, b0, b1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (ch + 1 < nch) mult(ch + 1, na0, na1, nb0, nb1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (ch + 2 < nch) mult(ch + 2, a0, a1, b0, b1);
 #pragma unroll
     for (int nj = 0; nj < 2; ++nj)
 #pragma unroll

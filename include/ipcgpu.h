@@ -164,6 +164,12 @@ int ipcgpu_linsys_analyze_pattern(ipcgpu_ctx*); /* analyze_pattern, CHOLMODSolve
 int ipcgpu_linsys_factorize(ipcgpu_ctx*); /* factorize, :130-137; returns IPCGPU_NOT_PD */
 int ipcgpu_linsys_solve(ipcgpu_ctx*, const double* rhs, double* result); /* solve, :139-154 */
 int ipcgpu_linsys_precondition_diag(ipcgpu_ctx*, const double* in, double* out); /* :411-420 */
+/* TEST HOOK, not part of the solver interface the adapters use (its flags2 and the upload of result exist for tests/test_gpu_solve_boundary.py; it may change
+ * or go with them).  factorize + solve in one go, as the time stepper calls them (IPCGPU_SOLVER_MULTIFRONTAL: the forward sweep runs beside the factorisation).  result is
+ * uploaded first and read back afterwards, so an entry the solver does not write keeps the caller's value.  negate_rhs != 0: solves A x = -rhs.  wait == 0:
+ * everything is enqueued before the pivot flag is looked at, as in the stepper's Newton iteration.  flags2 (may be null): { the pivot flag as published to
+ * the host, the pivot flag read from device memory }, 0 = positive definite.  Returns IPCGPU_NOT_PD like ipcgpu_linsys_factorize. */
+int ipcgpu_linsys_factorize_solve(ipcgpu_ctx*, const double* rhs, double* result, int negate_rhs, int wait, int* flags2);
 /* IPCGPU_SOLVER_PCG: preconditioned conjugate gradients from x = 0, the reference's iterative choice (`linearSolver AMGCL`: CG to a relative
  * residual, AMGCLSolver.cpp:24-25, 44, 201, 225-232; its smoothed-aggregation hierarchy is not rebuilt: IPCGPU_PRECOND_TWO_LEVEL is a two-level
  * method with a coarse space of its own).  Defaults when set_iterative is never

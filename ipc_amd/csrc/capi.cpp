@@ -714,6 +714,26 @@ int ipcgpu_linsys_solve(ipcgpu_ctx* c, const double* rhs, double* x)
         return ok ? IPCGPU_OK : IPCGPU_NOT_PD;
     });
 }
+int ipcgpu_linsys_factorize_solve(ipcgpu_ctx* c, const double* rhs, double* x, int negateRhs, int wait, int* flags2)
+{
+    return guarded([&] {
+        bind(c);
+        HipLinSysSolver& l = L(c);
+        needArg(rhs && x, "null argument");
+        DevBuf<double> db, dx;
+        db.upload(rhs, l.numRows, c->stream);
+        dx.upload(x, l.numRows, c->stream);
+        bool ok = l.factorizeSolve(db.p, dx.p, wait != 0, negateRhs != 0);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        ok = ok && l.lastPivotsOk();
+        if (flags2) {
+            flags2[0] = ok ? 0 : 1;
+            flags2[1] = l.solverType == 0 ? l.devicePivotFlag() : flags2[0];
+        }
+        dx.download(x, l.numRows, c->stream);
+        return ok ? IPCGPU_OK : IPCGPU_NOT_PD;
+    });
+}
 int ipcgpu_linsys_precondition_diag(ipcgpu_ctx* c, const double* in, double* out)
 {
     return guarded([&] {

@@ -87,8 +87,11 @@ public:
     void analyze_pattern(const HipMesh* meshForCoords);
     bool factorize();
     bool solve(const double* rhs_dev, double* x_dev); // false: the iterative solver met p.Ap <= 0 (the exact solvers always return true)
-    bool factorizeSolve(const double* rhs_dev, double* x_dev, bool wait = true); // factorize + solve, forward sweep overlapped with the factorisation
+    // factorize + solve, forward sweep overlapped with the factorisation.  negateRhs (multifrontal solver only, solverType 0): solves A x = -rhs, the sign
+    // taken in the solver's own pass over the right-hand side
+    bool factorizeSolve(const double* rhs_dev, double* x_dev, bool wait = true, bool negateRhs = false);
     bool lastPivotsOk() const; // after factorizeSolve(..., wait = false) and a synchronisation of the stream
+    int devicePivotFlag() const { return num_.devicePivotFlag(); } // tests: the multifrontal solver's flag read from device memory (synchronises)
     bool lastSyncOk_ = true;
     void multiply(const double* x_dev, double* y_dev);
     void precondition_diag(const double* in_dev, double* out_dev);

@@ -356,11 +356,12 @@ bool HipLinSysSolver::factorize()
 }
 
 // factorize() followed by solve(), with the forward sweep running beside the factorisation (MfNumeric::factorizeSolve)
-bool HipLinSysSolver::factorizeSolve(const double* rhs_dev, double* x_dev, bool wait)
+bool HipLinSysSolver::factorizeSolve(const double* rhs_dev, double* x_dev, bool wait, bool negateRhs)
 {
     if (!analyzed_) throw StateError("factorize before analyze_pattern");
     lastSyncOk_ = true;
-    if (solverType == 0) return lastSyncOk_ = num_.factorizeSolve(d_a.p, rhs_dev, x_dev, wait);
+    if (solverType == 0) return lastSyncOk_ = num_.factorizeSolve(d_a.p, rhs_dev, x_dev, wait, negateRhs);
+    if (negateRhs) throw StateError("factorizeSolve: only the multifrontal solver takes the sign of the right-hand side");
     const bool ok = factorize();
     return lastSyncOk_ = ok && solve(rhs_dev, x_dev);
 }

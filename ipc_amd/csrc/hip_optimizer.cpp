@@ -1138,7 +1138,12 @@ void HipOptimizer::enqueueDirNorm()
 void HipOptimizer::computeSearchDir()
 {
     bool ok;
-    launch_negate(3 * mesh.nV, d_gradient.p, d_minusG.p, stream);
+    // The multifrontal solver takes the sign in the pass that permutes its right-hand side: no vector pass for -g on that path, where the diagonal fallback
+    // below forms d_minusG when it is taken.  The other solver types take d_minusG as their right-hand side as before.  (Elsewhere the buffer is scratch: the
+    // barrier gradient of the kappa update, the output of ipcgpu_bench_factor_solve.)
+    const bool signInSolver = lin.solverType == 0;
+    const double* const rhs = signInSolver ? d_gradient.p : d_minusG.p;
+    if (!signInSolver) launch_negate(3 * mesh.nV, d_gradient.p, d_minusG.p, stream);
     cachedTrialValid = false;
     cachedDistValid = false; // (|p|_inf of the direction this call replaces)
     if (fastPath()) {
@@ -1149,7 +1154,7 @@ void HipOptimizer::computeSearchDir()
         // bad pivot -> back to the iterate and the diagonal fallback; trial inverted or uphill -> back to the iterate and the general loop.
         Tic t(timers[3], stream); // (its synchronisation is the one)
         const size_t bytes = 3 * (size_t)mesh.nV * sizeof(double);
-        if (lin.factorizeSolve(d_minusG.p, d_searchDir.p, /*wait=*/false)) {
+        if (lin.factorizeSolve(rhs, d_searchDir.p, /*wait=*/false, signInSolver)) {
             // ten launches (fifteen before round 4: the resets, the copy + step-size + step and the two read-backs are one launch each now)
             launch_iter_reset(d_scalar.p, d_flag.p, stream); // (zeroes the slot of |p|_inf with the others: no enqueueDirNorm(), whose fill would be one launch more)
             launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
@@ -1188,7 +1193,7 @@ void HipOptimizer::computeSearchDir()
         if (worldSize == 1) {
             // one process: nothing waits inside the solver; |p|_inf for the convergence test of the next pass (Optimizer.cpp:1869-1879) is enqueued behind
             // the sweeps and the pivot flag comes back with it -- one synchronisation (round 6; two before, and a third at the head of the next pass)
-            ok = lin.factorizeSolve(d_minusG.p, d_searchDir.p, /*wait=*/false);
+            ok = lin.factorizeSolve(rhs, d_searchDir.p, /*wait=*/false, signInSolver);
             if (ok) {
                 enqueueDirNorm();
                 launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
@@ -1200,10 +1205,11 @@ void HipOptimizer::computeSearchDir()
                 }
             }
         }
-        else ok = lin.factorizeSolve(d_minusG.p, d_searchDir.p);
+        else ok = lin.factorizeSolve(rhs, d_searchDir.p, /*wait=*/true, signInSolver);
     }
     Tic t(timers[4], stream);
     if (!ok) {
+        if (signInSolver) launch_negate(3 * mesh.nV, d_gradient.p, d_minusG.p, stream);
         completeMatrix(); // (owner-computes sharding: the diagonal of the rows other ranks hold)
         lin.precondition_diag(d_minusG.p, d_searchDir.p); // Optimizer.cpp:2331-2348
     }
@@ -1528,15 +1534,14 @@ void HipOptimizer::buildTargetPositions(bool deferTolerance)
         tpIdsOnDevice = tpIds;
     }
     d_tpPos.ensure(3 * (size_t)n);
-    d_tpLam.ensure(3 * (size_t)n);
-    d_tpLam.zeroN(3 * (size_t)n, stream);
+    d_tpLam.ensure(3 * (size_t)n); // (cleared by the kernel below, which walks the same 3 n entries)
     // targets x + p formed on the device (round 6: x and p of the scripted nodes used to travel to the host, their sum back); the host only needs p for the tolerance,
     // summed there in index order as before.  deferTolerance: p goes to pinned host memory and finishTolerance() sums it behind the caller's next synchronisation
     // (through a device buffer and ONE copy into pinned memory: thousands of 8-byte stores of a kernel into mapped host memory are thousands of bus transactions --
     // 7 ms for the Dirichlet nodes of 4_rodsTwist when this was first written that way)
     if (h_tpStage.n < 3 * (size_t)n) h_tpStage.alloc(3 * (size_t)n + 3 * (size_t)n / 2 + 16);
     d_tpStage.ensure(3 * (size_t)n);
-    launch_target_positions(n, d_tpIds.p, mesh.d_x.p, d_searchDir.p, d_tpPos.p, d_tpStage.p, stream);
+    launch_target_positions(n, d_tpIds.p, mesh.d_x.p, d_searchDir.p, d_tpPos.p, d_tpStage.p, d_tpLam.p, stream);
     HIP_CHECK(hipMemcpyAsync(h_tpStage.p, d_tpStage.p, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
     tolPending = true;
     if (!deferTolerance) {

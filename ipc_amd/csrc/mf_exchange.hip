@@ -180,9 +180,9 @@ void MfNumeric::reduceSolution()
 // "a non-positive pivot was met" on any rank -> on every rank: one double
 void MfNumeric::allreduceFlag()
 {
-    hipLaunchKernelGGL(k_flag_to_double, dim3(1), dim3(1), 0, stream_, flag_.p, xchgBuf_.p);
+    hipLaunchKernelGGL(k_flag_to_double, dim3(1), dim3(1), 0, stream_, curFlag(), xchgBuf_.p);
     allreduceSum(xchgBuf_.p, 1);
-    hipLaunchKernelGGL(k_double_to_flag, dim3(1), dim3(1), 0, stream_, xchgBuf_.p, flag_.p);
+    hipLaunchKernelGGL(k_double_to_flag, dim3(1), dim3(1), 0, stream_, xchgBuf_.p, curFlag());
 }
 
 } // namespace ipcgpu

@@ -83,15 +83,23 @@ public:
     double sharedFlopFraction() const { return mp_.sharedFlops; } // share of the factorisation flops above the cut (executed once each since round 5, on the chain of the cut's levels)
     // a_dev: CSR values (device).  Returns false when a non-positive pivot was met.
     bool factorize(const double* a_dev);
-    // rhs_dev / x_dev: device vectors in the user's ordering
-    void solve(const double* rhs_dev, double* x_dev);
+    // rhs_dev / x_dev: device vectors in the user's ordering; negateRhs: solve A x = -rhs (the sign rides in the pass that permutes the right-hand side)
+    void solve(const double* rhs_dev, double* x_dev, bool negateRhs = false);
     // factorize(a) and solve(rhs) in one go, the forward sweep overlapped with the factorisation (single rank); returns false when a
     // non-positive pivot was met (x is then meaningless)
     // wait = false: everything is enqueued and the call returns true without synchronising (the pivot flag is on its way to pinned memory:
     // lastPivotsOk() after the caller's own synchronisation of the stream).  Returns false when the call had to take the synchronous
     // two-call sequence (sharded / graph runs) and the factorisation failed there.
-    bool factorizeSolve(const double* a_dev, const double* rhs_dev, double* x_dev, bool wait = true);
+    bool factorizeSolve(const double* a_dev, const double* rhs_dev, double* x_dev, bool wait = true, bool negateRhs = false);
     bool lastPivotsOk() const { return pivotsOk(); }
+    // tests: the last factorisation's flag read from device memory, not from the mapped slot it is published to (synchronises the stream)
+    int devicePivotFlag() const
+    {
+        int f = 0;
+        HIP_CHECK(hipMemcpyAsync(&f, curFlag(), sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        return f;
+    }
     bool pivotsOk() const; // false: a non-positive pivot
     bool ready() const { return ns_ > 0; }
     // diagnosis / tests: the slot of every entry of the user's matrix in the front buffer, as the set-up's device kernel computed it (nnz values)
@@ -100,7 +108,7 @@ public:
 
 private:
     void enqueueFactor(const double* a_dev, bool overlapForward = false);
-    void enqueueSolve(const double* rhs_dev, double* x_dev);
+    void enqueueSolve(const double* rhs_dev, double* x_dev, bool negateRhs);
     typedef MfRange Range;
     typedef MfLevelPlan LevelPlan;
     typedef MfXinvLevel XinvLevel;
@@ -134,7 +142,7 @@ private:
     void allreduceFlag();
     // mf_sweeps.hip
     void configureSweepKernels(size_t maxSolveLds, size_t maxBwdLds, size_t maxTriLds);
-    void enqueuePermuteRhs(const double* rhs_dev, hipStream_t st);
+    void enqueuePermuteRhs(const double* rhs_dev, hipStream_t st, bool negate);
     const MfSymbolic* sym_ = nullptr;
     hipStream_t stream_ = nullptr;
     int ns_ = 0, nLevels_ = 0;
@@ -153,17 +161,17 @@ private:
     hipEvent_t evRhs_ = nullptr, evFwdDone_ = nullptr;
     std::vector<hipEvent_t> evFactLevel_;
     void enqueueForwardLevel(int l, hipStream_t st);
-    void enqueueBackward(double* x_dev);
+    void enqueueBackward(double* x_dev, bool publishFlag = false); // publishFlag: the sweep's first launch also carries the pivot flag to its mapped slot
     hipEvent_t evSide_ = nullptr;
     std::vector<hipEvent_t> evLevel_, evInvDone_;
     bool sidePending_ = false; // the last factorisation left work on the side stream that nothing has waited for yet
     void enqueueInverses(int level, hipStream_t st);
     DevBuf<double> dinv_; // explicit inverses of the 32x32 diagonal blocks of L, 1024 doubles each
-    DevBuf<int> idx_, idxPtr_, firstNode_, childPtr_, child_, invPtr_, inv_, newOf_, flag_;
+    DevBuf<int> idx_, idxPtr_, firstNode_, childPtr_, child_, invPtr_, inv_, newOf_, oldOf_, flag_; // oldOf_: the caller's node of every permuted node (the backward kernels write x in the caller's order)
+    int flagCur_ = 0; // the slot of flag_ the current factorisation sets; the other one is cleared for the next (enqueueFactor)
+    int* curFlag() const { return flag_.p + flagCur_; }
     DevBuf<long long> frontOff_, wOff_, dinvOff_;
-    DevBuf<int> aSrc_, aLoc_; // entries of A per fused front: CSR source index, offset inside the LDS panel
-    DevBuf<double> aPerm_; // values of A gathered into fused-front order at the start of every factorisation
-    int nFusedA_ = 0;
+    DevBuf<int2> aEnt_; // entries of A per fused front: (offset inside the LDS panel, CSR source index), read through by k_front_fused
     DevBuf<int> bigFd_; // packed records of the other fronts (k_extend_add)
     DevBuf<int> fdesc_; // packed descriptors of the fused fronts (64 ints each, launch order)
     DevBuf<int> bigASrc_; // entries of A of the other fronts, grouped by extend-add tile: source index ...

@@ -36,15 +36,8 @@ namespace ipcgpu {
 namespace {
 
 __global__ void k_publish_flag(const int* __restrict__ flag, int* __restrict__ mapped) { mapped[0] = flag[0]; }
-
-// values of A in fused-front order: the fused kernel then reads its entries contiguously instead of chasing a[aSrc[e]]
-// (the first kernel of every factorisation: it also clears the pivot flag -- a memset of four bytes was a launch of its own on the critical path)
-__global__ void k_gather_a(int cnt, const int* __restrict__ src, const double* __restrict__ a, double* __restrict__ aP, int* __restrict__ flag)
-{
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k == 0) flag[0] = 0;
-    if (k < cnt) aP[k] = a[src[k]];
-}
+// (only behind a factorisation that launched no fused front, whose workgroup 0 clears the next factorisation's flag otherwise)
+__global__ void k_clear_flag(int* __restrict__ flag) { flag[0] = 0; }
 
 
 // desc = (record, ti, tj, 0): one 64 x 64 tile (ti >= tj) of a parent front.  `record` indexes a packed 64-int descriptor
@@ -131,7 +124,7 @@ __global__ __launch_bounds__(1024) void k_scan_exclusive(int n, const int* __res
     if (t == 1023) out[n] = part[1023];
 }
 __global__ void k_entry_scatter(int nnz, int ns, const long long* __restrict__ dst, const int* __restrict__ bucket, const int* __restrict__ start,
-    int* __restrict__ cursor, const long long* __restrict__ frontOff, int* __restrict__ aSrc, int* __restrict__ aLoc, int* __restrict__ bigSrc,
+    int* __restrict__ cursor, const long long* __restrict__ frontOff, int2* __restrict__ aEnt, int* __restrict__ bigSrc,
     long long* __restrict__ bigDst)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -140,8 +133,7 @@ __global__ void k_entry_scatter(int nnz, int ns, const long long* __restrict__ d
     if (b < 0) return;
     const int pos = start[b] + atomicAdd(&cursor[b], 1);
     if (b < ns) {
-        aSrc[pos] = k;
-        aLoc[pos] = (int)(dst[k] - frontOff[b]); // row + N * column, column < nc
+        aEnt[pos] = make_int2((int)(dst[k] - frontOff[b]), k); // (row + N * column inside the LDS panel, column < nc; index into the CSR values): read as one pair
     }
     else {
         const int q = pos - start[ns]; // the batched fronts' entries have an index space of their own
@@ -420,14 +412,17 @@ __device__ const int* g_probeBase;
 #endif
 template <int NT>
 __global__ __launch_bounds__(NT, 3) void k_front_fused(const int* __restrict__ fdesc, const int* __restrict__ invMap,
-    const int* __restrict__ aLoc, const double* __restrict__ aP, double* __restrict__ fronts,
-    double* __restrict__ dinv, int* __restrict__ flag)
+    const int2* __restrict__ aEnt, const double* __restrict__ a, double* __restrict__ fronts,
+    double* __restrict__ dinv, int* __restrict__ flag, int* __restrict__ flagNext)
 {
     extern __shared__ double P[];
     __shared__ double Xs[NB * LDX]; // inverse of the current pivot block
     __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid < FD_STRIDE) fd[tid] = fdesc[(size_t)blockIdx.x * FD_STRIDE + tid];
+    // flagNext (first launch of a factorisation only): the pivot flag of the NEXT factorisation, cleared here.  This factorisation's own flag was cleared
+    // by the one before it: a clear inside the launch that may set the flag would race with another workgroup's atomicOr.
+    if (flagNext && blockIdx.x == 0 && tid == 0) flagNext[0] = 0;
     __syncthreads();
     const int N = fd[2], nc = fd[3], nk = fd[8];
     double* F = fronts + *reinterpret_cast<const long long*>(fd);
@@ -445,6 +440,14 @@ __global__ __launch_bounds__(NT, 3) void k_front_fused(const int* __restrict__ f
     }
 #endif
     MF_PROBE(0);
+    // ---- entries of A, first round: the (location, source) pairs are requested now and the values a[source] behind the index maps, so that both round
+    // trips of the indirect read run beside the children's phase (the values used to be copied into front order by a launch of their own, k_gather_a:
+    // 11 us and 30 MB per factorisation on the chain)
+    const int aLast = max(aEnd - 1, 0);
+    int2 ent0[4];
+    double av0[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) ent0[u] = aEnt[min(aBeg + u * NT + tid, aLast)];
     // ---- index maps of the children
     for (int q = 0; q < nk; ++q) {
         const int* inv = invMap + fd[16 + 6 * q + 4];
@@ -455,6 +458,8 @@ __global__ __launch_bounds__(NT, 3) void k_front_fused(const int* __restrict__ f
             cm[q * N + I] = ic >= 0 ? ncc + 3 * ic + (I - 3 * In) : -1;
         }
     }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) av0[u] = a[ent0[u].y];
     __syncthreads();
     MF_PROBE(1);
     // ---- own columns: children sums (lower triangle), zeros above the diagonal.  The loads are unconditional (clamped
@@ -500,19 +505,20 @@ __global__ __launch_bounds__(NT, 3) void k_front_fused(const int* __restrict__ f
     __syncthreads();
     MF_PROBE(2);
     // ---- entries of A (every destination is distinct)
-    // aP: the values of A gathered into front order (k_gather_a); four (location, value) pairs requested per round
-    for (int e0 = aBeg; e0 < aEnd; e0 += 4 * NT) {
-        int loc[4];
+    // the first round arrived during the phases above; further rounds (a front with more than 4 NT entries): four pairs, then their four values, per round
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (aBeg + u * NT + tid < aEnd) P[ent0[u].x] += av0[u];
+    for (int e0 = aBeg + 4 * NT; e0 < aEnd; e0 += 4 * NT) {
+        int2 ent[4];
         double av[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e = min(e0 + u * NT + tid, aEnd - 1);
-            loc[u] = aLoc[e];
-            av[u] = aP[e];
-        }
+        for (int u = 0; u < 4; ++u) ent[u] = aEnt[min(e0 + u * NT + tid, aLast)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) av[u] = a[ent[u].y];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (e0 + u * NT + tid < aEnd) P[loc[u]] += av[u];
+            if (e0 + u * NT + tid < aEnd) P[ent[u].x] += av[u];
     }
     __syncthreads();
     MF_PROBE(3);
@@ -1614,10 +1620,13 @@ void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_d
     invPtr_.upload(sym.invPtr, stream);
     inv_.upload(sym.inv.empty() ? std::vector<int>{ 0 } : sym.inv, stream);
     newOf_.upload(sym.newOf, stream);
+    oldOf_.upload(sym.oldOf, stream);
     frontOff_.upload(std::vector<long long>(sym.frontOff.begin(), sym.frontOff.end()), stream);
     wOff_.upload(std::vector<long long>(sym.wOff.begin(), sym.wOff.end()), stream);
     lap("buffers + tree uploads");
-    flag_.alloc(1);
+    flag_.alloc(2); // two slots: a factorisation sets flag_[flagCur_] and clears the other one for its successor (k_front_fused)
+    flag_.zero(stream);
+    flagCur_ = 0;
     hflag_.alloc(4);
     auto newEvent = [] {
         hipEvent_t e;
@@ -1673,15 +1682,13 @@ void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_d
     std::vector<int> start((size_t)nBuckets + 1);
     bucketStart_.download(start.data(), start.size(), stream); // (synchronises)
     const size_t nFused = (size_t)start[ns_], nBig = (size_t)(start[nBuckets] - start[ns_]);
-    nFusedA_ = (int)nFused;
-    aPerm_.ensure(std::max<size_t>(nFused, 1));
-    aSrc_.ensure(nFused + 1);
-    aLoc_.ensure(nFused + 1);
+    aEnt_.ensure(nFused + 1);
+    aEnt_.zeroN(1, stream); // (a front without entries would still request its first pair)
     bigASrc_.ensure(nBig + 1);
     bigADst_.ensure(nBig + 1);
     if (nnz)
         hipLaunchKernelGGL(k_entry_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, (int)nnz, ns_, entryDst_.p, entryBucket_.p, bucketStart_.p,
-            bucketHist_.p + nBuckets + 1, frontOff_.p, aSrc_.p, aLoc_.p, bigASrc_.p, bigADst_.p);
+            bucketHist_.p + nBuckets + 1, frontOff_.p, aEnt_.p, bigASrc_.p, bigADst_.p);
     lap("A-entry lists");
     // plan, step 2 (beside the scatter kernel): every descriptor of the factorisation and of the sweeps
     planning([&] { mf_plan_launches(sym, start.data(), mp_); });
@@ -1759,7 +1766,7 @@ bool MfNumeric::factorize(const double* a_dev)
         // forest that was not cut (several bodies, world > number of roots) lives on one rank alone -- one double
         allreduceFlag();
     }
-    hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(1), 0, stream_, flag_.p, hflag_.dev); // mapped pinned memory: no blit
+    hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(1), 0, stream_, curFlag(), hflag_.dev); // mapped pinned memory: no blit
     HIP_CHECK(hipStreamSynchronize(stream_));
 #ifdef MF_FUSED_PROBE
     {
@@ -1797,26 +1804,26 @@ bool MfNumeric::pivotsOk() const
     return hflag_.p[0] == 0;
 }
 
-bool MfNumeric::factorizeSolve(const double* a_dev, const double* rhs_dev, double* x_dev, bool wait)
+bool MfNumeric::factorizeSolve(const double* a_dev, const double* rhs_dev, double* x_dev, bool wait, bool negateRhs)
 {
     if (!sym_) throw StateError("factorize before analyze_pattern");
     if (world_ > 1 || !fwd_) { // sharded runs keep the two-call sequence
         const bool ok = factorize(a_dev);
-        if (ok) solve(rhs_dev, x_dev);
+        if (ok) solve(rhs_dev, x_dev, negateRhs);
         return ok;
     }
     // the right-hand side is ready on the main stream now: permute it on the forward stream, then level by level behind the factorisation
     HIP_CHECK(hipEventRecord(evRhs_, stream_));
     HIP_CHECK(hipStreamWaitEvent(fwd_, evRhs_, 0));
-    enqueuePermuteRhs(rhs_dev, fwd_);
+    enqueuePermuteRhs(rhs_dev, fwd_, negateRhs);
     fwdJoined_ = false;
     enqueueFactor(a_dev, true);
     if (!fwdJoined_) HIP_CHECK(hipEventRecord(evFwdDone_, fwd_));
-    hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(1), 0, stream_, flag_.p, hflag_.dev);
     // the backward sweep follows the root's forward result; enqueued before the flag is looked at (a failed pivot makes x meaningless,
-    // the caller falls back to the diagonal preconditioner as after factorize() == false)
+    // the caller falls back to the diagonal preconditioner as after factorize() == false).  The pivot flag is final here: the first launch of the
+    // sweep carries it to its mapped slot (a launch of its own, k_publish_flag, used to sit between the two sweeps)
     if (!fwdJoined_) HIP_CHECK(hipStreamWaitEvent(stream_, evFwdDone_, 0));
-    enqueueBackward(x_dev);
+    enqueueBackward(x_dev, /*publishFlag=*/true);
     if (!wait) return true;
     HIP_CHECK(hipStreamSynchronize(stream_));
     return pivotsOk();
@@ -1835,19 +1842,23 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
         HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_probeBase), &base, sizeof(base), 0, hipMemcpyHostToDevice, stream_));
     }
 #endif
-    if (nFusedA_) hipLaunchKernelGGL(k_gather_a, dim3((nFusedA_ + 255) / 256), dim3(256), 0, stream_, nFusedA_, aSrc_.p, a_dev, aPerm_.p, flag_.p);
-    else flag_.zero(stream_);
+    // the pivot flag of this factorisation: the slot the previous one cleared (setup() cleared both).  The first fused launch clears the other slot for the
+    // next factorisation; a tree without fused fronts does it with a one-thread launch behind its last kernel
+    flagCur_ ^= 1;
+    int* const flag = flag_.p + flagCur_;
+    int* flagNext = flag_.p + (flagCur_ ^ 1);
     for (int l = 0; l < nLevels_; ++l) {
         const LevelPlan& P = mp_.level[l];
         if (P.small.cnt)
         {
             const int* fd = fdesc_.p + (size_t)P.small.off * FD_STRIDE;
             if (P.smallThreads == 512)
-                hipLaunchKernelGGL(k_front_fused<512>, dim3(P.small.cnt), dim3(512), P.smallLds, stream_, fd, inv_.p, aLoc_.p, aPerm_.p, fronts_.p,
-                    dinv_.p, flag_.p);
+                hipLaunchKernelGGL(k_front_fused<512>, dim3(P.small.cnt), dim3(512), P.smallLds, stream_, fd, inv_.p, aEnt_.p, a_dev, fronts_.p,
+                    dinv_.p, flag, flagNext);
             else
-                hipLaunchKernelGGL(k_front_fused<256>, dim3(P.small.cnt), dim3(256), P.smallLds, stream_, fd, inv_.p, aLoc_.p, aPerm_.p, fronts_.p,
-                    dinv_.p, flag_.p);
+                hipLaunchKernelGGL(k_front_fused<256>, dim3(P.small.cnt), dim3(256), P.smallLds, stream_, fd, inv_.p, aEnt_.p, a_dev, fronts_.p,
+                    dinv_.p, flag, flagNext);
+            flagNext = nullptr;
         }
         if (P.ea.cnt) {
             hipLaunchKernelGGL(k_extend_add, dim3(P.ea.cnt), dim3(WG), 0, stream_, eaDesc_.p + P.ea.off, bigFd_.p, inv_.p, fronts_.p, P.fuseEA ? 1 : 0, eaAPtr_.p,
@@ -1855,8 +1866,8 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
         }
         for (const Range& R : P.step) { // one launch per 32-column step, each with look-ahead (k_big_step)
             if (!R.cnt) continue;
-            if (P.stepTop) hipLaunchKernelGGL(k_big_step<true>, dim3(R.cnt), dim3(WGB), 0, stream_, desc_.p + R.off, tv, fronts_.p, dinv_.p, flag_.p, xvF);
-            else hipLaunchKernelGGL(k_big_step<false>, dim3(R.cnt), dim3(WGB), 0, stream_, desc_.p + R.off, tv, fronts_.p, dinv_.p, flag_.p, xvF);
+            if (P.stepTop) hipLaunchKernelGGL(k_big_step<true>, dim3(R.cnt), dim3(WGB), 0, stream_, desc_.p + R.off, tv, fronts_.p, dinv_.p, flag, xvF);
+            else hipLaunchKernelGGL(k_big_step<false>, dim3(R.cnt), dim3(WGB), 0, stream_, desc_.p + R.off, tv, fronts_.p, dinv_.p, flag, xvF);
             const Range& U = P.bulk[&R - P.step.data()]; // wide fronts: the outer block that ended with this launch's panel goes to the own columns behind it
             if (U.cnt) hipLaunchKernelGGL(k_big_bulk, dim3(U.cnt), dim3(WG), 0, stream_, desc_.p + U.off, fronts_.p);
         }
@@ -1907,6 +1918,7 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
     // stream does not wait here: enqueueSolve waits per level, the next factorisation waits before it touches the fronts.
     if (sideUsed) HIP_CHECK(hipEventRecord(evSide_, side_));
     sidePending_ = sideUsed;
+    if (flagNext) hipLaunchKernelGGL(k_clear_flag, dim3(1), dim3(1), 0, stream_, flagNext);
 }
 
 // X = L11^-1 of the fronts of one level (see k_xinv_*), enqueued on `st`

@@ -8,6 +8,10 @@
 #ifndef FWD_NARROW
 #define FWD_NARROW 1 // the forward sweep of the narrow levels with two waves per workgroup as well (0: four)
 #endif
+#ifndef MF_BWD_DIRECT_X
+#define MF_BWD_DIRECT_X 0 // 1: the backward kernels store x in the caller's order themselves, no k_unpermute_x behind the sweep.  Measured and put back: the second
+                          // store and its index load cost the ~14 dependent launches of the sweep more than the one launch saves (-0.3 %, profiles/solve_boundary_ab.txt)
+#endif
 #ifndef BWD_NARROW_MAX_N
 #define BWD_NARROW_MAX_N 160 // levels whose fronts have at most this many rows sweep backward with two waves per workgroup (0 = never)
 #endif
@@ -17,14 +21,18 @@ namespace ipcgpu {
 namespace {
 
 // ---- triangular solves ------------------------------------------------------------------------------------
-__global__ void k_permute_rhs(int nn, const int* __restrict__ newOf, const double* __restrict__ b, double* __restrict__ bp)
+// negate: bp = -b permuted (the stepper's right-hand side is minus the gradient: the sign rides here instead of in a vector pass of its own; exact)
+__global__ void k_permute_rhs(int nn, const int* __restrict__ newOf, const double* __restrict__ b, double* __restrict__ bp, int negate)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 3 * nn) {
         int v = i / 3, d = i - 3 * v;
-        bp[3 * newOf[v] + d] = b[i];
+        bp[3 * newOf[v] + d] = negate ? -b[i] : b[i];
     }
 }
+// (only where the backward sweep launches nothing that could carry the flag: an empty tree)
+__global__ void k_publish_flag_late(const int* __restrict__ flag, int* __restrict__ mapped) { mapped[0] = flag[0]; }
+// (sharded runs only: there the solution is summed over the ranks in elimination order first)
 __global__ void k_unpermute_x(int nn, const int* __restrict__ newOf, const double* __restrict__ xp, double* __restrict__ x)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -32,6 +40,26 @@ __global__ void k_unpermute_x(int nn, const int* __restrict__ newOf, const doubl
         int v = i / 3, d = i - 3 * v;
         x[i] = xp[3 * newOf[v] + d];
     }
+}
+
+// What the backward kernels write beside xsol (which stays in elimination order: the descendants read it).  xout: the solution in the caller's node order,
+// every kernel for the columns of its own fronts (null: k_unpermute_x follows); oldOf: the caller's node of a permuted node.  mapped (first launch of the
+// sweep behind an overlapped factorisation, else null): the slot in mapped host memory the final pivot flag is carried to.
+struct BwdOut {
+    double* xout;
+    const int* oldOf;
+    const int* flag;
+    int* mapped;
+};
+// position in xout of permuted scalar index p (requested at the head of a kernel for the entries a thread will write at its end)
+__device__ __forceinline__ int xout_pos(const BwdOut& o, int p)
+{
+    const int pn = p / 3;
+    return 3 * o.oldOf[pn] + (p - 3 * pn);
+}
+__device__ __forceinline__ void publish_flag(const BwdOut& o)
+{
+    if (o.mapped && blockIdx.x == 0 && threadIdx.x == 0) o.mapped[0] = o.flag[0];
 }
 
 // w[I] of a front: own right-hand side rows plus what the children pushed up.  Four children at a time, level by level of
@@ -269,7 +297,7 @@ __global__ __launch_bounds__(WG) void k_big_fwd_rect(const int4* __restrict__ de
 // the level -- one latency-bound round of workgroups -- takes 22 instead of 36 us)
 template <int NT>
 __global__ __launch_bounds__(NT) void k_bwd_level(const int* __restrict__ list, TreeView tv, const double* __restrict__ fronts,
-    const double* __restrict__ dinv, const double* __restrict__ yperm, double* __restrict__ xsol)
+    const double* __restrict__ dinv, const double* __restrict__ yperm, double* __restrict__ xsol, BwdOut out)
 {
     constexpr int NW = NT / 64;
     extern __shared__ double x[];
@@ -280,6 +308,8 @@ __global__ __launch_bounds__(NT) void k_bwd_level(const int* __restrict__ list, 
     const int* idx = tv.idx + tv.idxPtr[s];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col0 = 3 * tv.firstNode[s];
+    publish_flag(out);
+    const int xo0 = (out.xout && tid < nc) ? xout_pos(out, col0 + tid) : 0;
     for (int I = tid; I < N; I += NT) {
         const int In = I / 3;
         x[I] = (I < nc) ? yperm[col0 + I] : xsol[3 * idx[In] + (I - 3 * In)];
@@ -315,7 +345,10 @@ __global__ __launch_bounds__(NT) void k_bwd_level(const int* __restrict__ list, 
     }
     __syncthreads();
     bwd_triangle<NT>(L, N, nc, dinv + tv.dinvOff[s] * (NB * NB), x, invs, tid);
-    for (int I = tid; I < nc; I += NT) xsol[col0 + I] = x[I];
+    for (int I = tid; I < nc; I += NT) {
+        xsol[col0 + I] = x[I];
+        if (out.xout) out.xout[I == tid ? xo0 : xout_pos(out, col0 + I)] = x[I];
+    }
 }
 
 // big fronts, backward prologue: y_c -= sum_{r >= nc} L(r, c) x_r  (x of the ancestors).  desc = (front, first column, 0, 0);
@@ -380,7 +413,7 @@ __global__ __launch_bounds__(WG) void k_big_bwd_init(const int4* __restrict__ de
 }
 // ... then one workgroup sweeps the transposed triangle
 __global__ __launch_bounds__(WGT) void k_big_bwd_tri(const int* __restrict__ list, TreeView tv, const double* __restrict__ fronts,
-    const double* __restrict__ dinv, const double* __restrict__ yperm, double* __restrict__ xsol)
+    const double* __restrict__ dinv, const double* __restrict__ yperm, double* __restrict__ xsol, BwdOut out)
 {
     extern __shared__ double t[];
     __shared__ double invs[NB * LDP];
@@ -389,10 +422,15 @@ __global__ __launch_bounds__(WGT) void k_big_bwd_tri(const int* __restrict__ lis
     const double* L = fronts + tv.frontOff[s];
     const int tid = threadIdx.x;
     const int col0 = 3 * tv.firstNode[s];
+    publish_flag(out);
+    const int xo0 = (out.xout && tid < nc) ? xout_pos(out, col0 + tid) : 0;
     for (int I = tid; I < nc; I += WGT) t[I] = yperm[col0 + I];
     __syncthreads();
     bwd_triangle<WGT>(L, N, nc, dinv + tv.dinvOff[s] * (NB * NB), t, invs, tid);
-    for (int I = tid; I < nc; I += WGT) xsol[col0 + I] = t[I];
+    for (int I = tid; I < nc; I += WGT) {
+        xsol[col0 + I] = t[I];
+        if (out.xout) out.xout[I == tid ? xo0 : xout_pos(out, col0 + I)] = t[I];
+    }
 }
 
 // forward: y1 = X w1.  desc = (front, first row, 0, 0): 32 rows per workgroup, eight column groups.
@@ -451,7 +489,7 @@ __global__ __launch_bounds__(WG) void k_xinv_fwd(const int4* __restrict__ desc, 
 // backward: x1 = X^T t with t = y1 - L21^T x2 (left in yperm by k_big_bwd_init).  desc = (front, first column, 0, 0):
 // one wave per column (contiguous reads), 16 columns per workgroup.
 __global__ __launch_bounds__(WG) void k_xinv_bwd(const int4* __restrict__ desc, TreeView tv, XinvView xv, const double* __restrict__ yperm,
-    double* __restrict__ xsol)
+    double* __restrict__ xsol, BwdOut out)
 {
     extern __shared__ double tt[];
     const int4 d = desc[blockIdx.x];
@@ -468,6 +506,12 @@ __global__ __launch_bounds__(WG) void k_xinv_bwd(const int4* __restrict__ desc, 
     double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
 #pragma unroll
     for (int q = 0; q < 4; ++q) cq[q] = c0 + wave + 4 * q;
+    publish_flag(out);
+    int xo[4] = { 0, 0, 0, 0 };
+    if (out.xout && lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xo[q] = xout_pos(out, col0 + min(cq[q], nc - 1));
+    }
     for (int r0 = c0 + wave; r0 < nc; r0 += 128) {
         const int ra = r0 + lane, rb = r0 + 64 + lane;
         const double ta = (ra < nc) ? tt[min(ra, nc - 1) - c0] : 0.0, tb = (rb < nc) ? tt[min(rb, nc - 1) - c0] : 0.0;
@@ -486,7 +530,10 @@ __global__ __launch_bounds__(WG) void k_xinv_bwd(const int4* __restrict__ desc, 
         double t = acc[q];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-        if (lane == 0 && cq[q] < min(nc, c0 + 16)) xsol[col0 + cq[q]] = t;
+        if (lane == 0 && cq[q] < min(nc, c0 + 16)) {
+            xsol[col0 + cq[q]] = t;
+            if (out.xout) out.xout[xo[q]] = t;
+        }
     }
 }
 
@@ -515,23 +562,23 @@ void MfNumeric::configureSweepKernels(size_t maxSolveLds, size_t maxBwdLds, size
 }
 
 // the right-hand side into the elimination order (on the forward stream when the forward sweep runs beside the factorisation)
-void MfNumeric::enqueuePermuteRhs(const double* rhs_dev, hipStream_t st)
+void MfNumeric::enqueuePermuteRhs(const double* rhs_dev, hipStream_t st, bool negate)
 {
     const int n3 = sym_->n;
-    hipLaunchKernelGGL(k_permute_rhs, dim3((n3 + 255) / 256), dim3(256), 0, st, sym_->nn, newOf_.p, rhs_dev, bperm_.p);
+    hipLaunchKernelGGL(k_permute_rhs, dim3((n3 + 255) / 256), dim3(256), 0, st, sym_->nn, newOf_.p, rhs_dev, bperm_.p, negate ? 1 : 0);
 }
 
-void MfNumeric::solve(const double* rhs_dev, double* x_dev)
+void MfNumeric::solve(const double* rhs_dev, double* x_dev, bool negateRhs)
 {
     if (!sym_) throw StateError("solve before analyze_pattern");
-    enqueueSolve(rhs_dev, x_dev);
+    enqueueSolve(rhs_dev, x_dev, negateRhs);
 }
 
-void MfNumeric::enqueueSolve(const double* rhs_dev, double* x_dev)
+void MfNumeric::enqueueSolve(const double* rhs_dev, double* x_dev, bool negateRhs)
 {
     // the permuted right-hand side stays in its own buffer: the forward kernels of a level write y into yperm while other
     // workgroups of the same launch still gather right-hand-side entries
-    enqueuePermuteRhs(rhs_dev, stream_);
+    enqueuePermuteRhs(rhs_dev, stream_, negateRhs);
     for (int l = 0; l < nLevels_; ++l) {
         const LevelPlan& P = mp_.level[l];
         if (P.xinvFwd.cnt && sidePending_) HIP_CHECK(hipStreamWaitEvent(stream_, evInvDone_[l], 0));
@@ -564,12 +611,21 @@ void MfNumeric::enqueueForwardLevel(int l, hipStream_t st)
         hipLaunchKernelGGL(k_big_fwd_rect, dim3(P.fwdRect.cnt), dim3(WG), 0, st, desc_.p + P.fwdRect.off, tv, wOff_.p, fronts_.p, w_.p, yperm_.p);
 }
 
-void MfNumeric::enqueueBackward(double* x_dev)
+void MfNumeric::enqueueBackward(double* x_dev, bool publishFlag)
 {
     const MfSymbolic& sym = *sym_;
     TreeView tv{ frontOff_.p, idxPtr_.p, firstNode_.p, childPtr_.p, child_.p, invPtr_.p, inv_.p, idx_.p, dinvOff_.p };
     XinvView xv{ xinvOff_.p, xinvX_.p, xinvT_.p };
     const int n3 = sym.n;
+    // MF_BWD_DIRECT_X on one rank: every kernel writes its own columns of x in the caller's order.  Otherwise k_unpermute_x follows the sweep (sharded: behind
+    // the sum of the ranks' parts in elimination order, reduceSolution)
+    const bool direct = MF_BWD_DIRECT_X && world_ <= 1;
+    BwdOut out{ direct ? x_dev : nullptr, oldOf_.p, curFlag(), publishFlag ? hflag_.dev : nullptr };
+    bool published = !publishFlag;
+    auto launched = [&] { // (behind every launch that takes `out`: the first one carried the flag)
+        out.mapped = nullptr;
+        published = true;
+    };
 #ifdef MF_BWD_PROBE // diagnosis build (-DMF_BWD_PROBE): timing events between the launches of the backward sweep, printed once (profiles/r06_backward_sweep_probe.txt)
     static int probeCall = 0;
     const bool probe = ++probeCall == 40;
@@ -595,18 +651,21 @@ void MfNumeric::enqueueBackward(double* x_dev)
         if (P.bwdInit.cnt) mark("bwd_init", l);
         if (P.bigTri.cnt)
             hipLaunchKernelGGL(k_big_bwd_tri, dim3(P.bigTri.cnt), dim3(WGT), P.triLds, stream_, triList_.p + P.bigTri.off, tv, fronts_.p,
-                dinv_.p, yperm_.p, xsol_.p);
+                dinv_.p, yperm_.p, xsol_.p, out);
+        if (P.bigTri.cnt) launched();
         if (P.bigTri.cnt) mark("bwd_tri", l);
         if (P.xinvBwd.cnt)
             hipLaunchKernelGGL(k_xinv_bwd, dim3(P.xinvBwd.cnt), dim3(WG), mp_.xinvLds, stream_, xinvDesc_.p + P.xinvBwd.off, tv, xv, yperm_.p,
-                xsol_.p);
+                xsol_.p, out);
+        if (P.xinvBwd.cnt) launched();
         if (P.small.cnt) {
             if (P.solveLds <= BWD_NARROW_MAX_N * sizeof(double))
                 hipLaunchKernelGGL(k_bwd_level<128>, dim3(P.small.cnt), dim3(128), P.solveLds, stream_, smallList_.p + P.small.off, tv, fronts_.p, dinv_.p,
-                    yperm_.p, xsol_.p);
+                    yperm_.p, xsol_.p, out);
             else
                 hipLaunchKernelGGL(k_bwd_level<256>, dim3(P.small.cnt), dim3(WG), P.solveLds, stream_, smallList_.p + P.small.off, tv, fronts_.p, dinv_.p,
-                    yperm_.p, xsol_.p);
+                    yperm_.p, xsol_.p, out);
+            launched();
         }
         if (P.xinvBwd.cnt || P.small.cnt) mark("xinv/small", l);
         if (world_ > 1) exchange(xchg_[l].opsX); // solution entries of this level's fronts above the cut -> the ranks that execute fronts below them
@@ -621,8 +680,11 @@ void MfNumeric::enqueueBackward(double* x_dev)
         }
     }
 #endif
-    if (world_ > 1) reduceSolution(); // every rank holds the solution of the fronts it executed: sum of the masked parts (mf_exchange.hip)
-    hipLaunchKernelGGL(k_unpermute_x, dim3((n3 + 255) / 256), dim3(256), 0, stream_, sym.nn, newOf_.p, xsol_.p, x_dev);
+    if (!published) hipLaunchKernelGGL(k_publish_flag_late, dim3(1), dim3(1), 0, stream_, out.flag, hflag_.dev); // (a tree without a single front)
+    if (!direct) {
+        if (world_ > 1) reduceSolution(); // every rank holds the solution of the fronts it executed: sum of the masked parts (mf_exchange.hip; nodeExec_ exists on sharded runs only)
+        hipLaunchKernelGGL(k_unpermute_x, dim3((n3 + 255) / 256), dim3(256), 0, stream_, sym.nn, newOf_.p, xsol_.p, x_dev);
+    }
 }
 
 } // namespace ipcgpu

@@ -677,9 +677,10 @@ __global__ void k_gather3(int n, const int* __restrict__ ids, const double* __re
     const int k = i / 3, c = i - 3 * k;
     out[i] = x[3 * (size_t)ids[k] + c];
 }
-// target positions of the scripted nodes (AnimScripter.cpp:2150-2157): pos = x + p at the listed nodes, and p at those nodes for the host's tolerance sum
+// target positions of the scripted nodes (AnimScripter.cpp:2150-2157): pos = x + p at the listed nodes, and p at those nodes for the host's tolerance sum;
+// lam: the multipliers of the same 3 n entries start the time step at zero (a memset of its own in front of this launch until the solve-boundary change)
 __global__ void k_target_positions(int n, const int* __restrict__ ids, const double* __restrict__ x, const double* __restrict__ p, double* __restrict__ pos,
-    double* __restrict__ pOut)
+    double* __restrict__ pOut, double* __restrict__ lam)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 3 * n) return;
@@ -688,6 +689,7 @@ __global__ void k_target_positions(int n, const int* __restrict__ ids, const dou
     const double pi = p[j];
     pOut[i] = pi;
     pos[i] = x[j] + pi; // (the same sum the host formed: x[i] += p[i])
+    lam[i] = 0.0;
 }
 // scripted Dirichlet motion (AnimScripter.cpp:1440-1462): p += R (x - c) + c + linVel dt - x
 __global__ void k_dbc_motion(int n, const int* __restrict__ ids, DbcMotion m, const double* __restrict__ x, double* __restrict__ p)
@@ -1063,9 +1065,9 @@ void launch_mdbc_lambda(const MdbcView& m, const double* x, double rho, hipStrea
 {
     if (m.n) hipLaunchKernelGGL(k_mdbc_lambda, dim3(nblk(3LL * m.n)), dim3(BLOCK), 0, s, m.n, m.ids, m.pos, m.lam, m.mass, x, rho);
 }
-void launch_target_positions(int n, const int* ids, const double* x, const double* p, double* pos, double* pOut, hipStream_t s)
+void launch_target_positions(int n, const int* ids, const double* x, const double* p, double* pos, double* pOut, double* lam, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_target_positions, dim3(nblk(3LL * n)), dim3(BLOCK), 0, s, n, ids, x, p, pos, pOut);
+    if (n) hipLaunchKernelGGL(k_target_positions, dim3(nblk(3LL * n)), dim3(BLOCK), 0, s, n, ids, x, p, pos, pOut, lam);
 }
 void launch_gather3(int n, const int* ids, const double* x, double* out, hipStream_t s)
 {

@@ -1,5 +1,5 @@
 """Where one Newton iteration of the bench spends its wall time, from a rocprofv3 kernel-trace csv (`--kernel-trace --output-format csv`).
-An iteration = everything between two k_unpermute_x launches.  Kernels are put into classes; for each class: busy time (union of its intervals),
+An iteration = everything between two k_permute_rhs launches.  Kernels are put into classes; for each class: busy time (union of its intervals),
 first start and last end relative to the iteration; plus the union over all kernels (GPU busy) against the iteration's wall time.
 usage: python tools/iter_breakdown.py <dir with *kernel_trace.csv> [first] [count]"""
 import csv
@@ -42,7 +42,7 @@ def main():
         for r in csv.DictReader(fh):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Queue_Id"]))
     rows.sort()
-    idx = [i for i, r in enumerate(rows) if "k_unpermute_x" in r[2]]
+    idx = [i for i, r in enumerate(rows) if "k_permute_rhs" in r[2]]
     acc = {}
     walls, busys = [], []
     for it in range(first, first + count):

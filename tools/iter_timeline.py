@@ -1,6 +1,6 @@
 """Launch-by-launch timeline of ONE Newton iteration of the bench out of a rocprofv3 kernel-trace csv (`--kernel-trace --output-format csv`):
 kernel, queue, start relative to the iteration, duration, gap to the previous end on the same queue, workgroups.
-An iteration = everything between two k_unpermute_x launches.
+An iteration = everything between two k_permute_rhs launches.
 usage: python tools/iter_timeline.py <dir with *kernel_trace.csv> [which iteration]"""
 import csv
 import glob
@@ -17,7 +17,7 @@ def main():
             wg = max(int(r.get("Workgroup_Size_X", r.get("Workgroup_Size", 1)) or 1), 1)
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Queue_Id"], int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0) // wg))
     rows.sort()
-    idx = [i for i, r in enumerate(rows) if "k_unpermute_x" in r[2]]
+    idx = [i for i, r in enumerate(rows) if "k_permute_rhs" in r[2]]
     seq = rows[idx[which] + 1:idx[which + 1] + 1]
     t0 = rows[idx[which]][1]
     qs = sorted(set(r[3] for r in seq))

@@ -1,4 +1,4 @@
-"""Per-dispatch timeline of one factorisation + solve (everything between two k_unpermute_x launches) out of a rocprofv3
+"""Per-dispatch timeline of one factorisation + solve (everything between two k_permute_rhs launches) out of a rocprofv3
 kernel-trace database.
 usage: python tools/rocprof_timeline.py <results.db> [which]"""
 import sqlite3
@@ -9,7 +9,7 @@ def main():
     db = sqlite3.connect(sys.argv[1])
     which = int(sys.argv[2]) if len(sys.argv) > 2 else 10
     rows = db.execute("select name,start,end,grid_x,workgroup_x from kernels order by start").fetchall()
-    idx = [i for i, r in enumerate(rows) if "k_unpermute_x" in r[0]]
+    idx = [i for i, r in enumerate(rows) if "k_permute_rhs" in r[0]]
     seq = rows[idx[which] + 1:idx[which + 1] + 1]
     t0 = seq[0][1]
     prev_end = t0

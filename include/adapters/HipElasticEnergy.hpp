@@ -64,7 +64,8 @@ class HipElasticEnergy : public Energy<3> {
     }
 
 public:
-    // energyType: 0 = neo-Hookean (needs the inversion safeguard), 1 = fixed corotated (Config.cpp:107-111)
+    // energyType: 0 = neo-Hookean (needs the inversion safeguard), 1 = fixed corotated (Config.cpp:107-111), 2 = stable neo-Hookean (ipcgpu.h; the reference's
+    // Config cannot express it, and like FCR it has no safeguard: Energy<3>(false))
     // may be constructed before the mesh is uploaded (the optimizer adapter creates it ahead of its base class)
     HipElasticEnergy(ipcgpu_ctx* shared, int energyType = 0) : Energy<3>(energyType == 0), ctx(shared), energyType_(energyType) {}
 

@@ -90,7 +90,16 @@ int ipcgpu_clear_dbc(ipcgpu_ctx*);
 int ipcgpu_set_component_material(ipcgpu_ctx*, int nodeBegin, int nodeEnd, int tetBegin, int tetEnd, double rho, double YM, double PR);
 /* Config `energy NH|FCR` (src/Config.cpp:23-24,107-111; selects NeoHookeanEnergy or FixedCoRotEnergy in main.cpp): 0 = NH,
  * 1 = FCR (src/Energy/Physics_Elasticity/FixedCoRotEnergy.cpp:62-153).  FCR has no element-inversion safeguard
- * (Energy<dim>(false)): inversion checks and the injective step filter are skipped as in Optimizer.cpp:252,517,545,2710. */
+ * (Energy<dim>(false)): inversion checks and the injective step filter are skipped as in Optimizer.cpp:252,517,545,2710.
+ * 2 = SNH, the stable neo-Hookean energy (Smith, de Goes, Kim, "Stable Neo-Hookean Flesh Simulation", ACM TOG 2018; no counterpart in the reference).  The
+ * element's Lame parameters (ipcgpu_get_features / ipcgpu_set_mesh_features) keep their meaning; the kernels apply the paper's 3-D reparametrisation where
+ * they load them:  mu = 4/3 mu_L, lam = lam_L + 5/6 mu_L, alpha = 1 + 3 mu / (4 lam), and with I_C = |F|_F^2, J = det F, c = I_C / (I_C + 1), k = lam (J - alpha)
+ *   psi = mu/2 (I_C - 3) + lam/2 (J - alpha)^2 - mu/2 log(I_C + 1) - psi0,  psi0 = 9 mu^2 / (32 lam) - mu/2 log 4  (psi(I) = 0),   P = mu c F + k cof F.
+ * Finite and C2 for every F (inverted, flat, F = 0), rest-stable, and d2psi/dF2 at F = I is Hooke's tensor of (mu_L, lam_L).  Energy and gradient need no SVD;
+ * the projected Hessian uses the sigma-space blocks A_ii = mu c + 2 mu s_i^2 / (I_C+1)^2 + lam n_i^2, A_ij = 2 mu s_i s_j / (I_C+1)^2 + lam n_i n_j + k s_m
+ * (n_i the product of the other two singular values, m the third index) and B_ij = [[mu c, -k s_m], [-k s_m, mu c]], eigenvalues mu c -+ k s_m clamped at 0.
+ * Like FCR, SNH has no element-inversion safeguard: ipcgpu_filter_step_size returns the step untouched and the stepper neither launches nor consults an
+ * inversion check.  ipcgpu_check_inversion under SNH is the plain mesh query (det < 0 of some element).  Any other value: IPCGPU_ERR_ARG. */
 int ipcgpu_set_energy_type(ipcgpu_ctx*, int energy_type);
 /* Mesh::V (current positions) */
 int ipcgpu_set_positions(ipcgpu_ctx*, const double* V_colmajor);
@@ -122,6 +131,8 @@ int ipcgpu_elastic_energy_per_elem(ipcgpu_ctx*, double* perElem_nT);
  * F the deformation gradient, J = det F, mu / lam the element's Lame parameters:
  *   NH   sigma = (mu (F F^T - I) + lam ln J I) / J
  *   FCR  sigma = 2 mu (F - R) F^T / J + lam (J - 1) I,  R = U V^T the rotation of the SVD F = U diag(s) V^T (only s_2 may be negative)
+ *   SNH  sigma = mu c F F^T / J + k I  with the reparametrised mu, lam and c, k of ipcgpu_set_energy_type; finite for J < 0 (nInvalid = 0) like FCR, inf or
+ *        NaN, uncounted, at J = 0 exactly
  * perElem: column-major nT x 8 -- sxx, syy, szz, sxy, syz, sxz (the symmetric-tensor order of VTK), the von Mises stress sqrt(3/2 dev sigma : dev
  * sigma), J.  An element without stiffness (mu = lam = 0) gets zeros and its J.  An NH element with J <= 0 has no stress: NaN in all eight entries,
  * and *nInvalid counts such elements; FCR is finite for inverted elements (nInvalid = 0) as long as J != 0 -- at J = 0 exactly P F^T / J is inf or

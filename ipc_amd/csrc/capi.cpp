@@ -280,7 +280,7 @@ int ipcgpu_set_energy_type(ipcgpu_ctx* c, int energyType)
     specChanged(c);
     return guarded([&] {
         HipMesh& m = M(c);
-        needArg(energyType == 0 || energyType == 1, "energy type: 0 = NH, 1 = FCR");
+        needArg(energyType >= 0 && energyType <= 2, "energy type: 0 = NH, 1 = FCR, 2 = SNH");
         m.energyType = energyType;
         return IPCGPU_OK;
     });
@@ -404,7 +404,7 @@ int ipcgpu_check_inversion(ipcgpu_ctx* c, int* ok)
         HipOptimizer& o = O(c);
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
-        *ok = o.checkInversion() ? 1 : 0;
+        *ok = o.checkInversion(M(c).energyType == 2) ? 1 : 0; // SNH: the plain mesh query (FCR keeps answering 1, as before)
         return IPCGPU_OK;
     });
 }

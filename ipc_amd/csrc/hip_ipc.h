@@ -54,7 +54,9 @@ public:
     void setCodimNodes(int n, const int* ids, const double* nodeMass, hipStream_t s);
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
-    int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated
+    int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
+    // Energy::getNeedElemInvSafeGuard(): only NH has a barrier at J = 0; the step filter and the inversion checks of the stepper serve it alone
+    bool needElemInvSafeGuard() const { return energyType == 0; }
     double density = 0; // global density handed to computeFeatures (component overrides rescale the nodal mass by rho / density)
     void setComponentMaterial(int nodeBegin, int nodeEnd, int tetBegin, int tetEnd, double rho, double YM, double PR, hipStream_t s);
     bool isDBCVertex(int v) const { return dbcType[v] != 0; }
@@ -205,7 +207,7 @@ public:
     void stepFeasible(double& stepSize);
     double filterStepSize(const double* p_dev, double stepSize);
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
-    bool checkInversion();
+    bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
 
     HipMesh& mesh;

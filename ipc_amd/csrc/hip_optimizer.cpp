@@ -1056,9 +1056,10 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
     if (!projectDBC && rhoDBC && !tpIds.empty()) launch_mdbc_hessian(mdbc(), lin.d_ia.p, rhoDBC, lin.d_a.p, stream); // :3711-3713
 }
 
-bool HipOptimizer::checkInversion()
+bool HipOptimizer::checkInversion(bool meshQuery)
 {
-    if (mesh.energyType == 1) return true; // Optimizer.cpp:252,517,545,2710: only under getNeedElemInvSafeGuard()
+    // Optimizer.cpp:252,517,545,2710: only under getNeedElemInvSafeGuard().  meshQuery: the caller asks about the mesh, not on behalf of the material
+    if (!mesh.needElemInvSafeGuard() && !meshQuery) return true;
     d_flag.zero(stream);
     launch_check_inversion(view(), d_flag.p, stream);
     launch_publish(d_flag.p, h_flag.dev, 1, stream);
@@ -1088,7 +1089,7 @@ double HipOptimizer::fullCcd(double slackness, double stepSize)
 double HipOptimizer::filterStepSize(const double* p_dev, double stepSize)
 {
     // Energy.cpp:565-581: min over elements of the root, applied only when 0 < min < stepSize
-    if (mesh.energyType == 1) return stepSize; // :567 needElemInvSafeGuard
+    if (!mesh.needElemInvSafeGuard()) return stepSize; // :567 needElemInvSafeGuard
     launch_fill(d_scalar.p + 2, 1, 1e20, stream);
     launch_inversion_step(view(), p_dev, 0.2, stepSize, d_scalar.p + 2, stream);
     reduceMin(d_scalar.p + 2, 1);
@@ -1158,10 +1159,10 @@ void HipOptimizer::computeSearchDir()
             // ten launches (fifteen before round 4: the resets, the copy + step-size + step and the two read-backs are one launch each now)
             launch_iter_reset(d_scalar.p, d_flag.p, stream); // (zeroes the slot of |p|_inf with the others: no enqueueDirNorm(), whose fill would be one launch more)
             launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
-            if (mesh.energyType != 1) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
+            if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
             launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
-            launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, mesh.energyType != 1, d_scalar.p + 6, stream);
-            if (mesh.energyType != 1) launch_check_inversion(view(), d_flag.p, stream);
+            launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, mesh.needElemInvSafeGuard(), d_scalar.p + 6, stream);
+            if (mesh.needElemInvSafeGuard()) launch_check_inversion(view(), d_flag.p, stream);
             launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p + 1, stream);
             launch_publish2(d_flag.p, h_flag.dev, 1, d_scalar.p, h_scalar.dev, 14, stream); // the inversion flag + 7 doubles
             // the ONE synchronisation waits for the read-back, not for the stream: behind it runs the next pass's assembly at the trial point, enqueued ahead
@@ -1176,7 +1177,7 @@ void HipOptimizer::computeSearchDir()
                 cachedFilter = h_scalar.p[2];
                 cachedDist = h_scalar.p[3];
                 cachedAlpha = h_scalar.p[6];
-                cachedTrialInverted = mesh.energyType != 1 && h_flag.p[0] != 0;
+                cachedTrialInverted = mesh.needElemInvSafeGuard() && h_flag.p[0] != 0;
                 cachedDistValid = cachedE0Valid = cachedTrialValid = true;
                 return;
             }
@@ -1219,7 +1220,7 @@ void HipOptimizer::computeSearchDir()
         // (line search entry, :2681)
         enqueueDirNorm();
         launch_fill(d_scalar.p + 2, 1, 1e20, stream);
-        if (mesh.energyType != 1) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
+        if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
         launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
         launch_publish(d_scalar.p, h_scalar.dev, 8, stream); // 4 doubles = 8 words
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -1300,7 +1301,7 @@ void HipOptimizer::lineSearch(double& stepSize)
             HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, bytes, hipMemcpyDeviceToDevice, stream));
             stepForward(d_x0.p, stepSize);
             int inverted = 0;
-            if (mesh.energyType != 1) {
+            if (mesh.needElemInvSafeGuard()) {
                 d_flag.zero(stream);
                 launch_check_inversion(view(), d_flag.p, stream);
                 launch_publish(d_flag.p, h_flag.dev, 1, stream);
@@ -1308,7 +1309,7 @@ void HipOptimizer::lineSearch(double& stepSize)
             launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
             launch_publish(d_scalar.p, h_scalar.dev, 2, stream);
             HIP_CHECK(hipStreamSynchronize(stream));
-            if (mesh.energyType != 1) inverted = h_flag.p[0];
+            if (mesh.needElemInvSafeGuard()) inverted = h_flag.p[0];
             testingE = h_scalar.p[0];
             done = !inverted && !(testingE > lastEnergyVal);
         }
@@ -1404,7 +1405,7 @@ void HipOptimizer::beginTimestep()
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.
     const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && !(warmStart >= 1 && warmStart <= 5);
     if (batched) {
-        const bool guard = mesh.energyType != 1; // Optimizer.cpp:252, 517: only under getNeedElemInvSafeGuard()
+        const bool guard = mesh.needElemInvSafeGuard(); // Optimizer.cpp:252, 517: only under getNeedElemInvSafeGuard()
         d_flag.zero(stream);
         if (guard) launch_check_inversion(view(), d_flag.p, stream);
         d_searchDir.zero(stream);
@@ -1646,7 +1647,7 @@ bool HipOptimizer::newtonIter()
         const bool batchedBounds = !cachedTrialValid && !cachedE0Valid && selfCollision && planes.empty() && worldSize == 1;
         if (cachedTrialValid) alpha = cachedAlpha; // decided on the device by the same rule, the trial step is already taken with it
         else if (cachedE0Valid) { // Optimizer.cpp:1887 with the value the solve's batch brought back
-            if (mesh.energyType != 1 && cachedFilter > 0.0 && cachedFilter < alpha) alpha = cachedFilter;
+            if (mesh.needElemInvSafeGuard() && cachedFilter > 0.0 && cachedFilter < alpha) alpha = cachedFilter;
         }
         else if (!batchedBounds)
         alpha = filterStepSize(d_searchDir.p, alpha); // Optimizer.cpp:1887
@@ -1659,7 +1660,7 @@ bool HipOptimizer::newtonIter()
             double pMax;
             if (batchedBounds) {
                 // inversion filter, partial CCD and surface speed in one batch: the filter's root stays on the device and bounds the CCD there
-                const bool filter = mesh.energyType != 1; // Energy.cpp:567 needElemInvSafeGuard
+                const bool filter = mesh.needElemInvSafeGuard(); // Energy.cpp:567 needElemInvSafeGuard
                 if (filter) {
                     launch_fill(d_scalar.p + 2, 1, 1e20, stream);
                     launch_inversion_step(view(), d_searchDir.p, 0.2, alpha, d_scalar.p + 2, stream);

@@ -447,6 +447,144 @@ __device__ __forceinline__ void element_generators(const ElemView& v, int t, dou
     forces();
 }
 
+// Stable neo-Hookean (Smith, de Goes, Kim 2018, 3-D), energy type 2: no SVD and no logarithm of J in the energy and the stress.
+// The element's Lame parameters keep their meaning; the paper's reparametrisation (section 3.4) is applied here, where they are loaded:
+//   mu = 4/3 mu_L   lam = lam_L + 5/6 mu_L   alpha = 1 + 3 mu / (4 lam)
+//   psi = mu/2 (I_C - 3) + lam/2 (J - alpha)^2 - mu/2 log(I_C + 1) - psi0,   psi0 = 9 mu^2 / (32 lam) - mu/2 log 4   (psi(I) = 0)
+struct SnhParams {
+    double mu, lam, alpha;
+};
+__device__ __forceinline__ SnhParams snh_params(double muL, double lamL)
+{
+    SnhParams q;
+    q.mu = 4.0 / 3.0 * muL;
+    q.lam = lamL + 5.0 / 6.0 * muL;
+    q.alpha = 1.0 + 0.75 * q.mu / q.lam;
+    return q;
+}
+__device__ __forceinline__ double snh_psi(const double F[9], double muL, double lamL)
+{
+    if (muL == 0.0 && lamL == 0.0) return 0.0;
+    const SnhParams q = snh_params(muL, lamL);
+    double IC = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) IC += F[i] * F[i];
+    const double d = det3(F) - q.alpha;
+    const double psi0 = 9.0 * q.mu * q.mu / (32.0 * q.lam) - q.mu / 2.0 * 1.3862943611198906; // log 4
+    return q.mu / 2.0 * (IC - 3.0) + q.lam / 2.0 * d * d - q.mu / 2.0 * log(IC + 1.0) - psi0;
+}
+// P w = w (mu c F + k cof F),  c = I_C / (I_C + 1),  k = lam (J - alpha); returns c and k for the sigma-space derivatives
+__device__ __forceinline__ void snh_piola(const double F[9], const SnhParams& q, double w, double P[9], double& c, double& k)
+{
+    double C[9]; // cofactor, column-major (as in piola)
+    C[0] = F[4] * F[8] - F[7] * F[5];
+    C[3] = F[7] * F[2] - F[1] * F[8];
+    C[6] = F[1] * F[5] - F[4] * F[2];
+    C[1] = F[6] * F[5] - F[3] * F[8];
+    C[4] = F[0] * F[8] - F[6] * F[2];
+    C[7] = F[3] * F[2] - F[0] * F[5];
+    C[2] = F[3] * F[7] - F[6] * F[4];
+    C[5] = F[6] * F[1] - F[0] * F[7];
+    C[8] = F[0] * F[4] - F[3] * F[1];
+    const double J = F[0] * C[0] + F[3] * C[3] + F[6] * C[6];
+    double IC = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) IC += F[i] * F[i];
+    c = IC / (IC + 1.0);
+    k = q.lam * (J - q.alpha);
+    const double mc = q.mu * c;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) P[i] = w * (mc * F[i] + k * C[i]);
+}
+
+// element_generators for the stable neo-Hookean energy: the same 33 doubles.  Sigma space, n_i the product of the other two singular values, m the
+// third index of a pair (i, j):
+//   A_ii = mu c + 2 mu s_i^2 / (I_C + 1)^2 + lam n_i^2        A_ij = 2 mu s_i s_j / (I_C + 1)^2 + lam n_i n_j + k s_m
+//   B_ij = [[mu c, -k s_m], [-k s_m, mu c]]: both divided differences of Energy.cpp:467-491 reduce exactly, (dE_i -+ dE_j) / (s_i -+ s_j) = mu c -+ k s_m,
+//   so the block has the eigenpairs (mu c - k s_m, (1, 1)), (mu c + k s_m, (1, -1)) and its PSD projection is the two clamped eigenvalues recombined:
+//   no division, no clamp of s_i + s_j, no makePD2d.  A goes through make_pd3.  A gradient-only evaluation does no SVD.
+template <class GradFn>
+__device__ __forceinline__ void snh_generators(const ElemView& v, int t, double coef, int projectDBC, bool wantGrad, bool wantHess, GradFn&& gradFn,
+    ElemGen& g)
+{
+    const int4 tv = v.tet[t];
+    g.vid[0] = tv.x; g.vid[1] = tv.y; g.vid[2] = tv.z; g.vid[3] = tv.w;
+    const d3 x0 = ld3(v.x, tv.x), x1 = ld3(v.x, tv.y), x2 = ld3(v.x, tv.z), x3 = ld3(v.x, tv.w);
+    double A[9], F[9];
+    load_A(v, t, A);
+    deformation_gradient(x0, x1, x2, x3, A, F);
+    const double muL = v.mu[t], lamL = v.lam[t];
+    const double w = coef * v.vol[t];
+    double b[4][3];
+    shape_grads(A, b);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g.dtype[k] = v.dbc[g.vid[k]];
+    const bool stiff = !(muL == 0.0 && lamL == 0.0);
+    g.active = wantHess && stiff;
+    auto emitForces = [&](const double P[9]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (projectDBC && g.dtype[k] != 0) continue; // Energy.cpp:284-288
+#pragma unroll
+            for (int i = 0; i < 3; ++i) gradFn(k, i, P[i] * b[k][0] + P[i + 3] * b[k][1] + P[i + 6] * b[k][2]);
+        }
+    };
+    double P[9];
+    if (!stiff) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) P[i] = 0.0;
+        if (wantGrad) emitForces(P);
+        return;
+    }
+    const SnhParams q = snh_params(muL, lamL);
+    double c, k;
+    snh_piola(F, q, w, P, c, k);
+    if (!g.active) {
+        if (wantGrad) emitForces(P);
+        return;
+    }
+    double s[3], V[9];
+    svd3(F, g.U, s, V);
+    const double IC1 = s[0] * s[0] + s[1] * s[1] + s[2] * s[2] + 1.0;
+    const double h = 2.0 * q.mu / (IC1 * IC1), mc = q.mu * c;
+    const double n[3] = { s[1] * s[2], s[2] * s[0], s[0] * s[1] };
+    double A3[6];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) A3[i] = mc + h * s[i] * s[i] + q.lam * n[i] * n[i];
+    A3[3] = h * s[0] * s[1] + q.lam * n[0] * n[1] + k * s[2];
+    A3[4] = h * s[1] * s[2] + q.lam * n[1] * n[2] + k * s[0];
+    A3[5] = h * s[2] * s[0] + q.lam * n[2] * n[0] + k * s[1];
+    make_pd3(A3);
+    double B00[3], B01[3]; // pair kk -> (i, j) = (kk, (kk+1)%3), m = (kk+2)%3
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) {
+        const double ks = k * s[(kk + 2) % 3];
+        const double l1 = fmax(mc - ks, 0.0), l2 = fmax(mc + ks, 0.0);
+        B00[kk] = 0.5 * (l1 + l2);
+        B01[kk] = 0.5 * (l1 - l2);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) g.Ad[i] = w * A3[i];
+    g.Bd[0] = w * B00[0]; g.Bd[1] = w * B00[0]; g.Bo[0] = w * B01[0];
+    g.Bd[2] = w * B00[1]; g.Bd[3] = w * B00[1]; g.Bo[1] = w * B01[1];
+    g.Bd[4] = w * B00[2]; g.Bd[5] = w * B00[2]; g.Bo[2] = w * B01[2];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int qq = 0; qq < 3; ++qq) g.beta[kk][qq] = V[3 * qq] * b[kk][0] + V[3 * qq + 1] * b[kk][1] + V[3 * qq + 2] * b[kk][2];
+    if (wantGrad) emitForces(P); // last, like element_generators
+}
+
+// the generators of the energy chosen at compile time: the kernels that call this are instantiated per energy and dispatched on the host, so the
+// NH / FCR instantiations carry no stable-neo-Hookean code (and no registers for it)
+template <bool SNH, class GradFn>
+__device__ __forceinline__ void generators(const ElemView& v, int t, double coef, int projectDBC, bool wantGrad, bool wantHess, GradFn&& gradFn,
+    ElemGen& g)
+{
+    if constexpr (SNH) snh_generators(v, t, coef, projectDBC, wantGrad, wantHess, gradFn, g);
+    else element_generators(v, t, coef, projectDBC, wantGrad, wantHess, gradFn, g);
+}
+
 // H = U T U^T for the node pair with sigma-space shape vectors ba, bc
 __device__ __forceinline__ void pair_block(const double U[9], const double ba[3], const double bc[3], const double Ad[6], const double Bd[6],
     const double Bo[3], double H[3][3])
@@ -478,11 +616,11 @@ __device__ __forceinline__ void pair_block(const double U[9], const double ba[3]
 //   sink.wantPair(ka, kc, e)                does anybody consume block (ka, kc)?  e = local edge id (-1: diagonal)
 //   sink.diagBlock(ka, H)                   3x3 symmetric block of node ka (upper triangle is used)
 //   sink.offBlock(e, ka, kc, aFirst, H)     3x3 block rows ka / cols kc; aFirst <=> global id(ka) < global id(kc)
-template <bool HESS, class Sink>
+template <bool HESS, bool SNH, class Sink>
 __device__ __forceinline__ void assemble_element(const ElemView& v, int t, double coef, int projectDBC, bool wantGrad, Sink& sink)
 {
     ElemGen g;
-    element_generators(v, t, coef, projectDBC, wantGrad, HESS, [&](int k, int i, double val) { sink.grad(k, i, val); }, g);
+    generators<SNH>(v, t, coef, projectDBC, wantGrad, HESS, [&](int k, int i, double val) { sink.grad(k, i, val); }, g);
     if (!HESS || !g.active) return;
     bool proj[4];
 #pragma unroll

@@ -61,7 +61,7 @@ struct GlobalAtomicSink {
     }
 };
 
-template <bool HESS>
+template <bool HESS, bool SNH>
 __global__ __launch_bounds__(BLOCK) void k_assemble(ElemView v, double coef, int projectDBC, double* __restrict__ grad,
     double* __restrict__ a)
 {
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(BLOCK) void k_assemble(ElemView v, double coef, int
     if (t >= v.tetEnd) return;
     const int4 tv = v.tet[t];
     GlobalAtomicSink sink{ v, t, { tv.x, tv.y, tv.z, tv.w }, grad, a };
-    assemble_element<HESS>(v, t, coef, projectDBC, grad != nullptr, sink);
+    assemble_element<HESS, SNH>(v, t, coef, projectDBC, grad != nullptr, sink);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_node_init(ElemView v, int projectDBC, int owner, double* __restrict__ a,
@@ -124,9 +124,11 @@ __device__ __forceinline__ double nh_psi(const double F[9], double mu, double la
     return mu / 2.0 * (I1 - 3.0) - (mu - lam / 2.0 * lJ) * lJ; // NeoHookeanEnergy.cpp:64-68 with sum sigma^2 = |F|^2, prod sigma = det F
 }
 
-// strain energy density of the configured material
+// strain energy density of the configured material; SNH (energy type 2) is chosen at compile time and dispatched on the host
+template <bool SNH>
 __device__ __forceinline__ double elem_psi(const ElemView& v, const double F[9], double mu, double lam)
 {
+    if constexpr (SNH) return snh_psi(F, mu, lam);
     if (v.energyType != 1) return nh_psi(F, mu, lam);
     if (mu == 0.0 && lam == 0.0) return 0.0;
     double U[9], s[3], V[9];
@@ -134,6 +136,7 @@ __device__ __forceinline__ double elem_psi(const ElemView& v, const double F[9],
     return fcr_psi(s, mu, lam);
 }
 
+template <bool SNH>
 __global__ __launch_bounds__(BLOCK) void k_energy(ElemView v, double coef, int withInertia, int owner, double* __restrict__ partial)
 {
     __shared__ double sm[BLOCK / 64];
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(BLOCK) void k_energy(ElemView v, double coef, int w
         double A[9], F[9];
         load_A(v, t, A);
         deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
-        e = coef * v.vol[t] * elem_psi(v, F, v.mu[t], v.lam[t]);
+        e = coef * v.vol[t] * elem_psi<SNH>(v, F, v.mu[t], v.lam[t]);
     }
     if (withInertia && owner && gid < v.nV) {
         double d2 = 0.0;
@@ -169,6 +172,7 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double* __restr
     if (threadIdx.x == 0) out[0] = r;
 }
 
+template <bool SNH>
 __global__ __launch_bounds__(BLOCK) void k_energy_per_elem(ElemView v, double* __restrict__ out)
 {
     const int t = blockIdx.x * BLOCK + threadIdx.x;
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(BLOCK) void k_energy_per_elem(ElemView v, double* _
     double A[9], F[9];
     load_A(v, t, A);
     deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
-    out[t] = v.vol[t] * elem_psi(v, F, v.mu[t], v.lam[t]);
+    out[t] = v.vol[t] * elem_psi<SNH>(v, F, v.mu[t], v.lam[t]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -186,10 +190,11 @@ __global__ __launch_bounds__(BLOCK) void k_energy_per_elem(ElemView v, double* _
 //   pass 1  one lane per element: F as the energy kernels form it, the Cauchy stress sigma = P F^T / J of the configured energy in the closed forms
 //             NH   sigma = (mu (F F^T - I) + lam ln J I) / J                       (P = mu (F - F^-T) + lam ln J F^-T, F^-T F^T = I)
 //             FCR  sigma = 2 mu (F - R) F^T / J + lam (J - 1) I,  R = U V^T        (P = 2 mu (F - R) + lam (J - 1) cof F, cof F F^T = J I)
+//             SNH  sigma = mu c F F^T / J + k I,  c = I_C / (I_C + 1), k = lam (J - alpha)  (P = mu c F + k cof F, the reparametrised mu, lam of nh_device.h)
 //           which never form F^-T or cof F.  (F - R) F^T is symmetric up to round-off only: the mean of the two off-diagonal entries is stored.
 //           An element without stiffness (mu = lam = 0, the convention of piola) gets zeros and its J; an NH element with J <= 0 has no logarithm:
 //           NaN in all eight slots, and it is counted.  FCR is finite for every F with J != 0, inverted ones included (at J = 0 exactly the division by J
-//           gives inf / NaN like any other evaluation of P F^T / J; such an element is not counted).
+//           gives inf / NaN like any other evaluation of P F^T / J; such an element is not counted).  SNH likewise: finite for J < 0, inf / NaN uncounted at J = 0.
 //   pass 2  one lane per node: the rest-volume-weighted mean of the records of its elements, walked in ascending element index (stress_plan.h), the
 //           von Mises stress OF THAT MEAN, and the volume sum.  A NaN record makes the stress entries of its four nodes NaN; a node without an element gets zeros.
 // No atomics on any floating-point value and a fixed order everywhere: the same state gives the same bits.
@@ -202,7 +207,7 @@ __device__ __forceinline__ double von_mises(double sxx, double syy, double szz, 
     return sqrt(0.5 * (a * a + b * b + c * c) + 3.0 * (sxy * sxy + syz * syz + sxz * sxz));
 }
 
-template <bool FCR>
+template <int ET> // the energy type: 0 NH, 1 FCR, 2 SNH
 __global__ __launch_bounds__(BLOCK) void k_stress_elements(ElemView v, double* __restrict__ out, int* __restrict__ nInvalid)
 {
     const int t = blockIdx.x * BLOCK + threadIdx.x;
@@ -212,11 +217,12 @@ __global__ __launch_bounds__(BLOCK) void k_stress_elements(ElemView v, double* _
         double A[9], F[9];
         load_A(v, t, A);
         deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
-        const double mu = v.mu[t], lam = v.lam[t];
+        constexpr bool FCR = ET == 1, SNH = ET == 2;
+        double mu = v.mu[t], lam = v.lam[t];
         const double J = det3(F);
         double s[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, vm = 0.0, Jout = J; // {xx, yy, zz, xy, yz, xz}
         if (!(mu == 0.0 && lam == 0.0)) {
-            if (!FCR && !(J > 0.0)) {
+            if (ET == 0 && !(J > 0.0)) {
                 invalid = true;
                 const double nan = __longlong_as_double(0x7ff8000000000000LL);
 #pragma unroll
@@ -235,6 +241,18 @@ __global__ __launch_bounds__(BLOCK) void k_stress_elements(ElemView v, double* _
                         for (int i = 0; i < 3; ++i) G[i + 3 * j] = 2.0 * (F[i + 3 * j] - (U[i] * V[j] + U[i + 3] * V[j + 3] + U[i + 6] * V[j + 6]));
                     isoJ = 0.0;
                     iso = lam * (J - 1.0); // lam (J - 1) J / J
+                }
+                else if (SNH) {
+                    const SnhParams q = snh_params(mu, lam);
+                    double IC = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) {
+                        G[i] = F[i];
+                        IC += F[i] * F[i];
+                    }
+                    mu = q.mu * (IC / (IC + 1.0)); // mu c: the factor of F F^T below
+                    isoJ = 0.0;
+                    iso = q.lam * (J - q.alpha);
                 }
                 else {
 #pragma unroll
@@ -301,6 +319,7 @@ __device__ __forceinline__ double wave_sum(double x)
     return x;
 }
 
+template <bool SNH>
 __global__ __launch_bounds__(BLOCK) void k_report_slices(ElemView v, const double* __restrict__ xStart, const int* __restrict__ slices, int nNodeSlices,
     double dt, double gx, double gy, double gz, double* __restrict__ rec)
 {
@@ -328,7 +347,7 @@ __global__ __launch_bounds__(BLOCK) void k_report_slices(ElemView v, const doubl
         double A[9], F[9];
         load_A(v, i, A);
         deformation_gradient(ld3(v.x, tv.x), ld3(v.x, tv.y), ld3(v.x, tv.z), ld3(v.x, tv.w), A, F);
-        q[0] = v.vol[i] * elem_psi(v, F, v.mu[i], v.lam[i]); // the value of k_energy_per_elem (:3751, 3762)
+        q[0] = v.vol[i] * elem_psi<SNH>(v, F, v.mu[i], v.lam[i]); // the value of k_energy_per_elem (:3751, 3762)
     }
 #pragma unroll
     for (int k = 0; k < REPORT_Q; ++k)
@@ -880,8 +899,11 @@ void launch_assemble(const ElemView& v, double coef, int projectDBC, double* gra
 {
     const int n = v.tetEnd - v.tetBegin;
     if (n <= 0) return;
-    if (a) hipLaunchKernelGGL(k_assemble<true>, dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
-    else hipLaunchKernelGGL(k_assemble<false>, dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    const bool snh = v.energyType == 2;
+    if (a && snh) hipLaunchKernelGGL((k_assemble<true, true>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else if (a) hipLaunchKernelGGL((k_assemble<true, false>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else if (snh) hipLaunchKernelGGL((k_assemble<false, true>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else hipLaunchKernelGGL((k_assemble<false, false>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
 }
 const char* assemble_kernel_name() { return "k_assemble"; }
 
@@ -891,18 +913,22 @@ void launch_energy(const ElemView& v, double coef, bool withInertia, bool ownerR
     const int n = std::max(v.tetEnd - v.tetBegin, withInertia ? v.nV : 0);
     const int nb = std::max(1, nblk(n));
     (void)partialCap;
-    hipLaunchKernelGGL(k_energy, dim3(nb), dim3(BLOCK), 0, s, v, coef, withInertia ? 1 : 0, ownerRank ? 1 : 0, partial);
+    if (v.energyType == 2) hipLaunchKernelGGL(k_energy<true>, dim3(nb), dim3(BLOCK), 0, s, v, coef, withInertia ? 1 : 0, ownerRank ? 1 : 0, partial);
+    else hipLaunchKernelGGL(k_energy<false>, dim3(nb), dim3(BLOCK), 0, s, v, coef, withInertia ? 1 : 0, ownerRank ? 1 : 0, partial);
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0, s, partial, nb, out);
 }
 void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s)
 {
-    if (v.nT) hipLaunchKernelGGL(k_energy_per_elem, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
+    if (!v.nT) return;
+    if (v.energyType == 2) hipLaunchKernelGGL(k_energy_per_elem<true>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
+    else hipLaunchKernelGGL(k_energy_per_elem<false>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
 }
 void launch_stress_elements(const ElemView& v, double* rec, int* nInvalid, hipStream_t s)
 {
     if (!v.nT) return;
-    if (v.energyType == 1) hipLaunchKernelGGL(k_stress_elements<true>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
-    else hipLaunchKernelGGL(k_stress_elements<false>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    if (v.energyType == 2) hipLaunchKernelGGL(k_stress_elements<2>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    else if (v.energyType == 1) hipLaunchKernelGGL(k_stress_elements<1>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    else hipLaunchKernelGGL(k_stress_elements<0>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
 }
 void launch_stress_nodes(int nV, int nT, const int* ptr, const int* elems, const double* vol, const double* rec, double* out, hipStream_t s)
 {
@@ -911,8 +937,10 @@ void launch_stress_nodes(int nV, int nT, const int* ptr, const int* elems, const
 void launch_system_report(const ElemView& v, const double* xStart, const int* slices, int nNodeSlices, int nSlices, const int* nodeStart,
     const int* tetStart, int nComp, double dt, const double* g3, double* rec, double* out, hipStream_t s)
 {
-    if (nSlices)
-        hipLaunchKernelGGL(k_report_slices, dim3(nSlices), dim3(BLOCK), 0, s, v, xStart, slices, nNodeSlices, dt, g3[0], g3[1], g3[2], rec);
+    if (nSlices && v.energyType == 2)
+        hipLaunchKernelGGL(k_report_slices<true>, dim3(nSlices), dim3(BLOCK), 0, s, v, xStart, slices, nNodeSlices, dt, g3[0], g3[1], g3[2], rec);
+    else if (nSlices)
+        hipLaunchKernelGGL(k_report_slices<false>, dim3(nSlices), dim3(BLOCK), 0, s, v, xStart, slices, nNodeSlices, dt, g3[0], g3[1], g3[2], rec);
     hipLaunchKernelGGL(k_report_components, dim3(nComp), dim3(64), 0, s, rec, nodeStart, tetStart, out);
 }
 void launch_check_inversion(const ElemView& v, int* flag, hipStream_t s)

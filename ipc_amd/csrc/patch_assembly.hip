@@ -34,7 +34,7 @@ __device__ __forceinline__ double row_shl(double x)
 #else
 #define ASM_OCC
 #endif
-template <bool HESS, int BLOCK>
+template <bool HESS, int BLOCK, bool SNH> // SNH: the stable neo-Hookean generators (energy type 2), dispatched on the host
 __global__ __launch_bounds__(BLOCK) ASM_OCC void k_assemble_patch(ElemView v, PatchView pv, int patchBegin, int tcap, int ncap, double coef,
     int projectDBC, double* __restrict__ grad, double* __restrict__ a, int probe, const int* __restrict__ patchList)
 {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) ASM_OCC void k_assemble_patch(ElemView v, Pa
 #pragma unroll
         for (int k = 0; k < 4; ++k) gs[k] = grad ? pv.gradSlot[(size_t)k * pv.totalTets + inst] : (uint16_t)0xFFFF;
         ElemGen g;
-        element_generators(v, pv.tets[inst], coef, projectDBC, grad != nullptr, HESS, [&](int k, int i, double val) { fb[3 * k + i] = val; }, g);
+        generators<SNH>(v, pv.tets[inst], coef, projectDBC, grad != nullptr, HESS, [&](int k, int i, double val) { fb[3 * k + i] = val; }, g);
         if (HESS) {
             int mask = g.active ? 16 : 0;
 #pragma unroll
@@ -492,23 +492,25 @@ size_t PatchPlan::ldsBytes() const
     return sizeof(double) * (NF * tcap + 3 * (size_t)maxNodes);
 }
 
-void launch_assemble_patches(const ElemView& v, const PatchPlan& plan, int patchBegin, int patchEnd, double coef, int projectDBC,
-    double* grad, double* a, hipStream_t s, const int* patchList)
+namespace {
+template <bool SNH>
+void launch_assemble_patches_of(const ElemView& v, const PatchPlan& plan, int patchBegin, int patchEnd, double coef, int projectDBC, double* grad,
+    double* a, hipStream_t s, const int* patchList)
 {
     const int n = patchEnd - patchBegin; // with a list: its length (patchBegin = 0)
     if (n <= 0) return;
     const size_t lds = plan.ldsBytes();
     const int tcap = (plan.maxTets + 63) / 64 * 64;
     const bool wide = plan.maxTets > 256; // patches of up to 512 elements: 512-thread workgroups
-    static size_t attrSet[2] = { 0, 0 };
+    static size_t attrSet[2] = { 0, 0 }; // (one pair per energy instantiation)
     if (lds > 64 * 1024 && lds > attrSet[wide]) {
         if (wide) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<true, 512, SNH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<false, 512, SNH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
         else {
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<true, 256, SNH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_assemble_patch<false, 256, SNH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
         attrSet[wide] = lds;
     }
@@ -516,16 +518,24 @@ void launch_assemble_patches(const ElemView& v, const PatchPlan& plan, int patch
     const int probe = 0;
     if (wide) {
         if (a)
-            hipLaunchKernelGGL((k_assemble_patch<true, 512>), dim3(n), dim3(512), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
+            hipLaunchKernelGGL((k_assemble_patch<true, 512, SNH>), dim3(n), dim3(512), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
         else
-            hipLaunchKernelGGL((k_assemble_patch<false, 512>), dim3(n), dim3(512), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
+            hipLaunchKernelGGL((k_assemble_patch<false, 512, SNH>), dim3(n), dim3(512), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
     }
     else {
         if (a)
-            hipLaunchKernelGGL((k_assemble_patch<true, 256>), dim3(n), dim3(256), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
+            hipLaunchKernelGGL((k_assemble_patch<true, 256, SNH>), dim3(n), dim3(256), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
         else
-            hipLaunchKernelGGL((k_assemble_patch<false, 256>), dim3(n), dim3(256), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
+            hipLaunchKernelGGL((k_assemble_patch<false, 256, SNH>), dim3(n), dim3(256), lds, s, v, pv, patchBegin, tcap, plan.maxNodes, coef, projectDBC, grad, a, probe, patchList);
     }
+}
+} // namespace
+
+void launch_assemble_patches(const ElemView& v, const PatchPlan& plan, int patchBegin, int patchEnd, double coef, int projectDBC,
+    double* grad, double* a, hipStream_t s, const int* patchList)
+{
+    if (v.energyType == 2) launch_assemble_patches_of<true>(v, plan, patchBegin, patchEnd, coef, projectDBC, grad, a, s, patchList);
+    else launch_assemble_patches_of<false>(v, plan, patchBegin, patchEnd, coef, projectDBC, grad, a, s, patchList);
 }
 
 } // namespace ipcgpu

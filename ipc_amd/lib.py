@@ -321,8 +321,8 @@ class Context:
         return E, M, L
 
     def set_energy_type(self, name):
-        """Scene-script `energy NH|FCR`."""
-        self._chk(self._L.ipcgpu_set_energy_type(self.h, C.c_int({"NH": 0, "FCR": 1}[name])))
+        """Scene-script `energy NH|FCR|SNH` (SNH: stable neo-Hookean, energy type 2 of the C ABI)."""
+        self._chk(self._L.ipcgpu_set_energy_type(self.h, C.c_int({"NH": 0, "FCR": 1, "SNH": 2}[name])))
 
     def clear_dbc(self):
         self._chk(self._L.ipcgpu_clear_dbc(self.h))

@@ -109,7 +109,7 @@ class SceneConfig:
                 continue
             k, a = tok[0], tok[1:]
             if k == "energy":
-                if a[0] not in ("NH", "FCR"):
+                if a[0] not in ("NH", "FCR", "SNH"):  # SNH: stable neo-Hookean, this project's third energy (not a keyword of the reference)
                     raise UnsupportedKeyword(f"energy {a[0]}")
                 cfg.energy = a[0]
             elif k == "timeIntegration":

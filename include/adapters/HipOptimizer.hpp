@@ -316,6 +316,14 @@ protected:
             }
     }
 
+    // Contact groups (ipcgpu_set_contact_groups; no counterpart in the reference): one group per component handed to the device -- those of Mesh<3> in
+    // script order, then the mesh collision objects as one more --, a symmetric 0 / 1 matrix over the groups and friction ratios (empty: all 1).
+    // Resident mode, after the mesh is on the device; the largest coefficient goes to Config::selfFric.
+    void setContactGroups(const std::vector<int>& group, int nGroups, const std::vector<unsigned char>& collide, const std::vector<double>& fricScale = {})
+    {
+        chk(ipcgpu_set_contact_groups(Parts::ctx, (int)group.size(), group.data(), nGroups, collide.data(), fricScale.empty() ? nullptr : fricScale.data()));
+    }
+
     // the three files of the reference's precompute() and fullyImplicit[_IP](), neither of which runs in resident mode
     void writeSystemReport(bool open)
     {

@@ -296,6 +296,32 @@ int ipcgpu_get_surface(ipcgpu_ctx*, int* counts3 /*nSVI,nSF,nSFEdges*/, int* SVI
    (a scene with `meshCO` but `selfCollisionOff`: Optimizer.cpp:2448-2470 asks only the collision objects).  Bounding box and
    mean nodal mass (dHat, kappa) are taken over element nodes, so the obstacle does not change them.  Call after set_surface. */
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx*, int n, const int* vert_ids, int obstacle_only);
+/* Contact groups: which bodies collide at all, and a friction factor per pair of groups (a project extension; the reference has neither).
+ * Every component of ipcgpu_opt_set_components (default: one, the whole mesh) gets a group g in [0, nGroups), nGroups <= 16.
+ *   collide[g * nGroups + h]    symmetric, 0 / 1: do primitives of groups g and h form contact pairs?
+ *   fricScale[g * nGroups + h]  symmetric, finite, >= 0 (null: all 1): factor on the lagged normal force of a friction stencil between g and h
+ * The group of a surface primitive (vertex, edge, triangle) is the group of its FIRST node -- the convention of the contact report; a primitive never
+ * spans components.  A primitive pair with collide == 0 does not exist for contact: it is absent from the active set, the mollified set (paraEEMMCVIDSet
+ * and paraEEeIeJSet) and the CCD candidate list that ipcgpu_contact_build and the time stepper form, it is not swept by ipcgpu_ccd_full,
+ * ipcgpu_ccd_full_reference (vertex-vertex, vertex-edge, vertex-triangle and edge-edge pairs) or -- through the candidate list -- ipcgpu_ccd_partial, and
+ * it is not tested by ipcgpu_is_intersected (edge against triangle; a codimensional point against a tetrahedron by the group of the tetrahedron's
+ * first node).  collide[g][g] == 0 also removes the pairs INSIDE every component of group g.  The filter adds to the existing ones (incident
+ * primitives, all-Dirichlet pairs, obstacle_only of ipcgpu_set_obstacle_nodes).  Sets handed in with ipcgpu_contact_set / ipcgpu_halfspace_set are
+ * taken as they are: the filter applies to what the library builds.
+ * Friction: the lagged multiplier of a stencil between groups ga and gb is multiplied by fricScale[ga][gb], on top of the factors of
+ * ipcgpu_opt_set_friction_scales, so the effective coefficient is selfFric x scale: pass the LARGEST coefficient to ipcgpu_opt_set_friction and the
+ * ratios here.  A scale of 0 leaves the stencil in the lagged set with a zero multiplier (it adds exact zeros): neither the number of lagged stencils
+ * nor the matrix pattern depends on the scales.
+ * Half-spaces take no part: a plane collides with every group and keeps its own coefficient (ipcgpu_opt_set_half_space_friction).
+ * nComp must equal the number of components (else IPCGPU_ERR_ARG, as for a group outside [0, nGroups), nGroups outside [1, 16], an asymmetric matrix,
+ * a collide entry other than 0 / 1, a negative or non-finite scale).  nComp == 0 goes back to the default, which is also the state after
+ * ipcgpu_set_mesh and after ipcgpu_opt_set_components: every node in group 0, group 0 collides with itself, all scales 1.  Before ipcgpu_set_mesh:
+ * IPCGPU_ERR_STATE.  Sharded context: IPCGPU_ERR_UNSUPPORTED.
+ * ipcgpu_get_contact_groups: the number of groups and, per node, the word the contact kernels read: bits 4-7 the node's group, bits 16-31 the
+ * group's row of collide (bit 16 + h), other bits 0; 0xFFFF0000 everywhere in the default state.  Either pointer may be null. */
+int ipcgpu_set_contact_groups(ipcgpu_ctx*, int nComp, const int* group_nComp, int nGroups, const unsigned char* collide_nGroups2,
+    const double* fricScale_nGroups2 /*nullable: all 1*/);
+int ipcgpu_get_contact_groups(ipcgpu_ctx*, int* nGroups, int* nodeWord_nV /*nullable*/);
 /* Surface-only ("codimensional") components of the simulated mesh: nodes of no tetrahedron that nevertheless belong to Mesh<3> --
  * the triangle meshes listed under `shapes` (componentCoDim 2; src/main.cpp, src/Mesh.cpp:310-345).  Unlike the nodes of a MeshCO
  * (ipcgpu_set_obstacle_nodes), which the reference keeps outside the mesh, they carry lumped masses: density x a third of the areas

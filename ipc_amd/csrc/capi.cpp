@@ -944,6 +944,40 @@ int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
         return IPCGPU_OK;
     });
 }
+int ipcgpu_set_contact_groups(ipcgpu_ctx* c, int nComp, const int* group, int nGroups, const unsigned char* collide, const double* fricScale)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        if (c->worldSize > 1) throw UnsupportedError("contact groups on a sharded context (not implemented)");
+        needArg(nComp >= 0, "contact groups: negative component count");
+        const int nV = c->mesh->nV;
+        if (nComp == 0) { // back to the default: one group that collides with itself, all scales 1
+            if (c->contact) c->contact->setGroups(nV, {}, {}, 1);
+            return IPCGPU_OK;
+        }
+        std::vector<int> ends = o.compNodeEnd; // no table (or one of another mesh): the whole mesh, as the reports have it
+        if (ends.empty() || ends.back() != nV) ends.assign(1, nV);
+        std::vector<int> words;
+        std::vector<double> scale16;
+        std::string err;
+        if (!buildContactGroupWords(nV, (int)ends.size(), ends.data(), nComp, group, nGroups, collide, fricScale, words, scale16, err)) throw ArgError(err);
+        CT(c).setGroups(nV, words, scale16, nGroups);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_get_contact_groups(ipcgpu_ctx* c, int* nGroups, int* nodeWord)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        if (c->worldSize > 1) throw UnsupportedError("contact groups on a sharded context (not implemented)");
+        const bool on = c->contact && c->contact->hasGroups;
+        if (nGroups) *nGroups = on ? c->contact->nGroups : 1;
+        for (int v = 0; nodeWord && v < m.nV; ++v) nodeWord[v] = on ? c->contact->groupWord[v] : (int)CONTACT_GROUP_DEFAULT_WORD;
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_contact_get(ipcgpu_ctx* c, int* a4, int* p4, int* pe2, int* cs2)
 {
     return guarded([&] {
@@ -1670,6 +1704,11 @@ int ipcgpu_opt_set_components(ipcgpu_ctx* c, int nComp, const int* nodeEnd, cons
         HipOptimizer& o = O(c);
         needArg(nComp >= 1 && nodeEnd && tetEnd, "set_components: at least one component and both tables");
         o.setComponents(nComp, nodeEnd, tetEnd);
+        if (c->contact && c->contact->hasGroups) { // the contact groups belong to the previous table: back to the default
+            specChanged(c);
+            bind(c);
+            c->contact->setGroups(c->mesh->nV, {}, {}, 1);
+        }
         return IPCGPU_OK;
     });
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdlib>
 #include "common.h"
+#include "contact_groups.h"
 #include <array>
 #include <utility>
 #include <functional>
@@ -62,6 +63,14 @@ public:
     bool hasObstacle = false, obstacleOnly = false;
     DevBuf<int> d_obst, d_pairFlags;
     const int* pairFlags(int nV, const int* dbc_dev);
+    // contact groups (ipcgpu_set_contact_groups; contact_groups.h): per node the group of its component and the group's row of the collide matrix, OR-ed
+    // into the pair flags, and the 16 x 16 friction scales k_friction_lag multiplies the lagged normal forces with.  Empty words: the default (one group)
+    void setGroups(int nV, const std::vector<int>& words, const std::vector<double>& scale16, int nGroups);
+    bool hasGroups = false;
+    int nGroups = 1;
+    std::vector<int> groupWord;
+    DevBuf<int> d_groupWord;
+    DevBuf<double> d_groupScale;
     void setSets(int nA, const int* a4, int nP, const int* p4, const int* pe2);
     void uploadSets();
     // returns #active

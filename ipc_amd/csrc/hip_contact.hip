@@ -660,8 +660,8 @@ __device__ __forceinline__ void fr_normalize(double* a)
 // obst / scaleSelf / scaleObst: a kinematic mesh obstacle carries its own friction coefficient (MeshCO::friction); the caller passes the
 // larger coefficient to the friction terms and the lagged normal force of a stencil is scaled by the factor of its kind here
 __global__ __launch_bounds__(BLOCK) void k_friction_lag(int n, const int* __restrict__ set, const double* __restrict__ x, double dHat, double kappa,
-    const int* __restrict__ obst, double scaleSelf, double scaleObst, double* __restrict__ lambda, double* __restrict__ coord,
-    double* __restrict__ basis)
+    const int* __restrict__ obst, double scaleSelf, double scaleObst, const int* __restrict__ groupWord, const double* __restrict__ groupScale,
+    double* __restrict__ lambda, double* __restrict__ coord, double* __restrict__ basis)
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -677,6 +677,9 @@ __global__ __launch_bounds__(BLOCK) void k_friction_lag(int n, const int* __rest
         for (int k = 0; k < s.n; ++k) ob = ob || obst[s.node[k]] != 0;
         lam *= ob ? scaleObst : scaleSelf;
     }
+    // contact groups: the factor of the pair of groups on top (the two primitives' first nodes: the stencil's first node and its last).  A factor of 0
+    // leaves the stencil in the lagged set with lambda = 0: the set and the pattern never depend on the scales
+    if (groupWord) lam *= groupScale[16 * ((groupWord[s.node[0]] >> 4) & 15) + ((groupWord[s.node[s.n - 1]] >> 4) & 15)];
     lambda[i] = lam;
     double co[2] = { 0.0, 0.0 }, t0[3], t1[3], tmp[3];
     if (s.kind == K_EE) {
@@ -824,11 +827,19 @@ __device__ __forceinline__ int cell_of(const Grid& g, double x, int c)
 // Pair flags of a node as the broad / narrow phase kernels read them: bit 0 Dirichlet node, bit 1 node of a kinematic
 // obstacle (the reference's MeshCO riding along as a surface-only component), bit 2 "only pairs that involve an obstacle"
 // (a scene with `meshCO` and `selfCollisionOff`; set on every node so that either operand tells).
-__device__ __forceinline__ bool pair_filtered(int fa, int fb) { return (fa & 4) && !((fa | fb) & 2); }
-__global__ void k_pair_flags(int nV, const int* __restrict__ dbc, const int* __restrict__ obst, int obstacleOnly, int* __restrict__ flags)
+// Contact groups (ipcgpu_set_contact_groups, contact_groups.h) ride in the same word: bits 4-7 the group of the node's component, bits 16-31 that
+// group's row of the collide matrix (bit 16 + h: pairs with group h exist).  A primitive's group is that of its first node -- the operands every call
+// site passes; the matrix is symmetric, so the row of either operand tells.  Without a table every node is in group 0 with an all-ones row.
+__device__ __forceinline__ bool pair_filtered(int fa, int fb)
+{
+    return ((fa & 4) && !((fa | fb) & 2)) || !(((unsigned)fa >> (16 + ((fb >> 4) & 15))) & 1u);
+}
+__global__ void k_pair_flags(int nV, const int* __restrict__ dbc, const int* __restrict__ obst, int obstacleOnly, const int* __restrict__ groupWord,
+    int* __restrict__ flags)
 {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < nV) flags[v] = (dbc[v] != 0 ? 1 : 0) | ((obst && obst[v]) ? 2 : 0) | (obstacleOnly ? 4 : 0);
+    if (v < nV)
+        flags[v] = (dbc[v] != 0 ? 1 : 0) | ((obst && obst[v]) ? 2 : 0) | (obstacleOnly ? 4 : 0) | (groupWord ? groupWord[v] : (int)CONTACT_GROUP_DEFAULT_WORD);
 }
 
 // The box of a workgroup from the boxes (lo, hi) of its threads: wave shuffles, then the waves' boxes through LDS.  True in threads 0 .. 5, which receive
@@ -2000,13 +2011,16 @@ __device__ __forceinline__ bool point_behind_tri(const double* t0, const double*
 }
 template <bool exact>
 __global__ __launch_bounds__(BLOCK) void k_points_in_tets(int nPts, const int* __restrict__ pts, int nT, const int4* __restrict__ tet,
-    const double* __restrict__ x, int* __restrict__ flag)
+    const double* __restrict__ x, const int* __restrict__ pf, int* __restrict__ flag)
 {
     const long long gi = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (gi >= (long long)nPts * nT) return;
     const int v = pts[gi / nT];
     const int4 t = tet[gi % nT];
     const int id[4] = { t.x, t.y, t.z, t.w };
+    // contact groups only (the group of the point against that of the element's first node): the reference applies neither the Dirichlet nor the
+    // obstacle-only filter here, so bits 0-2 stay out of it
+    if (pair_filtered(pf[v] & ~7, pf[id[0]] & ~7)) return;
     double p[3], q[4][3];
     for (int c = 0; c < 3; ++c) {
         p[c] = x[3 * (size_t)v + c];
@@ -2308,11 +2322,28 @@ void HipContact::setObstacle(int nV, int n, const int* ids, bool only)
     obstacleOnly = only;
     HIP_CHECK(hipStreamSynchronize(stream));
 }
+// contact groups: the per-node words and the 16 x 16 table of friction scales as contact_groups.cpp made them; n == 0: back to the default
+void HipContact::setGroups(int nV, const std::vector<int>& words, const std::vector<double>& scale16, int nGroups_)
+{
+    if (words.empty()) {
+        hasGroups = false;
+        nGroups = 1;
+        groupWord.clear();
+        return;
+    }
+    if ((int)words.size() != nV || scale16.size() != 256) throw ArgError("set_contact_groups: tables of the wrong size");
+    groupWord = words;
+    d_groupWord.upload(words, stream);
+    d_groupScale.upload(scale16, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    hasGroups = true;
+    nGroups = nGroups_;
+}
 const int* HipContact::pairFlags(int nV, const int* dbc_dev)
 {
     d_pairFlags.ensure((size_t)std::max(nV, 1));
     hipLaunchKernelGGL(k_pair_flags, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dbc_dev, hasObstacle ? d_obst.p : (const int*)nullptr, obstacleOnly ? 1 : 0,
-        d_pairFlags.p);
+        hasGroups ? (const int*)d_groupWord.p : nullptr, d_pairFlags.p);
     return d_pairFlags.p;
 }
 
@@ -2697,7 +2728,8 @@ void HipContact::frictionLagUpdate(const double* x_dev, double dHat, double kapp
     d_fricBasis.ensure(6 * (size_t)n);
     const bool scaled = hasObstacle && (fricScaleSelf != 1.0 || fricScaleObst != 1.0);
     hipLaunchKernelGGL(k_friction_lag, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_fricSet.p, x_dev, dHat, kappa, scaled ? (const int*)d_obst.p : nullptr,
-        fricScaleSelf, fricScaleObst, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p);
+        fricScaleSelf, fricScaleObst, hasGroups ? (const int*)d_groupWord.p : nullptr, hasGroups ? (const double*)d_groupScale.p : nullptr, d_fricLambda.p,
+        d_fricCoord.p, d_fricBasis.p);
 }
 
 void HipContact::frictionGet(double* lambda, double* coord2, double* basis6)
@@ -3252,10 +3284,10 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
         const dim3 grid(nblk((long long)codimPoints.size() * mesh.nT));
         if (exactPredicates)
             hipLaunchKernelGGL(k_points_in_tets<true>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
-                counters_.p);
+                pf, counters_.p);
         else
             hipLaunchKernelGGL(k_points_in_tets<false>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
-                counters_.p);
+                pf, counters_.p);
     };
     counters_.alloc(16);
     if (nSF == 0 || nSFE == 0) {

@@ -531,6 +531,31 @@ class Context:
         ids = _i32(ids)
         self._chk(self._L.ipcgpu_set_obstacle_nodes(self.h, C.c_int(len(ids)), _ip(ids), C.c_int(int(obstacle_only))))
 
+    def set_contact_groups(self, groups, collide, fric_scale=None):
+        """Contact groups (ipcgpu_set_contact_groups): `groups[c]` the group of component c of set_components, `collide` a symmetric 0 / 1 matrix over the
+        groups (0: the pair of groups forms no contact pair at all), `fric_scale` a symmetric matrix of factors >= 0 on the lagged normal forces (None:
+        all 1; effective coefficient = selfFric x scale).  `groups=None` or empty goes back to the default."""
+        g = _i32([] if groups is None else groups).ravel()
+        if len(g) == 0:
+            self._chk(self._L.ipcgpu_set_contact_groups(self.h, C.c_int(0), None, C.c_int(0), None, None))
+            return
+        col = np.ascontiguousarray(collide, dtype=np.uint8)
+        if col.ndim != 2 or col.shape[0] != col.shape[1]:
+            raise ValueError("set_contact_groups: collide must be a square matrix")
+        fs = None
+        if fric_scale is not None:
+            fs = _f64(fric_scale)
+            if fs.shape != col.shape:
+                raise ValueError("set_contact_groups: fric_scale must have the shape of collide")
+        self._chk(self._L.ipcgpu_set_contact_groups(self.h, C.c_int(len(g)), _ip(g), C.c_int(col.shape[0]), col.ctypes.data_as(C.POINTER(C.c_ubyte)), _dp(fs)))
+
+    def get_contact_groups(self):
+        """(nGroups, words[nV]): per node the word the contact kernels read -- bits 4-7 its group, bits 16-31 the group's row of `collide`."""
+        n = C.c_int()
+        w = np.zeros(self.nV, dtype=np.int32)
+        self._chk(self._L.ipcgpu_get_contact_groups(self.h, C.byref(n), _ip(w)))
+        return n.value, w.view(np.uint32)
+
     def get_surface(self):
         n = np.zeros(3, dtype=np.int32)
         self._chk(self._L.ipcgpu_get_surface(self.h, _ip(n), None, None))

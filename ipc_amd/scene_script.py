@@ -49,6 +49,7 @@ class Shape:
     mesh_seq: str = None  # `meshSeq <folder>`: the component follows the positions of <folder>/<step>.{msh,obj,seg,pt} (Config.cpp:284-289)
     dbc: list = field(default_factory=list)  # (rel_min, rel_max, lin_vel, ang_vel_deg, t0, t1)
     nbc: list = field(default_factory=list)  # (rel_min, rel_max, acceleration, t0, t1)
+    contact_group: int = 0  # `contactGroup g` (this project's keyword): the contact group of the component, see SceneConfig.contact_group_tables
 
 
 @dataclass
@@ -92,6 +93,41 @@ class SceneConfig:
     half_spaces: list = field(default_factory=list)  # (origin, normal, friction)
     mesh_cos: list = field(default_factory=list)  # (obj path, origin, scale, friction, rotate_deg) -- kinematic mesh obstacles (MeshCO)
     shapes: list = field(default_factory=list)
+    # contact groups (this project's keywords, not the reference's): `contactIgnore g h` -- groups g and h form no contact pair --, `contactFric g h mu` -- the
+    # friction coefficient between groups g and h --, and a trailing `contactGroup g` on a shape line (Shape.contact_group)
+    contact_ignore: list = field(default_factory=list)  # (g, h)
+    contact_fric: list = field(default_factory=list)  # (g, h, mu)
+
+    def uses_contact_groups(self):
+        return bool(self.contact_ignore or self.contact_fric or any(sh.contact_group for sh in self.shapes))
+
+    def effective_self_fric(self):
+        """selfFric as the library gets it: the largest coefficient of the scene, the pairs of groups carry ratios to it (contact_group_tables)."""
+        return max([self.self_fric] + [mu for _, _, mu in self.contact_fric])
+
+    def contact_group_tables(self, n_components=None):
+        """What `contactGroup` / `contactIgnore` / `contactFric` amount to, as Context.set_contact_groups takes it: None for a scene without these
+        keywords, else (groups[n_components], collide[n, n], fric_scale[n, n] or None, self_fric).  Components behind the shapes (mesh collision
+        objects) are in group 0.  A pair of groups without a `contactFric` line carries the scene's selfFric; self_fric is the largest coefficient and
+        fric_scale holds the ratios to it (None: no `contactFric` line, or no friction at all).  A later line for the same pair replaces an earlier one."""
+        if not self.uses_contact_groups():
+            return None
+        n_components = len(self.shapes) if n_components is None else n_components
+        if n_components < len(self.shapes):
+            raise ValueError("contact groups: fewer components than shapes")
+        groups = np.zeros(n_components, dtype=np.int32)
+        groups[:len(self.shapes)] = [sh.contact_group for sh in self.shapes]
+        n = 1 + max([int(groups.max())] + [max(g, h) for g, h, *_ in self.contact_ignore + self.contact_fric])
+        collide = np.ones((n, n), dtype=np.uint8)
+        for g, h in self.contact_ignore:
+            collide[g, h] = collide[h, g] = 0
+        mu_max = self.effective_self_fric()
+        fric_scale = None
+        if self.contact_fric and mu_max > 0:
+            fric_scale = np.full((n, n), self.self_fric / mu_max)
+            for g, h, mu in self.contact_fric:
+                fric_scale[g, h] = fric_scale[h, g] = mu / mu_max
+        return groups, collide, fric_scale, mu_max
 
     @staticmethod
     def parse(text, base_dir="."):
@@ -282,6 +318,17 @@ class SceneConfig:
                 cfg.damping_stiff = max(float(a[0]), 0.0)
             elif k == "dampingRatio":  # Config.cpp:148-157
                 cfg.damping_ratio = min(max(float(a[0]), 0.0), 1.0)
+            elif k == "contactIgnore":  # this project's keyword: the two groups form no contact pair (g == h: no contact inside the group either)
+                if len(a) < 2:
+                    raise ValueError("contactIgnore needs two groups")
+                cfg.contact_ignore.append((_contact_group(a[0]), _contact_group(a[1])))
+            elif k == "contactFric":  # this project's keyword: friction coefficient between two groups
+                if len(a) < 3:
+                    raise ValueError("contactFric needs two groups and a coefficient")
+                mu = float(a[2])
+                if not (math.isfinite(mu) and mu >= 0):
+                    raise ValueError("contactFric: the coefficient must be finite and not negative")
+                cfg.contact_fric.append((_contact_group(a[0]), _contact_group(a[1]), mu))
             elif k in VIEWER_KEYWORDS:
                 pass  # viewer / logging only
             elif k in ("resolution", "inexactSolve"):
@@ -291,6 +338,13 @@ class SceneConfig:
         if cfg.damping_ratio > 0:  # Config.cpp:614-616
             cfg.damping_stiff = cfg.damping_ratio * cfg.dt ** 3 * 3 / 4
         return cfg
+
+
+def _contact_group(tok):
+    g = int(tok)
+    if not 0 <= g < 16:
+        raise ValueError(f"contact group {g}: groups are numbered 0 .. 15")
+    return g
 
 
 def _parse_shape(st, resolve):
@@ -310,6 +364,11 @@ def _parse_shape(st, resolve):
             j += 3
         elif e == "meshSeq":
             sh.mesh_seq = resolve(st[j])
+            j += 1
+        elif e == "contactGroup":
+            if j >= len(st):
+                raise ValueError("contactGroup needs a group")
+            sh.contact_group = _contact_group(st[j])
             j += 1
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
@@ -1028,6 +1087,9 @@ def apply(sc, be):
         # the components of the system report (compVAccSize / compFAccSize, main.cpp:1111-1112): the shapes in script order, then every mesh
         # collision object as a component of its own (they are not part of the reference's Mesh<3>: its files end with the last shape)
         be.set_components(sc.node_ranges[1:], sc.tet_ranges[1:])
+    groups = cfg.contact_group_tables(len(sc.node_ranges) - 1)
+    if groups is not None:
+        be.set_contact_groups(groups[0], groups[1], groups[2])
     if sc.codim_nodes is not None:
         be.set_codim_nodes(sc.codim_nodes, sc.codim_mass)
     be.set_energy_type(cfg.energy)
@@ -1045,7 +1107,7 @@ def apply(sc, be):
         be.set_surface(sc.SF)
     if sc.codim_fixed is not None:
         be.set_dbc(sc.codim_fixed, 2)
-    self_fric = cfg.self_fric
+    self_fric = cfg.effective_self_fric()  # (selfFric itself in a scene without `contactFric`)
     fric_scales = None
     if sc.obstacle_nodes is not None:
         # static obstacle: all of its nodes are ZERO Dirichlet nodes; without `selfCollisionOn` only pairs that involve the
@@ -1057,7 +1119,7 @@ def apply(sc, be):
         # self-collision set only (Optimizer.cpp:3357-3376, 3473-3510, 3676-3705); the value merely switches the lagging loop on
         # (:156-161).  Seen in a run of the reference-compiled code (cubeCliffCO.txt with and without the coefficient).  So pairs that
         # involve an obstacle node carry no friction, the others selfFric.
-        self_fric = cfg.self_fric if cfg.self_collision else 0.0
+        self_fric = self_fric if cfg.self_collision else 0.0
         if self_fric > 0:
             fric_scales = (1.0, 0.0)
     if cfg.self_collision or sc.obstacle_nodes is not None:

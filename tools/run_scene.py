@@ -43,10 +43,10 @@ report = ss.ReportWriter(args.report) if args.report else None
 if report:
     report.write(c)
 has_contact = cfg.self_collision or sc.obstacle_nodes is not None
-fields = ss.FieldsWriter(args.fields, sc, has_contact, cfg.self_fric if cfg.self_collision else 0.0) if args.fields else None
+fields = ss.FieldsWriter(args.fields, sc, has_contact, cfg.effective_self_fric() if cfg.self_collision else 0.0) if args.fields else None
 contact_report = None
 if args.contact_report and (cfg.self_collision or cfg.half_spaces):
-    contact_report = ss.ContactReportWriter(args.contact_report, cfg.self_fric if cfg.self_collision else 0.0)
+    contact_report = ss.ContactReportWriter(args.contact_report, cfg.effective_self_fric() if cfg.self_collision else 0.0)
 elif args.contact_report:
     print("--contact-report: the scene has neither self-collision nor a half-space, nothing will be written")
 steps = args.steps if args.steps is not None else int(round(cfg.duration / cfg.dt))

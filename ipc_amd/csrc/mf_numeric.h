@@ -172,7 +172,8 @@ private:
     int* curFlag() const { return flag_.p + flagCur_; }
     DevBuf<long long> frontOff_, wOff_, dinvOff_;
     DevBuf<int2> aEnt_; // entries of A per fused front: (offset inside the LDS panel, CSR source index), read through by k_front_fused
-    DevBuf<int> bigFd_; // packed records of the other fronts (k_extend_add)
+    DevBuf<int> childMap_, eaTile_, schurTile_; // row maps of the batched fronts' children; tile records of k_extend_add / k_big_schur64_ea (TILE_REC in mf_plan.h)
+    DevBuf<int4> kidRec_; // per (batched front, child): what a tile needs of the child
     DevBuf<int> fdesc_; // packed descriptors of the fused fronts (64 ints each, launch order)
     DevBuf<int> bigASrc_; // entries of A of the other fronts, grouped by extend-add tile: source index ...
     DevBuf<long long> bigADst_; // ... and destination in the front buffer
@@ -180,7 +181,6 @@ private:
     DevBuf<int> entryBucket_, bucketHist_, bucketStart_, nodeFront_; // ... its bucket, the buckets' counts + tickets and starts, the front of every permuted node
     DevBuf<int4> frontInfo_;
     DevBuf<int> eaAPtr_; // per extend-add tile: first of its entries in bigASrc_ / bigADst_ (the extend-add kernel adds them, round 5)
-    DevBuf<int4> eaDesc_;
     DevBuf<int> smallList_, bigList_;
     DevBuf<int4> desc_; // all big-front step descriptors
     PinnedBuf<int> hflag_;

@@ -40,13 +40,6 @@ __global__ void k_publish_flag(const int* __restrict__ flag, int* __restrict__ m
 __global__ void k_clear_flag(int* __restrict__ flag) { flag[0] = 0; }
 
 
-// desc = (record, ti, tj, 0): one 64 x 64 tile (ti >= tj) of a parent front.  `record` indexes a packed 64-int descriptor
-// (layout of the fused kernel: [0,1] front offset [2] N [8] #children in this record [9] next record or -1; child q at
-// 16 + 6 q: [0,1] front offset [2] N [3] nc [4] inverse-map offset) so that front, child list, child geometry and map
-// offsets arrive in one load instead of five dependent ones.  Per child the parent-row / parent-column -> child-index maps of
-// the tile are built once in LDS; lanes run along rows, which are (mostly) consecutive in the child as well, the four waves
-// split the 64 columns.  The gathers are unconditional (clamped address, value selected afterwards): all in flight together.
-// ownOnly: the level's Schur kernel gathers the children for the update block itself (k_big_schur64_ea): only columns < nc are written here
 // ---- entries of A -> slots of the fronts, and their lists, on the device (round 5) --------------------------------------------------------------------
 // A pattern change of a contact scene used to spend 2.9 ms on the host computing, for every entry of the user's CSR matrix, the front that owns it and its
 // offset in that front (mf_entry_destinations, 16 threads) and 3.0 ms sorting the entries by destination (a counting sort into pinned staging buffers, then
@@ -142,74 +135,143 @@ __global__ void k_entry_scatter(int nnz, int ns, const long long* __restrict__ d
     }
 }
 
-// Round 5: the entries of A of the tile follow in the same launch (they used to be a launch of their own per level, k_scatter_big: 5 us on the chain of
-// every level).  aPtr[d.w] .. aPtr[d.w + 1]: the tile's entries in aSrc / aDst (sorted by tile on the host, MfNumeric::setup); every entry of A lands
-// in a column < nc, i.e. in a tile this kernel writes, and no two entries share a slot.
-__global__ __launch_bounds__(WG) void k_extend_add(const int4* __restrict__ desc, const int* __restrict__ bigFd,
-    const int* __restrict__ invMap, double* __restrict__ fronts, int ownOnly, const int* __restrict__ aPtr, const int* __restrict__ aSrc,
-    const long long* __restrict__ aDst, const double* __restrict__ a)
+// Diagnosis build only (-DMF_EA_PROBE, tools/ea_gather_probe.py): thread 0 of every workgroup of k_extend_add and k_big_schur64_ea stamps the 100 MHz wall
+// clock after each phase, behind a wait for everything the wave has in flight (so a phase ends when its loads have landed: the probe build serialises what the
+// product build overlaps); the deltas are summed per level.  MfNumeric::enqueueFactor stamps factorisation 20 and prints the level averages in front of the
+// next one.  Expands to nothing in the product build.
+#ifdef MF_EA_PROBE
+constexpr int EA_PROBE_PH = 8;
+__device__ unsigned long long g_eaProbe[2][64][EA_PROBE_PH + 1]; // [kernel][level]: ticks per phase 1 .. 7, workgroups
+struct EaProbe {
+    unsigned long long t[EA_PROBE_PH];
+};
+#define EA_PROBE_DECL EaProbe pr_ = {}
+#define EA_STAMP(k)                                                                                                                                           \
+    do {                                                                                                                                                      \
+        if (probeLevel >= 0) {                                                                                                                                \
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                                                       \
+            if (threadIdx.x == 0) pr_.t[k] = wall_clock64();                                                                                                  \
+        }                                                                                                                                                     \
+    } while (0)
+__device__ inline void ea_probe_flush(const EaProbe& p, int kernel, int level)
 {
-    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE];
-    __shared__ int rmap[FUSED_MAX_KIDS][TS], cmap[FUSED_MAX_KIDS][TS];
-    const int4 d = desc[blockIdx.x];
-    const int i0 = TS * d.y, j0 = TS * d.z;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (threadIdx.x != 0 || level < 0 || level >= 64) return;
+    unsigned long long prev = p.t[0];
+    for (int k = 1; k < EA_PROBE_PH; ++k) { // a phase that was not stamped counts as empty
+        const unsigned long long t = p.t[k] ? p.t[k] : prev;
+        atomicAdd(&g_eaProbe[kernel][level][k], t - prev);
+        prev = t;
+    }
+    atomicAdd(&g_eaProbe[kernel][level][EA_PROBE_PH], 1ull);
+}
+#define EA_PROBE_FLUSH(kernel) ea_probe_flush(pr_, kernel, probeLevel)
+#else
+#define EA_PROBE_DECL do {} while (0)
+#define EA_STAMP(k) do {} while (0)
+#define EA_PROBE_FLUSH(kernel) do {} while (0)
+#endif
+
+// the gather of one child for a lane's 16 slots of a 64 x 64 tile: r = the lane's row inside the child (-1: none), cc = the slots' columns inside the child.
+// Unconditional loads (clamped address, value selected afterwards): all in flight together.
+struct KidGather {
+    double x[16];
+    bool ok[16];
+};
+__device__ __forceinline__ void kid_gather(const double* __restrict__ Fc, const long long Nc, const int r, const int (&cc)[16], KidGather& g)
+{
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        g.ok[q] = r >= 0 && cc[q] >= 0 && r >= cc[q];
+        g.x[q] = Fc[g.ok[q] ? r + Nc * cc[q] : 0];
+    }
+}
+__device__ __forceinline__ const double* kid_front(const double* fronts, const int4 k)
+{
+    return fronts + (((long long)(unsigned)k.y << 32) | (unsigned)k.x);
+}
+
+// One 64 x 64 tile (ti >= tj) of a parent front per workgroup: lanes run along rows, which are (mostly) consecutive in the child as well, the four waves split
+// the 64 columns.  tile = the workgroup's record (TILE_REC in mf_plan.h: the front, the tile and the first two children in one 64-byte line); the lane's row and
+// the wave's 16 columns inside each child come straight from the child's row map (mf_plan.cpp, childMaps).  Until the maps existed every tile rebuilt them in
+// LDS from the packed front record and the node map: record -> LDS -> barrier -> node map -> LDS -> barrier in front of the first gather, child after child
+// behind it (profiles/extend_add_gather_phases.txt).  Now nothing is staged and no barrier precedes the store: the gathers of both inline children are in
+// flight together, and so are the tile's first entries of A (their three dependent loads used to start behind the store).  Every slot is still
+// ((0 + child 0) + child 1 ...) stored, then + a: the fronts keep their bits.  Children 2, 3, ... (rare: a separator with more than two parts) follow one by one.
+// ownOnly: the level's Schur kernel gathers the children for the update block itself (k_big_schur64_ea): only columns < nc are written here.
+// aPtr[b] .. aPtr[b + 1]: the entries of A of tile b in aSrc / aDst (sorted by tile, MfNumeric::setup); every entry of A lands in a column < nc, i.e. in a tile
+// this kernel writes, and no two entries share a slot.
+__global__ __launch_bounds__(WG) void k_extend_add(const int4* __restrict__ tile, const int* __restrict__ childMap, const int4* __restrict__ kidRec,
+    double* __restrict__ fronts, int ownOnly, const int* __restrict__ aPtr, const int* __restrict__ aSrc, const long long* __restrict__ aDst,
+    const double* __restrict__ a
+#ifdef MF_EA_PROBE
+    ,
+    int probeLevel
+#endif
+)
+{
+    EA_PROBE_DECL;
+    EA_STAMP(0);
+    const int4 g = tile[4 * blockIdx.x], t = tile[4 * blockIdx.x + 1], k0 = tile[4 * blockIdx.x + 2], k1 = tile[4 * blockIdx.x + 3];
+    const int aBeg = aPtr[blockIdx.x], aEnd = aPtr[blockIdx.x + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the thread's first entry of A: requested now, added behind the store
+    const int e0 = aBeg + tid;
+    long long dst0 = 0;
+    double a0 = 0.0;
+    if (e0 < aEnd) {
+        dst0 = aDst[e0];
+        a0 = a[aSrc[e0]];
+    }
+    EA_STAMP(1);
+    const int N = g.x, ncOwn = g.y, nk = t.z;
+    double* F = fronts + (((long long)(unsigned)g.w << 32) | (unsigned)g.z);
+    const int I = TS * t.x + lane, J0 = TS * t.y + 16 * wv; // (rows and columns up to N + 63: the maps are padded)
+    const int* m0 = childMap + k0.w;
+    const int* m1 = childMap + k1.w;
+    const int r0 = m0[I], r1 = m1[I];
+    int c0[16], c1[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        c0[q] = m0[J0 + q];
+        c1[q] = m1[J0 + q];
+    }
+    EA_STAMP(2);
+    KidGather g0, g1;
+    kid_gather(kid_front(fronts, k0), k0.z, r0, c0, g0);
+    kid_gather(kid_front(fronts, k1), k1.z, r1, c1, g1);
     double sum[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) sum[q] = 0.0;
-    int N = 0, ncOwn = 0;
-    double* F = nullptr;
-    for (int rec = d.x; rec >= 0;) {
-        __syncthreads();
-        if (tid < FD_STRIDE) fd[tid] = bigFd[(size_t)rec * FD_STRIDE + tid];
-        __syncthreads();
-        N = fd[2];
-        ncOwn = fd[3];
-        F = fronts + *reinterpret_cast<const long long*>(fd);
-        const int nk = fd[8];
-        rec = fd[9];
-        for (int e = tid; e < nk * 2 * TS; e += WG) {
-            const int k = e / (2 * TS), t = e - k * (2 * TS);
-            const int* inv = invMap + fd[16 + 6 * k + 4];
-            const int ncc = fd[16 + 6 * k + 3];
-            const int I = (t < TS ? i0 : j0 - TS) + t;
-            int m = -1;
-            if (I < N) {
-                const int ic = inv[I / 3];
-                if (ic >= 0) m = ncc + 3 * ic + (I - 3 * (I / 3));
-            }
-            (t < TS ? rmap[k] : cmap[k] - TS)[t] = m;
-        }
-        __syncthreads();
-        for (int k = 0; k < nk; ++k) {
-            const double* __restrict__ Fc = fronts + *reinterpret_cast<const long long*>(fd + 16 + 6 * k);
-            const long long Nc = fd[16 + 6 * k + 2];
-            const int r = rmap[k][lane];
-            double x[16];
-            bool ok[16];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int cc = cmap[k][16 * wv + q];
-                ok[q] = r >= 0 && cc >= 0 && r >= cc;
-                x[q] = Fc[ok[q] ? r + Nc * cc : 0];
-            }
+    for (int q = 0; q < 16; ++q) sum[q] += g0.ok[q] ? g0.x[q] : 0.0;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) sum[q] += ok[q] ? x[q] : 0.0;
-        }
+    for (int q = 0; q < 16; ++q) sum[q] += g1.ok[q] ? g1.x[q] : 0.0;
+    EA_STAMP(4);
+    for (int k = 2; k < nk; ++k) { // (workgroup-uniform)
+        const int4 kr = kidRec[t.w + k];
+        const int* m = childMap + kr.w;
+        const int r = m[I];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) c0[q] = m[J0 + q];
+        kid_gather(kid_front(fronts, kr), kr.z, r, c0, g0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) sum[q] += g0.ok[q] ? g0.x[q] : 0.0;
     }
-    const int I = i0 + lane;
     if (I < N) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int J = j0 + 16 * wv + q;
+            const int J = J0 + q;
             if (J <= I && (!ownOnly || J < ncOwn)) F[I + (long long)N * J] = sum[q]; // write, not accumulate: the fronts are never zero-filled
         }
     }
-    const int aBeg = aPtr[d.w], aEnd = aPtr[d.w + 1];
+    EA_STAMP(6);
     if (aBeg < aEnd) { // (workgroup-uniform)
         __syncthreads(); // the tile is written: the entries of A are added by whichever thread picks them up
-        for (int e = aBeg + tid; e < aEnd; e += WG) fronts[aDst[e]] += a[aSrc[e]];
+        if (e0 < aEnd) fronts[dst0] += a0;
+        for (int e = e0 + WG; e < aEnd; e += WG) fronts[aDst[e]] += a[aSrc[e]];
     }
+    EA_STAMP(7);
+    EA_PROBE_FLUSH(0);
 }
 
 // value of `v` in lane `lane` (uniform, here always a compile-time constant after unrolling): two v_readlane_b32
@@ -878,9 +940,14 @@ __device__ __forceinline__ double load_uniform_plus_lane(const double* uniformBa
 {
     return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(uniformBase) + laneBytes);
 }
-template <bool LOAD_OLD>
+// fillOld (LOAD_OLD = false): called once, behind the request for the first operand chunk, to fill `old` -- the caller's gathers are in flight by then and are
+// consumed while the operands travel.
+struct SchurNoFill {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <bool LOAD_OLD, class FillOld = SchurNoFill>
 __device__ __forceinline__ void schur_tile64_core(const int N, const int orig, const int colEnd, const int nc, double* __restrict__ F, const int ti, const int tj,
-    const int cLo, double (&old)[2][2][4])
+    const int cLo, double (&old)[2][2][4], FillOld fillOld = FillOld(), unsigned long long* probeProduct = nullptr)
 {
     if (cLo >= nc) return;
     const int tid = threadIdx.x;
@@ -934,6 +1001,11 @@ __device__ __forceinline__ void schur_tile64_core(const int N, const int orig, c
     // ping-pong register sets, unconditional fetches behind scheduling fences: see k_big_schur
     const int ch0 = cLo / CW;
     fetch(ch0, a0, a1, b0, b1);
+    if (!LOAD_OLD) {
+        __builtin_amdgcn_sched_barrier(0);
+        fillOld();
+        __builtin_amdgcn_sched_barrier(0);
+    }
     int ch = ch0;
     // main loop: the two chunks it multiplies and the two it fetches all lie below nc (lane_bytes above)
     const unsigned va0 = lane_bytes(pa0, F, N, ak), va1 = lane_bytes(pa1, F, N, ak), vb0 = lane_bytes(pb0, F, N, ak), vb1 = lane_bytes(pb1, F, N, ak);
@@ -979,6 +1051,12 @@ __device__ __forceinline__ void schur_tile64_core(const int N, const int orig, c
     if (ch + 1 < nch) mult(ch + 1, na0, na1, nb0, nb1);
     __builtin_amdgcn_sched_barrier(0);
     if (ch + 2 < nch) mult(ch + 2, a0, a1, b0, b1);
+#ifdef MF_EA_PROBE
+    if (probeProduct) {
+        asm volatile("s_nop 15\n\ts_nop 15" ::"v"(acc[1][1][3]) : "memory"); // (behind the last MFMA)
+        *probeProduct = wall_clock64();
+    }
+#endif
 #pragma unroll
     for (int nj = 0; nj < 2; ++nj)
 #pragma unroll
@@ -1022,75 +1100,88 @@ __global__ __launch_bounds__(WG, MF_SCHUR_OCC) void k_big_bulk(const int4* __res
 
 // The same with the EXTEND-ADD of the update block fused in (round 4): S = (children) - L21 L21^T written once.  The extend-add kernel of such a level
 // only writes the front's own columns; the update block used to be written by it (children sums or zeros), read back and written again here: two passes
-// over the largest part of every middle-level front.  desc = (front, ti, tj, packed record of the front's children) + (N, nc, front offset); the
-// records, the child -> parent index maps and the order of the sums are those of k_extend_add.
-__global__ __launch_bounds__(WG) void k_big_schur64_ea(const int4* __restrict__ desc, const int* __restrict__ bigFd, const int* __restrict__ invMap,
-    double* __restrict__ fronts)
+// over the largest part of every middle-level front.  tile = the workgroup's record as in k_extend_add (tile indices counted from nc); the row maps and the
+// order of the sums are those of k_extend_add.  No LDS and no barrier: a quadrant above the diagonal leaves at once, the others request both inline children's
+// values together and then the first operand chunk of the product, so that the product's first round trip runs beside the gathers.
+struct KidGather64 {
+    double x[2][2][4];
+    bool ok[2][2][4];
+};
+__device__ __forceinline__ void kid_gather64(const double* __restrict__ Fc, const long long Nc, const int* __restrict__ m, const int I0, const int J0, const int ar,
+    const int ak, KidGather64& g)
 {
-    __shared__ __attribute__((aligned(16))) int fd[FD_STRIDE];
-    __shared__ int rmap[FUSED_MAX_KIDS][TQ64], cmap[FUSED_MAX_KIDS][TQ64];
-    const int4 d = desc[2 * blockIdx.x];
-    const int4 d2 = desc[2 * blockIdx.x + 1];
-    const int N = d2.x, nc = d2.y;
-    double* F = fronts + (((long long)(unsigned)d2.w << 32) | (unsigned)d2.z);
-    const int tid = threadIdx.x, wv = tid >> 6, l = tid & 63, ar = l & 15, ak = l >> 4;
-    const int I0 = nc + TQ64 * d.y, J0 = nc + TQ64 * d.z;
-    const int qi = 32 * (wv & 1), qj = 32 * (wv >> 1);
-    const bool active = !(I0 + qi + 31 < J0 + qj || I0 + qi >= N || J0 + qj >= N);
-    double old[2][2][4];
+    int rr[2], cc[2][4];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) rr[mi] = m[I0 + 16 * mi + ar];
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cc[nj][r] = m[J0 + 16 * nj + ak + 4 * r];
 #pragma unroll
     for (int nj = 0; nj < 2; ++nj)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) old[nj][mi][r] = 0.0;
-    for (int rec = d.w; rec >= 0;) {
-        __syncthreads();
-        if (tid < FD_STRIDE) fd[tid] = bigFd[(size_t)rec * FD_STRIDE + tid];
-        __syncthreads();
-        const int nk = fd[8];
-        rec = fd[9];
-        for (int e = tid; e < nk * 2 * TQ64; e += WG) {
-            const int k = e / (2 * TQ64), t = e - k * (2 * TQ64);
-            const int* inv = invMap + fd[16 + 6 * k + 4];
-            const int ncc = fd[16 + 6 * k + 3];
-            const int I = (t < TQ64 ? I0 : J0 - TQ64) + t;
-            int m = -1;
-            if (I < N) {
-                const int ic = inv[I / 3];
-                if (ic >= 0) m = ncc + 3 * ic + (I - 3 * (I / 3));
+            for (int r = 0; r < 4; ++r) {
+                g.ok[nj][mi][r] = rr[mi] >= 0 && cc[nj][r] >= 0 && rr[mi] >= cc[nj][r];
+                g.x[nj][mi][r] = Fc[g.ok[nj][mi][r] ? rr[mi] + Nc * cc[nj][r] : 0];
             }
-            (t < TQ64 ? rmap[k] : cmap[k] - TQ64)[t] = m;
+}
+__device__ __forceinline__ void kid_add64(const KidGather64& g, double (&old)[2][2][4])
+{
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) old[nj][mi][r] += g.ok[nj][mi][r] ? g.x[nj][mi][r] : 0.0;
+}
+__global__ __launch_bounds__(WG) void k_big_schur64_ea(const int4* __restrict__ tile, const int* __restrict__ childMap, const int4* __restrict__ kidRec,
+    double* __restrict__ fronts
+#ifdef MF_EA_PROBE
+    ,
+    int probeLevel
+#endif
+)
+{
+    EA_PROBE_DECL;
+    EA_STAMP(0);
+    const int4 g = tile[4 * blockIdx.x], t = tile[4 * blockIdx.x + 1], k0 = tile[4 * blockIdx.x + 2], k1 = tile[4 * blockIdx.x + 3];
+    const int N = g.x, nc = g.y, nk = t.z;
+    double* F = fronts + (((long long)(unsigned)g.w << 32) | (unsigned)g.z);
+    const int tid = threadIdx.x, wv = tid >> 6, l = tid & 63, ar = l & 15, ak = l >> 4;
+    const int I0 = nc + TQ64 * t.x + 32 * (wv & 1), J0 = nc + TQ64 * t.y + 32 * (wv >> 1); // this wave's quadrant (rows and columns up to N + 63: the maps are padded)
+    if (I0 + 31 < J0 || I0 >= N || J0 >= N) return; // entirely above the diagonal or outside
+    EA_STAMP(1);
+    KidGather64 g0, g1;
+    kid_gather64(kid_front(fronts, k0), k0.z, childMap + k0.w, I0, J0, ar, ak, g0);
+    kid_gather64(kid_front(fronts, k1), k1.z, childMap + k1.w, I0, J0, ar, ak, g1);
+    double old[2][2][4];
+    auto sums = [&]() { // (called by the product behind the request for its first operands)
+#pragma unroll
+        for (int nj = 0; nj < 2; ++nj)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) old[nj][mi][r] = 0.0;
+        kid_add64(g0, old);
+        kid_add64(g1, old);
+        EA_STAMP(4);
+        for (int k = 2; k < nk; ++k) { // (workgroup-uniform; rare: a separator with more than two parts)
+            const int4 kr = kidRec[t.w + k];
+            kid_gather64(kid_front(fronts, kr), kr.z, childMap + kr.w, I0, J0, ar, ak, g0);
+            kid_add64(g0, old);
         }
-        __syncthreads();
-        if (active) {
-            for (int k = 0; k < nk; ++k) {
-                const double* __restrict__ Fc = fronts + *reinterpret_cast<const long long*>(fd + 16 + 6 * k);
-                const long long Nc = fd[16 + 6 * k + 2];
-                double x[2][2][4];
-                bool ok[2][2][4];
-#pragma unroll
-                for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-                    for (int mi = 0; mi < 2; ++mi) {
-                        const int rr = rmap[k][qi + 16 * mi + ar];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int cc = cmap[k][qj + 16 * nj + ak + 4 * r];
-                            ok[nj][mi][r] = rr >= 0 && cc >= 0 && rr >= cc;
-                            x[nj][mi][r] = Fc[ok[nj][mi][r] ? rr + Nc * cc : 0];
-                        }
-                    }
-#pragma unroll
-                for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-                    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) old[nj][mi][r] += ok[nj][mi][r] ? x[nj][mi][r] : 0.0;
-            }
-        }
-    }
-    if (active) schur_tile64_core<false>(N, nc, N, nc, F, d.y, d.z, 0, old);
+    };
+#ifdef MF_EA_PROBE
+    unsigned long long tProduct = 0;
+    schur_tile64_core<false>(N, nc, N, nc, F, t.x, t.y, 0, old, sums, probeLevel >= 0 && tid == 0 ? &tProduct : nullptr);
+    pr_.t[5] = tProduct;
+#else
+    schur_tile64_core<false>(N, nc, N, nc, F, t.x, t.y, 0, old, sums);
+#endif
+    EA_STAMP(6);
+    EA_PROBE_FLUSH(1);
 }
 
 
@@ -1706,8 +1797,10 @@ void MfNumeric::setup(const MfSymbolic& sym, hipStream_t stream, const int* ia_d
     lap("inverse plan + buffers");
     smallList_.upload(mp_.smallList, stream);
     bigList_.upload(mp_.bigList, stream);
-    uploadRecs(eaDesc_, mp_.ea, stream);
-    bigFd_.uploadGrow(mp_.bigFd, stream);
+    childMap_.uploadGrow(mp_.childMap, stream);
+    uploadRecs(kidRec_, mp_.kidRec, stream);
+    eaTile_.uploadGrow(mp_.eaTile, stream);
+    schurTile_.uploadGrow(mp_.schurTile, stream);
     uploadRecs(desc_, mp_.desc, stream);
     if (world_ > 1) { // the exchange groups: the plan's offsets into the staging buffer and the solution vector become pointers
         xchgBuf_.ensure((size_t)mp_.xchgStaging + 1);
@@ -1842,6 +1935,29 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
         HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_probeBase), &base, sizeof(base), 0, hipMemcpyHostToDevice, stream_));
     }
 #endif
+#ifdef MF_EA_PROBE
+    static int eaProbeCalls = 0;
+    const bool probeCall = ++eaProbeCalls == 20; // a warm one
+    if (eaProbeCalls == 21) { // (diagnosis build: the synchronisation does not matter)
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        static unsigned long long h[2][64][EA_PROBE_PH + 1];
+        HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_eaProbe), sizeof(h)));
+        const char* kn[2] = { "k_extend_add", "k_big_schur64_ea" };
+        const char* names[EA_PROBE_PH] = { "", "records", "maps", "child0", "children", "product", "store", "A" };
+        for (int k = 0; k < 2; ++k)
+            for (int l = 0; l < nLevels_ && l < 64; ++l) {
+                const double n = (double)h[k][l][EA_PROBE_PH];
+                if (n == 0) continue;
+                double tot = 0;
+                std::fprintf(stderr, "[ea probe] %-16s level %2d: %5.0f workgroups |", kn[k], l, n);
+                for (int ph = 1; ph < EA_PROBE_PH; ++ph) {
+                    std::fprintf(stderr, " %s %.2f", names[ph], 0.01 * (double)h[k][l][ph] / n); // 100 MHz ticks -> us, per workgroup
+                    tot += 0.01 * (double)h[k][l][ph] / n;
+                }
+                std::fprintf(stderr, " | total %.2f us\n", tot);
+            }
+    }
+#endif
     // the pivot flag of this factorisation: the slot the previous one cleared (setup() cleared both).  The first fused launch clears the other slot for the
     // next factorisation; a tree without fused fronts does it with a one-thread launch behind its last kernel
     flagCur_ ^= 1;
@@ -1860,9 +1976,15 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
                     dinv_.p, flag, flagNext);
             flagNext = nullptr;
         }
-        if (P.ea.cnt) {
-            hipLaunchKernelGGL(k_extend_add, dim3(P.ea.cnt), dim3(WG), 0, stream_, eaDesc_.p + P.ea.off, bigFd_.p, inv_.p, fronts_.p, P.fuseEA ? 1 : 0, eaAPtr_.p,
+        if (P.ea.cnt) { // (tile b of the launch is extend-add tile P.ea.off + b: its record and its range of entries of A)
+            const int4* tiles = reinterpret_cast<const int4*>(eaTile_.p + (size_t)P.ea.off * TILE_REC);
+#ifdef MF_EA_PROBE
+            hipLaunchKernelGGL(k_extend_add, dim3(P.ea.cnt), dim3(WG), 0, stream_, tiles, childMap_.p, kidRec_.p, fronts_.p, P.fuseEA ? 1 : 0, eaAPtr_.p + P.ea.off,
+                bigASrc_.p, bigADst_.p, a_dev, probeCall ? l : -1);
+#else
+            hipLaunchKernelGGL(k_extend_add, dim3(P.ea.cnt), dim3(WG), 0, stream_, tiles, childMap_.p, kidRec_.p, fronts_.p, P.fuseEA ? 1 : 0, eaAPtr_.p + P.ea.off,
                 bigASrc_.p, bigADst_.p, a_dev);
+#endif
         }
         for (const Range& R : P.step) { // one launch per 32-column step, each with look-ahead (k_big_step)
             if (!R.cnt) continue;
@@ -1872,7 +1994,14 @@ void MfNumeric::enqueueFactor(const double* a_dev, bool overlapForward)
             if (U.cnt) hipLaunchKernelGGL(k_big_bulk, dim3(U.cnt), dim3(WG), 0, stream_, desc_.p + U.off, fronts_.p);
         }
         if (P.schur.cnt) {
-            if (P.fuseEA) hipLaunchKernelGGL(k_big_schur64_ea, dim3(P.schur.cnt), dim3(WG), 0, stream_, desc_.p + P.schur.off, bigFd_.p, inv_.p, fronts_.p);
+            if (P.fuseEA) {
+                const int4* tiles = reinterpret_cast<const int4*>(schurTile_.p + (size_t)P.schurTileOff * TILE_REC);
+#ifdef MF_EA_PROBE
+                hipLaunchKernelGGL(k_big_schur64_ea, dim3(P.schur.cnt), dim3(WG), 0, stream_, tiles, childMap_.p, kidRec_.p, fronts_.p, probeCall ? l : -1);
+#else
+                hipLaunchKernelGGL(k_big_schur64_ea, dim3(P.schur.cnt), dim3(WG), 0, stream_, tiles, childMap_.p, kidRec_.p, fronts_.p);
+#endif
+            }
             else if (P.schur64) hipLaunchKernelGGL(k_big_schur64, dim3(P.schur.cnt), dim3(WG), 0, stream_, desc_.p + P.schur.off, fronts_.p);
             else hipLaunchKernelGGL(k_big_schur, dim3(P.schur.cnt), dim3(WG), 0, stream_, desc_.p + P.schur.off, fronts_.p);
         }

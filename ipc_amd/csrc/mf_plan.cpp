@@ -194,6 +194,56 @@ std::vector<int> packBigFronts(const MfSymbolic& sym, MfPlan& plan)
     return recOf;
 }
 
+// The children of the batched fronts for the tile kernels (TILE_REC in mf_plan.h): per child one map parent scalar row -> child scalar row, which the kernels
+// used to derive for every tile from the node map (nc(child) + 3 inv[I / 3] + I % 3), and one record per child.
+void childMaps(const MfSymbolic& sym, MfPlan& plan)
+{
+    int maxN = 0;
+    size_t total = 0, kids = 0;
+    for (int s : plan.bigList) {
+        maxN = std::max(maxN, sym.N(s));
+        total += (size_t)kidsOf(sym, s) * (sym.N(s) + TILE_MAP_PAD);
+        kids += kidsOf(sym, s);
+    }
+    total += (size_t)maxN + TILE_MAP_PAD;
+    if (total > (size_t)INT_MAX) throw MfPlanError("the child maps of the batched fronts exceed 2^31 entries");
+    plan.childMap.assign(total, -1);
+    plan.kidRec.clear();
+    plan.kidRec.reserve(kids + 1);
+    plan.kidBase.assign(sym.ns, -1);
+    size_t at = (size_t)maxN + TILE_MAP_PAD;
+    for (int s : plan.bigList) {
+        plan.kidBase[s] = (int)plan.kidRec.size();
+        const int N = sym.N(s);
+        for (int q = 0; q < kidsOf(sym, s); ++q) {
+            const int c = sym.child[sym.childPtr[s] + q];
+            const int* inv = sym.inv.data() + sym.invPtr[c];
+            const int ncc = sym.nc(c);
+            int* m = plan.childMap.data() + at;
+            for (int I = 0; I < N; ++I) {
+                const int ic = inv[I / 3];
+                if (ic >= 0) m[I] = ncc + 3 * ic + I % 3;
+            }
+            const long long coff = sym.frontOff[c];
+            plan.kidRec.push_back(MfRec4{ (int)(unsigned)(coff & 0xffffffffll), (int)(unsigned)(coff >> 32), sym.N(c), (int)at });
+            at += (size_t)N + TILE_MAP_PAD;
+        }
+    }
+    if (plan.kidRec.empty()) plan.kidRec.push_back(MfRec4{ 0, 0, 0, 0 });
+}
+
+// the record of tile (ti, tj) of batched front s: the front's geometry and its first two children inline
+void pushTileRecord(const MfSymbolic& sym, const MfPlan& plan, int s, int ti, int tj, std::vector<int>& out)
+{
+    const MfRec4 g = geometryRec(sym, s);
+    const int nk = kidsOf(sym, s), base = plan.kidBase[s];
+    out.insert(out.end(), { g.x, g.y, g.z, g.w, ti, tj, nk, base });
+    for (int q = 0; q < 2; ++q) {
+        const MfRec4 k = q < nk ? plan.kidRec[base + q] : MfRec4{ 0, 0, 0, 0 };
+        out.insert(out.end(), { k.x, k.y, k.z, k.w });
+    }
+}
+
 // packed descriptors of the fused fronts, in launch order
 void packFusedFronts(const MfSymbolic& sym, MfPlan& plan)
 {
@@ -220,6 +270,7 @@ void extendAddTiles(const MfSymbolic& sym, MfPlan& plan, const std::vector<int>&
                 if (P.fuseEA && TS * tj >= sym.nc(s)) continue; // a tile of the update block alone: the Schur kernel's
                 if ((int)ea.size() != plan.eaTileOf(s, ti, tj)) throw MfPlanError("internal: extend-add tiles are not numbered in emission order");
                 ea.push_back(MfRec4{ recOf[s], ti, tj, plan.eaTileOf(s, ti, tj) });
+                pushTileRecord(sym, plan, s, ti, tj, plan.eaTile);
             }
     }
     P.ea.cnt = (int)ea.size() - P.ea.off;
@@ -359,6 +410,12 @@ void schurTiles(const MfSymbolic& sym, MfPlan& plan, const std::vector<int>& rec
             desc.push_back(t.b);
         }
     P.schur.cnt = ((int)desc.size() - P.schur.off) / 2; // workgroups: two records each
+    P.schurTileOff = (int)(plan.schurTile.size() / TILE_REC);
+    if (P.fuseEA) // the same workgroups, as the records k_big_schur64_ea reads (tile indices count from nc, as above)
+        for (int w = 0; w < P.schur.cnt; ++w) {
+            const MfRec4& a = desc[(size_t)P.schur.off + 2 * w];
+            pushTileRecord(sym, plan, a.x, a.y, a.z, plan.schurTile);
+        }
 }
 
 // the row-/column-parallel halves of the big-front solves below the triangle
@@ -500,6 +557,7 @@ void mf_plan_launches(const MfSymbolic& sym, const int* start, MfPlan& plan)
     plan.eaAPtr.resize((size_t)plan.nEaTiles + 1);
     for (int t = 0; t <= plan.nEaTiles; ++t) plan.eaAPtr[t] = start[ns + t] - start[ns]; // per extend-add tile: its range among the big fronts' entries
     const std::vector<int> recOf = packBigFronts(sym, plan);
+    childMaps(sym, plan);
     for (int l = 0; l < nLevels; ++l) {
         levelLds(sym, plan, l);
         extendAddTiles(sym, plan, recOf, l);
@@ -518,6 +576,8 @@ void mf_plan_launches(const MfSymbolic& sym, const int* start, MfPlan& plan)
     if (plan.bigList.empty()) plan.bigList.push_back(0);
     if (plan.ea.empty()) plan.ea.push_back(MfRec4{ 0, 0, 0, 0 });
     if (plan.bigFd.empty()) plan.bigFd.resize(FD_STRIDE, 0);
+    if (plan.eaTile.empty()) plan.eaTile.resize(TILE_REC, 0);
+    if (plan.schurTile.empty()) plan.schurTile.resize(TILE_REC, 0);
     if (plan.desc.empty()) plan.desc.push_back(MfRec4{ 0, 0, 0, 0 });
     if (plan.world > 1 && plan.xchgDesc.empty()) plan.xchgDesc.push_back(MfRec4{ 0, 0, 0, 0 });
 }

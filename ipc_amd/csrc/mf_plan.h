@@ -30,6 +30,15 @@ constexpr int MV_ROWS = 32; // rows per workgroup of the forward matrix-vector k
 // ([4..7] are filled for the fused fronts only, [9] for the chained records of the others.)
 constexpr int FD_STRIDE = 64;
 constexpr int FUSED_MAX_KIDS = 8;
+// Tile records of the two kernels that gather children per 64 x 64 tile (k_extend_add, k_big_schur64_ea): 16 ints = four int4 = one 64-byte line per workgroup,
+// so that everything in front of the gathers arrives with the tile's first load:
+//   [0] N  [1] nc  [2,3] front offset | [4] ti  [5] tj  [6] #children of the front  [7] first of its records in kidRec
+//   child q (0, 1) at 8 + 4 q: [0,1] front offset  [2] N  [3] offset of its row map in childMap   (an absent child: front offset 0, N 0, the map of -1s at offset 0)
+// Children 2, 3, ... of a front are read from kidRec (the same four ints each, the front's children in ascending order), one after the other.
+// childMap: per (batched front, child) N(parent) + TILE_MAP_PAD ints: parent scalar row I -> scalar row inside the child's front, -1 where the child's structure
+// lacks it.  The pad (rows N .. N + 63, all -1) lets a tile that hangs over the front's last row load its indices without a clamp.
+constexpr int TILE_REC = 16;
+constexpr int TILE_MAP_PAD = 64;
 
 #ifndef MF_BORDER_MAX_NC
 #define MF_BORDER_MAX_NC 1536 // (1024 until round 6: the 1 440-column root of the two-sheet contact stack keeps 0.17 ms of doubling rounds behind its factorisation, profiles/r06_border_max_nc_ab.txt)
@@ -73,6 +82,7 @@ struct MfLevelPlan {
     std::vector<MfRange> step; // fused factor steps: launch 0 factors panel 0, launch j+1 applies panel j / factors j+1
     std::vector<MfRange> bulk; // per step launch: the bulk updates of the wide fronts that follow it (k_big_bulk; empty ranges elsewhere)
     MfRange schur; // one-pass Schur complement tiles of the big fronts
+    int schurTileOff = 0; // fuseEA levels: first of the level's records in schurTile (one per workgroup, in the order of `schur`)
     bool schur64 = false; // ... as 64 x 64 tiles (k_big_schur64) instead of 32 x 32 with the columns split over the waves
     bool stepTop = false; // the level's step launches carry role C, the explicit inverse growing by bordering (k_big_step<true>)
     bool fuseEA = false; // the level's Schur kernel gathers the children of the update block itself (k_big_schur64_ea); the extend-add only writes own columns
@@ -126,8 +136,14 @@ struct MfPlan {
     std::vector<int> aPtr; // ns + 1: entry range of every fused front (the bucket starts of the device sort)
     size_t nFusedA = 0, nBigA = 0; // entries of A of the fused fronts / of the others
     std::vector<int> eaAPtr; // per extend-add tile: first of its entries among the others'
-    std::vector<MfRec4> ea; // extend-add descriptors (record, ti, tj, tile number)
-    std::vector<int> bigFd; // packed records of the fronts of the multi-workgroup path (k_extend_add, k_big_schur64_ea)
+    std::vector<MfRec4> ea; // extend-add tiles (record in bigFd, ti, tj, tile number): the host's list; the kernel reads eaTile
+    std::vector<int> bigFd; // packed records of the fronts of the multi-workgroup path (host only since the tile records below: tests read the plan through them)
+    // the children of the batched fronts as the tile kernels read them (TILE_REC above): they depend on the pattern alone, like every other array here
+    std::vector<int> childMap; // [0, maxN + TILE_MAP_PAD): -1s (the map of an absent child); then the maps, front after front in bigList order, child after child
+    std::vector<MfRec4> kidRec; // per (batched front, child): (front offset lo, hi, N, map offset)
+    std::vector<int> kidBase; // per front: first of its records in kidRec, -1 for a front that is not batched
+    std::vector<int> eaTile; // TILE_REC ints per extend-add tile, in the order of `ea`
+    std::vector<int> schurTile; // TILE_REC ints per Schur workgroup of the fuseEA levels
     std::vector<int> fdesc; // packed records of the fused fronts, in launch order
     std::vector<MfRec4> desc; // step, bulk, Schur and sweep descriptors of the big fronts
     std::vector<MfRec4> xinvDesc; // all descriptors of the inverse machinery

@@ -331,6 +331,46 @@ int ipcgpu_get_contact_groups(ipcgpu_ctx*, int* nGroups, int* nodeWord_nV /*null
  * fix or move them as Dirichlet nodes (`script DCOFix`: ipcgpu_set_dbc(ids, NONZERO)).  Call after ipcgpu_set_mesh, before
  * ipcgpu_opt_init / ipcgpu_opt_enable_self_collision. */
 int ipcgpu_set_codim_nodes(ipcgpu_ctx*, int n, const int* node_ids, const double* node_mass);
+/* Elastic shells (no counterpart in the reference): membrane and bending energy on triangle components.  Per triangle with rest positions X, positions
+ * x, thickness h, Lame parameters from (E, nu) and rest area A:
+ *   membrane  St. Venant-Kirchhoff, plane stress: Dm = [X1 - X0, X2 - X0] in the rest plane, F = [x1 - x0, x2 - x0] Dm^-1, G = (F^T F - I) / 2,
+ *             psi = mu |G|_F^2 + lambda_ps tr(G)^2 / 2, mu = E / (2 (1 + nu)), lambda_ps = E nu / (1 - nu^2); energy h A psi; exact gradient; the 9 x 9
+ *             Hessian projected to PSD per triangle.  A polynomial, finite everywhere: no inversion check, no step filter (as for FCR and SNH).
+ *   bending   one hinge per edge shared by two triangles, nodes (x0, x1) on the edge and (x2, x3) opposite: bendScale k_b w_e (theta - thetaBar)^2 with
+ *             theta the signed dihedral angle (atan2 of the two normals about the edge), thetaBar the same at rest (curved rest shapes are stress-free),
+ *             w_e = 3 |eBar|^2 / (A1 + A2), k_b = E h^3 / (24 (1 - nu^2)) (mean of the two triangles).  Exact gradient; Gauss-Newton Hessian
+ *             2 bendScale k_b w_e grad theta grad theta^T.  theta - thetaBar is NOT unwrapped: a hinge folded through +-pi is a self-intersection, which
+ *             contact prevents.
+ * ipcgpu_set_shell: tri_colmajor nTri x 3 node ids; thickness, E, nu, rho per triangle; bendScale >= 0.  After ipcgpu_set_mesh, before ipcgpu_opt_init
+ * (else IPCGPU_ERR_STATE) and before ipcgpu_linsys_set_pattern: the node pairs of the shell (triangle edges and the opposite pair of every hinge) join
+ * vNeighbor, so a pattern built afterwards holds every block the shell Hessian writes (a node pattern that exists already is rebuilt by this call from
+ * the new vNeighbor, without extra pairs; a pattern given by ipcgpu_linsys_set_pattern_csr is the caller's business).  It sets the lumped masses of the shell nodes itself
+ * (sum rho h A / 3) and marks them as element nodes: they enter the bounding box behind dHat, eps_v and the tolerance and the mean nodal mass behind
+ * kappa -- a cloth-only scene sizes those from the cloth.  The surface triangles still come through ipcgpu_set_surface.  IPCGPU_ERR_ARG: a node id out of
+ * range, a triangle that repeats a node, zero rest area, an edge shared by more than two triangles, two triangles that traverse a shared edge in the
+ * same direction, a shell node that belongs to a tetrahedron, h, E, rho <= 0 or nu outside (-1, 1).  nTri == 0 removes the shell (no-op without one), a
+ * second call replaces it: the nodes of the old shell get back the masses they had before it (those of ipcgpu_set_codim_nodes, or 0).
+ * Sharded context (ipcgpu_ctx_set_shard, world > 1): IPCGPU_ERR_UNSUPPORTED.  ipcgpu_set_mesh drops the shell.
+ * With a shell set its terms enter the stepper and the building blocks (ipcgpu_assemble_newton, ipcgpu_incremental_potential, ipcgpu_gradient) wherever
+ * the tetrahedral elastic term does, with the same coefficient; ipcgpu_opt_system_report returns IPCGPU_ERR_UNSUPPORTED (its slices do not know the shell
+ * energy); ipcgpu_elastic_stress keeps its zeros for nodes without tetrahedra.  Without a shell no shell kernel is ever launched.
+ * ipcgpu_shell_get: counts2 = { nTri, nHinge }; hinge_4n hinge-major (x0, x1, x2, x3), ascending by (x0, x1) with x0 < x1, x2 opposite in the triangle
+ * that traverses x0 -> x1; restAngle, hingeWeight (w_e) per hinge; rest areas per triangle; mass_nV the shell's lumped masses (0 elsewhere).  Any pointer
+ * may be null.
+ * ipcgpu_shell_energy: coef * (membrane + bending) at the current positions; it uses the optimizer's reduction buffers, hence after ipcgpu_opt_init (before:
+ * IPCGPU_ERR_STATE).  The three entry points below need only the mesh and the shell (and the pattern, for the Hessian).  ipcgpu_shell_energy_per_elem: the
+ * unscaled terms.  Without a shell all of them return IPCGPU_OK and do nothing: the energy is 0, the per-element arrays have length 0, grad and the
+ * matrix stay as they are.
+ * ipcgpu_shell_gradient_add: grad (host, 3 nV, xyz interleaved) += coef * gradient; entries of projected Dirichlet nodes are dropped (type ZERO always,
+ * NONZERO with projectDBC).  ipcgpu_shell_hessian_add: the PSD blocks into the upper CSR values (after ipcgpu_linsys_set_pattern), rows and columns of
+ * projected Dirichlet nodes dropped; a block the pattern lacks: IPCGPU_ERR_STATE.  fp64 atomics: sums agree to rounding, not to the bit. */
+int ipcgpu_set_shell(ipcgpu_ctx*, int nTri, const int* tri_colmajor, const double* thickness_nTri, const double* YM_nTri, const double* PR_nTri,
+    const double* rho_nTri, double bendScale);
+int ipcgpu_shell_get(ipcgpu_ctx*, int* counts2, int* hinge_4n, double* restAngle, double* hingeWeight, double* area_nTri, double* mass_nV);
+int ipcgpu_shell_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_shell_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri, double* perHinge_nHinge);
+int ipcgpu_shell_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_shell_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

@@ -177,6 +177,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
     specChanged(c);
     return guarded([&] {
         needArg(c && world >= 1 && rank >= 0 && rank < world, "bad shard");
+        if (world > 1 && c->mesh->shell.nTri()) throw UnsupportedError("shells on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -929,6 +930,108 @@ int ipcgpu_set_codim_nodes(ipcgpu_ctx* c, int n, const int* ids, const double* m
         needArg(n >= 0 && ((ids && mass) || !n), "bad codimensional node list");
         need(!c->opt->initialised, "ipcgpu_set_codim_nodes must come before ipcgpu_opt_init (dHat and kappa derive from the mesh extent and mass)");
         m.setCodimNodes(n, ids, mass, c->stream);
+        return IPCGPU_OK;
+    });
+}
+// ---- Elastic shells -----------------------------------------------------------------------------------
+int ipcgpu_set_shell(ipcgpu_ctx* c, int nTri, const int* tri, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        needArg(nTri >= 0 && ((tri && thickness && YM && PR && rho) || !nTri), "bad shell arguments");
+        if (nTri == 0 && m.shell.nTri() == 0) return IPCGPU_OK; // nothing to remove
+        if (c->worldSize > 1) throw UnsupportedError("shells on a sharded context");
+        need(!c->opt->initialised, "ipcgpu_set_shell must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built");
+        m.setShell(nTri, tri, thickness, YM, PR, rho, bendScale, c->stream);
+        // a pattern built before this call lacks the opposite pairs of the hinges: it is rebuilt from the new vNeighbor (without extra pairs)
+        if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_get(ipcgpu_ctx* c, int* counts2, int* hinge, double* restAngle, double* hingeWeight, double* area, double* mass)
+{
+    return guarded([&] {
+        const ShellPlan& p = M(c).shell.plan;
+        if (counts2) {
+            counts2[0] = p.nTri;
+            counts2[1] = p.nHinge;
+        }
+        if (hinge) std::copy(p.hinge.begin(), p.hinge.end(), hinge);
+        if (restAngle) std::copy(p.restAngle.begin(), p.restAngle.end(), restAngle);
+        if (hingeWeight) std::copy(p.hingeWeight.begin(), p.hingeWeight.end(), hingeWeight);
+        if (area) std::copy(p.area.begin(), p.area.end(), area);
+        if (mass) {
+            std::fill(mass, mass + c->mesh->nV, 0.0);
+            std::copy(p.mass.begin(), p.mass.end(), mass);
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(E != nullptr, "null argument");
+        need(o.initialised, "call ipcgpu_opt_init first");
+        *E = 0.0;
+        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
+        launch_shell_energy(o.shellView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
+        *E = o.readScalar(o.d_scalar.p);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_energy_per_elem(ipcgpu_ctx* c, double* perTri, double* perHinge)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri()) return IPCGPU_OK;
+        DevBuf<double> t, h;
+        t.alloc(sh.nTri());
+        h.alloc(sh.nHinge());
+        launch_shell_energy_per_elem(o.shellView(c->mesh->d_x.p), perTri ? t.p : nullptr, perHinge ? h.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (perTri) t.download(perTri, sh.nTri(), c->stream);
+        if (perHinge) h.download(perHinge, sh.nHinge(), c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(g != nullptr, "null argument");
+        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
+        DevBuf<double> dg;
+        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
+        o.shellAssembleAdd(coef, projectDBC != 0, dg.p, nullptr);
+        HIP_CHECK(hipGetLastError());
+        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
+        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
+        o.shellAssembleAdd(coef, projectDBC != 0, nullptr, c->lin->d_a.p);
+        HIP_CHECK(hipGetLastError());
+        int err = 0;
+        c->mesh->shell.d_err.download(&err, 1, c->stream);
+        if (err) {
+            c->mesh->shell.d_err.zero(c->stream);
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            throw StateError("the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell");
+        }
         return IPCGPU_OK;
     });
 }
@@ -1718,6 +1821,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         HipOptimizer& o = O(c);
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
+        if (c->mesh->shell.nTri()) throw UnsupportedError("system report with a shell set (the report's slices do not know the shell energy)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

@@ -17,6 +17,8 @@
 #include "pcg.h"
 #include "pcg_coarse.h"
 #include "report_plan.h"
+#include "shell_kernels.h"
+#include "shell_plan.h"
 #include "stress_plan.h"
 #include <map>
 #include <memory>
@@ -27,6 +29,20 @@ typedef int (*ipcgpu_allreduce_fn_t)(void* user, void* buf_dev, long long count,
 typedef int (*ipcgpu_allreduce_stream_fn_t)(void* user, void* buf_dev, long long count, int op, void* hipStream);
 
 namespace ipcgpu {
+
+// Elastic shell of the mesh (ipcgpu_set_shell): the host plan and its device copy.  nTri() == 0: no shell, and then nothing below is ever read.
+struct HipShell {
+    ShellPlan plan;
+    double bendScale = 1.0;
+    // what the shell replaced, put back when it is removed or replaced: the masses its nodes had before (codimensional area masses, or 0) and avgEdgeLen
+    std::vector<double> massBefore;
+    double avgEdgeLenBefore = 0.0;
+    DevBuf<int> d_tri, d_err;
+    DevBuf<int4> d_hinge;
+    DevBuf<double> d_triConst, d_hingeConst;
+    int nTri() const { return plan.nTri; }
+    int nHinge() const { return plan.nHinge; }
+};
 
 class HipMesh {
 public:
@@ -52,6 +68,12 @@ public:
     std::vector<char> inMesh; // per node: referenced by an element (the components of codimension 3)
     void addSurfaceEdges(int nSF, const int* SF_colmajor, int nCE = 0, const int* CE_pairs = nullptr);
     void setCodimNodes(int n, const int* ids, const double* nodeMass, hipStream_t s);
+    // Elastic shell on triangle components (shell_plan.h): validates, sets the lumped masses of the shell nodes, marks them as element nodes (bounding box,
+    // mean nodal mass), adds the plan's node pairs to vNeighbor and uploads the constants.  nTri = 0 removes the shell, a second call replaces it: the nodes
+    // of the old shell get back the masses they had before it (ipcgpu_set_codim_nodes' or 0) and lose the mark; the neighbour pairs stay.  With no tetrahedron
+    // in the mesh avgEdgeLen is the mean side of the shell triangles while a shell is set.
+    HipShell shell;
+    void setShell(int nTri, const int* tri_colmajor, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s);
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -209,6 +231,12 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
+    // shell terms (shell_kernels.h): enter wherever the tetrahedral elastic term does, with the same coefficient; every call is guarded on mesh.shell.nTri()
+    ShellView shellView(const double* x_dev) const;
+    void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and, with a shell, its energy on top
+    void shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
+    // a mesh without tetrahedra has no patch plan: the node pass initialises the gradient / the matrix diagonal in its place (only with a shell set)
+    bool shellOnly() const { return mesh.nT == 0 && mesh.shell.nTri() > 0; }
 
     HipMesh& mesh;
     HipLinSysSolver& lin;

@@ -31,6 +31,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
 {
     if (nV_ <= 0 || nT_ < 0) throw ArgError("set_mesh: bad sizes");
     ++featuresVersion;
+    if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -141,6 +142,68 @@ void HipMesh::setCodimNodes(int n, const int* ids, const double* nodeMass, hipSt
     for (int i = 0; i < n; ++i) mass[ids[i]] = nodeMass[i];
     meshBBox();
     d_mass.upload(mass, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s)
+{
+    if (nTri == 0 && shell.nTri() == 0) return; // nothing to remove: no state changes at all
+    if (!(bendScale >= 0.0)) throw ArgError("set_shell: bendScale must not be negative");
+    ShellPlan plan;
+    std::string err;
+    if (!buildShellPlan(nV, nTri, tri, V_rest.data(), thickness, YM, PR, rho, nT, F.data(), plan, err)) throw ArgError(err);
+    if (shell.nTri()) { // the shell this call replaces or removes: its nodes go back to what they were
+        for (int v = 0; v < nV; ++v)
+            if (shell.plan.isShellNode[v]) {
+                mass[v] = shell.massBefore[v];
+                inMesh[v] = 0;
+            }
+        avgEdgeLen = shell.avgEdgeLenBefore;
+    }
+    shell.massBefore = mass;
+    shell.avgEdgeLenBefore = avgEdgeLen;
+    for (int v = 0; v < nV; ++v)
+        if (plan.isShellNode[v]) {
+            mass[v] = plan.mass[v];
+            inMesh[v] = 1;
+        }
+    meshBBox();
+    if (nT == 0 && nTri) avgEdgeLen = plan.edgeLenSum / (3.0 * nTri);
+    // the plan's pairs join vNeighbor: triangle edges (addSurfaceEdges adds the same ones) and the opposite pair of every hinge
+    std::vector<std::pair<int, int>> edges;
+    edges.reserve(nb.size() + plan.pairs.size());
+    for (int v = 0; v < nV; ++v)
+        for (int k = nbPtr[v]; k < nbPtr[v + 1]; ++k) edges.emplace_back(v, nb[k]);
+    for (size_t i = 0; i + 1 < plan.pairs.size(); i += 2) {
+        edges.emplace_back(plan.pairs[i], plan.pairs[i + 1]);
+        edges.emplace_back(plan.pairs[i + 1], plan.pairs[i]);
+    }
+    std::sort(edges.begin(), edges.end());
+    edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+    if (edges.size() != nb.size()) {
+        nbPtr.assign(nV + 1, 0);
+        for (auto& e : edges) nbPtr[e.first + 1]++;
+        for (int v = 0; v < nV; ++v) nbPtr[v + 1] += nbPtr[v];
+        nb.resize(edges.size());
+        for (size_t i = 0; i < edges.size(); ++i) nb[i] = edges[i].second;
+    }
+    shell.plan = std::move(plan);
+    shell.bendScale = bendScale;
+    const ShellPlan& p = shell.plan;
+    d_mass.upload(mass, s);
+    shell.d_tri.upload(p.tri, s);
+    shell.d_triConst.upload(p.triConst, s);
+    std::vector<int4> h4((size_t)p.nHinge);
+    std::vector<double> hc(2 * (size_t)p.nHinge);
+    for (int i = 0; i < p.nHinge; ++i) {
+        h4[i] = make_int4(p.hinge[4 * (size_t)i], p.hinge[4 * (size_t)i + 1], p.hinge[4 * (size_t)i + 2], p.hinge[4 * (size_t)i + 3]);
+        hc[i] = p.restAngle[i];
+        hc[(size_t)p.nHinge + i] = bendScale * p.hingeK[i] * p.hingeWeight[i];
+    }
+    shell.d_hinge.upload(h4.data(), h4.size(), s);
+    shell.d_hingeConst.upload(hc, s);
+    shell.d_err.alloc(1);
+    shell.d_err.zero(s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -71,6 +71,36 @@ ElemView HipOptimizer::view() const
     return v;
 }
 
+ShellView HipOptimizer::shellView(const double* x_dev) const
+{
+    const HipShell& sh = mesh.shell;
+    ShellView v;
+    v.nTri = sh.nTri();
+    v.nHinge = sh.nHinge();
+    v.tri = sh.d_tri.p;
+    v.triConst = sh.d_triConst.p;
+    v.hinge = sh.d_hinge.p;
+    v.hingeConst = sh.d_hingeConst.p;
+    v.x = x_dev;
+    v.dbc = mesh.d_dbc.p;
+    v.rowBase = lin.d_rowBase.p;
+    v.rowLen = lin.d_rowLen.p;
+    v.ja = lin.d_ja.p;
+    return v;
+}
+
+void HipOptimizer::enqueueElasticEnergy(bool ownerRank, double* out_dev)
+{
+    launch_energy(view(), elasticCoef(), true, ownerRank, d_partial.p, (int)d_partial.n, out_dev, stream);
+    if (mesh.shell.nTri()) launch_shell_energy(shellView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_shell)
+}
+
+void HipOptimizer::shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
+{
+    if (!mesh.shell.nTri()) return;
+    launch_shell_assemble(shellView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
+}
+
 void HipOptimizer::init(double dt_, bool withGravity)
 {
     dt = dt_;
@@ -92,7 +122,7 @@ void HipOptimizer::init(double dt_, bool withGravity)
     d_gradient.zero(stream);
     d_minusG.alloc(n3);
     d_x0.alloc(n3);
-    d_partial.alloc((size_t)std::max(mesh.nT, mesh.nV) / 256 + 2);
+    d_partial.alloc(std::max((size_t)std::max(mesh.nT, mesh.nV), (size_t)mesh.shell.nTri() + (size_t)mesh.shell.nHinge()) / 256 + 2);
     d_scalar.alloc(8);
     d_flag.alloc(2); // [0] the inversion flag of the stepper, [1] a second one for batches that test two states (beginTimestep)
     h_scalar.alloc(8);
@@ -297,7 +327,7 @@ double HipOptimizer::readScalar(const double* dev)
 
 double HipOptimizer::computeEnergyVal()
 {
-    launch_energy(view(), elasticCoef(), true, rank == 0, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
+    enqueueElasticEnergy(rank == 0, d_scalar.p);
     reduceSum(d_scalar.p, 1);
     // the barrier energy of the self-contact sets is enqueued behind the elastic one and read back with it: one synchronisation instead of two (round 6; the
     // reduction of the elastic partial sums is on the stream before the contact kernel reuses d_partial)
@@ -353,7 +383,9 @@ void HipOptimizer::assembleDampingMtr()
     v.xTilde = d_xDamp.p;
     v.mass = d_zeroMass.p; // the patch pass owns the diagonal: no mass here, and the identity of the projected rows is cleared below
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
+    if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
+    shellAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell Hessian at the damping positions
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -834,9 +866,10 @@ void HipOptimizer::barrierGradientAdd(bool projectDBC, double kappa_, bool activ
 
 void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
 {
-    if (lin.rowBase.empty()) { // no pattern yet: tet-parallel atomic path
+    if (lin.rowBase.empty() || shellOnly()) { // no pattern yet (or no tetrahedron, hence no patch plan): tet-parallel atomic path
         launch_node_init(view(), projectDBC, rank == 0, nullptr, d_gradient.p, stream);
         launch_assemble(view(), elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
+        shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
         reduceSum(d_gradient.p, 3LL * mesh.nV);
         neumannGradientAdd(d_gradient.p);
         return;
@@ -856,6 +889,7 @@ void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
     patchShard(pb, pe);
     if (worldSize > 1) d_gradient.zero(stream);
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
+    shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
     reduceSum(d_gradient.p, 3LL * mesh.nV);
     neumannGradientAdd(d_gradient.p);
 }
@@ -1018,8 +1052,13 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
         lin.setZero();
         if (withGradient) d_gradient.zero(stream);
     }
+    if (shellOnly()) { // no patch plan: the node pass writes mass / identity on a cleared matrix and the inertia term of the gradient
+        lin.setZero();
+        launch_node_init(view(), projectDBC, rank == 0, lin.d_a.p, withGradient ? d_gradient.p : nullptr, stream);
+    }
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p, stream,
         owner ? d_ownerPatches.p : nullptr);
+    shellAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
     matrixComplete = !owner;
     if (owner) {
         if (withGradient) ownerGradientTail(projectDBC);
@@ -1120,7 +1159,12 @@ void HipOptimizer::speculativeAssembly()
         resolveEventTimers(); // (the last timed assembly: finished long ago)
         HIP_CHECK(hipEventRecord(evAsm0, stream));
     }
+    if (shellOnly()) {
+        HIP_CHECK(hipMemsetAsync(d_aSpec.p, 0, sizeof(double) * lin.ja.size(), stream));
+        launch_node_init(view(), 1, true, d_aSpec.p, d_gradSpec.p, stream);
+    }
     launch_assemble_patches(view(), patch, 0, patch.nPatches, elasticCoef(), 1, d_gradSpec.p, d_aSpec.p, stream); // what computePrecondMtr(true, true) launches on this path
+    shellAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
     if (timeIt) {
         HIP_CHECK(hipEventRecord(evAsm1, stream));
         evAsmPending = true;
@@ -1160,10 +1204,10 @@ void HipOptimizer::computeSearchDir()
             launch_iter_reset(d_scalar.p, d_flag.p, stream); // (zeroes the slot of |p|_inf with the others: no enqueueDirNorm(), whose fill would be one launch more)
             launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
             if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
-            launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
+            enqueueElasticEnergy(true, d_scalar.p);
             launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, mesh.needElemInvSafeGuard(), d_scalar.p + 6, stream);
             if (mesh.needElemInvSafeGuard()) launch_check_inversion(view(), d_flag.p, stream);
-            launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p + 1, stream);
+            enqueueElasticEnergy(true, d_scalar.p + 1);
             launch_publish2(d_flag.p, h_flag.dev, 1, d_scalar.p, h_scalar.dev, 14, stream); // the inversion flag + 7 doubles
             // the ONE synchronisation waits for the read-back, not for the stream: behind it runs the next pass's assembly at the trial point, enqueued ahead
             if (!evTail) HIP_CHECK(hipEventCreateWithFlags(&evTail, hipEventDisableTiming));
@@ -1221,7 +1265,7 @@ void HipOptimizer::computeSearchDir()
         enqueueDirNorm();
         launch_fill(d_scalar.p + 2, 1, 1e20, stream);
         if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
-        launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
+        enqueueElasticEnergy(true, d_scalar.p);
         launch_publish(d_scalar.p, h_scalar.dev, 8, stream); // 4 doubles = 8 words
         HIP_CHECK(hipStreamSynchronize(stream));
         cachedE0 = h_scalar.p[0];
@@ -1306,7 +1350,7 @@ void HipOptimizer::lineSearch(double& stepSize)
                 launch_check_inversion(view(), d_flag.p, stream);
                 launch_publish(d_flag.p, h_flag.dev, 1, stream);
             }
-            launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream);
+            enqueueElasticEnergy(true, d_scalar.p);
             launch_publish(d_scalar.p, h_scalar.dev, 2, stream);
             HIP_CHECK(hipStreamSynchronize(stream));
             if (mesh.needElemInvSafeGuard()) inverted = h_flag.p[0];
@@ -1418,7 +1462,7 @@ void HipOptimizer::beginTimestep()
         if (guard) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // filterStepSize(p, 1.0) ...
         launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, guard, d_scalar.p + 6, stream); // ... applied by its rule; x0 = x, x += step p
         if (guard) launch_check_inversion(view(), d_flag.p + 1, stream);
-        launch_energy(view(), elasticCoef(), true, true, d_partial.p, (int)d_partial.n, d_scalar.p, stream); // computeEnergyVal() of this configuration: elasticity + inertia
+        enqueueElasticEnergy(true, d_scalar.p); // computeEnergyVal() of this configuration: elasticity + inertia
         launch_publish2(d_flag.p, h_flag.dev, 2, d_scalar.p, h_scalar.dev, 14, stream);
         HIP_CHECK(hipStreamSynchronize(stream));
         if (h_flag.p[0]) throw StateError("element inversion before scripted motion (Optimizer.cpp:517-522)");

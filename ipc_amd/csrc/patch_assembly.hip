@@ -315,7 +315,11 @@ void PatchPlan::build(const HipMesh& mesh, const HipLinSysSolver& lin, hipStream
             int fresh = 0;
             for (int k = vtPtr[v]; k < vtPtr[v + 1]; ++k)
                 if (mark[vt[k]] != pid) ++fresh;
-            if ((int)hNodes.size() > hNodePtr.back() && (int)curTets.size() + fresh > tetCap) closePatch();
+            // ... and at most NODE_CAP nodes: nodes without elements (a cloth, a codimensional surface) never fill the element budget, and a patch keeps
+            // 3 doubles of LDS per owned node (40 000 shell nodes in one patch asked for 1 MB).  A tetrahedral patch owns 40-60 nodes: the cap never binds there.
+            constexpr int NODE_CAP = 1024;
+            const int curNodes = (int)hNodes.size() - hNodePtr.back();
+            if (curNodes > 0 && ((int)curTets.size() + fresh > tetCap || curNodes >= NODE_CAP)) closePatch();
             for (int k = vtPtr[v]; k < vtPtr[v + 1]; ++k)
                 if (mark[vt[k]] != pid) {
                     mark[vt[k]] = pid;

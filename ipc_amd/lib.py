@@ -527,6 +527,46 @@ class Context:
         m = _f64(np.asarray(mass, dtype=np.float64))
         self._chk(self._L.ipcgpu_set_codim_nodes(self.h, C.c_int(len(ids)), _ip(ids), _dp(m)))
 
+    # ---- elastic shells (ipcgpu_set_shell: membrane + bending energy on triangle components)
+    def set_shell(self, tri, thickness, YM, PR, rho, bend_scale=1.0):
+        """tri: nTri x 3 node ids; thickness, YM, PR, rho: scalars or one value per triangle.  After set_mesh, before opt_init and set_pattern; sets the
+        masses of the shell nodes and marks them as element nodes.  An empty `tri` removes the shell."""
+        tri = np.asfortranarray(np.asarray(tri, dtype=np.int32).reshape(-1, 3))
+        n = tri.shape[0]
+        per = [_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))) for a in (thickness, YM, PR, rho)]
+        self._chk(self._L.ipcgpu_set_shell(self.h, C.c_int(n), _ip(tri), _dp(per[0]), _dp(per[1]), _dp(per[2]), _dp(per[3]), C.c_double(bend_scale)))
+
+    def shell_get(self):
+        """dict: nTri, nHinge, hinges (nHinge x 4: x0, x1 on the edge, x2, x3 opposite), restAngle, hingeWeight, area, mass (nV)"""
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_shell_get(self.h, _ip(cnt), None, None, None, None, None))
+        nTri, nH = int(cnt[0]), int(cnt[1])
+        hinges = np.zeros((nH, 4), dtype=np.int32)
+        rest, w, area, mass = np.zeros(nH), np.zeros(nH), np.zeros(nTri), np.zeros(self.nV)
+        self._chk(self._L.ipcgpu_shell_get(self.h, _ip(cnt), _ip(hinges), _dp(rest), _dp(w), _dp(area), _dp(mass)))
+        return {"nTri": nTri, "nHinge": nH, "hinges": hinges, "restAngle": rest, "hingeWeight": w, "area": area, "mass": mass}
+
+    def shell_energy(self, coef=1.0):
+        e = C.c_double()
+        self._chk(self._L.ipcgpu_shell_energy(self.h, C.c_double(coef), C.byref(e)))
+        return e.value
+
+    def shell_energy_per_elem(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_shell_get(self.h, _ip(cnt), None, None, None, None, None))
+        t, h = np.zeros(int(cnt[0])), np.zeros(int(cnt[1]))
+        self._chk(self._L.ipcgpu_shell_energy_per_elem(self.h, _dp(t), _dp(h)))
+        return t, h
+
+    def shell_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * shell gradient; returns it"""
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(self._L.ipcgpu_shell_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
+        return g
+
+    def shell_hessian_add(self, coef=1.0, projectDBC=True):
+        self._chk(self._L.ipcgpu_shell_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)
         self._chk(self._L.ipcgpu_set_obstacle_nodes(self.h, C.c_int(len(ids)), _ip(ids), C.c_int(int(obstacle_only))))

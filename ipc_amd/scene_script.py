@@ -50,6 +50,10 @@ class Shape:
     dbc: list = field(default_factory=list)  # (rel_min, rel_max, lin_vel, ang_vel_deg, t0, t1)
     nbc: list = field(default_factory=list)  # (rel_min, rel_max, acceleration, t0, t1)
     contact_group: int = 0  # `contactGroup g` (this project's keyword): the contact group of the component, see SceneConfig.contact_group_tables
+    # `shell <thickness> [bend <scale>]` (this project's keyword, triangle meshes only): the component is an elastic shell -- membrane and bending energy with
+    # the shape's `material` or the scene's density / stiffness (Context.set_shell) -- and may be free, partly held by `DBC` boxes or moved by the scripts
+    shell_thickness: float = None
+    shell_bend: float = 1.0
 
 
 @dataclass
@@ -370,6 +374,18 @@ def _parse_shape(st, resolve):
                 raise ValueError("contactGroup needs a group")
             sh.contact_group = _contact_group(st[j])
             j += 1
+        elif e == "shell":
+            if j >= len(st):
+                raise ValueError("shell needs a thickness")
+            sh.shell_thickness = float(st[j])
+            j += 1
+            if j < len(st) and st[j] == "bend":
+                if j + 1 >= len(st):
+                    raise ValueError("bend needs a scale")
+                sh.shell_bend = float(st[j + 1])
+                j += 2
+            if not sh.shell_thickness > 0.0 or not sh.shell_bend >= 0.0:
+                raise ValueError("shell needs a positive thickness and a bend scale >= 0")
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
             sh.init_vel = (tuple(v[:3]), tuple(v[3:]))
@@ -400,6 +416,8 @@ def _parse_shape(st, resolve):
             sh.nbc.append((v[0:3], v[3:6], v[6:9], t0, t1))
         else:
             raise UnsupportedKeyword(f"shape keyword {e}")
+    if sh.shell_thickness is not None and os.path.splitext(sh.path.lower())[1] != ".obj":
+        raise ValueError("shell is valid on a triangle-mesh shape only (not on a tetrahedral, segment or point shape)")
     return sh
 
 
@@ -517,6 +535,8 @@ class AssembledScene:
     mesh_i: int = 0  # AnimScripter::meshI: index of the next file of the sequences
     read_seq: object = None  # (folder, index, ext) -> positions; None = the files themselves (tests hand in a fixture's)
     motions: list = None  # rule-driven scripts: per Dirichlet group (lin, ang in degrees, fixed rotation centre or None), nodes NONZERO throughout
+    # the shapes that carry `shell`, as Context.set_shell takes them: {tri, thickness, YM, PR, rho (per triangle), bend (one scale for the scene)}, or None
+    shell: dict = None
 
     def before_step(self, be, t):
         """What AnimScripter::stepAnimScript decides from the state before a time step (call with the step's start time)."""
@@ -618,6 +638,7 @@ def assemble(cfg, read_mesh):
     codim = []  # (node ids, triangles, moved by its own keywords, segments) of the components of the mesh without tetrahedra
     CEs = []
     seqs = []  # mesh sequences: {ids, folder, ext}
+    shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
     for sh in cfg.shapes:
         ext = os.path.splitext(sh.path.lower())[1]
         is_codim = ext in (".obj", ".seg", ".pt")  # main.cpp:948-1005: kinematic surface / segments / points (componentCoDim 2 / 1 / 0)
@@ -659,9 +680,12 @@ def assemble(cfg, read_mesh):
             ids = np.arange(V.shape[0], dtype=np.int32) + off
             dirichlet.append((ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")))
             seqs.append({"ids": ids, "folder": sh.mesh_seq, "ext": ext})
-        if is_codim:
+        if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
+            mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
+            shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat))
+        if is_codim:  # (an elastic shell needs nobody to hold it: it counts as moved)
             codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
-                          sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None, E + off))
+                          sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None or sh.shell_thickness is not None, E + off))
         CEs.append(E + off)
         Vs.append(V)
         Ts.append(T + off)
@@ -1071,6 +1095,12 @@ def assemble(cfg, read_mesh):
     sc = AssembledScene(cfg, V, T, SF, nr, tr, dirichlet, vel, neumann, obst, release, codim_nodes, codim_mass, codim_fixed, V0)
     sc.motions = motions
     sc.codim_edges = codim_edges
+    if shells:
+        if len({b for _t, _h, b, _m in shells}) > 1:
+            raise ValueError("one bend scale per scene: the shell shapes give different ones")
+        per = lambda k: np.concatenate([np.full(len(t), float(m[k])) for t, _h, _b, m in shells])  # noqa: E731
+        sc.shell = {"tri": np.vstack([t for t, *_ in shells]).astype(np.int32), "thickness": np.concatenate([np.full(len(t), float(h)) for t, h, *_ in shells]),
+                    "rho": per(0), "YM": per(1), "PR": per(2), "bend": float(shells[0][2])}
     for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = seqs
@@ -1092,9 +1122,14 @@ def apply(sc, be):
         be.set_contact_groups(groups[0], groups[1], groups[2])
     if sc.codim_nodes is not None:
         be.set_codim_nodes(sc.codim_nodes, sc.codim_mass)
+    if sc.shell is not None:  # after set_codim_nodes (it replaces the area masses of its nodes), before opt_init and the pattern
+        q = sc.shell
+        be.set_shell(q["tri"], q["thickness"], q["YM"], q["PR"], q["rho"], q["bend"])
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
-        if sh.material is not None and all(np.isfinite(sh.material)):
+        # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density
+        # once more, and it has no tetrahedra whose Lame parameters it could set)
+        if sh.material is not None and all(np.isfinite(sh.material)) and sh.shell_thickness is None:
             be.set_component_material((sc.node_ranges[s], sc.node_ranges[s + 1]), (sc.tet_ranges[s], sc.tet_ranges[s + 1]), *sh.material)
     if sc.V0 is not None:
         be.set_positions(sc.V0)

@@ -371,6 +371,41 @@ int ipcgpu_shell_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_shell_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri, double* perHinge_nHinge);
 int ipcgpu_shell_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_shell_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+/* Elastic rods (no counterpart in the reference): stretching and bending energy on segment components.
+ *   stretching  per segment (a, b): rest length L, length l, radius r, Young's modulus E, A = pi r^2, k_s = E A / L, W_s = k_s (l - L)^2 / 2.  Exact gradient.
+ *               With t = (x_b - x_a) / l the 3 x 3 block is B = k_s [t t^T + max(0, 1 - L / l) (I - t t^T)], the 6 x 6 Hessian [[B, -B], [-B, B]]: the clamp
+ *               at 0 is the exact eigenvalue projection of the full Hessian (spectrum 2 k_s, 2 k_s (1 - L / l) twice, 0 three times).
+ *   bending     per interior node b (exactly two incident segments (a, b), (b, c)): e0 = x_b - x_a, e1 = x_c - x_b, kb = 2 e0 x e1 / d,
+ *               d = |e0||e1| + e0 . e1, W_b = bendScale k_b |kb|^2, k_b = E_m I / (L0 + L1), I = pi r_m^4 / 4 (means of the two segments): the bending term of
+ *               discrete elastic rods without twist (|kb| = 2 tan(theta / 2)), with a STRAIGHT rest state.  Exact gradient 2 bendScale k_b J^T kb,
+ *               J = d kb / d (x_a, x_b, x_c); Gauss-Newton Hessian 2 bendScale k_b J^T J (rank <= 3, PSD).  W_b grows without bound as the node folds flat
+ *               (d -> 0), which keeps two adjacent segments -- they share a node and form no contact pair -- from folding onto each other; where d <= 0 in
+ *               floating point the energy is +infinity, never NaN, and the line search backtracks.
+ * Not modelled: twist and material frames; rest curvature (ipcgpu_rod_get returns the rest |kb| per interior node: a curved rest polyline will be pulled
+ * straight; bendScale = 0 switches bending off); bending at junctions (a node with three or more segments carries stretching only); a thickness offset in
+ * contact (the gap stays dHat around the centre line).
+ * ipcgpu_set_rod: seg_colmajor nSeg x 2 node ids; radius, E, rho per segment; bendScale >= 0.  After ipcgpu_set_mesh, before ipcgpu_opt_init (else
+ * IPCGPU_ERR_STATE) and before ipcgpu_linsys_set_pattern: the node pairs of the rod (segments and the outer pair (a, c) of every bending triple) join
+ * vNeighbor (a node pattern that exists already is rebuilt by this call, without extra pairs).  It sets the lumped masses of the rod nodes itself (sum
+ * rho pi r^2 L / 2) and marks them as element nodes, as ipcgpu_set_shell does for shell nodes.  Collision still needs the segments passed to
+ * ipcgpu_set_surface (its CE list): this call gives them elasticity, not contact.  IPCGPU_ERR_ARG: a node id out of range, a segment with a == b, a repeated
+ * segment (in either direction), zero rest length, a rod node that belongs to a tetrahedron or to a shell triangle, radius, E or rho <= 0 (and ipcgpu_set_shell
+ * refuses a shell node that belongs to a rod segment).  nSeg == 0 removes
+ * the rod (no-op without one), a second call replaces it: the nodes of the old rod get back the masses they had before it.  Sharded context:
+ * IPCGPU_ERR_UNSUPPORTED.  ipcgpu_set_mesh drops the rod.
+ * With a rod set its terms enter the stepper and the building blocks wherever the shell and the tetrahedral elastic terms do, with the same coefficient;
+ * ipcgpu_opt_system_report returns IPCGPU_ERR_UNSUPPORTED; ipcgpu_elastic_stress keeps its zeros for rod nodes.  Without a rod no rod kernel is ever launched.
+ * ipcgpu_rod_get: counts2 = { nSeg, nBend }; bend_3n triple-major (a, b, c), ascending by b; rest lengths and k_s per segment; k_b (without bendScale) and
+ * the rest |kb| per triple; mass_nV the rod's lumped masses (0 elsewhere).  Any pointer may be null.
+ * ipcgpu_rod_energy / _energy_per_elem / _gradient_add / _hessian_add: the semantics of their ipcgpu_shell_* namesakes (the energy after ipcgpu_opt_init;
+ * per-element terms unscaled; projected Dirichlet entries dropped; a block the pattern lacks: IPCGPU_ERR_STATE; fp64 atomics).  Without a rod all of them
+ * return IPCGPU_OK and do nothing. */
+int ipcgpu_set_rod(ipcgpu_ctx*, int nSeg, const int* seg_colmajor, const double* radius_nSeg, const double* YM_nSeg, const double* rho_nSeg, double bendScale);
+int ipcgpu_rod_get(ipcgpu_ctx*, int* counts2, int* bend_3n, double* restLen_nSeg, double* ks_nSeg, double* kb_nBend, double* restKb_nBend, double* mass_nV);
+int ipcgpu_rod_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_rod_energy_per_elem(ipcgpu_ctx*, double* perSeg_nSeg, double* perBend_nBend);
+int ipcgpu_rod_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_rod_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

@@ -178,6 +178,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
     return guarded([&] {
         needArg(c && world >= 1 && rank >= 0 && rank < world, "bad shard");
         if (world > 1 && c->mesh->shell.nTri()) throw UnsupportedError("shells on a sharded context");
+        if (world > 1 && c->mesh->rod.nSeg()) throw UnsupportedError("rods on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -1035,6 +1036,110 @@ int ipcgpu_shell_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
         return IPCGPU_OK;
     });
 }
+// ---- Elastic rods -------------------------------------------------------------------------------------
+int ipcgpu_set_rod(ipcgpu_ctx* c, int nSeg, const int* seg, const double* radius, const double* YM, const double* rho, double bendScale)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        needArg(nSeg >= 0 && ((seg && radius && YM && rho) || !nSeg), "bad rod arguments");
+        if (nSeg == 0 && m.rod.nSeg() == 0) return IPCGPU_OK; // nothing to remove
+        if (c->worldSize > 1) throw UnsupportedError("rods on a sharded context");
+        need(!c->opt->initialised, "ipcgpu_set_rod must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built");
+        m.setRod(nSeg, seg, radius, YM, rho, bendScale, c->stream);
+        // a pattern built before this call lacks the outer pairs of the bending triples: it is rebuilt from the new vNeighbor (without extra pairs)
+        if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_rod_get(ipcgpu_ctx* c, int* counts2, int* bend, double* restLen, double* ks, double* kb, double* restKb, double* mass)
+{
+    return guarded([&] {
+        const RodPlan& p = M(c).rod.plan;
+        if (counts2) {
+            counts2[0] = p.nSeg;
+            counts2[1] = p.nBend;
+        }
+        if (bend) std::copy(p.bend.begin(), p.bend.end(), bend);
+        if (restLen) std::copy(p.segConst.begin(), p.segConst.begin() + p.nSeg, restLen);
+        if (ks) std::copy(p.segConst.begin() + p.nSeg, p.segConst.end(), ks);
+        if (kb) std::copy(p.bendK.begin(), p.bendK.end(), kb);
+        if (restKb) std::copy(p.restKb.begin(), p.restKb.end(), restKb);
+        if (mass) {
+            std::fill(mass, mass + c->mesh->nV, 0.0);
+            std::copy(p.mass.begin(), p.mass.end(), mass);
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_rod_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(E != nullptr, "null argument");
+        need(o.initialised, "call ipcgpu_opt_init first");
+        *E = 0.0;
+        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
+        launch_rod_energy(o.rodView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
+        *E = o.readScalar(o.d_scalar.p);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_rod_energy_per_elem(ipcgpu_ctx* c, double* perSeg, double* perBend)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipRod& r = c->mesh->rod;
+        if (!r.nSeg()) return IPCGPU_OK;
+        DevBuf<double> t, h;
+        t.alloc(r.nSeg());
+        h.alloc(r.nBend());
+        h.zero(c->stream); // (with `bend 0` no triple is evaluated: its terms are 0)
+        launch_rod_energy_per_elem(o.rodView(c->mesh->d_x.p), perSeg ? t.p : nullptr, perBend ? h.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (perSeg) t.download(perSeg, r.nSeg(), c->stream);
+        if (perBend) h.download(perBend, r.nBend(), c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_rod_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(g != nullptr, "null argument");
+        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
+        DevBuf<double> dg;
+        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
+        o.rodAssembleAdd(coef, projectDBC != 0, dg.p, nullptr);
+        HIP_CHECK(hipGetLastError());
+        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_rod_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
+        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
+        o.rodAssembleAdd(coef, projectDBC != 0, nullptr, c->lin->d_a.p);
+        HIP_CHECK(hipGetLastError());
+        int err = 0;
+        c->mesh->rod.d_err.download(&err, 1, c->stream);
+        if (err) {
+            c->mesh->rod.d_err.zero(c->stream);
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            throw StateError("the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod");
+        }
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {
     specChanged(c);
@@ -1822,6 +1927,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
         if (c->mesh->shell.nTri()) throw UnsupportedError("system report with a shell set (the report's slices do not know the shell energy)");
+        if (c->mesh->rod.nSeg()) throw UnsupportedError("system report with a rod set (the report's slices do not know the rod energy)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

@@ -17,6 +17,8 @@
 #include "pcg.h"
 #include "pcg_coarse.h"
 #include "report_plan.h"
+#include "rod_kernels.h"
+#include "rod_plan.h"
 #include "shell_kernels.h"
 #include "shell_plan.h"
 #include "stress_plan.h"
@@ -42,6 +44,22 @@ struct HipShell {
     DevBuf<double> d_triConst, d_hingeConst;
     int nTri() const { return plan.nTri; }
     int nHinge() const { return plan.nHinge; }
+};
+
+// Elastic rod of the mesh (ipcgpu_set_rod): the host plan and its device copy.  nSeg() == 0: no rod, and then nothing below is ever read.
+struct HipRod {
+    RodPlan plan;
+    double bendScale = 1.0;
+    // what the rod replaced, put back when it is removed or replaced: the masses its nodes had before (the reference's segment masses, or 0) and avgEdgeLen
+    std::vector<double> massBefore;
+    double avgEdgeLenBefore = 0.0;
+    bool ownsAvgEdgeLen = false;
+    DevBuf<int2> d_seg;
+    DevBuf<int> d_bend, d_err;
+    DevBuf<double> d_segConst, d_bendConst;
+    int nSeg() const { return plan.nSeg; }
+    int nBend() const { return plan.nBend; }
+    int nBendActive() const { return bendScale > 0.0 ? plan.nBend : 0; } // `bend 0` switches bending off: no triple reaches the kernels
 };
 
 class HipMesh {
@@ -74,6 +92,13 @@ public:
     // in the mesh avgEdgeLen is the mean side of the shell triangles while a shell is set.
     HipShell shell;
     void setShell(int nTri, const int* tri_colmajor, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s);
+    // Elastic rod on segment components (rod_plan.h): as setShell -- validates, sets the lumped masses of the rod nodes, marks them as element nodes, adds
+    // the plan's node pairs to vNeighbor and uploads the constants.  nSeg = 0 removes the rod, a second call replaces it: the nodes of the old rod get back
+    // the masses they had before it and lose the mark; the neighbour pairs stay.  With neither a tetrahedron nor a shell in the mesh avgEdgeLen is the mean
+    // rest length of the segments while a rod is set.  A rod node may belong to no tetrahedron and no shell triangle (setShell checks the converse).
+    HipRod rod;
+    void addNeighbourPairs(const std::vector<int>& pairs); // (lo, hi) pairs into vNeighbor, both directions, sorted and unique
+    void setRod(int nSeg, const int* seg_colmajor, const double* radius, const double* YM, const double* rho, double bendScale, hipStream_t s);
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -233,10 +258,14 @@ public:
     ElemView view() const;
     // shell terms (shell_kernels.h): enter wherever the tetrahedral elastic term does, with the same coefficient; every call is guarded on mesh.shell.nTri()
     ShellView shellView(const double* x_dev) const;
-    void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and, with a shell, its energy on top
+    void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and, with a shell or a rod, their energies on top
     void shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
-    // a mesh without tetrahedra has no patch plan: the node pass initialises the gradient / the matrix diagonal in its place (only with a shell set)
-    bool shellOnly() const { return mesh.nT == 0 && mesh.shell.nTri() > 0; }
+    // rod terms (rod_kernels.h): enter wherever the shell terms do, with the same coefficient; every call is guarded on mesh.rod.nSeg()
+    RodView rodView(const double* x_dev) const;
+    void rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
+    // a mesh without tetrahedra has no patch plan: the node pass initialises the gradient / the matrix diagonal in its place (only with a shell or a rod
+    // set: shells only, rods only, or both)
+    bool shellOnly() const { return mesh.nT == 0 && (mesh.shell.nTri() > 0 || mesh.rod.nSeg() > 0); }
 
     HipMesh& mesh;
     HipLinSysSolver& lin;

@@ -32,6 +32,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (nV_ <= 0 || nT_ < 0) throw ArgError("set_mesh: bad sizes");
     ++featuresVersion;
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
+    if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -145,6 +146,27 @@ void HipMesh::setCodimNodes(int n, const int* ids, const double* nodeMass, hipSt
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
+void HipMesh::addNeighbourPairs(const std::vector<int>& pairs)
+{
+    std::vector<std::pair<int, int>> edges;
+    edges.reserve(nb.size() + pairs.size());
+    for (int v = 0; v < nV; ++v)
+        for (int k = nbPtr[v]; k < nbPtr[v + 1]; ++k) edges.emplace_back(v, nb[k]);
+    for (size_t i = 0; i + 1 < pairs.size(); i += 2) {
+        edges.emplace_back(pairs[i], pairs[i + 1]);
+        edges.emplace_back(pairs[i + 1], pairs[i]);
+    }
+    std::sort(edges.begin(), edges.end());
+    edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+    if (edges.size() != nb.size()) {
+        nbPtr.assign(nV + 1, 0);
+        for (auto& e : edges) nbPtr[e.first + 1]++;
+        for (int v = 0; v < nV; ++v) nbPtr[v + 1] += nbPtr[v];
+        nb.resize(edges.size());
+        for (size_t i = 0; i < edges.size(); ++i) nb[i] = edges[i].second;
+    }
+}
+
 void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s)
 {
     if (nTri == 0 && shell.nTri() == 0) return; // nothing to remove: no state changes at all
@@ -152,6 +174,9 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     ShellPlan plan;
     std::string err;
     if (!buildShellPlan(nV, nTri, tri, V_rest.data(), thickness, YM, PR, rho, nT, F.data(), plan, err)) throw ArgError(err);
+    if (rod.nSeg())
+        for (int v = 0; v < nV; ++v)
+            if (plan.isShellNode[v] && rod.plan.isRodNode[v]) throw ArgError("set_shell: shell node " + std::to_string(v) + " belongs to a rod segment");
     if (shell.nTri()) { // the shell this call replaces or removes: its nodes go back to what they were
         for (int v = 0; v < nV; ++v)
             if (shell.plan.isShellNode[v]) {
@@ -170,23 +195,7 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     meshBBox();
     if (nT == 0 && nTri) avgEdgeLen = plan.edgeLenSum / (3.0 * nTri);
     // the plan's pairs join vNeighbor: triangle edges (addSurfaceEdges adds the same ones) and the opposite pair of every hinge
-    std::vector<std::pair<int, int>> edges;
-    edges.reserve(nb.size() + plan.pairs.size());
-    for (int v = 0; v < nV; ++v)
-        for (int k = nbPtr[v]; k < nbPtr[v + 1]; ++k) edges.emplace_back(v, nb[k]);
-    for (size_t i = 0; i + 1 < plan.pairs.size(); i += 2) {
-        edges.emplace_back(plan.pairs[i], plan.pairs[i + 1]);
-        edges.emplace_back(plan.pairs[i + 1], plan.pairs[i]);
-    }
-    std::sort(edges.begin(), edges.end());
-    edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
-    if (edges.size() != nb.size()) {
-        nbPtr.assign(nV + 1, 0);
-        for (auto& e : edges) nbPtr[e.first + 1]++;
-        for (int v = 0; v < nV; ++v) nbPtr[v + 1] += nbPtr[v];
-        nb.resize(edges.size());
-        for (size_t i = 0; i < edges.size(); ++i) nb[i] = edges[i].second;
-    }
+    addNeighbourPairs(plan.pairs);
     shell.plan = std::move(plan);
     shell.bendScale = bendScale;
     const ShellPlan& p = shell.plan;
@@ -204,6 +213,58 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     shell.d_hingeConst.upload(hc, s);
     shell.d_err.alloc(1);
     shell.d_err.zero(s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setRod(int nSeg, const int* seg, const double* radius, const double* YM, const double* rho, double bendScale, hipStream_t s)
+{
+    if (nSeg == 0 && rod.nSeg() == 0) return; // nothing to remove: no state changes at all
+    if (!(bendScale >= 0.0)) throw ArgError("set_rod: bendScale must not be negative");
+    RodPlan plan;
+    std::string err;
+    if (!buildRodPlan(nV, nSeg, seg, V_rest.data(), radius, YM, rho, nT, F.data(), shell.nTri(), shell.plan.tri.data(), plan, err)) throw ArgError(err);
+    if (rod.nSeg()) { // the rod this call replaces or removes: its nodes go back to what they were
+        for (int v = 0; v < nV; ++v)
+            if (rod.plan.isRodNode[v]) {
+                mass[v] = rod.massBefore[v];
+                inMesh[v] = 0;
+            }
+        if (rod.ownsAvgEdgeLen) {
+            // (a shell set after this rod took the rod's mean length for the value to put back: it gets the one from before the rod)
+            if (shell.nTri()) shell.avgEdgeLenBefore = rod.avgEdgeLenBefore;
+            else avgEdgeLen = rod.avgEdgeLenBefore;
+        }
+    }
+    rod.massBefore = mass;
+    rod.avgEdgeLenBefore = avgEdgeLen;
+    for (int v = 0; v < nV; ++v)
+        if (plan.isRodNode[v]) {
+            mass[v] = plan.mass[v];
+            inMesh[v] = 1;
+        }
+    meshBBox();
+    rod.ownsAvgEdgeLen = nT == 0 && shell.nTri() == 0 && nSeg > 0;
+    if (rod.ownsAvgEdgeLen) avgEdgeLen = plan.lenSum / nSeg;
+    // the plan's pairs join vNeighbor: the segments (addSurfaceEdges adds the same ones) and the outer pair (a, c) of every bending triple
+    addNeighbourPairs(plan.pairs);
+    rod.plan = std::move(plan);
+    rod.bendScale = bendScale;
+    const RodPlan& p = rod.plan;
+    d_mass.upload(mass, s);
+    std::vector<int2> s2((size_t)p.nSeg);
+    for (int i = 0; i < p.nSeg; ++i) s2[i] = make_int2(p.seg[2 * (size_t)i], p.seg[2 * (size_t)i + 1]);
+    rod.d_seg.upload(s2.data(), s2.size(), s);
+    rod.d_segConst.upload(p.segConst, s);
+    std::vector<int> b3(3 * (size_t)p.nBend);
+    std::vector<double> bc((size_t)p.nBend);
+    for (int i = 0; i < p.nBend; ++i) {
+        for (int k = 0; k < 3; ++k) b3[(size_t)k * p.nBend + i] = p.bend[3 * (size_t)i + k];
+        bc[i] = bendScale * p.bendK[i];
+    }
+    rod.d_bend.upload(b3, s);
+    rod.d_bendConst.upload(bc, s);
+    rod.d_err.alloc(1);
+    rod.d_err.zero(s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -89,16 +89,41 @@ ShellView HipOptimizer::shellView(const double* x_dev) const
     return v;
 }
 
+RodView HipOptimizer::rodView(const double* x_dev) const
+{
+    const HipRod& r = mesh.rod;
+    RodView v;
+    v.nSeg = r.nSeg();
+    v.nBend = r.nBendActive();
+    v.seg = r.d_seg.p;
+    v.segConst = r.d_segConst.p;
+    v.bend = r.d_bend.p;
+    v.bendConst = r.d_bendConst.p;
+    v.x = x_dev;
+    v.dbc = mesh.d_dbc.p;
+    v.rowBase = lin.d_rowBase.p;
+    v.rowLen = lin.d_rowLen.p;
+    v.ja = lin.d_ja.p;
+    return v;
+}
+
 void HipOptimizer::enqueueElasticEnergy(bool ownerRank, double* out_dev)
 {
     launch_energy(view(), elasticCoef(), true, ownerRank, d_partial.p, (int)d_partial.n, out_dev, stream);
     if (mesh.shell.nTri()) launch_shell_energy(shellView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_shell)
+    if (mesh.rod.nSeg()) launch_rod_energy(rodView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_rod)
 }
 
 void HipOptimizer::shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
 {
     if (!mesh.shell.nTri()) return;
     launch_shell_assemble(shellView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
+}
+
+void HipOptimizer::rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
+{
+    if (!mesh.rod.nSeg()) return;
+    launch_rod_assemble(rodView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.rod.d_err.p, stream);
 }
 
 void HipOptimizer::init(double dt_, bool withGravity)
@@ -122,7 +147,8 @@ void HipOptimizer::init(double dt_, bool withGravity)
     d_gradient.zero(stream);
     d_minusG.alloc(n3);
     d_x0.alloc(n3);
-    d_partial.alloc(std::max((size_t)std::max(mesh.nT, mesh.nV), (size_t)mesh.shell.nTri() + (size_t)mesh.shell.nHinge()) / 256 + 2);
+    d_partial.alloc(std::max({ (size_t)std::max(mesh.nT, mesh.nV), (size_t)mesh.shell.nTri() + (size_t)mesh.shell.nHinge(),
+                        (size_t)mesh.rod.nSeg() + (size_t)mesh.rod.nBend() }) / 256 + 2);
     d_scalar.alloc(8);
     d_flag.alloc(2); // [0] the inversion flag of the stepper, [1] a second one for batches that test two states (beginTimestep)
     h_scalar.alloc(8);
@@ -386,6 +412,7 @@ void HipOptimizer::assembleDampingMtr()
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
     shellAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell Hessian at the damping positions
+    rodAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // ... and the rod Hessian
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -870,6 +897,7 @@ void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
         launch_node_init(view(), projectDBC, rank == 0, nullptr, d_gradient.p, stream);
         launch_assemble(view(), elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
         shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
+        rodAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
         reduceSum(d_gradient.p, 3LL * mesh.nV);
         neumannGradientAdd(d_gradient.p);
         return;
@@ -890,6 +918,7 @@ void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
     if (worldSize > 1) d_gradient.zero(stream);
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
     shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
+    rodAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
     reduceSum(d_gradient.p, 3LL * mesh.nV);
     neumannGradientAdd(d_gradient.p);
 }
@@ -1059,6 +1088,7 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p, stream,
         owner ? d_ownerPatches.p : nullptr);
     shellAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
+    rodAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
     matrixComplete = !owner;
     if (owner) {
         if (withGradient) ownerGradientTail(projectDBC);
@@ -1165,6 +1195,7 @@ void HipOptimizer::speculativeAssembly()
     }
     launch_assemble_patches(view(), patch, 0, patch.nPatches, elasticCoef(), 1, d_gradSpec.p, d_aSpec.p, stream); // what computePrecondMtr(true, true) launches on this path
     shellAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
+    rodAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
     if (timeIt) {
         HIP_CHECK(hipEventRecord(evAsm1, stream));
         evAsmPending = true;
@@ -1326,6 +1357,8 @@ void HipOptimizer::lineSearch(double& stepSize)
         // the first trial came back with the solve (computeSearchDir): d_x0 holds the iterate, x the trial point
         cachedTrialValid = cachedE0Valid = false;
         lastEnergyVal = cachedE0; // Optimizer.cpp:2681
+        // (a +infinity trial energy -- a rod node folded flat, rod_kernels.h -- is greater than every finite one: rejected here, in the branch below and in
+        // the halving loop, which backtracks it like any increase.  The rod kernels return +infinity, never NaN, which `!(NaN > E)` would accept.)
         if (!cachedTrialInverted && !(cachedTrialE > lastEnergyVal)) {
             lastEnergyVal = cachedTrialE;
             return;
@@ -1390,7 +1423,7 @@ void HipOptimizer::lineSearch(double& stepSize)
         testingE = computeEnergyVal();
     }
     const double LFStepSize = stepSize;
-    while (testingE > lastEnergyVal && stepSize > 0.0) { // Optimizer.cpp:2761-2797
+    while (testingE > lastEnergyVal && stepSize > 0.0) { // Optimizer.cpp:2761-2797 (+infinity > finite: an infinite trial energy is halved away too)
         stepSize /= 2.0;
         if (stepSize == 0.0) break;
         {

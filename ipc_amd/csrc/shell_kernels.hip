@@ -5,6 +5,7 @@
 // Launch bounds differ on purpose: the membrane kernel with Hessian needs 137 VGPRs for the iterate and its rotations (64-lane workgroups so that the
 // compiler may take them: three waves per SIMD, no scratch); the other two are small (63 .. 92 VGPRs) and run 256 wide.  Figures: DESIGN.md.
 #include "shell_kernels.h"
+#include "csr_scatter_device.h"
 #include "stencil_hessian_device.h"
 #include <algorithm>
 
@@ -16,14 +17,7 @@ constexpr int ENERGY_BLOCK = 256;
 constexpr int MEMBRANE_BLOCK = 64;
 constexpr int HINGE_BLOCK = 256;
 
-__device__ __forceinline__ bool projected_dbc(int type, int projectDBC) { return type == 1 || (type == 2 && projectDBC); }
-
-__device__ __forceinline__ void ld3(const double* __restrict__ x, int v, double* p)
-{
-    p[0] = x[3 * (size_t)v];
-    p[1] = x[3 * (size_t)v + 1];
-    p[2] = x[3 * (size_t)v + 2];
-}
+using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, block_sum (csr_scatter_device.h)
 
 // ---- membrane ----------------------------------------------------------------------------------------------------------------------------
 struct Membrane {
@@ -101,50 +95,6 @@ __device__ __forceinline__ double hinge_angle(const double* x0, const double* x1
     return theta;
 }
 
-// ---- scatter into the upper CSR (block rows of LinSysSolver.hpp:63-111: row 3 v has rowLen entries, 3 v + 1 one less, 3 v + 2 two less) -----------------------
-struct CsrSink {
-    const int* rowBase;
-    const int* rowLen;
-    const int* ja;
-    double* a;
-    int* err;
-};
-// upper triangle of the diagonal block of node n; A[r + 3 c]
-__device__ __forceinline__ void add_diag(const CsrSink& k, int n, const double* A)
-{
-    const int base = k.rowBase[n], Lr = k.rowLen[n];
-    atomicAdd(&k.a[base + 0], A[0]);
-    atomicAdd(&k.a[base + 1], A[3]);
-    atomicAdd(&k.a[base + 2], A[6]);
-    atomicAdd(&k.a[base + Lr + 0], A[4]);
-    atomicAdd(&k.a[base + Lr + 1], A[7]);
-    atomicAdd(&k.a[base + 2 * Lr - 1], A[8]);
-}
-// block with rows of node nk and columns of node nl (nk != nl); A[r + 3 c].  The upper CSR holds (min, max): transposed when nl comes first.
-__device__ __forceinline__ void add_off(const CsrSink& k, int nk, int nl, const double* A)
-{
-    const bool swap = nk > nl;
-    const int rn = swap ? nl : nk, cn = swap ? nk : nl;
-    const int base = k.rowBase[rn], Lr = k.rowLen[rn];
-    int lo = base + 3, hi = base + Lr; // neighbour blocks start behind the 3 diagonal-block entries
-    const int end = hi, target = 3 * cn;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (k.ja[mid] < target) lo = mid + 1;
-        else hi = mid;
-    }
-    if (!(lo < end && k.ja[lo] == target)) {
-        atomicOr(k.err, 1); // the pattern lacks this pair: ipcgpu_set_shell must come before the pattern is built
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int p = lo + (r == 0 ? 0 : (r == 1 ? Lr - 1 : 2 * Lr - 3));
-#pragma unroll
-        for (int c = 0; c < 3; ++c) atomicAdd(&k.a[p + c], swap ? A[c + 3 * r] : A[r + 3 * c]);
-    }
-}
-
 template <int K, int L>
 __device__ __forceinline__ void emit_membrane_pair(const CsrSink& k, const double* C, const int* node, const bool* proj)
 {
@@ -153,21 +103,6 @@ __device__ __forceinline__ void emit_membrane_pair(const CsrSink& k, const doubl
     sh::pair_block<2, K, L, 6>(C, A);
     if constexpr (K == L) add_diag(k, node[K], A);
     else add_off(k, node[K], node[L], A);
-}
-
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-    // fixed-order tree: deterministic
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < ENERGY_BLOCK / 64; ++i) r += sm[i];
-    }
-    return r;
 }
 
 __device__ __forceinline__ double triangle_energy(const ShellView& v, int t)
@@ -199,16 +134,8 @@ __global__ __launch_bounds__(ENERGY_BLOCK) void k_shell_energy(ShellView v, doub
     double e = 0.0;
     if (gid < v.nTri) e = coef * triangle_energy(v, gid);
     else if (gid - v.nTri < v.nHinge) e = coef * hinge_energy(v, gid - v.nTri);
-    const double r = block_sum(e, sm);
+    const double r = block_sum<ENERGY_BLOCK>(e, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-__global__ __launch_bounds__(ENERGY_BLOCK) void k_shell_reduce(const double* __restrict__ partial, int n, int accumulate, double* __restrict__ out)
-{
-    __shared__ double sm[ENERGY_BLOCK / 64];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += ENERGY_BLOCK) x += partial[i];
-    const double r = block_sum(x, sm);
-    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + r : r;
 }
 __global__ __launch_bounds__(ENERGY_BLOCK) void k_shell_energy_per_elem(ShellView v, double* __restrict__ perTri, double* __restrict__ perHinge)
 {
@@ -338,7 +265,7 @@ void launch_shell_energy(const ShellView& v, double coef, double* partial, doubl
 {
     const int nb = shell_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_energy, dim3(nb), dim3(ENERGY_BLOCK), 0, s, v, coef, partial);
-    hipLaunchKernelGGL(k_shell_reduce, dim3(1), dim3(ENERGY_BLOCK), 0, s, partial, nb, accumulate ? 1 : 0, out);
+    hipLaunchKernelGGL(k_reduce_partials<ENERGY_BLOCK>, dim3(1), dim3(ENERGY_BLOCK), 0, s, partial, nb, accumulate ? 1 : 0, out);
 }
 void launch_shell_energy_per_elem(const ShellView& v, double* perTri, double* perHinge, hipStream_t s)
 {

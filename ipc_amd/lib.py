@@ -567,6 +567,46 @@ class Context:
     def shell_hessian_add(self, coef=1.0, projectDBC=True):
         self._chk(self._L.ipcgpu_shell_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
 
+    # ---- elastic rods (ipcgpu_set_rod: stretching + bending energy on segment components)
+    def set_rod(self, seg, radius, YM, rho, bend_scale=1.0):
+        """seg: nSeg x 2 node ids; radius, YM, rho: scalars or one value per segment.  After set_mesh, before opt_init and set_pattern; sets the masses of
+        the rod nodes and marks them as element nodes.  Collision still needs the segments in set_surface.  An empty `seg` removes the rod."""
+        seg = np.asfortranarray(np.asarray(seg, dtype=np.int32).reshape(-1, 2))
+        n = seg.shape[0]
+        per = [_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))) for a in (radius, YM, rho)]
+        self._chk(self._L.ipcgpu_set_rod(self.h, C.c_int(n), _ip(seg), _dp(per[0]), _dp(per[1]), _dp(per[2]), C.c_double(bend_scale)))
+
+    def rod_get(self):
+        """dict: nSeg, nBend, bend (nBend x 3: a, b, c with b the interior node), restLen, ks (per segment), kb, restKb (per triple), mass (nV)"""
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_rod_get(self.h, _ip(cnt), None, None, None, None, None, None))
+        nSeg, nB = int(cnt[0]), int(cnt[1])
+        bend = np.zeros((nB, 3), dtype=np.int32)
+        L, ks, kb, rest, mass = np.zeros(nSeg), np.zeros(nSeg), np.zeros(nB), np.zeros(nB), np.zeros(self.nV)
+        self._chk(self._L.ipcgpu_rod_get(self.h, _ip(cnt), _ip(bend), _dp(L), _dp(ks), _dp(kb), _dp(rest), _dp(mass)))
+        return {"nSeg": nSeg, "nBend": nB, "bend": bend, "restLen": L, "ks": ks, "kb": kb, "restKb": rest, "mass": mass}
+
+    def rod_energy(self, coef=1.0):
+        e = C.c_double()
+        self._chk(self._L.ipcgpu_rod_energy(self.h, C.c_double(coef), C.byref(e)))
+        return e.value
+
+    def rod_energy_per_elem(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_rod_get(self.h, _ip(cnt), None, None, None, None, None, None))
+        t, h = np.zeros(int(cnt[0])), np.zeros(int(cnt[1]))
+        self._chk(self._L.ipcgpu_rod_energy_per_elem(self.h, _dp(t), _dp(h)))
+        return t, h
+
+    def rod_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * rod gradient; returns it"""
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(self._L.ipcgpu_rod_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
+        return g
+
+    def rod_hessian_add(self, coef=1.0, projectDBC=True):
+        self._chk(self._L.ipcgpu_rod_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)
         self._chk(self._L.ipcgpu_set_obstacle_nodes(self.h, C.c_int(len(ids)), _ip(ids), C.c_int(int(obstacle_only))))

@@ -54,6 +54,10 @@ class Shape:
     # the shape's `material` or the scene's density / stiffness (Context.set_shell) -- and may be free, partly held by `DBC` boxes or moved by the scripts
     shell_thickness: float = None
     shell_bend: float = 1.0
+    # `rod <radius> [bend <scale>]` (this project's keyword, `.seg` shapes only): the component is an elastic rod -- stretching and bending energy with the
+    # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
+    rod_radius: float = None
+    rod_bend: float = 1.0
 
 
 @dataclass
@@ -386,6 +390,18 @@ def _parse_shape(st, resolve):
                 j += 2
             if not sh.shell_thickness > 0.0 or not sh.shell_bend >= 0.0:
                 raise ValueError("shell needs a positive thickness and a bend scale >= 0")
+        elif e == "rod":
+            if j >= len(st):
+                raise ValueError("rod needs a radius")
+            sh.rod_radius = float(st[j])
+            j += 1
+            if j < len(st) and st[j] == "bend":
+                if j + 1 >= len(st):
+                    raise ValueError("bend needs a scale")
+                sh.rod_bend = float(st[j + 1])
+                j += 2
+            if not sh.rod_radius > 0.0 or not sh.rod_bend >= 0.0:
+                raise ValueError("rod needs a positive radius and a bend scale >= 0")
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
             sh.init_vel = (tuple(v[:3]), tuple(v[3:]))
@@ -418,6 +434,8 @@ def _parse_shape(st, resolve):
             raise UnsupportedKeyword(f"shape keyword {e}")
     if sh.shell_thickness is not None and os.path.splitext(sh.path.lower())[1] != ".obj":
         raise ValueError("shell is valid on a triangle-mesh shape only (not on a tetrahedral, segment or point shape)")
+    if sh.rod_radius is not None and os.path.splitext(sh.path.lower())[1] != ".seg":
+        raise ValueError("rod is valid on a segment shape only (not on a tetrahedral, triangle-mesh or point shape)")
     return sh
 
 
@@ -537,6 +555,8 @@ class AssembledScene:
     motions: list = None  # rule-driven scripts: per Dirichlet group (lin, ang in degrees, fixed rotation centre or None), nodes NONZERO throughout
     # the shapes that carry `shell`, as Context.set_shell takes them: {tri, thickness, YM, PR, rho (per triangle), bend (one scale for the scene)}, or None
     shell: dict = None
+    # the shapes that carry `rod`, as Context.set_rod takes them: {seg, radius, YM, rho (per segment), bend (one scale for the scene)}, or None
+    rod: dict = None
 
     def before_step(self, be, t):
         """What AnimScripter::stepAnimScript decides from the state before a time step (call with the step's start time)."""
@@ -639,6 +659,7 @@ def assemble(cfg, read_mesh):
     CEs = []
     seqs = []  # mesh sequences: {ids, folder, ext}
     shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
+    rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
     for sh in cfg.shapes:
         ext = os.path.splitext(sh.path.lower())[1]
         is_codim = ext in (".obj", ".seg", ".pt")  # main.cpp:948-1005: kinematic surface / segments / points (componentCoDim 2 / 1 / 0)
@@ -658,12 +679,14 @@ def assemble(cfg, read_mesh):
         off = nr[-1]
         # Dirichlet / Neumann nodes are picked on the mesh AS READ (IglUtils::Init_Dirichlet on newV, main.cpp:1045-1068); the
         # shape is scaled / rotated / translated only afterwards (main.cpp:1073-1077), so the relative box follows the shape
+        # (the reference picks among the nodes of surface triangles; a `rod` shape has none: its boxes pick among the nodes of its segments)
+        pick = E if sh.rod_radius is not None else SF
         for rel_min, rel_max, lin, ang, t0, t1 in sh.dbc:
-            ids = _scene.select_dirichlet(V, SF, rel_min, rel_max)
+            ids = _scene.select_dirichlet(V, pick, rel_min, rel_max)
             if len(ids):
                 dirichlet.append((ids + off, lin, ang, t0, t1))
         for rel_min, rel_max, acc, t0, t1 in sh.nbc:  # same vertex selection (main.cpp:1057-1068)
-            ids = _scene.select_dirichlet(V, SF, rel_min, rel_max)
+            ids = _scene.select_dirichlet(V, pick, rel_min, rel_max)
             if len(ids):
                 neumann.append((ids + off, acc, t0, t1))
         V = (V * sh.scale) @ _rot(sh.rotate_deg).T + sh.translate
@@ -683,9 +706,13 @@ def assemble(cfg, read_mesh):
         if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat))
-        if is_codim:  # (an elastic shell needs nobody to hold it: it counts as moved)
+        if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
+            mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
+            rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
+        if is_codim:  # (an elastic shell or rod needs nobody to hold it: it counts as moved)
+            elastic = sh.shell_thickness is not None or sh.rod_radius is not None
             codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
-                          sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None or sh.shell_thickness is not None, E + off))
+                          sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None or elastic, E + off))
         CEs.append(E + off)
         Vs.append(V)
         Ts.append(T + off)
@@ -1101,6 +1128,12 @@ def assemble(cfg, read_mesh):
         per = lambda k: np.concatenate([np.full(len(t), float(m[k])) for t, _h, _b, m in shells])  # noqa: E731
         sc.shell = {"tri": np.vstack([t for t, *_ in shells]).astype(np.int32), "thickness": np.concatenate([np.full(len(t), float(h)) for t, h, *_ in shells]),
                     "rho": per(0), "YM": per(1), "PR": per(2), "bend": float(shells[0][2])}
+    if rods:
+        if len({b for _s, _r, b, _m in rods}) > 1:
+            raise ValueError("one bend scale per scene: the rod shapes give different ones")
+        per = lambda k: np.concatenate([np.full(len(e), float(m[k])) for e, _r, _b, m in rods])  # noqa: E731
+        sc.rod = {"seg": np.vstack([e for e, *_ in rods]).astype(np.int32), "radius": np.concatenate([np.full(len(e), float(r)) for e, r, *_ in rods]),
+                  "rho": per(0), "YM": per(1), "bend": float(rods[0][2])}
     for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = seqs
@@ -1125,11 +1158,15 @@ def apply(sc, be):
     if sc.shell is not None:  # after set_codim_nodes (it replaces the area masses of its nodes), before opt_init and the pattern
         q = sc.shell
         be.set_shell(q["tri"], q["thickness"], q["YM"], q["PR"], q["rho"], q["bend"])
+    if sc.rod is not None:  # after set_codim_nodes and set_shell (it replaces the segment masses of its nodes), before opt_init and the pattern
+        q = sc.rod
+        be.set_rod(q["seg"], q["radius"], q["YM"], q["rho"], q["bend"])
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
         # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density
         # once more, and it has no tetrahedra whose Lame parameters it could set)
-        if sh.material is not None and all(np.isfinite(sh.material)) and sh.shell_thickness is None:
+        # (the same holds for a rod shape and set_rod)
+        if sh.material is not None and all(np.isfinite(sh.material)) and sh.shell_thickness is None and sh.rod_radius is None:
             be.set_component_material((sc.node_ranges[s], sc.node_ranges[s + 1]), (sc.tet_ranges[s], sc.tet_ranges[s + 1]), *sh.material)
     if sc.V0 is not None:
         be.set_positions(sc.V0)

@@ -371,6 +371,32 @@ int ipcgpu_shell_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_shell_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri, double* perHinge_nHinge);
 int ipcgpu_shell_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_shell_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+/* Strain limiting of the shell (no counterpart in the reference): a log barrier on the principal stretches of the limited triangles.  With F the 3 x 2
+ * deformation gradient of the membrane, sigma1 >= sigma2 its singular values (closed form), per triangle with limit s > 0, onset sHat and stiffness stiff:
+ *   W = stiff h A E (b(sigma1) + b(sigma2)),  b = 0 for sigma <= sHat,  -y^2 ln(1 - y) with y = (sigma - sHat) / (s - sHat) below s,  +infinity from s on
+ *   (never NaN).  b is C^2 at the onset, increasing and convex.  Exact gradient; the exact Hessian is PSD as it stands (closed-form eigenpairs, each clamped
+ *   at 0 against round-off).  A triangle at or over its limit adds +infinity to the energy and nothing to gradient and matrix, which stay finite.
+ * ipcgpu_shell_set_strain_limit: limit per triangle, 0 = unlimited; onset (null: 1) and stiff (null: 1) per triangle, read where limit > 0.  All limits zero,
+ * or a null limit, removes the term.  After ipcgpu_set_shell (without a shell: IPCGPU_ERR_STATE), at any time: it changes no mass and adds no node pair --
+ * the blocks are the membrane's, so the pattern stays.  ipcgpu_set_shell and ipcgpu_set_mesh drop the limit.  IPCGPU_ERR_ARG: 0 < limit <= onset,
+ * onset < 1, stiff <= 0, a negative limit or a value that is not finite.
+ * With a limit set the term is part of the shell energy everywhere: ipcgpu_shell_energy, ipcgpu_shell_gradient_add and ipcgpu_shell_hessian_add include it,
+ * and through the stepper's shell terms so do ipcgpu_assemble_newton, ipcgpu_gradient, ipcgpu_incremental_potential and the stiffness damping.  The stepper
+ * never accepts a state with a stretch at or over its limit: a trial energy of +infinity is backtracked by the line search; a scripted Dirichlet move is
+ * shortened until the moved state is feasible (the augmented-Lagrangian solve takes the nodes the rest of the way); a time step that starts from a state
+ * at or over a limit returns IPCGPU_ERR_STATE, the message naming the number of such triangles, and changes nothing.  Without a limit none of the limit
+ * kernels is ever launched.
+ * ipcgpu_shell_limit_energy / _energy_per_elem / _gradient_add / _hessian_add: the limit term alone, with the semantics of their ipcgpu_shell_* namesakes
+ * (perTri has nTri entries, 0 for an unlimited triangle; coef > 0).  Without a limit they return IPCGPU_OK and add nothing.
+ * ipcgpu_shell_stretch: sigma_2nTri (nullable) = sigma1, sigma2 of triangle t at 2 t, 2 t + 1; maxRatio (nullable) = the maximum of sigma1 / limit over the
+ * limited triangles, exactly the maximum of those quotients of the returned values, 0 without a limited triangle.  Works with or without a limit; without
+ * a shell it returns IPCGPU_OK, maxRatio 0. */
+int ipcgpu_shell_set_strain_limit(ipcgpu_ctx*, const double* limit_nTri, const double* onset_nTri, const double* stiff_nTri);
+int ipcgpu_shell_limit_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_shell_limit_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
+int ipcgpu_shell_limit_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_shell_limit_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_shell_stretch(ipcgpu_ctx*, double* sigma_2nTri, double* maxRatio);
 /* Elastic rods (no counterpart in the reference): stretching and bending energy on segment components.
  *   stretching  per segment (a, b): rest length L, length l, radius r, Young's modulus E, A = pi r^2, k_s = E A / L, W_s = k_s (l - L)^2 / 2.  Exact gradient.
  *               With t = (x_b - x_a) / l the 3 x 3 block is B = k_s [t t^T + max(0, 1 - L / l) (I - t t^T)], the 6 x 6 Hessian [[B, -B], [-B, B]]: the clamp

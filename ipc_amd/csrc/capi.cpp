@@ -321,6 +321,7 @@ int ipcgpu_set_positions(ipcgpu_ctx* c, const double* V)
         bind(c);
         needArg(V != nullptr, "null V");
         uploadColMajor(c, V, c->mesh->d_x);
+        c->mesh->shell.limitUnchecked = c->mesh->shell.nLimited() > 0; // the stepper's last energy no longer describes these positions
         return IPCGPU_OK;
     });
 }
@@ -980,6 +981,7 @@ int ipcgpu_shell_energy(ipcgpu_ctx* c, double coef, double* E)
         *E = 0.0;
         if (!c->mesh->shell.nTri()) return IPCGPU_OK;
         launch_shell_energy(o.shellView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
+        if (c->mesh->shell.nLimited()) launch_shell_limit_energy(o.shellLimitView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, true, c->stream);
         *E = o.readScalar(o.d_scalar.p);
         return IPCGPU_OK;
     });
@@ -1033,6 +1035,91 @@ int ipcgpu_shell_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
             HIP_CHECK(hipStreamSynchronize(c->stream));
             throw StateError("the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell");
         }
+        return IPCGPU_OK;
+    });
+}
+// ---- Strain limit of the shells -----------------------------------------------------------------------
+int ipcgpu_shell_set_strain_limit(ipcgpu_ctx* c, const double* limit, const double* onset, const double* stiff)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        m.setShellStrainLimit(limit, onset, stiff, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_limit_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(E != nullptr, "null argument");
+        needArg(coef > 0.0, "the coefficient of the strain-limit energy must be positive");
+        need(o.initialised, "call ipcgpu_opt_init first");
+        *E = 0.0;
+        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
+        launch_shell_limit_energy(o.shellLimitView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
+        *E = o.readScalar(o.d_scalar.p);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_limit_energy_per_elem(ipcgpu_ctx* c, double* perTri)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri() || !perTri) return IPCGPU_OK;
+        DevBuf<double> t;
+        t.alloc(sh.nTri());
+        launch_shell_limit_energy_per_elem(o.shellLimitView(c->mesh->d_x.p), t.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        t.download(perTri, sh.nTri(), c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_limit_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(g != nullptr, "null argument");
+        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
+        DevBuf<double> dg;
+        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
+        launch_shell_limit_assemble(o.shellLimitView(c->mesh->d_x.p), coef, projectDBC != 0, dg.p, nullptr, c->mesh->shell.d_err.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_limit_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
+        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
+        launch_shell_limit_assemble(o.shellLimitView(c->mesh->d_x.p), coef, projectDBC != 0, nullptr, c->lin->d_a.p, c->mesh->shell.d_err.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        int err = 0;
+        c->mesh->shell.d_err.download(&err, 1, c->stream);
+        if (err) {
+            c->mesh->shell.d_err.zero(c->stream);
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            throw StateError("the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell");
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_stretch(ipcgpu_ctx* c, double* sigma, double* maxRatio)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        o.shellStretch(sigma, maxRatio, nullptr);
         return IPCGPU_OK;
     });
 }

@@ -20,6 +20,8 @@
 #include "rod_kernels.h"
 #include "rod_plan.h"
 #include "shell_kernels.h"
+#include "shell_limit_kernels.h"
+#include "shell_limit_plan.h"
 #include "shell_plan.h"
 #include "stress_plan.h"
 #include <map>
@@ -44,6 +46,14 @@ struct HipShell {
     DevBuf<double> d_triConst, d_hingeConst;
     int nTri() const { return plan.nTri; }
     int nHinge() const { return plan.nHinge; }
+    // strain limit (ipcgpu_shell_set_strain_limit; shell_limit_plan.h): arrays of its own beside the shell's.  nLimited() == 0: no limit, and then none of
+    // the limit kernels is launched.  unchecked: set where the stepper cannot know from its last energy whether the state is feasible (a new limit,
+    // positions written from outside): the next time step then asks the device once
+    ShellLimitPlan limit;
+    DevBuf<int> d_limTri;
+    DevBuf<double> d_limConst, d_triLimit, d_stretchPartial, d_stretchOut;
+    bool limitUnchecked = false;
+    int nLimited() const { return limit.nLimited; }
 };
 
 // Elastic rod of the mesh (ipcgpu_set_rod): the host plan and its device copy.  nSeg() == 0: no rod, and then nothing below is ever read.
@@ -92,6 +102,9 @@ public:
     // in the mesh avgEdgeLen is the mean side of the shell triangles while a shell is set.
     HipShell shell;
     void setShell(int nTri, const int* tri_colmajor, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s);
+    // Strain limit of the shell (shell_limit_plan.h): validates and uploads the compact list and the constants.  All limits zero (or null) removes it;
+    // setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair (the blocks are the membrane's).
+    void setShellStrainLimit(const double* limit, const double* onset, const double* stiff, hipStream_t s);
     // Elastic rod on segment components (rod_plan.h): as setShell -- validates, sets the lumped masses of the rod nodes, marks them as element nodes, adds
     // the plan's node pairs to vNeighbor and uploads the constants.  nSeg = 0 removes the rod, a second call replaces it: the nodes of the old rod get back
     // the masses they had before it and lose the mark; the neighbour pairs stay.  With neither a tetrahedron nor a shell in the mesh avgEdgeLen is the mean
@@ -260,6 +273,12 @@ public:
     ShellView shellView(const double* x_dev) const;
     void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and, with a shell or a rod, their energies on top
     void shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
+    // the shell's strain limit (shell_limit_kernels.h): part of the shell energy wherever that enters; every launch is guarded on mesh.shell.nLimited()
+    ShellLimitView shellLimitView(const double* x_dev) const;
+    // sigma1, sigma2 per triangle (host, 2 nTri, nullable), the maximum of sigma1 / limit and the number of triangles at or over their limit (synchronises)
+    void shellStretch(double* sigma_host, double* maxRatio, int* nOver, const double* x_dev = nullptr);
+    bool shellLimitFeasible(); // true without a limit; else one stretch query at the current positions
+    void requireShellLimitFeasible(); // StateError naming the number of triangles over their limit
     // rod terms (rod_kernels.h): enter wherever the shell terms do, with the same coefficient; every call is guarded on mesh.rod.nSeg()
     RodView rodView(const double* x_dev) const;
     void rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);

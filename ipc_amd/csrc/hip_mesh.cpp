@@ -32,6 +32,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (nV_ <= 0 || nT_ < 0) throw ArgError("set_mesh: bad sizes");
     ++featuresVersion;
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
+    shell.limit = ShellLimitPlan(); // ... and its strain limit with it
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     nV = nV_;
     nT = nT_;
@@ -197,6 +198,7 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     // the plan's pairs join vNeighbor: triangle edges (addSurfaceEdges adds the same ones) and the opposite pair of every hinge
     addNeighbourPairs(plan.pairs);
     shell.plan = std::move(plan);
+    shell.limit = ShellLimitPlan(); // a strain limit belongs to the shell it was set on
     shell.bendScale = bendScale;
     const ShellPlan& p = shell.plan;
     d_mass.upload(mass, s);
@@ -213,6 +215,21 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     shell.d_hingeConst.upload(hc, s);
     shell.d_err.alloc(1);
     shell.d_err.zero(s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setShellStrainLimit(const double* limit, const double* onset, const double* stiff, hipStream_t s)
+{
+    if (!shell.nTri()) throw StateError("shell_set_strain_limit: no shell is set (call ipcgpu_set_shell first)");
+    ShellLimitPlan plan;
+    std::string err;
+    if (!buildShellLimitPlan(shell.nTri(), limit, onset, stiff, shell.plan.membraneK.data(), plan, err)) throw ArgError(err);
+    shell.limit = std::move(plan);
+    shell.limitUnchecked = shell.limit.nLimited > 0;
+    if (!shell.limit.nLimited) return;
+    shell.d_limTri.upload(shell.limit.tri, s);
+    shell.d_limConst.upload(shell.limit.limConst, s);
+    shell.d_triLimit.upload(shell.limit.triLimit, s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -111,6 +111,8 @@ void HipOptimizer::enqueueElasticEnergy(bool ownerRank, double* out_dev)
 {
     launch_energy(view(), elasticCoef(), true, ownerRank, d_partial.p, (int)d_partial.n, out_dev, stream);
     if (mesh.shell.nTri()) launch_shell_energy(shellView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_shell)
+    // the strain limit: +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node
+    if (mesh.shell.nLimited()) launch_shell_limit_energy(shellLimitView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream);
     if (mesh.rod.nSeg()) launch_rod_energy(rodView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_rod)
 }
 
@@ -118,6 +120,65 @@ void HipOptimizer::shellAssembleAdd(double coef, bool projectDBC, double* grad_d
 {
     if (!mesh.shell.nTri()) return;
     launch_shell_assemble(shellView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
+    if (mesh.shell.nLimited())
+        launch_shell_limit_assemble(shellLimitView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
+}
+
+ShellLimitView HipOptimizer::shellLimitView(const double* x_dev) const
+{
+    const HipShell& sh = mesh.shell;
+    ShellLimitView v;
+    v.nTri = sh.nTri();
+    v.nLimited = sh.nLimited();
+    v.tri = sh.d_tri.p;
+    v.triConst = sh.d_triConst.p;
+    v.limTri = sh.d_limTri.p;
+    v.limConst = sh.d_limConst.p;
+    v.triLimit = sh.nLimited() ? sh.d_triLimit.p : nullptr;
+    v.x = x_dev;
+    v.dbc = mesh.d_dbc.p;
+    v.rowBase = lin.d_rowBase.p;
+    v.rowLen = lin.d_rowLen.p;
+    v.ja = lin.d_ja.p;
+    return v;
+}
+
+void HipOptimizer::shellStretch(double* sigma_host, double* maxRatio, int* nOver, const double* x_dev)
+{
+    HipShell& sh = mesh.shell;
+    if (maxRatio) *maxRatio = 0.0;
+    if (nOver) *nOver = 0;
+    if (!sh.nTri()) return;
+    const ShellLimitView v = shellLimitView(x_dev ? x_dev : mesh.d_x.p);
+    DevBuf<double> sigma;
+    if (sigma_host) sigma.alloc(2 * (size_t)sh.nTri());
+    sh.d_stretchPartial.ensure(2 * (size_t)shell_stretch_blocks(v));
+    sh.d_stretchOut.alloc(2);
+    launch_shell_stretch(v, sigma_host ? sigma.p : nullptr, sh.d_stretchPartial.p, sh.d_stretchOut.p, stream);
+    HIP_CHECK(hipGetLastError());
+    double out[2] = { 0.0, 0.0 };
+    if (sigma_host) HIP_CHECK(hipMemcpyAsync(sigma_host, sigma.p, 2 * (size_t)sh.nTri() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sh.d_stretchOut.download(out, 2, stream); // synchronises
+    if (maxRatio) *maxRatio = out[0];
+    if (nOver) *nOver = (int)out[1];
+}
+
+bool HipOptimizer::shellLimitFeasible()
+{
+    if (!mesh.shell.nLimited()) return true;
+    int nOver = 0;
+    shellStretch(nullptr, nullptr, &nOver);
+    return nOver == 0;
+}
+
+void HipOptimizer::requireShellLimitFeasible()
+{
+    if (!mesh.shell.nLimited()) return;
+    int nOver = 0;
+    shellStretch(nullptr, nullptr, &nOver);
+    mesh.shell.limitUnchecked = false;
+    if (nOver)
+        throw StateError(std::to_string(nOver) + " shell triangle" + (nOver == 1 ? " has" : "s have") + " a principal stretch at or over the strain limit at the start of the time step");
 }
 
 void HipOptimizer::rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
@@ -672,6 +733,7 @@ void HipOptimizer::loadStatus(const std::string& path)
     }
     if (in.bad()) throw StateError("read error on status file " + path);
     mesh.d_x.upload(x, stream);
+    mesh.shell.limitUnchecked = mesh.shell.nLimited() > 0;
     d_xPrev.upload(x, stream);
     d_xStepStart.upload(x, stream); // V_prev = V (Optimizer.cpp:247): a report right after a restart has no kinetic part
     d_vel.upload(vel, stream);
@@ -1348,6 +1410,17 @@ void HipOptimizer::stepFeasible(double& stepSize)
             stepSize /= 2.0;
             stepForward(d_x0.p, stepSize);
         }
+    // the shells' strain limit: the feasible set is convex and d_x0 lies inside it (beginTimestep), so halving ends, and a step shortened further for
+    // another reason stays feasible.  What a scripted Dirichlet move loses here the augmented-Lagrangian solve takes up (completedStep < 1).
+    while (stepSize > 0.0 && !shellLimitFeasible()) {
+        stepSize /= 2.0;
+        stepForward(d_x0.p, stepSize);
+        if (ipOn())
+            while (anyIntersection()) {
+                stepSize /= 2.0;
+                stepForward(d_x0.p, stepSize);
+            }
+    }
 }
 
 void HipOptimizer::lineSearch(double& stepSize)
@@ -1480,7 +1553,13 @@ void HipOptimizer::beginTimestep()
     // The contact-free twist (BASELINE configs[1]; round 6): everything the set-up of a time step asks the device -- inverted before the motion? the filter's bound
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.
-    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && !(warmStart >= 1 && warmStart <= 5);
+    // (a strain limit takes the general sequence: its scripted step is shortened by stepFeasible)
+    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && !(warmStart >= 1 && warmStart <= 5)
+        && !mesh.shell.nLimited();
+    // With a strain limit the stepper never accepts a state with a stretch at or over it, so a time step may only start from a feasible one.  The energy the
+    // stepper holds on the host tells: it is +infinity exactly then (or at the fold of a rod node, which the count below tells apart) -- no device query on
+    // the usual path.  Positions or a limit set from outside since then are asked for once.  Nothing has been changed yet when this throws.
+    if (mesh.shell.nLimited() && (mesh.shell.limitUnchecked || !(lastEnergyVal < INFINITY))) requireShellLimitFeasible();
     if (batched) {
         const bool guard = mesh.needElemInvSafeGuard(); // Optimizer.cpp:252, 517: only under getNeedElemInvSafeGuard()
         d_flag.zero(stream);

@@ -567,6 +567,47 @@ class Context:
     def shell_hessian_add(self, coef=1.0, projectDBC=True):
         self._chk(self._L.ipcgpu_shell_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
 
+    # ---- strain limit of the shell (ipcgpu_shell_set_strain_limit: a log barrier on the principal stretches of the limited triangles)
+    def _shell_ntri(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_shell_get(self.h, _ip(cnt), None, None, None, None, None))
+        return int(cnt[0])
+
+    def set_shell_strain_limit(self, limit, onset=None, stiff=None):
+        """limit, onset (None: 1), stiff (None: 1): scalars or one value per shell triangle; limit 0 leaves a triangle unlimited, None or all zeros removes the
+        term.  After set_shell; set_shell and set_mesh drop it."""
+        n = self._shell_ntri()
+        per = [None if a is None else _f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))) for a in (limit, onset, stiff)]
+        self._chk(self._L.ipcgpu_shell_set_strain_limit(self.h, _dp(per[0]), _dp(per[1]), _dp(per[2])))
+
+    def shell_limit_energy(self, coef=1.0):
+        e = C.c_double()
+        self._chk(self._L.ipcgpu_shell_limit_energy(self.h, C.c_double(coef), C.byref(e)))
+        return e.value
+
+    def shell_limit_energy_per_elem(self):
+        """the unscaled barrier energy per shell triangle (0 for an unlimited one, inf at or over the limit)"""
+        t = np.zeros(self._shell_ntri())
+        self._chk(self._L.ipcgpu_shell_limit_energy_per_elem(self.h, _dp(t)))
+        return t
+
+    def shell_limit_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * gradient of the limit term; returns it"""
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(self._L.ipcgpu_shell_limit_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
+        return g
+
+    def shell_limit_hessian_add(self, coef=1.0, projectDBC=True):
+        self._chk(self._L.ipcgpu_shell_limit_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+
+    def shell_stretch(self):
+        """(sigma (nTri x 2: the principal stretches sigma1 >= sigma2 of every shell triangle), the maximum of sigma1 / limit over the limited triangles --
+        0 without one)"""
+        s = np.zeros((self._shell_ntri(), 2))
+        r = C.c_double()
+        self._chk(self._L.ipcgpu_shell_stretch(self.h, _dp(s), C.byref(r)))
+        return s, r.value
+
     # ---- elastic rods (ipcgpu_set_rod: stretching + bending energy on segment components)
     def set_rod(self, seg, radius, YM, rho, bend_scale=1.0):
         """seg: nSeg x 2 node ids; radius, YM, rho: scalars or one value per segment.  After set_mesh, before opt_init and set_pattern; sets the masses of

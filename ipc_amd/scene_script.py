@@ -54,6 +54,11 @@ class Shape:
     # the shape's `material` or the scene's density / stiffness (Context.set_shell) -- and may be free, partly held by `DBC` boxes or moved by the scripts
     shell_thickness: float = None
     shell_bend: float = 1.0
+    # `shell <thickness> [bend <scale>] [limit <s> [onset <sHat>] [stiff <k>]]`: strain limiting of this shape's triangles -- a barrier on their principal
+    # stretches that starts at the onset (default 1) and is infinite at the limit (Context.set_shell_strain_limit); per shape, shapes may differ
+    shell_limit: float = None
+    shell_onset: float = 1.0
+    shell_stiff: float = 1.0
     # `rod <radius> [bend <scale>]` (this project's keyword, `.seg` shapes only): the component is an elastic rod -- stretching and bending energy with the
     # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
     rod_radius: float = None
@@ -390,6 +395,21 @@ def _parse_shape(st, resolve):
                 j += 2
             if not sh.shell_thickness > 0.0 or not sh.shell_bend >= 0.0:
                 raise ValueError("shell needs a positive thickness and a bend scale >= 0")
+            if j < len(st) and st[j] == "limit":
+                if j + 1 >= len(st):
+                    raise ValueError("limit needs a stretch")
+                sh.shell_limit = float(st[j + 1])
+                j += 2
+                for word, attr in (("onset", "shell_onset"), ("stiff", "shell_stiff")):
+                    if j < len(st) and st[j] == word:
+                        if j + 1 >= len(st):
+                            raise ValueError(word + " needs a value")
+                        setattr(sh, attr, float(st[j + 1]))
+                        j += 2
+                if not (np.isfinite(sh.shell_limit) and sh.shell_onset >= 1.0 and sh.shell_limit > sh.shell_onset and 0.0 < sh.shell_stiff < float("inf")):
+                    raise ValueError("limit needs 1 <= onset < limit and a stiffness > 0")
+            elif j < len(st) and st[j] in ("onset", "stiff"):
+                raise ValueError(st[j] + " belongs behind limit")
         elif e == "rod":
             if j >= len(st):
                 raise ValueError("rod needs a radius")
@@ -553,7 +573,8 @@ class AssembledScene:
     mesh_i: int = 0  # AnimScripter::meshI: index of the next file of the sequences
     read_seq: object = None  # (folder, index, ext) -> positions; None = the files themselves (tests hand in a fixture's)
     motions: list = None  # rule-driven scripts: per Dirichlet group (lin, ang in degrees, fixed rotation centre or None), nodes NONZERO throughout
-    # the shapes that carry `shell`, as Context.set_shell takes them: {tri, thickness, YM, PR, rho (per triangle), bend (one scale for the scene)}, or None
+    # the shapes that carry `shell`, as Context.set_shell takes them: {tri, thickness, YM, PR, rho (per triangle), bend (one scale for the scene)}, or None;
+    # with `limit` on a shape also {limit, onset, stiff (per triangle; limit 0 on the triangles of a shape without it)} for Context.set_shell_strain_limit
     shell: dict = None
     # the shapes that carry `rod`, as Context.set_rod takes them: {seg, radius, YM, rho (per segment), bend (one scale for the scene)}, or None
     rod: dict = None
@@ -659,6 +680,7 @@ def assemble(cfg, read_mesh):
     CEs = []
     seqs = []  # mesh sequences: {ids, folder, ext}
     shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
+    shell_limits = []  # ... and their (limit or 0, onset, stiffness)
     rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
     for sh in cfg.shapes:
         ext = os.path.splitext(sh.path.lower())[1]
@@ -706,6 +728,7 @@ def assemble(cfg, read_mesh):
         if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat))
+            shell_limits.append((0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff))
         if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
@@ -1128,6 +1151,9 @@ def assemble(cfg, read_mesh):
         per = lambda k: np.concatenate([np.full(len(t), float(m[k])) for t, _h, _b, m in shells])  # noqa: E731
         sc.shell = {"tri": np.vstack([t for t, *_ in shells]).astype(np.int32), "thickness": np.concatenate([np.full(len(t), float(h)) for t, h, *_ in shells]),
                     "rho": per(0), "YM": per(1), "PR": per(2), "bend": float(shells[0][2])}
+        if any(q[0] > 0.0 for q in shell_limits):  # per triangle, as Context.set_shell_strain_limit takes them; a shape without `limit` stays unlimited (0)
+            for k, name in enumerate(("limit", "onset", "stiff")):
+                sc.shell[name] = np.concatenate([np.full(len(t[0]), float(q[k])) for t, q in zip(shells, shell_limits)])
     if rods:
         if len({b for _s, _r, b, _m in rods}) > 1:
             raise ValueError("one bend scale per scene: the rod shapes give different ones")
@@ -1158,6 +1184,8 @@ def apply(sc, be):
     if sc.shell is not None:  # after set_codim_nodes (it replaces the area masses of its nodes), before opt_init and the pattern
         q = sc.shell
         be.set_shell(q["tri"], q["thickness"], q["YM"], q["PR"], q["rho"], q["bend"])
+        if "limit" in q:
+            be.set_shell_strain_limit(q["limit"], q["onset"], q["stiff"])
     if sc.rod is not None:  # after set_codim_nodes and set_shell (it replaces the segment masses of its nodes), before opt_init and the pattern
         q = sc.rod
         be.set_rod(q["seg"], q["radius"], q["YM"], q["rho"], q["bend"])

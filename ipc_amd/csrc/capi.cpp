@@ -110,6 +110,79 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
     for (int v = 0; v < nV; ++v)
         for (int k = 0; k < 3; ++k) Vcm[v + (size_t)nV * k] = aos[3 * (size_t)v + k];
 }
+
+// ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
+// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its limit, ipcgpu_shell_limit_* the limit alone, ipcgpu_rod_* the rod.
+constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT, ROD = HipOptimizer::CODIM_ROD;
+const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
+const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
+// What an entry point returns early on: no triangle, no limited triangle, no segment.
+int codimCount(const HipMesh& m, unsigned which)
+{
+    return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri() : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited() : m.rod.nSeg();
+}
+int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
+{
+    HipOptimizer& o = O(c);
+    bind(c);
+    needArg(E != nullptr, "null argument");
+    // (ipcgpu_shell_limit_energy alone asks for this: its +infinity must keep its sign)
+    needArg(which != HipOptimizer::CODIM_SHELL_LIMIT || coef > 0.0, "the coefficient of the strain-limit energy must be positive");
+    need(o.initialised, "call ipcgpu_opt_init first");
+    *E = 0.0;
+    if (!codimCount(*c->mesh, which)) return IPCGPU_OK;
+    o.codimEnergyAdd(c->mesh->d_x.p, coef, o.d_scalar.p, /*accumulate=*/false, which);
+    *E = o.readScalar(o.d_scalar.p);
+    return IPCGPU_OK;
+}
+int codimGradientAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, double* g)
+{
+    HipOptimizer& o = O(c);
+    bind(c);
+    needArg(g != nullptr, "null argument");
+    if (!codimCount(*c->mesh, which)) return IPCGPU_OK;
+    DevBuf<double> dg;
+    dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
+    o.codimAssembleAdd(coef, projectDBC != 0, dg.p, nullptr, nullptr, which);
+    HIP_CHECK(hipGetLastError());
+    dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
+    return IPCGPU_OK;
+}
+int codimHessianAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, const char* missMessage)
+{
+    HipOptimizer& o = O(c);
+    bind(c);
+    if (!codimCount(*c->mesh, which)) return IPCGPU_OK;
+    need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
+    o.codimAssembleAdd(coef, projectDBC != 0, nullptr, c->lin->d_a.p, nullptr, which);
+    HIP_CHECK(hipGetLastError());
+    int err = 0;
+    c->mesh->d_codimErr.download(&err, 1, c->stream);
+    if (err) {
+        c->mesh->d_codimErr.zero(c->stream);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        throw StateError(missMessage);
+    }
+    return IPCGPU_OK;
+}
+// ipcgpu_set_shell / ipcgpu_set_rod (which: CODIM_SHELL / CODIM_ROD): n elements, set(mesh) the call that differs
+template <class Set>
+int setCodimBody(ipcgpu_ctx* c, unsigned which, bool argsOk, int n, Set&& set)
+{
+    specChanged(c);
+    return guarded([&] {
+        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : "rod";
+        HipMesh& m = M(c);
+        bind(c);
+        needArg(argsOk, ("bad " + what + " arguments").c_str());
+        if (n == 0 && codimCount(m, which) == 0) return IPCGPU_OK; // nothing to remove
+        if (c->worldSize > 1) throw UnsupportedError(what + "s on a sharded context");
+        need(!c->opt->initialised, ("ipcgpu_set_" + what + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
+        set(m);
+        if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr); // (a pattern built before this call lacks the new body's node pairs)
+        return IPCGPU_OK;
+    });
+}
 } // namespace
 
 extern "C" {
@@ -938,19 +1011,9 @@ int ipcgpu_set_codim_nodes(ipcgpu_ctx* c, int n, const int* ids, const double* m
 // ---- Elastic shells -----------------------------------------------------------------------------------
 int ipcgpu_set_shell(ipcgpu_ctx* c, int nTri, const int* tri, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale)
 {
-    specChanged(c);
-    return guarded([&] {
-        HipMesh& m = M(c);
-        bind(c);
-        needArg(nTri >= 0 && ((tri && thickness && YM && PR && rho) || !nTri), "bad shell arguments");
-        if (nTri == 0 && m.shell.nTri() == 0) return IPCGPU_OK; // nothing to remove
-        if (c->worldSize > 1) throw UnsupportedError("shells on a sharded context");
-        need(!c->opt->initialised, "ipcgpu_set_shell must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built");
-        m.setShell(nTri, tri, thickness, YM, PR, rho, bendScale, c->stream);
-        // a pattern built before this call lacks the opposite pairs of the hinges: it is rebuilt from the new vNeighbor (without extra pairs)
-        if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr);
-        return IPCGPU_OK;
-    });
+    return setCodimBody(c, HipOptimizer::CODIM_SHELL, nTri >= 0 && ((tri && thickness && YM && PR && rho) || !nTri), nTri,
+        // a pattern built before this call lacks the opposite pairs of the hinges: setCodimBody rebuilds it from the new vNeighbor (without extra pairs)
+        [&](HipMesh& m) { m.setShell(nTri, tri, thickness, YM, PR, rho, bendScale, c->stream); });
 }
 int ipcgpu_shell_get(ipcgpu_ctx* c, int* counts2, int* hinge, double* restAngle, double* hingeWeight, double* area, double* mass)
 {
@@ -973,18 +1036,7 @@ int ipcgpu_shell_get(ipcgpu_ctx* c, int* counts2, int* hinge, double* restAngle,
 }
 int ipcgpu_shell_energy(ipcgpu_ctx* c, double coef, double* E)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(E != nullptr, "null argument");
-        need(o.initialised, "call ipcgpu_opt_init first");
-        *E = 0.0;
-        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
-        launch_shell_energy(o.shellView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
-        if (c->mesh->shell.nLimited()) launch_shell_limit_energy(o.shellLimitView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, true, c->stream);
-        *E = o.readScalar(o.d_scalar.p);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimEnergy(c, SHELL_AND_LIMIT, coef, E); });
 }
 int ipcgpu_shell_energy_per_elem(ipcgpu_ctx* c, double* perTri, double* perHinge)
 {
@@ -1005,38 +1057,12 @@ int ipcgpu_shell_energy_per_elem(ipcgpu_ctx* c, double* perTri, double* perHinge
 }
 int ipcgpu_shell_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(g != nullptr, "null argument");
-        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
-        DevBuf<double> dg;
-        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
-        o.shellAssembleAdd(coef, projectDBC != 0, dg.p, nullptr);
-        HIP_CHECK(hipGetLastError());
-        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimGradientAdd(c, SHELL_AND_LIMIT, coef, projectDBC, g); });
 }
 int ipcgpu_shell_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
 {
     specChanged(c);
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        if (!c->mesh->shell.nTri()) return IPCGPU_OK;
-        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
-        o.shellAssembleAdd(coef, projectDBC != 0, nullptr, c->lin->d_a.p);
-        HIP_CHECK(hipGetLastError());
-        int err = 0;
-        c->mesh->shell.d_err.download(&err, 1, c->stream);
-        if (err) {
-            c->mesh->shell.d_err.zero(c->stream);
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            throw StateError("the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell");
-        }
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimHessianAdd(c, SHELL_AND_LIMIT, coef, projectDBC, SHELL_MISS); });
 }
 // ---- Strain limit of the shells -----------------------------------------------------------------------
 int ipcgpu_shell_set_strain_limit(ipcgpu_ctx* c, const double* limit, const double* onset, const double* stiff)
@@ -1051,18 +1077,7 @@ int ipcgpu_shell_set_strain_limit(ipcgpu_ctx* c, const double* limit, const doub
 }
 int ipcgpu_shell_limit_energy(ipcgpu_ctx* c, double coef, double* E)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(E != nullptr, "null argument");
-        needArg(coef > 0.0, "the coefficient of the strain-limit energy must be positive");
-        need(o.initialised, "call ipcgpu_opt_init first");
-        *E = 0.0;
-        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
-        launch_shell_limit_energy(o.shellLimitView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
-        *E = o.readScalar(o.d_scalar.p);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimEnergy(c, LIMIT_ALONE, coef, E); });
 }
 int ipcgpu_shell_limit_energy_per_elem(ipcgpu_ctx* c, double* perTri)
 {
@@ -1081,38 +1096,12 @@ int ipcgpu_shell_limit_energy_per_elem(ipcgpu_ctx* c, double* perTri)
 }
 int ipcgpu_shell_limit_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(g != nullptr, "null argument");
-        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
-        DevBuf<double> dg;
-        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
-        launch_shell_limit_assemble(o.shellLimitView(c->mesh->d_x.p), coef, projectDBC != 0, dg.p, nullptr, c->mesh->shell.d_err.p, c->stream);
-        HIP_CHECK(hipGetLastError());
-        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimGradientAdd(c, LIMIT_ALONE, coef, projectDBC, g); });
 }
 int ipcgpu_shell_limit_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
 {
     specChanged(c);
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        if (!c->mesh->shell.nLimited()) return IPCGPU_OK;
-        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
-        launch_shell_limit_assemble(o.shellLimitView(c->mesh->d_x.p), coef, projectDBC != 0, nullptr, c->lin->d_a.p, c->mesh->shell.d_err.p, c->stream);
-        HIP_CHECK(hipGetLastError());
-        int err = 0;
-        c->mesh->shell.d_err.download(&err, 1, c->stream);
-        if (err) {
-            c->mesh->shell.d_err.zero(c->stream);
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            throw StateError("the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell");
-        }
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimHessianAdd(c, LIMIT_ALONE, coef, projectDBC, SHELL_MISS); });
 }
 int ipcgpu_shell_stretch(ipcgpu_ctx* c, double* sigma, double* maxRatio)
 {
@@ -1126,19 +1115,9 @@ int ipcgpu_shell_stretch(ipcgpu_ctx* c, double* sigma, double* maxRatio)
 // ---- Elastic rods -------------------------------------------------------------------------------------
 int ipcgpu_set_rod(ipcgpu_ctx* c, int nSeg, const int* seg, const double* radius, const double* YM, const double* rho, double bendScale)
 {
-    specChanged(c);
-    return guarded([&] {
-        HipMesh& m = M(c);
-        bind(c);
-        needArg(nSeg >= 0 && ((seg && radius && YM && rho) || !nSeg), "bad rod arguments");
-        if (nSeg == 0 && m.rod.nSeg() == 0) return IPCGPU_OK; // nothing to remove
-        if (c->worldSize > 1) throw UnsupportedError("rods on a sharded context");
-        need(!c->opt->initialised, "ipcgpu_set_rod must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built");
-        m.setRod(nSeg, seg, radius, YM, rho, bendScale, c->stream);
-        // a pattern built before this call lacks the outer pairs of the bending triples: it is rebuilt from the new vNeighbor (without extra pairs)
-        if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr);
-        return IPCGPU_OK;
-    });
+    return setCodimBody(c, HipOptimizer::CODIM_ROD, nSeg >= 0 && ((seg && radius && YM && rho) || !nSeg), nSeg,
+        // a pattern built before this call lacks the outer pairs of the bending triples: setCodimBody rebuilds it from the new vNeighbor (without extra pairs)
+        [&](HipMesh& m) { m.setRod(nSeg, seg, radius, YM, rho, bendScale, c->stream); });
 }
 int ipcgpu_rod_get(ipcgpu_ctx* c, int* counts2, int* bend, double* restLen, double* ks, double* kb, double* restKb, double* mass)
 {
@@ -1162,17 +1141,7 @@ int ipcgpu_rod_get(ipcgpu_ctx* c, int* counts2, int* bend, double* restLen, doub
 }
 int ipcgpu_rod_energy(ipcgpu_ctx* c, double coef, double* E)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(E != nullptr, "null argument");
-        need(o.initialised, "call ipcgpu_opt_init first");
-        *E = 0.0;
-        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
-        launch_rod_energy(o.rodView(c->mesh->d_x.p), coef, o.d_partial.p, o.d_scalar.p, false, c->stream);
-        *E = o.readScalar(o.d_scalar.p);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimEnergy(c, ROD, coef, E); });
 }
 int ipcgpu_rod_energy_per_elem(ipcgpu_ctx* c, double* perSeg, double* perBend)
 {
@@ -1194,38 +1163,12 @@ int ipcgpu_rod_energy_per_elem(ipcgpu_ctx* c, double* perSeg, double* perBend)
 }
 int ipcgpu_rod_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
 {
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(g != nullptr, "null argument");
-        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
-        DevBuf<double> dg;
-        dg.upload(g, 3 * (size_t)c->mesh->nV, c->stream);
-        o.rodAssembleAdd(coef, projectDBC != 0, dg.p, nullptr);
-        HIP_CHECK(hipGetLastError());
-        dg.download(g, 3 * (size_t)c->mesh->nV, c->stream);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimGradientAdd(c, ROD, coef, projectDBC, g); });
 }
 int ipcgpu_rod_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
 {
     specChanged(c);
-    return guarded([&] {
-        HipOptimizer& o = O(c);
-        bind(c);
-        if (!c->mesh->rod.nSeg()) return IPCGPU_OK;
-        need(!c->lin->rowBase.empty(), "call ipcgpu_linsys_set_pattern first");
-        o.rodAssembleAdd(coef, projectDBC != 0, nullptr, c->lin->d_a.p);
-        HIP_CHECK(hipGetLastError());
-        int err = 0;
-        c->mesh->rod.d_err.download(&err, 1, c->stream);
-        if (err) {
-            c->mesh->rod.d_err.zero(c->stream);
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            throw StateError("the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod");
-        }
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return codimHessianAdd(c, ROD, coef, projectDBC, ROD_MISS); });
 }
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {

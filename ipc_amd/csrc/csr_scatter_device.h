@@ -1,10 +1,13 @@
-// What the element-parallel kernels of the codimensional energies (shell_kernels.hip, rod_kernels.hip) share: the Dirichlet projection rule, the scatter of
-// 3 x 3 blocks into the upper CSR through the row lookup of the contact stencils, and the fixed-order block sum of the energy kernels.  Device only.
+// What the element-parallel kernels of the codimensional energies (shell_kernels.hip, shell_limit_kernels.hip, rod_kernels.hip) share: the Dirichlet
+// projection rule, the scatter of 3 x 3 blocks into the upper CSR through the row lookup of the contact stencils, the fixed-order block sum of the energy
+// kernels and the launch of their reduction.  For .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace ipcgpu {
 namespace scatter {
+
+inline int nblk(int n, int block) { return (n + block - 1) / block; }
 
 __device__ __forceinline__ bool projected_dbc(int type, int projectDBC) { return type == 1 || (type == 2 && projectDBC); }
 
@@ -75,6 +78,15 @@ __device__ __forceinline__ double block_sum(double x, double* sm)
     return r;
 }
 
+// the tail of an energy kernel: partial[blockIdx.x] = the sum of e over the workgroup
+template <int BLOCK>
+__device__ __forceinline__ void store_block_sum(double e, double* __restrict__ partial)
+{
+    __shared__ double sm[BLOCK / 64];
+    const double r = block_sum<BLOCK>(e, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
 // out[0] = (accumulate ? out[0] : 0) + sum of the n partial sums, one workgroup of BLOCK lanes, fixed order
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double* __restrict__ partial, int n, int accumulate, double* __restrict__ out)
@@ -84,6 +96,11 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double* __restr
     for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
     const double r = block_sum<BLOCK>(x, sm);
     if (threadIdx.x == 0) out[0] = accumulate ? out[0] + r : r;
+}
+
+inline void launch_reduce_partials(const double* partial, int n, bool accumulate, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_reduce_partials<256>, dim3(1), dim3(256), 0, s, partial, n, accumulate ? 1 : 0, out);
 }
 
 } // namespace scatter

@@ -41,7 +41,7 @@ struct HipShell {
     // what the shell replaced, put back when it is removed or replaced: the masses its nodes had before (codimensional area masses, or 0) and avgEdgeLen
     std::vector<double> massBefore;
     double avgEdgeLenBefore = 0.0;
-    DevBuf<int> d_tri, d_err;
+    DevBuf<int> d_tri;
     DevBuf<int4> d_hinge;
     DevBuf<double> d_triConst, d_hingeConst;
     int nTri() const { return plan.nTri; }
@@ -65,7 +65,7 @@ struct HipRod {
     double avgEdgeLenBefore = 0.0;
     bool ownsAvgEdgeLen = false;
     DevBuf<int2> d_seg;
-    DevBuf<int> d_bend, d_err;
+    DevBuf<int> d_bend;
     DevBuf<double> d_segConst, d_bendConst;
     int nSeg() const { return plan.nSeg; }
     int nBend() const { return plan.nBend; }
@@ -110,6 +110,12 @@ public:
     // the masses they had before it and lose the mark; the neighbour pairs stay.  With neither a tetrahedron nor a shell in the mesh avgEdgeLen is the mean
     // rest length of the segments while a rod is set.  A rod node may belong to no tetrahedron and no shell triangle (setShell checks the converse).
     HipRod rod;
+    // set to 1 by a codimensional Hessian kernel that finds no block for a node pair in the pattern (csr_scatter_device.h); allocated and zeroed
+    // with the first shell or rod.  The C entry points *_hessian_add read and clear it after their launch; the stepper builds its own pattern and never reads it
+    DevBuf<int> d_codimErr;
+    // what setShell and setRod share: the nodes of the body that is replaced or removed (null: none) get back massBefore and lose the inMesh mark, massBefore
+    // becomes a snapshot of the masses, the new body's nodes take newMass and the mark
+    void replaceBodyMasses(const std::vector<char>* oldNodes, std::vector<double>& massBefore, const std::vector<char>& newNodes, const std::vector<double>& newMass);
     void addNeighbourPairs(const std::vector<int>& pairs); // (lo, hi) pairs into vNeighbor, both directions, sorted and unique
     void setRod(int nSeg, const int* seg_colmajor, const double* radius, const double* YM, const double* rho, double bendScale, hipStream_t s);
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
@@ -269,19 +275,25 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // shell terms (shell_kernels.h): enter wherever the tetrahedral elastic term does, with the same coefficient; every call is guarded on mesh.shell.nTri()
+    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod (the energy sum is
+    // ((E + shell) + limit) + rod) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg()); none of them is ever sharded.
+    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ALL = 7 };
+    CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
-    void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and, with a shell or a rod, their energies on top
-    void shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
-    // the shell's strain limit (shell_limit_kernels.h): part of the shell energy wherever that enters; every launch is guarded on mesh.shell.nLimited()
     ShellLimitView shellLimitView(const double* x_dev) const;
+    RodView rodView(const double* x_dev) const;
+    size_t codimPartials() const; // doubles of d_partial the largest energy launch needs
+    // *out_dev (+)= coef * energy of the chosen terms at x_dev; accumulate == false: the first term launched overwrites *out_dev, the later ones add.  The
+    // limit's energy is +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node
+    void codimEnergyAdd(const double* x_dev, double coef, double* out_dev, bool accumulate, unsigned which = CODIM_ALL);
+    // grad_dev (nullable) += coef * gradient, a_dev (nullable) += coef * PSD Hessian blocks, at x_dev (null: the mesh's positions)
+    void codimAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr, unsigned which = CODIM_ALL);
+    void enqueueElasticEnergy(bool ownerRank, double* out_dev); // launch_energy (elasticity + inertia) and the codimensional energies on top
     // sigma1, sigma2 per triangle (host, 2 nTri, nullable), the maximum of sigma1 / limit and the number of triangles at or over their limit (synchronises)
     void shellStretch(double* sigma_host, double* maxRatio, int* nOver, const double* x_dev = nullptr);
     bool shellLimitFeasible(); // true without a limit; else one stretch query at the current positions
     void requireShellLimitFeasible(); // StateError naming the number of triangles over their limit
-    // rod terms (rod_kernels.h): enter wherever the shell terms do, with the same coefficient; every call is guarded on mesh.rod.nSeg()
-    RodView rodView(const double* x_dev) const;
-    void rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev = nullptr);
     // a mesh without tetrahedra has no patch plan: the node pass initialises the gradient / the matrix diagonal in its place (only with a shell or a rod
     // set: shells only, rods only, or both)
     bool shellOnly() const { return mesh.nT == 0 && (mesh.shell.nTri() > 0 || mesh.rod.nSeg() > 0); }

@@ -168,6 +168,22 @@ void HipMesh::addNeighbourPairs(const std::vector<int>& pairs)
     }
 }
 
+void HipMesh::replaceBodyMasses(const std::vector<char>* oldNodes, std::vector<double>& massBefore, const std::vector<char>& newNodes, const std::vector<double>& newMass)
+{
+    if (oldNodes) // the body this call replaces or removes: its nodes go back to what they were
+        for (int v = 0; v < nV; ++v)
+            if ((*oldNodes)[v]) {
+                mass[v] = massBefore[v];
+                inMesh[v] = 0;
+            }
+    massBefore = mass;
+    for (int v = 0; v < nV; ++v)
+        if (newNodes[v]) {
+            mass[v] = newMass[v];
+            inMesh[v] = 1;
+        }
+}
+
 void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const double* YM, const double* PR, const double* rho, double bendScale, hipStream_t s)
 {
     if (nTri == 0 && shell.nTri() == 0) return; // nothing to remove: no state changes at all
@@ -178,21 +194,9 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     if (rod.nSeg())
         for (int v = 0; v < nV; ++v)
             if (plan.isShellNode[v] && rod.plan.isRodNode[v]) throw ArgError("set_shell: shell node " + std::to_string(v) + " belongs to a rod segment");
-    if (shell.nTri()) { // the shell this call replaces or removes: its nodes go back to what they were
-        for (int v = 0; v < nV; ++v)
-            if (shell.plan.isShellNode[v]) {
-                mass[v] = shell.massBefore[v];
-                inMesh[v] = 0;
-            }
-        avgEdgeLen = shell.avgEdgeLenBefore;
-    }
-    shell.massBefore = mass;
+    if (shell.nTri()) avgEdgeLen = shell.avgEdgeLenBefore; // (the shell this call replaces or removes)
     shell.avgEdgeLenBefore = avgEdgeLen;
-    for (int v = 0; v < nV; ++v)
-        if (plan.isShellNode[v]) {
-            mass[v] = plan.mass[v];
-            inMesh[v] = 1;
-        }
+    replaceBodyMasses(shell.nTri() ? &shell.plan.isShellNode : nullptr, shell.massBefore, plan.isShellNode, plan.mass);
     meshBBox();
     if (nT == 0 && nTri) avgEdgeLen = plan.edgeLenSum / (3.0 * nTri);
     // the plan's pairs join vNeighbor: triangle edges (addSurfaceEdges adds the same ones) and the opposite pair of every hinge
@@ -213,8 +217,10 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     }
     shell.d_hinge.upload(h4.data(), h4.size(), s);
     shell.d_hingeConst.upload(hc, s);
-    shell.d_err.alloc(1);
-    shell.d_err.zero(s);
+    if (!d_codimErr.n) { // the first shell or rod of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -240,25 +246,13 @@ void HipMesh::setRod(int nSeg, const int* seg, const double* radius, const doubl
     RodPlan plan;
     std::string err;
     if (!buildRodPlan(nV, nSeg, seg, V_rest.data(), radius, YM, rho, nT, F.data(), shell.nTri(), shell.plan.tri.data(), plan, err)) throw ArgError(err);
-    if (rod.nSeg()) { // the rod this call replaces or removes: its nodes go back to what they were
-        for (int v = 0; v < nV; ++v)
-            if (rod.plan.isRodNode[v]) {
-                mass[v] = rod.massBefore[v];
-                inMesh[v] = 0;
-            }
-        if (rod.ownsAvgEdgeLen) {
-            // (a shell set after this rod took the rod's mean length for the value to put back: it gets the one from before the rod)
-            if (shell.nTri()) shell.avgEdgeLenBefore = rod.avgEdgeLenBefore;
-            else avgEdgeLen = rod.avgEdgeLenBefore;
-        }
+    if (rod.nSeg() && rod.ownsAvgEdgeLen) { // (the rod this call replaces or removes)
+        // (a shell set after this rod took the rod's mean length for the value to put back: it gets the one from before the rod)
+        if (shell.nTri()) shell.avgEdgeLenBefore = rod.avgEdgeLenBefore;
+        else avgEdgeLen = rod.avgEdgeLenBefore;
     }
-    rod.massBefore = mass;
     rod.avgEdgeLenBefore = avgEdgeLen;
-    for (int v = 0; v < nV; ++v)
-        if (plan.isRodNode[v]) {
-            mass[v] = plan.mass[v];
-            inMesh[v] = 1;
-        }
+    replaceBodyMasses(rod.nSeg() ? &rod.plan.isRodNode : nullptr, rod.massBefore, plan.isRodNode, plan.mass);
     meshBBox();
     rod.ownsAvgEdgeLen = nT == 0 && shell.nTri() == 0 && nSeg > 0;
     if (rod.ownsAvgEdgeLen) avgEdgeLen = plan.lenSum / nSeg;
@@ -280,8 +274,10 @@ void HipMesh::setRod(int nSeg, const int* seg, const double* radius, const doubl
     }
     rod.d_bend.upload(b3, s);
     rod.d_bendConst.upload(bc, s);
-    rod.d_err.alloc(1);
-    rod.d_err.zero(s);
+    if (!d_codimErr.n) { // the first shell or rod of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -17,6 +17,7 @@
 #include <iterator>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #ifndef BEGIN_BATCHED
 #define BEGIN_BATCHED 1 // 0: the time-step set-up of the contact-free twist question by question, as in rounds 1-5 (A/B: profiles/r06_begin_timestep_batch_ab.txt)
@@ -71,63 +72,43 @@ ElemView HipOptimizer::view() const
     return v;
 }
 
+// the kernel argument of every view holds the term's own fields first and the shared ones behind them (codim_view.h): a reorder changes the kernels' code
+#define CODIM_VIEW_LAYOUT(View, Fields, first)                                                                                              \
+    static_assert(std::is_trivially_copyable<View>::value && sizeof(View) == sizeof(Fields) + sizeof(CodimBase) && __builtin_offsetof(View, first) == 0 \
+            && __builtin_offsetof(View, x) == sizeof(Fields),                                                                                    \
+        #View " is " #Fields " followed by CodimBase, nothing else")
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof" // (the views are not standard-layout: two bases with fields; the offsets are the ABI's all the same)
+CODIM_VIEW_LAYOUT(ShellView, ShellFields, nTri);
+CODIM_VIEW_LAYOUT(ShellLimitView, ShellLimitFields, nTri);
+CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
+#pragma clang diagnostic pop
+#undef CODIM_VIEW_LAYOUT
+
+CodimBase HipOptimizer::codimBase(const double* x_dev) const
+{
+    return CodimBase{ x_dev, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, lin.d_ja.p };
+}
+
 ShellView HipOptimizer::shellView(const double* x_dev) const
 {
     const HipShell& sh = mesh.shell;
     ShellView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
     v.nTri = sh.nTri();
     v.nHinge = sh.nHinge();
     v.tri = sh.d_tri.p;
     v.triConst = sh.d_triConst.p;
     v.hinge = sh.d_hinge.p;
     v.hingeConst = sh.d_hingeConst.p;
-    v.x = x_dev;
-    v.dbc = mesh.d_dbc.p;
-    v.rowBase = lin.d_rowBase.p;
-    v.rowLen = lin.d_rowLen.p;
-    v.ja = lin.d_ja.p;
     return v;
-}
-
-RodView HipOptimizer::rodView(const double* x_dev) const
-{
-    const HipRod& r = mesh.rod;
-    RodView v;
-    v.nSeg = r.nSeg();
-    v.nBend = r.nBendActive();
-    v.seg = r.d_seg.p;
-    v.segConst = r.d_segConst.p;
-    v.bend = r.d_bend.p;
-    v.bendConst = r.d_bendConst.p;
-    v.x = x_dev;
-    v.dbc = mesh.d_dbc.p;
-    v.rowBase = lin.d_rowBase.p;
-    v.rowLen = lin.d_rowLen.p;
-    v.ja = lin.d_ja.p;
-    return v;
-}
-
-void HipOptimizer::enqueueElasticEnergy(bool ownerRank, double* out_dev)
-{
-    launch_energy(view(), elasticCoef(), true, ownerRank, d_partial.p, (int)d_partial.n, out_dev, stream);
-    if (mesh.shell.nTri()) launch_shell_energy(shellView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_shell)
-    // the strain limit: +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node
-    if (mesh.shell.nLimited()) launch_shell_limit_energy(shellLimitView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream);
-    if (mesh.rod.nSeg()) launch_rod_energy(rodView(mesh.d_x.p), elasticCoef(), d_partial.p, out_dev, /*accumulate=*/true, stream); // (never sharded: ipcgpu_set_rod)
-}
-
-void HipOptimizer::shellAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
-{
-    if (!mesh.shell.nTri()) return;
-    launch_shell_assemble(shellView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
-    if (mesh.shell.nLimited())
-        launch_shell_limit_assemble(shellLimitView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.shell.d_err.p, stream);
 }
 
 ShellLimitView HipOptimizer::shellLimitView(const double* x_dev) const
 {
     const HipShell& sh = mesh.shell;
     ShellLimitView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
     v.nTri = sh.nTri();
     v.nLimited = sh.nLimited();
     v.tri = sh.d_tri.p;
@@ -135,12 +116,70 @@ ShellLimitView HipOptimizer::shellLimitView(const double* x_dev) const
     v.limTri = sh.d_limTri.p;
     v.limConst = sh.d_limConst.p;
     v.triLimit = sh.nLimited() ? sh.d_triLimit.p : nullptr;
-    v.x = x_dev;
-    v.dbc = mesh.d_dbc.p;
-    v.rowBase = lin.d_rowBase.p;
-    v.rowLen = lin.d_rowLen.p;
-    v.ja = lin.d_ja.p;
     return v;
+}
+
+RodView HipOptimizer::rodView(const double* x_dev) const
+{
+    const HipRod& r = mesh.rod;
+    RodView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nSeg = r.nSeg();
+    v.nBend = r.nBendActive();
+    v.seg = r.d_seg.p;
+    v.segConst = r.d_segConst.p;
+    v.bend = r.d_bend.p;
+    v.bendConst = r.d_bendConst.p;
+    return v;
+}
+
+// The codimensional terms, one row each, in launch order.  A new term is a kernel file, a view builder and a row here.
+namespace {
+struct CodimTerm {
+    unsigned bit;
+    int (*lanes)(const HipMesh&); // lanes of its energy kernel; 0: the mesh has no such term and nothing of it is launched
+    void (*energy)(const HipOptimizer&, const double* x, double coef, double* partial, double* out, bool accumulate);
+    void (*assemble)(const HipOptimizer&, const double* x, double coef, int projectDBC, double* grad, double* a, int* err);
+};
+const CodimTerm CODIM_TERMS[] = {
+    { HipOptimizer::CODIM_SHELL, [](const HipMesh& m) { return m.shell.nTri() ? m.shell.nTri() + m.shell.nHinge() : 0; },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_energy(o.shellView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_assemble(o.shellView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_SHELL_LIMIT, [](const HipMesh& m) { return m.shell.nLimited(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_limit_energy(o.shellLimitView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_limit_assemble(o.shellLimitView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_ROD, [](const HipMesh& m) { return m.rod.nSeg() ? m.rod.nSeg() + m.rod.nBend() : 0; },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_rod_energy(o.rodView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_rod_assemble(o.rodView(x), coef, proj, g, a, err, o.stream); } },
+};
+} // namespace
+
+size_t HipOptimizer::codimPartials() const
+{
+    size_t n = 0;
+    for (const CodimTerm& t : CODIM_TERMS) n = std::max(n, (size_t)t.lanes(mesh));
+    return n;
+}
+
+void HipOptimizer::codimEnergyAdd(const double* x_dev, double coef, double* out_dev, bool accumulate, unsigned which)
+{
+    for (const CodimTerm& t : CODIM_TERMS) {
+        if (!(which & t.bit) || !t.lanes(mesh)) continue;
+        t.energy(*this, x_dev, coef, d_partial.p, out_dev, accumulate);
+        accumulate = true;
+    }
+}
+
+void HipOptimizer::codimAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev, unsigned which)
+{
+    for (const CodimTerm& t : CODIM_TERMS)
+        if ((which & t.bit) && t.lanes(mesh)) t.assemble(*this, x_dev ? x_dev : mesh.d_x.p, coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.d_codimErr.p);
+}
+
+void HipOptimizer::enqueueElasticEnergy(bool ownerRank, double* out_dev)
+{
+    launch_energy(view(), elasticCoef(), true, ownerRank, d_partial.p, (int)d_partial.n, out_dev, stream);
+    codimEnergyAdd(mesh.d_x.p, elasticCoef(), out_dev, /*accumulate=*/true);
 }
 
 void HipOptimizer::shellStretch(double* sigma_host, double* maxRatio, int* nOver, const double* x_dev)
@@ -181,12 +220,6 @@ void HipOptimizer::requireShellLimitFeasible()
         throw StateError(std::to_string(nOver) + " shell triangle" + (nOver == 1 ? " has" : "s have") + " a principal stretch at or over the strain limit at the start of the time step");
 }
 
-void HipOptimizer::rodAssembleAdd(double coef, bool projectDBC, double* grad_dev, double* a_dev, const double* x_dev)
-{
-    if (!mesh.rod.nSeg()) return;
-    launch_rod_assemble(rodView(x_dev ? x_dev : mesh.d_x.p), coef, projectDBC ? 1 : 0, grad_dev, a_dev, mesh.rod.d_err.p, stream);
-}
-
 void HipOptimizer::init(double dt_, bool withGravity)
 {
     dt = dt_;
@@ -208,8 +241,7 @@ void HipOptimizer::init(double dt_, bool withGravity)
     d_gradient.zero(stream);
     d_minusG.alloc(n3);
     d_x0.alloc(n3);
-    d_partial.alloc(std::max({ (size_t)std::max(mesh.nT, mesh.nV), (size_t)mesh.shell.nTri() + (size_t)mesh.shell.nHinge(),
-                        (size_t)mesh.rod.nSeg() + (size_t)mesh.rod.nBend() }) / 256 + 2);
+    d_partial.alloc(std::max((size_t)std::max(mesh.nT, mesh.nV), codimPartials()) / 256 + 2);
     d_scalar.alloc(8);
     d_flag.alloc(2); // [0] the inversion flag of the stepper, [1] a second one for batches that test two states (beginTimestep)
     h_scalar.alloc(8);
@@ -472,8 +504,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    shellAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell Hessian at the damping positions
-    rodAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // ... and the rod Hessian
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell, limit and rod Hessians at the damping positions
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -958,8 +989,7 @@ void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
     if (lin.rowBase.empty() || shellOnly()) { // no pattern yet (or no tetrahedron, hence no patch plan): tet-parallel atomic path
         launch_node_init(view(), projectDBC, rank == 0, nullptr, d_gradient.p, stream);
         launch_assemble(view(), elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
-        shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
-        rodAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
+        codimAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
         reduceSum(d_gradient.p, 3LL * mesh.nV);
         neumannGradientAdd(d_gradient.p);
         return;
@@ -979,8 +1009,7 @@ void HipOptimizer::elasticInertiaGradient(bool projectDBC, bool finish)
     patchShard(pb, pe);
     if (worldSize > 1) d_gradient.zero(stream);
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, d_gradient.p, nullptr, stream);
-    shellAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
-    rodAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
+    codimAssembleAdd(elasticCoef(), projectDBC, d_gradient.p, nullptr);
     reduceSum(d_gradient.p, 3LL * mesh.nV);
     neumannGradientAdd(d_gradient.p);
 }
@@ -1149,8 +1178,7 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
     }
     launch_assemble_patches(view(), patch, pb, pe, elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p, stream,
         owner ? d_ownerPatches.p : nullptr);
-    shellAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
-    rodAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
+    codimAssembleAdd(elasticCoef(), projectDBC, withGradient ? d_gradient.p : nullptr, lin.d_a.p);
     matrixComplete = !owner;
     if (owner) {
         if (withGradient) ownerGradientTail(projectDBC);
@@ -1256,8 +1284,7 @@ void HipOptimizer::speculativeAssembly()
         launch_node_init(view(), 1, true, d_aSpec.p, d_gradSpec.p, stream);
     }
     launch_assemble_patches(view(), patch, 0, patch.nPatches, elasticCoef(), 1, d_gradSpec.p, d_aSpec.p, stream); // what computePrecondMtr(true, true) launches on this path
-    shellAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
-    rodAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
+    codimAssembleAdd(elasticCoef(), true, d_gradSpec.p, d_aSpec.p);
     if (timeIt) {
         HIP_CHECK(hipEventRecord(evAsm1, stream));
         evAsmPending = true;

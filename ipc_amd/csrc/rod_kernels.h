@@ -20,23 +20,19 @@
 // atomicAdd through the row lookup of csr_scatter_device.h (3 upper blocks per segment, 6 per triple); rows, columns and gradient entries of projected
 // Dirichlet nodes are dropped (Energy.cpp:402-407), the diagonal identity stays with the node pass of the elastic assembly.
 #pragma once
+#include "codim_view.h"
 #include <hip/hip_runtime.h>
 
 namespace ipcgpu {
 
-struct RodView {
+struct RodFields {
     int nSeg, nBend;
     const int2* seg; // nSeg: a, b
     const double* segConst; // SoA [2][nSeg]: L, k_s (rod_plan.h)
     const int* bend; // SoA [3][nBend]: a, b, c
     const double* bendConst; // nBend: bendScale k_b
-    const double* x; // positions, xyz interleaved
-    const int* dbc; // nV, DirichletBCType
-    // CSR map (valid after set_pattern; only the Hessian kernels read it)
-    const int* rowBase; // nV: ia[3 v]
-    const int* rowLen; // nV: ia[3 v + 1] - ia[3 v]
-    const int* ja;
 };
+struct RodView : RodFields, CodimBase {}; // (the shared fields behind the term's own: codim_view.h)
 
 int rod_energy_blocks(const RodView& v); // partial sums launch_rod_energy writes
 // *out (device) = (accumulate ? *out : 0) + coef * (stretching + bending energy); partial: rod_energy_blocks(v) doubles.  Deterministic: fixed order.

@@ -12,7 +12,7 @@ namespace ipcgpu {
 
 namespace {
 
-using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, block_sum (csr_scatter_device.h)
+using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, store_block_sum, nblk, launch_reduce_partials (csr_scatter_device.h)
 
 constexpr int ROD_BLOCK = 256;
 
@@ -64,13 +64,11 @@ __device__ __forceinline__ double bend_energy(const RodView& v, int i)
 
 __global__ __launch_bounds__(ROD_BLOCK) void k_rod_energy(RodView v, double coef, double* __restrict__ partial)
 {
-    __shared__ double sm[ROD_BLOCK / 64];
     const int gid = blockIdx.x * ROD_BLOCK + threadIdx.x;
     double e = 0.0;
     if (gid < v.nSeg) e = coef * stretch_energy(v, gid);
     else if (gid - v.nSeg < v.nBend) e = coef * bend_energy(v, gid - v.nSeg);
-    const double r = block_sum<ROD_BLOCK>(e, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    store_block_sum<ROD_BLOCK>(e, partial);
 }
 __global__ __launch_bounds__(ROD_BLOCK) void k_rod_energy_per_elem(RodView v, double* __restrict__ perSeg, double* __restrict__ perBend)
 {
@@ -199,8 +197,6 @@ __global__ __launch_bounds__(ROD_BLOCK) void k_rod_bend(RodView v, double coef, 
     }
 }
 
-inline int nblk(int n, int block) { return (n + block - 1) / block; }
-
 } // namespace
 
 int rod_energy_blocks(const RodView& v) { return std::max(1, nblk(v.nSeg + v.nBend, ROD_BLOCK)); }
@@ -209,7 +205,7 @@ void launch_rod_energy(const RodView& v, double coef, double* partial, double* o
 {
     const int nb = rod_energy_blocks(v);
     hipLaunchKernelGGL(k_rod_energy, dim3(nb), dim3(ROD_BLOCK), 0, s, v, coef, partial);
-    hipLaunchKernelGGL(k_reduce_partials<ROD_BLOCK>, dim3(1), dim3(ROD_BLOCK), 0, s, partial, nb, accumulate ? 1 : 0, out);
+    launch_reduce_partials(partial, nb, accumulate, out, s);
 }
 void launch_rod_energy_per_elem(const RodView& v, double* perSeg, double* perBend, hipStream_t s)
 {

@@ -18,23 +18,19 @@
 // same row lookup as the contact stencils use (binary search of column 3 * max in row 3 * min); rows, columns and gradient entries of projected Dirichlet
 // nodes are dropped (Energy.cpp:402-407), the diagonal identity stays with the node pass of the elastic assembly.
 #pragma once
+#include "codim_view.h"
 #include <hip/hip_runtime.h>
 
 namespace ipcgpu {
 
-struct ShellView {
+struct ShellFields {
     int nTri, nHinge;
     const int* tri; // 3 nTri
     const double* triConst; // SoA [6][nTri]: Dm^-1 (b00, b10, b01, b11), h A mu, h A lambda_ps (shell_plan.h)
     const int4* hinge; // nHinge: x0, x1 on the edge, x2, x3 opposite
     const double* hingeConst; // SoA [2][nHinge]: thetaBar, bendScale k_b w_e
-    const double* x; // positions, xyz interleaved
-    const int* dbc; // nV, DirichletBCType
-    // CSR map (valid after set_pattern; only the Hessian kernels read it)
-    const int* rowBase; // nV: ia[3 v]
-    const int* rowLen; // nV: ia[3 v + 1] - ia[3 v]
-    const int* ja;
 };
+struct ShellView : ShellFields, CodimBase {}; // (the shared fields behind the term's own: codim_view.h)
 
 int shell_energy_blocks(const ShellView& v); // partial sums launch_shell_energy writes
 // *out (device) = (accumulate ? *out : 0) + coef * (membrane + bending energy); partial: shell_energy_blocks(v) doubles.  Deterministic: fixed order.

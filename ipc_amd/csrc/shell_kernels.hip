@@ -17,7 +17,7 @@ constexpr int ENERGY_BLOCK = 256;
 constexpr int MEMBRANE_BLOCK = 64;
 constexpr int HINGE_BLOCK = 256;
 
-using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, block_sum (csr_scatter_device.h)
+using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, store_block_sum, nblk, launch_reduce_partials (csr_scatter_device.h)
 
 // ---- membrane ----------------------------------------------------------------------------------------------------------------------------
 struct Membrane {
@@ -129,13 +129,11 @@ __device__ __forceinline__ double hinge_energy(const ShellView& v, int h)
 
 __global__ __launch_bounds__(ENERGY_BLOCK) void k_shell_energy(ShellView v, double coef, double* __restrict__ partial)
 {
-    __shared__ double sm[ENERGY_BLOCK / 64];
     const int gid = blockIdx.x * ENERGY_BLOCK + threadIdx.x;
     double e = 0.0;
     if (gid < v.nTri) e = coef * triangle_energy(v, gid);
     else if (gid - v.nTri < v.nHinge) e = coef * hinge_energy(v, gid - v.nTri);
-    const double r = block_sum<ENERGY_BLOCK>(e, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    store_block_sum<ENERGY_BLOCK>(e, partial);
 }
 __global__ __launch_bounds__(ENERGY_BLOCK) void k_shell_energy_per_elem(ShellView v, double* __restrict__ perTri, double* __restrict__ perHinge)
 {
@@ -255,8 +253,6 @@ __global__ __launch_bounds__(HINGE_BLOCK) void k_shell_hinge(ShellView v, double
     }
 }
 
-inline int nblk(int n, int block) { return (n + block - 1) / block; }
-
 } // namespace
 
 int shell_energy_blocks(const ShellView& v) { return std::max(1, nblk(v.nTri + v.nHinge, ENERGY_BLOCK)); }
@@ -265,7 +261,7 @@ void launch_shell_energy(const ShellView& v, double coef, double* partial, doubl
 {
     const int nb = shell_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_energy, dim3(nb), dim3(ENERGY_BLOCK), 0, s, v, coef, partial);
-    hipLaunchKernelGGL(k_reduce_partials<ENERGY_BLOCK>, dim3(1), dim3(ENERGY_BLOCK), 0, s, partial, nb, accumulate ? 1 : 0, out);
+    launch_reduce_partials(partial, nb, accumulate, out, s);
 }
 void launch_shell_energy_per_elem(const ShellView& v, double* perTri, double* perHinge, hipStream_t s)
 {

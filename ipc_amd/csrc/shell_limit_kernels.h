@@ -24,24 +24,20 @@
 // One lane per limited triangle.  Gradient entries and the six upper 3 x 3 blocks (the membrane's: no new node pairs) go through csr_scatter_device.h; rows,
 // columns and gradient entries of projected Dirichlet nodes are dropped.  Without a limit (nLimited == 0) nothing here is launched.
 #pragma once
+#include "codim_view.h"
 #include <hip/hip_runtime.h>
 
 namespace ipcgpu {
 
-struct ShellLimitView {
+struct ShellLimitFields {
     int nTri, nLimited;
     const int* tri; // 3 nTri (the shell's)
     const double* triConst; // SoA [6][nTri] (the shell's; the first four rows, Dm^-1, are read)
     const int* limTri; // nLimited: indices of the limited triangles
     const double* limConst; // SoA [3][nLimited]: onset, limit, k (shell_limit_plan.h)
     const double* triLimit; // nTri: limit per triangle, 0 = none; null without a limit (only the stretch kernel reads it)
-    const double* x; // positions, xyz interleaved
-    const int* dbc; // nV, DirichletBCType
-    // CSR map (valid after set_pattern; only the Hessian kernel reads it)
-    const int* rowBase;
-    const int* rowLen;
-    const int* ja;
 };
+struct ShellLimitView : ShellLimitFields, CodimBase {}; // (the shared fields behind the term's own: codim_view.h)
 
 int shell_limit_energy_blocks(const ShellLimitView& v); // partial sums launch_shell_limit_energy writes
 // *out (device) = (accumulate ? *out : 0) + coef * barrier energy, +infinity with a stretch at or over its limit; partial: shell_limit_energy_blocks(v) doubles.

@@ -14,7 +14,7 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, block_sum (csr_scatter_device.h)
+using namespace scatter; // projected_dbc, ld3, CsrSink, add_diag, add_off, block_sum, store_block_sum, nblk, launch_reduce_partials (csr_scatter_device.h)
 
 struct Stretch {
     double f1[3], f2[3]; // columns of F
@@ -95,15 +95,13 @@ __device__ __forceinline__ double limit_energy(const ShellLimitView& v, int i)
 
 __global__ __launch_bounds__(BLOCK) void k_shell_limit_energy(ShellLimitView v, double coef, double* __restrict__ partial)
 {
-    __shared__ double sm[BLOCK / 64];
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     double e = 0.0;
     if (i < v.nLimited) {
         e = limit_energy(v, i);
         if (e != 0.0) e *= coef; // (coef > 0: an infinite term stays +infinity)
     }
-    const double r = block_sum<BLOCK>(e, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    store_block_sum<BLOCK>(e, partial);
 }
 __global__ __launch_bounds__(BLOCK) void k_shell_limit_energy_per_elem(ShellLimitView v, double* __restrict__ perTri)
 {
@@ -274,30 +272,28 @@ __global__ __launch_bounds__(BLOCK) void k_shell_stretch_reduce(const double* __
     }
 }
 
-inline int nblk(int n) { return (n + BLOCK - 1) / BLOCK; }
-
 } // namespace
 
-int shell_limit_energy_blocks(const ShellLimitView& v) { return std::max(1, nblk(v.nLimited)); }
-int shell_stretch_blocks(const ShellLimitView& v) { return std::max(1, nblk(v.nTri)); }
+int shell_limit_energy_blocks(const ShellLimitView& v) { return std::max(1, nblk(v.nLimited, BLOCK)); }
+int shell_stretch_blocks(const ShellLimitView& v) { return std::max(1, nblk(v.nTri, BLOCK)); }
 
 void launch_shell_limit_energy(const ShellLimitView& v, double coef, double* partial, double* out, bool accumulate, hipStream_t s)
 {
     const int nb = shell_limit_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_limit_energy, dim3(nb), dim3(BLOCK), 0, s, v, coef, partial);
-    hipLaunchKernelGGL(k_reduce_partials<BLOCK>, dim3(1), dim3(BLOCK), 0, s, partial, nb, accumulate ? 1 : 0, out);
+    launch_reduce_partials(partial, nb, accumulate, out, s);
 }
 void launch_shell_limit_energy_per_elem(const ShellLimitView& v, double* perTri, hipStream_t s)
 {
     if (v.nTri <= 0) return;
     (void)hipMemsetAsync(perTri, 0, sizeof(double) * (size_t)v.nTri, s);
-    if (v.nLimited > 0) hipLaunchKernelGGL(k_shell_limit_energy_per_elem, dim3(nblk(v.nLimited)), dim3(BLOCK), 0, s, v, perTri);
+    if (v.nLimited > 0) hipLaunchKernelGGL(k_shell_limit_energy_per_elem, dim3(nblk(v.nLimited, BLOCK)), dim3(BLOCK), 0, s, v, perTri);
 }
 void launch_shell_limit_assemble(const ShellLimitView& v, double coef, int projectDBC, double* grad, double* a, int* err, hipStream_t s)
 {
     if (v.nLimited <= 0) return;
-    if (a) hipLaunchKernelGGL(k_shell_limit<true>, dim3(nblk(v.nLimited)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a, err);
-    else hipLaunchKernelGGL(k_shell_limit<false>, dim3(nblk(v.nLimited)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a, err);
+    if (a) hipLaunchKernelGGL(k_shell_limit<true>, dim3(nblk(v.nLimited, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a, err);
+    else hipLaunchKernelGGL(k_shell_limit<false>, dim3(nblk(v.nLimited, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a, err);
 }
 void launch_shell_stretch(const ShellLimitView& v, double* sigma, double* partial, double* out2, hipStream_t s)
 {

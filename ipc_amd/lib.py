@@ -527,6 +527,20 @@ class Context:
         m = _f64(np.asarray(mass, dtype=np.float64))
         self._chk(self._L.ipcgpu_set_codim_nodes(self.h, C.c_int(len(ids)), _ip(ids), _dp(m)))
 
+    # ---- what the methods of the codimensional energies (shell_*, shell_limit_*, rod_*) share: `term` is the middle of the entry point's name
+    def _codim_energy(self, term, coef):
+        e = C.c_double()
+        self._chk(getattr(self._L, f"ipcgpu_{term}_energy")(self.h, C.c_double(coef), C.byref(e)))
+        return e.value
+
+    def _codim_gradient_add(self, term, coef, projectDBC, grad):
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(getattr(self._L, f"ipcgpu_{term}_gradient_add")(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
+        return g
+
+    def _codim_hessian_add(self, term, coef, projectDBC):
+        self._chk(getattr(self._L, f"ipcgpu_{term}_hessian_add")(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+
     # ---- elastic shells (ipcgpu_set_shell: membrane + bending energy on triangle components)
     def set_shell(self, tri, thickness, YM, PR, rho, bend_scale=1.0):
         """tri: nTri x 3 node ids; thickness, YM, PR, rho: scalars or one value per triangle.  After set_mesh, before opt_init and set_pattern; sets the
@@ -547,9 +561,7 @@ class Context:
         return {"nTri": nTri, "nHinge": nH, "hinges": hinges, "restAngle": rest, "hingeWeight": w, "area": area, "mass": mass}
 
     def shell_energy(self, coef=1.0):
-        e = C.c_double()
-        self._chk(self._L.ipcgpu_shell_energy(self.h, C.c_double(coef), C.byref(e)))
-        return e.value
+        return self._codim_energy("shell", coef)
 
     def shell_energy_per_elem(self):
         cnt = np.zeros(2, dtype=np.int32)
@@ -560,12 +572,10 @@ class Context:
 
     def shell_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
         """grad (3 nV, xyz interleaved; zeros when None) += coef * shell gradient; returns it"""
-        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
-        self._chk(self._L.ipcgpu_shell_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
-        return g
+        return self._codim_gradient_add("shell", coef, projectDBC, grad)
 
     def shell_hessian_add(self, coef=1.0, projectDBC=True):
-        self._chk(self._L.ipcgpu_shell_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+        self._codim_hessian_add("shell", coef, projectDBC)
 
     # ---- strain limit of the shell (ipcgpu_shell_set_strain_limit: a log barrier on the principal stretches of the limited triangles)
     def _shell_ntri(self):
@@ -581,9 +591,7 @@ class Context:
         self._chk(self._L.ipcgpu_shell_set_strain_limit(self.h, _dp(per[0]), _dp(per[1]), _dp(per[2])))
 
     def shell_limit_energy(self, coef=1.0):
-        e = C.c_double()
-        self._chk(self._L.ipcgpu_shell_limit_energy(self.h, C.c_double(coef), C.byref(e)))
-        return e.value
+        return self._codim_energy("shell_limit", coef)
 
     def shell_limit_energy_per_elem(self):
         """the unscaled barrier energy per shell triangle (0 for an unlimited one, inf at or over the limit)"""
@@ -593,12 +601,10 @@ class Context:
 
     def shell_limit_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
         """grad (3 nV, xyz interleaved; zeros when None) += coef * gradient of the limit term; returns it"""
-        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
-        self._chk(self._L.ipcgpu_shell_limit_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
-        return g
+        return self._codim_gradient_add("shell_limit", coef, projectDBC, grad)
 
     def shell_limit_hessian_add(self, coef=1.0, projectDBC=True):
-        self._chk(self._L.ipcgpu_shell_limit_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+        self._codim_hessian_add("shell_limit", coef, projectDBC)
 
     def shell_stretch(self):
         """(sigma (nTri x 2: the principal stretches sigma1 >= sigma2 of every shell triangle), the maximum of sigma1 / limit over the limited triangles --
@@ -628,9 +634,7 @@ class Context:
         return {"nSeg": nSeg, "nBend": nB, "bend": bend, "restLen": L, "ks": ks, "kb": kb, "restKb": rest, "mass": mass}
 
     def rod_energy(self, coef=1.0):
-        e = C.c_double()
-        self._chk(self._L.ipcgpu_rod_energy(self.h, C.c_double(coef), C.byref(e)))
-        return e.value
+        return self._codim_energy("rod", coef)
 
     def rod_energy_per_elem(self):
         cnt = np.zeros(2, dtype=np.int32)
@@ -641,12 +645,10 @@ class Context:
 
     def rod_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
         """grad (3 nV, xyz interleaved; zeros when None) += coef * rod gradient; returns it"""
-        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
-        self._chk(self._L.ipcgpu_rod_gradient_add(self.h, C.c_double(coef), C.c_int(int(projectDBC)), _dp(g)))
-        return g
+        return self._codim_gradient_add("rod", coef, projectDBC, grad)
 
     def rod_hessian_add(self, coef=1.0, projectDBC=True):
-        self._chk(self._L.ipcgpu_rod_hessian_add(self.h, C.c_double(coef), C.c_int(int(projectDBC))))
+        self._codim_hessian_add("rod", coef, projectDBC)
 
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)

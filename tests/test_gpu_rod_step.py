@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import rod_mp as rmp
+from codim_common import five_tet_cube, step_context
 from ipc_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -17,25 +18,7 @@ NO_SF = np.zeros((0, 3), dtype=np.int32)
 
 
 def rod_context(gpu_lib, V, seg, solver=0, bend=1.0, T=None, dt=0.01, gravity=True, held=None, x0=None, r=R, E=YM):
-    c = gpu_lib.Context(0, solver=solver)
-    c.set_mesh(V, NO_T if T is None else T, YM=YM, PR=0.4, density=RHO)
-    c.set_rod(seg, r, E, RHO, bend_scale=bend)
-    if x0 is not None:
-        c.set_positions(x0)
-    c.opt_init(dt, gravity)
-    c.set_time_integration("BE")
-    if held is not None and len(held):
-        c.add_dirichlet(np.asarray(held, dtype=np.int32))
-    return c
-
-
-def five_tet_cube(size, lo):
-    P = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], dtype=np.float64) * size + lo
-    T = np.array([[1, 3, 4, 6], [0, 1, 3, 4], [2, 3, 1, 6], [5, 4, 6, 1], [7, 6, 4, 3]], dtype=np.int32)
-    for t in T:  # positive volumes
-        if np.linalg.det(P[t[1:]] - P[t[0]]) < 0:
-            t[[2, 3]] = t[[3, 2]]
-    return P, T
+    return step_context(gpu_lib, V, lambda c: c.set_rod(seg, r, E, RHO, bend_scale=bend), solver, T, YM, RHO, dt, gravity, held, x0)
 
 
 @pytest.mark.parametrize("solver", SOLVERS)

@@ -4,6 +4,7 @@ block are its own; the tolerance is shell_limit_mp.tolerance = M (sens + u scale
 import numpy as np
 import pytest
 
+import codim_common as cc
 import shell_limit_mp as lmp
 
 pytestmark = pytest.mark.gpu
@@ -62,24 +63,6 @@ def unlimited(gpu_lib):
     return Carrier(gpu_lib, lmp.load(), limited=False)
 
 
-def _compare(cases, k, got_of, coef, proj, worst, bad, where):
-    for i, cs in enumerate(cases):
-        ref, tol = lmp.expected(cs, k, coef, proj)
-        got = got_of(i)
-        if k == "E" and ref == np.inf:
-            if not got == np.inf:
-                bad.append(f"{cs['name']} E {where}: {got} instead of +inf")
-            continue
-        if k == "H":
-            ref = np.triu(ref)  # the upper CSR: the lower triangle of `got` is zero like the reference's here
-            tol = np.triu(tol)
-        assert np.all(np.isfinite(got)), (cs["name"], k)
-        r = float(np.max(lmp.ratio(got - ref, tol / lmp.M)))
-        worst[k] = max(worst.get(k, 0.0), r)
-        if not r <= lmp.M:
-            bad.append(f"{cs['name']} {k} {where}: err / (sens + u scale) = {r:.3g}")
-
-
 def test_energy_gradient_hessian_against_mpmath(carrier):
     c, cases, off = carrier.c, carrier.cases, carrier.off
     worst, bad = {}, []
@@ -87,15 +70,15 @@ def test_energy_gradient_hessian_against_mpmath(carrier):
     assert np.all(perTri[carrier.limit == 0] == 0.0)
     for coef in COEFS:
         assert c.shell_limit_energy(coef) == np.inf  # the case over its limit: +infinity, not NaN
-        _compare(cases, "E", lambda i: coef * perTri[carrier.triOwner == i].sum(), coef, True, worst, bad, f"coef {coef:g}")
+        cc.compare(lmp, cases, "E", lambda i: coef * perTri[carrier.triOwner == i].sum(), coef, True, worst, bad, f"coef {coef:g}")
         for proj in (True, False):
             g = c.shell_limit_gradient_add(coef, proj)
             c.set_zero()
             c.shell_limit_hessian_add(coef, proj)
             A = carrier.dense_upper()
             where = f"coef {coef:g} projectDBC {int(proj)}"
-            _compare(cases, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
-            _compare(cases, "H", lambda i: A[3 * off[i]:3 * off[i + 1], 3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
+            cc.compare(lmp, cases, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
+            cc.compare(lmp, cases, "H", lambda i: A[3 * off[i]:3 * off[i + 1], 3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
             dropped = np.repeat((carrier.dbc == 1) | ((carrier.dbc == 2) & proj), 3)
             assert np.all(g[dropped] == 0.0) and np.all(A[dropped, :] == 0.0) and np.all(A[:, dropped] == 0.0)
             for i in range(len(cases)):  # nothing between the components

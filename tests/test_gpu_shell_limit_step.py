@@ -7,6 +7,7 @@ import pytest
 import rod_mp as rmp
 import shell_limit_mp as lmp
 import shell_mp as smp
+from codim_common import five_tet_cube, step_context
 from ipc_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -18,18 +19,11 @@ ONE_TRI = np.array([[0, 1, 2]], dtype=np.int32)
 
 
 def context(gpu_lib, V, tri, E, rho=1000.0, limit=None, onset=None, stiff=None, T=None, dt=0.01, gravity=True, held=None, x0=None, solver=0):
-    c = gpu_lib.Context(0, solver=solver)
-    c.set_mesh(V, NO_T if T is None else T, YM=1e7, PR=0.4, density=1000.0)
-    c.set_shell(tri, H, E, PR, rho)
-    if limit is not None:
-        c.set_shell_strain_limit(limit, onset, stiff)
-    if x0 is not None:
-        c.set_positions(x0)
-    c.opt_init(dt, gravity)
-    c.set_time_integration("BE")
-    if held is not None and len(held):
-        c.add_dirichlet(np.asarray(held, dtype=np.int32))
-    return c
+    def set_body(c):
+        c.set_shell(tri, H, E, PR, rho)
+        if limit is not None:
+            c.set_shell_strain_limit(limit, onset, stiff)
+    return step_context(gpu_lib, V, set_body, solver, T, 1e7, 1000.0, dt, gravity, held, x0)
 
 
 def hanging_strip():
@@ -106,15 +100,6 @@ def test_limit_never_reached_leaves_the_run_bit_identical(gpu_lib):
         if limit:
             assert c.shell_limit_energy() == 0.0 and 0.0 < c.shell_stretch()[1] < 0.2
     assert np.array_equal(out[0], out[1]) and np.abs(out[0] - ONE_V * 1.2).max() > 1e-3
-
-
-def five_tet_cube(size, lo):
-    P = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], dtype=np.float64) * size + lo
-    T = np.array([[1, 3, 4, 6], [0, 1, 3, 4], [2, 3, 1, 6], [5, 4, 6, 1], [7, 6, 4, 3]], dtype=np.int32)
-    for t in T:  # positive volumes
-        if np.linalg.det(P[t[1:]] - P[t[0]]) < 0:
-            t[[2, 3]] = t[[3, 2]]
-    return P, T
 
 
 def test_strip_dropped_onto_a_block_and_a_plane_stays_feasible(gpu_lib):

@@ -4,6 +4,7 @@ shell_mp.tolerance = M (sens + u scale), derived there and pinned on the CPU by 
 import numpy as np
 import pytest
 
+import codim_common as cc
 import shell_mp as smp
 
 pytestmark = pytest.mark.gpu
@@ -50,19 +51,6 @@ def carrier(gpu_lib):
     return Carrier(gpu_lib, smp.load())
 
 
-def _compare(cases, off, k, got_of, coef, proj, worst, bad, where):
-    for i, cs in enumerate(cases):
-        ref, tol = smp.expected(cs, k, coef, proj)
-        got = got_of(i)
-        if k == "H":
-            ref = np.triu(ref)  # the upper CSR: the lower triangle of `got` is zero like the reference's here (tol > 0 everywhere: scale > 0)
-        assert np.all(np.isfinite(got)), (cs["name"], k)
-        r = float(np.max(np.abs(got - ref) / (tol / smp.M)))
-        worst[k] = max(worst.get(k, 0.0), r)
-        if not r <= smp.M:
-            bad.append(f"{cs['name']} {k} {where}: err / (sens + u scale) = {r:.3g}")
-
-
 def test_energy_gradient_hessian_against_mpmath(carrier):
     c, cases, off = carrier.c, carrier.cases, carrier.off
     worst, bad = {}, []
@@ -74,15 +62,15 @@ def test_energy_gradient_hessian_against_mpmath(carrier):
         Eall = c.shell_energy(coef)
         Esum = sum(smp.expected(cs, "E", coef)[0] for cs in cases)
         assert abs(Eall - Esum) <= sum(smp.expected(cs, "E", coef)[1] for cs in cases)
-        _compare(cases, off, "E", lambda i: coef * (perTri[triOwner == i].sum() + perHinge[hingeOwner == i].sum()), coef, True, worst, bad, f"coef {coef:g}")
+        cc.compare(smp, cases, "E", lambda i: coef * (perTri[triOwner == i].sum() + perHinge[hingeOwner == i].sum()), coef, True, worst, bad, f"coef {coef:g}")
         for proj in (True, False):
             g = c.shell_gradient_add(coef, proj)
             c.set_zero()
             c.shell_hessian_add(coef, proj)
             A = carrier.dense_upper()
             where = f"coef {coef:g} projectDBC {int(proj)}"
-            _compare(cases, off, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
-            _compare(cases, off, "H", lambda i: A[3 * off[i]:3 * off[i + 1], 3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
+            cc.compare(smp, cases, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
+            cc.compare(smp, cases, "H", lambda i: A[3 * off[i]:3 * off[i + 1], 3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, where)
             dropped = np.repeat((carrier.dbc == 1) | ((carrier.dbc == 2) & proj), 3)
             assert np.all(g[dropped] == 0.0) and np.all(A[dropped, :] == 0.0) and np.all(A[:, dropped] == 0.0)
             for i in range(len(cases)):  # nothing between the components
@@ -104,8 +92,8 @@ def test_newton_assembly_adds_the_shell_terms_to_mass_and_inertia(carrier):
         D = np.repeat(np.where(dropped, 1.0, mass), 3)
         g2 = c.gradient(coef, proj)
         worst, bad = {}, []
-        _compare(cases, off, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, "assemble_newton")
-        _compare(cases, off, "g", lambda i: g2[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, "gradient")
+        cc.compare(smp, cases, "g", lambda i: g[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, "assemble_newton")
+        cc.compare(smp, cases, "g", lambda i: g2[3 * off[i]:3 * off[i + 1]], coef, proj, worst, bad, "gradient")
         # the diagonal holds fl(m + H_ii): that one rounding, u (m + |H_ii|), is not part of the Hessian's tolerance and is taken off before measuring
         H = A - np.diag(D)
         slack = np.diag(2 * smp.U * np.maximum(D, np.abs(np.diag(H))))
@@ -114,7 +102,7 @@ def test_newton_assembly_adds_the_shell_terms_to_mass_and_inertia(carrier):
             ref = np.triu(smp.expected(cases[i], "H", coef, proj)[0])
             err = H[s, s] - ref
             return ref + np.sign(err) * np.maximum(np.abs(err) - slack[s, s], 0.0)
-        _compare(cases, off, "H", block, coef, proj, worst, bad, "assemble_newton")
+        cc.compare(smp, cases, "H", block, coef, proj, worst, bad, "assemble_newton")
         assert not bad, "\n".join(bad)
     E = c.incremental_potential(coef)
     want = sum(smp.expected(cs, "E", coef)[0] for cs in cases)

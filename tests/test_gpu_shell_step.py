@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import shell_mp as smp
+from codim_common import five_tet_cube, step_context
 from ipc_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -20,16 +21,7 @@ def cloth(n, m=None, spacing=0.1, y=0.0, origin=(0.0, 0.0)):
 
 
 def shell_context(gpu_lib, V, tri, solver=0, bend=1.0, T=None, dt=0.01, gravity=True, held=None, x0=None, h=H, E=YM):
-    c = gpu_lib.Context(0, solver=solver)
-    c.set_mesh(V, np.zeros((0, 4), dtype=np.int32) if T is None else T, YM=YM, PR=0.4, density=RHO)
-    c.set_shell(tri, h, E, PR, RHO, bend_scale=bend)
-    if x0 is not None:
-        c.set_positions(x0)
-    c.opt_init(dt, gravity)
-    c.set_time_integration("BE")
-    if held is not None and len(held):
-        c.add_dirichlet(np.asarray(held, dtype=np.int32))
-    return c
+    return step_context(gpu_lib, V, lambda c: c.set_shell(tri, h, E, PR, RHO, bend_scale=bend), solver, T, YM, RHO, dt, gravity, held, x0)
 
 
 @pytest.mark.parametrize("solver", SOLVERS)
@@ -114,15 +106,6 @@ def test_clamped_strip_sags_less_with_more_bending_stiffness(gpu_lib, solver):
     d1, d10 = (V[tip, 1] - X1[tip, 1]).mean(), (V[tip, 1] - X10[tip, 1]).mean()
     print(f"solver {solver}: tip deflection bend 1: {d1:.6g}, bend 10: {d10:.6g}")
     assert 0.0 < d10 < d1
-
-
-def five_tet_cube(size, lo):
-    P = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], dtype=np.float64) * size + lo
-    T = np.array([[1, 3, 4, 6], [0, 1, 3, 4], [2, 3, 1, 6], [5, 4, 6, 1], [7, 6, 4, 3]], dtype=np.int32)
-    for t in T:  # positive volumes
-        if np.linalg.det(P[t[1:]] - P[t[0]]) < 0:
-            t[[2, 3]] = t[[3, 2]]
-    return P, T
 
 
 @pytest.mark.parametrize("solver", SOLVERS)

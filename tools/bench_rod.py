@@ -12,9 +12,10 @@ import sys
 
 import numpy as np
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import timed  # noqa: E402
 from ipc_amd import lib  # noqa: E402
-from tools.bench_shell import timed  # noqa: E402
 
 R, YM, RHO = 2e-3, 1e7, 1000.0
 

@@ -7,16 +7,16 @@ profiles/shell_bench.json).
     difference to the connected cloth.  The soup scatters into more distinct rows, so the difference slightly favours the hinge kernel.
 usage: python tools/bench_shell.py [--n 200] [--reps 20]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
 import time
 
 import numpy as np
-import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import timed  # noqa: E402
 from ipc_amd import lib, scene  # noqa: E402
 
 H, YM, PR, RHO = 1e-3, 1e5, 0.3, 1000.0
@@ -35,26 +35,6 @@ def context(V, tri, dt=0.01, gravity=True):
     c.set_shell(tri, H, YM, PR, RHO)
     c.opt_init(dt, gravity)
     return c
-
-
-def stream_of(c):
-    p = C.c_void_p()
-    c._chk(c._L.ipcgpu_ctx_get_stream(c.h, C.byref(p)))
-    return torch.cuda.ExternalStream(p.value)
-
-
-def timed(c, fn, reps):
-    s = stream_of(c)
-    fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(s)
-        fn()
-        b.record(s)
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms))
 
 
 def main():

@@ -16,7 +16,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bench_shell import context, grid, timed  # noqa: E402
+from _timing import timed  # noqa: E402
+from bench_shell import context, grid  # noqa: E402
 
 ONSET, LIMIT = 1.0, 1.15
 

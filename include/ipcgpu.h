@@ -432,6 +432,46 @@ int ipcgpu_rod_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_rod_energy_per_elem(ipcgpu_ctx*, double* perSeg_nSeg, double* perBend_nBend);
 int ipcgpu_rod_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_rod_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+/* Attachments (no counterpart in the reference): springs that tie a point A to a point B -- stitches (rest length 0) and tethers (rest length > 0).
+ *   Each point is a fixed convex combination of one to three nodes (a node, a point on an edge, a point in a triangle), given as up to three (node, weight)
+ *   pairs with weights >= 0 that sum to 1; an unused slot is node id -1 with weight 0.  The nodes may belong to any components, the same one included:
+ *   tetrahedral, shell, rod, scripted or obstacle nodes.  A node that appears in both points is merged into one signed coefficient
+ *   c_i = weight in A - weight in B (sum c_i = 0, up to 6 distinct nodes); nodes whose coefficient is zero are dropped.
+ *   energy      per attachment, stiffness k > 0 (a force per length, the caller's: no material scales it) and rest length L >= 0:
+ *               d = sum_i c_i x_i, l = |d|, W = k (l - L)^2 / 2.  Exact gradient grad_i = k (l - L) c_i t, t = d / l.  Hessian blocks H_ij = c_i c_j B,
+ *               B = k [t t^T + max(0, 1 - L / l) (I - t t^T)]: the clamp at 0 is the exact eigenvalue projection of the full Hessian (c c^T) (x) B_full
+ *               (spectrum |c|^2 times k, k (1 - L / l) twice).  L == 0: W = k |d|^2 / 2, grad_i = k c_i d, B = k I, without a square root or a
+ *               division, well defined at d = 0.  L > 0 and l == 0: the energy k L^2 / 2, no force and no block.  Never NaN.
+ *   Rows, columns and gradient entries of projected Dirichlet nodes are dropped: a point tied to a scripted collider follows it.
+ *   Contact is NOT changed: attached bodies still form contact pairs, so a zero-length stitch between two different surfaces settles at a gap below dHat
+ *   with the barrier active.  A caller who wants none of that masks the pair of bodies with ipcgpu_set_contact_groups or gives the attachment a rest length.
+ * Not modelled: breaking or plastic stitches; damping of the spring beyond the stiffness-proportional damping every elastic term shares; any exemption
+ * from contact.
+ * ipcgpu_set_attachments: nodesA_3n / weightsA_3n / nodesB_3n / weightsB_3n attachment-major (slot s of attachment i at 3 i + s); k_n, L_n per attachment.
+ * After ipcgpu_set_mesh, before ipcgpu_opt_init (else IPCGPU_ERR_STATE) and before ipcgpu_linsys_set_pattern: every node pair of an attachment joins
+ * vNeighbor (a node pattern that exists already is rebuilt by this call, without extra pairs).  It changes no mass and marks no node.  IPCGPU_ERR_ARG: a node
+ * id out of range, a point with no node, a weight that is negative or not finite (or != 0 in an unused slot), weights of a point that do not sum to 1 within
+ * 1e-12, k <= 0, L < 0 or either not finite, an attachment whose two points are the same.  n == 0 removes the attachments (no-op without any), a second
+ * call replaces them.  Sharded context: IPCGPU_ERR_UNSUPPORTED (both ways: ipcgpu_ctx_set_shard refuses a context with attachments).  ipcgpu_set_mesh
+ * drops them.
+ * With attachments set their term enters the stepper and the building blocks wherever the shell, rod and tetrahedral elastic terms do, with the same
+ * coefficient; ipcgpu_opt_system_report returns IPCGPU_ERR_UNSUPPORTED (the energy belongs to no single component).  Without any no attachment kernel is
+ * ever launched.
+ * ipcgpu_attach_get: *count = n; counts_n the distinct nodes per attachment (2 to 6); nodes_6n / coefs_6n slot-major (slot s of attachment i at s n + i):
+ * the merged ids and signed coefficients, the slots behind counts_n[i] repeat slot 0 with coefficient 0; k_n, L_n; restDist_n the distance |d| of the two
+ * points at the rest positions (which stitches are pre-stretched).  Any pointer may be null.
+ * ipcgpu_attach_energy / _energy_per_elem / _gradient_add / _hessian_add: the semantics of their ipcgpu_rod_* namesakes (the energy after ipcgpu_opt_init;
+ * per-attachment terms unscaled; projected Dirichlet entries dropped; a block the pattern lacks: IPCGPU_ERR_STATE; fp64 atomics).
+ * ipcgpu_attach_state: per attachment the current length l and the signed force k (l - L) (positive: in tension); either pointer may be null.
+ * Without attachments all of them return IPCGPU_OK and do nothing. */
+int ipcgpu_set_attachments(ipcgpu_ctx*, int n, const int* nodesA_3n, const double* weightsA_3n, const int* nodesB_3n, const double* weightsB_3n, const double* k_n,
+    const double* L_n);
+int ipcgpu_attach_get(ipcgpu_ctx*, int* count, int* counts_n, int* nodes_6n, double* coefs_6n, double* k_n, double* L_n, double* restDist_n);
+int ipcgpu_attach_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_attach_energy_per_elem(ipcgpu_ctx*, double* perAttach_n);
+int ipcgpu_attach_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_attach_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_attach_state(ipcgpu_ctx*, double* length_n, double* force_n);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

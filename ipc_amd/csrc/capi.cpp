@@ -112,14 +112,20 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 }
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
-// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its limit, ipcgpu_shell_limit_* the limit alone, ipcgpu_rod_* the rod.
-constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT, ROD = HipOptimizer::CODIM_ROD;
+// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its limit, ipcgpu_shell_limit_* the limit alone, ipcgpu_rod_* the rod,
+// ipcgpu_attach_* the attachments.
+constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT, ROD = HipOptimizer::CODIM_ROD,
+                   ATTACH = HipOptimizer::CODIM_ATTACH;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
-// What an entry point returns early on: no triangle, no limited triangle, no segment.
+const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hessian: build it after ipcgpu_set_attachments";
+// What an entry point returns early on: no triangle, no limited triangle, no segment, no attachment.
 int codimCount(const HipMesh& m, unsigned which)
 {
-    return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri() : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited() : m.rod.nSeg();
+    return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
+        : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited()
+        : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
+                                                    : m.attach.n();
 }
 int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
 {
@@ -165,19 +171,19 @@ int codimHessianAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, 
     }
     return IPCGPU_OK;
 }
-// ipcgpu_set_shell / ipcgpu_set_rod (which: CODIM_SHELL / CODIM_ROD): n elements, set(mesh) the call that differs
+// ipcgpu_set_shell / ipcgpu_set_rod / ipcgpu_set_attachments (which: CODIM_SHELL / CODIM_ROD / CODIM_ATTACH): n elements, set(mesh) the call that differs
 template <class Set>
 int setCodimBody(ipcgpu_ctx* c, unsigned which, bool argsOk, int n, Set&& set)
 {
     specChanged(c);
     return guarded([&] {
-        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : "rod";
+        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : which == HipOptimizer::CODIM_ROD ? "rod" : "attachment";
         HipMesh& m = M(c);
         bind(c);
         needArg(argsOk, ("bad " + what + " arguments").c_str());
         if (n == 0 && codimCount(m, which) == 0) return IPCGPU_OK; // nothing to remove
         if (c->worldSize > 1) throw UnsupportedError(what + "s on a sharded context");
-        need(!c->opt->initialised, ("ipcgpu_set_" + what + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
+        need(!c->opt->initialised, ("ipcgpu_set_" + what + (which == HipOptimizer::CODIM_ATTACH ? "s" : "") + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
         set(m);
         if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr); // (a pattern built before this call lacks the new body's node pairs)
         return IPCGPU_OK;
@@ -252,6 +258,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         needArg(c && world >= 1 && rank >= 0 && rank < world, "bad shard");
         if (world > 1 && c->mesh->shell.nTri()) throw UnsupportedError("shells on a sharded context");
         if (world > 1 && c->mesh->rod.nSeg()) throw UnsupportedError("rods on a sharded context");
+        if (world > 1 && c->mesh->attach.n()) throw UnsupportedError("attachments on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -1170,6 +1177,74 @@ int ipcgpu_rod_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
     specChanged(c);
     return guarded([&] { return codimHessianAdd(c, ROD, coef, projectDBC, ROD_MISS); });
 }
+// ---- Attachments ---------------------------------------------------------------------------------------
+int ipcgpu_set_attachments(ipcgpu_ctx* c, int n, const int* nodesA, const double* weightsA, const int* nodesB, const double* weightsB, const double* k, const double* L)
+{
+    return setCodimBody(c, HipOptimizer::CODIM_ATTACH, n >= 0 && ((nodesA && weightsA && nodesB && weightsB && k && L) || !n), n,
+        // a pattern built before this call lacks the node pairs of the attachments: setCodimBody rebuilds it from the new vNeighbor (without extra pairs)
+        [&](HipMesh& m) { m.setAttachments(n, nodesA, weightsA, nodesB, weightsB, k, L, c->stream); });
+}
+int ipcgpu_attach_get(ipcgpu_ctx* c, int* count, int* counts, int* nodes, double* coefs, double* k, double* L, double* restDist)
+{
+    return guarded([&] {
+        const HipMesh& m = M(c);
+        const AttachPlan& p = m.attach.plan;
+        if (count) *count = p.n;
+        if (counts) std::copy(p.count.begin(), p.count.end(), counts);
+        if (nodes) std::copy(p.node.begin(), p.node.end(), nodes);
+        if (coefs) std::copy(p.coef.begin(), p.coef.end(), coefs);
+        if (k) std::copy(p.kL.begin(), p.kL.begin() + p.n, k);
+        if (L) std::copy(p.kL.begin() + p.n, p.kL.end(), L);
+        if (restDist)
+            for (int i = 0; i < p.n; ++i) restDist[i] = attachRestDistance(p, i, m.nV, m.V_rest.data());
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_attach_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] { return codimEnergy(c, ATTACH, coef, E); });
+}
+int ipcgpu_attach_energy_per_elem(ipcgpu_ctx* c, double* perAttach)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const int n = c->mesh->attach.n();
+        if (!n || !perAttach) return IPCGPU_OK;
+        DevBuf<double> e;
+        e.alloc(n);
+        launch_attach_energy_per_elem(o.attachView(c->mesh->d_x.p), e.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        e.download(perAttach, n, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_attach_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] { return codimGradientAdd(c, ATTACH, coef, projectDBC, g); });
+}
+int ipcgpu_attach_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] { return codimHessianAdd(c, ATTACH, coef, projectDBC, ATTACH_MISS); });
+}
+int ipcgpu_attach_state(ipcgpu_ctx* c, double* length, double* force)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const int n = c->mesh->attach.n();
+        if (!n) return IPCGPU_OK;
+        DevBuf<double> l, f;
+        if (length) l.alloc(n);
+        if (force) f.alloc(n);
+        launch_attach_state(o.attachView(c->mesh->d_x.p), length ? l.p : nullptr, force ? f.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (length) l.download(length, n, c->stream);
+        if (force) f.download(force, n, c->stream);
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {
     specChanged(c);
@@ -1958,6 +2033,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         need(o.initialised, "call ipcgpu_opt_init first");
         if (c->mesh->shell.nTri()) throw UnsupportedError("system report with a shell set (the report's slices do not know the shell energy)");
         if (c->mesh->rod.nSeg()) throw UnsupportedError("system report with a rod set (the report's slices do not know the rod energy)");
+        if (c->mesh->attach.n()) throw UnsupportedError("system report with attachments set (their energy belongs to no single component)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

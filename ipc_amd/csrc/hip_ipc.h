@@ -7,6 +7,8 @@
 // one-line forwards.  Everything here is reached through the C ABI of include/ipcgpu.h.
 #pragma once
 #include "common.h"
+#include "attach_kernels.h"
+#include "attach_plan.h"
 #include "contact_pattern.h"
 #include "mf_numeric.h"
 #include "mf_symbolic.h"
@@ -72,6 +74,17 @@ struct HipRod {
     int nBendActive() const { return bendScale > 0.0 ? plan.nBend : 0; } // `bend 0` switches bending off: no triple reaches the kernels
 };
 
+// Attachments of the mesh (ipcgpu_set_attachments): the host plan and its device copy.  n() == 0: none, and then nothing below is ever read.
+struct HipAttach {
+    AttachPlan plan;
+    DevBuf<int> d_node;
+    DevBuf<double> d_coef, d_kL;
+    // vNeighbor as it was before this set's pairs joined it, and HipMesh::nbVersion right after they did (setAttachments)
+    std::vector<int> nbPtrBefore, nbBefore;
+    unsigned nbVersionAfter = 0;
+    int n() const { return plan.n; }
+};
+
 class HipMesh {
 public:
     int nV = 0, nT = 0;
@@ -82,6 +95,7 @@ public:
     std::vector<double> triArea, mass, mu, lam;
     std::vector<int> dbcType;
     std::vector<int> nbPtr, nb; // vNeighbor as sorted CSR adjacency (Mesh.cpp:470-493)
+    unsigned nbVersion = 0; // bumped by everything that rebuilds or extends vNeighbor
     double avgEdgeLen = 0, bboxDiag2 = 0, bboxLo[3] = { 0, 0, 0 }, bboxHi[3] = { 0, 0, 0 };
     // device
     DevBuf<double> d_x, d_xTilde, d_mass, d_A, d_vol, d_mu, d_lam;
@@ -111,13 +125,17 @@ public:
     // rest length of the segments while a rod is set.  A rod node may belong to no tetrahedron and no shell triangle (setShell checks the converse).
     HipRod rod;
     // set to 1 by a codimensional Hessian kernel that finds no block for a node pair in the pattern (csr_scatter_device.h); allocated and zeroed
-    // with the first shell or rod.  The C entry points *_hessian_add read and clear it after their launch; the stepper builds its own pattern and never reads it
+    // with the first shell, rod or attachment set.  The C entry points *_hessian_add read and clear it after their launch; the stepper builds its own pattern and never reads it
     DevBuf<int> d_codimErr;
     // what setShell and setRod share: the nodes of the body that is replaced or removed (null: none) get back massBefore and lose the inMesh mark, massBefore
     // becomes a snapshot of the masses, the new body's nodes take newMass and the mark
     void replaceBodyMasses(const std::vector<char>* oldNodes, std::vector<double>& massBefore, const std::vector<char>& newNodes, const std::vector<double>& newMass);
     void addNeighbourPairs(const std::vector<int>& pairs); // (lo, hi) pairs into vNeighbor, both directions, sorted and unique
     void setRod(int nSeg, const int* seg_colmajor, const double* radius, const double* YM, const double* rho, double bendScale, hipStream_t s);
+    // Attachments (attach_plan.h): validates, adds the plan's node pairs to vNeighbor and uploads the stencils.  n = 0 removes them, a second call replaces
+    // them (their neighbour pairs leave vNeighbor again unless something else has extended it since); computeFeatures drops them.  Touches no mass and no inMesh mark: an attachment is no body.
+    HipAttach attach;
+    void setAttachments(int n, const int* nodesA, const double* weightsA, const int* nodesB, const double* weightsB, const double* k, const double* L, hipStream_t s);
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -275,14 +293,15 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h) enter wherever the tetrahedral elastic term does, with the same
-    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod (the energy sum is
-    // ((E + shell) + limit) + rod) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg()); none of them is ever sharded.
-    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ALL = 7 };
+    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod, attachments (the energy sum
+    // is (((E + shell) + limit) + rod) + attach) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg(), attach.n()); none of them is ever sharded.
+    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_ALL = 15 };
     CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
     ShellLimitView shellLimitView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
+    AttachView attachView(const double* x_dev) const;
     size_t codimPartials() const; // doubles of d_partial the largest energy launch needs
     // *out_dev (+)= coef * energy of the chosen terms at x_dev; accumulate == false: the first term launched overwrites *out_dev, the later ones add.  The
     // limit's energy is +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node

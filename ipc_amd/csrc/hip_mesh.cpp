@@ -31,9 +31,11 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
 {
     if (nV_ <= 0 || nT_ < 0) throw ArgError("set_mesh: bad sizes");
     ++featuresVersion;
+    ++nbVersion;
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
     shell.limit = ShellLimitPlan(); // ... and its strain limit with it
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
+    if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -149,6 +151,7 @@ void HipMesh::setCodimNodes(int n, const int* ids, const double* nodeMass, hipSt
 
 void HipMesh::addNeighbourPairs(const std::vector<int>& pairs)
 {
+    ++nbVersion;
     std::vector<std::pair<int, int>> edges;
     edges.reserve(nb.size() + pairs.size());
     for (int v = 0; v < nV; ++v)
@@ -281,11 +284,41 @@ void HipMesh::setRod(int nSeg, const int* seg, const double* radius, const doubl
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
+void HipMesh::setAttachments(int n, const int* nodesA, const double* weightsA, const int* nodesB, const double* weightsB, const double* k, const double* L, hipStream_t s)
+{
+    if (n == 0 && attach.n() == 0) return; // nothing to remove: no state changes at all
+    AttachPlan plan;
+    std::string err;
+    if (!buildAttachPlan(nV, n, nodesA, weightsA, nodesB, weightsB, k, L, plan, err)) throw ArgError(err);
+    // The plan's pairs join vNeighbor: every pair among the (up to six) nodes of an attachment.  The pairs of the set this call replaces or removes
+    // leave it again where nothing else has touched vNeighbor since (then a context is, to the bit, what it was without them); otherwise they stay.
+    if (attach.n() && attach.nbVersionAfter == nbVersion) {
+        nbPtr = attach.nbPtrBefore;
+        nb = attach.nbBefore;
+    }
+    attach.nbPtrBefore = nbPtr;
+    attach.nbBefore = nb;
+    addNeighbourPairs(plan.pairs);
+    attach.nbVersionAfter = nbVersion;
+    attach.plan = std::move(plan);
+    if (!attach.n()) return;
+    const AttachPlan& p = attach.plan;
+    attach.d_node.upload(p.node, s);
+    attach.d_coef.upload(p.coef, s);
+    attach.d_kL.upload(p.kL, s);
+    if (!d_codimErr.n) { // the first codimensional term of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void HipMesh::addSurfaceEdges(int nSF, const int* SF, int nCE, const int* CE)
 {
     // Mesh.cpp:480-487: every surface triangle's edges enter vNeighbor too.  For a tet component they only repeat tet edges; for
     // a surface-only component (shell, scripted collision surface) they are the only adjacency its nodes have, and the barrier
     // blocks of a stencil whose nodes share such a triangle land on them once the nodes are free (penalty phase of a moving DBC).
+    ++nbVersion;
     std::vector<std::pair<int, int>> edges;
     edges.reserve(nb.size() + 6 * (size_t)nSF);
     for (int v = 0; v < nV; ++v)

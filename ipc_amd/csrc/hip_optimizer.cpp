@@ -82,6 +82,7 @@ ElemView HipOptimizer::view() const
 CODIM_VIEW_LAYOUT(ShellView, ShellFields, nTri);
 CODIM_VIEW_LAYOUT(ShellLimitView, ShellLimitFields, nTri);
 CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
+CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
 #pragma clang diagnostic pop
 #undef CODIM_VIEW_LAYOUT
 
@@ -133,6 +134,18 @@ RodView HipOptimizer::rodView(const double* x_dev) const
     return v;
 }
 
+AttachView HipOptimizer::attachView(const double* x_dev) const
+{
+    const HipAttach& t = mesh.attach;
+    AttachView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.n = t.n();
+    v.node = t.d_node.p;
+    v.coef = t.d_coef.p;
+    v.kL = t.d_kL.p;
+    return v;
+}
+
 // The codimensional terms, one row each, in launch order.  A new term is a kernel file, a view builder and a row here.
 namespace {
 struct CodimTerm {
@@ -151,6 +164,9 @@ const CodimTerm CODIM_TERMS[] = {
     { HipOptimizer::CODIM_ROD, [](const HipMesh& m) { return m.rod.nSeg() ? m.rod.nSeg() + m.rod.nBend() : 0; },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_rod_energy(o.rodView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_rod_assemble(o.rodView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_ATTACH, [](const HipMesh& m) { return m.attach.n(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_attach_energy(o.attachView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_attach_assemble(o.attachView(x), coef, proj, g, a, err, o.stream); } },
 };
 } // namespace
 
@@ -504,7 +520,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell, limit and rod Hessians at the damping positions
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell, limit, rod and attachment Hessians at the damping positions
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;

@@ -650,6 +650,76 @@ class Context:
     def rod_hessian_add(self, coef=1.0, projectDBC=True):
         self._codim_hessian_add("rod", coef, projectDBC)
 
+    # ---- attachments (ipcgpu_set_attachments: springs that tie a point of the mesh to another -- stitches and tethers)
+    @staticmethod
+    def _attach_points(nodes, weights, n):
+        """nodes: n ids or n x (1 .. 3) ids (-1: unused slot); weights: None (one node per point, weight 1) or the same shape -> (n x 3 ids, n x 3 weights)"""
+        ids = np.asarray(nodes, dtype=np.int32).reshape(n, -1)
+        if ids.shape[1] > 3:
+            raise ValueError("set_attachments: a point has at most three nodes")
+        if weights is None:
+            if ids.shape[1] != 1:
+                raise ValueError("set_attachments: points of more than one node need weights")
+            w = np.ones((n, 1))
+        else:
+            w = np.asarray(weights, dtype=np.float64).reshape(n, -1)
+            if w.shape != ids.shape:
+                raise ValueError("set_attachments: one weight per node slot")
+        N, W = np.full((n, 3), -1, dtype=np.int32), np.zeros((n, 3))
+        N[:, :ids.shape[1]], W[:, :ids.shape[1]] = ids, w
+        return np.ascontiguousarray(N), np.ascontiguousarray(W)
+
+    def set_attachments(self, nodesA, nodesB, k, L=0.0, weightsA=None, weightsB=None):
+        """Ties point A to point B of every attachment with W = k (|d| - L)^2 / 2, d = A - B.  nodesA / nodesB: n node ids, or n x (1 .. 3) ids with
+        weightsA / weightsB of the same shape (>= 0, sum 1; id -1 with weight 0: unused slot) for points on edges and in triangles; k, L: scalars or one
+        value per attachment.  After set_mesh, before opt_init and set_pattern; changes no mass.  Contact between the attached bodies stays as it is (mask
+        it with set_contact_groups, or give a rest length).  An empty list removes the attachments."""
+        n = len(np.asarray(nodesA))
+        if n == 0:
+            self._chk(self._L.ipcgpu_set_attachments(self.h, C.c_int(0), None, None, None, None, None, None))
+            return
+        NA, WA = self._attach_points(nodesA, weightsA, n)
+        NB, WB = self._attach_points(nodesB, weightsB, n)
+        kk, LL = (_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))) for a in (k, L))
+        self._chk(self._L.ipcgpu_set_attachments(self.h, C.c_int(n), _ip(NA), _dp(WA), _ip(NB), _dp(WB), _dp(kk), _dp(LL)))
+
+    def _attach_n(self):
+        n = C.c_int()
+        self._chk(self._L.ipcgpu_attach_get(self.h, C.byref(n), None, None, None, None, None, None))
+        return n.value
+
+    def attach_get(self):
+        """dict: n, count (distinct nodes per attachment), nodes, coefs (n x 6: merged ids and signed coefficients, padding repeats slot 0 with 0), k, L,
+        restDist (the distance of the two points at the rest positions)"""
+        n = self._attach_n()
+        cnt, nodes, coefs = np.zeros(n, dtype=np.int32), np.zeros((6, n), dtype=np.int32), np.zeros((6, n))
+        k, L, rest = np.zeros(n), np.zeros(n), np.zeros(n)
+        m = C.c_int()
+        self._chk(self._L.ipcgpu_attach_get(self.h, C.byref(m), _ip(cnt), _ip(nodes), _dp(coefs), _dp(k), _dp(L), _dp(rest)))
+        return {"n": n, "count": cnt, "nodes": nodes.T.copy(), "coefs": coefs.T.copy(), "k": k, "L": L, "restDist": rest}
+
+    def attach_energy(self, coef=1.0):
+        return self._codim_energy("attach", coef)
+
+    def attach_energy_per_elem(self):
+        e = np.zeros(self._attach_n())
+        self._chk(self._L.ipcgpu_attach_energy_per_elem(self.h, _dp(e)))
+        return e
+
+    def attach_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * attachment gradient; returns it"""
+        return self._codim_gradient_add("attach", coef, projectDBC, grad)
+
+    def attach_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("attach", coef, projectDBC)
+
+    def attach_state(self):
+        """(length l, signed force k (l - L)) per attachment at the current positions"""
+        n = self._attach_n()
+        l, f = np.zeros(n), np.zeros(n)
+        self._chk(self._L.ipcgpu_attach_state(self.h, _dp(l), _dp(f)))
+        return l, f
+
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)
         self._chk(self._L.ipcgpu_set_obstacle_nodes(self.h, C.c_int(len(ids)), _ip(ids), C.c_int(int(obstacle_only))))

@@ -8,6 +8,10 @@ anything else raises `UnsupportedKeyword` instead of being ignored silently.
     cfg = SceneConfig.parse(open(path).read(), base_dir)       # grammar only
     scene = assemble(cfg, read_mesh)                          # shapes -> one mesh (main.cpp:880-1198)
     apply(scene, backend)                                     # C-ABI calls, in the order INTEGRATION.md gives
+
+Keywords of this project beside the reference's: `shell`, `limit`, `rod`, `contactGroup` on a shape line (see Shape), and the top-level lines
+`contactIgnore`, `contactFric`, `attach <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]` and `stitch <shapeA> <shapeB> <radius> <k> [rest]` (see SceneConfig):
+the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.
 """
 from dataclasses import dataclass, field
 import math
@@ -110,6 +114,13 @@ class SceneConfig:
     # friction coefficient between groups g and h --, and a trailing `contactGroup g` on a shape line (Shape.contact_group)
     contact_ignore: list = field(default_factory=list)  # (g, h)
     contact_fric: list = field(default_factory=list)  # (g, h, mu)
+    # `attach <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]` and `stitch <shapeA> <shapeB> <radius> <k> [rest]` (this project's keywords, top-level lines):
+    # springs W = k (|x_A - x_B| - L)^2 / 2 between nodes of two shapes (Context.set_attachments).  Shapes count the `shapes` block from 0, nodes are local
+    # to their shape.  `attach` ties one pair (L defaults to 0).  `stitch` ties every node of shape A whose rest position (after the shape's transform) lies
+    # within <radius> of a node of shape B to its nearest such node, with L = 0 or, with `rest`, the rest distance of the pair; one that ties nothing is
+    # an error.  Contact between the two shapes is not changed: mask it with contactGroup / contactIgnore, or give a rest length.
+    attach: list = field(default_factory=list)  # (shapeA, nodeA, shapeB, nodeB, k, L)
+    stitch: list = field(default_factory=list)  # (shapeA, shapeB, radius, k, rest)
 
     def uses_contact_groups(self):
         return bool(self.contact_ignore or self.contact_fric or any(sh.contact_group for sh in self.shapes))
@@ -342,6 +353,20 @@ class SceneConfig:
                 if not (math.isfinite(mu) and mu >= 0):
                     raise ValueError("contactFric: the coefficient must be finite and not negative")
                 cfg.contact_fric.append((_contact_group(a[0]), _contact_group(a[1]), mu))
+            elif k == "attach":  # this project's keyword: one node-to-node attachment
+                if len(a) not in (5, 6):
+                    raise ValueError("attach needs <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]")
+                kk, L = float(a[4]), float(a[5]) if len(a) == 6 else 0.0
+                if not (math.isfinite(kk) and kk > 0 and math.isfinite(L) and L >= 0):
+                    raise ValueError("attach: k must be positive and L must not be negative")
+                cfg.attach.append((int(a[0]), int(a[1]), int(a[2]), int(a[3]), kk, L))
+            elif k == "stitch":  # this project's keyword: the nodes of shape A near shape B, each tied to its nearest node there
+                if len(a) not in (4, 5) or (len(a) == 5 and a[4] != "rest"):
+                    raise ValueError("stitch needs <shapeA> <shapeB> <radius> <k> [rest]")
+                radius, kk = float(a[2]), float(a[3])
+                if not (math.isfinite(radius) and radius >= 0 and math.isfinite(kk) and kk > 0):
+                    raise ValueError("stitch: the radius must not be negative and k must be positive")
+                cfg.stitch.append((int(a[0]), int(a[1]), radius, kk, len(a) == 5))
             elif k in VIEWER_KEYWORDS:
                 pass  # viewer / logging only
             elif k in ("resolution", "inexactSolve"):
@@ -578,6 +603,8 @@ class AssembledScene:
     shell: dict = None
     # the shapes that carry `rod`, as Context.set_rod takes them: {seg, radius, YM, rho (per segment), bend (one scale for the scene)}, or None
     rod: dict = None
+    # every `attach` and `stitch` line, as Context.set_attachments takes them: {nodesA, nodesB (global node ids), k, L (per attachment)}, or None
+    attachments: dict = None
 
     def before_step(self, be, t):
         """What AnimScripter::stepAnimScript decides from the state before a time step (call with the step's start time)."""
@@ -673,6 +700,44 @@ class AssembledScene:
         return False
 
 
+def _attachments(cfg, Vs, nr):
+    """the `attach` and `stitch` lines over the transformed shapes Vs (node offsets nr) -> {nodesA, nodesB, k, L} in script order (attach lines first), or None"""
+    def shape(s, line):
+        if not 0 <= s < len(Vs):
+            raise ValueError(f"{line}: shape {s} does not exist (the scene has {len(Vs)})")
+        return s
+    A, B, K, L, R = [], [], [], [], []  # (R: L is the rest distance of the pair, taken from the assembled rest shape)
+    for sa, na, sb, nb_, k, l0 in cfg.attach:
+        for s, n in ((shape(sa, "attach"), na), (shape(sb, "attach"), nb_)):
+            if not 0 <= n < len(Vs[s]):
+                raise ValueError(f"attach: node {n} does not exist in shape {s} ({len(Vs[s])} nodes)")
+        if (sa, na) == (sb, nb_):
+            raise ValueError(f"attach: node {na} of shape {sa} is tied to itself")
+        A.append(nr[sa] + na)
+        B.append(nr[sb] + nb_)
+        K.append(k)
+        L.append(l0)
+        R.append(False)
+    for sa, sb, radius, k, rest in cfg.stitch:
+        if shape(sa, "stitch") == shape(sb, "stitch"):
+            raise ValueError("stitch: the two shapes must differ")
+        d = np.linalg.norm(Vs[sa][:, None, :] - Vs[sb][None, :, :], axis=2)
+        near = d.argmin(axis=1)
+        dist = d[np.arange(len(near)), near]
+        tied = np.flatnonzero(dist <= radius)
+        if not len(tied):
+            raise ValueError(f"stitch {sa} {sb}: no node of shape {sa} lies within {radius:g} of a node of shape {sb} (the nearest pair is {dist.min():g} apart)")
+        A += (nr[sa] + tied).tolist()
+        B += (nr[sb] + near[tied]).tolist()
+        K += [k] * len(tied)
+        L += [0.0] * len(tied)
+        R += [bool(rest)] * len(tied)
+    if not A:
+        return None
+    return {"nodesA": np.array(A, dtype=np.int32), "nodesB": np.array(B, dtype=np.int32), "k": np.array(K, dtype=np.float64), "L": np.array(L, dtype=np.float64),
+            "rest": np.array(R, dtype=bool)}
+
+
 def assemble(cfg, read_mesh):
     """main.cpp:880-1198: select Dirichlet / Neumann nodes per shape on the mesh as read, transform the shape (R (p * scale) + translate), concatenate."""
     Vs, Ts, SFs, nr, tr, dirichlet, neumann = [], [], [], [0], [0], [], []
@@ -742,6 +807,7 @@ def assemble(cfg, read_mesh):
         SFs.append(SF + off)
         nr.append(off + V.shape[0])
         tr.append(tr[-1] + T.shape[0])
+    attachments = _attachments(cfg, Vs, nr)
     # kinematic mesh obstacles (MeshCO::MeshCO, MeshCO.cpp:37-58): centred on the vertex mean, rotated, scaled so that the largest
     # bounding-box extent equals `scale`, moved to `origin`.  They ride along as surface-only components: nodes of no tetrahedron.
     obstacle = []
@@ -1160,6 +1226,10 @@ def assemble(cfg, read_mesh):
         per = lambda k: np.concatenate([np.full(len(e), float(m[k])) for e, _r, _b, m in rods])  # noqa: E731
         sc.rod = {"seg": np.vstack([e for e, *_ in rods]).astype(np.int32), "radius": np.concatenate([np.full(len(e), float(r)) for e, r, *_ in rods]),
                   "rho": per(0), "YM": per(1), "bend": float(rods[0][2])}
+    if attachments is not None:  # (`stitch ... rest`: the distance in the rest shape as the stepper gets it, behind `size`)
+        r = attachments.pop("rest")
+        attachments["L"][r] = np.linalg.norm(V[attachments["nodesA"][r]] - V[attachments["nodesB"][r]], axis=1)
+    sc.attachments = attachments
     for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = seqs
@@ -1189,6 +1259,9 @@ def apply(sc, be):
     if sc.rod is not None:  # after set_codim_nodes and set_shell (it replaces the segment masses of its nodes), before opt_init and the pattern
         q = sc.rod
         be.set_rod(q["seg"], q["radius"], q["YM"], q["rho"], q["bend"])
+    if sc.attachments is not None:  # every `attach` and `stitch` line in one call, behind set_shell / set_rod, before opt_init and the pattern
+        q = sc.attachments
+        be.set_attachments(q["nodesA"], q["nodesB"], q["k"], q["L"])
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
         # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density

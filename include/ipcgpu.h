@@ -472,6 +472,53 @@ int ipcgpu_attach_energy_per_elem(ipcgpu_ctx*, double* perAttach_n);
 int ipcgpu_attach_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_attach_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 int ipcgpu_attach_state(ipcgpu_ctx*, double* length_n, double* force_n);
+/* Pressure chambers: a constant gas pressure inside closed surfaces (a balloon, a cushion, a hollow body under outside pressure).  A project extension: the
+ * reference has none.  A pressure load is a follower load -- its direction and size move with the surface --, which ipcgpu_opt_add_neumann (a constant
+ * acceleration) cannot stand in for.
+ *   A chamber is a closed, consistently oriented set of triangles (outward normals by the right-hand rule) over any nodes of the mesh: shell nodes, surface
+ *   nodes of tetrahedral components, scripted nodes.  It may consist of several closed pieces.  Chamber c holds the constant gauge pressure p_c: positive
+ *   pushes outward, negative is suction or an outside hydrostatic pressure.
+ *   energy      with a reference point r_c that is constant during any one evaluation and y_i = x_i - r_c:  V_c = 1/6 sum_t y0 . (y1 x y2) over the
+ *               chamber's triangles, W_c = -p_c V_c, per triangle W_t = -(p_c / 6) y0 . (y1 x y2).  Exact gradient dW_t/dx0 = -(p/6) y1 x y2,
+ *               dW_t/dx1 = -(p/6) y2 x y0, dW_t/dx2 = -(p/6) y0 x y1.  The 9 x 9 Hessian of a triangle has zero diagonal blocks and H01 = (p/6) [y2]x,
+ *               H02 = -(p/6) [y1]x, H12 = (p/6) [y0]x; it is indefinite and is projected to PSD per triangle (a Jacobi eigen-iteration on 9 x 9).
+ *   r_c         For a closed surface V_c and its gradient do not depend on r_c in exact arithmetic; the per-triangle Hessian does (its entries grow with
+ *               |y|), so a projection about the world origin would add a spurious stiffness proportional to the body's distance from the origin.  r_c is
+ *               the mean of the centroids of the chamber's triangles: ipcgpu_set_chambers computes it at the rest positions, ipcgpu_opt_begin_timestep
+ *               refreshes it on the device from the positions the step starts from, and it stays fixed through that step's Newton iterations and line
+ *               searches (every energy comparison inside a step uses one r_c).  ipcgpu_set_positions does not move it.
+ *   Rows, columns and gradient entries of projected Dirichlet nodes are dropped.  The term is no stiffness: it does not enter the lagged stiffness damping
+ *   (ipcgpu_opt_set_damping), whose matrix is to the bit what it is without chambers.  Contact is NOT changed.
+ * Not modelled: a gas law (pressure as a function of the volume) -- its Hessian has a dense rank-one term per chamber, beta gradV gradV^T, that for real air
+ * on cloth dominates every other stiffness; omitting it stalls Newton and lagging the pressure per step is unstable, so it needs a low-rank correction
+ * inside the linear solve (a follow-up); until then ipcgpu_chamber_set_pressure and ipcgpu_chamber_state let a caller drive the pressure between time
+ * steps --; open chambers closed by a plane; the mass of the enclosed gas.
+ * ipcgpu_set_chambers: chamber c owns the triangles [triEnd_nCh[c - 1], triEnd_nCh[c]) (from 0 for c = 0) of tri_colmajor (nTri x 3, nTri = triEnd_nCh[nCh - 1]);
+ * pressure_nCh per chamber.  After ipcgpu_set_mesh, before ipcgpu_opt_init (else IPCGPU_ERR_STATE) and before ipcgpu_linsys_set_pattern: the three edges
+ * of every triangle join vNeighbor (a node pattern that exists already is rebuilt by this call, without extra pairs).  It changes no mass and marks no
+ * node.  IPCGPU_ERR_ARG, with a message that names the chamber and the triangle or edge: a node id out of range, a triangle that repeats a node, an edge of a
+ * chamber that is not used by exactly two of that chamber's triangles (an open surface), two triangles that traverse a shared edge in the same direction,
+ * an empty chamber, triEnd not ascending, a pressure that is not finite, a rest volume <= 0 (the chamber is oriented inward).  nCh == 0 removes the
+ * chambers (no-op without any), a second call replaces them.  Sharded context: IPCGPU_ERR_UNSUPPORTED (both ways: ipcgpu_ctx_set_shard refuses a context
+ * with chambers).  ipcgpu_set_mesh drops them.  Pressures are not part of the status file.
+ * With chambers set their term enters the stepper and the building blocks wherever the shell, rod and tetrahedral elastic terms do, with the same
+ * coefficient; ipcgpu_opt_system_report returns IPCGPU_ERR_UNSUPPORTED.  Without any no chamber kernel is ever launched.
+ * ipcgpu_chamber_set_pressure: new pressures, at any time, also between time steps; checks that they are finite (IPCGPU_ERR_ARG) and needs chambers
+ * (IPCGPU_ERR_STATE without).
+ * ipcgpu_chamber_get: counts2 = {nCh, nTri}; the lists as given; restVolume_nCh the volume at the rest positions; the current pressures.  Any pointer may be null.
+ * ipcgpu_chamber_state: per chamber, at the current positions, the enclosed volume and the surface area (a deterministic segmented reduction; the volume is
+ * taken about the centroid mean of the current positions), and refPoint_3nCh, the r_c the evaluations use now.  Any pointer may be null.
+ * ipcgpu_chamber_energy / _energy_per_elem / _gradient_add / _hessian_add: the semantics of their ipcgpu_attach_* namesakes (the energy after ipcgpu_opt_init;
+ * per-triangle terms unscaled; projected Dirichlet entries dropped; a block the pattern lacks: IPCGPU_ERR_STATE; fp64 atomics; a chamber with p == 0 adds nothing).
+ * Without chambers every query returns IPCGPU_OK and does nothing. */
+int ipcgpu_set_chambers(ipcgpu_ctx*, int nCh, const int* triEnd_nCh, const int* tri_colmajor, const double* pressure_nCh);
+int ipcgpu_chamber_set_pressure(ipcgpu_ctx*, const double* pressure_nCh);
+int ipcgpu_chamber_get(ipcgpu_ctx*, int* counts2, int* triEnd_nCh, int* tri_colmajor, double* restVolume_nCh, double* pressure_nCh);
+int ipcgpu_chamber_state(ipcgpu_ctx*, double* volume_nCh, double* area_nCh, double* refPoint_3nCh);
+int ipcgpu_chamber_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_chamber_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
+int ipcgpu_chamber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_chamber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

@@ -113,19 +113,21 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
 // `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its limit, ipcgpu_shell_limit_* the limit alone, ipcgpu_rod_* the rod,
-// ipcgpu_attach_* the attachments.
+// ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers.
 constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT, ROD = HipOptimizer::CODIM_ROD,
-                   ATTACH = HipOptimizer::CODIM_ATTACH;
+                   ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
 const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hessian: build it after ipcgpu_set_attachments";
-// What an entry point returns early on: no triangle, no limited triangle, no segment, no attachment.
+const char* const CHAMBER_MISS = "the pattern lacks a block of the chamber Hessian: build it after ipcgpu_set_chambers";
+// What an entry point returns early on: no triangle, no limited triangle, no segment, no attachment, no chamber triangle.
 int codimCount(const HipMesh& m, unsigned which)
 {
     return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
         : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited()
         : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
-                                                    : m.attach.n();
+        : (which & HipOptimizer::CODIM_ATTACH)      ? m.attach.n()
+                                                    : m.chamber.nTri();
 }
 int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
 {
@@ -171,19 +173,21 @@ int codimHessianAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, 
     }
     return IPCGPU_OK;
 }
-// ipcgpu_set_shell / ipcgpu_set_rod / ipcgpu_set_attachments (which: CODIM_SHELL / CODIM_ROD / CODIM_ATTACH): n elements, set(mesh) the call that differs
+// ipcgpu_set_shell / ipcgpu_set_rod / ipcgpu_set_attachments / ipcgpu_set_chambers (which: CODIM_SHELL / CODIM_ROD / CODIM_ATTACH / CODIM_CHAMBER): n elements,
+// set(mesh) the call that differs
 template <class Set>
 int setCodimBody(ipcgpu_ctx* c, unsigned which, bool argsOk, int n, Set&& set)
 {
     specChanged(c);
     return guarded([&] {
-        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : which == HipOptimizer::CODIM_ROD ? "rod" : "attachment";
+        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : which == HipOptimizer::CODIM_ROD ? "rod" : which == HipOptimizer::CODIM_ATTACH ? "attachment" : "chamber";
+        const bool plural = which == HipOptimizer::CODIM_ATTACH || which == HipOptimizer::CODIM_CHAMBER;
         HipMesh& m = M(c);
         bind(c);
         needArg(argsOk, ("bad " + what + " arguments").c_str());
         if (n == 0 && codimCount(m, which) == 0) return IPCGPU_OK; // nothing to remove
         if (c->worldSize > 1) throw UnsupportedError(what + "s on a sharded context");
-        need(!c->opt->initialised, ("ipcgpu_set_" + what + (which == HipOptimizer::CODIM_ATTACH ? "s" : "") + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
+        need(!c->opt->initialised, ("ipcgpu_set_" + what + (plural ? "s" : "") + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
         set(m);
         if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr); // (a pattern built before this call lacks the new body's node pairs)
         return IPCGPU_OK;
@@ -259,6 +263,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->shell.nTri()) throw UnsupportedError("shells on a sharded context");
         if (world > 1 && c->mesh->rod.nSeg()) throw UnsupportedError("rods on a sharded context");
         if (world > 1 && c->mesh->attach.n()) throw UnsupportedError("attachments on a sharded context");
+        if (world > 1 && c->mesh->chamber.n()) throw UnsupportedError("chambers on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -1245,6 +1250,86 @@ int ipcgpu_attach_state(ipcgpu_ctx* c, double* length, double* force)
         return IPCGPU_OK;
     });
 }
+// ---- Pressure chambers ---------------------------------------------------------------------------------
+int ipcgpu_set_chambers(ipcgpu_ctx* c, int nCh, const int* triEnd, const int* tri, const double* pressure)
+{
+    // (setCodimBody counts triangles: nCh == 0 with no chamber set is "nothing to remove")
+    return setCodimBody(c, HipOptimizer::CODIM_CHAMBER, nCh >= 0 && ((triEnd && tri && pressure) || !nCh), nCh,
+        // a pattern built before this call lacks the edges of the chambers' triangles: setCodimBody rebuilds it from the new vNeighbor (without extra pairs)
+        [&](HipMesh& m) { m.setChambers(nCh, triEnd, tri, pressure, c->stream); });
+}
+int ipcgpu_chamber_set_pressure(ipcgpu_ctx* c, const double* pressure)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        m.setChamberPressure(pressure, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_get(ipcgpu_ctx* c, int* counts2, int* triEnd, int* tri, double* restVolume, double* pressure)
+{
+    return guarded([&] {
+        const ChamberPlan& p = M(c).chamber.plan;
+        if (counts2) {
+            counts2[0] = p.n;
+            counts2[1] = p.nTri;
+        }
+        if (triEnd) std::copy(p.triEnd.begin(), p.triEnd.end(), triEnd);
+        if (tri) std::copy(p.tri.begin(), p.tri.end(), tri);
+        if (restVolume) std::copy(p.restVolume.begin(), p.restVolume.end(), restVolume);
+        if (pressure) std::copy(p.pressure.begin(), p.pressure.end(), pressure);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_state(ipcgpu_ctx* c, double* volume, double* area, double* refPoint)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipChamber& h = c->mesh->chamber;
+        const int n = h.n();
+        if (!n) return IPCGPU_OK;
+        DevBuf<double> v, a;
+        if (volume) v.alloc(n);
+        if (area) a.alloc(n);
+        launch_chamber_state(o.chamberView(c->mesh->d_x.p), volume ? v.p : nullptr, area ? a.p : nullptr, nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (volume) v.download(volume, n, c->stream);
+        if (area) a.download(area, n, c->stream);
+        if (refPoint) h.d_ref.download(refPoint, 3 * (size_t)n, c->stream); // r_c as the evaluations use it now, not the centroid mean of the current positions
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] { return codimEnergy(c, CHAMBER, coef, E); });
+}
+int ipcgpu_chamber_energy_per_elem(ipcgpu_ctx* c, double* perTri)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const int n = c->mesh->chamber.nTri();
+        if (!n || !perTri) return IPCGPU_OK;
+        DevBuf<double> e;
+        e.alloc(n);
+        launch_chamber_energy_per_elem(o.chamberView(c->mesh->d_x.p), e.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        e.download(perTri, n, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] { return codimGradientAdd(c, CHAMBER, coef, projectDBC, g); });
+}
+int ipcgpu_chamber_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] { return codimHessianAdd(c, CHAMBER, coef, projectDBC, CHAMBER_MISS); });
+}
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {
     specChanged(c);
@@ -2034,6 +2119,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         if (c->mesh->shell.nTri()) throw UnsupportedError("system report with a shell set (the report's slices do not know the shell energy)");
         if (c->mesh->rod.nSeg()) throw UnsupportedError("system report with a rod set (the report's slices do not know the rod energy)");
         if (c->mesh->attach.n()) throw UnsupportedError("system report with attachments set (their energy belongs to no single component)");
+        if (c->mesh->chamber.n()) throw UnsupportedError("system report with chambers set (the report's slices do not know the pressure energy)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

@@ -9,6 +9,8 @@
 #include "common.h"
 #include "attach_kernels.h"
 #include "attach_plan.h"
+#include "chamber_kernels.h"
+#include "chamber_plan.h"
 #include "contact_pattern.h"
 #include "mf_numeric.h"
 #include "mf_symbolic.h"
@@ -85,6 +87,18 @@ struct HipAttach {
     int n() const { return plan.n; }
 };
 
+// Pressure chambers of the mesh (ipcgpu_set_chambers): the host plan and its device copy.  n() == 0: none, and then nothing below is ever read.
+struct HipChamber {
+    ChamberPlan plan; // plan.pressure is the host copy of the pressures (ipcgpu_chamber_set_pressure keeps it current)
+    DevBuf<int> d_tri, d_chamberOf, d_triEnd;
+    DevBuf<double> d_pressure, d_ref; // d_ref: r_c, the rest value until the first time step refreshes it (chamber_kernels.h)
+    // vNeighbor as it was before this set's pairs joined it, and HipMesh::nbVersion right after they did (setChambers)
+    std::vector<int> nbPtrBefore, nbBefore;
+    unsigned nbVersionAfter = 0;
+    int n() const { return plan.n; }
+    int nTri() const { return plan.nTri; }
+};
+
 class HipMesh {
 public:
     int nV = 0, nT = 0;
@@ -136,6 +150,12 @@ public:
     // them (their neighbour pairs leave vNeighbor again unless something else has extended it since); computeFeatures drops them.  Touches no mass and no inMesh mark: an attachment is no body.
     HipAttach attach;
     void setAttachments(int n, const int* nodesA, const double* weightsA, const int* nodesB, const double* weightsB, const double* k, const double* L, hipStream_t s);
+    // Pressure chambers (chamber_plan.h): validates, adds the plan's node pairs to vNeighbor and uploads the lists, the pressures and the rest reference
+    // points.  nCh = 0 removes them, a second call replaces them (their neighbour pairs leave vNeighbor again unless something else has extended it since);
+    // computeFeatures drops them.  Touches no mass and no inMesh mark: a chamber is no body.
+    HipChamber chamber;
+    void setChambers(int nCh, const int* triEnd, const int* tri_colmajor, const double* pressure, hipStream_t s);
+    void setChamberPressure(const double* pressure, hipStream_t s); // finite values only; needs chambers
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -293,15 +313,18 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h) enter wherever the tetrahedral elastic term does, with the same
-    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod, attachments (the energy sum
-    // is (((E + shell) + limit) + rod) + attach) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg(), attach.n()); none of them is ever sharded.
-    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_ALL = 15 };
+    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod, attachments, chambers (the energy sum
+    // is ((((E + shell) + limit) + rod) + attach) + chamber) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg(), attach.n(), chamber.nTri()); none of them is ever sharded.
+    // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness.
+    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_ALL = 31, CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER };
     CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
     ShellLimitView shellLimitView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
     AttachView attachView(const double* x_dev) const;
+    ChamberView chamberView(const double* x_dev) const;
+    void refreshChamberRef(); // r_c of every chamber from the current positions, on the device (beginTimestep)
     size_t codimPartials() const; // doubles of d_partial the largest energy launch needs
     // *out_dev (+)= coef * energy of the chosen terms at x_dev; accumulate == false: the first term launched overwrites *out_dev, the later ones add.  The
     // limit's energy is +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node

@@ -36,6 +36,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     shell.limit = ShellLimitPlan(); // ... and its strain limit with it
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
+    if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -310,6 +311,48 @@ void HipMesh::setAttachments(int n, const int* nodesA, const double* weightsA, c
         d_codimErr.alloc(1);
         d_codimErr.zero(s);
     }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setChambers(int nCh, const int* triEnd, const int* tri, const double* pressure, hipStream_t s)
+{
+    if (nCh == 0 && chamber.n() == 0) return; // nothing to remove: no state changes at all
+    ChamberPlan plan;
+    std::string err;
+    if (!buildChamberPlan(nV, V_rest.data(), nCh, triEnd, tri, pressure, plan, err)) throw ArgError(err);
+    // The plan's pairs (the triangle edges) join vNeighbor.  As with the attachments, the pairs of the set this call replaces or removes leave it again
+    // where nothing else has touched vNeighbor since (then a context is, to the bit, what it was without them); otherwise they stay.
+    if (chamber.n() && chamber.nbVersionAfter == nbVersion) {
+        nbPtr = chamber.nbPtrBefore;
+        nb = chamber.nbBefore;
+    }
+    chamber.nbPtrBefore = nbPtr;
+    chamber.nbBefore = nb;
+    addNeighbourPairs(plan.pairs);
+    chamber.nbVersionAfter = nbVersion;
+    chamber.plan = std::move(plan);
+    if (!chamber.n()) return;
+    const ChamberPlan& p = chamber.plan;
+    chamber.d_tri.upload(p.tri, s);
+    chamber.d_chamberOf.upload(p.chamberOf, s);
+    chamber.d_triEnd.upload(p.triEnd, s);
+    chamber.d_pressure.upload(p.pressure, s);
+    chamber.d_ref.upload(p.restRef, s);
+    if (!d_codimErr.n) { // the first codimensional term of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setChamberPressure(const double* pressure, hipStream_t s)
+{
+    if (!chamber.n()) throw StateError("ipcgpu_chamber_set_pressure without chambers: call ipcgpu_set_chambers first");
+    if (!pressure) throw ArgError("chamber_set_pressure: null argument");
+    for (int c = 0; c < chamber.n(); ++c)
+        if (!std::isfinite(pressure[c])) throw ArgError("chamber_set_pressure: the pressure of chamber " + std::to_string(c) + " is not finite");
+    chamber.plan.pressure.assign(pressure, pressure + chamber.n());
+    chamber.d_pressure.upload(chamber.plan.pressure, s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -83,6 +83,7 @@ CODIM_VIEW_LAYOUT(ShellView, ShellFields, nTri);
 CODIM_VIEW_LAYOUT(ShellLimitView, ShellLimitFields, nTri);
 CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
 CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
+CODIM_VIEW_LAYOUT(ChamberView, ChamberFields, nTri);
 #pragma clang diagnostic pop
 #undef CODIM_VIEW_LAYOUT
 
@@ -146,6 +147,28 @@ AttachView HipOptimizer::attachView(const double* x_dev) const
     return v;
 }
 
+ChamberView HipOptimizer::chamberView(const double* x_dev) const
+{
+    const HipChamber& h = mesh.chamber;
+    ChamberView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nTri = h.nTri();
+    v.n = h.n();
+    v.tri = h.d_tri.p;
+    v.chamberOf = h.d_chamberOf.p;
+    v.triEnd = h.d_triEnd.p;
+    v.pressure = h.d_pressure.p;
+    v.ref = h.d_ref.p;
+    return v;
+}
+
+void HipOptimizer::refreshChamberRef()
+{
+    if (!mesh.chamber.n()) return;
+    launch_chamber_state(chamberView(mesh.d_x.p), nullptr, nullptr, mesh.chamber.d_ref.p, stream);
+    HIP_CHECK(hipGetLastError());
+}
+
 // The codimensional terms, one row each, in launch order.  A new term is a kernel file, a view builder and a row here.
 namespace {
 struct CodimTerm {
@@ -167,6 +190,9 @@ const CodimTerm CODIM_TERMS[] = {
     { HipOptimizer::CODIM_ATTACH, [](const HipMesh& m) { return m.attach.n(); },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_attach_energy(o.attachView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_attach_assemble(o.attachView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_CHAMBER, [](const HipMesh& m) { return m.chamber.nTri(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_chamber_energy(o.chamberView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_chamber_assemble(o.chamberView(x), coef, proj, g, a, err, o.stream); } },
 };
 } // namespace
 
@@ -520,7 +546,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p); // the shell, limit, rod and attachment Hessians at the damping positions
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness)
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -1593,6 +1619,7 @@ void HipOptimizer::beginTimestep()
     if (!initialised) throw StateError("opt_begin_timestep before opt_init");
     if (!lin.analyzed()) throw StateError("opt_begin_timestep before opt_precompute");
     Tic t(timers[11], stream);
+    refreshChamberRef(); // r_c of the pressure chambers follows the body: from the positions this step starts from, fixed until the next step (chamber_kernels.h)
     // The contact-free twist (BASELINE configs[1]; round 6): everything the set-up of a time step asks the device -- inverted before the motion? the filter's bound
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.

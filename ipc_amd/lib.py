@@ -720,6 +720,60 @@ class Context:
         self._chk(self._L.ipcgpu_attach_state(self.h, _dp(l), _dp(f)))
         return l, f
 
+    # ---- pressure chambers (ipcgpu_set_chambers: a constant gas pressure inside closed surfaces)
+    def set_chambers(self, tri_lists, pressures):
+        """tri_lists: one m x 3 array of node ids per chamber -- a closed surface (or several), consistently oriented, outward by the right-hand rule --,
+        pressures: one gauge pressure per chamber (positive pushes outward).  W = -p V per chamber, a follower load.  After set_mesh, before opt_init
+        and set_pattern; changes no mass.  An empty list removes the chambers."""
+        lists = [np.asarray(t, dtype=np.int32).reshape(-1, 3) for t in tri_lists]
+        if len(lists) == 0:
+            self._chk(self._L.ipcgpu_set_chambers(self.h, C.c_int(0), None, None, None))
+            return
+        p = _f64(np.broadcast_to(np.asarray(pressures, dtype=np.float64), (len(lists),)))
+        end = _i32(np.cumsum([len(t) for t in lists]))
+        tri = np.asfortranarray(np.vstack(lists), dtype=np.int32)
+        self._chk(self._L.ipcgpu_set_chambers(self.h, C.c_int(len(lists)), _ip(end), _ip(tri), _dp(p)))
+
+    def chamber_set_pressure(self, pressures):
+        """new pressures (a scalar or one per chamber), at any time, also between time steps"""
+        p = _f64(np.broadcast_to(np.asarray(pressures, dtype=np.float64), (self._chamber_counts()[0],)))
+        self._chk(self._L.ipcgpu_chamber_set_pressure(self.h, _dp(p)))
+
+    def _chamber_counts(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_chamber_get(self.h, _ip(cnt), None, None, None, None))
+        return int(cnt[0]), int(cnt[1])
+
+    def chamber_get(self):
+        """dict: n (chambers), nTri, triEnd, tri (nTri x 3, as given), restVolume, pressure"""
+        n, nTri = self._chamber_counts()
+        cnt, end, tri = np.zeros(2, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((nTri, 3), dtype=np.int32, order="F")
+        rest, p = np.zeros(n), np.zeros(n)
+        self._chk(self._L.ipcgpu_chamber_get(self.h, _ip(cnt), _ip(end), _ip(tri), _dp(rest), _dp(p)))
+        return {"n": n, "nTri": nTri, "triEnd": end, "tri": np.ascontiguousarray(tri), "restVolume": rest, "pressure": p}
+
+    def chamber_state(self):
+        """(volume, area, refPoint n x 3) per chamber at the current positions; refPoint is the r_c the evaluations use now"""
+        n = self._chamber_counts()[0]
+        v, a, r = np.zeros(n), np.zeros(n), np.zeros((n, 3))
+        self._chk(self._L.ipcgpu_chamber_state(self.h, _dp(v), _dp(a), _dp(r)))
+        return v, a, r
+
+    def chamber_energy(self, coef=1.0):
+        return self._codim_energy("chamber", coef)
+
+    def chamber_energy_per_elem(self):
+        e = np.zeros(self._chamber_counts()[1])
+        self._chk(self._L.ipcgpu_chamber_energy_per_elem(self.h, _dp(e)))
+        return e
+
+    def chamber_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * chamber gradient; returns it"""
+        return self._codim_gradient_add("chamber", coef, projectDBC, grad)
+
+    def chamber_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("chamber", coef, projectDBC)
+
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)
         self._chk(self._L.ipcgpu_set_obstacle_nodes(self.h, C.c_int(len(ids)), _ip(ids), C.c_int(int(obstacle_only))))

@@ -11,7 +11,8 @@ anything else raises `UnsupportedKeyword` instead of being ignored silently.
 
 Keywords of this project beside the reference's: `shell`, `limit`, `rod`, `contactGroup` on a shape line (see Shape), and the top-level lines
 `contactIgnore`, `contactFric`, `attach <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]` and `stitch <shapeA> <shapeB> <radius> <k> [rest]` (see SceneConfig):
-the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.
+the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.  `pressure <p> [ramp <seconds>]` on a
+shape line (a `shell` shape or a tetrahedral shape) makes the shape's closed surface one pressure chamber (Context.set_chambers; see Shape).
 """
 from dataclasses import dataclass, field
 import math
@@ -67,6 +68,13 @@ class Shape:
     # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
     rod_radius: float = None
     rod_bend: float = 1.0
+    # `pressure <p> [ramp <seconds>]` (this project's keyword, on a `shell` shape or a tetrahedral shape): the shape's surface triangles -- the shell's own, or
+    # the boundary faces of the tetrahedra -- are ONE pressure chamber with the constant gauge pressure p (positive pushes outward; Context.set_chambers).  The
+    # surface must be closed (an open one is a ValueError that names the shape); where its triangle list encloses a negative volume the CHAMBER's copy of the
+    # list is flipped, never the shell's own.  With `ramp` the pressure of the step that ends at time t is p min(1, t / ramp) (tools/run_scene.py sets it
+    # before each step through AssembledScene.chamber_pressures and Context.chamber_set_pressure)
+    pressure: float = None
+    pressure_ramp: float = 0.0
 
 
 @dataclass
@@ -447,6 +455,20 @@ def _parse_shape(st, resolve):
                 j += 2
             if not sh.rod_radius > 0.0 or not sh.rod_bend >= 0.0:
                 raise ValueError("rod needs a positive radius and a bend scale >= 0")
+        elif e == "pressure":
+            if j >= len(st):
+                raise ValueError("pressure needs a value")
+            sh.pressure = float(st[j])
+            j += 1
+            if j < len(st) and st[j] == "ramp":
+                if j + 1 >= len(st):
+                    raise ValueError("ramp needs a time")
+                sh.pressure_ramp = float(st[j + 1])
+                j += 2
+                if not (0.0 < sh.pressure_ramp < float("inf")):
+                    raise ValueError("ramp needs a positive, finite time")
+            if not np.isfinite(sh.pressure):
+                raise ValueError("pressure needs a finite value")
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
             sh.init_vel = (tuple(v[:3]), tuple(v[3:]))
@@ -481,6 +503,10 @@ def _parse_shape(st, resolve):
         raise ValueError("shell is valid on a triangle-mesh shape only (not on a tetrahedral, segment or point shape)")
     if sh.rod_radius is not None and os.path.splitext(sh.path.lower())[1] != ".seg":
         raise ValueError("rod is valid on a segment shape only (not on a tetrahedral, triangle-mesh or point shape)")
+    if sh.pressure is not None:
+        ext = os.path.splitext(sh.path.lower())[1]
+        if ext in (".seg", ".pt") or (ext == ".obj" and sh.shell_thickness is None):
+            raise ValueError("pressure is valid on a shell shape or a tetrahedral shape only (not on a segment, point or kinematic triangle-mesh shape)")
     return sh
 
 
@@ -605,6 +631,18 @@ class AssembledScene:
     rod: dict = None
     # every `attach` and `stitch` line, as Context.set_attachments takes them: {nodesA, nodesB (global node ids), k, L (per attachment)}, or None
     attachments: dict = None
+    # the shapes that carry `pressure`, one chamber each in script order, as Context.set_chambers takes them: {tri_lists (global node ids, outward),
+    # pressure, ramp (seconds per chamber, 0: none)}, or None
+    chambers: dict = None
+
+    def chamber_pressures(self, t):
+        """the pressures of the chambers for the time step that ends at time t: p min(1, t / ramp) where a shape gives `ramp`, p elsewhere; None when no
+        shape has a ramp (then the pressures set by apply() stay)"""
+        q = self.chambers
+        if q is None or not np.any(q["ramp"] > 0.0):
+            return None
+        with np.errstate(divide="ignore"):
+            return q["pressure"] * np.where(q["ramp"] > 0.0, np.minimum(1.0, t / np.where(q["ramp"] > 0.0, q["ramp"], 1.0)), 1.0)
 
     def before_step(self, be, t):
         """What AnimScripter::stepAnimScript decides from the state before a time step (call with the step's start time)."""
@@ -738,6 +776,27 @@ def _attachments(cfg, Vs, nr):
             "rest": np.array(R, dtype=bool)}
 
 
+def _chamber_list(SF, V, name):
+    """the chamber of one shape: its surface triangles SF (node ids into V) as a closed, outward-oriented list.  ValueError naming the shape where an edge is
+    not shared by exactly two triangles that walk it in opposite directions; a list that encloses a negative volume is returned flipped (a copy)."""
+    tri = np.array(SF, dtype=np.int32).reshape(-1, 3)
+    if len(tri) == 0:
+        raise ValueError(f"pressure: {name} has no surface triangle")
+    uses = {}
+    for t in tri:
+        for a, b in ((t[0], t[1]), (t[1], t[2]), (t[2], t[0])):
+            uses.setdefault((min(int(a), int(b)), max(int(a), int(b))), []).append(a < b)
+    for (a, b), d in uses.items():
+        if len(d) != 2:
+            raise ValueError(f"pressure: the surface of {name} is open or not a manifold (edge {a} - {b} belongs to {len(d)} of its triangles, not to two)")
+        if d[0] == d[1]:
+            raise ValueError(f"pressure: the surface of {name} is not consistently oriented (two triangles walk edge {a} - {b} in the same direction)")
+    y = V[tri] - V[np.unique(tri)].mean(axis=0)
+    if np.einsum("ti,ti->", y[:, 0], np.cross(y[:, 1], y[:, 2])) < 0.0:
+        tri = np.ascontiguousarray(tri[:, ::-1])
+    return tri
+
+
 def assemble(cfg, read_mesh):
     """main.cpp:880-1198: select Dirichlet / Neumann nodes per shape on the mesh as read, transform the shape (R (p * scale) + translate), concatenate."""
     Vs, Ts, SFs, nr, tr, dirichlet, neumann = [], [], [], [0], [0], [], []
@@ -747,7 +806,8 @@ def assemble(cfg, read_mesh):
     shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
     shell_limits = []  # ... and their (limit or 0, onset, stiffness)
     rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
-    for sh in cfg.shapes:
+    chambers = []  # (triangle list, pressure, ramp) of the shapes that carry `pressure`
+    for s_index, sh in enumerate(cfg.shapes):
         ext = os.path.splitext(sh.path.lower())[1]
         is_codim = ext in (".obj", ".seg", ".pt")  # main.cpp:948-1005: kinematic surface / segments / points (componentCoDim 2 / 1 / 0)
         E = np.zeros((0, 2), dtype=np.int32)
@@ -797,6 +857,8 @@ def assemble(cfg, read_mesh):
         if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
+        if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
+            chambers.append((_chamber_list(SF, V, f"shape {s_index} ({os.path.basename(sh.path)})") + off, sh.pressure, sh.pressure_ramp))
         if is_codim:  # (an elastic shell or rod needs nobody to hold it: it counts as moved)
             elastic = sh.shell_thickness is not None or sh.rod_radius is not None
             codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
@@ -1230,6 +1292,9 @@ def assemble(cfg, read_mesh):
         r = attachments.pop("rest")
         attachments["L"][r] = np.linalg.norm(V[attachments["nodesA"][r]] - V[attachments["nodesB"][r]], axis=1)
     sc.attachments = attachments
+    if chambers:
+        sc.chambers = {"tri_lists": [t.astype(np.int32) for t, _p, _r in chambers], "pressure": np.array([p for _t, p, _r in chambers], dtype=np.float64),
+                       "ramp": np.array([r for _t, _p, r in chambers], dtype=np.float64)}
     for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = seqs
@@ -1262,6 +1327,8 @@ def apply(sc, be):
     if sc.attachments is not None:  # every `attach` and `stitch` line in one call, behind set_shell / set_rod, before opt_init and the pattern
         q = sc.attachments
         be.set_attachments(q["nodesA"], q["nodesB"], q["k"], q["L"])
+    if sc.chambers is not None:  # every `pressure` shape in one call, behind set_shell, before opt_init and the pattern
+        be.set_chambers(sc.chambers["tri_lists"], sc.chambers["pressure"])
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
         # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density

@@ -54,6 +54,9 @@ timestep = c.state()["timestep"] if fields else 0  # not 0 after `restart`
 for step in range(steps):
     t0 = time.time()
     sc.before_step(c, step * cfg.dt)  # state-dependent script decisions (AnimScripter::stepAnimScript)
+    ramped = sc.chamber_pressures((step + 1) * cfg.dt)  # `pressure <p> ramp <seconds>`: p min(1, t / ramp) at the time this step ends; None without a ramp
+    if ramped is not None:
+        c.chamber_set_pressure(ramped)
     writes_fields = fields is not None and (timestep + 1) % max(args.fields_every, 1) == 0
     x_prev = c.get_positions() if writes_fields or contact_report else None  # the friction field / columns need the positions the step started from
     it = c.solve_timestep(1000)

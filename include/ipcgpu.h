@@ -472,7 +472,7 @@ int ipcgpu_attach_energy_per_elem(ipcgpu_ctx*, double* perAttach_n);
 int ipcgpu_attach_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_attach_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 int ipcgpu_attach_state(ipcgpu_ctx*, double* length_n, double* force_n);
-/* Pressure chambers: a constant gas pressure inside closed surfaces (a balloon, a cushion, a hollow body under outside pressure).  A project extension: the
+/* Pressure chambers: a gas pressure inside closed surfaces, constant or following the ideal-gas law (a balloon, a cushion, a hollow body under outside pressure).  A project extension: the
  * reference has none.  A pressure load is a follower load -- its direction and size move with the surface --, which ipcgpu_opt_add_neumann (a constant
  * acceleration) cannot stand in for.
  *   A chamber is a closed, consistently oriented set of triangles (outward normals by the right-hand rule) over any nodes of the mesh: shell nodes, surface
@@ -489,10 +489,23 @@ int ipcgpu_attach_state(ipcgpu_ctx*, double* length_n, double* force_n);
  *               searches (every energy comparison inside a step uses one r_c).  ipcgpu_set_positions does not move it.
  *   Rows, columns and gradient entries of projected Dirichlet nodes are dropped.  The term is no stiffness: it does not enter the lagged stiffness damping
  *   (ipcgpu_opt_set_damping), whose matrix is to the bit what it is without chambers.  Contact is NOT changed.
- * Not modelled: a gas law (pressure as a function of the volume) -- its Hessian has a dense rank-one term per chamber, beta gradV gradV^T, that for real air
- * on cloth dominates every other stiffness; omitting it stalls Newton and lagging the pressure per step is unstable, so it needs a low-rank correction
- * inside the linear solve (a follow-up); until then ipcgpu_chamber_set_pressure and ipcgpu_chamber_state let a caller drive the pressure between time
- * steps --; open chambers closed by a plane; the mass of the enclosed gas.
+ * The gas law (ipcgpu_chamber_set_gas).  A chamber is either constant (above, the default) or GAS: an ideal gas with the ambient absolute pressure
+ *   p_amb >= 0, the exponent gamma >= 1 (1 isothermal, 1.4 adiabatic air) and the fill volume V0 > 0 (default: the rest volume).  The chamber's pressure p_c
+ *   then is the gauge pressure the gas has at V0, P0 = p_amb + p_c > 0, and ipcgpu_chamber_set_pressure between steps pumps gas in or out.  With V the
+ *   enclosed volume about r_c:
+ *     P(V) = P0 (V0 / V)^gamma,  gauge(V) = P(V) - p_amb
+ *     W = -P0 V0 ln(V / V0) + p_amb (V - V0)  (gamma == 1),   W = P0 V0 / (gamma - 1) ((V0 / V)^(gamma - 1) - 1) + p_amb (V - V0)  (gamma > 1),
+ *     W = +infinity for V <= 0 (the line search backs off)
+ *     dW/dx = -gauge(V) gradV,   d2W/dx2 = -gauge(V) d2V/dx2 + beta gradV gradV^T,  beta = gamma P(V) / V > 0
+ *   The first Hessian term is the constant chamber's per-triangle block with p = gauge(V) at the current positions, projected as above.  The second is PSD,
+ *   rank one and dense; it never enters the matrix.  The stepper applies it as a rank-k correction around the factor (Woodbury; k gas chambers, k <= 8):
+ *   y = A^-1 r, z_c = A^-1 u_c (u_c = gradV_c), C = diag(1 / (coef beta_c)) + U^T Z, C w = U^T y, d = y - Z w.  Where the factorisation reports a bad pivot
+ *   the diagonal fallback runs as without it and ignores the term.  Exact solvers only: with a gas chamber IPCGPU_SOLVER_PCG is IPCGPU_ERR_UNSUPPORTED, both
+ *   ways round.  Like the constant chamber the term stays out of the stiffness damping, the sparse part and the rank-one part both.
+ *   V_c, gauge_c, beta_c and W_c come from a deterministic two-pass reduction on the device (no floating-point atomic, no host read-back): the same state
+ *   gives the same bits, between calls and between contexts.
+ * Not modelled: open chambers closed by a plane; the mass, the temperature and any leakage of the enclosed gas; the gas law under the iterative solver or on
+ * a sharded context.
  * ipcgpu_set_chambers: chamber c owns the triangles [triEnd_nCh[c - 1], triEnd_nCh[c]) (from 0 for c = 0) of tri_colmajor (nTri x 3, nTri = triEnd_nCh[nCh - 1]);
  * pressure_nCh per chamber.  After ipcgpu_set_mesh, before ipcgpu_opt_init (else IPCGPU_ERR_STATE) and before ipcgpu_linsys_set_pattern: the three edges
  * of every triangle join vNeighbor (a node pattern that exists already is rebuilt by this call, without extra pairs).  It changes no mass and marks no
@@ -503,8 +516,24 @@ int ipcgpu_attach_state(ipcgpu_ctx*, double* length_n, double* force_n);
  * with chambers).  ipcgpu_set_mesh drops them.  Pressures are not part of the status file.
  * With chambers set their term enters the stepper and the building blocks wherever the shell, rod and tetrahedral elastic terms do, with the same
  * coefficient; ipcgpu_opt_system_report returns IPCGPU_ERR_UNSUPPORTED.  Without any no chamber kernel is ever launched.
- * ipcgpu_chamber_set_pressure: new pressures, at any time, also between time steps; checks that they are finite (IPCGPU_ERR_ARG) and needs chambers
- * (IPCGPU_ERR_STATE without).
+ * ipcgpu_chamber_set_pressure: new pressures, at any time, also between time steps; checks that they are finite and that a gas chamber keeps
+ * p_amb + p_c > 0 (IPCGPU_ERR_ARG) and needs chambers (IPCGPU_ERR_STATE without).
+ * ipcgpu_chamber_set_gas: per chamber isGas (0: constant), ambient, gamma and fillVolume (a null pointer or a value <= 0: the rest volume); the values of a
+ * chamber with isGas == 0 are not looked at.  After ipcgpu_set_chambers (IPCGPU_ERR_STATE without chambers), at any time, also between time steps.
+ * IPCGPU_ERR_ARG, naming the chamber: a value that is not finite, ambient < 0, gamma < 1, ambient + p_c <= 0, more than 8 gas chambers.  All isGas == 0
+ * restores the constant chambers exactly (the launches and the bits of a context that never called it).  ipcgpu_set_chambers drops the gas law.  Gas
+ * parameters are not part of the status file.
+ * ipcgpu_chamber_gas_get: what ipcgpu_chamber_set_gas set (a constant chamber: 0, 0, 1, its rest volume).  Any pointer may be null.
+ * ipcgpu_chamber_gas_state: per chamber at the current positions V, gauge(V) and beta (a constant chamber: its volume, p_c and 0; V <= 0 of a gas chamber:
+ * gauge = beta = 0).  Any pointer may be null.
+ * ipcgpu_chamber_volume_gradient: u = gradV of one chamber (gas or constant) at the current positions, 3 nV doubles, xyz interleaved; with projectDBC the
+ * entries of projected Dirichlet nodes are dropped, as in the gradient.
+ * ipcgpu_chamber_gas_solve: x = (A + coef sum_c beta_c u_c u_c^T)^-1 rhs, A the matrix as last assembled and factorised (exact solvers), the sum over the gas
+ * chambers with beta and u (Dirichlet entries projected) at the current positions: the routine the stepper wraps its own solve in.  Without a gas chamber:
+ * ipcgpu_linsys_solve.
+ * With a gas chamber the building blocks follow the gas energy: ipcgpu_chamber_energy returns W; _gradient_add uses gauge(V); _hessian_add and
+ * ipcgpu_assemble_newton add ONLY THE SPARSE PART, -gauge(V) d2V/dx2 projected -- the rank-one part exists in ipcgpu_chamber_gas_solve and the stepper alone;
+ * _energy_per_elem gives a gas chamber's triangle the share W_c V_t / V_c.
  * ipcgpu_chamber_get: counts2 = {nCh, nTri}; the lists as given; restVolume_nCh the volume at the rest positions; the current pressures.  Any pointer may be null.
  * ipcgpu_chamber_state: per chamber, at the current positions, the enclosed volume and the surface area (a deterministic segmented reduction; the volume is
  * taken about the centroid mean of the current positions), and refPoint_3nCh, the r_c the evaluations use now.  Any pointer may be null.
@@ -519,6 +548,11 @@ int ipcgpu_chamber_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_chamber_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_chamber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_chamber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_chamber_set_gas(ipcgpu_ctx*, const int* isGas_nCh, const double* ambient_nCh, const double* gamma_nCh, const double* fillVolume_nCh /*nullable or <= 0: rest volume*/);
+int ipcgpu_chamber_gas_get(ipcgpu_ctx*, int* isGas_nCh, double* ambient_nCh, double* gamma_nCh, double* fillVolume_nCh);
+int ipcgpu_chamber_gas_state(ipcgpu_ctx*, double* volume_nCh, double* gauge_nCh, double* beta_nCh);
+int ipcgpu_chamber_volume_gradient(ipcgpu_ctx*, int chamber, int projectDBC, double* u_3nV);
+int ipcgpu_chamber_gas_solve(ipcgpu_ctx*, double coef, const double* rhs_3nV, double* x_3nV);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

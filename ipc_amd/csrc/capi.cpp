@@ -250,6 +250,7 @@ int ipcgpu_ctx_set_solver(ipcgpu_ctx* c, int type)
             g_err = "the iterative solver is not sharded";
             return IPCGPU_ERR_UNSUPPORTED;
         }
+        if (type == IPCGPU_SOLVER_PCG && c->mesh->chamber.nGas()) throw UnsupportedError("the iterative solver with a gas chamber (its operator lacks the rank-k term of the gas law)");
         if (type != c->lin->solverType) c->lin->invalidateAnalysis();
         c->lin->solverType = type;
         return IPCGPU_OK;
@@ -1315,7 +1316,12 @@ int ipcgpu_chamber_energy_per_elem(ipcgpu_ctx* c, double* perTri)
         if (!n || !perTri) return IPCGPU_OK;
         DevBuf<double> e;
         e.alloc(n);
-        launch_chamber_energy_per_elem(o.chamberView(c->mesh->d_x.p), e.p, c->stream);
+        const HipChamber& h = c->mesh->chamber;
+        launch_chamber_energy_per_elem(o.chamberView(c->mesh->d_x.p, HipOptimizer::CHAMBER_P_CONSTANT), e.p, c->stream);
+        if (h.nGas()) { // a gas chamber's triangle gets the share W_c V_t / V_c
+            launch_chamber_gas_update(o.chamberView(c->mesh->d_x.p), h.gasView(), 0.0, nullptr, false, c->stream);
+            launch_chamber_gas_energy_per_elem(o.chamberView(c->mesh->d_x.p), h.d_isGas.p, h.d_gasState.p, e.p, c->stream);
+        }
         HIP_CHECK(hipGetLastError());
         e.download(perTri, n, c->stream);
         return IPCGPU_OK;
@@ -1329,6 +1335,106 @@ int ipcgpu_chamber_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
 {
     specChanged(c);
     return guarded([&] { return codimHessianAdd(c, CHAMBER, coef, projectDBC, CHAMBER_MISS); });
+}
+int ipcgpu_chamber_set_gas(ipcgpu_ctx* c, const int* isGas, const double* ambient, const double* gamma, const double* fillVolume)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (!m.chamber.n()) throw StateError("ipcgpu_chamber_set_gas without chambers: call ipcgpu_set_chambers first");
+        needArg(isGas && ambient && gamma, "null argument");
+        bool any = false;
+        for (int i = 0; i < m.chamber.n(); ++i) any = any || isGas[i] != 0;
+        if (any && c->lin->solverType == IPCGPU_SOLVER_PCG) throw UnsupportedError("a gas chamber with the iterative solver (its operator lacks the rank-k term of the gas law)");
+        m.setChamberGas(isGas, ambient, gamma, fillVolume, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_gas_get(ipcgpu_ctx* c, int* isGas, double* ambient, double* gamma, double* fillVolume)
+{
+    return guarded([&] {
+        const HipChamber& h = M(c).chamber;
+        for (int i = 0; i < h.n(); ++i) {
+            const bool g = h.nGas() && h.gas.isGas[i];
+            if (isGas) isGas[i] = g ? 1 : 0;
+            if (ambient) ambient[i] = g ? h.gas.ambient[i] : 0.0;
+            if (gamma) gamma[i] = g ? h.gas.gamma[i] : 1.0;
+            if (fillVolume) fillVolume[i] = g ? h.gas.fillVolume[i] : h.plan.restVolume[i];
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_gas_state(ipcgpu_ctx* c, double* volume, double* gauge, double* beta)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipChamber& h = c->mesh->chamber;
+        const int n = h.n();
+        if (!n) return IPCGPU_OK;
+        // a constant chamber: its volume from the segmented reduction of ipcgpu_chamber_state, gauge = p_c, beta = 0
+        std::vector<double> v((size_t)n, 0.0), st;
+        if (volume && h.nGas() < n) {
+            DevBuf<double> dv;
+            dv.alloc(n);
+            launch_chamber_state(o.chamberView(c->mesh->d_x.p), dv.p, nullptr, nullptr, c->stream);
+            HIP_CHECK(hipGetLastError());
+            dv.download(v.data(), n, c->stream);
+        }
+        if (h.nGas()) {
+            st.resize(4 * (size_t)n);
+            launch_chamber_gas_update(o.chamberView(c->mesh->d_x.p), h.gasView(), 0.0, nullptr, false, c->stream);
+            HIP_CHECK(hipGetLastError());
+            h.d_gasState.download(st.data(), st.size(), c->stream);
+        }
+        for (int i = 0; i < n; ++i) {
+            const bool g = h.nGas() && h.gas.isGas[i];
+            if (volume) volume[i] = g ? st[4 * (size_t)i] : v[i];
+            if (gauge) gauge[i] = g ? st[4 * (size_t)i + 1] : h.plan.pressure[i];
+            if (beta) beta[i] = g ? st[4 * (size_t)i + 2] : 0.0;
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_volume_gradient(ipcgpu_ctx* c, int chamber, int projectDBC, double* u)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipChamber& h = c->mesh->chamber;
+        if (!h.n()) throw StateError("ipcgpu_chamber_volume_gradient without chambers: call ipcgpu_set_chambers first");
+        needArg(u != nullptr, "null argument");
+        needArg(chamber >= 0 && chamber < h.n(), "chamber index out of range");
+        const size_t n3 = 3 * (size_t)c->mesh->nV;
+        std::vector<double> sel((size_t)h.n(), 0.0);
+        sel[(size_t)chamber] = 1.0;
+        DevBuf<double> ds, du;
+        ds.upload(sel, c->stream);
+        du.alloc(n3);
+        launch_chamber_volume_gradient(o.chamberView(c->mesh->d_x.p), ds.p, projectDBC ? 1 : 0, du.p, n3, c->stream);
+        HIP_CHECK(hipGetLastError());
+        du.download(u, n3, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_chamber_gas_solve(ipcgpu_ctx* c, double coef, const double* rhs, double* x)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        HipLinSysSolver& l = L(c);
+        needArg(rhs && x, "null argument");
+        need(l.numRows == 3 * c->mesh->nV && l.analyzed(), "ipcgpu_chamber_gas_solve needs the node pattern, analysed and factorised");
+        if (l.solverType == IPCGPU_SOLVER_PCG) throw UnsupportedError("ipcgpu_chamber_gas_solve with the iterative solver");
+        DevBuf<double> db, dx;
+        db.upload(rhs, l.numRows, c->stream);
+        dx.alloc(l.numRows);
+        const bool ok = l.solve(db.p, dx.p);
+        o.chamberGasCorrect(coef, /*projectDBC=*/true, dx.p); // the routine of the stepper (HipOptimizer::computeSearchDir)
+        dx.download(x, l.numRows, c->stream);
+        return ok ? IPCGPU_OK : IPCGPU_NOT_PD;
+    });
 }
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {

@@ -16,12 +16,28 @@
 // The rule for r_c: the mean of the centroids of the chamber's triangles.  ipcgpu_set_chambers computes it at the rest positions (chamber_plan.h);
 //   ipcgpu_opt_begin_timestep refreshes it on the device from the positions the step starts from (launch_chamber_state); it stays fixed through that step's
 //   Newton iterations and line searches, so every energy comparison inside a step uses one r_c.  ipcgpu_set_positions does not move it.
-// NOT modelled:
-//   * a gas law (pressure as a function of the volume).  Its Hessian has a dense rank-one term per chamber, beta gradV gradV^T, that for real air on cloth
-//     dominates every other stiffness: omitting it stalls Newton and lagging the pressure per step is unstable.  It needs a low-rank correction inside the
-//     linear solve.  Until then ipcgpu_chamber_set_pressure and ipcgpu_chamber_state let a caller drive the pressure between time steps.
-//   * open chambers closed by a plane;  * the mass of the enclosed gas;  * any change to contact.
-// The term is no stiffness: it does not enter the lagged stiffness damping (HipOptimizer::assembleDampingMtr masks it out).
+// The gas law (ipcgpu_chamber_set_gas).  A chamber is either CONSTANT (above, the default) or GAS: an ideal gas with the ambient absolute pressure p_amb >= 0,
+//   the exponent gamma >= 1 (1 isothermal, 1.4 adiabatic air) and the fill volume V0 > 0 (default: the rest volume).  p_c then is the gauge pressure the gas
+//   has at V0: P0 = p_amb + p_c > 0, and ipcgpu_chamber_set_pressure between steps pumps gas in or out.  With V the enclosed volume about r_c:
+//     P(V) = P0 (V0 / V)^gamma,   gauge(V) = P(V) - p_amb
+//     W = -P0 V0 ln(V / V0) + p_amb (V - V0)                                  gamma == 1
+//     W =  P0 V0 / (gamma - 1) ((V0 / V)^(gamma - 1) - 1) + p_amb (V - V0)    gamma  > 1
+//     W = +infinity for V <= 0   (the line search backs off, as for the rod's exact fold; gauge and beta are reported as 0 there)
+//     dW/dx = -gauge(V) gradV,    d2W/dx2 = -gauge(V) d2V/dx2 + beta gradV gradV^T,   beta = gamma P(V) / V > 0
+//   The first Hessian term is the constant chamber's per-triangle block with p = gauge(V) at the current positions, projected as above: the assemble kernel
+//   reads an EFFECTIVE pressure per chamber -- p_c of a constant chamber, written when the pressure is set; gauge(V_c) of a gas chamber, written by the gas
+//   update, which is enqueued ahead of every assembly at the same positions.  The second term is PSD, rank one and DENSE: it never enters the CSR.  The stepper
+//   applies it as a rank-k correction around the factor (k gas chambers, k <= 8; Woodbury):
+//     (A + coef sum_c beta_c u_c u_c^T) d = r,  u_c = gradV_c:   y = A^-1 r,  z_c = A^-1 u_c,  C = diag(1 / (coef beta_c)) + U^T Z,  C w = U^T y,  d = y - Z w
+//   ipcgpu_chamber_hessian_add and ipcgpu_assemble_newton add the sparse part only.
+// The gas update is two passes, deterministic, without a floating-point atomic and without the host: the host plan cuts every gas chamber's triangle range
+//   into slices of at most 256 triangles of one chamber (chamber_plan.h); pass 1, one 256-lane workgroup per slice, sums the triple products (a wave-level
+//   reduction, then LDS across the four waves) into one partial per slice; pass 2, one wave per gas chamber, sums that chamber's partials in index order and
+//   writes V_c, gauge_c, beta_c and W_c, gauge_c into the effective pressure, and adds coef W_c into the energy slot in chamber order.
+// NOT modelled: open chambers closed by a plane;  the mass, the temperature and any leakage of the enclosed gas;  the rank-k term inside the operator of the
+//   iterative solver (a context with a gas chamber refuses that solver);  any change to contact.
+// The term is no stiffness: it does not enter the lagged stiffness damping (HipOptimizer::assembleDampingMtr masks it out), neither as a constant chamber
+// nor as a gas chamber (its sparse part and its rank-one part both stay out).
 //
 // One lane per triangle, ids and y in registers.  Gradient entries and the 3 diagonal + 3 off-diagonal projected blocks go into the nodal vector and the upper
 // CSR by fp64 atomicAdd through the row lookup of csr_scatter_device.h.  Rows, columns and gradient entries of projected Dirichlet nodes are dropped
@@ -38,7 +54,7 @@ struct ChamberFields {
     const int* tri; // SoA [3][nTri]
     const int* chamberOf; // nTri
     const int* triEnd; // n: chamber c owns the triangles [triEnd[c - 1], triEnd[c])
-    const double* pressure; // n
+    const double* pressure; // n: the effective pressure (p_c; with gas chambers see above)
     const double* ref; // 3 n: r_c
 };
 struct ChamberView : ChamberFields, CodimBase {}; // (the shared fields behind the term's own: codim_view.h)
@@ -53,5 +69,32 @@ void launch_chamber_assemble(const ChamberView& v, double coef, int projectDBC, 
 // Any pointer may be null; refPoint may be the buffer behind v.ref (the kernel never reads v.ref): that is the stepper's refresh of r_c.
 // A segmented reduction in a fixed order: one workgroup per chamber strides over its triangle range, then a tree in LDS.  Deterministic.
 void launch_chamber_state(const ChamberView& v, double* volume, double* area, double* refPoint, hipStream_t s);
+
+// ---- the gas law -------------------------------------------------------------------------------------------------------------------------
+struct ChamberGasView {
+    int nGas, nSlice;
+    const int* sliceBegin; // nSlice
+    const int* sliceEnd; // nSlice
+    const int* sliceOff; // nGas + 1
+    const int* gasChamber; // nGas
+    const double* param; // 3 n: ambient, gamma, fill volume of chamber c at 3 c
+    const double* basePressure; // n: p_c
+    double* slicePartial; // nSlice (pass 1 -> pass 2)
+    double* effPressure; // n: pass 2 writes gauge_c of the gas chambers
+    double* state; // 4 n: V, gauge, beta, W of chamber c at 4 c (gas chambers only are written)
+};
+// The gas update at v.x (the value of v.pressure is not used).  out (nullable): *out = (accumulate ? *out : 0) + coef * (W of the gas chambers, in chamber order).
+void launch_chamber_gas_update(const ChamberView& v, const ChamberGasView& g, double coef, double* out, bool accumulate, hipStream_t s);
+// perTri[t] = W_c V_t / V_c for the triangles of the gas chambers (the others are not touched).  isGas: n ints, state: 4 n doubles as the last gas
+// update left them (ChamberGasView::state), both on the device.
+void launch_chamber_gas_energy_per_elem(const ChamberView& v, const int* isGas, const double* state, double* perTri, hipStream_t s);
+// u (n3 = 3 nV doubles, zeroed here) = gradV of ONE chamber: the gradient kernel with unit pressure.  select: n doubles, 1 at that chamber and 0 elsewhere.
+// Entries of projected Dirichlet nodes are dropped, as in the gradient.
+void launch_chamber_volume_gradient(const ChamberView& v, const double* select, int projectDBC, double* u, size_t n3, hipStream_t s);
+// The rank-k correction, k = g.nGas <= 8.  U, Z: k vectors of n3 doubles each, y: n3, dots: chamber_gas_dot_doubles(n3, k) doubles, w: 8 doubles.
+//   y -= Z w,  (diag(1 / (coef beta_c)) + U^T Z) w = U^T y;  the k + k (k + 1) / 2 dot products in a fixed order in two passes, the k x k Cholesky in one wave.
+//   A chamber with beta_c == 0 (V_c <= 0) gets w_c = 0.
+size_t chamber_gas_dot_doubles(size_t n3, int k);
+void launch_chamber_gas_woodbury(const ChamberGasView& g, double coef, size_t n3, const double* U, const double* Z, double* y, double* dots, double* w, hipStream_t s);
 
 } // namespace ipcgpu

@@ -214,7 +214,198 @@ __global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_state(ChamberView v, 
     }
 }
 
+// ---- the gas law ----
+constexpr int GAS_MAX = 8; // gas chambers per context (chamber_plan.h: CHAMBER_GAS_MAX)
+constexpr int GAS_DOT_BLOCKS = 128; // partial sums per dot product at the most
+
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x; // (lane 0 holds the sum)
+}
+
+// pass 1: one workgroup per slice, one lane per triangle of it
+__global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_gas_slice(ChamberView v, ChamberGasView g)
+{
+    const int t = g.sliceBegin[blockIdx.x] + (int)threadIdx.x;
+    double e = 0.0;
+    if (t < g.sliceEnd[blockIdx.x]) {
+        Tri T;
+        load_tri(v, t, T);
+        e = triple(T.y);
+    }
+    store_block_sum<CHAMBER_BLOCK>(e, g.slicePartial);
+}
+
+// pass 2: wave w takes gas chamber w; thread 0 then adds the energies in chamber order
+__global__ __launch_bounds__(64 * GAS_MAX) void k_chamber_gas_state(ChamberGasView g, double coef, double* __restrict__ out, int accumulate)
+{
+    __shared__ double sW[GAS_MAX];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w < g.nGas) {
+        double x = 0.0;
+        for (int i = g.sliceOff[w] + lane; i < g.sliceOff[w + 1]; i += 64) x += g.slicePartial[i];
+        x = wave_sum(x);
+        if (lane == 0) {
+            const int c = g.gasChamber[w];
+            const double V = x / 6.0, pAmb = g.param[3 * c], gamma = g.param[3 * c + 1], V0 = g.param[3 * c + 2], pc = g.basePressure[c], P0 = pAmb + pc;
+            double gauge = 0.0, beta = 0.0, W = INFINITY;
+            if (V > 0.0) {
+                // ln(V0 / V).  Near V0 from the exact difference V - V0: log(V0 / V) carries the quotient's rounding, an ABSOLUTE error of u however close V is
+                // to V0, i.e. u P0 V0 in W -- with real air far above what the line search must resolve for a body at rest (the two terms of W nearly cancel
+                // there).  Far from V0 the quotient is the better conditioned form (log1p amplifies the error of its argument by V0 / V).
+                const double dV = V - V0;
+                const double lr = fabs(dV) <= 0.5 * V0 ? -log1p(dV / V0) : log(V0 / V);
+                const double grow = expm1(gamma * lr); // (V0 / V)^gamma - 1
+                gauge = pc + P0 * grow;
+                beta = gamma * (P0 + P0 * grow) / V;
+                W = (gamma == 1.0 ? P0 * V0 * lr : P0 * V0 * (expm1((gamma - 1.0) * lr) / (gamma - 1.0))) + pAmb * (V - V0);
+            }
+            g.state[4 * c] = V;
+            g.state[4 * c + 1] = gauge;
+            g.state[4 * c + 2] = beta;
+            g.state[4 * c + 3] = W;
+            g.effPressure[c] = gauge;
+            sW[w] = W;
+        }
+    }
+    __syncthreads();
+    if (out && threadIdx.x == 0) {
+        double e = accumulate ? out[0] : 0.0;
+        if (coef != 0.0) // (0 x inf of a collapsed chamber would be NaN: a zero coefficient adds nothing)
+            for (int i = 0; i < g.nGas; ++i) e += coef * sW[i];
+        out[0] = e;
+    }
+}
+
+__global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_gas_energy_per_elem(ChamberView v, const int* __restrict__ isGas, const double* __restrict__ state, double* __restrict__ perTri)
+{
+    const int t = blockIdx.x * CHAMBER_BLOCK + threadIdx.x;
+    if (t >= v.nTri) return;
+    const int c = v.chamberOf[t];
+    if (!isGas[c]) return;
+    Tri T;
+    load_tri(v, t, T);
+    perTri[t] = state[4 * c + 3] * ((triple(T.y) / 6.0) / state[4 * c]);
+}
+
+// dot product q of the k + k (k + 1) / 2: q < k is u_q . y, then u_i . z_j for i <= j in row order; one partial per workgroup, each workgroup a contiguous chunk
+__global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_gas_dots(int k, size_t n3, size_t chunk, const double* __restrict__ U, const double* __restrict__ Z, const double* __restrict__ y,
+    double* __restrict__ partial)
+{
+    int q = blockIdx.y, i = q, j = -1;
+    if (q >= k) {
+        q -= k;
+        for (i = 0; q >= k - i; ++i) q -= k - i;
+        j = i + q;
+    }
+    const double* a = U + (size_t)i * n3;
+    const double* b = j < 0 ? y : Z + (size_t)j * n3;
+    const size_t begin = blockIdx.x * chunk, end = begin + chunk < n3 ? begin + chunk : n3;
+    double x = 0.0;
+    for (size_t e = begin + threadIdx.x; e < end; e += CHAMBER_BLOCK) x += a[e] * b[e];
+    __shared__ double sm[CHAMBER_BLOCK / 64];
+    const double r = block_sum<CHAMBER_BLOCK>(x, sm);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
+}
+
+// one wave: the second pass of the dot products, then C w = U^T y by a k x k Cholesky
+__global__ __launch_bounds__(64) void k_chamber_gas_small_solve(ChamberGasView g, double coef, int nb, const double* __restrict__ partial, double* __restrict__ w)
+{
+    __shared__ double sd[GAS_MAX + GAS_MAX * (GAS_MAX + 1) / 2];
+    const int k = g.nGas, nq = k + k * (k + 1) / 2, lane = threadIdx.x;
+    for (int q = 0; q < nq; ++q) {
+        double x = 0.0;
+        for (int i = lane; i < nb; i += 64) x += partial[(size_t)q * nb + i];
+        x = wave_sum(x);
+        if (lane == 0) sd[q] = x;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    __shared__ double C[GAS_MAX][GAS_MAX], b[GAS_MAX]; // (in LDS: indexed by loop variables, registers would spill to scratch)
+    __shared__ int on[GAS_MAX];
+    int q = k;
+    for (int i = 0; i < k; ++i) {
+        const double cb = coef * g.state[4 * g.gasChamber[i] + 2];
+        on[i] = cb > 0.0;
+        b[i] = sd[i];
+        for (int j = i; j < k; ++j) C[j][i] = C[i][j] = sd[q++];
+        C[i][i] += on[i] ? 1.0 / cb : 0.0;
+    }
+    // a chamber without a rank-one term (beta == 0) leaves the system: its row and column become the identity's
+    for (int i = 0; i < k; ++i)
+        if (!on[i]) {
+            for (int j = 0; j < k; ++j) C[i][j] = C[j][i] = 0.0;
+            C[i][i] = 1.0;
+            b[i] = 0.0;
+        }
+    for (int j = 0; j < k; ++j) { // C = L L^T, L in the lower triangle
+        double d = C[j][j];
+        for (int p = 0; p < j; ++p) d -= C[j][p] * C[j][p];
+        d = sqrt(d);
+        C[j][j] = d;
+        for (int i = j + 1; i < k; ++i) {
+            double x = C[i][j];
+            for (int p = 0; p < j; ++p) x -= C[i][p] * C[j][p];
+            C[i][j] = x / d;
+        }
+    }
+    for (int i = 0; i < k; ++i) {
+        double x = b[i];
+        for (int p = 0; p < i; ++p) x -= C[i][p] * b[p];
+        b[i] = x / C[i][i];
+    }
+    for (int i = k - 1; i >= 0; --i) {
+        double x = b[i];
+        for (int p = i + 1; p < k; ++p) x -= C[p][i] * b[p];
+        b[i] = x / C[i][i];
+    }
+    for (int i = 0; i < GAS_MAX; ++i) w[i] = i < k ? b[i] : 0.0;
+}
+
+__global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_gas_apply(int k, size_t n3, const double* __restrict__ Z, const double* __restrict__ w, double* __restrict__ y)
+{
+    const size_t e = (size_t)blockIdx.x * CHAMBER_BLOCK + threadIdx.x;
+    if (e >= n3) return;
+    double x = y[e];
+    for (int c = 0; c < k; ++c) x -= Z[(size_t)c * n3 + e] * w[c];
+    y[e] = x;
+}
+
+int gas_dot_blocks(size_t n3) { return (int)std::max<size_t>(1, std::min<size_t>(GAS_DOT_BLOCKS, (n3 + CHAMBER_BLOCK - 1) / CHAMBER_BLOCK)); }
+
 } // namespace
+
+void launch_chamber_gas_update(const ChamberView& v, const ChamberGasView& g, double coef, double* out, bool accumulate, hipStream_t s)
+{
+    if (g.nGas <= 0) return;
+    hipLaunchKernelGGL(k_chamber_gas_slice, dim3(g.nSlice), dim3(CHAMBER_BLOCK), 0, s, v, g);
+    hipLaunchKernelGGL(k_chamber_gas_state, dim3(1), dim3(64 * GAS_MAX), 0, s, g, coef, out, accumulate ? 1 : 0);
+}
+void launch_chamber_gas_energy_per_elem(const ChamberView& v, const int* isGas, const double* state, double* perTri, hipStream_t s)
+{
+    if (v.nTri <= 0 || !perTri) return;
+    hipLaunchKernelGGL(k_chamber_gas_energy_per_elem, dim3(nblk(v.nTri, CHAMBER_BLOCK)), dim3(CHAMBER_BLOCK), 0, s, v, isGas, state, perTri);
+}
+void launch_chamber_volume_gradient(const ChamberView& v, const double* select, int projectDBC, double* u, size_t n3, hipStream_t s)
+{
+    (void)hipMemsetAsync(u, 0, n3 * sizeof(double), s);
+    ChamberView one = v;
+    one.pressure = select;
+    launch_chamber_assemble(one, -1.0, projectDBC, u, nullptr, nullptr, s); // dW/dx = -p gradV: p = 1 and the coefficient -1 leave gradV
+}
+size_t chamber_gas_dot_doubles(size_t n3, int k) { return (size_t)gas_dot_blocks(n3) * (size_t)(k + k * (k + 1) / 2); }
+void launch_chamber_gas_woodbury(const ChamberGasView& g, double coef, size_t n3, const double* U, const double* Z, double* y, double* dots, double* w, hipStream_t s)
+{
+    const int k = g.nGas;
+    if (k <= 0 || !n3) return;
+    const int nb = gas_dot_blocks(n3);
+    const size_t chunk = (n3 + nb - 1) / nb;
+    hipLaunchKernelGGL(k_chamber_gas_dots, dim3(nb, k + k * (k + 1) / 2), dim3(CHAMBER_BLOCK), 0, s, k, n3, chunk, U, Z, y, dots);
+    hipLaunchKernelGGL(k_chamber_gas_small_solve, dim3(1), dim3(64), 0, s, g, coef, nb, dots, w);
+    hipLaunchKernelGGL(k_chamber_gas_apply, dim3((unsigned)((n3 + CHAMBER_BLOCK - 1) / CHAMBER_BLOCK)), dim3(CHAMBER_BLOCK), 0, s, k, n3, Z, w, y);
+}
 
 int chamber_energy_blocks(const ChamberView& v) { return std::max(1, nblk(v.nTri, CHAMBER_BLOCK)); }
 

@@ -100,4 +100,59 @@ bool buildChamberPlan(int nV, const double* Vrest, int nCh, const int* triEnd, c
     return true;
 }
 
+bool chamberGasPressureOk(const ChamberGas& gas, int n, const double* pressure, std::string& err)
+{
+    if (!gas.nGas) return true;
+    for (int c = 0; c < n; ++c)
+        if (gas.isGas[c] && !(gas.ambient[c] + pressure[c] > 0.0)) {
+            err = "gas chamber " + std::to_string(c) + ": ambient + pressure = " + std::to_string(gas.ambient[c] + pressure[c]) + " <= 0 (the absolute pressure at the fill volume must be positive)";
+            return false;
+        }
+    return true;
+}
+
+bool buildChamberGas(const ChamberPlan& plan, const int* isGas, const double* ambient, const double* gamma, const double* fillVolume, ChamberGas& gas, std::string& err)
+{
+    gas = ChamberGas();
+    auto fail = [&](const std::string& what) {
+        gas = ChamberGas();
+        err = what;
+        return false;
+    };
+    const int n = plan.n;
+    if (n <= 0) return fail("chamber_set_gas without chambers");
+    if (!isGas || !ambient || !gamma) return fail("chamber_set_gas: null argument");
+    gas.isGas.assign((std::size_t)n, 0);
+    gas.ambient.assign((std::size_t)n, 0.0);
+    gas.gamma.assign((std::size_t)n, 1.0);
+    gas.fillVolume = plan.restVolume;
+    for (int c = 0; c < n; ++c) {
+        if (!isGas[c]) continue;
+        const std::string at = "chamber_set_gas: chamber " + std::to_string(c);
+        if (!std::isfinite(ambient[c]) || !std::isfinite(gamma[c]) || (fillVolume && !std::isfinite(fillVolume[c]))) return fail(at + " has a parameter that is not finite");
+        if (ambient[c] < 0.0) return fail(at + " has the ambient pressure " + std::to_string(ambient[c]) + " < 0");
+        if (gamma[c] < 1.0) return fail(at + " has the exponent gamma " + std::to_string(gamma[c]) + " < 1");
+        gas.isGas[c] = 1;
+        gas.ambient[c] = ambient[c];
+        gas.gamma[c] = gamma[c];
+        if (fillVolume && fillVolume[c] > 0.0) gas.fillVolume[c] = fillVolume[c];
+        gas.gasChamber.push_back(c);
+    }
+    gas.nGas = (int)gas.gasChamber.size();
+    if (gas.nGas > CHAMBER_GAS_MAX)
+        return fail("chamber_set_gas: " + std::to_string(gas.nGas) + " gas chambers, more than the " + std::to_string(CHAMBER_GAS_MAX) + " a context can hold");
+    std::string perr;
+    if (!chamberGasPressureOk(gas, n, plan.pressure.data(), perr)) return fail("chamber_set_gas: " + perr);
+    gas.sliceOff.push_back(0);
+    for (int c : gas.gasChamber) {
+        const int begin = c ? plan.triEnd[c - 1] : 0, end = plan.triEnd[c];
+        for (int b = begin; b < end; b += CHAMBER_GAS_SLICE) {
+            gas.sliceBegin.push_back(b);
+            gas.sliceEnd.push_back(std::min(b + CHAMBER_GAS_SLICE, end));
+        }
+        gas.sliceOff.push_back(gas.nSlice());
+    }
+    return true;
+}
+
 } // namespace ipcgpu

@@ -29,4 +29,28 @@ struct ChamberPlan {
 // two triangles that traverse a shared edge in the same direction, a rest volume <= 0 (the chamber is oriented inward).
 bool buildChamberPlan(int nV, const double* Vrest, int nCh, const int* triEnd, const int* tri, const double* pressure, ChamberPlan& plan, std::string& err);
 
+// The gas law of the chambers (ipcgpu_chamber_set_gas; the model is stated in chamber_kernels.h): which chambers follow it, their parameters, and the cut of
+// every gas chamber's triangle range into slices for the two-pass volume reduction.  nGas == 0: every chamber is constant and nothing else is ever read.
+constexpr int CHAMBER_GAS_MAX = 8; // gas chambers per context: the rank of the correction inside the linear solve
+constexpr int CHAMBER_GAS_SLICE = 256; // triangles per slice at the most: one workgroup of the first pass
+
+struct ChamberGas {
+    int nGas = 0;
+    std::vector<int> isGas; // n (0 / 1)
+    std::vector<double> ambient, gamma, fillVolume; // n; of a constant chamber 0, 1 and its rest volume
+    std::vector<int> gasChamber; // nGas: the gas chambers, ascending
+    // the slices: chamber after chamber (gas chambers only), inside a chamber by ascending triangle index; every slice holds 1 .. CHAMBER_GAS_SLICE triangles of
+    // ONE chamber, and the slices of gas chamber g (the g-th of gasChamber) are [sliceOff[g], sliceOff[g + 1])
+    std::vector<int> sliceBegin, sliceEnd; // nSlice: triangles [begin, end)
+    std::vector<int> sliceOff; // nGas + 1
+    int nSlice() const { return (int)sliceBegin.size(); }
+};
+
+// isGas, ambient, gamma: n values each; fillVolume: nullable, and a value <= 0 means the chamber's rest volume.  The parameters of a chamber with isGas == 0 are
+// not looked at.  false, with the reason in err (it names the chamber) and gas empty: no chambers, a null argument, a value that is not finite, ambient < 0,
+// gamma < 1, ambient + pressure <= 0, more than CHAMBER_GAS_MAX gas chambers.
+bool buildChamberGas(const ChamberPlan& plan, const int* isGas, const double* ambient, const double* gamma, const double* fillVolume, ChamberGas& gas, std::string& err);
+// may the chambers take these pressures: false, naming the chamber, where a gas chamber would get ambient + pressure <= 0
+bool chamberGasPressureOk(const ChamberGas& gas, int n, const double* pressure, std::string& err);
+
 } // namespace ipcgpu

@@ -97,6 +97,18 @@ struct HipChamber {
     unsigned nbVersionAfter = 0;
     int n() const { return plan.n; }
     int nTri() const { return plan.nTri; }
+    // The gas law (ipcgpu_chamber_set_gas; chamber_kernels.h).  nGas() == 0: every chamber is constant, nothing below is allocated or read, and the launches
+    // are those of a context that never heard of the gas law.  Otherwise the kernels read TWO pressure arrays in place of d_pressure (which keeps p_c):
+    //   d_pConst  p_c of the constant chambers and 0 for the gas chambers: what the per-triangle energy kernel multiplies the volume with
+    //   d_pEff    the effective pressure the assemble kernel reads: p_c of the constant chambers, gauge(V_c) of the gas chambers as the last gas update left it
+    ChamberGas gas;
+    DevBuf<int> d_sliceBegin, d_sliceEnd, d_sliceOff, d_gasChamber, d_isGas;
+    DevBuf<double> d_pConst, d_pEff, d_gasParam, d_slicePartial, d_gasState, d_gasSelect; // d_gasSelect: nGas rows of n doubles, row g is 1 at gasChamber[g]
+    int nGas() const { return gas.nGas; }
+    ChamberGasView gasView() const
+    {
+        return ChamberGasView{ gas.nGas, gas.nSlice(), d_sliceBegin.p, d_sliceEnd.p, d_sliceOff.p, d_gasChamber.p, d_gasParam.p, d_pressure.p, d_slicePartial.p, d_pEff.p, d_gasState.p };
+    }
 };
 
 class HipMesh {
@@ -155,7 +167,11 @@ public:
     // computeFeatures drops them.  Touches no mass and no inMesh mark: a chamber is no body.
     HipChamber chamber;
     void setChambers(int nCh, const int* triEnd, const int* tri_colmajor, const double* pressure, hipStream_t s);
-    void setChamberPressure(const double* pressure, hipStream_t s); // finite values only; needs chambers
+    void setChamberPressure(const double* pressure, hipStream_t s); // finite values only; needs chambers; a gas chamber keeps ambient + pressure > 0
+    // The gas law (chamber_plan.h: buildChamberGas): validates, uploads the parameters, the slices and the two pressure arrays.  All isGas == 0 drops it
+    // again.  setChambers and computeFeatures drop it too.
+    void setChamberGas(const int* isGas, const double* ambient, const double* gamma, const double* fillVolume, hipStream_t s);
+    void uploadChamberGasPressures(hipStream_t s); // d_pConst and d_pEff from plan.pressure
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -323,8 +339,17 @@ public:
     ShellLimitView shellLimitView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
     AttachView attachView(const double* x_dev) const;
-    ChamberView chamberView(const double* x_dev) const;
+    // pressure: which array the kernels read as the pressure -- d_pressure without a gas chamber, whatever is asked; with one, the effective pressure
+    // (CHAMBER_P_EFFECTIVE, what the assembly wants) or the constant chambers' alone (CHAMBER_P_CONSTANT, what the per-triangle energy wants)
+    enum { CHAMBER_P_EFFECTIVE = 0, CHAMBER_P_CONSTANT = 1 };
+    ChamberView chamberView(const double* x_dev, int pressure = CHAMBER_P_EFFECTIVE) const;
     void refreshChamberRef(); // r_c of every chamber from the current positions, on the device (beginTimestep)
+    // The gas chambers' dense rank-k Hessian term, coef sum_c beta_c u_c u_c^T, as a correction around the solver's retained factor (chamber_kernels.h):
+    // y_dev holds A^-1 r on entry and (A + coef sum beta_c u_c u_c^T)^-1 r on return, with beta and u at the mesh's current positions.  k further solves,
+    // everything on the stream, no synchronisation.  Nothing without a gas chamber.  The stepper (computeSearchDir) and ipcgpu_chamber_gas_solve both call it.
+    void chamberGasCorrect(double coef, bool projectDBC, double* y_dev);
+    void chamberVolumeGradient(int gasIndex, bool projectDBC, double* u_dev); // u_c of the gasIndex-th gas chamber at the current positions
+    DevBuf<double> d_gasU, d_gasZ, d_gasDots, d_gasW;
     size_t codimPartials() const; // doubles of d_partial the largest energy launch needs
     // *out_dev (+)= coef * energy of the chosen terms at x_dev; accumulate == false: the first term launched overwrites *out_dev, the later ones add.  The
     // limit's energy is +infinity with a stretch at or over its limit, which every comparison of the line search rejects like the fold of a rod node

@@ -37,6 +37,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
     if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
+    chamber.gas = ChamberGas(); // ... with their gas law
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -331,6 +332,7 @@ void HipMesh::setChambers(int nCh, const int* triEnd, const int* tri, const doub
     addNeighbourPairs(plan.pairs);
     chamber.nbVersionAfter = nbVersion;
     chamber.plan = std::move(plan);
+    chamber.gas = ChamberGas(); // the gas law belonged to the chambers this call replaces
     if (!chamber.n()) return;
     const ChamberPlan& p = chamber.plan;
     chamber.d_tri.upload(p.tri, s);
@@ -351,9 +353,56 @@ void HipMesh::setChamberPressure(const double* pressure, hipStream_t s)
     if (!pressure) throw ArgError("chamber_set_pressure: null argument");
     for (int c = 0; c < chamber.n(); ++c)
         if (!std::isfinite(pressure[c])) throw ArgError("chamber_set_pressure: the pressure of chamber " + std::to_string(c) + " is not finite");
+    std::string err;
+    if (!chamberGasPressureOk(chamber.gas, chamber.n(), pressure, err)) throw ArgError("chamber_set_pressure: " + err);
     chamber.plan.pressure.assign(pressure, pressure + chamber.n());
     chamber.d_pressure.upload(chamber.plan.pressure, s);
+    if (chamber.nGas()) uploadChamberGasPressures(s);
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::uploadChamberGasPressures(hipStream_t s)
+{
+    // the gas chambers' entries of d_pEff hold p_c until the next gas update overwrites them with gauge(V_c): every assembly enqueues one first
+    std::vector<double> pConst = chamber.plan.pressure;
+    for (int c : chamber.gas.gasChamber) pConst[c] = 0.0;
+    chamber.d_pConst.upload(pConst, s);
+    chamber.d_pEff.upload(chamber.plan.pressure, s);
+    HIP_CHECK(hipStreamSynchronize(s)); // (pConst leaves scope)
+}
+
+void HipMesh::setChamberGas(const int* isGas, const double* ambient, const double* gamma, const double* fillVolume, hipStream_t s)
+{
+    if (!chamber.n()) throw StateError("ipcgpu_chamber_set_gas without chambers: call ipcgpu_set_chambers first");
+    ChamberGas gas;
+    std::string err;
+    if (!buildChamberGas(chamber.plan, isGas, ambient, gamma, fillVolume, gas, err)) throw ArgError(err);
+    HIP_CHECK(hipStreamSynchronize(s)); // (nothing enqueued reads the arrays this call replaces)
+    if (!gas.nGas) { // every chamber constant: the context is what it was before the gas law was ever set
+        chamber.gas = ChamberGas();
+        return;
+    }
+    chamber.gas = std::move(gas);
+    const ChamberGas& g = chamber.gas;
+    const size_t n = (size_t)chamber.n();
+    chamber.d_sliceBegin.upload(g.sliceBegin, s);
+    chamber.d_sliceEnd.upload(g.sliceEnd, s);
+    chamber.d_sliceOff.upload(g.sliceOff, s);
+    chamber.d_gasChamber.upload(g.gasChamber, s);
+    chamber.d_isGas.upload(g.isGas, s);
+    std::vector<double> param(3 * n), select((size_t)g.nGas * n, 0.0);
+    for (size_t c = 0; c < n; ++c) {
+        param[3 * c] = g.ambient[c];
+        param[3 * c + 1] = g.gamma[c];
+        param[3 * c + 2] = g.fillVolume[c];
+    }
+    for (int i = 0; i < g.nGas; ++i) select[(size_t)i * n + (size_t)g.gasChamber[i]] = 1.0;
+    chamber.d_gasParam.upload(param, s);
+    chamber.d_gasSelect.upload(select, s);
+    chamber.d_slicePartial.alloc((size_t)g.nSlice());
+    chamber.d_gasState.alloc(4 * n);
+    chamber.d_gasState.zero(s);
+    uploadChamberGasPressures(s);
 }
 
 void HipMesh::addSurfaceEdges(int nSF, const int* SF, int nCE, const int* CE)

@@ -147,7 +147,7 @@ AttachView HipOptimizer::attachView(const double* x_dev) const
     return v;
 }
 
-ChamberView HipOptimizer::chamberView(const double* x_dev) const
+ChamberView HipOptimizer::chamberView(const double* x_dev, int pressure) const
 {
     const HipChamber& h = mesh.chamber;
     ChamberView v;
@@ -157,9 +157,34 @@ ChamberView HipOptimizer::chamberView(const double* x_dev) const
     v.tri = h.d_tri.p;
     v.chamberOf = h.d_chamberOf.p;
     v.triEnd = h.d_triEnd.p;
-    v.pressure = h.d_pressure.p;
+    v.pressure = !h.nGas() ? h.d_pressure.p : pressure == CHAMBER_P_CONSTANT ? h.d_pConst.p : h.d_pEff.p;
     v.ref = h.d_ref.p;
     return v;
+}
+
+void HipOptimizer::chamberVolumeGradient(int gasIndex, bool projectDBC, double* u_dev)
+{
+    const HipChamber& h = mesh.chamber;
+    launch_chamber_volume_gradient(chamberView(mesh.d_x.p), h.d_gasSelect.p + (size_t)gasIndex * (size_t)h.n(), projectDBC ? 1 : 0, u_dev, 3 * (size_t)mesh.nV, stream);
+}
+
+void HipOptimizer::chamberGasCorrect(double coef, bool projectDBC, double* y_dev)
+{
+    const HipChamber& h = mesh.chamber;
+    const int k = h.nGas();
+    if (!k) return;
+    const size_t n3 = 3 * (size_t)mesh.nV;
+    d_gasU.alloc((size_t)k * n3);
+    d_gasZ.alloc((size_t)k * n3);
+    d_gasDots.alloc(chamber_gas_dot_doubles(n3, k));
+    d_gasW.alloc(8);
+    launch_chamber_gas_update(chamberView(mesh.d_x.p), h.gasView(), 0.0, nullptr, false, stream); // beta_c at the current positions
+    for (int c = 0; c < k; ++c) {
+        chamberVolumeGradient(c, projectDBC, d_gasU.p + (size_t)c * n3);
+        lin.solve(d_gasU.p + (size_t)c * n3, d_gasZ.p + (size_t)c * n3);
+    }
+    launch_chamber_gas_woodbury(h.gasView(), coef, n3, d_gasU.p, d_gasZ.p, y_dev, d_gasDots.p, d_gasW.p, stream);
+    HIP_CHECK(hipGetLastError());
 }
 
 void HipOptimizer::refreshChamberRef()
@@ -191,8 +216,21 @@ const CodimTerm CODIM_TERMS[] = {
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_attach_energy(o.attachView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_attach_assemble(o.attachView(x), coef, proj, g, a, err, o.stream); } },
     { HipOptimizer::CODIM_CHAMBER, [](const HipMesh& m) { return m.chamber.nTri(); },
-        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_chamber_energy(o.chamberView(x), coef, partial, out, acc, o.stream); },
-        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_chamber_assemble(o.chamberView(x), coef, proj, g, a, err, o.stream); } },
+        // with a gas chamber: the per-triangle energy of the constant chambers (where there is one), then the gas update, which adds the gas chambers' W; and the
+        // gas update ahead of the assembly, which reads the gauge pressures it leaves (chamber_kernels.h).  Without one: the two launches as they always were.
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) {
+            const HipChamber& h = o.mesh.chamber;
+            if (!h.nGas() || h.nGas() < h.n()) {
+                launch_chamber_energy(o.chamberView(x, HipOptimizer::CHAMBER_P_CONSTANT), coef, partial, out, acc, o.stream);
+                acc = true;
+            }
+            if (h.nGas()) launch_chamber_gas_update(o.chamberView(x), h.gasView(), coef, out, acc, o.stream);
+        },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) {
+            const HipChamber& h = o.mesh.chamber;
+            if (h.nGas()) launch_chamber_gas_update(o.chamberView(x), h.gasView(), 0.0, nullptr, false, o.stream);
+            launch_chamber_assemble(o.chamberView(x), coef, proj, g, a, err, o.stream);
+        } },
 };
 } // namespace
 
@@ -1402,6 +1440,7 @@ void HipOptimizer::computeSearchDir()
             // the sweeps and the pivot flag comes back with it -- one synchronisation (round 6; two before, and a third at the head of the next pass)
             ok = lin.factorizeSolve(rhs, d_searchDir.p, /*wait=*/false, signInSolver);
             if (ok) {
+                chamberGasCorrect(elasticCoef(), projDBC, d_searchDir.p); // (enqueued behind the sweeps; a bad pivot ends in the diagonal fallback below, which ignores the rank-k term)
                 enqueueDirNorm();
                 launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
                 HIP_CHECK(hipStreamSynchronize(stream));
@@ -1452,7 +1491,8 @@ void HipOptimizer::computeSearchDir()
 bool HipOptimizer::fastPath() const
 {
     // (the iterative solver synchronises inside its solve and may end in the diagonal fallback: the general branch of computeSearchDir)
-    return worldSize == 1 && !ipOn() && nbcGroups.empty() && !(dampingStiff > 0.0) && !(rhoDBC && !tpIds.empty()) && lin.solverType != 2;
+    // (a gas chamber puts k further solves and the rank-k correction behind the solve: the general branch too)
+    return worldSize == 1 && !ipOn() && nbcGroups.empty() && !(dampingStiff > 0.0) && !(rhoDBC && !tpIds.empty()) && lin.solverType != 2 && !mesh.chamber.nGas();
 }
 
 void HipOptimizer::resolveEventTimers()

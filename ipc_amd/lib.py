@@ -772,7 +772,47 @@ class Context:
         return self._codim_gradient_add("chamber", coef, projectDBC, grad)
 
     def chamber_hessian_add(self, coef=1.0, projectDBC=True):
+        """the sparse part only: a gas chamber's rank-one term beta gradV gradV^T lives in chamber_gas_solve and the stepper"""
         self._codim_hessian_add("chamber", coef, projectDBC)
+
+    # ---- the gas law of the chambers (ipcgpu_chamber_set_gas)
+    def chamber_set_gas(self, is_gas, ambient=0.0, gamma=1.0, fill_volume=None):
+        """per chamber (scalars broadcast): is_gas (False: constant pressure), the ambient absolute pressure, the exponent gamma (1 isothermal, 1.4 adiabatic
+        air) and the fill volume (None or <= 0: the rest volume).  The chamber's pressure becomes the gauge pressure at the fill volume.  After set_chambers,
+        at any time; all False restores the constant chambers exactly."""
+        n = self._chamber_counts()[0]
+        g = _i32(np.broadcast_to(np.asarray(is_gas).astype(np.int32), (n,)))
+        a = _f64(np.broadcast_to(np.asarray(ambient, dtype=np.float64), (n,)))
+        k = _f64(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (n,)))
+        f = None if fill_volume is None else _f64(np.broadcast_to(np.asarray(fill_volume, dtype=np.float64), (n,)))
+        self._chk(self._L.ipcgpu_chamber_set_gas(self.h, _ip(g), _dp(a), _dp(k), _dp(f)))
+
+    def chamber_gas_get(self):
+        """dict: isGas, ambient, gamma, fillVolume per chamber"""
+        n = self._chamber_counts()[0]
+        g, a, k, f = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n), np.zeros(n)
+        self._chk(self._L.ipcgpu_chamber_gas_get(self.h, _ip(g), _dp(a), _dp(k), _dp(f)))
+        return {"isGas": g, "ambient": a, "gamma": k, "fillVolume": f}
+
+    def chamber_gas_state(self):
+        """(volume, gauge, beta) per chamber at the current positions; a constant chamber: (volume, p, 0)"""
+        n = self._chamber_counts()[0]
+        v, g, b = np.zeros(n), np.zeros(n), np.zeros(n)
+        self._chk(self._L.ipcgpu_chamber_gas_state(self.h, _dp(v), _dp(g), _dp(b)))
+        return v, g, b
+
+    def chamber_volume_gradient(self, chamber, projectDBC=True):
+        """gradV of one chamber at the current positions (3 nV, xyz interleaved)"""
+        u = np.zeros(3 * self.nV)
+        self._chk(self._L.ipcgpu_chamber_volume_gradient(self.h, C.c_int(int(chamber)), C.c_int(int(projectDBC)), _dp(u)))
+        return u
+
+    def chamber_gas_solve(self, coef, rhs):
+        """(A + coef sum_c beta_c u_c u_c^T)^-1 rhs on the matrix as last assembled and factorised: the stepper's own routine"""
+        rhs = _f64(rhs)
+        x = np.zeros_like(rhs)
+        self._chk(self._L.ipcgpu_chamber_gas_solve(self.h, C.c_double(coef), _dp(rhs), _dp(x)))
+        return x
 
     def set_obstacle(self, ids, obstacle_only=False):
         ids = _i32(ids)

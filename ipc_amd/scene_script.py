@@ -11,8 +11,9 @@ anything else raises `UnsupportedKeyword` instead of being ignored silently.
 
 Keywords of this project beside the reference's: `shell`, `limit`, `rod`, `contactGroup` on a shape line (see Shape), and the top-level lines
 `contactIgnore`, `contactFric`, `attach <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]` and `stitch <shapeA> <shapeB> <radius> <k> [rest]` (see SceneConfig):
-the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.  `pressure <p> [ramp <seconds>]` on a
-shape line (a `shell` shape or a tetrahedral shape) makes the shape's closed surface one pressure chamber (Context.set_chambers; see Shape).
+the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.  `pressure <p> [ramp <seconds>]
+[gas <ambient> [gamma <g>]]` on a shape line (a `shell` shape or a tetrahedral shape) makes the shape's closed surface one pressure chamber, constant or
+following the ideal-gas law (Context.set_chambers, Context.chamber_set_gas; see Shape).
 """
 from dataclasses import dataclass, field
 import math
@@ -72,9 +73,14 @@ class Shape:
     # the boundary faces of the tetrahedra -- are ONE pressure chamber with the constant gauge pressure p (positive pushes outward; Context.set_chambers).  The
     # surface must be closed (an open one is a ValueError that names the shape); where its triangle list encloses a negative volume the CHAMBER's copy of the
     # list is flipped, never the shell's own.  With `ramp` the pressure of the step that ends at time t is p min(1, t / ramp) (tools/run_scene.py sets it
-    # before each step through AssembledScene.chamber_pressures and Context.chamber_set_pressure)
+    # before each step through AssembledScene.chamber_pressures and Context.chamber_set_pressure).  `gas <ambient> [gamma <g>]` behind them makes it a gas
+    # chamber (Context.chamber_set_gas): an ideal gas of the ambient absolute pressure <ambient> >= 0 and the exponent g >= 1 (default 1, isothermal; 1.4 is
+    # adiabatic air), filled at the rest volume; p is then the gauge pressure at the rest volume, ambient + p > 0, and a `ramp` pumps the gas in
     pressure: float = None
     pressure_ramp: float = 0.0
+    pressure_gas: bool = False
+    pressure_ambient: float = 0.0
+    pressure_gamma: float = 1.0
 
 
 @dataclass
@@ -469,6 +475,24 @@ def _parse_shape(st, resolve):
                     raise ValueError("ramp needs a positive, finite time")
             if not np.isfinite(sh.pressure):
                 raise ValueError("pressure needs a finite value")
+            if j < len(st) and st[j] == "gas":
+                if j + 1 >= len(st):
+                    raise ValueError("gas needs an ambient pressure")
+                sh.pressure_gas = True
+                sh.pressure_ambient = float(st[j + 1])
+                j += 2
+                if j < len(st) and st[j] == "gamma":
+                    if j + 1 >= len(st):
+                        raise ValueError("gamma needs a value")
+                    sh.pressure_gamma = float(st[j + 1])
+                    j += 2
+                if not (0.0 <= sh.pressure_ambient < float("inf")):
+                    raise ValueError("gas needs a finite ambient pressure >= 0")
+                if not (1.0 <= sh.pressure_gamma < float("inf")):
+                    raise ValueError("gamma needs a finite value >= 1")
+                # (with a ramp the pressure starts near 0: the ambient pressure alone must then carry the gas)
+                if not sh.pressure_ambient + min(sh.pressure, 0.0 if sh.pressure_ramp > 0.0 else sh.pressure) > 0.0:
+                    raise ValueError("gas needs ambient + pressure > 0 (the absolute pressure at the rest volume)")
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
             sh.init_vel = (tuple(v[:3]), tuple(v[3:]))
@@ -632,7 +656,8 @@ class AssembledScene:
     # every `attach` and `stitch` line, as Context.set_attachments takes them: {nodesA, nodesB (global node ids), k, L (per attachment)}, or None
     attachments: dict = None
     # the shapes that carry `pressure`, one chamber each in script order, as Context.set_chambers takes them: {tri_lists (global node ids, outward),
-    # pressure, ramp (seconds per chamber, 0: none)}, or None
+    # pressure, ramp (seconds per chamber, 0: none)}, or None.  Where a shape carries `gas` the dictionary also holds gas (bool), ambient and gamma per chamber,
+    # as Context.chamber_set_gas takes them
     chambers: dict = None
 
     def chamber_pressures(self, t):
@@ -807,6 +832,7 @@ def assemble(cfg, read_mesh):
     shell_limits = []  # ... and their (limit or 0, onset, stiffness)
     rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
     chambers = []  # (triangle list, pressure, ramp) of the shapes that carry `pressure`
+    chamber_gas = []  # ... and their (gas, ambient, gamma)
     for s_index, sh in enumerate(cfg.shapes):
         ext = os.path.splitext(sh.path.lower())[1]
         is_codim = ext in (".obj", ".seg", ".pt")  # main.cpp:948-1005: kinematic surface / segments / points (componentCoDim 2 / 1 / 0)
@@ -859,6 +885,7 @@ def assemble(cfg, read_mesh):
             rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
         if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
             chambers.append((_chamber_list(SF, V, f"shape {s_index} ({os.path.basename(sh.path)})") + off, sh.pressure, sh.pressure_ramp))
+            chamber_gas.append((sh.pressure_gas, sh.pressure_ambient, sh.pressure_gamma))
         if is_codim:  # (an elastic shell or rod needs nobody to hold it: it counts as moved)
             elastic = sh.shell_thickness is not None or sh.rod_radius is not None
             codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
@@ -1295,6 +1322,9 @@ def assemble(cfg, read_mesh):
     if chambers:
         sc.chambers = {"tri_lists": [t.astype(np.int32) for t, _p, _r in chambers], "pressure": np.array([p for _t, p, _r in chambers], dtype=np.float64),
                        "ramp": np.array([r for _t, _p, r in chambers], dtype=np.float64)}
+        if any(g for g, _a, _k in chamber_gas):
+            sc.chambers.update(gas=np.array([g for g, _a, _k in chamber_gas], dtype=bool), ambient=np.array([a for _g, a, _k in chamber_gas], dtype=np.float64),
+                               gamma=np.array([k for _g, _a, k in chamber_gas], dtype=np.float64))
     for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = seqs
@@ -1329,6 +1359,8 @@ def apply(sc, be):
         be.set_attachments(q["nodesA"], q["nodesB"], q["k"], q["L"])
     if sc.chambers is not None:  # every `pressure` shape in one call, behind set_shell, before opt_init and the pattern
         be.set_chambers(sc.chambers["tri_lists"], sc.chambers["pressure"])
+        if "gas" in sc.chambers:
+            be.chamber_set_gas(sc.chambers["gas"], sc.chambers["ambient"], sc.chambers["gamma"])
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
         # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density

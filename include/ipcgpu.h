@@ -397,6 +397,35 @@ int ipcgpu_shell_limit_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_shell_limit_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_shell_limit_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 int ipcgpu_shell_stretch(ipcgpu_ctx*, double* sigma_2nTri, double* maxRatio);
+/* Rubber membrane of the shell (no counterpart in the reference): the incompressible Mooney-Rivlin membrane on chosen triangles, in place of their StVK
+ * membrane.  With F the 3 x 2 deformation gradient of the membrane, C = F^T F and the thickness stretch eliminated by incompressibility (1 / sqrt(det C)):
+ *   I1 = tr C + 1 / det C,  I2 = tr C / det C + det C,  W = h A (c1 (I1 - 3) + c2 (I2 - 3)),  c1 = mu (1 - alpha) / 2,  c2 = mu alpha / 2,  mu = E / 3.
+ *   alpha = 0 is the incompressible neo-Hookean membrane.  mu = E / 3 is the incompressible shear modulus: the Poisson ratio given to ipcgpu_set_shell is not
+ *   read by this term (it still enters the bending constant of the hinges).  Exact gradient; the exact Hessian with its eigenvalues clamped at 0 per triangle.
+ *   A degenerate rubber triangle (det C not positive, or not finite in floating point: collapsed to a line) adds +infinity to the energy and nothing to gradient
+ *   and matrix, which stay finite; the 1 / det C term is a barrier, so a rubber triangle cannot collapse at finite energy.
+ * ipcgpu_shell_set_membrane: model per triangle, 0 = StVK as without this call, 1 = rubber; alpha (null: 0) per triangle, read where model is 1.  All models
+ *   zero, or a null model, removes the term.  After ipcgpu_set_shell (without a shell: IPCGPU_ERR_STATE), at any time between steps: it changes no mass and adds
+ *   no node pair -- the blocks are the membrane's, so the pattern stays.  ipcgpu_set_shell and ipcgpu_set_mesh drop it.  IPCGPU_ERR_ARG: a model other than 0
+ *   or 1, alpha outside [0, 1) or not finite.  A rubber triangle carries no StVK membrane energy; its hinges keep their bending term; a strain limit on the
+ *   same triangle composes with it unchanged.
+ * With rubber triangles the term is part of the shell energy everywhere: ipcgpu_shell_energy, ipcgpu_shell_gradient_add and ipcgpu_shell_hessian_add include
+ *   it, and so do the time stepper and the stiffness damping.  The stepper never accepts a state with a degenerate rubber triangle: a trial energy of +infinity
+ *   is backtracked by the line search; a scripted Dirichlet move that would flatten a rubber triangle is shortened; ipcgpu_opt_begin_timestep from a state
+ *   with a degenerate rubber triangle returns IPCGPU_ERR_STATE, the message naming the number of such triangles, and changes nothing.  Without a rubber
+ *   triangle none of the rubber kernels is launched and every result is bit-identical to a context that never made this call.
+ * ipcgpu_shell_membrane_get: model and alpha per triangle as set (zeros without the term); either pointer may be null.
+ * ipcgpu_shell_rubber_energy / _energy_per_elem / _gradient_add / _hessian_add: the rubber term alone, with the semantics of their ipcgpu_shell_* namesakes
+ *   (perTri has nTri entries, 0 for a StVK triangle; coef > 0).  Without a rubber triangle they return IPCGPU_OK and add nothing.
+ * ipcgpu_shell_thickness: the current thickness per triangle: h / (sigma1 sigma2) on a rubber triangle (sigma as ipcgpu_shell_stretch returns them), the rest
+ *   thickness h on a StVK triangle, whose law does not thin. */
+int ipcgpu_shell_set_membrane(ipcgpu_ctx*, const int* model_nTri, const double* alpha_nTri);
+int ipcgpu_shell_membrane_get(ipcgpu_ctx*, int* model_nTri, double* alpha_nTri);
+int ipcgpu_shell_rubber_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_shell_rubber_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
+int ipcgpu_shell_rubber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_shell_rubber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_shell_thickness(ipcgpu_ctx*, double* h_nTri);
 /* Elastic rods (no counterpart in the reference): stretching and bending energy on segment components.
  *   stretching  per segment (a, b): rest length L, length l, radius r, Young's modulus E, A = pi r^2, k_s = E A / L, W_s = k_s (l - L)^2 / 2.  Exact gradient.
  *               With t = (x_b - x_a) / l the 3 x 3 block is B = k_s [t t^T + max(0, 1 - L / l) (I - t t^T)], the 6 x 6 Hessian [[B, -B], [-B, B]]: the clamp

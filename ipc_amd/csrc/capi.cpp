@@ -112,19 +112,21 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 }
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
-// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its limit, ipcgpu_shell_limit_* the limit alone, ipcgpu_rod_* the rod,
-// ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers.
-constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT, ROD = HipOptimizer::CODIM_ROD,
+// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its rubber membrane and its limit, ipcgpu_shell_limit_* the limit alone,
+// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers.
+constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_RUBBER | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT,
+                   RUBBER_ALONE = HipOptimizer::CODIM_SHELL_RUBBER, ROD = HipOptimizer::CODIM_ROD,
                    ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
 const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hessian: build it after ipcgpu_set_attachments";
 const char* const CHAMBER_MISS = "the pattern lacks a block of the chamber Hessian: build it after ipcgpu_set_chambers";
-// What an entry point returns early on: no triangle, no limited triangle, no segment, no attachment, no chamber triangle.
+// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle.
 int codimCount(const HipMesh& m, unsigned which)
 {
     return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
         : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited()
+        : (which & HipOptimizer::CODIM_SHELL_RUBBER) ? m.shell.nRubber()
         : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
         : (which & HipOptimizer::CODIM_ATTACH)      ? m.attach.n()
                                                     : m.chamber.nTri();
@@ -136,6 +138,7 @@ int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
     needArg(E != nullptr, "null argument");
     // (ipcgpu_shell_limit_energy alone asks for this: its +infinity must keep its sign)
     needArg(which != HipOptimizer::CODIM_SHELL_LIMIT || coef > 0.0, "the coefficient of the strain-limit energy must be positive");
+    needArg(which != HipOptimizer::CODIM_SHELL_RUBBER || coef > 0.0, "the coefficient of the rubber-membrane energy must be positive");
     need(o.initialised, "call ipcgpu_opt_init first");
     *E = 0.0;
     if (!codimCount(*c->mesh, which)) return IPCGPU_OK;
@@ -408,6 +411,7 @@ int ipcgpu_set_positions(ipcgpu_ctx* c, const double* V)
         needArg(V != nullptr, "null V");
         uploadColMajor(c, V, c->mesh->d_x);
         c->mesh->shell.limitUnchecked = c->mesh->shell.nLimited() > 0; // the stepper's last energy no longer describes these positions
+        c->mesh->shell.rubberUnchecked = c->mesh->shell.nRubber() > 0;
         return IPCGPU_OK;
     });
 }
@@ -1122,6 +1126,72 @@ int ipcgpu_shell_stretch(ipcgpu_ctx* c, double* sigma, double* maxRatio)
         HipOptimizer& o = O(c);
         bind(c);
         o.shellStretch(sigma, maxRatio, nullptr);
+        return IPCGPU_OK;
+    });
+}
+// ---- Rubber membrane of the shells --------------------------------------------------------------------
+int ipcgpu_shell_set_membrane(ipcgpu_ctx* c, const int* model, const double* alpha)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        m.setShellMembrane(model, alpha, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_membrane_get(ipcgpu_ctx* c, int* model, double* alpha)
+{
+    return guarded([&] {
+        const HipShell& sh = M(c).shell;
+        if (model) std::fill(model, model + sh.nTri(), 0);
+        if (alpha) std::fill(alpha, alpha + sh.nTri(), 0.0);
+        if (!sh.nRubber()) return IPCGPU_OK;
+        if (model) std::copy(sh.rubber.model.begin(), sh.rubber.model.end(), model);
+        if (alpha) std::copy(sh.rubber.alpha.begin(), sh.rubber.alpha.end(), alpha);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_rubber_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] { return codimEnergy(c, RUBBER_ALONE, coef, E); });
+}
+int ipcgpu_shell_rubber_energy_per_elem(ipcgpu_ctx* c, double* perTri)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri() || !perTri) return IPCGPU_OK;
+        DevBuf<double> t;
+        t.alloc(sh.nTri());
+        launch_shell_rubber_energy_per_elem(o.shellRubberView(c->mesh->d_x.p), t.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        t.download(perTri, sh.nTri(), c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_rubber_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] { return codimGradientAdd(c, RUBBER_ALONE, coef, projectDBC, g); });
+}
+int ipcgpu_shell_rubber_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] { return codimHessianAdd(c, RUBBER_ALONE, coef, projectDBC, SHELL_MISS); });
+}
+int ipcgpu_shell_thickness(ipcgpu_ctx* c, double* h)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri() || !h) return IPCGPU_OK;
+        std::copy(sh.plan.thickness.begin(), sh.plan.thickness.end(), h);
+        if (!sh.nRubber()) return IPCGPU_OK;
+        std::vector<double> sigma(2 * (size_t)sh.nTri());
+        o.shellStretch(sigma.data(), nullptr, nullptr);
+        for (int t : sh.rubber.tri) h[t] = sh.plan.thickness[(size_t)t] / (sigma[2 * (size_t)t] * sigma[2 * (size_t)t + 1]); // incompressible: lambda_3 = 1 / (sigma1 sigma2)
         return IPCGPU_OK;
     });
 }

@@ -27,6 +27,8 @@
 #include "shell_limit_kernels.h"
 #include "shell_limit_plan.h"
 #include "shell_plan.h"
+#include "shell_rubber_kernels.h"
+#include "shell_rubber_plan.h"
 #include "stress_plan.h"
 #include <map>
 #include <memory>
@@ -58,6 +60,14 @@ struct HipShell {
     DevBuf<double> d_limConst, d_triLimit, d_stretchPartial, d_stretchOut;
     bool limitUnchecked = false;
     int nLimited() const { return limit.nLimited; }
+    // rubber membrane (ipcgpu_shell_set_membrane; shell_rubber_plan.h): arrays of its own beside the shell's.  nRubber() == 0: every triangle is StVK, none of
+    // the rubber kernels is launched and d_triConst is the plan's triConst; otherwise d_triConst holds zeros for the two StVK constants of the rubber
+    // triangles.  unchecked: as limitUnchecked, for "a rubber triangle is degenerate" (its energy is +infinity)
+    ShellRubberPlan rubber;
+    DevBuf<int> d_rubTri;
+    DevBuf<double> d_rubConst, d_rubCount;
+    bool rubberUnchecked = false;
+    int nRubber() const { return rubber.nRubber; }
 };
 
 // Elastic rod of the mesh (ipcgpu_set_rod): the host plan and its device copy.  nSeg() == 0: no rod, and then nothing below is ever read.
@@ -145,6 +155,10 @@ public:
     // Strain limit of the shell (shell_limit_plan.h): validates and uploads the compact list and the constants.  All limits zero (or null) removes it;
     // setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair (the blocks are the membrane's).
     void setShellStrainLimit(const double* limit, const double* onset, const double* stiff, hipStream_t s);
+    // Membrane model of the shell's triangles (shell_rubber_plan.h): validates, uploads the compact list of the rubber triangles with their constants, and the
+    // shell's triConst with the StVK constants of those triangles zeroed (the plan's own where none is rubber).  All models zero (or null) removes the term;
+    // setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair (the blocks are the membrane's).
+    void setShellMembrane(const int* model, const double* alpha, hipStream_t s);
     // Elastic rod on segment components (rod_plan.h): as setShell -- validates, sets the lumped masses of the rod nodes, marks them as element nodes, adds
     // the plan's node pairs to vNeighbor and uploads the constants.  nSeg = 0 removes the rod, a second call replaces it: the nodes of the old rod get back
     // the masses they had before it and lose the mark; the neighbour pairs stay.  With neither a tetrahedron nor a shell in the mesh avgEdgeLen is the mean
@@ -329,14 +343,15 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // The codimensional terms (shell_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h) enter wherever the tetrahedral elastic term does, with the same
-    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, limit, rod, attachments, chambers (the energy sum
-    // is ((((E + shell) + limit) + rod) + attach) + chamber) and launch a term only where the mesh has it (nTri(), nLimited(), nSeg(), attach.n(), chamber.nTri()); none of them is ever sharded.
+    // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, limit, rod, attachments, chambers (the energy sum
+    // is (((((E + shell) + rubber) + limit) + rod) + attach) + chamber) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri()); none of them is ever sharded.
     // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness.
-    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_ALL = 31, CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER };
+    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_ALL = 63, CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER };
     CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
     ShellLimitView shellLimitView(const double* x_dev) const;
+    ShellRubberView shellRubberView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
     AttachView attachView(const double* x_dev) const;
     // pressure: which array the kernels read as the pressure -- d_pressure without a gas chamber, whatever is asked; with one, the effective pressure
@@ -361,6 +376,9 @@ public:
     void shellStretch(double* sigma_host, double* maxRatio, int* nOver, const double* x_dev = nullptr);
     bool shellLimitFeasible(); // true without a limit; else one stretch query at the current positions
     void requireShellLimitFeasible(); // StateError naming the number of triangles over their limit
+    int shellRubberDegenerate(); // the number of rubber triangles whose energy is +infinity at the current positions (0 without rubber; synchronises)
+    bool shellRubberFeasible() { return !mesh.shell.nRubber() || shellRubberDegenerate() == 0; }
+    void requireShellRubberFeasible(); // StateError naming the number of degenerate rubber triangles
     // a mesh without tetrahedra has no patch plan: the node pass initialises the gradient / the matrix diagonal in its place (only with a shell or a rod
     // set: shells only, rods only, or both)
     bool shellOnly() const { return mesh.nT == 0 && (mesh.shell.nTri() > 0 || mesh.rod.nSeg() > 0); }

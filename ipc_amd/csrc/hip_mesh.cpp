@@ -34,6 +34,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     ++nbVersion;
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
     shell.limit = ShellLimitPlan(); // ... and its strain limit with it
+    shell.rubber = ShellRubberPlan(); // ... and its rubber membrane
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
     if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
@@ -208,6 +209,7 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     addNeighbourPairs(plan.pairs);
     shell.plan = std::move(plan);
     shell.limit = ShellLimitPlan(); // a strain limit belongs to the shell it was set on
+    shell.rubber = ShellRubberPlan(); // ... and so does a rubber membrane (d_triConst below is the new plan's own)
     shell.bendScale = bendScale;
     const ShellPlan& p = shell.plan;
     d_mass.upload(mass, s);
@@ -241,6 +243,24 @@ void HipMesh::setShellStrainLimit(const double* limit, const double* onset, cons
     shell.d_limTri.upload(shell.limit.tri, s);
     shell.d_limConst.upload(shell.limit.limConst, s);
     shell.d_triLimit.upload(shell.limit.triLimit, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setShellMembrane(const int* model, const double* alpha, hipStream_t s)
+{
+    if (!shell.nTri()) throw StateError("shell_set_membrane: no shell is set (call ipcgpu_set_shell first)");
+    ShellRubberPlan plan;
+    std::string err;
+    if (!buildShellRubberPlan(shell.nTri(), model, alpha, shell.plan.membraneK.data(), plan, err)) throw ArgError(err);
+    if (!plan.nRubber && !shell.rubber.nRubber) return; // StVK before and after: nothing is touched
+    shell.rubber = std::move(plan);
+    shell.rubberUnchecked = shell.rubber.nRubber > 0;
+    const std::vector<double> triConst = shellTriConstWithoutRubber(shell.plan.triConst, shell.rubber); // (the plan's own once the last rubber triangle is gone)
+    shell.d_triConst.upload(triConst, s);
+    if (shell.rubber.nRubber) {
+        shell.d_rubTri.upload(shell.rubber.tri, s);
+        shell.d_rubConst.upload(shell.rubber.rubConst, s);
+    }
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -81,6 +81,7 @@ ElemView HipOptimizer::view() const
 #pragma clang diagnostic ignored "-Winvalid-offsetof" // (the views are not standard-layout: two bases with fields; the offsets are the ABI's all the same)
 CODIM_VIEW_LAYOUT(ShellView, ShellFields, nTri);
 CODIM_VIEW_LAYOUT(ShellLimitView, ShellLimitFields, nTri);
+CODIM_VIEW_LAYOUT(ShellRubberView, ShellRubberFields, nTri);
 CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
 CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
 CODIM_VIEW_LAYOUT(ChamberView, ChamberFields, nTri);
@@ -118,6 +119,20 @@ ShellLimitView HipOptimizer::shellLimitView(const double* x_dev) const
     v.limTri = sh.d_limTri.p;
     v.limConst = sh.d_limConst.p;
     v.triLimit = sh.nLimited() ? sh.d_triLimit.p : nullptr;
+    return v;
+}
+
+ShellRubberView HipOptimizer::shellRubberView(const double* x_dev) const
+{
+    const HipShell& sh = mesh.shell;
+    ShellRubberView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nTri = sh.nTri();
+    v.nRubber = sh.nRubber();
+    v.tri = sh.d_tri.p;
+    v.triConst = sh.d_triConst.p;
+    v.rubTri = sh.d_rubTri.p;
+    v.rubConst = sh.d_rubConst.p;
     return v;
 }
 
@@ -206,6 +221,9 @@ const CodimTerm CODIM_TERMS[] = {
     { HipOptimizer::CODIM_SHELL, [](const HipMesh& m) { return m.shell.nTri() ? m.shell.nTri() + m.shell.nHinge() : 0; },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_energy(o.shellView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_assemble(o.shellView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_SHELL_RUBBER, [](const HipMesh& m) { return m.shell.nRubber(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_rubber_energy(o.shellRubberView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_rubber_assemble(o.shellRubberView(x), coef, proj, g, a, err, o.stream); } },
     { HipOptimizer::CODIM_SHELL_LIMIT, [](const HipMesh& m) { return m.shell.nLimited(); },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_limit_energy(o.shellLimitView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_limit_assemble(o.shellLimitView(x), coef, proj, g, a, err, o.stream); } },
@@ -298,6 +316,27 @@ void HipOptimizer::requireShellLimitFeasible()
     mesh.shell.limitUnchecked = false;
     if (nOver)
         throw StateError(std::to_string(nOver) + " shell triangle" + (nOver == 1 ? " has" : "s have") + " a principal stretch at or over the strain limit at the start of the time step");
+}
+
+int HipOptimizer::shellRubberDegenerate()
+{
+    HipShell& sh = mesh.shell;
+    if (!sh.nRubber()) return 0;
+    const ShellRubberView v = shellRubberView(mesh.d_x.p);
+    sh.d_rubCount.ensure((size_t)shell_rubber_energy_blocks(v) + 1); // the count, then the partial sums
+    launch_shell_rubber_degenerate(v, sh.d_rubCount.p + 1, sh.d_rubCount.p, stream);
+    HIP_CHECK(hipGetLastError());
+    double n = 0.0;
+    sh.d_rubCount.download(&n, 1, stream); // synchronises
+    return (int)n;
+}
+
+void HipOptimizer::requireShellRubberFeasible()
+{
+    if (!mesh.shell.nRubber()) return;
+    const int n = shellRubberDegenerate();
+    mesh.shell.rubberUnchecked = false;
+    if (n) throw StateError(std::to_string(n) + " rubber triangle" + (n == 1 ? " is" : "s are") + " degenerate (collapsed to a line: the energy is infinite) at the start of the time step");
 }
 
 void HipOptimizer::init(double dt_, bool withGravity)
@@ -584,7 +623,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness)
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness)
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -845,6 +884,7 @@ void HipOptimizer::loadStatus(const std::string& path)
     if (in.bad()) throw StateError("read error on status file " + path);
     mesh.d_x.upload(x, stream);
     mesh.shell.limitUnchecked = mesh.shell.nLimited() > 0;
+    mesh.shell.rubberUnchecked = mesh.shell.nRubber() > 0;
     d_xPrev.upload(x, stream);
     d_xStepStart.upload(x, stream); // V_prev = V (Optimizer.cpp:247): a report right after a restart has no kinetic part
     d_vel.upload(vel, stream);
@@ -1521,7 +1561,8 @@ void HipOptimizer::stepFeasible(double& stepSize)
         }
     // the shells' strain limit: the feasible set is convex and d_x0 lies inside it (beginTimestep), so halving ends, and a step shortened further for
     // another reason stays feasible.  What a scripted Dirichlet move loses here the augmented-Lagrangian solve takes up (completedStep < 1).
-    while (stepSize > 0.0 && !shellLimitFeasible()) {
+    // The rubber membrane likewise: d_x0 has no degenerate rubber triangle (beginTimestep), and a move that flattens one is halved away from it.
+    while (stepSize > 0.0 && !(shellLimitFeasible() && shellRubberFeasible())) {
         stepSize /= 2.0;
         stepForward(d_x0.p, stepSize);
         if (ipOn())
@@ -1663,13 +1704,14 @@ void HipOptimizer::beginTimestep()
     // The contact-free twist (BASELINE configs[1]; round 6): everything the set-up of a time step asks the device -- inverted before the motion? the filter's bound
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.
-    // (a strain limit takes the general sequence: its scripted step is shortened by stepFeasible)
+    // (a strain limit or a rubber membrane takes the general sequence: its scripted step is shortened by stepFeasible)
     const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && !(warmStart >= 1 && warmStart <= 5)
-        && !mesh.shell.nLimited();
+        && !mesh.shell.nLimited() && !mesh.shell.nRubber();
     // With a strain limit the stepper never accepts a state with a stretch at or over it, so a time step may only start from a feasible one.  The energy the
     // stepper holds on the host tells: it is +infinity exactly then (or at the fold of a rod node, which the count below tells apart) -- no device query on
     // the usual path.  Positions or a limit set from outside since then are asked for once.  Nothing has been changed yet when this throws.
     if (mesh.shell.nLimited() && (mesh.shell.limitUnchecked || !(lastEnergyVal < INFINITY))) requireShellLimitFeasible();
+    if (mesh.shell.nRubber() && (mesh.shell.rubberUnchecked || !(lastEnergyVal < INFINITY))) requireShellRubberFeasible(); // the same for a degenerate rubber triangle
     if (batched) {
         const bool guard = mesh.needElemInvSafeGuard(); // Optimizer.cpp:252, 517: only under getNeedElemInvSafeGuard()
         d_flag.zero(stream);

@@ -61,6 +61,7 @@ bool buildShellPlan(int nV, int nTri, const int* tri, const double* Vrest, const
     plan.triConst.assign(6 * nt, 0.0);
     plan.area.assign(nt, 0.0);
     plan.membraneK.assign(nt, 0.0);
+    plan.thickness.assign(nt, 0.0);
     std::vector<double> kb(nt);
     std::vector<HalfEdge> half;
     half.reserve(3 * nt);
@@ -97,6 +98,7 @@ bool buildShellPlan(int nV, int nTri, const int* tri, const double* Vrest, const
         plan.triConst[5 * nt + t] = h * A * (E * nu / (1.0 - nu * nu));
         plan.area[t] = A;
         plan.membraneK[t] = h * A * E;
+        plan.thickness[t] = h;
         kb[t] = E * h * h * h / (24.0 * (1.0 - nu * nu));
         for (int k = 0; k < 3; ++k) {
             plan.mass[(std::size_t)v[k]] += r * h * A / 3.0;

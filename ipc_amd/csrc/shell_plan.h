@@ -15,7 +15,8 @@ struct ShellPlan {
     // along X1 - X0), then h A mu and h A lambda_ps with mu = E / (2 (1 + nu)), lambda_ps = E nu / (1 - nu^2)
     std::vector<double> triConst;
     std::vector<double> area; // nTri rest areas
-    std::vector<double> membraneK; // nTri: h A E, the scale of the strain-limit barrier (shell_limit_plan.h)
+    std::vector<double> membraneK; // nTri: h A E, the scale of the strain-limit barrier (shell_limit_plan.h) and of the rubber membrane (shell_rubber_plan.h)
+    std::vector<double> thickness; // nTri: h at rest, as given (ipcgpu_shell_thickness)
     // hinges: one per edge shared by two triangles, ascending by (smaller edge node, larger edge node).  hinge[4 i ..] = x0 < x1 on the edge, x2 the node
     // opposite in the triangle that traverses x0 -> x1, x3 the node opposite in the one that traverses x1 -> x0
     std::vector<int> hinge;

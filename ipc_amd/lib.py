@@ -614,6 +614,44 @@ class Context:
         self._chk(self._L.ipcgpu_shell_stretch(self.h, _dp(s), C.byref(r)))
         return s, r.value
 
+    # ---- rubber membrane of the shell (ipcgpu_shell_set_membrane: incompressible Mooney-Rivlin on the chosen triangles, in place of their StVK membrane)
+    def set_shell_membrane(self, model, alpha=None):
+        """model: 0 (StVK) or 1 (rubber), alpha (None: 0; 0 <= alpha < 1, the Mooney-Rivlin fraction): scalars or one value per shell triangle; None or all
+        zeros removes the term.  After set_shell; set_shell and set_mesh drop it."""
+        n = self._shell_ntri()
+        m = None if model is None else np.ascontiguousarray(np.broadcast_to(np.asarray(model, dtype=np.int32), (n,)))
+        a = None if alpha is None else _f64(np.broadcast_to(np.asarray(alpha, dtype=np.float64), (n,)))
+        self._chk(self._L.ipcgpu_shell_set_membrane(self.h, _ip(m), _dp(a)))
+
+    def shell_membrane_get(self):
+        """(model (nTri, int32), alpha (nTri)) as set; zeros without a rubber triangle"""
+        n = self._shell_ntri()
+        m, a = np.zeros(n, dtype=np.int32), np.zeros(n)
+        self._chk(self._L.ipcgpu_shell_membrane_get(self.h, _ip(m), _dp(a)))
+        return m, a
+
+    def shell_rubber_energy(self, coef=1.0):
+        return self._codim_energy("shell_rubber", coef)
+
+    def shell_rubber_energy_per_elem(self):
+        """the unscaled rubber energy per shell triangle (0 for a StVK one, inf for a degenerate rubber one)"""
+        t = np.zeros(self._shell_ntri())
+        self._chk(self._L.ipcgpu_shell_rubber_energy_per_elem(self.h, _dp(t)))
+        return t
+
+    def shell_rubber_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * gradient of the rubber term; returns it"""
+        return self._codim_gradient_add("shell_rubber", coef, projectDBC, grad)
+
+    def shell_rubber_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("shell_rubber", coef, projectDBC)
+
+    def shell_thickness(self):
+        """the current thickness per shell triangle: h / (sigma1 sigma2) on a rubber triangle, the rest thickness on a StVK one"""
+        h = np.zeros(self._shell_ntri())
+        self._chk(self._L.ipcgpu_shell_thickness(self.h, _dp(h)))
+        return h
+
     # ---- elastic rods (ipcgpu_set_rod: stretching + bending energy on segment components)
     def set_rod(self, seg, radius, YM, rho, bend_scale=1.0):
         """seg: nSeg x 2 node ids; radius, YM, rho: scalars or one value per segment.  After set_mesh, before opt_init and set_pattern; sets the masses of

@@ -65,6 +65,10 @@ class Shape:
     shell_limit: float = None
     shell_onset: float = 1.0
     shell_stiff: float = 1.0
+    # `shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]`: this shape's triangles carry the incompressible Mooney-Rivlin membrane in place of
+    # the StVK one (Context.set_shell_membrane); alpha in [0, 1) is the I2 fraction, default 0 = neo-Hookean; per shape, shapes may differ
+    shell_rubber: bool = False
+    shell_alpha: float = 0.0
     # `rod <radius> [bend <scale>]` (this project's keyword, `.seg` shapes only): the component is an elastic rod -- stretching and bending energy with the
     # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
     rod_radius: float = None
@@ -434,6 +438,20 @@ def _parse_shape(st, resolve):
                 j += 2
             if not sh.shell_thickness > 0.0 or not sh.shell_bend >= 0.0:
                 raise ValueError("shell needs a positive thickness and a bend scale >= 0")
+            if j < len(st) and st[j] == "rubber":
+                sh.shell_rubber = True
+                j += 1
+                if j < len(st) and st[j] == "mr":
+                    if j + 1 >= len(st):
+                        raise ValueError("mr needs a fraction")
+                    sh.shell_alpha = float(st[j + 1])
+                    j += 2
+                if not (np.isfinite(sh.shell_alpha) and 0.0 <= sh.shell_alpha < 1.0):
+                    raise ValueError("mr needs a fraction 0 <= alpha < 1")
+                if j < len(st) and st[j] in ("bend", "rubber", "mr"):
+                    raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]")
+            elif j < len(st) and st[j] == "mr":
+                raise ValueError("mr belongs behind rubber")
             if j < len(st) and st[j] == "limit":
                 if j + 1 >= len(st):
                     raise ValueError("limit needs a stretch")
@@ -449,6 +467,8 @@ def _parse_shape(st, resolve):
                     raise ValueError("limit needs 1 <= onset < limit and a stiffness > 0")
             elif j < len(st) and st[j] in ("onset", "stiff"):
                 raise ValueError(st[j] + " belongs behind limit")
+            if j < len(st) and st[j] in ("rubber", "mr", "bend"):
+                raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]")
         elif e == "rod":
             if j >= len(st):
                 raise ValueError("rod needs a radius")
@@ -830,6 +850,7 @@ def assemble(cfg, read_mesh):
     seqs = []  # mesh sequences: {ids, folder, ext}
     shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
     shell_limits = []  # ... and their (limit or 0, onset, stiffness)
+    shell_models = []  # ... and their (model, alpha): (1, alpha) for `rubber`, (0, 0) otherwise
     rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
     chambers = []  # (triangle list, pressure, ramp) of the shapes that carry `pressure`
     chamber_gas = []  # ... and their (gas, ambient, gamma)
@@ -880,6 +901,7 @@ def assemble(cfg, read_mesh):
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat))
             shell_limits.append((0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff))
+            shell_models.append((1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0))
         if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
             mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
             rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
@@ -1309,6 +1331,9 @@ def assemble(cfg, read_mesh):
         if any(q[0] > 0.0 for q in shell_limits):  # per triangle, as Context.set_shell_strain_limit takes them; a shape without `limit` stays unlimited (0)
             for k, name in enumerate(("limit", "onset", "stiff")):
                 sc.shell[name] = np.concatenate([np.full(len(t[0]), float(q[k])) for t, q in zip(shells, shell_limits)])
+        if any(m for m, _a in shell_models):  # per triangle, as Context.set_shell_membrane takes them; a shape without `rubber` stays StVK (0)
+            sc.shell["model"] = np.concatenate([np.full(len(t[0]), m, dtype=np.int32) for t, (m, _a) in zip(shells, shell_models)])
+            sc.shell["alpha"] = np.concatenate([np.full(len(t[0]), float(a)) for t, (_m, a) in zip(shells, shell_models)])
     if rods:
         if len({b for _s, _r, b, _m in rods}) > 1:
             raise ValueError("one bend scale per scene: the rod shapes give different ones")
@@ -1349,6 +1374,8 @@ def apply(sc, be):
     if sc.shell is not None:  # after set_codim_nodes (it replaces the area masses of its nodes), before opt_init and the pattern
         q = sc.shell
         be.set_shell(q["tri"], q["thickness"], q["YM"], q["PR"], q["rho"], q["bend"])
+        if "model" in q:
+            be.set_shell_membrane(q["model"], q["alpha"])
         if "limit" in q:
             be.set_shell_strain_limit(q["limit"], q["onset"], q["stiff"])
     if sc.rod is not None:  # after set_codim_nodes and set_shell (it replaces the segment masses of its nodes), before opt_init and the pattern

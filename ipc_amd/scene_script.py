@@ -6,7 +6,7 @@ scene files the reference ships, so both start from identical inputs.  Only keyw
 anything else raises `UnsupportedKeyword` instead of being ignored silently.
 
     cfg = SceneConfig.parse(open(path).read(), base_dir)       # grammar only
-    scene = assemble(cfg, read_mesh)                          # shapes -> one mesh (main.cpp:880-1198)
+    scene = assemble(cfg, read_mesh)                          # shapes -> one mesh (main.cpp:880-1198); the script's set-up: anim_script.py
     apply(scene, backend)                                     # C-ABI calls, in the order INTEGRATION.md gives
 
 Keywords of this project beside the reference's: `shell`, `limit`, `rod`, `contactGroup` on a shape line (see Shape), and the top-level lines
@@ -22,12 +22,10 @@ import warnings
 
 import numpy as np
 
+from . import anim_script as _anim
 from . import scene as _scene
-
-
-class UnsupportedKeyword(ValueError):
-    pass
-
+from .anim_script import (DCO_SCRIPTS, HANDLE_SCRIPTS, HOLD_SCRIPTS, INITVEL_SCRIPTS, PULL_SCRIPTS, RULE_SCRIPTS,  # noqa: F401  (the scripts themselves
+                          UnsupportedKeyword)  # are restated in anim_script.py; their names stay importable from here)
 
 VIEWER_KEYWORDS = {"view", "zoom", "cameraTracking", "playBackSpeed", "appendStr", "disableCout", "section"}
 
@@ -617,35 +615,6 @@ def read_seq_file(folder, index, ext):
     return read_pt(base + ".pt")
 
 
-# The hard-coded scripts of AnimScripter that move whole components (set-up AnimScripter.cpp:1060-1300, per step :1961-2135): how many
-# leading components they move and with what.  Linear velocities in units / s, angular velocities in rad / s about x, y, z.
-_S6 = [(1.0, 0, 0), (-1.0, 0, 0), (0, 1.0, 0), (0, -1.0, 0), (0, 0, 1.0), (0, 0, -1.0)]
-_HP = math.pi / 2.0
-DCO_SCRIPTS = {
-    "DCOSquash": {"n": 2, "lin": _S6[:2]},  # two plates closing along x, turning round when 0.1 apart (:1172-1191, 2034-2051)
-    "DCOSquash6": {"n": 6, "lin": _S6},  # six plates closing along x, y, z (the trash compactor; :1193-1221, 2053-2074)
-    "DCORotCylinders": {"n": 4, "ang": [(_HP, 0, 0), (-_HP, 0, 0), (0, 0, -_HP), (0, 0, _HP)]},  # :1060-1086, 1961-1975
-    "DCOVerschoorRoller": {"n": 6, "ang": [(0, 0, -4.0), (0, 0, -2.0), (0, 0, 2.0), (0, 0, 4.0), (2.0, 0, 0), (-2.0, 0, 0)]},  # :1088-1118, 1977-1991
-    "DCOSqueezeOut": {"n": 0},  # every surface-only component is held (the rule of :2102-2124 that would move the first one never fires, see assemble)
-}
-
-
-# scripts that pick their Dirichlet / Neumann nodes from the bounding box of the assembled mesh (set-up in AnimScripter::initAnimScript)
-HANDLE_SCRIPTS = ("fixLowerHalf", "pushRightMost1", "utopiaComparison", "DCOSegBedSquash", "hangLeft")
-# nodes picked by a box rule of the start positions and HELD (ZERO: taken out of the system; NONZERO: a Dirichlet set that does not move), or moved
-# at a constant velocity (AnimScripter.cpp:153-189, 224-247, 284-297, 318-373, 459-473, 502-516, 790-807, 860-893; per step :1536-1551, 1597-1603,
-# 1817-1826); `drop`, `leftHitRight`, `XYRotate` only give start velocities (:853-858, 1336-1374)
-HOLD_SCRIPTS = ("hang", "hang2", "hangTopLeft", "stamp", "stampTopLeft", "stampBoth", "stand", "topbottomfix", "corner", "fixRightMost1")
-PULL_SCRIPTS = ("stretch", "squash", "dragdown", "curtain")
-INITVEL_SCRIPTS = ("drop", "leftHitRight", "XYRotate")
-# handle sets that move, turn round or stop by a rule on one "turning" node (AnimScripter.cpp:375-457, 518-553, 574-631; per step :1554-1595, 1648-1729)
-RULE_SCRIPTS = ("push", "tear", "upndown", "undstamp", "stretchnsquash", "bend", "twistnstretch", "twistnsns", "twistnsns_old",
-                # handle sets that are LET GO (the others stop) when the turning node has travelled far enough (:633-760, 827-851; per step :1731-1812)
-                "rubberBandPull", "fourLegPull", "headTailPull", "toggleTop",
-                # start positions changed and / or nodes held (:129-151, 206-222, 265-282, 299-316), Neumann pull on the top (:912-954)
-                "scaleF", "swing", "stampInv", "standInv", "NMFixBottomDragLeft", "NMFixBottomDragForward")
-
-
 @dataclass
 class AssembledScene:
     cfg: SceneConfig
@@ -701,86 +670,7 @@ class AssembledScene:
         if r is None or r["done"]:
             return False
         x = np.asarray(be.state()["V"]).reshape(-1, 3)
-        if r.get("kind") == "dco":
-            nr = self.node_ranges
-            if r["script"] in ("DCOSquash", "DCOSquash6"):
-                # AnimScripter.cpp:2034-2074: while the first two plates are closer than 0.1 in x, EVERY velocity changes sign -- once per
-                # time step, as written
-                if x[nr[1]:nr[2], 0].min() - x[nr[0]:nr[1], 0].max() < 0.1:
-                    r["lin"] = [tuple(-c for c in v) for v in r["lin"]]
-                    for g, v in enumerate(r["lin"]):
-                        be.set_dirichlet_motion(g, lin_vel=v, force_nonzero=True)
-                    return True
-            return False
-        if r.get("kind") == "segbed":  # AnimScripter.cpp:2080-2100: the upper parts move only while they are more than 0.1 above the lower ones
-            top_min = x[r["up"], 1].min()
-            bottom_max = x[r["down"], 1].max() if len(r["down"]) else -np.inf
-            moving = bool(top_min - bottom_max > 0.1)
-            if moving != r["moving"]:
-                r["moving"] = moving
-                be.set_dirichlet_motion(r["group"], lin_vel=(0.0, -1.0, 0.0) if moving else (0.0, 0.0, 0.0), force_nonzero=True)
-                return True
-            return False
-        if r.get("kind") == "turn":
-            # one node decides (velocityTurningPoints): outside its window the listed velocity components change sign -- every step it is found
-            # outside, as written (AnimScripter.cpp:1568-1595, 1648-1660, 1702-1729) -- or, `push`, the handles stop for good (:1554-1566)
-            c = x[r["turn"], r["axis"]]
-            if not (c <= r["lo"] or c >= r["hi"]):
-                return False
-            if r["stop"]:
-                r["lin"] = [(0.0, 0.0, 0.0) if g in r["groups"] else v for g, v in enumerate(r["lin"])]
-                r["done"] = True
-            else:
-                r["lin"] = [tuple(-c_ if k == r["comp"] else c_ for k, c_ in enumerate(v)) if g in r["groups"] else v for g, v in enumerate(r["lin"])]
-            for g in r["groups"]:
-                be.set_dirichlet_motion(g, lin_vel=r["lin"][g], ang_vel_deg=r["ang"][g], center=r["ctr"][g], force_nonzero=True)
-            return True
-        if r.get("kind") == "aco":
-            # AnimScripter.cpp:1832-1871: the analytic planes close in at 1 along their axis, every velocity of a pair changing sign while the two
-            # are closer than 0.1 (ACOSquash) / 0.2 (ACOSquash6); each plane then moves by the fraction of v dt that HalfSpace::move admits
-            o, v = r["origins"], r["vel"]
-            for a, gap in r["pairs"]:
-                if o[a + 1][a // 2] - o[a][a // 2] < gap:
-                    v[a][a // 2] *= -1.0
-                    v[a + 1][a // 2] *= -1.0
-            for i in range(len(v)):
-                d = v[i] * self.cfg.dt
-                o[i] = o[i] + (1.0 - be.half_space_move(i, d, 0.5)) * d
-            return True
-        if r.get("kind") == "while_above":  # AnimScripter.cpp:1996-2012, 2019-2030: the component moves in the steps that start with its lowest node above the mark
-            moving = bool(x[r["ids"], 1].min() > r["y"])
-            if moving != r["moving"]:
-                r["moving"] = moving
-                lin, ang, ctr = r["motion"] if moving else ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), None)
-                be.set_dirichlet_motion(0, lin_vel=lin, ang_vel_deg=ang, center=ctr, force_nonzero=True)
-                return True
-            return False
-        if r.get("kind") == "let_go":
-            c = x[r["turn"], r["axis"]]
-            if not (c <= r["limit"] if r["below"] else c >= r["limit"]):
-                return False
-            for g in r["free"]:
-                be.end_dirichlet(g, t)
-            for g in r["stop"]:
-                be.set_dirichlet_motion(g, lin_vel=(0.0, 0.0, 0.0), force_nonzero=True)
-            r["done"] = True
-            return True
-        if r.get("kind") == "pause":
-            # `script stretchAndPause` (AnimScripter.cpp:1605-1616): the handles move while the turning vertex has not passed x = -0.28;
-            # from then on every Dirichlet node is held (vertexDBCType ZERO)
-            if x[r["turn"], 0] >= r["x_limit"]:
-                return False
-            for g in r["groups"]:
-                be.end_dirichlet(g, t)
-            for ids in r["ids"]:
-                be.add_dirichlet(ids, lin_vel=(0.0, 0.0, 0.0), ang_vel_deg=(0.0, 0.0, 0.0), t0=t, t1=float("inf"))
-            r["done"] = True
-            return True
-        if x[: r["nSim"], 0].min() > r["x_limit"]:
-            be.end_dirichlet(r["group"], t)
-            r["done"] = True
-            return True
-        return False
+        return _anim.RULES[r.get("kind", "dragright")](self, r, be, x, t)  # (the dictionary of `dragright` carries no `kind`)
 
 
 def _attachments(cfg, Vs, nr):
@@ -842,35 +732,57 @@ def _chamber_list(SF, V, name):
     return tri
 
 
-def assemble(cfg, read_mesh):
-    """main.cpp:880-1198: select Dirichlet / Neumann nodes per shape on the mesh as read, transform the shape (R (p * scale) + translate), concatenate."""
-    Vs, Ts, SFs, nr, tr, dirichlet, neumann = [], [], [], [0], [0], [], []
-    codim = []  # (node ids, triangles, moved by its own keywords, segments) of the components of the mesh without tetrahedra
-    CEs = []
-    seqs = []  # mesh sequences: {ids, folder, ext}
-    shells = []  # (triangles, thickness, bend scale, (rho, E, nu)) of the shapes that carry `shell`
-    shell_limits = []  # ... and their (limit or 0, onset, stiffness)
-    shell_models = []  # ... and their (model, alpha): (1, alpha) for `rubber`, (0, 0) otherwise
-    rods = []  # (segments, radius, bend scale, (rho, E, nu)) of the shapes that carry `rod`
-    chambers = []  # (triangle list, pressure, ramp) of the shapes that carry `pressure`
-    chamber_gas = []  # ... and their (gas, ambient, gamma)
+@dataclass
+class _Parts:
+    """what the loop over the shapes collects: the transformed meshes with global indices, and what the shapes' own keywords ask for"""
+    Vs: list = field(default_factory=list)
+    Ts: list = field(default_factory=list)
+    SFs: list = field(default_factory=list)
+    CEs: list = field(default_factory=list)
+    nr: list = field(default_factory=lambda: [0])  # node ranges
+    tr: list = field(default_factory=lambda: [0])  # tetrahedron ranges
+    codim: list = field(default_factory=list)  # (node ids, triangles, moved by its own keywords, segments) of the components of the mesh without tetrahedra
+    given: _anim.ScriptSetup = field(default_factory=_anim.ScriptSetup)  # the Dirichlet / Neumann sets and mesh sequences of the shapes' keywords
+    shells: list = field(default_factory=list)  # (triangles, thickness, bend scale, (rho, E, nu), (limit or 0, onset, stiffness), (model, alpha)) per `shell` shape
+    rods: list = field(default_factory=list)  # (segments, radius, bend scale, (rho, E, nu)) per `rod` shape
+    chambers: list = field(default_factory=list)  # (triangle list, pressure, ramp, (gas, ambient, gamma)) per `pressure` shape
+
+
+def _read_shape(sh, read_mesh):
+    """(ext, V, T, SF, E) of a shape as its file gives it.  main.cpp:948-1005: `.obj` / `.seg` / `.pt` are kinematic surface / segments / points
+    (componentCoDim 2 / 1 / 0), components without tetrahedra"""
+    ext = os.path.splitext(sh.path.lower())[1]
+    T, SF, E = np.zeros((0, 4), dtype=np.int32), np.zeros((0, 3), dtype=np.int32), np.zeros((0, 2), dtype=np.int32)
+    if ext == ".obj":
+        V, SF = read_obj(sh.path)
+    elif ext == ".seg":
+        V, E = read_seg(sh.path)
+    elif ext == ".pt":
+        V = read_pt(sh.path)
+    else:
+        V, T, SF = read_mesh(sh.path)
+    return ext, V, T, SF, E
+
+
+def _codim_keywords(cfg, sh, name, V, SF, E, off, p):
+    """the `shell`, `rod` and `pressure` keywords of one shape (transformed nodes V, first node `off`) as records of p"""
+    mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
+    if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
+        p.shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat, (0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff),
+                         (1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0)))
+    if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
+        p.rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
+    if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
+        p.chambers.append((_chamber_list(SF, V, name) + off, sh.pressure, sh.pressure_ramp, (sh.pressure_gas, sh.pressure_ambient, sh.pressure_gamma)))
+
+
+def _assemble_shapes(cfg, read_mesh):
+    """main.cpp:880-1077: select Dirichlet / Neumann nodes per shape on the mesh as read, transform the shape (R (p * scale) + translate), concatenate."""
+    p = _Parts()
     for s_index, sh in enumerate(cfg.shapes):
-        ext = os.path.splitext(sh.path.lower())[1]
-        is_codim = ext in (".obj", ".seg", ".pt")  # main.cpp:948-1005: kinematic surface / segments / points (componentCoDim 2 / 1 / 0)
-        E = np.zeros((0, 2), dtype=np.int32)
-        if ext == ".obj":
-            V, SF = read_obj(sh.path)
-        elif ext == ".seg":
-            V, E = read_seg(sh.path)
-            SF = np.zeros((0, 3), dtype=np.int32)
-        elif ext == ".pt":
-            V = read_pt(sh.path)
-            SF = np.zeros((0, 3), dtype=np.int32)
-        else:
-            V, T, SF = read_mesh(sh.path)
-        if is_codim:
-            T = np.zeros((0, 4), dtype=np.int32)
-        off = nr[-1]
+        ext, V, T, SF, E = _read_shape(sh, read_mesh)
+        is_codim = ext in (".obj", ".seg", ".pt")
+        off = p.nr[-1]
         # Dirichlet / Neumann nodes are picked on the mesh AS READ (IglUtils::Init_Dirichlet on newV, main.cpp:1045-1068); the
         # shape is scaled / rotated / translated only afterwards (main.cpp:1073-1077), so the relative box follows the shape
         # (the reference picks among the nodes of surface triangles; a `rod` shape has none: its boxes pick among the nodes of its segments)
@@ -878,15 +790,15 @@ def assemble(cfg, read_mesh):
         for rel_min, rel_max, lin, ang, t0, t1 in sh.dbc:
             ids = _scene.select_dirichlet(V, pick, rel_min, rel_max)
             if len(ids):
-                dirichlet.append((ids + off, lin, ang, t0, t1))
+                p.given.dirichlet.append((ids + off, lin, ang, t0, t1))
         for rel_min, rel_max, acc, t0, t1 in sh.nbc:  # same vertex selection (main.cpp:1057-1068)
             ids = _scene.select_dirichlet(V, pick, rel_min, rel_max)
             if len(ids):
-                neumann.append((ids + off, acc, t0, t1))
+                p.given.neumann.append((ids + off, acc, t0, t1))
         V = (V * sh.scale) @ _rot(sh.rotate_deg).T + sh.translate
         if sh.lin_vel is not None or sh.ang_vel_deg is not None:  # scripted component: every node moves (AnimScripter.cpp:1413-1435)
             ids = np.arange(V.shape[0], dtype=np.int32) + off
-            dirichlet.append((ids, sh.lin_vel or (0, 0, 0), sh.ang_vel_deg or (0, 0, 0), 0.0, float("inf")))
+            p.given.dirichlet.append((ids, sh.lin_vel or (0, 0, 0), sh.ang_vel_deg or (0, 0, 0), 0.0, float("inf")))
         if sh.mesh_seq is not None:
             # AnimScripter.cpp:1465-1528: every node of the component is moved to the positions of the next file of the sequence before each
             # step.  The nodes carry the type their velocities give them: a codimensional component without velocities is held (ZERO, :62-70)
@@ -895,46 +807,42 @@ def assemble(cfg, read_mesh):
             if not is_codim:
                 raise UnsupportedKeyword("meshSeq on a tetrahedral component (its nodes are free: the sequence would only nudge them)")
             ids = np.arange(V.shape[0], dtype=np.int32) + off
-            dirichlet.append((ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")))
-            seqs.append({"ids": ids, "folder": sh.mesh_seq, "ext": ext})
-        if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
-            mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
-            shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat))
-            shell_limits.append((0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff))
-            shell_models.append((1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0))
-        if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
-            mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
-            rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
-        if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
-            chambers.append((_chamber_list(SF, V, f"shape {s_index} ({os.path.basename(sh.path)})") + off, sh.pressure, sh.pressure_ramp))
-            chamber_gas.append((sh.pressure_gas, sh.pressure_ambient, sh.pressure_gamma))
+            p.given.dirichlet.append((ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")))
+            p.given.seqs.append({"ids": ids, "folder": sh.mesh_seq, "ext": ext})  # (the very array of the Dirichlet row: assemble() finds the row by it)
+        _codim_keywords(cfg, sh, f"shape {s_index} ({os.path.basename(sh.path)})", V, SF, E, off, p)
         if is_codim:  # (an elastic shell or rod needs nobody to hold it: it counts as moved)
             elastic = sh.shell_thickness is not None or sh.rod_radius is not None
-            codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
-                          sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None or elastic, E + off))
-        CEs.append(E + off)
-        Vs.append(V)
-        Ts.append(T + off)
-        SFs.append(SF + off)
-        nr.append(off + V.shape[0])
-        tr.append(tr[-1] + T.shape[0])
-    attachments = _attachments(cfg, Vs, nr)
-    # kinematic mesh obstacles (MeshCO::MeshCO, MeshCO.cpp:37-58): centred on the vertex mean, rotated, scaled so that the largest
-    # bounding-box extent equals `scale`, moved to `origin`.  They ride along as surface-only components: nodes of no tetrahedron.
-    obstacle = []
+            p.codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
+                            sh.lin_vel is not None or sh.ang_vel_deg is not None or sh.mesh_seq is not None or elastic, E + off))
+        p.CEs.append(E + off)
+        p.Vs.append(V)
+        p.Ts.append(T + off)
+        p.SFs.append(SF + off)
+        p.nr.append(off + V.shape[0])
+        p.tr.append(p.tr[-1] + T.shape[0])
+    return p
+
+
+def _add_mesh_obstacles(cfg, p):
+    """kinematic mesh obstacles (MeshCO::MeshCO, MeshCO.cpp:37-58): centred on the vertex mean, rotated, scaled so that the largest
+    bounding-box extent equals `scale`, moved to `origin`.  They ride along as surface-only components: nodes of no tetrahedron.  -> their node ids"""
+    obstacles = []
     for path, origin, scale, _mu, rot in cfg.mesh_cos:
         Vo, Fo = read_obj(path)
         Vo = Vo - Vo.mean(0)
         Vo = Vo @ _rot(rot).T
         Vo = Vo * (scale / (Vo.max(0) - Vo.min(0)).max()) + origin
-        off = nr[-1]
-        obstacle.append(np.arange(off, off + Vo.shape[0], dtype=np.int32))
-        Vs.append(Vo)
-        SFs.append(Fo + off)
-        nr.append(off + Vo.shape[0])
-        tr.append(tr[-1])
-    V, T, SF = np.vstack(Vs), np.vstack(Ts).astype(np.int32), np.vstack(SFs).astype(np.int32)
-    nSim = nr[len(cfg.shapes)]  # the simulated mesh: everything before the obstacle components
+        off = p.nr[-1]
+        obstacles.append(np.arange(off, off + Vo.shape[0], dtype=np.int32))
+        p.Vs.append(Vo)
+        p.SFs.append(Fo + off)
+        p.nr.append(off + Vo.shape[0])
+        p.tr.append(p.tr[-1])
+    return obstacles
+
+
+def _start_positions(cfg, V, nSim):
+    """`rotateModel` and `size` on the simulated mesh V[:nSim] (in place) -> the start positions where they differ from the rest shape, else None"""
     V0 = None
     if cfg.rot_deg != 0.0 and nSim:
         # main.cpp:1115-1139: the START positions are the model turned about an axis (Eigen::AngleAxis::toRotationMatrix, the axis as
@@ -953,408 +861,100 @@ def assemble(cfg, read_mesh):
         V[:nSim] *= cfg.size / ext
         if V0 is not None:
             V0[:nSim] *= cfg.size / ext
-        lo = (V if V0 is None else V0)[:nSim].min(0).copy()
+        lo = U[:nSim].min(0).copy()
         V[:nSim] -= lo
         if V0 is not None:
             V0[:nSim] -= lo
-    if cfg.script in ("fall", "fallNoShift"):  # AnimScripter.cpp:779-788: lifted by half the bounding-box diagonal, no Dirichlet nodes
-        if cfg.script == "fall":  # Mesh<3> only: the obstacles are not part of it in the reference (dragdown lifts the same way, below)
-            U = V if V0 is None else V0
-            lift = 0.5 * np.linalg.norm(U[:nSim].max(0) - U[:nSim].min(0))
-            V[:nSim, 1] += lift
-            if V0 is not None:
-                V0[:nSim, 1] += lift
-        dirichlet = []
-    if cfg.script in HOLD_SCRIPTS + PULL_SCRIPTS:
-        if cfg.script == "dragdown":  # AnimScripter.cpp:790-792: lifted like `fall`
-            U = V if V0 is None else V0
-            lift = 0.5 * np.linalg.norm(U[:nSim].max(0) - U[:nSim].min(0))
-            V[:nSim, 1] += lift
-            if V0 is not None:
-                V0[:nSim, 1] += lift
-        U = (V if V0 is None else V0)[:nSim]
-        lo, hi = U.min(0), U.max(0)  # mesh.V.colwise().minCoeff() / maxCoeff()
-        rng = hi - lo
-        left, right = _scene.border_verts(U, cfg.handle_ratio)  # mesh.borderVerts_primitive (main.cpp:1180)
-        ids32 = lambda m: np.nonzero(m)[0].astype(np.int32)  # noqa: E731
-        inf = float("inf")
-        zero3 = (0.0, 0.0, 0.0)
-        hold = None  # (node ids, ZERO?)
-        if cfg.script == "hang":  # the LAST node of either border set, ZERO
-            hold = (np.array([b[-1] for b in (left, right) if len(b)], dtype=np.int32), True)
-        elif cfg.script == "hang2":  # the top 1 %, ZERO
-            hold = (ids32(U[:, 1] > hi[1] - rng[1] * 0.01), True)
-        elif cfg.script == "hangTopLeft":  # the nodes of the left border set in the top 1 % and within 1 % of either z end, ZERO
-            L = np.asarray(left)
-            m = (U[L, 1] > hi[1] - rng[1] * 0.01) & ((U[L, 2] > hi[2] - rng[2] * 0.01) | (U[L, 2] < lo[2] + rng[2] * 0.01))
-            hold = (L[m].astype(np.int32), True)
-        elif cfg.script == "stamp":
-            hold = (np.asarray(left, dtype=np.int32), False)
-        elif cfg.script == "stampTopLeft":
-            L = np.asarray(left)
-            hold = (L[U[L, 1] > hi[1] - rng[1] * 0.01].astype(np.int32), False)
-        elif cfg.script == "stampBoth":
-            hold = (np.concatenate([left, right]).astype(np.int32), False)
-        elif cfg.script == "stand":  # the bottom 1 %
-            hold = (ids32(U[:, 1] < lo[1] + rng[1] * 0.01), False)
-        elif cfg.script == "topbottomfix":  # the bottom and the top 2 %
-            hold = (ids32((U[:, 1] < lo[1] + rng[1] * 0.02) | (U[:, 1] > hi[1] - rng[1] * 0.02)), False)
-        elif cfg.script == "corner":  # within 1 % of the x, y or z minimum
-            hold = (ids32((U[:, 0] < lo[0] + rng[0] * 0.01) | (U[:, 1] < lo[1] + rng[1] * 0.01) | (U[:, 2] < lo[2] + rng[2] * 0.01)), False)
-        elif cfg.script == "fixRightMost1":  # the FIRST node within 1e-3 of the right end
-            hold = (ids32(U[:, 0] > hi[0] - 1.0e-3 * rng[0])[:1], False)
-        if hold is not None:
-            hp_dirichlet = [(hold[0], zero3, zero3, 0.0, inf)] if len(hold[0]) else []
-            hp_motions = None if hold[1] or not hp_dirichlet else [(zero3, zero3, None)]
+    return V0
+
+
+def _codim_masses(cfg, m, T):
+    """the nodes of the components without tetrahedra and their lumped masses from the rest shape as it is NOW (see anim_script.lift_at_start), or None, None"""
+    if not m.codim:
+        return None, None
+    V, mass = m.V, np.zeros(m.V.shape[0])
+    for ids, tri, _moved, seg in m.codim:
+        if len(tri):  # barycentric lumping of the triangle areas times the density (Mesh.cpp:318-343, 399)
+            a = 0.5 * np.linalg.norm(np.cross(V[tri[:, 1]] - V[tri[:, 0]], V[tri[:, 2]] - V[tri[:, 0]]), axis=1)
+            for k in range(3):
+                np.add.at(mass, tri[:, k], cfg.rho * a / 3.0)
+        elif len(seg):  # both ends of a segment of length l get density * l^3 pi / 12 (Mesh.cpp:279-295, 399)
+            l = np.linalg.norm(V[seg[:, 0]] - V[seg[:, 1]], axis=1)
+            for k in range(2):
+                np.add.at(mass, seg[:, k], cfg.rho * l ** 3 * math.pi / 12.0)
         else:
-            groups = []
-            if cfg.script in ("stretch", "squash"):  # the border sets pulled apart at 0.1 / pushed together at 0.03 along x
-                v = -0.1 if cfg.script == "stretch" else 0.03
-                groups = [(np.asarray(left, dtype=np.int32), (v, 0.0, 0.0)), (np.asarray(right, dtype=np.int32), (-v, 0.0, 0.0))]
-            elif cfg.script == "dragdown":  # the middle of the bottom tenth pulled down at 1.5
-                m = (U[:, 1] < lo[1] + rng[1] * 0.1) & (U[:, 0] < lo[0] + rng[0] * 0.52) & (U[:, 0] > lo[0] + rng[0] * 0.42)
-                groups = [(ids32(m), (0.0, -1.5, 0.0))]
-            else:  # curtain: eight pins along the top edge, pin i drawn in +x at 0.04 (7 - i) / 7; a node takes the first pin that fits
-                taken = np.zeros(len(U), dtype=bool)
-                for pin in range(8):
-                    x0 = lo[0] + rng[0] / 7.0 * pin
-                    m = (U[:, 0] > x0 - rng[0] * 0.0025) & (U[:, 0] < x0 + rng[0] * 0.0025) & (U[:, 1] > hi[1] - rng[1] * 0.005) & ~taken
-                    taken |= m
-                    groups.append((ids32(m), (0.04 * (7.0 - pin) / 7.0, 0.0, 0.0)))
-            groups = [g for g in groups if len(g[0])]
-            hp_dirichlet = [(ids, lin, zero3, 0.0, inf) for ids, lin in groups]
-            hp_motions = [(lin, zero3, None) for _ids, lin in groups]
-    rule_release = None
-    if cfg.script in RULE_SCRIPTS:
-        U = (V if V0 is None else V0)[:nSim]
-        lo, hi = U.min(0), U.max(0)
-        rng = hi - lo
-        left, right = (np.asarray(b, dtype=np.int32) for b in _scene.border_verts(U, cfg.handle_ratio))
-        ids32 = lambda m: np.nonzero(m)[0].astype(np.int32)  # noqa: E731
-        zero3 = (0.0, 0.0, 0.0)
-        ctr_rest = tuple(0.5 * (V[:nSim].min(0) + V[:nSim].max(0)))  # mesh.bbox.colwise().mean(): the rest shape's box
-        groups = []  # (ids, lin, ang in degrees, centre)
-        turn = None  # (node, axis, lo, hi, component that changes sign, groups it applies to, stop instead)
-        let_go = None
-        rule_zero = False  # the held set is typed ZERO
-        if cfg.script in ("push", "tear"):  # bottom 1 % held; top 1 % pushed down at 1 until it is 0.5 lower / dragged in -x at 5, turning at 4 further left
-            bottom = U[:, 1] < lo[1] + rng[1] * 0.01
-            top = ids32(~bottom & (U[:, 1] > hi[1] - rng[1] * 0.01))
-            groups = [(ids32(bottom), zero3, zero3, None), (top, (0.0, -1.0, 0.0) if cfg.script == "push" else (-5.0, 0.0, 0.0), zero3, None)]
-            if len(top):
-                turn = (int(top[0]), 1, U[top[0], 1] - 0.5, np.inf, 1, [1], True) if cfg.script == "push" else (int(top[0]), 0, U[top[0], 0] - 4.0, np.inf, 0, [1], False)
-        elif cfg.script in ("upndown", "undstamp"):  # the border sets (undstamp: the left one) go up / down at 1.8, turning 0.6 above and below the start
-            sets = [left, right] if cfg.script == "upndown" else [left]
-            groups = [(b, (0.0, (-1.0) ** i * 1.8, 0.0), zero3, None) for i, b in enumerate(sets)]
-            turn = (int(left[0]), 1, U[left[0], 1] - 0.6, U[left[0], 1] + 0.6, 1, list(range(len(sets))), False)
-        elif cfg.script == "stretchnsquash":  # pulled apart at 0.9, turning when the first left node is 0.8 further out / 0.4 further in
-            groups = [(b, ((-1.0) ** i * -0.9, 0.0, 0.0), zero3, None) for i, b in enumerate((left, right))]
-            turn = (int(left[0]), 0, U[left[0], 0] - 0.8, U[left[0], 0] + 0.4, 0, [0, 1], False)
-        elif cfg.script == "bend":  # every border node but the last of its set turns about z through that last one at 0.05 pi (9 degrees) per unit time
-            for i, b in enumerate((left, right)):
-                groups.append((b[:-1], zero3, (0.0, 0.0, (-1.0) ** i * -9.0), tuple(U[b[-1]])))
-                groups.append((b[-1:], zero3, zero3, None))
-        elif cfg.script in ("rubberBandPull", "fourLegPull", "headTailPull", "toggleTop"):
-            y0, y1, x0, x1, z0, z1 = lo[1], hi[1], lo[0], hi[0], lo[2], hi[2]
-            if cfg.script == "rubberBandPull":  # bottom / top 2 % drawn apart at 0.2, the waist pulled in -x at 2.5 and let go 5 further left
-                a = U[:, 1] < y0 + rng[1] * 0.02
-                b = ~a & (U[:, 1] > y1 - rng[1] * 0.02)
-                w = ~a & ~b & (U[:, 1] < y1 - rng[1] * 0.48) & (U[:, 1] > y0 + rng[1] * 0.48)
-                sets = [(a, (0.0, -0.2, 0.0), False), (b, (0.0, 0.2, 0.0), False), (w, (-2.5, 0.0, 0.0), True)]
-                lim = (2, 0, -5.0, True)  # (set whose first node decides, axis, offset of the limit, "<=")
-            elif cfg.script == "fourLegPull":
-                a = (U[:, 1] > y1 - rng[1] * 0.129) & (U[:, 0] < x0 + rng[0] * 0.16)
-                b = ~a & (U[:, 1] > y1 - rng[1] * 0.16) & (U[:, 0] > x1 - rng[0] * 0.16)
-                c = ~a & ~b & (U[:, 1] < y0 + rng[1] * 0.02) & (U[:, 0] > x1 - rng[0] * 0.25)
-                d = ~a & ~b & ~c & (U[:, 1] < y0 + rng[1] * 0.02) & (U[:, 0] < x0 + rng[0] * 0.25)
-                sets = [(a, zero3, False), (b, (2.5, 0.0, 0.0), True), (c, (2.5, -3.5, 0.0), True), (d, (0.0, -3.5, 0.0), True)]
-                lim = (3, 1, -5.0, True)
-            elif cfg.script == "headTailPull":
-                a = U[:, 2] < z0 + rng[2] * 0.02
-                b = ~a & (U[:, 2] > z1 - rng[2] * 0.02)
-                c = ~a & ~b & (U[:, 2] > z0 + rng[2] * 0.46) & (U[:, 2] < z0 + rng[2] * 0.54)
-                sets = [(a, (3.5, 0.0, 0.0), True), (b, (3.5, 0.0, 0.0), True), (c, zero3, False)]
-                lim = (0, 0, 4.5, False)
-            else:  # toggleTop: the top 2 % drawn in -x at 0.5 and let go 0.1 further left
-                sets = [(U[:, 1] > y1 - rng[1] * 0.02, (-0.5, 0.0, 0.0), True)]
-                lim = (0, 0, -0.1, True)
-            groups = [(ids32(m), lin, zero3, None) for m, lin, _f in sets]
-            first = groups[lim[0]][0]
-            if len(first):
-                let_go = {"kind": "let_go", "turn": int(first[0]), "axis": lim[1], "limit": float(U[first[0], lim[1]] + lim[2]), "below": lim[3],
-                          "free": [k for k, (_m, _l, f) in enumerate(sets) if f], "stop": [k for k, (_m, _l, f) in enumerate(sets) if not f], "done": False}
-        elif cfg.script in ("scaleF", "swing", "stampInv", "standInv", "NMFixBottomDragLeft", "NMFixBottomDragForward"):
-            W = V if V0 is None else V0  # the start positions themselves (the rest shape stays)
-            if cfg.script in ("scaleF", "stampInv", "standInv", "swing") and V0 is None:
-                V0 = V.copy()
-                W = V0
-            if cfg.script == "scaleF":  # every start position times 1.5 about the origin
-                W[:nSim] *= 1.5
-            elif cfg.script == "swing":  # lifted by 1.3 heights, the left 5 % held (ZERO)
-                W[:nSim, 1] += 1.3 * rng[1]
-                groups = [(ids32(U[:, 0] < lo[0] + rng[0] * 0.05), zero3, zero3, None)]
-                rule_zero = True
-            elif cfg.script in ("stampInv", "standInv"):  # the left / bottom 1 % held; the start turned inside out and squeezed to a tenth about it
-                ax = 0 if cfg.script == "stampInv" else 1
-                held = ids32(U[:, ax] < lo[ax] + rng[ax] * 0.01)
-                groups = [(held, zero3, zero3, None)]
-                off = 1.1 * U[held[0], ax]  # *mesh.DBCVertexIds.begin(): the smallest held index
-                W[:nSim, ax] = -0.1 * W[:nSim, ax] + off
-            else:  # the bottom 5 % held, the top 5 % pulled by a Neumann acceleration of 600 in -x / +x
-                bottom = U[:, 1] < lo[1] + rng[1] * 0.05
-                groups = [(ids32(bottom), zero3, zero3, None)]
-                neumann = [(ids32(~bottom & (U[:, 1] > hi[1] - rng[1] * 0.05)), (-600.0 if cfg.script == "NMFixBottomDragLeft" else 600.0, 0.0, 0.0), 0.0, float("inf"))]
-        else:  # twist about x through the rest box centre + a pull along x; twistnsns turns the pull round like stretchnsquash
-            w, v, out = {"twistnstretch": (18.0, 0.1, None), "twistnsns": (72.0, 1.2, 1.2), "twistnsns_old": (72.0, 0.9, 0.8)}[cfg.script]
-            groups = [(b, ((-1.0) ** i * -v, 0.0, 0.0), ((-1.0) ** i * -w, 0.0, 0.0), ctr_rest) for i, b in enumerate((left, right))]
-            if out is not None:
-                turn = (int(left[0]), 0, U[left[0], 0] - out, U[left[0], 0] + 0.4, 0, [0, 1], False)
-        keep = [k for k, g in enumerate(groups) if len(g[0])]
-        remap = {k: i for i, k in enumerate(keep)}
-        groups = [groups[k] for k in keep]
-        hp_dirichlet = [(ids, lin, ang, 0.0, float("inf")) for ids, lin, ang, _c in groups]
-        hp_motions = None if rule_zero or not groups else [(lin, ang, c) for _ids, lin, ang, c in groups]
-        if let_go is not None:
-            let_go["free"] = [remap[g] for g in let_go["free"] if g in remap]
-            let_go["stop"] = [remap[g] for g in let_go["stop"] if g in remap]
-            rule_release = let_go
-        if turn is not None:
-            rule_release = {"kind": "turn", "turn": turn[0], "axis": turn[1], "lo": float(turn[2]), "hi": float(turn[3]), "comp": turn[4],
-                            "groups": [remap[g] for g in turn[5] if g in remap], "stop": turn[6], "lin": [m[0] for m in hp_motions],
-                            "ang": [m[1] for m in hp_motions], "ctr": [m[2] for m in hp_motions], "done": False}
-    codim_nodes = codim_mass = codim_fixed = None
-    codim_edges = np.vstack(CEs).astype(np.int32) if CEs else np.zeros((0, 2), dtype=np.int32)
-    if codim:
-        codim_nodes = np.concatenate([ids for ids, _f, _m, _e in codim])
-        m = np.zeros(V.shape[0])
-        for ids, tri, _m, seg in codim:
-            if len(tri):  # barycentric lumping of the triangle areas times the density (Mesh.cpp:318-343, 399)
-                a = 0.5 * np.linalg.norm(np.cross(V[tri[:, 1]] - V[tri[:, 0]], V[tri[:, 2]] - V[tri[:, 0]]), axis=1)
-                for k in range(3):
-                    np.add.at(m, tri[:, k], cfg.rho * a / 3.0)
-            elif len(seg):  # both ends of a segment of length l get density * l^3 pi / 12 (Mesh.cpp:279-295, 399)
-                l = np.linalg.norm(V[seg[:, 0]] - V[seg[:, 1]], axis=1)
-                for k in range(2):
-                    np.add.at(m, seg[:, k], cfg.rho * l ** 3 * math.pi / 12.0)
-            else:
-                # a point carries the mean nodal mass of the tetrahedral components (avgNodeMass(dim), Mesh.cpp:403-411, 583-607): lumped
-                # masses = density * a quarter of the adjacent element volumes
-                tm = np.zeros(V.shape[0])
-                if T.shape[0]:
-                    vol = np.abs(np.einsum("ij,ij->i", np.cross(V[T[:, 1]] - V[T[:, 0]], V[T[:, 2]] - V[T[:, 0]]), V[T[:, 3]] - V[T[:, 0]])) / 6.0
-                    for k in range(4):
-                        np.add.at(tm, T[:, k], cfg.rho * vol / 4.0)
-                n_tet_nodes = sum(nr[c + 1] - nr[c] for c in range(len(cfg.shapes)) if tr[c + 1] > tr[c])
-                m[ids] = tm.sum() / n_tet_nodes if n_tet_nodes else 0.0
-        codim_mass = m[codim_nodes]
-        if cfg.script in ("DCOFix", "DCOBallHitWall"):  # AnimScripter.cpp:1222-1236: every codimensional component is held (NONZERO, no motion)
-            dirichlet = []
-            codim_fixed = codim_nodes
-        elif cfg.script not in DCO_SCRIPTS and cfg.script not in ("DCOSegBedSquash", "meshSeqFromFile", "DCOHammerWalnut", "DCOCut") and not all(moved for _i, _f, moved, _e in codim):
-            raise UnsupportedKeyword("codimensional shape that no script fixes or moves")
-    elif cfg.script in ("DCOFix", "DCOBallHitWall"):
-        dirichlet = []  # mesh.resetDBCVertices(); nothing to hold
-    release = None
-    if cfg.script == "dragright":
-        # AnimScripter.cpp:809-826: lifted like `fall`, the nodes within 4 % of the right end of the body become a NONZERO handle
-        # pulled at 0.5 in +x; stepAnimScript lets go once the whole body is right of every mesh obstacle (:1619-1632)
-        # (the script works on mesh.V, the START positions: with `rotateModel` those are not the rest shape -- 13_dolphinFunnel.txt; found by
-        # running that scene through the reference: lift and handle were taken from the rest shape before)
-        U = V if V0 is None else V0
-        U[:nSim, 1] += 0.5 * np.linalg.norm(U[:nSim].max(0) - U[:nSim].min(0))
-        lo, hi = U[:nSim].min(0), U[:nSim].max(0)
-        ids = np.nonzero(U[:nSim, 0] > hi[0] - 0.04 * (hi[0] - lo[0]))[0].astype(np.int32)
-        dirichlet = [(ids, (0.5, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))]
-        limit = max((V[o, 0].max() for o in obstacle), default=-np.inf)
-        release = {"group": 0, "x_limit": float(limit), "nSim": int(nSim), "done": False}
-    motions = None  # per Dirichlet group: (lin, ang in degrees, fixed centre or None) with the nodes typed NONZERO throughout
-    if cfg.script in ("ACOSquash", "ACOSquash6"):  # AnimScripter.cpp:956-985: no Dirichlet nodes; planes 2 i / 2 i + 1 move at +1 / -1 along axis i
-        nP = 2 if cfg.script == "ACOSquash" else 6
-        if len(cfg.half_spaces) < nP:
-            raise UnsupportedKeyword(f"script {cfg.script} needs {nP} analytic planes (ground / halfSpace)")
-        dirichlet = []
-        vel_p = [np.eye(3)[i // 2] * (1.0 if i % 2 == 0 else -1.0) for i in range(nP)]
-        release = {"kind": "aco", "vel": vel_p, "origins": [np.array(h[0], dtype=np.float64) for h in cfg.half_spaces[:nP]],
-                   "pairs": [(a, 0.1 if nP == 2 else 0.2) for a in range(0, nP, 2)], "done": False}
-    if cfg.script == "meshSeqFromFile":
-        # AnimScripter.cpp:1222-1236, 2126-2144: every component without tetrahedra is a NONZERO Dirichlet set; before each step the FIRST of them is
-        # moved onto the positions of <folder>/<meshI>.obj, meshI counted from 1
-        parts = [ids for ids, _f, _m, _e in codim]
-        if not parts:
-            raise UnsupportedKeyword("script meshSeqFromFile without a surface-only component to move")
-        dirichlet = [(ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")) for ids in parts]
-        motions = [((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), None)] * len(parts)
-        seqs = [{"ids": parts[0], "folder": cfg.script_seq_folder, "ext": ".obj"}]
-        codim_fixed = None
-    if cfg.script in HOLD_SCRIPTS + PULL_SCRIPTS + RULE_SCRIPTS:  # resetDBCVertices(): the scripts replace whatever the shapes' own DBC keywords selected
-        dirichlet, motions = hp_dirichlet, hp_motions
-        if cfg.script in RULE_SCRIPTS:
-            release = rule_release
-    if cfg.script in DCO_SCRIPTS:
-        spec = DCO_SCRIPTS[cfg.script]
-        U = V if V0 is None else V0
-        dirichlet, motions = [], []
-        codim_comp = {int(ids[0]): True for ids, _f, _m, _e in codim}  # first node of every component without tetrahedra
-        if cfg.script == "DCOSqueezeOut":
-            # Every surface-only component is a NONZERO Dirichlet node set (AnimScripter.cpp:1261-1280); the first one carries a velocity of
-            # 0.3 downwards that is applied while `topMax > bottomMin + (bottomMax - bottomMin) / 3.8 * 0.9` (:2102-2124).  As shipped that
-            # test is never true: bottomMin starts at -infinity and is updated with std::min, so it STAYS -infinity and the right-hand side
-            # is -inf + inf = NaN.  Seen in a run of the reference-compiled code (the plane does not move); restated as what it does.
-            comps = [c for c in range(len(cfg.shapes)) if nr[c] in codim_comp]  # mesh.componentCoDim[compI] < 3
-            for c in comps:
-                dirichlet.append((np.arange(nr[c], nr[c + 1], dtype=np.int32), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")))
-                motions.append(((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), None))
-            release = None
-        else:
-            n = spec["n"]
-            if len(cfg.shapes) < n + 1:
-                raise UnsupportedKeyword(f"script {cfg.script} needs {n} scripted components and a body")
-            for c in range(n):
-                ids = np.arange(nr[c], nr[c + 1], dtype=np.int32)
-                lin = tuple(float(x) for x in spec["lin"][c]) if "lin" in spec else (0.0, 0.0, 0.0)
-                ang = tuple(math.degrees(x) for x in spec["ang"][c]) if "ang" in spec else (0.0, 0.0, 0.0)
-                ctr = tuple(0.5 * (U[ids].max(0) + U[ids].min(0))) if "ang" in spec else None  # MCORotCenter: fixed at set-up
-                dirichlet.append((ids, lin, ang, 0.0, float("inf")))
-                motions.append((lin, ang, ctr))
-            release = {"kind": "dco", "script": cfg.script, "done": False, "lin": [m[0] for m in motions]} if "lin" in spec else None
-            comps = list(range(n))
-        if any(nr[c] in codim_comp and c not in comps for c in range(len(cfg.shapes))):
-            raise UnsupportedKeyword("surface-only component that the script neither moves nor holds")
-        codim_fixed = None
-    if cfg.script in ("DCOHammerWalnut", "DCOCut"):
-        # AnimScripter.cpp:1120-1170, 1993-2032: the SECOND component (whatever its kind) is a NONZERO set; while its lowest node is above 0.05 it
-        # turns about z at pi / 6 through (x max, y min, z middle) of its start box (the hammer), resp. above 0.001 it moves at (0, -1, -1) (the knife)
-        if len(cfg.shapes) < 2:
-            raise UnsupportedKeyword(f"script {cfg.script} needs a second component to move")
-        U = V if V0 is None else V0
-        ids = np.arange(nr[1], nr[2], dtype=np.int32)
-        lo, hi = U[ids].min(0), U[ids].max(0)
-        if cfg.script == "DCOHammerWalnut":
-            mot = ((0.0, 0.0, 0.0), (0.0, 0.0, 30.0), (float(hi[0]), float(lo[1]), float(0.5 * (hi[2] + lo[2]))))
-            y_stop = 0.05
-        else:
-            mot = ((0.0, -1.0, -1.0), (0.0, 0.0, 0.0), None)
-            y_stop = 0.001
-        dirichlet, motions = [(ids, mot[0], mot[1], 0.0, float("inf"))], [mot]
-        release = {"kind": "while_above", "ids": ids, "y": y_stop, "motion": mot, "moving": True, "done": False}
-        if any(c != 1 for c in range(len(cfg.shapes)) if not tr[c + 1] > tr[c]):
-            raise UnsupportedKeyword("surface-only component that the script neither moves nor holds")
-        codim_fixed = None
-    if cfg.script == "stretchAndPause":
-        # AnimScripter.cpp:475-500: the nodes within 1 % of the left / right end of the model are NONZERO handles pulled apart at 1 in
-        # -x / +x; the turning vertex is the LAST left handle in index order (`turningPointAdded` is never set), the limit x = -0.28
-        U = V if V0 is None else V0
-        lo, hi = U[:nSim].min(0), U[:nSim].max(0)
-        left = np.nonzero(U[:nSim, 0] < lo[0] + 0.01 * (hi[0] - lo[0]))[0].astype(np.int32)
-        right = np.nonzero((U[:nSim, 0] > hi[0] - 0.01 * (hi[0] - lo[0])) & ~(U[:nSim, 0] < lo[0] + 0.01 * (hi[0] - lo[0])))[0].astype(np.int32)
-        dirichlet = [(left, (-1.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")), (right, (1.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))]
-        release = {"kind": "pause", "turn": int(left[-1]), "x_limit": -0.28, "groups": [0, 1], "ids": [left, right], "done": False}
-    if cfg.script in HANDLE_SCRIPTS:
-        U = V if V0 is None else V0
-        lo, hi = U[:nSim].min(0), U[:nSim].max(0)  # mesh.V.colwise().minCoeff() / maxCoeff(): every node of Mesh<3>
-        rng = hi - lo
-        still = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), None)
-        if cfg.script == "hangLeft":  # AnimScripter.cpp:191-204: the left border nodes (IglUtils::findBorderVerts, handleRatio 0.01) are held (ZERO)
-            left, _right = _scene.border_verts(U[:nSim], cfg.handle_ratio)
-            dirichlet = [(np.asarray(left, dtype=np.int32), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))]
-        elif cfg.script == "fixLowerHalf":  # AnimScripter.cpp:337-350: the lower half of the model is held (NONZERO, no motion)
-            ids = np.nonzero(U[:nSim, 1] < lo[1] + rng[1] * 0.5)[0].astype(np.int32)
-            dirichlet, motions = [(ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))], [still]
-        elif cfg.script == "pushRightMost1":  # :895-910, 1820-1826: the FIRST node within 1e-3 of the right end is pushed at 0.15 in -x
-            ids = np.nonzero(U[:nSim, 0] > hi[0] - 1.0e-3 * rng[0])[0][:1].astype(np.int32)
-            dirichlet, motions = [(ids, (-0.15, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))], [((-0.15, 0.0, 0.0), (0.0, 0.0, 0.0), None)]
-        elif cfg.script == "utopiaComparison":
-            # :1283-1302, 1641-1646: nodes within 1e-4 of the model's WIDTH (range[0], as written) of the top carry a Neumann acceleration of
-            # 1.5 downwards, those as close to the bottom are held
-            top = U[:nSim, 1] > hi[1] - rng[0] * 1e-4
-            bottom = ~top & (U[:nSim, 1] < lo[1] + rng[0] * 1e-4)
-            dirichlet, motions = [(np.nonzero(bottom)[0].astype(np.int32), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf"))], [still]
-            neumann = [(np.nonzero(top)[0].astype(np.int32), (0.0, -1.5, 0.0), 0.0, float("inf"))]
-        else:
-            # DCOSegBedSquash (:1239-1259, 2080-2100): every component without tetrahedra is a NONZERO Dirichlet set; those in the upper half of
-            # the component list (index >= (#components + 1) / 2) move down at 1 while the gap between the lowest node of the upper ones and the
-            # highest node of the lower ones exceeds 0.1 -- the two beds of `17_pinCushionBall.txt` closing on the ball
-            ncomp = len(cfg.shapes)
-            parts = [c for c in range(ncomp) if not tr[c + 1] > tr[c]]
-            if not parts:
-                raise UnsupportedKeyword("script DCOSegBedSquash without a component to move")
-            up = [c for c in parts if c >= (ncomp + 1) // 2]
-            down = [c for c in parts if c < (ncomp + 1) // 2]
-            cat = lambda cs: np.concatenate([np.arange(nr[c], nr[c + 1], dtype=np.int32) for c in cs]) if cs else np.zeros(0, np.int32)  # noqa: E731
-            dirichlet, motions = [], []
-            for ids, lin in ((cat(down), (0.0, 0.0, 0.0)), (cat(up), (0.0, -1.0, 0.0))):
-                if len(ids):
-                    dirichlet.append((ids, lin, (0.0, 0.0, 0.0), 0.0, float("inf")))
-                    motions.append((lin, (0.0, 0.0, 0.0), None))
-            release = {"kind": "segbed", "up": cat(up), "down": cat(down), "group": len(dirichlet) - 1, "moving": True, "done": False} if len(up) else None
-            codim_fixed = None
-    vel = np.zeros_like(V)
-    fixed = np.zeros(V.shape[0], dtype=bool)
-    for ids, *_ in dirichlet:
-        fixed[ids] = True
-    if cfg.script == "DCOBallHitWall":  # AnimScripter.cpp:1376-1389: every node of a tetrahedral component starts at v_x (default 1000)
-        vx = cfg.script_params[0] if cfg.script_params and cfg.script_params[0] == cfg.script_params[0] else 1000.0
-        for s in range(len(cfg.shapes)):
-            if tr[s + 1] > tr[s]:
-                vel[nr[s]:nr[s + 1], 0] = vx
-    if cfg.script in INITVEL_SCRIPTS:  # AnimScripter::initVelocity (AnimScripter.cpp:1336-1374), over every node of Mesh<3>
-        U = (V if V0 is None else V0)[:nSim]
-        lo, hi = U.min(0), U.max(0)
-        rng = hi - lo
-        if cfg.script == "drop":
-            vel[:nSim, 1] = -1.0
-        elif cfg.script == "leftHitRight":
-            vel[:nSim][U[:, 0] < lo[0] + rng[0] / 2.0, 0] = 1.0
-        else:
-            bottom = U[:, 1] < lo[1] + rng[1] * 0.01
-            vel[:nSim][bottom, 0] = 1.0
-            vel[:nSim][~bottom & (U[:, 1] > hi[1] - rng[1] * 0.01), 0] = -1.0
-    for s, sh in enumerate(cfg.shapes):  # AnimScripter::initVelocity (AnimScripter.cpp:1319-1333): `initVel` under `script null` only
-        if sh.init_vel is None or cfg.script != "null" or not tr[s + 1] > tr[s]:
-            continue
-        a, b = nr[s], nr[s + 1]
-        ctr = 0.5 * (V[a:b].max(0) + V[a:b].min(0))
-        w = np.radians(np.array(sh.init_vel[1]))
-        v = np.array(sh.init_vel[0]) + np.cross(w, V[a:b] - ctr)
-        v[fixed[a:b]] = 0.0
-        vel[a:b] = v
-    obst = np.concatenate(obstacle) if obstacle else None
-    sc = AssembledScene(cfg, V, T, SF, nr, tr, dirichlet, vel, neumann, obst, release, codim_nodes, codim_mass, codim_fixed, V0)
-    sc.motions = motions
-    sc.codim_edges = codim_edges
-    if shells:
-        if len({b for _t, _h, b, _m in shells}) > 1:
+            # a point carries the mean nodal mass of the tetrahedral components (avgNodeMass(dim), Mesh.cpp:403-411, 583-607): lumped
+            # masses = density * a quarter of the adjacent element volumes
+            tm = np.zeros(V.shape[0])
+            if T.shape[0]:
+                vol = np.abs(np.einsum("ij,ij->i", np.cross(V[T[:, 1]] - V[T[:, 0]], V[T[:, 2]] - V[T[:, 0]]), V[T[:, 3]] - V[T[:, 0]])) / 6.0
+                for k in range(4):
+                    np.add.at(tm, T[:, k], cfg.rho * vol / 4.0)
+            n_tet_nodes = sum(m.node_ranges[c + 1] - m.node_ranges[c] for c in range(m.n_shapes) if m.has_tets(c))
+            mass[ids] = tm.sum() / n_tet_nodes if n_tet_nodes else 0.0
+    nodes = np.concatenate([ids for ids, _f, _m, _e in m.codim])
+    return nodes, mass[nodes]
+
+
+def _per(records, value, dtype=np.float64):
+    """one value per primitive: value(record) repeated over the primitives record[0] of every record"""
+    return np.concatenate([np.full(len(r[0]), value(r), dtype=dtype) for r in records])
+
+
+def _codim_payloads(p, attachments, V):
+    """-> (shell, rod, attachments, chambers) as AssembledScene holds them and apply() hands them on, None where no shape asks for one"""
+    shell = rod = chambers = None
+    if p.shells:
+        if len({r[2] for r in p.shells}) > 1:
             raise ValueError("one bend scale per scene: the shell shapes give different ones")
-        per = lambda k: np.concatenate([np.full(len(t), float(m[k])) for t, _h, _b, m in shells])  # noqa: E731
-        sc.shell = {"tri": np.vstack([t for t, *_ in shells]).astype(np.int32), "thickness": np.concatenate([np.full(len(t), float(h)) for t, h, *_ in shells]),
-                    "rho": per(0), "YM": per(1), "PR": per(2), "bend": float(shells[0][2])}
-        if any(q[0] > 0.0 for q in shell_limits):  # per triangle, as Context.set_shell_strain_limit takes them; a shape without `limit` stays unlimited (0)
+        shell = {"tri": np.vstack([r[0] for r in p.shells]).astype(np.int32), "thickness": _per(p.shells, lambda r: float(r[1])),
+                 "rho": _per(p.shells, lambda r: float(r[3][0])), "YM": _per(p.shells, lambda r: float(r[3][1])), "PR": _per(p.shells, lambda r: float(r[3][2])),
+                 "bend": float(p.shells[0][2])}
+        if any(r[4][0] > 0.0 for r in p.shells):  # per triangle, as Context.set_shell_strain_limit takes them; a shape without `limit` stays unlimited (0)
             for k, name in enumerate(("limit", "onset", "stiff")):
-                sc.shell[name] = np.concatenate([np.full(len(t[0]), float(q[k])) for t, q in zip(shells, shell_limits)])
-        if any(m for m, _a in shell_models):  # per triangle, as Context.set_shell_membrane takes them; a shape without `rubber` stays StVK (0)
-            sc.shell["model"] = np.concatenate([np.full(len(t[0]), m, dtype=np.int32) for t, (m, _a) in zip(shells, shell_models)])
-            sc.shell["alpha"] = np.concatenate([np.full(len(t[0]), float(a)) for t, (_m, a) in zip(shells, shell_models)])
-    if rods:
-        if len({b for _s, _r, b, _m in rods}) > 1:
+                shell[name] = _per(p.shells, lambda r: float(r[4][k]))
+        if any(r[5][0] for r in p.shells):  # per triangle, as Context.set_shell_membrane takes them; a shape without `rubber` stays StVK (0)
+            shell["model"] = _per(p.shells, lambda r: r[5][0], dtype=np.int32)
+            shell["alpha"] = _per(p.shells, lambda r: float(r[5][1]))
+    if p.rods:
+        if len({r[2] for r in p.rods}) > 1:
             raise ValueError("one bend scale per scene: the rod shapes give different ones")
-        per = lambda k: np.concatenate([np.full(len(e), float(m[k])) for e, _r, _b, m in rods])  # noqa: E731
-        sc.rod = {"seg": np.vstack([e for e, *_ in rods]).astype(np.int32), "radius": np.concatenate([np.full(len(e), float(r)) for e, r, *_ in rods]),
-                  "rho": per(0), "YM": per(1), "bend": float(rods[0][2])}
+        rod = {"seg": np.vstack([r[0] for r in p.rods]).astype(np.int32), "radius": _per(p.rods, lambda r: float(r[1])),
+               "rho": _per(p.rods, lambda r: float(r[3][0])), "YM": _per(p.rods, lambda r: float(r[3][1])), "bend": float(p.rods[0][2])}
     if attachments is not None:  # (`stitch ... rest`: the distance in the rest shape as the stepper gets it, behind `size`)
         r = attachments.pop("rest")
         attachments["L"][r] = np.linalg.norm(V[attachments["nodesA"][r]] - V[attachments["nodesB"][r]], axis=1)
-    sc.attachments = attachments
-    if chambers:
-        sc.chambers = {"tri_lists": [t.astype(np.int32) for t, _p, _r in chambers], "pressure": np.array([p for _t, p, _r in chambers], dtype=np.float64),
-                       "ramp": np.array([r for _t, _p, r in chambers], dtype=np.float64)}
-        if any(g for g, _a, _k in chamber_gas):
-            sc.chambers.update(gas=np.array([g for g, _a, _k in chamber_gas], dtype=bool), ambient=np.array([a for _g, a, _k in chamber_gas], dtype=np.float64),
-                               gamma=np.array([k for _g, _a, k in chamber_gas], dtype=np.float64))
-    for q in seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
-        q["group"] = next(g for g, d in enumerate(dirichlet) if d[0] is q["ids"])
-    sc.mesh_seqs = seqs
-    if cfg.script == "meshSeqFromFile":
-        sc.mesh_i = 1
+    if p.chambers:
+        chambers = {"tri_lists": [q[0].astype(np.int32) for q in p.chambers], "pressure": np.array([q[1] for q in p.chambers], dtype=np.float64),
+                    "ramp": np.array([q[2] for q in p.chambers], dtype=np.float64)}
+        if any(q[3][0] for q in p.chambers):
+            chambers.update(gas=np.array([q[3][0] for q in p.chambers], dtype=bool), ambient=np.array([q[3][1] for q in p.chambers], dtype=np.float64),
+                            gamma=np.array([q[3][2] for q in p.chambers], dtype=np.float64))
+    return shell, rod, attachments, chambers
+
+
+def assemble(cfg, read_mesh):
+    """main.cpp:880-1198 and AnimScripter::initAnimScript: the shapes become one mesh, the script (anim_script.SETUP) sets up what it holds and moves.  The
+    ORDER of the steps is behaviour: see anim_script.lift_at_start, and `rest` of a stitch is measured behind `size`."""
+    p = _assemble_shapes(cfg, read_mesh)
+    attachments = _attachments(cfg, p.Vs, p.nr)
+    obstacles = _add_mesh_obstacles(cfg, p)
+    V, T, SF = np.vstack(p.Vs), np.vstack(p.Ts).astype(np.int32), np.vstack(p.SFs).astype(np.int32)
+    nSim = p.nr[len(cfg.shapes)]  # the simulated mesh: everything before the obstacle components
+    model = _anim.Model(V, _start_positions(cfg, V, nSim), nSim, p.nr, p.tr, len(cfg.shapes), p.codim, obstacles, cfg.handle_ratio)
+    _anim.lift_at_start(cfg, model)
+    codim_nodes, codim_mass = _codim_masses(cfg, model, T)
+    _anim.check_codim_moved(cfg, model)  # (before the refusals of the scripts themselves)
+    st = _anim.SETUP[cfg.script](cfg, model, p.given)
+    vel = _anim.start_velocity(cfg, model, st.dirichlet)
+    sc = AssembledScene(cfg, V, T, SF, p.nr, p.tr, st.dirichlet, vel, st.neumann, np.concatenate(obstacles) if obstacles else None, st.release,
+                        codim_nodes, codim_mass, st.codim_fixed, model.V0)
+    sc.motions, sc.mesh_i = st.motions, st.mesh_i
+    sc.codim_edges = np.vstack(p.CEs).astype(np.int32) if p.CEs else np.zeros((0, 2), dtype=np.int32)
+    sc.shell, sc.rod, sc.attachments, sc.chambers = _codim_payloads(p, attachments, V)
+    for q in st.seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
+        q["group"] = next(g for g, d in enumerate(st.dirichlet) if d[0] is q["ids"])
+    sc.mesh_seqs = st.seqs
     return sc
 
 

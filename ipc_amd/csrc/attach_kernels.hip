@@ -151,7 +151,7 @@ void launch_attach_energy(const AttachView& v, double coef, double* partial, dou
 {
     const int nb = attach_energy_blocks(v);
     hipLaunchKernelGGL(k_attach_energy, dim3(nb), dim3(ATTACH_BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_attach_energy_per_elem(const AttachView& v, double* perAttach, hipStream_t s)
 {

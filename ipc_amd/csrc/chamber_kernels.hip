@@ -218,13 +218,6 @@ __global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_state(ChamberView v, 
 constexpr int GAS_MAX = 8; // gas chambers per context (chamber_plan.h: CHAMBER_GAS_MAX)
 constexpr int GAS_DOT_BLOCKS = 128; // partial sums per dot product at the most
 
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x; // (lane 0 holds the sum)
-}
-
 // pass 1: one workgroup per slice, one lane per triangle of it
 __global__ __launch_bounds__(CHAMBER_BLOCK) void k_chamber_gas_slice(ChamberView v, ChamberGasView g)
 {
@@ -413,7 +406,7 @@ void launch_chamber_energy(const ChamberView& v, double coef, double* partial, d
 {
     const int nb = chamber_energy_blocks(v);
     hipLaunchKernelGGL(k_chamber_energy, dim3(nb), dim3(CHAMBER_BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_chamber_energy_per_elem(const ChamberView& v, double* perTri, hipStream_t s)
 {

@@ -1,15 +1,20 @@
-// What the element-parallel kernels of the codimensional energies (shell_kernels.hip, shell_limit_kernels.hip, rod_kernels.hip) share: the Dirichlet
-// projection rule, the scatter of 3 x 3 blocks into the upper CSR through the row lookup of the contact stencils, the fixed-order block sum of the energy
-// kernels and the launch of their reduction.  For .hip files only.
+// The atomic scatter of 3 x 3 blocks into the upper CSR through the row lookup of the contact stencils, for the element-parallel kernels of the codimensional
+// energies (shell_kernels, shell_limit_kernels, shell_rubber_kernels, rod_kernels, attach_kernels, chamber_kernels).  Those units take everything else they share
+// -- the Dirichlet projection rule, the fixed-order reductions and their launch, nblk, block_row_off -- from device_prims.h through this header.  For .hip files only.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "device_prims.h"
 
 namespace ipcgpu {
 namespace scatter {
 
-inline int nblk(int n, int block) { return (n + block - 1) / block; }
-
-__device__ __forceinline__ bool projected_dbc(int type, int projectDBC) { return type == 1 || (type == 2 && projectDBC); }
+using prims::block_row_off;
+using prims::block_sum;
+using prims::launch_reduce_partials;
+using prims::nblk;
+using prims::projected_dbc;
+using prims::store_block_sum;
+using prims::wave_max;
+using prims::wave_sum;
 
 __device__ __forceinline__ void ld3(const double* __restrict__ x, int v, double* p)
 {
@@ -18,7 +23,6 @@ __device__ __forceinline__ void ld3(const double* __restrict__ x, int v, double*
     p[2] = x[3 * (size_t)v + 2];
 }
 
-// ---- scatter into the upper CSR (block rows of LinSysSolver.hpp:63-111: row 3 v has rowLen entries, 3 v + 1 one less, 3 v + 2 two less) -----------------------
 struct CsrSink {
     const int* rowBase;
     const int* rowLen;
@@ -56,51 +60,10 @@ __device__ __forceinline__ void add_off(const CsrSink& k, int nk, int nl, const 
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        const int p = lo + (r == 0 ? 0 : (r == 1 ? Lr - 1 : 2 * Lr - 3));
+        const int p = lo + block_row_off(r, Lr);
 #pragma unroll
         for (int c = 0; c < 3; ++c) atomicAdd(&k.a[p + c], swap ? A[c + 3 * r] : A[r + 3 * c]);
     }
-}
-
-// sum over the workgroup of BLOCK lanes, valid in lane 0; fixed-order tree: deterministic.  sm: BLOCK / 64 doubles of LDS
-template <int BLOCK>
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < BLOCK / 64; ++i) r += sm[i];
-    }
-    return r;
-}
-
-// the tail of an energy kernel: partial[blockIdx.x] = the sum of e over the workgroup
-template <int BLOCK>
-__device__ __forceinline__ void store_block_sum(double e, double* __restrict__ partial)
-{
-    __shared__ double sm[BLOCK / 64];
-    const double r = block_sum<BLOCK>(e, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-// out[0] = (accumulate ? out[0] : 0) + sum of the n partial sums, one workgroup of BLOCK lanes, fixed order
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double* __restrict__ partial, int n, int accumulate, double* __restrict__ out)
-{
-    __shared__ double sm[BLOCK / 64];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
-    const double r = block_sum<BLOCK>(x, sm);
-    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + r : r;
-}
-
-inline void launch_reduce_partials(const double* partial, int n, bool accumulate, double* out, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_reduce_partials<256>, dim3(1), dim3(256), 0, s, partial, n, accumulate ? 1 : 0, out);
 }
 
 } // namespace scatter

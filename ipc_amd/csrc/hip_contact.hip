@@ -4,6 +4,7 @@
 #include "contact_device.h"
 #include "contact_report_plan.h"
 #include "halfspace_device.h"
+#include "device_prims.h"
 #include "stencil_hessian_device.h"
 #include "orient3d_exact.h"
 #include "hip_ipc.h"
@@ -19,6 +20,7 @@ namespace ipcgpu {
 namespace {
 
 using namespace cdev;
+using namespace prims;
 constexpr int BLOCK = 256;
 
 struct ContactView {
@@ -108,20 +110,6 @@ __device__ __forceinline__ double dist_only(int kind, const double (*X)[3])
     default: return d_EE(X[0], X[1], X[2], X[3]);
     }
 }
-__device__ __forceinline__ bool projected_dbc(int type, int projectDBC) { return type == 1 || (type == 2 && projectDBC); }
-
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < BLOCK / 64; ++i) r += sm[i];
-    return r;
-}
 
 // sum mult b(d) + sum e b(d)   (Optimizer.cpp:3252-3353), fixed-order reduction
 __global__ __launch_bounds__(BLOCK) void k_contact_energy(ContactView cv, double dHat, double* __restrict__ partial)
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(BLOCK) void k_contact_energy(ContactView cv, double
         mollifier(cross_sqnorm(XE[0], XE[1], XE[2], XE[3]), eps_x_of(cv.xRest, en[0], en[1], en[2], en[3]), &e, &eg, &eH);
         val = b * e;
     }
-    const double r = block_sum(val, sm);
+    const double r = block_sum<BLOCK>(val, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 // pubWords > 0: the block also copies pubWords 32-bit words pubSrc -> pubDst (mapped host memory) once its own result is written -- the read-back of a batch
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_scaled(const double* __restric
     __shared__ double sm[BLOCK / 64];
     double x = 0.0;
     for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
-    const double r = block_sum(x, sm);
+    const double r = block_sum<BLOCK>(x, sm);
     if (threadIdx.x == 0) out[0] = scale * r;
     if (pubWords > 0) {
         __threadfence();
@@ -207,27 +195,43 @@ __device__ __forceinline__ void sink_key_block(const BlockSink& k, size_t slot, 
     k.rowNode[slot] = rowNode;
     atomicAdd(k.count + p0 / 3, 1);
 }
+// How the counting sort reads its scan: the bucket of a key and where a bucket starts.  ScatterStarts: the scatter's int scan, bucket = key / div (1: nodes,
+// 3: CSR positions); ReportStarts: the contact report's packed 64-bit scan (ReportScanIn below), records before the key in the low word, bucket = key.
+__device__ __forceinline__ int cr_lo(unsigned long long s) { return (int)(s & 0xFFFFFFFFull); }
+__device__ __forceinline__ int cr_hi(unsigned long long s) { return (int)(s >> 32); }
+struct ScatterStarts {
+    const int* __restrict__ start;
+    int div;
+    __device__ __forceinline__ int bucket(unsigned key) const { return (int)(key / (unsigned)div); }
+    __device__ __forceinline__ int at(int b) const { return start[b]; }
+};
+struct ReportStarts {
+    const unsigned long long* __restrict__ start;
+    __device__ __forceinline__ int bucket(unsigned key) const { return (int)key; }
+    __device__ __forceinline__ int at(int b) const { return cr_lo(start[b]); }
+};
 // one thread per slot: its place in the bucket of its key
-__global__ __launch_bounds__(BLOCK) void k_det_fill(int n, const unsigned* __restrict__ keys, int div, const int* __restrict__ start, int* __restrict__ count,
-    int* __restrict__ seg)
+template <class Starts>
+__global__ __launch_bounds__(BLOCK) void k_det_fill(int n, const unsigned* __restrict__ keys, Starts st, int* __restrict__ count, int* __restrict__ seg)
 {
     const int t = blockIdx.x * BLOCK + threadIdx.x;
     if (t >= n) return;
     const unsigned key = keys[t];
     if (key == KEY_NONE) return;
-    const int b = (int)(key / (unsigned)div);
-    seg[start[b] + atomicSub(count + b, 1) - 1] = t;
+    const int b = st.bucket(key);
+    seg[st.at(b) + atomicSub(count + b, 1) - 1] = t;
 }
 // one thread per bucket ENTRY: its rank among the slot indices of its bucket (a few tens of independent loads that hit the cache; one thread per bucket
 // insertion-sorting in place was a chain of dependent global loads -- 0.12 ms for the fullest nodes), the bucket in ascending slot order into `sorted`
-__global__ __launch_bounds__(BLOCK) void k_det_rank(int n, const unsigned* __restrict__ keys, int div, const int* __restrict__ start, int nKeys,
-    const int* __restrict__ seg, int* __restrict__ sorted)
+template <class Starts>
+__global__ __launch_bounds__(BLOCK) void k_det_rank(int n, const unsigned* __restrict__ keys, Starts st, int nKeys, const int* __restrict__ seg,
+    int* __restrict__ sorted)
 {
     const int u = blockIdx.x * BLOCK + threadIdx.x;
-    if (u >= n || u >= start[nKeys]) return;
+    if (u >= n || u >= st.at(nKeys)) return;
     const int slot = seg[u];
-    const int b = (int)(keys[slot] / (unsigned)div);
-    const int s0 = start[b], s1 = start[b + 1];
+    const int b = st.bucket(keys[slot]);
+    const int s0 = st.at(b), s1 = st.at(b + 1);
     int rank = 0;
     for (int w = s0; w < s1; ++w) rank += seg[w] < slot ? 1 : 0;
     sorted[s0 + rank] = slot;
@@ -281,7 +285,7 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_sum_blocks(int nKeys, const in
     else {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-            const int rowOff = (r == 0) ? 0 : (r == 1 ? (L - 1) : (2 * L - 3));
+            const int rowOff = block_row_off(r, L);
 #pragma unroll
             for (int c = 0; c < 3; ++c) a[p0 + rowOff + c] += S[r + 3 * c];
         }
@@ -384,15 +388,7 @@ struct CsrView {
 // position of column 3*cn in row 3*rn of the upper CSR (cn > rn), -1 if absent
 __device__ __forceinline__ int find_block(const CsrView& m, int rn, int cn)
 {
-    int lo = m.ia[3 * rn] + 3, hi = m.ia[3 * rn + 1]; // neighbour blocks start behind the 3 diagonal-block entries
-    const int target = 3 * cn;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int c = m.ja[mid];
-        if (c < target) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < m.ia[3 * rn + 1] && m.ja[lo] == target) ? lo : -1;
+    return prims::find_block(m.ja, m.ia[3 * rn] + 3, m.ia[3 * rn + 1], cn);
 }
 // does the CSR pattern hold a block for every node pair the barrier Hessian of the current sets will write?  (flag |= 1 if not)
 __global__ void k_pattern_check(ContactView cv, CsrView m, int* __restrict__ flag)
@@ -743,7 +739,7 @@ __global__ __launch_bounds__(BLOCK) void k_friction_energy(FrictionView fv, cons
         const double x2 = u[0] * u[0] + u[1] * u[1], eps = sqrt(eps2);
         val = fv.lambda[i] * ((x2 > eps2) ? sqrt(x2) : (x2 * (-sqrt(x2) / 3.0 + eps) / (eps * eps) + eps / 3.0)); // f0_SF_C1
     }
-    const double r = block_sum(val, sm);
+    const double r = block_sum<BLOCK>(val, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 __global__ __launch_bounds__(BLOCK) void k_friction_gradient(FrictionView fv, const double* __restrict__ x, const double* __restrict__ xt, double eps2,
@@ -849,7 +845,7 @@ __device__ __forceinline__ bool block_box(double* lo, double* hi, double& r)
     __shared__ double sm[6][BLOCK / 64];
     for (int c = 0; c < 3; ++c) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) { // (wave_min and wave_max of device_prims.h in one loop: the two trees interleave)
             lo[c] = fmin(lo[c], __shfl_down(lo[c], off, 64));
             hi[c] = fmax(hi[c], __shfl_down(hi[c], off, 64));
         }
@@ -1724,8 +1720,7 @@ __device__ __forceinline__ void ref_pair(int kind, const int* node, unsigned lon
 }
 __device__ __forceinline__ void wave_count_add(int v, int* __restrict__ counter) // every lane of the wave must call it
 {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    v = wave_sum_all(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
 }
 __global__ __launch_bounds__(BLOCK) void k_ref_sweep_vertex(int nSVI, const int* __restrict__ SVI, const int* __restrict__ SF, const int* __restrict__ SFE,
@@ -2240,8 +2235,6 @@ __global__ void k_close_stencils(int n, const int* __restrict__ ids, const doubl
     }
 }
 
-inline int nblk(long long n, int b = BLOCK) { return (int)((n + b - 1) / b); }
-
 } // namespace
 
 void HipContact::setSurface(const HipMesh& mesh, int nSF_, const int* SFc, int nCE, const int* CE)
@@ -2342,7 +2335,7 @@ void HipContact::setGroups(int nV, const std::vector<int>& words, const std::vec
 const int* HipContact::pairFlags(int nV, const int* dbc_dev)
 {
     d_pairFlags.ensure((size_t)std::max(nV, 1));
-    hipLaunchKernelGGL(k_pair_flags, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dbc_dev, hasObstacle ? d_obst.p : (const int*)nullptr, obstacleOnly ? 1 : 0,
+    hipLaunchKernelGGL(k_pair_flags, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, dbc_dev, hasObstacle ? d_obst.p : (const int*)nullptr, obstacleOnly ? 1 : 0,
         hasGroups ? (const int*)d_groupWord.p : nullptr, d_pairFlags.p);
     return d_pairFlags.p;
 }
@@ -2420,7 +2413,7 @@ Grid HipContact::gridOverBox(double h, long long& nCells) const { return layGrid
 
 void HipContact::measureBox(int nV, const double* x_dev)
 {
-    const int nb = nblk(nV);
+    const int nb = nblk(nV, BLOCK);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
     hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
@@ -2445,7 +2438,7 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     // build measured (padded by two cells).  Only the first build of a surface waits for its own box.  (Round 6: one synchronisation per build less; the second --
     // the total number of cell entries -- went the same way: the fill pass writes into the capacity the last build needed and the total comes back with the counts.)
     if (!haveBox_) measureBox(nV, x_dev);
-    const int nb = nblk(nV);
+    const int nb = nblk(nV, BLOCK);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
     counters_.alloc(16);
@@ -2483,15 +2476,15 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
         counters_.zero(stream);
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
         hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
-        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 0, capItems, stale,
+        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 0, capItems, stale,
             gridCount, (const int*)nullptr, (int*)nullptr);
         exclusiveSum(gridCount, gridStart_.p, (int)nC2);
-        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 1, capItems, stale,
+        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 1, capItems, stale,
             gridCount, gridStart_.p, gridItems_.p);
         gridCount_.done();
-        hipLaunchKernelGGL(k_narrow_pt, dim3(nblk(COOP * nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, pf, g, cellStartT, gridItems_.p,
+        hipLaunchKernelGGL(k_narrow_pt, dim3(nblk(COOP * nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, pf, g, cellStartT, gridItems_.p,
             dHat, capPT, outPT_.p, counters_.p, capItems, stale, bucketCount);
-        hipLaunchKernelGGL(k_narrow_ee_cells, dim3((int)std::min<long long>(nblk(64 * nCells), 4096)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, d_xRest.p, pf, g, (int)nCells, cellStartE,
+        hipLaunchKernelGGL(k_narrow_ee_cells, dim3((int)std::min<long long>(nblk(64 * nCells, BLOCK), 4096)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, d_xRest.p, pf, g, (int)nCells, cellStartE,
             gridItems_.p, dHat, infl, capEE, outEE_.p, counters_.p + 1, capItems, stale, bucketCount + nSVI);
         // the buckets of the record sort: needed only when the build stands, enqueued before the host knows (one scan; the GPU would idle through the read-back)
         exclusiveSum(bucketCount, bucketStart_.p, nB + 1);
@@ -2531,10 +2524,10 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     flags_.ensure((size_t)n + 1);
     flagPos_.ensure((size_t)n + 1);
     // by (svI, sfI) and (eI, eJ) -- the order a serial scan emits --, the point-triangle records first
-    hipLaunchKernelGGL(k_bucket_fill, dim3(nblk(n)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, outPT_.p, outEE_.p, bucketStart_.p, bucketCount,
+    hipLaunchKernelGGL(k_bucket_fill, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, outPT_.p, outEE_.p, bucketStart_.p, bucketCount,
         reinterpret_cast<int2*>(bucketSeg_.p));
     bucketCount_.done();
-    hipLaunchKernelGGL(k_bucket_rank_classify, dim3(nblk(n + 1)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, nV, bucketStart_.p,
+    hipLaunchKernelGGL(k_bucket_rank_classify, dim3(nblk(n + 1, BLOCK)), dim3(BLOCK), 0, stream, nPT, nEE, nSVI, nV, bucketStart_.p,
         reinterpret_cast<const int2*>(bucketSeg_.p), outPT_.p, outEE_.p, permPT_.p, d_csPTEE.p, flags_.p, dupCount);
     const int* permPT = permPT_.p;
     const int* permEE = permPT_.p + nPT;
@@ -2548,15 +2541,15 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     d_paraEIEJ.ensure(2 * (size_t)n);
     dupTuple_.ensure(4 * (size_t)n);
     dupSorted_.ensure(4 * (size_t)n);
-    hipLaunchKernelGGL(k_scatter_sets, dim3(nblk(n)), dim3(BLOCK), 0, stream, nPT, nEE, nSFE, outPT_.p, permPT, outEE_.p, permEE, flagPos_.p,
+    hipLaunchKernelGGL(k_scatter_sets, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, nPT, nEE, nSFE, outPT_.p, permPT, outEE_.p, permEE, flagPos_.p,
         d_active.p, dupTuple_.p, dupStart_.p, dupCount, d_para.p, d_paraEIEJ.p, nV);
     dupCount_.done();
     // lexicographic order of (id0, id1, id2) = the map's: buckets by id0, each ordered by (id1, id2); one tuple per run, its multiplicity in the last slot
-    hipLaunchKernelGGL(k_dup_rank, dim3(nblk(n)), dim3(BLOCK), 0, stream, totalsDev, nV, dupStart_.p, reinterpret_cast<const int4*>(dupTuple_.p),
+    hipLaunchKernelGGL(k_dup_rank, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, totalsDev, nV, dupStart_.p, reinterpret_cast<const int4*>(dupTuple_.p),
         reinterpret_cast<int4*>(dupSorted_.p));
-    hipLaunchKernelGGL(k_dup_runs, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runs_.p);
+    hipLaunchKernelGGL(k_dup_runs, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runs_.p);
     exclusiveSum(runs_.p, runPos_.p, nV + 1);
-    hipLaunchKernelGGL(k_dup_emit, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, totalsDev, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runPos_.p,
+    hipLaunchKernelGGL(k_dup_emit, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, totalsDev, dupStart_.p, reinterpret_cast<const int4*>(dupSorted_.p), runPos_.p,
         reinterpret_cast<int4*>(d_active.p), rbDev);
     HIP_CHECK(hipStreamSynchronize(stream));
     const unsigned long long totals = rb->totals;
@@ -2603,7 +2596,7 @@ bool HipContact::energyEnqueue(const double* x_dev, double dHat, double kappa, D
     shardRange(nPara_, pB, pE);
     const int n = (aE - aB) + (pE - pB);
     ContactView cv{ aE - aB, pE - pB, d_active.p + 4 * (size_t)aB, d_para.p + 4 * (size_t)pB, d_paraEIEJ.p + 2 * (size_t)pB, d_SFE.p, x_dev, d_xRest.p };
-    const int nb = std::max(1, nblk(n));
+    const int nb = std::max(1, nblk(n, BLOCK));
     if (partial.n < (size_t)nb) partial.alloc(nb);
     if (n) hipLaunchKernelGGL(k_contact_energy, dim3(nb), dim3(BLOCK), 0, stream, cv, dHat, partial.p);
     const bool pub = pubWords > 0 && !(shardWorld > 1 && shardReduce); // (a sharded sum is complete only after the reduction below: the caller publishes)
@@ -2629,7 +2622,7 @@ void HipContact::evaluateTuples(const double* x_dev, int n, const int* tuples4, 
     if (n <= 0) return;
     tupleBuf_.upload(tuples4, 4 * (size_t)n, stream);
     tupleVal_.alloc((size_t)n);
-    hipLaunchKernelGGL(k_evaluate_tuples, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, tupleBuf_.p, x_dev, tupleVal_.p);
+    hipLaunchKernelGGL(k_evaluate_tuples, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, tupleBuf_.p, x_dev, tupleVal_.p);
     tupleVal_.download(val, (size_t)n, stream);
 }
 
@@ -2639,7 +2632,7 @@ void HipContact::jtMultiplyTuples(const double* x_dev, int nV, int n, const int*
     tupleBuf_.upload(tuples4, 4 * (size_t)n, stream);
     tupleVal_.upload(input, (size_t)n, stream);
     tupleOut_.upload(out_3nV, 3 * (size_t)nV, stream);
-    hipLaunchKernelGGL(k_jt_tuples, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, tupleBuf_.p, x_dev, tupleVal_.p, coef, tupleOut_.p);
+    hipLaunchKernelGGL(k_jt_tuples, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, tupleBuf_.p, x_dev, tupleVal_.p, coef, tupleOut_.p);
     tupleOut_.download(out_3nV, 3 * (size_t)nV, stream);
 }
 
@@ -2653,10 +2646,10 @@ void HipContact::gradientAdd(const double* x_dev, const int* dbc_dev, int nV, do
     if (n) {
         ContactView cv{ nA, nP, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, x_dev, d_xRest.p, need_dev };
         detBegin(8 * (size_t)n, 3, false, /*fillKeys=*/false, (size_t)nV); // the kernel writes every key
-        hipLaunchKernelGGL(k_contact_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, cv, dHat, kappa, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
+        hipLaunchKernelGGL(k_contact_gradient, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, dHat, kappa, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
         detReduce3(8 * (size_t)n, (size_t)nV, grad_dev);
     }
-    hipLaunchKernelGGL(k_zero_projected, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, dbc_dev, projectDBC, grad_dev);
+    hipLaunchKernelGGL(k_zero_projected, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, dbc_dev, projectDBC, grad_dev);
 }
 
 void HipContact::hessianAdd(const double* x_dev, const int* dbc_dev, const HipLinSysSolver& lin, double dHat, double kappa, int projectDBC,
@@ -2670,7 +2663,7 @@ void HipContact::hessianAdd(const double* x_dev, const int* dbc_dev, const HipLi
     counters_.alloc(16);
     counters_.zero(stream);
     hessPerm_.ensure((size_t)NBINS * (size_t)n);
-    hipLaunchKernelGGL(k_bin_stencils, dim3(nblk(n)), dim3(BLOCK), 0, stream, cv, counters_.p + 4, hessPerm_.p, n);
+    hipLaunchKernelGGL(k_bin_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, counters_.p + 4, hessPerm_.p, n);
     const size_t nSlots = (size_t)HSLOTS * (size_t)n;
     const size_t nKeys = lin.ja.size() / 3 + 1; // buckets of the block positions
     detBegin(nSlots, 9, true, /*fillKeys=*/false, nKeys); // the kernel writes every key
@@ -2706,7 +2699,7 @@ bool HipContact::patternCovers(const HipLinSysSolver& lin)
     CsrView m{ lin.d_ia.p, lin.d_ja.p };
     counters_.alloc(16);
     counters_.zero(stream);
-    hipLaunchKernelGGL(k_pattern_check, dim3(nblk(n)), dim3(BLOCK), 0, stream, cv, m, counters_.p);
+    hipLaunchKernelGGL(k_pattern_check, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, m, counters_.p);
     int miss = 0;
     counters_.download(&miss, 1, stream);
     return miss == 0;
@@ -2727,7 +2720,7 @@ void HipContact::frictionLagUpdate(const double* x_dev, double dHat, double kapp
     d_fricCoord.ensure(2 * (size_t)n);
     d_fricBasis.ensure(6 * (size_t)n);
     const bool scaled = hasObstacle && (fricScaleSelf != 1.0 || fricScaleObst != 1.0);
-    hipLaunchKernelGGL(k_friction_lag, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_fricSet.p, x_dev, dHat, kappa, scaled ? (const int*)d_obst.p : nullptr,
+    hipLaunchKernelGGL(k_friction_lag, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_fricSet.p, x_dev, dHat, kappa, scaled ? (const int*)d_obst.p : nullptr,
         fricScaleSelf, fricScaleObst, hasGroups ? (const int*)d_groupWord.p : nullptr, hasGroups ? (const double*)d_groupScale.p : nullptr, d_fricLambda.p,
         d_fricCoord.p, d_fricBasis.p);
 }
@@ -2746,7 +2739,7 @@ double HipContact::frictionEnergy(const double* x_dev, const double* xt_dev, dou
     const int n = (int)fricSet.size();
     if (!n) return 0.0;
     FrictionView fv{ n, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
-    const int nb = nblk(n);
+    const int nb = nblk(n, BLOCK);
     if (partial.n < (size_t)nb) partial.alloc(nb);
     hipLaunchKernelGGL(k_friction_energy, dim3(nb), dim3(BLOCK), 0, stream, fv, x_dev, xt_dev, eps2, partial.p);
     hipLaunchKernelGGL(k_reduce_scaled, dim3(1), dim3(BLOCK), 0, stream, partial.p, nb, coef, scalar_dev, (const unsigned*)nullptr, (unsigned*)nullptr, 0);
@@ -2772,19 +2765,19 @@ void HipContact::detBegin(size_t nSlots, int valsPerSlot, bool withRow, bool fil
 void HipContact::detBuckets(size_t nSlots, size_t nKeys, int div)
 {
     exclusiveSum(detCount_.buf.p, detStart_.p, (int)nKeys + 1);
-    hipLaunchKernelGGL(k_det_fill, dim3(nblk((int)nSlots)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, div, detStart_.p, detCount_.buf.p, detSeg_.p);
+    hipLaunchKernelGGL(k_det_fill<ScatterStarts>, dim3(nblk((int)nSlots, BLOCK)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, ScatterStarts{ detStart_.p, div }, detCount_.buf.p, detSeg_.p);
     detCount_.done();
-    hipLaunchKernelGGL(k_det_rank, dim3(nblk((int)nSlots)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, div, detStart_.p, (int)nKeys, detSeg_.p, detSorted_.p);
+    hipLaunchKernelGGL(k_det_rank<ScatterStarts>, dim3(nblk((int)nSlots, BLOCK)), dim3(BLOCK), 0, stream, (int)nSlots, detKey_.p, ScatterStarts{ detStart_.p, div }, (int)nKeys, detSeg_.p, detSorted_.p);
 }
 void HipContact::detReduce3(size_t nSlots, size_t nKeys, double* grad_dev)
 {
     detBuckets(nSlots, nKeys, 1);
-    hipLaunchKernelGGL(k_bucket_sum3, dim3(nblk((int)nKeys)), dim3(BLOCK), 0, stream, (int)nKeys, detStart_.p, detSorted_.p, detVals_.p, grad_dev);
+    hipLaunchKernelGGL(k_bucket_sum3, dim3(nblk((int)nKeys, BLOCK)), dim3(BLOCK), 0, stream, (int)nKeys, detStart_.p, detSorted_.p, detVals_.p, grad_dev);
 }
 void HipContact::detReduceBlocks(size_t nSlots, size_t nKeys, const int* ia_dev, double* a_dev)
 {
     detBuckets(nSlots, nKeys, 3);
-    hipLaunchKernelGGL(k_bucket_sum_blocks, dim3(nblk((int)nKeys)), dim3(BLOCK), 0, stream, (int)nKeys, detStart_.p, detSorted_.p, detKey_.p, detVals_.p, detRow_.p,
+    hipLaunchKernelGGL(k_bucket_sum_blocks, dim3(nblk((int)nKeys, BLOCK)), dim3(BLOCK), 0, stream, (int)nKeys, detStart_.p, detSorted_.p, detKey_.p, detVals_.p, detRow_.p,
         ia_dev, a_dev);
 }
 
@@ -2794,7 +2787,7 @@ void HipContact::frictionGradientAdd(const double* x_dev, const double* xt_dev, 
     if (!n) return;
     FrictionView fv{ n, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
     detBegin(8 * (size_t)n, 3, false, true, d_xRest.n / 3); // (d_xRest: three rest coordinates per node)
-    hipLaunchKernelGGL(k_friction_gradient, dim3(nblk(n)), dim3(BLOCK), 0, stream, fv, x_dev, xt_dev, eps2, coef, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
+    hipLaunchKernelGGL(k_friction_gradient, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, fv, x_dev, xt_dev, eps2, coef, GradSink{ detVals_.p, detKey_.p, detCount_.buf.p });
     detReduce3(8 * (size_t)n, d_xRest.n / 3, grad_dev);
 }
 
@@ -2809,7 +2802,7 @@ void HipContact::frictionHessianAdd(const double* x_dev, const double* xt_dev, c
     counters_.zero(stream);
     const size_t nKeys = lin.ja.size() / 3 + 1;
     detBegin(16 * (size_t)n, 9, true, true, nKeys);
-    hipLaunchKernelGGL(k_friction_hessian, dim3(nblk(n)), dim3(BLOCK), 0, stream, fv, m, x_dev, xt_dev, dbc_dev, projectDBC, eps2, coef,
+    hipLaunchKernelGGL(k_friction_hessian, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, fv, m, x_dev, xt_dev, dbc_dev, projectDBC, eps2, coef,
         BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.buf.p }, counters_.p);
     detReduceBlocks(16 * (size_t)n, nKeys, lin.d_ia.p, a_dev);
     int err[2];
@@ -2874,7 +2867,7 @@ void HipContact::candidateConnectivitySorted(std::vector<std::pair<int, int>>& p
     const size_t m = 4 * (size_t)n;
     sortKeyIn_.ensure(m + 1);
     sortKeyOut_.ensure(m + 1);
-    hipLaunchKernelGGL(k_cand_pair_keys, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, sortKeyIn_.p);
+    hipLaunchKernelGGL(k_cand_pair_keys, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, sortKeyIn_.p);
     {
         size_t bytes = 0;
         hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, sortKeyIn_.p, sortKeyOut_.p, (int)m, 0, 64, stream);
@@ -2980,8 +2973,7 @@ __global__ void k_max_speed(int n, const int* __restrict__ ids, const double* __
         const int v = ids ? ids[i] : i;
         s = sqrt(p[3 * (size_t)v] * p[3 * (size_t)v] + p[3 * (size_t)v + 1] * p[3 * (size_t)v + 1] + p[3 * (size_t)v + 2] * p[3 * (size_t)v + 2]);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s = fmax(s, __shfl_down(s, off, 64));
+    s = wave_max(s);
     if ((threadIdx.x & 63) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(s));
 }
 } // namespace
@@ -2990,7 +2982,7 @@ double HipContact::maxSurfaceSpeed(const double* p_dev)
 {
     ccdOut_.alloc(4);
     ccdOut_.zero(stream);
-    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p);
+    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p);
     unsigned long long bits = 0;
     HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -3003,7 +2995,7 @@ double HipContact::maxSurfaceSpeed(const double* p_dev)
 Grid HipContact::makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells)
 {
     const int nV = mesh.nV;
-    const int nb = nblk(nV);
+    const int nb = nblk(nV, BLOCK);
     bboxPartial_.ensure(6 * (size_t)nb);
     hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
     std::vector<double> part(6 * (size_t)nb);
@@ -3017,7 +3009,7 @@ Grid HipContact::makeGrid(const HipMesh& mesh, const double* x_dev, const double
     // swept boxes reach at most alpha * max |p| beyond the current bounding box
     ccdOut_.alloc(4);
     ccdOut_.zero(stream);
-    hipLaunchKernelGGL(k_max_speed, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, (const int*)nullptr, p_dev, ccdOut_.p);
+    hipLaunchKernelGGL(k_max_speed, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, (const int*)nullptr, p_dev, ccdOut_.p);
     unsigned long long bits = 0;
     HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -3039,7 +3031,7 @@ void HipContact::buildCells(const Grid& g, long long nCells, int nPrim, int nv, 
     start.ensure((size_t)nCells + 1);
     auto insert = [&](int mode) {
         cnt.zeroN((size_t)nCells + 1, stream);
-        hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrim)), dim3(BLOCK), 0, stream, nPrim, nv, prim, x_dev, p_dev, alpha, g, mode, cnt.p, start.p,
+        hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrim, BLOCK)), dim3(BLOCK), 0, stream, nPrim, nv, prim, x_dev, p_dev, alpha, g, mode, cnt.p, start.p,
             items.p);
     };
     insert(0);
@@ -3078,7 +3070,7 @@ double HipContact::ccdPartial(const double* x_dev, const double* p_dev, double s
     HIP_CHECK(hipMemcpyAsync(ccdOut_.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
     CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
     for (int pass = 0; pass < 2; ++pass)
-        hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
+        hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
             o, (const unsigned long long*)nullptr);
     unsigned long long h[2];
     HIP_CHECK(hipMemcpyAsync(h, ccdOut_.p, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -3100,9 +3092,9 @@ void HipContact::stepBounds(const double* x_dev, const double* p_dev, double sla
     const int n = nCand_;
     CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
     for (int pass = 0; pass < 2 && n; ++pass)
-        hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
+        hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
             o, (const unsigned long long*)(ccdOut_.p + 3));
-    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p + 2);
+    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p + 2);
     hipLaunchKernelGGL(k_publish_u64x4, dim3(1), dim3(4), 0, stream, (const unsigned long long*)ccdOut_.p, readback_.dev);
     HIP_CHECK(hipStreamSynchronize(stream));
     const unsigned long long* h = readback_.p;
@@ -3128,9 +3120,9 @@ double HipContact::ccdFull(const HipMesh& mesh, const double* x_dev, const doubl
     counters_.zero(stream);
     CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
     for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(k_ccd_full_pt, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, p_dev, pf, g, cellStartT_.p,
+        hipLaunchKernelGGL(k_ccd_full_pt, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, p_dev, pf, g, cellStartT_.p,
             cellItemsT_.p, stepSize, slackness, pass, o, counters_.p);
-        hipLaunchKernelGGL(k_ccd_full_ee, dim3(nblk(nSFE)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, g, cellStartE_.p, cellItemsE_.p,
+        hipLaunchKernelGGL(k_ccd_full_ee, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, g, cellStartE_.p, cellItemsE_.p,
             stepSize, slackness, pass, o, counters_.p);
     }
     unsigned long long h[2];
@@ -3154,7 +3146,7 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     const int* pf = pairFlags(mesh.nV, dbc_dev);
     // the cap (SpatialHash.hpp:603-618): mean |component| of p over the surface nodes against the cell size; corner and extent (:620-634): all nodes now, the
     // surface nodes at the capped step -- all on the device, ONE read-back (k_ref_cap, k_ref_bbox_swept_dev, k_ref_box_final)
-    const int nbS = nblk(nSVI), nbV = nblk(mesh.nV);
+    const int nbS = nblk(nSVI, BLOCK), nbV = nblk(mesh.nV, BLOCK);
     const size_t offAbs = 0, offBoxV = 2 * (size_t)nbS, offBoxS = offBoxV + 6 * (size_t)nbV, offOut = offBoxS + 6 * (size_t)nbS;
     bboxPartial_.ensure(offOut + 8);
     double* outDev = bboxPartial_.p + offOut;
@@ -3213,7 +3205,7 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     const int* prims[3] = { d_SVI.p, d_SFE.p, d_SF.p };
     for (int q = 0; q < 3; ++q)
         if (nPrims[q])
-            hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q])), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 0,
+            hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q], BLOCK)), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 0,
                 refCount + q * nC1, (const int*)nullptr, (int*)nullptr);
     exclusiveSum(refCount, refStart_.p, (int)(3 * nC1));
     readbackInit();
@@ -3223,7 +3215,7 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     refItems_.ensure((size_t)REC * std::max(1, totalItems));
     for (int q = 0; q < 3; ++q)
         if (nPrims[q])
-            hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q])), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 1,
+            hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q], BLOCK)), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 1,
                 refCount + q * nC1, (const int*)(refStart_.p + q * nC1), refItems_.p);
     refCount_.done();
     ccdOut_.alloc(4);
@@ -3237,12 +3229,12 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     CcdOut o{ ccdOut_.p, ccdOut_.p + 1, twoPass ? nullptr : ccdHits_.p, counters_.p + 1, twoPass ? 0 : HIT_CAP };
     const RefLists L{ refStart_.p, refItems_.p, refStart_.p + nC1, refItems_.p, refStart_.p + 2 * nC1, refItems_.p };
     auto sweep = [&](int pass) {
-        hipLaunchKernelGGL(k_ref_sweep_vertex, dim3(nblk(SWEEP_COOP * (long long)nSVI)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, pf,
+        hipLaunchKernelGGL(k_ref_sweep_vertex, dim3(nblk(SWEEP_COOP * (long long)nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, pf,
             d_v2sv.p, refVbox_.p, g, L, alpha, slackness, pass, o, counters_.p);
         // the bound the vertex sweeps left is what the edge pairs' boxes are swept over (SelfCollisionHandler.cpp:1189, 1219)
         if (pass == 0) HIP_CHECK(hipMemcpyAsync(ccdOut_.p + 2, ccdOut_.p, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
         if (nSFE)
-            hipLaunchKernelGGL(k_ref_sweep_edge, dim3(nblk(SWEEP_COOP * (long long)nSFE)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, d_v2sv.p,
+            hipLaunchKernelGGL(k_ref_sweep_edge, dim3(nblk(SWEEP_COOP * (long long)nSFE, BLOCK)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, d_v2sv.p,
                 refVbox_.p, g, L.startE, L.itemsE, alpha, ccdOut_.p + 2, slackness, pass, o, counters_.p);
     };
     sweep(0);
@@ -3281,7 +3273,7 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
     const int* pf = pairFlags(mesh.nV, dbc_dev);
     auto pointsInTets = [&]() {
         if (codimPoints.empty() || !mesh.nT) return;
-        const dim3 grid(nblk((long long)codimPoints.size() * mesh.nT));
+        const dim3 grid(nblk((long long)codimPoints.size() * mesh.nT, BLOCK));
         if (exactPredicates)
             hipLaunchKernelGGL(k_points_in_tets<true>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
                 pf, counters_.p);
@@ -3303,7 +3295,7 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
     // entries, result).  Like the constraint-set build it now lays its grid over the box the LAST build or check measured (a stale grid is detected on the
     // device and nothing runs), fills the edge cells into the capacity the last pass needed, and reads flag + stale flag + total + the fresh box back at once.
     // Only the first build or check of a surface waits for its own box.
-    const int nV = mesh.nV, nb = nblk(nV);
+    const int nV = mesh.nV, nb = nblk(nV, BLOCK);
     if (!haveBox_) measureBox(nV, x_dev);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
@@ -3321,17 +3313,17 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
         hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
         // (edges only, in cells [0, nCells): the kernel's offset of the edge cells is its nCells argument)
-        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 0, capItems, stale,
+        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 0, capItems, stale,
             gridCount, (const int*)nullptr, (int*)nullptr);
         exclusiveSum(gridCount, gridStart_.p, (int)nCells + 1);
-        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 1, capItems, stale,
+        hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 1, capItems, stale,
             gridCount, gridStart_.p, gridItems_.p);
         gridCount_.done();
         if (exactPredicates)
-            hipLaunchKernelGGL(k_intersect<true>, dim3(nblk(COOP * (long long)nSF)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
+            hipLaunchKernelGGL(k_intersect<true>, dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
                 gridItems_.p, counters_.p, capItems);
         else
-            hipLaunchKernelGGL(k_intersect<false>, dim3(nblk(COOP * (long long)nSF)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
+            hipLaunchKernelGGL(k_intersect<false>, dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
                 gridItems_.p, counters_.p, capItems);
         pointsInTets();
         hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + nCells, box_dev, reinterpret_cast<BuildReadback*>(readback_.dev));
@@ -3368,11 +3360,11 @@ void HipContact::closeStencils(const double* x_dev, double dTol, std::vector<std
         closeVal_.ensure((size_t)cap);
         counters_.alloc(16);
         counters_.zero(stream);
-        if (n) hipLaunchKernelGGL(k_close_stencils, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_active.p, x_dev, dTol, cap, closeIdx_.p, closeVal_.p, counters_.p);
+        if (n) hipLaunchKernelGGL(k_close_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_active.p, x_dev, dTol, cap, closeIdx_.p, closeVal_.p, counters_.p);
         if (nCheck) {
             ContactView cv{ nActive_, nPara_, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, nullptr, d_xRest.p };
             CsrView m{ lin->d_ia.p, lin->d_ja.p };
-            hipLaunchKernelGGL(k_pattern_check, dim3(nblk(nCheck)), dim3(BLOCK), 0, stream, cv, m, counters_.p + 2);
+            hipLaunchKernelGGL(k_pattern_check, dim3(nblk(nCheck, BLOCK)), dim3(BLOCK), 0, stream, cv, m, counters_.p + 2);
         }
         hipLaunchKernelGGL(k_publish_u64x4, dim3(1), dim3(2), 0, stream, reinterpret_cast<const unsigned long long*>(counters_.p), readback_.dev); // counters 0 .. 3
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -3412,7 +3404,7 @@ void HipContact::evalStencils(const std::vector<std::array<int, 4>>& ids, const 
         for (int k = 0; k < 4; ++k) flat[4 * (size_t)i + k] = ids[i][k];
     d_ids_.uploadGrow(flat, stream);
     d_vals_.ensure(n);
-    hipLaunchKernelGGL(k_eval_stencils, dim3(nblk(n)), dim3(BLOCK), 0, stream, n, d_ids_.p, x_dev, d_vals_.p);
+    hipLaunchKernelGGL(k_eval_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_ids_.p, x_dev, d_vals_.p);
     d_vals_.download(d2.data(), n, stream);
 }
 
@@ -3611,30 +3603,6 @@ __global__ __launch_bounds__(BLOCK) void k_creport_friction(FrictionView fv, con
 struct ReportScanIn {
     __host__ __device__ unsigned long long operator()(int c) const { return c > 0 ? ((1ull << 32) | (unsigned)c) : 0ull; }
 };
-__device__ __forceinline__ int cr_lo(unsigned long long s) { return (int)(s & 0xFFFFFFFFull); }
-__device__ __forceinline__ int cr_hi(unsigned long long s) { return (int)(s >> 32); }
-__global__ __launch_bounds__(BLOCK) void k_creport_fill(int n, const unsigned* __restrict__ keys, const unsigned long long* __restrict__ start, int* __restrict__ count,
-    int* __restrict__ seg)
-{
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= n) return;
-    const unsigned key = keys[t];
-    if (key == KEY_NONE) return;
-    seg[cr_lo(start[key]) + atomicSub(count + key, 1) - 1] = t;
-}
-// k_det_rank over the packed starts: every bucket into ascending record order
-__global__ __launch_bounds__(BLOCK) void k_creport_rank(int n, const unsigned* __restrict__ keys, const unsigned long long* __restrict__ start, int nKeys,
-    const int* __restrict__ seg, int* __restrict__ sorted)
-{
-    const int u = blockIdx.x * BLOCK + threadIdx.x;
-    if (u >= n || u >= cr_lo(start[nKeys])) return;
-    const int rec = seg[u];
-    const unsigned b = keys[rec];
-    const int s0 = cr_lo(start[b]), s1 = cr_lo(start[b + 1]);
-    int rank = 0;
-    for (int w = s0; w < s1; ++w) rank += seg[w] < rec ? 1 : 0;
-    sorted[s0 + rank] = rec;
-}
 // out (mapped host memory): [0] rows, [1] contributing records, then key and accumulated end per row (at most maxRows of them fit)
 __global__ __launch_bounds__(BLOCK) void k_creport_publish(int nKeys, const unsigned long long* __restrict__ start, int maxRows, int* __restrict__ out)
 {
@@ -3664,12 +3632,6 @@ __device__ __forceinline__ void cr_wave_min(double& d, int& p, int& id)
             id = oi;
         }
     }
-}
-__device__ __forceinline__ double cr_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
 }
 // slices: int triples (row, begin, end) into `sorted`.  outD: CR_Q doubles per slice ([0]: the smallest d), outI: 8 ints per slice -- five counts, the
 // index of the tuple that attains the minimum (-1: none) and its position in `sorted`
@@ -3701,7 +3663,7 @@ __global__ __launch_bounds__(BLOCK) void k_creport_slices(int n, const int* __re
     }
 #pragma unroll
     for (int k = 1; k < CR_Q; ++k) {
-        const double r = cr_wave_sum(q[k]);
+        const double r = wave_sum(q[k]);
         if (lane == 0) sm[k][wv] = r;
     }
     double d = q[0];
@@ -3756,7 +3718,7 @@ __global__ __launch_bounds__(64) void k_creport_rows(const int* __restrict__ sli
     for (int k = 1; k < CR_Q; ++k) {
         double a = 0.0;
         for (int j = s0 + lane; j < s1; j += 64) a += sliceD[CR_Q * (size_t)j + k];
-        a = cr_wave_sum(a);
+        a = wave_sum(a);
         if (lane == 0) rowsD[CR_Q * (size_t)r + k] = a;
     }
     double d = INFINITY;
@@ -3778,8 +3740,7 @@ __global__ __launch_bounds__(64) void k_creport_rows(const int* __restrict__ sli
     for (int k = 0; k < 5; ++k) {
         int c = 0;
         for (int j = s0 + lane; j < s1; j += 64) c += sliceI[8 * (size_t)j + k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        c = wave_sum(c);
         if (lane == 0) rowsI[8 * (size_t)r + 2 + k] = c;
     }
 }
@@ -3832,19 +3793,19 @@ int HipContact::contactReport(const double* x_dev, int nV, const std::vector<int
 
     if (nA + nP) {
         const ContactView cv{ nA, nP, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, x_dev, d_xRest.p };
-        hipLaunchKernelGGL(k_creport_contact, dim3(nblk(nA + nP)), dim3(BLOCK), 0, stream, cv, dHat, kappa, o);
+        hipLaunchKernelGGL(k_creport_contact, dim3(nblk(nA + nP, BLOCK)), dim3(BLOCK), 0, stream, cv, dHat, kappa, o);
     }
     int r0 = nA + nP;
     for (int h = 0; h < nHalf; ++h) {
         const ReportPlane& pl = planes[h];
         if (pl.count)
-            hipLaunchKernelGGL(k_creport_halfspace, dim3(nblk(pl.count)), dim3(BLOCK), 0, stream, pl.count, pl.set_dev, x_dev,
+            hipLaunchKernelGGL(k_creport_halfspace, dim3(nblk(pl.count, BLOCK)), dim3(BLOCK), 0, stream, pl.count, pl.set_dev, x_dev,
                 hsdev::Plane{ pl.n[0], pl.n[1], pl.n[2], pl.D }, h, r0, dHat, kappa, o);
         r0 += pl.count;
     }
     if (nF) {
         const FrictionView fv{ nF, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
-        hipLaunchKernelGGL(k_creport_friction, dim3(nblk(nF)), dim3(BLOCK), 0, stream, fv, x_dev, w.xt.p, eps2, coef, r0, o);
+        hipLaunchKernelGGL(k_creport_friction, dim3(nblk(nF, BLOCK)), dim3(BLOCK), 0, stream, fv, x_dev, w.xt.p, eps2, coef, r0, o);
     }
     {
         hipcub::TransformInputIterator<unsigned long long, ReportScanIn, const int*> in(count, ReportScanIn());
@@ -3853,10 +3814,10 @@ int HipContact::contactReport(const double* x_dev, int nV, const std::vector<int
         if (w.scanTmp.n < bytes) w.scanTmp.alloc(bytes + bytes / 4);
         HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.scanTmp.p, bytes, in, w.start.p, nKeys + 1, stream));
     }
-    hipLaunchKernelGGL(k_creport_fill, dim3(nblk(nRec)), dim3(BLOCK), 0, stream, nRec, w.key.p, w.start.p, count, w.seg.p);
+    hipLaunchKernelGGL(k_det_fill<ReportStarts>, dim3(nblk(nRec, BLOCK)), dim3(BLOCK), 0, stream, nRec, w.key.p, ReportStarts{ w.start.p }, count, w.seg.p);
     w.count.done();
-    hipLaunchKernelGGL(k_creport_rank, dim3(nblk(nRec)), dim3(BLOCK), 0, stream, nRec, w.key.p, w.start.p, nKeys, w.seg.p, w.sorted.p);
-    hipLaunchKernelGGL(k_creport_publish, dim3(nblk(nKeys)), dim3(BLOCK), 0, stream, nKeys, w.start.p, maxRows, w.hostI.dev);
+    hipLaunchKernelGGL(k_det_rank<ReportStarts>, dim3(nblk(nRec, BLOCK)), dim3(BLOCK), 0, stream, nRec, w.key.p, ReportStarts{ w.start.p }, nKeys, w.seg.p, w.sorted.p);
+    hipLaunchKernelGGL(k_creport_publish, dim3(nblk(nKeys, BLOCK)), dim3(BLOCK), 0, stream, nKeys, w.start.p, maxRows, w.hostI.dev);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream)); // the one read-back: the rows present and where their records end
 

@@ -4,6 +4,7 @@
 #include "hip_halfspace.h"
 #include "contact_device.h"
 #include "halfspace_device.h"
+#include "device_prims.h"
 #include <cmath>
 #include <cstring>
 #include <hipcub/hipcub.hpp>
@@ -11,22 +12,10 @@
 namespace ipcgpu {
 namespace {
 constexpr int BLOCK = 256;
-inline int nblk(int n) { return (n + BLOCK - 1) / BLOCK; }
 
+using namespace prims;
 using hsdev::Plane;
 using hsdev::plane_dist;
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < BLOCK / 64; ++i) r += sm[i];
-    return r;
-}
 // order-preserving map double -> uint64 so that atomicMin works for either sign
 __device__ __forceinline__ unsigned long long ordered_bits(double v)
 {
@@ -63,16 +52,8 @@ __global__ __launch_bounds__(BLOCK) void k_hs_energy(int n, const int* __restric
         cdev::barrier(dist * dist, dHat, &b, &gb, &Hb);
         val = b;
     }
-    const double r = block_sum(val, sm);
+    const double r = block_sum<BLOCK>(val, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-__global__ __launch_bounds__(BLOCK) void k_hs_reduce(const double* __restrict__ partial, int n, double scale, double* __restrict__ out)
-{
-    __shared__ double sm[BLOCK / 64];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
-    const double r = block_sum(x, sm);
-    if (threadIdx.x == 0) out[0] = scale * r;
 }
 
 __global__ void k_hs_gradient(int n, const int* __restrict__ set, const double* __restrict__ x, Plane h, double dHat, double kappa,
@@ -123,8 +104,7 @@ __global__ void k_hs_step(int nSVI, const int* __restrict__ svi, const double* _
             if (coef < 0.0) best = -plane_dist(h, x, v) / coef * slackness;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) best = fmin(best, __shfl_down(best, off, 64));
+    best = wave_min(best);
     if ((threadIdx.x & 63) == 0) atomicMin(out, ordered_bits(best));
 }
 
@@ -134,8 +114,7 @@ __global__ void k_hs_move(int nSVI, const int* __restrict__ svi, const double* _
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     double best = 1.0;
     if (i < nSVI) best = -plane_dist(h, x, svi[i]) / coef * slackness;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) best = fmin(best, __shfl_down(best, off, 64));
+    best = wave_min(best);
     if ((threadIdx.x & 63) == 0) atomicMin(out, ordered_bits(best));
 }
 
@@ -185,7 +164,7 @@ __global__ __launch_bounds__(BLOCK) void k_hs_fric_energy(int n, const int* __re
         const double m2 = vp[0] * vp[0] + vp[1] * vp[1] + vp[2] * vp[2], eps = sqrt(eps2);
         val = (m2 > eps2) ? mu * lambda[i] * (sqrt(m2) - eps * 0.5) : mu * lambda[i] * m2 / eps * 0.5;
     }
-    const double r = block_sum(val, sm);
+    const double r = block_sum<BLOCK>(val, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 __global__ void k_hs_fric_gradient(int n, const int* __restrict__ set, const double* __restrict__ lambda, const double* __restrict__ x,
@@ -251,7 +230,7 @@ int HipHalfSpace::build(int nSVI, const int* svi_dev, const double* x_dev, const
     flags_.alloc(nSVI);
     d_set.alloc(nSVI);
     count_.alloc(1);
-    hipLaunchKernelGGL(k_hs_flags, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, dbc_dev, h, dHat, flags_.p);
+    hipLaunchKernelGGL(k_hs_flags, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, dbc_dev, h, dHat, flags_.p);
     size_t bytes = 0; // order-preserving compaction: the set comes out in ascending surface-vertex order like the reference's
     HIP_CHECK(hipcub::DeviceSelect::Flagged(nullptr, bytes, svi_dev, flags_.p, d_set.p, count_.p, nSVI, stream));
     if (tmp_.n < bytes) tmp_.alloc(bytes);
@@ -276,10 +255,10 @@ double HipHalfSpace::energy(const double* x_dev, double dHat, double kappa)
     const int cnt = (int)set.size();
     if (!cnt) return 0.0;
     const Plane h{ n[0], n[1], n[2], D };
-    const int nb = nblk(cnt);
+    const int nb = nblk(cnt, BLOCK);
     if (partial_.n < (size_t)nb + 1) partial_.alloc(nb + 1);
     hipLaunchKernelGGL(k_hs_energy, dim3(nb), dim3(BLOCK), 0, stream, cnt, d_set.p, x_dev, h, dHat, partial_.p + 1);
-    hipLaunchKernelGGL(k_hs_reduce, dim3(1), dim3(BLOCK), 0, stream, partial_.p + 1, nb, kappa, partial_.p);
+    launch_reduce_partials(partial_.p + 1, nb, kappa, false, partial_.p, stream);
     double out = 0.0;
     partial_.download(&out, 1, stream);
     return out;
@@ -290,7 +269,7 @@ void HipHalfSpace::gradientAdd(const double* x_dev, double dHat, double kappa, d
     const int cnt = (int)set.size();
     if (!cnt) return;
     const Plane h{ n[0], n[1], n[2], D };
-    hipLaunchKernelGGL(k_hs_gradient, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, d_set.p, x_dev, h, dHat, kappa, grad_dev);
+    hipLaunchKernelGGL(k_hs_gradient, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, d_set.p, x_dev, h, dHat, kappa, grad_dev);
 }
 
 void HipHalfSpace::hessianAdd(const double* x_dev, const int* dbc_dev, const int* rowBase_dev, const int* rowLen_dev, double dHat, double kappa,
@@ -299,7 +278,7 @@ void HipHalfSpace::hessianAdd(const double* x_dev, const int* dbc_dev, const int
     const int cnt = (int)set.size();
     if (!cnt) return;
     const Plane h{ n[0], n[1], n[2], D };
-    hipLaunchKernelGGL(k_hs_hessian, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, d_set.p, x_dev, dbc_dev, rowBase_dev, rowLen_dev, h, dHat, kappa,
+    hipLaunchKernelGGL(k_hs_hessian, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, d_set.p, x_dev, dbc_dev, rowBase_dev, rowLen_dev, h, dHat, kappa,
         projectDBC, a_dev);
 }
 
@@ -311,7 +290,7 @@ double HipHalfSpace::stepBound(int nSVI, const int* svi_dev, const double* x_dev
     minOut_.alloc(1);
     const unsigned long long init = ~0ull;
     HIP_CHECK(hipMemcpyAsync(minOut_.p, &init, sizeof(init), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_hs_step, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, dbc_dev, p_dev, h, slackness, minOut_.p);
+    hipLaunchKernelGGL(k_hs_step, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, dbc_dev, p_dev, h, slackness, minOut_.p);
     unsigned long long k = 0;
     minOut_.download(&k, 1, stream);
     return std::min(stepSize, from_ordered_bits(k));
@@ -326,7 +305,7 @@ double HipHalfSpace::move(int nSVI, const int* svi_dev, const double* x_dev, con
         minOut_.alloc(1);
         const unsigned long long init = ~0ull;
         HIP_CHECK(hipMemcpyAsync(minOut_.p, &init, sizeof(init), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_hs_move, dim3(nblk(nSVI)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, h, coef, slackness, minOut_.p);
+        hipLaunchKernelGGL(k_hs_move, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, svi_dev, x_dev, h, coef, slackness, minOut_.p);
         unsigned long long k = 0;
         minOut_.download(&k, 1, stream);
         stepSize = std::min(1.0, from_ordered_bits(k));
@@ -341,7 +320,7 @@ bool HipHalfSpace::intersected(int nV, const double* x_dev, const int* dbc_dev)
     const Plane h{ n[0], n[1], n[2], D };
     count_.alloc(1);
     count_.zero(stream);
-    hipLaunchKernelGGL(k_hs_intersected, dim3(nblk(nV)), dim3(BLOCK), 0, stream, nV, x_dev, dbc_dev, h, count_.p);
+    hipLaunchKernelGGL(k_hs_intersected, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, x_dev, dbc_dev, h, count_.p);
     int f = 0;
     count_.download(&f, 1, stream);
     return f != 0;
@@ -355,7 +334,7 @@ void HipHalfSpace::evalDist2(const std::vector<int>& verts, const double* x_dev,
     const Plane h{ n[0], n[1], n[2], D };
     ids_.upload(verts, stream);
     if (vals_.n < (size_t)cnt) vals_.alloc(cnt);
-    hipLaunchKernelGGL(k_hs_dist2, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, ids_.p, x_dev, h, vals_.p);
+    hipLaunchKernelGGL(k_hs_dist2, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, ids_.p, x_dev, h, vals_.p);
     vals_.download(d2.data(), cnt, stream);
 }
 
@@ -368,7 +347,7 @@ void HipHalfSpace::lagUpdate(const double* x_dev, double dHat, double kappa)
     d_lagSet.ensure(cnt);
     d_lagLambda.ensure(cnt);
     HIP_CHECK(hipMemcpyAsync(d_lagSet.p, d_set.p, cnt * sizeof(int), hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_hs_lag, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, x_dev, h, dHat, kappa, d_lagLambda.p);
+    hipLaunchKernelGGL(k_hs_lag, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, x_dev, h, dHat, kappa, d_lagLambda.p);
 }
 
 double HipHalfSpace::frictionEnergy(const double* x_dev, const double* xt_dev, double eps2)
@@ -376,10 +355,10 @@ double HipHalfSpace::frictionEnergy(const double* x_dev, const double* xt_dev, d
     const int cnt = (int)lagSet.size();
     if (!cnt) return 0.0;
     const Plane h{ n[0], n[1], n[2], D };
-    const int nb = nblk(cnt);
+    const int nb = nblk(cnt, BLOCK);
     if (partial_.n < (size_t)nb + 1) partial_.alloc(nb + 1);
     hipLaunchKernelGGL(k_hs_fric_energy, dim3(nb), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, d_lagLambda.p, x_dev, xt_dev, h, friction, eps2, partial_.p + 1);
-    hipLaunchKernelGGL(k_hs_reduce, dim3(1), dim3(BLOCK), 0, stream, partial_.p + 1, nb, 1.0, partial_.p);
+    launch_reduce_partials(partial_.p + 1, nb, 1.0, false, partial_.p, stream);
     double out = 0.0;
     partial_.download(&out, 1, stream);
     return out;
@@ -390,7 +369,7 @@ void HipHalfSpace::frictionGradientAdd(const double* x_dev, const double* xt_dev
     const int cnt = (int)lagSet.size();
     if (!cnt) return;
     const Plane h{ n[0], n[1], n[2], D };
-    hipLaunchKernelGGL(k_hs_fric_gradient, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, d_lagLambda.p, x_dev, xt_dev, h, friction, eps2, grad_dev);
+    hipLaunchKernelGGL(k_hs_fric_gradient, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, d_lagLambda.p, x_dev, xt_dev, h, friction, eps2, grad_dev);
 }
 
 void HipHalfSpace::frictionHessianAdd(const double* x_dev, const double* xt_dev, const int* dbc_dev, const int* rowBase_dev, const int* rowLen_dev,
@@ -399,7 +378,7 @@ void HipHalfSpace::frictionHessianAdd(const double* x_dev, const double* xt_dev,
     const int cnt = (int)lagSet.size();
     if (!cnt) return;
     const Plane h{ n[0], n[1], n[2], D };
-    hipLaunchKernelGGL(k_hs_fric_hessian, dim3(nblk(cnt)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, d_lagLambda.p, x_dev, xt_dev, dbc_dev, rowBase_dev,
+    hipLaunchKernelGGL(k_hs_fric_hessian, dim3(nblk(cnt, BLOCK)), dim3(BLOCK), 0, stream, cnt, d_lagSet.p, d_lagLambda.p, x_dev, xt_dev, dbc_dev, rowBase_dev,
         rowLen_dev, h, friction, eps2, projectDBC, a_dev);
 }
 

@@ -3,6 +3,7 @@
 // One lane owns one tetrahedron; see nh_kernels.hip for the reference line map.
 #pragma once
 #include "nh_kernels.h"
+#include "device_prims.h"
 
 namespace ipcgpu {
 namespace dev {
@@ -314,10 +315,7 @@ __device__ __forceinline__ void fcr_piola(const double F[9], const double U[9], 
         }
 }
 
-__device__ __forceinline__ bool projected_dbc(int type, int projectDBC)
-{
-    return type == 1 || (type == 2 && projectDBC); // Mesh.hpp:135-144
-}
+using prims::projected_dbc;
 
 // ------------------------------------------------------------------------------------------------
 // The element computation is split in two so that kernels can place a workgroup-level exchange between them:

@@ -24,6 +24,7 @@ namespace {
 constexpr int BLOCK = 256;
 
 using namespace dev;
+using namespace prims;
 
 // ------------------------------------------------------------------------------------------------
 // Tet-parallel assembly with hardware fp64 atomics (global_atomic_add_f64).  This is the simple path: it serves
@@ -54,7 +55,7 @@ struct GlobalAtomicSink {
         const int Lr = v.rowLen[vid[aFirst ? ka : kc]];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-            const int rowOff = (r == 0) ? 0 : (r == 1 ? (Lr - 1) : (2 * Lr - 3));
+            const int rowOff = block_row_off(r, Lr);
 #pragma unroll
             for (int c = 0; c < 3; ++c) atomicAdd(&a[p0 + rowOff + c], aFirst ? H[r][c] : H[c][r]);
         }
@@ -99,21 +100,6 @@ __global__ __launch_bounds__(BLOCK) void k_node_init(ElemView v, int projectDBC,
 }
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-    // fixed-order tree: deterministic
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < BLOCK / 64; ++i) r += sm[i];
-    }
-    return r;
-}
-
 __device__ __forceinline__ double nh_psi(const double F[9], double mu, double lam)
 {
     if (mu == 0.0 && lam == 0.0) return 0.0;
@@ -159,17 +145,8 @@ __global__ __launch_bounds__(BLOCK) void k_energy(ElemView v, double coef, int w
         }
         e += d2 * v.mass[gid] / 2.0; // Optimizer.cpp:3234
     }
-    double r = block_sum(e, sm);
+    double r = block_sum<BLOCK>(e, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double* __restrict__ partial, int n, double* __restrict__ out)
-{
-    __shared__ double sm[BLOCK / 64];
-    double x = 0.0;
-    for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
-    double r = block_sum(x, sm);
-    if (threadIdx.x == 0) out[0] = r;
 }
 
 template <bool SNH>
@@ -311,13 +288,6 @@ __global__ __launch_bounds__(BLOCK) void k_stress_nodes(int nV, int nT, const in
 //           slices come first) and writes one record of REPORT_Q partial sums -- an element slice only entry 0 of it
 //   pass 2  one wave per component sums the records of its slices: lane l takes slices l, l + 64, ... in index order, then the shuffle tree
 constexpr int REPORT_Q = 7; // E, M xyz, L xyz
-
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
 
 template <bool SNH>
 __global__ __launch_bounds__(BLOCK) void k_report_slices(ElemView v, const double* __restrict__ xStart, const int* __restrict__ slices, int nNodeSlices,
@@ -499,8 +469,7 @@ __global__ __launch_bounds__(BLOCK) void k_inversion_step(ElemView v, const doub
         }
     }
     // all results are >= 0, so their bit patterns order like unsigned integers
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) res = fmin(res, __shfl_down(res, off, 64));
+    res = wave_min(res);
     // the caller starts the minimum at 1e20 = "no element limits the step": waves without a root (almost all of them) have nothing to report,
     // and the ones that do are few -- same-address atomics retire one at a time (~2.5 ns each; one per wave was 5 us of this kernel)
     if ((threadIdx.x & 63) == 0 && res < 1e20) atomicMin(outMin, (unsigned long long)__double_as_longlong(res));
@@ -565,8 +534,7 @@ __global__ __launch_bounds__(BLOCK) void k_max_abs(int n, const double* __restri
     __shared__ double sm[BLOCK / 64];
     double m = 0.0;
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) m = fmax(m, fabs(v[i]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -752,7 +720,7 @@ __global__ __launch_bounds__(BLOCK) void k_nbc_energy(int n, const int* __restri
         const size_t v = (size_t)ids[t];
         if (dbc[v] == 0) acc += mass[v] * (x[3 * v] * cx + x[3 * v + 1] * cy + x[3 * v + 2] * cz);
     }
-    const double r = block_sum(acc, sm);
+    const double r = block_sum<BLOCK>(acc, sm);
     if (threadIdx.x == 0) out[0] = r;
 }
 
@@ -793,7 +761,7 @@ __global__ __launch_bounds__(BLOCK) void k_mdbc_reduce(int n, const int* __restr
         }
         acc += mode == 0 ? (rho / 2.0 * mass[v] * sq - sqrt(mass[v]) * dot) : sq;
     }
-    const double r = block_sum(acc, sm);
+    const double r = block_sum<BLOCK>(acc, sm);
     if (threadIdx.x == 0) out[0] = r;
 }
 // ---- lagged stiffness-proportional damping (Optimizer.cpp:3381-3400, 3519-3540, 3707-3709, 3723-3735) -----------------------
@@ -824,7 +792,7 @@ __global__ __launch_bounds__(BLOCK) void k_dot_scaled(int n, const double* __res
     __shared__ double sm[BLOCK / 64];
     double acc = 0.0;
     for (int t = threadIdx.x; t < n; t += BLOCK) acc += x[t] * y[t];
-    const double r = block_sum(acc, sm);
+    const double r = block_sum<BLOCK>(acc, sm);
     if (threadIdx.x == 0) out[0] = scale * r;
 }
 // g . e and g . g in one pass over many workgroups (initKappa, Optimizer.cpp:2236-2313: once per time step over 3 nV entries -- as two single-workgroup dot products
@@ -839,9 +807,9 @@ __global__ __launch_bounds__(BLOCK) void k_dot2_partial(int n, const double* __r
         a1 += gi * e[i];
         a2 += gi * gi;
     }
-    const double r1 = block_sum(a1, sm);
+    const double r1 = block_sum<BLOCK>(a1, sm);
     __syncthreads();
-    const double r2 = block_sum(a2, sm);
+    const double r2 = block_sum<BLOCK>(a2, sm);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = r1;
         partial[gridDim.x + blockIdx.x] = r2;
@@ -886,13 +854,11 @@ __global__ void k_mdbc_lambda(int n, const int* __restrict__ ids, const double* 
     lam[i] -= rho * sqrt(mass[v]) * (x[3 * v + c] - pos[i]);
 }
 
-inline int nblk(long long n, int b = BLOCK) { return (int)((n + b - 1) / b); }
-
 } // namespace
 
 void launch_node_init(const ElemView& v, int projectDBC, bool ownerRank, double* a, double* grad, hipStream_t s)
 {
-    if (v.nV) hipLaunchKernelGGL(k_node_init, dim3(nblk(v.nV)), dim3(BLOCK), 0, s, v, projectDBC, ownerRank ? 1 : 0, a, grad);
+    if (v.nV) hipLaunchKernelGGL(k_node_init, dim3(nblk(v.nV, BLOCK)), dim3(BLOCK), 0, s, v, projectDBC, ownerRank ? 1 : 0, a, grad);
 }
 
 void launch_assemble(const ElemView& v, double coef, int projectDBC, double* grad, double* a, hipStream_t s)
@@ -900,10 +866,10 @@ void launch_assemble(const ElemView& v, double coef, int projectDBC, double* gra
     const int n = v.tetEnd - v.tetBegin;
     if (n <= 0) return;
     const bool snh = v.energyType == 2;
-    if (a && snh) hipLaunchKernelGGL((k_assemble<true, true>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
-    else if (a) hipLaunchKernelGGL((k_assemble<true, false>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
-    else if (snh) hipLaunchKernelGGL((k_assemble<false, true>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
-    else hipLaunchKernelGGL((k_assemble<false, false>), dim3(nblk(n)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    if (a && snh) hipLaunchKernelGGL((k_assemble<true, true>), dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else if (a) hipLaunchKernelGGL((k_assemble<true, false>), dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else if (snh) hipLaunchKernelGGL((k_assemble<false, true>), dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
+    else hipLaunchKernelGGL((k_assemble<false, false>), dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, coef, projectDBC, grad, a);
 }
 const char* assemble_kernel_name() { return "k_assemble"; }
 
@@ -911,28 +877,28 @@ void launch_energy(const ElemView& v, double coef, bool withInertia, bool ownerR
     hipStream_t s)
 {
     const int n = std::max(v.tetEnd - v.tetBegin, withInertia ? v.nV : 0);
-    const int nb = std::max(1, nblk(n));
+    const int nb = std::max(1, nblk(n, BLOCK));
     (void)partialCap;
     if (v.energyType == 2) hipLaunchKernelGGL(k_energy<true>, dim3(nb), dim3(BLOCK), 0, s, v, coef, withInertia ? 1 : 0, ownerRank ? 1 : 0, partial);
     else hipLaunchKernelGGL(k_energy<false>, dim3(nb), dim3(BLOCK), 0, s, v, coef, withInertia ? 1 : 0, ownerRank ? 1 : 0, partial);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0, s, partial, nb, out);
+    launch_reduce_partials(partial, nb, 1.0, false, out, s);
 }
 void launch_energy_per_elem(const ElemView& v, double* perElem, hipStream_t s)
 {
     if (!v.nT) return;
-    if (v.energyType == 2) hipLaunchKernelGGL(k_energy_per_elem<true>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
-    else hipLaunchKernelGGL(k_energy_per_elem<false>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, perElem);
+    if (v.energyType == 2) hipLaunchKernelGGL(k_energy_per_elem<true>, dim3(nblk(v.nT, BLOCK)), dim3(BLOCK), 0, s, v, perElem);
+    else hipLaunchKernelGGL(k_energy_per_elem<false>, dim3(nblk(v.nT, BLOCK)), dim3(BLOCK), 0, s, v, perElem);
 }
 void launch_stress_elements(const ElemView& v, double* rec, int* nInvalid, hipStream_t s)
 {
     if (!v.nT) return;
-    if (v.energyType == 2) hipLaunchKernelGGL(k_stress_elements<2>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
-    else if (v.energyType == 1) hipLaunchKernelGGL(k_stress_elements<1>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
-    else hipLaunchKernelGGL(k_stress_elements<0>, dim3(nblk(v.nT)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    if (v.energyType == 2) hipLaunchKernelGGL(k_stress_elements<2>, dim3(nblk(v.nT, BLOCK)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    else if (v.energyType == 1) hipLaunchKernelGGL(k_stress_elements<1>, dim3(nblk(v.nT, BLOCK)), dim3(BLOCK), 0, s, v, rec, nInvalid);
+    else hipLaunchKernelGGL(k_stress_elements<0>, dim3(nblk(v.nT, BLOCK)), dim3(BLOCK), 0, s, v, rec, nInvalid);
 }
 void launch_stress_nodes(int nV, int nT, const int* ptr, const int* elems, const double* vol, const double* rec, double* out, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_stress_nodes, dim3(nblk(nV)), dim3(BLOCK), 0, s, nV, nT, ptr, elems, vol, rec, out);
+    if (nV) hipLaunchKernelGGL(k_stress_nodes, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, s, nV, nT, ptr, elems, vol, rec, out);
 }
 void launch_system_report(const ElemView& v, const double* xStart, const int* slices, int nNodeSlices, int nSlices, const int* nodeStart,
     const int* tetStart, int nComp, double dt, const double* g3, double* rec, double* out, hipStream_t s)
@@ -946,26 +912,26 @@ void launch_system_report(const ElemView& v, const double* xStart, const int* sl
 void launch_check_inversion(const ElemView& v, int* flag, hipStream_t s)
 {
     const int n = v.tetEnd - v.tetBegin;
-    if (n > 0) hipLaunchKernelGGL(k_check_inversion, dim3(nblk(n)), dim3(BLOCK), 0, s, v, flag);
+    if (n > 0) hipLaunchKernelGGL(k_check_inversion, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, flag);
 }
 void launch_inversion_step(const ElemView& v, const double* p, double slackness, double tMax, double* outMin, hipStream_t s)
 {
     const int n = v.tetEnd - v.tetBegin;
     if (n > 0)
-        hipLaunchKernelGGL(k_inversion_step, dim3(nblk(n)), dim3(BLOCK), 0, s, v, p, slackness, tMax, (unsigned long long*)outMin);
+        hipLaunchKernelGGL(k_inversion_step, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, v, p, slackness, tMax, (unsigned long long*)outMin);
 }
 void launch_step_forward(int n3, const double* x0, const double* p, double alpha, double* x, hipStream_t s)
 {
-    if (n3) hipLaunchKernelGGL(k_step_forward, dim3(nblk(n3)), dim3(BLOCK), 0, s, n3, x0, p, alpha, x);
+    if (n3) hipLaunchKernelGGL(k_step_forward, dim3(nblk(n3, BLOCK)), dim3(BLOCK), 0, s, n3, x0, p, alpha, x);
 }
 void launch_trial_step(int n3, const double* x0, const double* p, const double* filterMin, bool useFilter, double* alphaOut, double* x, hipStream_t s)
 {
     hipLaunchKernelGGL(k_trial_alpha, dim3(1), dim3(1), 0, s, filterMin, useFilter ? 1 : 0, alphaOut);
-    if (n3) hipLaunchKernelGGL(k_step_forward_dev, dim3(nblk(n3)), dim3(BLOCK), 0, s, n3, x0, p, (const double*)alphaOut, x);
+    if (n3) hipLaunchKernelGGL(k_step_forward_dev, dim3(nblk(n3, BLOCK)), dim3(BLOCK), 0, s, n3, x0, p, (const double*)alphaOut, x);
 }
 void launch_trial_step_fused(int n3, double* x, double* x0, const double* p, const double* filterMin, bool useFilter, double* alphaOut, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_trial_step_fused, dim3(std::max(nblk(n3), 1)), dim3(BLOCK), 0, s, n3, x, x0, p, filterMin, useFilter ? 1 : 0, alphaOut);
+    hipLaunchKernelGGL(k_trial_step_fused, dim3(std::max(nblk(n3, BLOCK), 1)), dim3(BLOCK), 0, s, n3, x, x0, p, filterMin, useFilter ? 1 : 0, alphaOut);
 }
 void launch_iter_reset(double* scalar, int* flag, hipStream_t s) { hipLaunchKernelGGL(k_iter_reset, dim3(1), dim3(1), 0, s, scalar, flag); }
 void launch_publish2(const void* a, void* da, int na, const void* b, void* db, int nb, hipStream_t s)
@@ -974,29 +940,29 @@ void launch_publish2(const void* a, void* da, int na, const void* b, void* db, i
 }
 void launch_max_abs(int n, const double* v, double* out, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_max_abs, dim3(std::min(nblk(n), 256)), dim3(BLOCK), 0, s, n, v, (unsigned long long*)out);
+    if (n) hipLaunchKernelGGL(k_max_abs, dim3(std::min(nblk(n, BLOCK), 256)), dim3(BLOCK), 0, s, n, v, (unsigned long long*)out);
 }
 void launch_fill(double* p, size_t n, double v, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_fill, dim3(nblk((long long)n)), dim3(BLOCK), 0, s, p, n, v);
+    if (n) hipLaunchKernelGGL(k_fill, dim3(nblk((long long)n, BLOCK)), dim3(BLOCK), 0, s, p, n, v);
 }
 void launch_negate(int n, const double* in, double* out, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_negate, dim3(nblk(n)), dim3(BLOCK), 0, s, n, in, out);
+    if (n) hipLaunchKernelGGL(k_negate, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, n, in, out);
 }
 void launch_colmajor_to_aos(int nV, const double* src, double* dst, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_colmajor_to_aos, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, src, dst);
+    if (nV) hipLaunchKernelGGL(k_colmajor_to_aos, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, src, dst);
 }
 void launch_aos_to_colmajor(int nV, const double* src, double* dst, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_aos_to_colmajor, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, src, dst);
+    if (nV) hipLaunchKernelGGL(k_aos_to_colmajor, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, src, dst);
 }
 void launch_csr_symv(int nRows, const int* ia, const int* ja, const double* a, const double* x, double* y, hipStream_t s)
 {
     if (!nRows) return;
-    hipLaunchKernelGGL(k_csr_symv_zero, dim3(nblk(nRows)), dim3(BLOCK), 0, s, nRows, y);
-    hipLaunchKernelGGL(k_csr_symv, dim3(nblk(nRows)), dim3(BLOCK), 0, s, nRows, ia, ja, a, x, y);
+    hipLaunchKernelGGL(k_csr_symv_zero, dim3(nblk(nRows, BLOCK)), dim3(BLOCK), 0, s, nRows, y);
+    hipLaunchKernelGGL(k_csr_symv, dim3(nblk(nRows, BLOCK)), dim3(BLOCK), 0, s, nRows, ia, ja, a, x, y);
 }
 __global__ void k_apply_host_updates(long long nnz, const double* __restrict__ delta, const unsigned char* __restrict__ mask,
     const double* __restrict__ setVal, double* __restrict__ a)
@@ -1006,11 +972,11 @@ __global__ void k_apply_host_updates(long long nnz, const double* __restrict__ d
 }
 void launch_apply_host_updates(long long nnz, const double* delta, const unsigned char* mask, const double* setVal, double* a, hipStream_t s)
 {
-    if (nnz) hipLaunchKernelGGL(k_apply_host_updates, dim3(nblk(nnz)), dim3(BLOCK), 0, s, nnz, delta, mask, setVal, a);
+    if (nnz) hipLaunchKernelGGL(k_apply_host_updates, dim3(nblk(nnz, BLOCK)), dim3(BLOCK), 0, s, nnz, delta, mask, setVal, a);
 }
 void launch_precond_diag(int nRows, const int* ia, const double* a, const double* in, double* out, hipStream_t s)
 {
-    if (nRows) hipLaunchKernelGGL(k_precond_diag, dim3(nblk(nRows)), dim3(BLOCK), 0, s, nRows, ia, a, in, out);
+    if (nRows) hipLaunchKernelGGL(k_precond_diag, dim3(nblk(nRows, BLOCK)), dim3(BLOCK), 0, s, nRows, ia, a, in, out);
 }
 void launch_nm_update(int nV, const int* dbc, const double* x, double* xPrevOut, double* vel, double* acc, double* dxElastic, double* xTilde,
     double dt, double beta, double gamma, double gx, double gy, double gz, hipStream_t s)
@@ -1022,22 +988,22 @@ void launch_be_update(int nV, const int* dbc, const double* x, const double* xPr
     double dt, double gx, double gy, double gz, hipStream_t s)
 {
     if (nV)
-        hipLaunchKernelGGL(k_be_update, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, x, xPrev, xPrevOut, vel, acc, dxElastic, xTilde, dt, gx, gy,
+        hipLaunchKernelGGL(k_be_update, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, dbc, x, xPrev, xPrevOut, vel, acc, dxElastic, xTilde, dt, gx, gy,
             gz);
 }
 void launch_warm_dir(int nV, const int* dbc, const double* vel, const double* dx, double dt, const double* cgDtSqG3, double ce, double* p,
     hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_warm_dir, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, vel, dx, dt, cgDtSqG3[0], cgDtSqG3[1], cgDtSqG3[2], ce, p);
+    if (nV) hipLaunchKernelGGL(k_warm_dir, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, dbc, vel, dx, dt, cgDtSqG3[0], cgDtSqG3[1], cgDtSqG3[2], ce, p);
 }
 void launch_twist_dir(int nH, const int* ids, const double* ang, double cy, double cz, const double* x, double* p, hipStream_t s)
 {
-    if (nH) hipLaunchKernelGGL(k_twist_dir, dim3(nblk(nH)), dim3(BLOCK), 0, s, nH, ids, ang, cy, cz, x, p);
+    if (nH) hipLaunchKernelGGL(k_twist_dir, dim3(nblk(nH, BLOCK)), dim3(BLOCK), 0, s, nH, ids, ang, cy, cz, x, p);
 }
 
 void launch_nbc_gradient(int n, const int* ids, const int* dbc, const double* mass, const double* dtSqA3, double* g, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_nbc_gradient, dim3(nblk(n)), dim3(BLOCK), 0, s, n, ids, dbc, mass, dtSqA3[0], dtSqA3[1], dtSqA3[2], g);
+    if (n) hipLaunchKernelGGL(k_nbc_gradient, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, n, ids, dbc, mass, dtSqA3[0], dtSqA3[1], dtSqA3[2], g);
 }
 void launch_nbc_energy(int n, const int* ids, const int* dbc, const double* mass, const double* x, const double* dtSqA3, double* out, hipStream_t s)
 {
@@ -1045,15 +1011,15 @@ void launch_nbc_energy(int n, const int* ids, const int* dbc, const double* mass
 }
 void launch_damp_dx(int nV, const int* dbc, int mode, int projectDBC, const double* x, const double* xPrev, double* dx, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_damp_dx, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, mode, projectDBC, x, xPrev, dx);
+    if (nV) hipLaunchKernelGGL(k_damp_dx, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, dbc, mode, projectDBC, x, xPrev, dx);
 }
 void launch_damp_clear_diag(int nV, const int* dbc, const int* ia, double* d, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_damp_clear_diag, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, ia, d);
+    if (nV) hipLaunchKernelGGL(k_damp_clear_diag, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, dbc, ia, d);
 }
 void launch_axpy(long long n, double alpha, const double* x, double* y, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_axpy, dim3(nblk(n)), dim3(BLOCK), 0, s, n, alpha, x, y);
+    if (n) hipLaunchKernelGGL(k_axpy, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, n, alpha, x, y);
 }
 void launch_dot_scaled(int n, const double* x, const double* y, double scale, double* out, hipStream_t s)
 {
@@ -1067,7 +1033,7 @@ void launch_dot2(int n, const double* g, const double* e, double* partial, int p
 }
 void launch_keep_mine3(int nV, const unsigned char* mine, double* g, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_keep_mine3, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, mine, g);
+    if (nV) hipLaunchKernelGGL(k_keep_mine3, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, mine, g);
 }
 void launch_keep_mine_rows(int nRows, const unsigned char* mine, const int* ia, double* a, hipStream_t s)
 {
@@ -1075,7 +1041,7 @@ void launch_keep_mine_rows(int nRows, const unsigned char* mine, const int* ia, 
 }
 void launch_clear_projected(int nV, const int* dbc, int projectDBC, double* g, hipStream_t s)
 {
-    if (nV) hipLaunchKernelGGL(k_clear_projected, dim3(nblk(3LL * nV)), dim3(BLOCK), 0, s, nV, dbc, projectDBC, g);
+    if (nV) hipLaunchKernelGGL(k_clear_projected, dim3(nblk(3LL * nV, BLOCK)), dim3(BLOCK), 0, s, nV, dbc, projectDBC, g);
 }
 void launch_mdbc_reduce(const MdbcView& m, const double* x, double rho, int mode, double* out, hipStream_t s)
 {
@@ -1083,31 +1049,31 @@ void launch_mdbc_reduce(const MdbcView& m, const double* x, double rho, int mode
 }
 void launch_mdbc_gradient(const MdbcView& m, const double* x, double rho, double* g, hipStream_t s)
 {
-    if (m.n) hipLaunchKernelGGL(k_mdbc_gradient, dim3(nblk(3LL * m.n)), dim3(BLOCK), 0, s, m.n, m.ids, m.pos, m.lam, m.mass, x, rho, g);
+    if (m.n) hipLaunchKernelGGL(k_mdbc_gradient, dim3(nblk(3LL * m.n, BLOCK)), dim3(BLOCK), 0, s, m.n, m.ids, m.pos, m.lam, m.mass, x, rho, g);
 }
 void launch_mdbc_hessian(const MdbcView& m, const int* ia, double rho, double* a, hipStream_t s)
 {
-    if (m.n) hipLaunchKernelGGL(k_mdbc_hessian, dim3(nblk(3LL * m.n)), dim3(BLOCK), 0, s, m.n, m.ids, m.mass, ia, rho, a);
+    if (m.n) hipLaunchKernelGGL(k_mdbc_hessian, dim3(nblk(3LL * m.n, BLOCK)), dim3(BLOCK), 0, s, m.n, m.ids, m.mass, ia, rho, a);
 }
 void launch_mdbc_lambda(const MdbcView& m, const double* x, double rho, hipStream_t s)
 {
-    if (m.n) hipLaunchKernelGGL(k_mdbc_lambda, dim3(nblk(3LL * m.n)), dim3(BLOCK), 0, s, m.n, m.ids, m.pos, m.lam, m.mass, x, rho);
+    if (m.n) hipLaunchKernelGGL(k_mdbc_lambda, dim3(nblk(3LL * m.n, BLOCK)), dim3(BLOCK), 0, s, m.n, m.ids, m.pos, m.lam, m.mass, x, rho);
 }
 void launch_target_positions(int n, const int* ids, const double* x, const double* p, double* pos, double* pOut, double* lam, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_target_positions, dim3(nblk(3LL * n)), dim3(BLOCK), 0, s, n, ids, x, p, pos, pOut, lam);
+    if (n) hipLaunchKernelGGL(k_target_positions, dim3(nblk(3LL * n, BLOCK)), dim3(BLOCK), 0, s, n, ids, x, p, pos, pOut, lam);
 }
 void launch_gather3(int n, const int* ids, const double* x, double* out, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_gather3, dim3(nblk(3LL * n)), dim3(BLOCK), 0, s, n, ids, x, out);
+    if (n) hipLaunchKernelGGL(k_gather3, dim3(nblk(3LL * n, BLOCK)), dim3(BLOCK), 0, s, n, ids, x, out);
 }
 void launch_dbc_motion(int n, const int* ids, const DbcMotion& m, const double* x, double* p, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_dbc_motion, dim3(nblk(n)), dim3(BLOCK), 0, s, n, ids, m, x, p);
+    if (n) hipLaunchKernelGGL(k_dbc_motion, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, s, n, ids, m, x, p);
 }
 void launch_dbc_targets(int n, const int* ids, const double* target, const double* x, double* p, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(k_dbc_targets, dim3(nblk(3LL * n)), dim3(BLOCK), 0, s, n, ids, target, x, p);
+    if (n) hipLaunchKernelGGL(k_dbc_targets, dim3(nblk(3LL * n, BLOCK)), dim3(BLOCK), 0, s, n, ids, target, x, p);
 }
 
 __global__ void k_publish(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int n)

@@ -3,6 +3,7 @@
 // pass, the scalars never leave the device, and nothing is accumulated with atomics -- two runs give the same bits.
 #include "pcg.h"
 #include "pcg_coarse.h"
+#include "device_prims.h"
 #include <algorithm>
 
 namespace ipcgpu {
@@ -13,19 +14,7 @@ constexpr int GROUP = 16; // lanes that share one node block row of the product
 constexpr int NODES_PER_BLOCK = BLOCK / GROUP;
 constexpr int MAX_VEC_BLOCKS = 1024; // grid of the vector passes (grid-stride): at most this many partial sums per scalar
 
-__device__ __forceinline__ double block_sum(double x, double* sm)
-{
-    // fixed-order tree: deterministic
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) sm[wv] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < BLOCK / 64; ++i) r += sm[i];
-    return r;
-}
+using prims::block_sum; // fixed-order tree: deterministic
 // gate: 0 always, 1 while the iteration runs, 2 once it has ended
 __device__ __forceinline__ bool gated_out(const PcgState* st, int gate)
 {
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_symv_blocks(int nNodes, const int
         }
     }
     if (FUSE) {
-        const double r = block_sum(dot, sm);
+        const double r = block_sum<BLOCK>(dot, sm);
         if (threadIdx.x == 0) partial[blockIdx.x] = r;
     }
 }
@@ -143,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_symv_rows(int nRows, const int* _
         }
     }
     if (FUSE) {
-        const double s = block_sum(dot, sm);
+        const double s = block_sum<BLOCK>(dot, sm);
         if (threadIdx.x == 0) partial[blockIdx.x] = s;
     }
 }
@@ -206,14 +195,14 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_begin(int nNodes, int jacobi, int
             rz += r0 * z0 + r1 * z1 + r2 * z2;
         }
     }
-    const double sRz = block_sum(rz, smA), sRr = block_sum(rr, smB);
+    const double sRz = block_sum<BLOCK>(rz, smA), sRr = block_sum<BLOCK>(rr, smB);
     if (threadIdx.x == 0) pRz[blockIdx.x] = sRz, pRr[blockIdx.x] = sRr;
 }
 __device__ __forceinline__ double reduce_partials(const double* __restrict__ partial, int n, double* sm)
 {
     double x = 0.0;
     for (int i = threadIdx.x; i < n; i += BLOCK) x += partial[i];
-    return block_sum(x, sm);
+    return block_sum<BLOCK>(x, sm);
 }
 __global__ __launch_bounds__(BLOCK) void k_pcg_begin_state(int n, int jacobi, int restart, const double* __restrict__ pRz, const double* __restrict__ pRr,
     double relTol, int maxIter, PcgState* __restrict__ st)
@@ -266,7 +255,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_update(int nNodes, int jacobi, co
             rz += r0 * z0 + r1 * z1 + r2 * z2;
         }
     }
-    const double sRz = block_sum(rz, smA), sRr = block_sum(rr, smB);
+    const double sRz = block_sum<BLOCK>(rz, smA), sRr = block_sum<BLOCK>(rr, smB);
     if (threadIdx.x == 0) pRz[blockIdx.x] = sRz, pRr[blockIdx.x] = sRr;
 }
 __global__ __launch_bounds__(BLOCK) void k_pcg_update_state(int n, int jacobi, const double* __restrict__ pRz, const double* __restrict__ pRr,
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_dot(int n, const double* __restri
     if (st->done) return;
     double s = 0.0;
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) s += u[i] * w[i];
-    const double t = block_sum(s, sm);
+    const double t = block_sum<BLOCK>(s, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 __global__ __launch_bounds__(BLOCK) void k_pcg_rz_state(int n, int first, const double* __restrict__ pRz, PcgState* __restrict__ st)
@@ -318,7 +307,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_res(int n, const double* __restri
         const double d = b[i] - y[i];
         s += d * d;
     }
-    const double t = block_sum(s, sm);
+    const double t = block_sum<BLOCK>(s, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 __global__ __launch_bounds__(BLOCK) void k_pcg_res_state(int n, const double* __restrict__ partial, PcgState* __restrict__ st)
@@ -526,7 +515,7 @@ __global__ __launch_bounds__(BLOCK) void k_pcg_prolong(int nNodes, const int* __
         z[o] = z0, z[o + 1] = z1, z[o + 2] = z2;
         rz += r0 * z0 + r1 * z1 + r2 * z2;
     }
-    const double s = block_sum(rz, sm);
+    const double s = block_sum<BLOCK>(rz, sm);
     if (threadIdx.x == 0) pRz[blockIdx.x] = s;
 }
 

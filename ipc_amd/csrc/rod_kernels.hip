@@ -205,7 +205,7 @@ void launch_rod_energy(const RodView& v, double coef, double* partial, double* o
 {
     const int nb = rod_energy_blocks(v);
     hipLaunchKernelGGL(k_rod_energy, dim3(nb), dim3(ROD_BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_rod_energy_per_elem(const RodView& v, double* perSeg, double* perBend, hipStream_t s)
 {

@@ -261,7 +261,7 @@ void launch_shell_energy(const ShellView& v, double coef, double* partial, doubl
 {
     const int nb = shell_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_energy, dim3(nb), dim3(ENERGY_BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_shell_energy_per_elem(const ShellView& v, double* perTri, double* perHinge, hipStream_t s)
 {

@@ -215,8 +215,7 @@ __global__ __launch_bounds__(BLOCK) void k_shell_limit(ShellLimitView v, double 
 // maximum over the workgroup, valid in lane 0 (fixed-order tree; sm: BLOCK / 64 doubles)
 __device__ __forceinline__ double block_max(double x, double* sm)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_down(x, off, 64));
+    x = wave_max(x);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __syncthreads(); // (sm may still be read by a reduction before this one)
     if (lane == 0) sm[wv] = x;
@@ -281,7 +280,7 @@ void launch_shell_limit_energy(const ShellLimitView& v, double coef, double* par
 {
     const int nb = shell_limit_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_limit_energy, dim3(nb), dim3(BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_shell_limit_energy_per_elem(const ShellLimitView& v, double* perTri, hipStream_t s)
 {

@@ -194,7 +194,7 @@ void launch_shell_rubber_energy(const ShellRubberView& v, double coef, double* p
 {
     const int nb = shell_rubber_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_rubber_energy, dim3(nb), dim3(ENERGY_BLOCK), 0, s, v, coef, partial);
-    launch_reduce_partials(partial, nb, accumulate, out, s);
+    launch_reduce_partials(partial, nb, 1.0, accumulate, out, s);
 }
 void launch_shell_rubber_energy_per_elem(const ShellRubberView& v, double* perTri, hipStream_t s)
 {
@@ -212,7 +212,7 @@ void launch_shell_rubber_degenerate(const ShellRubberView& v, double* partial, d
 {
     const int nb = shell_rubber_energy_blocks(v);
     hipLaunchKernelGGL(k_shell_rubber_degenerate, dim3(nb), dim3(ENERGY_BLOCK), 0, s, v, partial);
-    launch_reduce_partials(partial, nb, false, out, s);
+    launch_reduce_partials(partial, nb, 1.0, false, out, s);
 }
 
 } // namespace ipcgpu

@@ -142,8 +142,8 @@ int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
     need(o.initialised, "call ipcgpu_opt_init first");
     *E = 0.0;
     if (!codimCount(*c->mesh, which)) return IPCGPU_OK;
-    o.codimEnergyAdd(c->mesh->d_x.p, coef, o.d_scalar.p, /*accumulate=*/false, which);
-    *E = o.readScalar(o.d_scalar.p);
+    o.codimEnergyAdd(c->mesh->d_x.p, coef, o.slot(S_SCRATCH), /*accumulate=*/false, which);
+    *E = o.readScalar(S_SCRATCH);
     return IPCGPU_OK;
 }
 int codimGradientAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, double* g)
@@ -509,9 +509,9 @@ int ipcgpu_elastic_energy(ipcgpu_ctx* c, double coef, double* E)
         HipOptimizer& o = O(c);
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
-        launch_energy(o.view(), coef, false, o.rank == 0, o.d_partial.p, (int)o.d_partial.n, o.d_scalar.p, c->stream);
-        o.reduceSum(o.d_scalar.p, 1);
-        *E = o.readScalar(o.d_scalar.p);
+        launch_energy(o.view(), coef, false, o.rank == 0, o.d_partial.p, (int)o.d_partial.n, o.slot(S_SCRATCH), c->stream);
+        o.reduceSum(o.slot(S_SCRATCH), 1);
+        *E = o.readScalar(S_SCRATCH);
         return IPCGPU_OK;
     });
 }
@@ -1602,7 +1602,7 @@ int ipcgpu_contact_energy(ipcgpu_ctx* c, double dHat, double kappa, double* E)
         HipOptimizer& o = O(c);
         bind(c);
         need(o.initialised, "call ipcgpu_opt_init first");
-        *E = CT(c).energy(c->mesh->d_x.p, dHat, kappa, o.d_partial, o.d_scalar.p + 4);
+        *E = CT(c).energy(c->mesh->d_x.p, dHat, kappa, o.d_partial, o.slot(S_CONTACT_E));
         return IPCGPU_OK;
     });
 }
@@ -2102,7 +2102,7 @@ int ipcgpu_friction_energy(ipcgpu_ctx* c, const double* Vt, double eps2, double 
         need(o.initialised, "call ipcgpu_opt_init first");
         needArg(Vt && E && eps2 > 0, "bad argument");
         uploadColMajor(c, Vt, o.d_x0);
-        *E = CT(c).frictionEnergy(c->mesh->d_x.p, o.d_x0.p, eps2, coef, o.d_partial, o.d_scalar.p + 4);
+        *E = CT(c).frictionEnergy(c->mesh->d_x.p, o.d_x0.p, eps2, coef, o.d_partial, o.slot(S_FRICTION_E));
         return IPCGPU_OK;
     });
 }

@@ -105,6 +105,14 @@ struct ZeroKeptCounters {
 };
 
 // pinned host scalar block for small readbacks
+// 32-bit words of `count` elements of T: what the publish kernels (device_prims.h, nh_kernels.h) copy into a PinnedBuf
+template <class T>
+constexpr int publish_words(int count)
+{
+    static_assert(sizeof(T) % sizeof(unsigned) == 0, "published types are whole 32-bit words");
+    return count * (int)(sizeof(T) / sizeof(unsigned));
+}
+
 template <class T>
 struct PinnedBuf {
     T* p = nullptr;

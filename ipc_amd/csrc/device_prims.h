@@ -1,12 +1,15 @@
 // The small device idioms that every kernel unit outside the direct solver shares, each defined once: the fixed-order wave and workgroup reductions
-// and the kernel that sums their partials, the Dirichlet projection rule, the launch grid size, and where the rows of a 3 x 3 block lie in the
-// upper CSR.  Bit-reproducible energies, gradients and CSR values rest on every unit running the SAME reduction tree, hence one definition.
+// and the kernel that sums their partials, the kernel that publishes a small result to mapped host memory, the Dirichlet projection rule, the launch
+// grid size, and where the rows of a 3 x 3 block lie in the upper CSR.  Bit-reproducible energies, gradients and CSR values rest on every unit running
+// the SAME reduction tree, hence one definition.
 // Everything is __forceinline__ and takes the including unit's -ffp-contract setting; nothing here multiplies and adds, so that setting cannot
 // change a bit -- keep arithmetic beyond add / min / max out of the helpers.  For .hip files only.
 //   nh_kernels, hip_contact, hip_halfspace, pcg          include this header
 //   shell*, rod, attach, chamber kernels                 get it through csr_scatter_device.h (the atomic block scatter)
+//   mf_numeric, mf_sweeps                                include it for the publish kernel alone
 #pragma once
 #include <hip/hip_runtime.h>
+#include "common.h"
 
 namespace ipcgpu {
 namespace prims {
@@ -101,6 +104,22 @@ template <int BLOCK = 256> // (a template: a unit that never calls it gets no ke
 inline void launch_reduce_partials(const double* partial, int n, double scale, bool accumulate, double* out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_reduce_partials<BLOCK>, dim3(1), dim3(BLOCK), 0, s, partial, n, scale, accumulate ? 1 : 0, out);
+}
+
+// ---- read-backs through mapped host memory ------------------------------------------------------------------------------------------------------------------
+// dst[i] = src[i] for the nWords <= 64 32-bit words of a small result, one lane each: THE kernel that carries flags, counters and scalars from device memory
+// to their mapped place on the host.  (k_publish2, k_publish_narrow and the tail of k_reduce_scaled stay where they are: two sources, or a gather.)
+template <int WAVE = 64> // (a template, like k_reduce_partials: a unit that never launches it gets no kernel)
+__global__ __launch_bounds__(WAVE) void k_publish_words(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int nWords)
+{
+    const int i = threadIdx.x;
+    if (i < nWords) dst[i] = src[i];
+}
+// `count` elements of T (publish_words, common.h)
+template <class T>
+inline void launch_publish(const T* src, T* dst, int count, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_publish_words<64>, dim3(1), dim3(64), 0, s, reinterpret_cast<const unsigned*>(src), reinterpret_cast<unsigned*>(dst), publish_words<T>(count));
 }
 
 // ---- 3 x 3 node blocks in the upper CSR (LinSysSolver.hpp:63-111) ----------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 //   augmentConnectivity       :330-415                            -> connectivity
 //   largestFeasibleStepSize[_CCD]  :564-686, 982-1366             -> ccdPartial / ccdFull / ccdFullReference (conservative additive CCD)
 #pragma once
+#include <cstddef>
 #include <cstdlib>
 #include "common.h"
 #include "contact_groups.h"
@@ -26,6 +27,42 @@ struct Grid {
     double lo[3], h;
     int dim[3];
 };
+
+// counters_ (HipContact): C_COUNT ints of device memory, zeroed at the head of every pass that counts.  One pass uses the block at a time; each pass has
+// its own enum for what the first entries mean.  The kernels take the address of the entry they count into, or the block's base and these indices.
+constexpr int C_COUNT = 16;
+enum BuildCounter : int { C_PT = 0, C_EE = 1, C_STALE = 2 }; // buildConstraintSet: point-triangle records, edge-edge records, "the positions have left the grid" (k_bbox_final).  isIntersected: C_PT is its flag
+enum HessianCounter : int { C_MISS = 0, C_SWEEPS = 1, C_BIN0 = 4 }; // hessianAdd, patternCovers: a node pair outside the CSR pattern, Jacobi sweeps of the projections, the first of the NBINS stencil-kind bin counts (k_bin_stencils)
+enum CcdCounter : int { C_QUERIED = 0, C_HITS = 1 }; // ccdFull, ccdFullReference: queried pairs, pairs that returned a time inside the step (the hit list)
+enum CloseCounter : int { C_CLOSE = 0, C_CLOSE_MISS = 2, C_CLOSE_END = 4 }; // closeStencils: stencils closer than dTol, the pattern check's miss flag riding along; [0, C_CLOSE_END) come back
+
+// what the host needs between the stages of a build, written to mapped host memory by one thread (three blits of 12, 4 and 48 bytes before)
+struct BuildReadback {
+    int cnt[4]; // point-triangle records, edge-edge records, stale-grid flag, total number of cell entries
+    double box[6];
+    unsigned long long totals; // category totals of the candidate list (k_bucket_rank_classify's flags, scanned)
+    int nUnique, pad;
+};
+// Everything the host reads from the contact kernels through mapped memory: HipContact::readback_ is one of these.  Every member but hessError is
+// written and read inside ONE call of the handler, between a launch and the synchronisation behind it, and the handler's calls do not overlap on its
+// stream: those members are never live together.  hessError is live from hessianAdd(deferCheck) to takeHessianError(), across whatever the stepper
+// calls in between (energy, stepBounds, both CCDs, builds): no other member may share its bytes.
+struct ContactReadback {
+    BuildReadback build; // buildConstraintSet (k_publish_narrow, then k_dup_emit: totals, nUnique), isIntersected (k_publish_narrow)
+    unsigned long long stepBounds[4]; // stepBounds: minimum time, its pair, largest surface speed, the step the CCD was bounded by (ccdOut_)
+    double energy; // energy(): the barrier energy behind energyEnqueue
+    double refBox[7]; // ccdFullReference, first wait: the capped step, lower and upper corner of the hash (k_ref_box_final)
+    unsigned long long refCcd[2]; // ccdFullReference, third wait: minimum time, its pair ...
+    int refCount[2]; // ... and C_QUERIED, C_HITS
+    int refItems; // ccdFullReference, second wait: total number of cell entries
+    int hessError; // C_MISS of a hessianAdd(deferCheck): see above
+    int close[C_CLOSE_END]; // closeStencils: counters [0, C_CLOSE_END)
+};
+static_assert(sizeof(BuildReadback) == 80 && offsetof(BuildReadback, box) % 8 == 0 && offsetof(BuildReadback, totals) % 8 == 0, "k_publish_narrow and k_dup_emit write this record");
+static_assert(offsetof(ContactReadback, build) == 0 && offsetof(ContactReadback, stepBounds) % 8 == 0 && offsetof(ContactReadback, energy) % 8 == 0
+        && offsetof(ContactReadback, refBox) % 8 == 0 && offsetof(ContactReadback, refCcd) % 8 == 0,
+    "the kernels store the 8-byte members whole");
+static_assert(sizeof(ContactReadback) == 224, "members are added at the end; every publish stays inside its own member");
 
 class HipContact {
 public:
@@ -89,9 +126,10 @@ public:
     double energy(const double* x_dev, double dHat, double kappa, DevBuf<double>& partial, double* scalar_dev);
     // the same without the read-back: the value is left in *scalar_dev on the stream (false: empty sets, nothing enqueued, the value is 0) -- the time stepper
     // reads it together with the elastic energy, one synchronisation for both
-    // pubWords > 0: the reduction's own launch also copies pubWords 32-bit words pubSrc -> pubDst (mapped host memory); publishedByEnergy() says whether it did
-    bool energyEnqueue(const double* x_dev, double dHat, double kappa, DevBuf<double>& partial, double* scalar_dev, const void* pubSrc = nullptr,
-        void* pubDst = nullptr, int pubWords = 0);
+    // pubCount > 0: the reduction's own launch also copies pubCount doubles pubSrc -> pubDst (mapped host memory; at most one wave of 32-bit words);
+    // publishedByEnergy() says whether it did
+    bool energyEnqueue(const double* x_dev, double dHat, double kappa, DevBuf<double>& partial, double* scalar_dev, const double* pubSrc = nullptr,
+        double* pubDst = nullptr, int pubCount = 0);
     bool publishedByEnergy() const { return publishedByEnergy_; }
     bool publishedByEnergy_ = false;
     // useActive / usePara: initKappa leaves the mollified set out (Optimizer.cpp:2262-2270)
@@ -204,7 +242,7 @@ private:
     DevBuf<int> bucketStart_, bucketSeg_, dupStart_, runs_, runPos_;
     void readbackInit();
     bool hessErrPending_ = false;
-    PinnedBuf<unsigned long long> readback_; // BuildReadback: what the host reads between the stages of a build (mapped memory, written by the kernels)
+    PinnedBuf<ContactReadback> readback_; // one record (mapped memory, written by the kernels)
     DevBuf<double> closeVal_;
     DevBuf<char> scanTmp_;
     // deterministic scatter of the barrier / friction terms (hip_contact.hip "Deterministic scatter"): per-stencil slots, keys, bucket counters / starts /

@@ -2075,13 +2075,6 @@ __device__ __forceinline__ int rec_category(const int* r, bool isEE)
     if (!isEE) return r[3] < 0 ? 1 : 0;
     return r[3] >= 0 ? 0 : (r[3] == -1 ? 1 : 2);
 }
-// what the host needs between the stages of a build, written to mapped host memory by one thread (three blits of 12, 4 and 48 bytes before)
-struct BuildReadback {
-    int cnt[4]; // point-triangle records, edge-edge records, stale-grid flag, total number of cell entries
-    double box[6];
-    unsigned long long totals; // category totals of the candidate list (k_bucket_rank_classify's flags, scanned)
-    int nUnique, pad;
-};
 // one thread per bucket ENTRY: the rank of its second primitive inside the bucket (the pair is unique, the bucket a handful of entries) gives the record's
 // place in the serial enumeration -- the bucket's range of the list IS its range there --, and the thread writes what belongs to that place: the permutation
 // (point-triangle records first, then the edge-edge ones, each as an index into its own list), the candidate list, the category flag for the prefix sum; it
@@ -2195,14 +2188,12 @@ __global__ void k_dup_emit(int nV, const unsigned long long* __restrict__ totals
 }
 __global__ void k_publish_narrow(const int* __restrict__ counters, const int* __restrict__ gridTotal, const double* __restrict__ box, BuildReadback* __restrict__ out)
 {
-    out->cnt[0] = counters[0];
-    out->cnt[1] = counters[1];
-    out->cnt[2] = counters[2];
+    out->cnt[0] = counters[C_PT];
+    out->cnt[1] = counters[C_EE];
+    out->cnt[2] = counters[C_STALE];
     out->cnt[3] = gridTotal[0];
     for (int c = 0; c < 6; ++c) out->box[c] = box[c];
 }
-__global__ void k_publish_u64(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst) { dst[0] = src[0]; }
-__global__ void k_publish_u64x4(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst) { dst[threadIdx.x] = src[threadIdx.x]; }
 // ccdOut of HipContact::stepBounds: [0] minimum time, [1] its pair (both "none"), [2] largest surface speed, [3] the step the CCD is bounded by
 __global__ void k_step_bounds_init(double stepSize, const double* __restrict__ filterRoot, unsigned long long* __restrict__ out)
 {
@@ -2215,7 +2206,6 @@ __global__ void k_step_bounds_init(double stepSize, const double* __restrict__ f
     }
     out[3] = (unsigned long long)__double_as_longlong(stepSize);
 }
-__global__ void k_publish_int(const int* __restrict__ src, int* __restrict__ dst) { dst[0] = src[0]; }
 // stencils of the active set closer than dTol (closeMConstraint bookkeeping, Optimizer.cpp:2365-2440): index + distance
 __global__ void k_close_stencils(int n, const int* __restrict__ ids, const double* __restrict__ x, double dTol, int cap, int* __restrict__ outIdx,
     double* __restrict__ outVal, int* __restrict__ counter)
@@ -2376,8 +2366,7 @@ void HipContact::uploadSets()
 
 void HipContact::readbackInit()
 {
-    if (!readback_.p) readback_.alloc(16); // >= sizeof(BuildReadback) / 8
-    static_assert(sizeof(BuildReadback) <= 16 * sizeof(unsigned long long), "read-back block too small");
+    if (!readback_.p) readback_.alloc(1);
 }
 
 void* HipContact::scanTmp(size_t bytes)
@@ -2441,8 +2430,8 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     const int nb = nblk(nV, BLOCK);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
-    counters_.alloc(16);
-    const int* stale = counters_.p + 2;
+    counters_.alloc(C_COUNT);
+    const int* stale = counters_.p + C_STALE;
     int capPT = std::max<int>(1 << 14, (int)outPT_.n / 6), capEE = std::max<int>(1 << 14, (int)outEE_.n / 6);
     const int nPrim = nSF + nSFE;
     if (gridItems_.n < (size_t)REC * 16 * (size_t)nPrim) gridItems_.ensure((size_t)REC * 16 * (size_t)nPrim); // (a first guess: 16 cells per primitive)
@@ -2455,8 +2444,8 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
     runs_.ensure((size_t)nV + 1);
     runPos_.ensure((size_t)nV + 1);
     readbackInit();
-    BuildReadback* rb = reinterpret_cast<BuildReadback*>(readback_.p);
-    BuildReadback* rbDev = reinterpret_cast<BuildReadback*>(readback_.dev);
+    const BuildReadback* rb = &readback_.p->build;
+    BuildReadback* rbDev = &readback_.dev->build;
     int nPT = 0, nEE = 0;
     Grid g;
     for (int attempt = 0;; ++attempt) {
@@ -2475,7 +2464,7 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
         const int capItems = (int)std::min<size_t>(gridItems_.n / REC, (size_t)INT_MAX);
         counters_.zero(stream);
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
-        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
+        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + C_STALE);
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nPrim, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, nSFE, d_SFE.p, x_dev, g, (int)nCells, infl, 0, capItems, stale,
             gridCount, (const int*)nullptr, (int*)nullptr);
         exclusiveSum(gridCount, gridStart_.p, (int)nC2);
@@ -2483,9 +2472,9 @@ int HipContact::buildConstraintSet(const HipMesh& mesh, const double* x_dev, con
             gridCount, gridStart_.p, gridItems_.p);
         gridCount_.done();
         hipLaunchKernelGGL(k_narrow_pt, dim3(nblk(COOP * nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, pf, g, cellStartT, gridItems_.p,
-            dHat, capPT, outPT_.p, counters_.p, capItems, stale, bucketCount);
+            dHat, capPT, outPT_.p, counters_.p + C_PT, capItems, stale, bucketCount);
         hipLaunchKernelGGL(k_narrow_ee_cells, dim3((int)std::min<long long>(nblk(64 * nCells, BLOCK), 4096)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, d_xRest.p, pf, g, (int)nCells, cellStartE,
-            gridItems_.p, dHat, infl, capEE, outEE_.p, counters_.p + 1, capItems, stale, bucketCount + nSVI);
+            gridItems_.p, dHat, infl, capEE, outEE_.p, counters_.p + C_EE, capItems, stale, bucketCount + nSVI);
         // the buckets of the record sort: needed only when the build stands, enqueued before the host knows (one scan; the GPU would idle through the read-back)
         exclusiveSum(bucketCount, bucketStart_.p, nB + 1);
         hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + (nC2 - 1), box_dev, rbDev);
@@ -2587,8 +2576,8 @@ void HipContact::syncHost() const
     self->hostStale_ = false;
 }
 
-bool HipContact::energyEnqueue(const double* x_dev, double dHat, double kappa, DevBuf<double>& partial, double* scalar_dev, const void* pubSrc, void* pubDst,
-    int pubWords)
+bool HipContact::energyEnqueue(const double* x_dev, double dHat, double kappa, DevBuf<double>& partial, double* scalar_dev, const double* pubSrc, double* pubDst,
+    int pubCount)
 {
     if (nActive_ + nPara_ == 0) return false;
     int aB, aE, pB, pE; // this rank's share of the two lists
@@ -2599,6 +2588,7 @@ bool HipContact::energyEnqueue(const double* x_dev, double dHat, double kappa, D
     const int nb = std::max(1, nblk(n, BLOCK));
     if (partial.n < (size_t)nb) partial.alloc(nb);
     if (n) hipLaunchKernelGGL(k_contact_energy, dim3(nb), dim3(BLOCK), 0, stream, cv, dHat, partial.p);
+    const int pubWords = publish_words<double>(pubCount);
     const bool pub = pubWords > 0 && !(shardWorld > 1 && shardReduce); // (a sharded sum is complete only after the reduction below: the caller publishes)
     hipLaunchKernelGGL(k_reduce_scaled, dim3(1), dim3(BLOCK), 0, stream, partial.p, n ? nb : 0, kappa, scalar_dev, pub ? (const unsigned*)pubSrc : nullptr,
         pub ? (unsigned*)pubDst : nullptr, pub ? pubWords : 0);
@@ -2610,11 +2600,9 @@ double HipContact::energy(const double* x_dev, double dHat, double kappa, DevBuf
 {
     if (!energyEnqueue(x_dev, dHat, kappa, partial, scalar_dev)) return 0.0;
     readbackInit();
-    hipLaunchKernelGGL(k_publish_u64, dim3(1), dim3(1), 0, stream, reinterpret_cast<const unsigned long long*>(scalar_dev), readback_.dev);
+    prims::launch_publish(scalar_dev, &readback_.dev->energy, 1, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    double out;
-    std::memcpy(&out, readback_.p, sizeof(out));
-    return out;
+    return readback_.p->energy;
 }
 
 void HipContact::evaluateTuples(const double* x_dev, int n, const int* tuples4, double* val)
@@ -2659,35 +2647,36 @@ void HipContact::hessianAdd(const double* x_dev, const int* dbc_dev, const HipLi
     if (!n) return;
     ContactView cv{ nActive_, nPara_, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, x_dev, d_xRest.p, need_dev };
     CsrView m{ lin.d_ia.p, lin.d_ja.p };
-    // counters: [0] pattern-miss flag, [1] Jacobi sweeps, [4 .. 11] the bin counts
-    counters_.alloc(16);
+    static_assert(C_BIN0 + NBINS <= C_COUNT, "the bin counts lie inside the counter block");
+    counters_.alloc(C_COUNT);
     counters_.zero(stream);
     hessPerm_.ensure((size_t)NBINS * (size_t)n);
-    hipLaunchKernelGGL(k_bin_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, counters_.p + 4, hessPerm_.p, n);
+    hipLaunchKernelGGL(k_bin_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, counters_.p + C_BIN0, hessPerm_.p, n);
     const size_t nSlots = (size_t)HSLOTS * (size_t)n;
     const size_t nKeys = lin.ja.size() / 3 + 1; // buckets of the block positions
     detBegin(nSlots, 9, true, /*fillKeys=*/false, nKeys); // the kernel writes every key
-    const HessBins bins{ counters_.p + 4, hessPerm_.p, n };
+    const HessBins bins{ counters_.p + C_BIN0, hessPerm_.p, n };
     hipLaunchKernelGGL(k_contact_hessian, dim3(nblk(n, HESS_W) + NBINS), dim3(HESS_W), 0, stream, cv, bins, m, dbc_dev, projectDBC, dHat, kappa,
         BlockSink{ detVals_.p, detKey_.p, detRow_.p, detCount_.buf.p }, counters_.p);
     detReduceBlocks(nSlots, nKeys, lin.d_ia.p, a_dev);
     if (deferCheck) { // the flag goes to mapped host memory behind the pass; the caller looks at it after its next synchronisation (takeHessianError)
         readbackInit();
-        hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(1), 0, stream, (const int*)counters_.p, reinterpret_cast<int*>(readback_.dev + 15));
+        prims::launch_publish(counters_.p + C_MISS, &readback_.dev->hessError, 1, stream);
         hessErrPending_ = true;
         return;
     }
     int err[2];
+    static_assert(C_MISS == 0 && C_SWEEPS == 1, "downloaded as a pair");
     counters_.download(err, 2, stream);
-    if (std::getenv("IPCGPU_DEBUG")) std::fprintf(stderr, "[ipcgpu] barrier Hessian: %d stencils, %.2f Jacobi sweeps on average\n", n, (double)err[1] / n);
-    if (err[0]) throw StateError("barrier Hessian touches a node pair outside the CSR pattern: call set_pattern with the contact connectivity first");
+    if (std::getenv("IPCGPU_DEBUG")) std::fprintf(stderr, "[ipcgpu] barrier Hessian: %d stencils, %.2f Jacobi sweeps on average\n", n, (double)err[C_SWEEPS] / n);
+    if (err[C_MISS]) throw StateError("barrier Hessian touches a node pair outside the CSR pattern: call set_pattern with the contact connectivity first");
 }
 
 void HipContact::takeHessianError()
 {
     if (!hessErrPending_) return;
     hessErrPending_ = false;
-    if (*reinterpret_cast<const volatile int*>(readback_.p + 15))
+    if (const_cast<const volatile int&>(readback_.p->hessError))
         throw StateError("barrier Hessian touches a node pair outside the CSR pattern: call set_pattern with the contact connectivity first");
 }
 
@@ -2697,7 +2686,7 @@ bool HipContact::patternCovers(const HipLinSysSolver& lin)
     if (!n) return true;
     ContactView cv{ nActive_, nPara_, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, nullptr, d_xRest.p };
     CsrView m{ lin.d_ia.p, lin.d_ja.p };
-    counters_.alloc(16);
+    counters_.alloc(C_COUNT);
     counters_.zero(stream);
     hipLaunchKernelGGL(k_pattern_check, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, cv, m, counters_.p);
     int miss = 0;
@@ -2798,7 +2787,7 @@ void HipContact::frictionHessianAdd(const double* x_dev, const double* xt_dev, c
     if (!n) return;
     FrictionView fv{ n, d_fricSet.p, d_fricLambda.p, d_fricCoord.p, d_fricBasis.p };
     CsrView m{ lin.d_ia.p, lin.d_ja.p };
-    counters_.alloc(16);
+    counters_.alloc(C_COUNT);
     counters_.zero(stream);
     const size_t nKeys = lin.ja.size() / 3 + 1;
     detBegin(16 * (size_t)n, 9, true, true, nKeys);
@@ -3095,9 +3084,9 @@ void HipContact::stepBounds(const double* x_dev, const double* p_dev, double sla
         hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
             o, (const unsigned long long*)(ccdOut_.p + 3));
     if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p + 2);
-    hipLaunchKernelGGL(k_publish_u64x4, dim3(1), dim3(4), 0, stream, (const unsigned long long*)ccdOut_.p, readback_.dev);
+    prims::launch_publish(ccdOut_.p, readback_.dev->stepBounds, 4, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    const unsigned long long* h = readback_.p;
+    const unsigned long long* h = readback_.p->stepBounds;
     double filtered;
     std::memcpy(&filtered, &h[3], sizeof(filtered));
     std::memcpy(pMaxOut, &h[2], sizeof(double));
@@ -3116,7 +3105,7 @@ double HipContact::ccdFull(const HipMesh& mesh, const double* x_dev, const doubl
     ccdOut_.alloc(4);
     const unsigned long long init[2] = { ~0ull, ~0ull };
     HIP_CHECK(hipMemcpyAsync(ccdOut_.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
-    counters_.alloc(16);
+    counters_.alloc(C_COUNT);
     counters_.zero(stream);
     CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
     for (int pass = 0; pass < 2; ++pass) {
@@ -3158,9 +3147,9 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     hipLaunchKernelGGL(k_bbox_partial, dim3(nbV), dim3(BLOCK), 0, stream, mesh.nV, x_dev, bboxPartial_.p + offBoxV);
     hipLaunchKernelGGL(k_ref_bbox_swept_dev, dim3(nbS), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, x_dev, p_dev, (const double*)outDev, bboxPartial_.p + offBoxS);
     hipLaunchKernelGGL(k_ref_box_final, dim3(1), dim3(BLOCK), 0, stream, nbV, bboxPartial_.p + offBoxV, nbS, bboxPartial_.p + offBoxS, outDev,
-        reinterpret_cast<double*>(readback_.dev));
+        readback_.dev->refBox);
     HIP_CHECK(hipStreamSynchronize(stream));
-    const double* hb = reinterpret_cast<const double*>(readback_.p);
+    const double* hb = readback_.p->refBox;
     alpha = hb[0];
     if (alphaCapped) *alphaCapped = alpha;
     double lb[3] = { hb[1], hb[2], hb[3] }, rt[3] = { hb[4], hb[5], hb[6] };
@@ -3209,9 +3198,9 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
                 refCount + q * nC1, (const int*)nullptr, (int*)nullptr);
     exclusiveSum(refCount, refStart_.p, (int)(3 * nC1));
     readbackInit();
-    hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(1), 0, stream, (const int*)(refStart_.p + 3 * nC1 - 1), reinterpret_cast<int*>(readback_.dev));
+    prims::launch_publish(refStart_.p + 3 * nC1 - 1, &readback_.dev->refItems, 1, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    const int totalItems = *reinterpret_cast<const int*>(readback_.p);
+    const int totalItems = readback_.p->refItems;
     refItems_.ensure((size_t)REC * std::max(1, totalItems));
     for (int q = 0; q < 3; ++q)
         if (nPrims[q])
@@ -3219,14 +3208,13 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
                 refCount + q * nC1, (const int*)(refStart_.p + q * nC1), refItems_.p);
     refCount_.done();
     ccdOut_.alloc(4);
-    counters_.alloc(16);
-    // counters_: [0] queried pairs, [1] pairs that returned a time inside the step (the hit list)
+    counters_.alloc(C_COUNT);
     constexpr int HIT_CAP = 1 << 20;
     const bool twoPass = false; // (true: the limiting pair by a second run of the sweep, rounds 1-2; profiles/r03m_contact_bench_lds_jacobi_two_pass_ccd.json)
     if (!twoPass) ccdHits_.ensure(2 * (size_t)HIT_CAP);
     HIP_CHECK(hipMemsetAsync(ccdOut_.p, 0xFF, 3 * sizeof(unsigned long long), stream)); // "no time yet" = all ones
     counters_.zero(stream);
-    CcdOut o{ ccdOut_.p, ccdOut_.p + 1, twoPass ? nullptr : ccdHits_.p, counters_.p + 1, twoPass ? 0 : HIT_CAP };
+    CcdOut o{ ccdOut_.p, ccdOut_.p + 1, twoPass ? nullptr : ccdHits_.p, counters_.p + C_HITS, twoPass ? 0 : HIT_CAP };
     const RefLists L{ refStart_.p, refItems_.p, refStart_.p + nC1, refItems_.p, refStart_.p + 2 * nC1, refItems_.p };
     auto sweep = [&](int pass) {
         hipLaunchKernelGGL(k_ref_sweep_vertex, dim3(nblk(SWEEP_COOP * (long long)nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, pf,
@@ -3243,18 +3231,20 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
     unsigned long long h[2];
     int cnt[2];
     // minimum, pair and the two counters in one read-back through mapped memory
-    hipLaunchKernelGGL(k_publish_u64x4, dim3(1), dim3(2), 0, stream, (const unsigned long long*)ccdOut_.p, readback_.dev);
-    hipLaunchKernelGGL(k_publish_u64, dim3(1), dim3(1), 0, stream, reinterpret_cast<const unsigned long long*>(counters_.p), readback_.dev + 2);
+    static_assert(C_QUERIED == 0 && C_HITS == 1, "published as a pair");
+    prims::launch_publish(ccdOut_.p, readback_.dev->refCcd, 2, stream);
+    prims::launch_publish(counters_.p + C_QUERIED, readback_.dev->refCount, 2, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    h[0] = readback_.p[0];
-    h[1] = readback_.p[1];
-    std::memcpy(cnt, readback_.p + 2, sizeof(cnt));
-    if (!twoPass && cnt[1] > HIT_CAP) { // more hits than the list holds (never seen): the limiting pair by the second run after all
+    h[0] = readback_.p->refCcd[0];
+    h[1] = readback_.p->refCcd[1];
+    cnt[C_QUERIED] = readback_.p->refCount[C_QUERIED];
+    cnt[C_HITS] = readback_.p->refCount[C_HITS];
+    if (!twoPass && cnt[C_HITS] > HIT_CAP) { // more hits than the list holds (never seen): the limiting pair by the second run after all
         sweep(1);
         HIP_CHECK(hipMemcpyAsync(h, ccdOut_.p, sizeof(h), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
-    if (nCand) *nCand = cnt[0];
+    if (nCand) *nCand = cnt[C_QUERIED];
     double t;
     std::memcpy(&t, &h[0], sizeof(t));
     if (h[1] == ~0ull || !(t < alpha)) return alpha;
@@ -3281,7 +3271,7 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
             hipLaunchKernelGGL(k_points_in_tets<false>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
                 pf, counters_.p);
     };
-    counters_.alloc(16);
+    counters_.alloc(C_COUNT);
     if (nSF == 0 || nSFE == 0) {
         // A surface without triangles (point clouds, segment-only shapes): no edge can pierce a triangle of it, and no grid is built.  What such a surface can
         // still do is put a codimensional point inside a tetrahedron.
@@ -3299,9 +3289,9 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
     if (!haveBox_) measureBox(nV, x_dev);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
-    const int* stale = counters_.p + 2;
+    const int* stale = counters_.p + C_STALE;
     readbackInit();
-    const BuildReadback* rb = reinterpret_cast<const BuildReadback*>(readback_.p);
+    const BuildReadback* rb = &readback_.p->build;
     for (int attempt = 0; attempt < 3; ++attempt) {
         long long nCells;
         const Grid g = gridOverBox(mesh.avgEdgeLen, nCells);
@@ -3311,7 +3301,7 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
         const int capItems = (int)std::min<size_t>(gridItems_.n / REC, (size_t)INT_MAX);
         counters_.zero(stream);
         hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
-        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + 2);
+        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, g, 1, counters_.p + C_STALE);
         // (edges only, in cells [0, nCells): the kernel's offset of the edge cells is its nCells argument)
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 0, capItems, stale,
             gridCount, (const int*)nullptr, (int*)nullptr);
@@ -3326,7 +3316,7 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
             hipLaunchKernelGGL(k_intersect<false>, dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
                 gridItems_.p, counters_.p, capItems);
         pointsInTets();
-        hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + nCells, box_dev, reinterpret_cast<BuildReadback*>(readback_.dev));
+        hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + nCells, box_dev, &readback_.dev->build);
         HIP_CHECK(hipStreamSynchronize(stream));
         for (int c = 0; c < 6; ++c) box_[c] = rb->box[c];
         if (rb->cnt[2]) continue; // stale grid: nothing ran, once more over the fresh box
@@ -3358,19 +3348,19 @@ void HipContact::closeStencils(const double* x_dev, double dTol, std::vector<std
     for (;;) {
         closeIdx_.ensure((size_t)cap);
         closeVal_.ensure((size_t)cap);
-        counters_.alloc(16);
+        counters_.alloc(C_COUNT);
         counters_.zero(stream);
-        if (n) hipLaunchKernelGGL(k_close_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_active.p, x_dev, dTol, cap, closeIdx_.p, closeVal_.p, counters_.p);
+        if (n) hipLaunchKernelGGL(k_close_stencils, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_active.p, x_dev, dTol, cap, closeIdx_.p, closeVal_.p, counters_.p + C_CLOSE);
         if (nCheck) {
             ContactView cv{ nActive_, nPara_, d_active.p, d_para.p, d_paraEIEJ.p, d_SFE.p, nullptr, d_xRest.p };
             CsrView m{ lin->d_ia.p, lin->d_ja.p };
-            hipLaunchKernelGGL(k_pattern_check, dim3(nblk(nCheck, BLOCK)), dim3(BLOCK), 0, stream, cv, m, counters_.p + 2);
+            hipLaunchKernelGGL(k_pattern_check, dim3(nblk(nCheck, BLOCK)), dim3(BLOCK), 0, stream, cv, m, counters_.p + C_CLOSE_MISS);
         }
-        hipLaunchKernelGGL(k_publish_u64x4, dim3(1), dim3(2), 0, stream, reinterpret_cast<const unsigned long long*>(counters_.p), readback_.dev); // counters 0 .. 3
+        prims::launch_publish(counters_.p, readback_.dev->close, C_CLOSE_END, stream);
         HIP_CHECK(hipStreamSynchronize(stream));
-        const int* h = reinterpret_cast<const int*>(readback_.p);
-        const int cnt = h[0];
-        if (covers) *covers = h[2] ? 0 : 1;
+        const int* h = readback_.p->close;
+        const int cnt = h[C_CLOSE];
+        if (covers) *covers = h[C_CLOSE_MISS] ? 0 : 1;
         if (cnt > cap) {
             cap = cnt + cnt / 4;
             continue;

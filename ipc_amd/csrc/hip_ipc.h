@@ -23,6 +23,7 @@
 #include "report_plan.h"
 #include "rod_kernels.h"
 #include "rod_plan.h"
+#include "scalar_slots.h"
 #include "shell_kernels.h"
 #include "shell_limit_kernels.h"
 #include "shell_limit_plan.h"
@@ -465,7 +466,13 @@ public:
     void setDBCVertices(); // AnimScripter::setDBCVertices, AnimScripter.cpp:58-110
     bool dbcGroupMotion(); // adds the active groups' motion to d_searchDir; true if any
     double rotCenter[3] = { 0, 0, 0 };
+    // the scalar board (scalar_slots.h): d_scalar holds one double per ScalarSlot, h_scalar.p[S] is the published copy of d_scalar.p[S] and nothing else
     PinnedBuf<double> h_scalar;
+    double* slot(ScalarSlot s) const { return d_scalar.p + s; }
+    double* slotMapped(ScalarSlot s) const { return h_scalar.dev + s; } // the slot's place in the mirror as kernels address it
+    double published(ScalarSlot s) const { return h_scalar.p[s]; } // valid behind a publish of s and a synchronisation
+    void publish(ScalarSlot first, int count = 1); // slots [first, first + count) to their places in the mirror: one launch, no synchronisation
+    double readScalar(ScalarSlot s); // publish(s), synchronise, published(s)
     PinnedBuf<int> h_flag;
     int innerIterAmt = 0, globalIterNum = 0, k = 0;
     double lastEnergyVal = 0, lastStepSize = 0, lastAlphaFeasible = 0;
@@ -504,7 +511,6 @@ public:
     void* allreduceStreamUser = nullptr; // separate slots: the two hooks can be set in any order
     void reduceSum(double* dev, long long n);
     void reduceMin(double* dev, long long n);
-    double readScalar(const double* dev);
     PatchPlan patch; // atomic-free assembly plan for the current pattern
     int patchVersion = -1;
     void ensurePatchPlan();

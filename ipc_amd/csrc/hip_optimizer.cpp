@@ -361,9 +361,9 @@ void HipOptimizer::init(double dt_, bool withGravity)
     d_minusG.alloc(n3);
     d_x0.alloc(n3);
     d_partial.alloc(std::max((size_t)std::max(mesh.nT, mesh.nV), codimPartials()) / 256 + 2);
-    d_scalar.alloc(8);
+    d_scalar.alloc(S_COUNT);
     d_flag.alloc(2); // [0] the inversion flag of the stepper, [1] a second one for batches that test two states (beginTimestep)
-    h_scalar.alloc(8);
+    h_scalar.alloc(S_COUNT);
     h_flag.alloc(2);
     HIP_CHECK(hipMemcpyAsync(d_xPrev.p, mesh.d_x.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(d_xStepStart.p, mesh.d_x.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -454,8 +454,8 @@ double HipOptimizer::neumannEnergy()
     for (const auto& g : nbcGroups) {
         if (stepStartTime < g->t0 || stepStartTime >= g->t1) continue;
         const double c[3] = { dtSq * g->a[0], dtSq * g->a[1], dtSq * g->a[2] };
-        launch_nbc_energy(g->n, g->d_ids.p, mesh.d_dbc.p, mesh.d_mass.p, mesh.d_x.p, c, d_scalar.p + 5, stream);
-        E -= readScalar(d_scalar.p + 5);
+        launch_nbc_energy(g->n, g->d_ids.p, mesh.d_dbc.p, mesh.d_mass.p, mesh.d_x.p, c, slot(S_SCRATCH), stream);
+        E -= readScalar(S_SCRATCH);
     }
     return E;
 }
@@ -556,24 +556,28 @@ void HipOptimizer::hookReduce(double* dev, long long n, int op)
     HIP_CHECK(hipStreamSynchronize(stream));
     if (allreduce(allreduceUser, dev, n, op) != 0) throw HipError("all-reduce hook failed");
 }
-double HipOptimizer::readScalar(const double* dev)
+void HipOptimizer::publish(ScalarSlot first, int count)
 {
-    launch_publish(dev, h_scalar.dev, 2, stream);
+    launch_publish(slot(first), slotMapped(first), count, stream);
+}
+double HipOptimizer::readScalar(ScalarSlot s)
+{
+    publish(s);
     HIP_CHECK(hipStreamSynchronize(stream));
-    return h_scalar.p[0];
+    return published(s);
 }
 
 double HipOptimizer::computeEnergyVal()
 {
-    enqueueElasticEnergy(rank == 0, d_scalar.p);
-    reduceSum(d_scalar.p, 1);
+    enqueueElasticEnergy(rank == 0, slot(S_E_ITERATE));
+    reduceSum(slot(S_E_ITERATE), 1);
     // the barrier energy of the self-contact sets is enqueued behind the elastic one and read back with it: one synchronisation instead of two (round 6; the
     // reduction of the elastic partial sums is on the stream before the contact kernel reuses d_partial)
-    const bool contactQueued = selfCollision && contact->energyEnqueue(mesh.d_x.p, dHat, kappa, d_partial, d_scalar.p + 4, d_scalar.p, h_scalar.dev, 10);
-    if (!(contactQueued && contact->publishedByEnergy())) launch_publish(d_scalar.p, h_scalar.dev, 10, stream); // d_scalar[0 .. 4]
+    const bool contactQueued = selfCollision && contact->energyEnqueue(mesh.d_x.p, dHat, kappa, d_partial, slot(S_CONTACT_E), slot(S_E_ITERATE), slotMapped(S_E_ITERATE), slotSpan(S_E_ITERATE, S_CONTACT_E));
+    if (!(contactQueued && contact->publishedByEnergy())) publish(S_E_ITERATE, slotSpan(S_E_ITERATE, S_CONTACT_E));
     HIP_CHECK(hipStreamSynchronize(stream));
-    double E = h_scalar.p[0];
-    const double Econtact = contactQueued ? h_scalar.p[4] : 0.0;
+    double E = published(S_E_ITERATE);
+    const double Econtact = contactQueued ? published(S_CONTACT_E) : 0.0;
     if (!nbcGroups.empty()) E += neumannEnergy();
     // barrier terms over the current constraint sets (Optimizer.cpp:3252-3353); replicated on every rank
     for (auto& h : planes) E += h->energy(mesh.d_x.p, dHat, kappa);
@@ -581,12 +585,12 @@ double HipOptimizer::computeEnergyVal()
     if (fricDHat > 0.0) { // lagged friction (Optimizer.cpp:3357-3377)
         for (auto& h : planes)
             if (h->friction > 0.0) E += h->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat);
-        if (selfCollision && selfFric > 0.0) E += contact->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, d_partial, d_scalar.p + 4);
+        if (selfCollision && selfFric > 0.0) E += contact->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, d_partial, slot(S_FRICTION_E));
     }
     if (dampingStiff > 0.0) E += dampingEnergy();
     if (rhoDBC && !tpIds.empty()) { // augmentMDBCEnergy (Optimizer.cpp:3402-3404)
-        launch_mdbc_reduce(mdbc(), mesh.d_x.p, rhoDBC, 0, d_scalar.p + 5, stream);
-        E += readScalar(d_scalar.p + 5);
+        launch_mdbc_reduce(mdbc(), mesh.d_x.p, rhoDBC, 0, slot(S_SCRATCH), stream);
+        E += readScalar(S_SCRATCH);
     }
     return E;
 }
@@ -637,8 +641,8 @@ double HipOptimizer::dampingEnergy()
     d_dampAdx.ensure(n3);
     launch_damp_dx(mesh.nV, mesh.d_dbc.p, 0, 1, mesh.d_x.p, d_xPrev.p, d_dampDx.p, stream);
     launch_csr_symv(n3, lin.d_ia.p, lin.d_ja.p, d_damp.p, d_dampDx.p, d_dampAdx.p, stream);
-    launch_dot_scaled(n3, d_dampDx.p, d_dampAdx.p, 0.5, d_scalar.p + 6, stream);
-    return readScalar(d_scalar.p + 6);
+    launch_dot_scaled(n3, d_dampDx.p, d_dampAdx.p, 0.5, slot(S_DAMPING_E), stream);
+    return readScalar(S_DAMPING_E);
 }
 void HipOptimizer::dampingGradientAdd(bool projectDBC, double* grad_dev)
 {
@@ -710,7 +714,7 @@ bool HipOptimizer::nextSubproblem()
         computePrecondMtr(true, true);
         computeSearchDir();
         enqueueDirNorm();
-        if (readScalar(d_scalar.p + 3) < targetGRes) updateFricDHat = false;
+        if (readScalar(S_DIR_NORM) < targetGRes) updateFricDHat = false;
         if (fricIterAmt > 0 && fricIterI >= fricIterAmt) updateFricDHat = false;
     }
     if (!updateDHat && !updateFricDHat) return false;
@@ -933,10 +937,10 @@ void HipOptimizer::initKappa()
     if (dampingStiff > 0.0) dampingGradientAdd(true, d_gradient.p); // still part of it (:3519-3540)
     d_minusG.zero(stream);
     barrierGradientAdd(true, 1.0, true, d_minusG.p); // also clears the DBC rows (:2275-2277)
-    launch_dot2(n3, d_minusG.p, d_gradient.p, d_partial.p, (int)d_partial.n, d_scalar.p + 6, stream);
-    launch_publish(d_scalar.p + 6, h_scalar.dev, 4, stream); // two doubles = four words
+    launch_dot2(n3, d_minusG.p, d_gradient.p, d_partial.p, (int)d_partial.n, slot(S_KAPPA_NUM), stream);
+    publish(S_KAPPA_NUM, slotSpan(S_KAPPA_NUM, S_KAPPA_DEN));
     HIP_CHECK(hipStreamSynchronize(stream));
-    const double num = h_scalar.p[0], den = h_scalar.p[1];
+    const double num = published(S_KAPPA_NUM), den = published(S_KAPPA_DEN);
     double minKappa = -num / den;
     if (minKappa > 0.0) kappa = minKappa;
     minKappa = kappaFloor();
@@ -1345,10 +1349,10 @@ bool HipOptimizer::checkInversion(bool meshQuery)
     HIP_CHECK(hipStreamSynchronize(stream));
     int f = h_flag.p[0];
     if (worldSize > 1) {
-        h_scalar.p[1] = (double)f;
-        HIP_CHECK(hipMemcpyAsync(d_scalar.p + 1, h_scalar.p + 1, sizeof(double), hipMemcpyHostToDevice, stream));
-        reduceSum(d_scalar.p + 1, 1);
-        f = readScalar(d_scalar.p + 1) != 0.0;
+        h_scalar.p[S_INVERSION_SUM] = (double)f; // (the one host write into the mirror: its own position is the pinned staging word of the upload)
+        HIP_CHECK(hipMemcpyAsync(slot(S_INVERSION_SUM), h_scalar.p + S_INVERSION_SUM, sizeof(double), hipMemcpyHostToDevice, stream));
+        reduceSum(slot(S_INVERSION_SUM), 1);
+        f = readScalar(S_INVERSION_SUM) != 0.0;
     }
     return f == 0;
 }
@@ -1369,10 +1373,10 @@ double HipOptimizer::filterStepSize(const double* p_dev, double stepSize)
 {
     // Energy.cpp:565-581: min over elements of the root, applied only when 0 < min < stepSize
     if (!mesh.needElemInvSafeGuard()) return stepSize; // :567 needElemInvSafeGuard
-    launch_fill(d_scalar.p + 2, 1, 1e20, stream);
-    launch_inversion_step(view(), p_dev, 0.2, stepSize, d_scalar.p + 2, stream);
-    reduceMin(d_scalar.p + 2, 1);
-    const double t = readScalar(d_scalar.p + 2);
+    launch_fill(slot(S_STEP_FILTER), 1, 1e20, stream);
+    launch_inversion_step(view(), p_dev, 0.2, stepSize, slot(S_STEP_FILTER), stream);
+    reduceMin(slot(S_STEP_FILTER), 1);
+    const double t = readScalar(S_STEP_FILTER);
     if (t > 0.0 && t < stepSize) stepSize = t;
     return stepSize;
 }
@@ -1413,11 +1417,11 @@ void HipOptimizer::speculativeAssembly()
     specAsmValid = true;
 }
 
-// |p|_inf of the search direction into d_scalar[3] (convergence test of the next pass, Optimizer.cpp:1869-1879): enqueued, the caller publishes or reads it
+// |p|_inf of the search direction into S_DIR_NORM (convergence test of the next pass, Optimizer.cpp:1869-1879): enqueued, the caller publishes or reads it
 void HipOptimizer::enqueueDirNorm()
 {
-    launch_fill(d_scalar.p + 3, 1, 0.0, stream);
-    launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
+    launch_fill(slot(S_DIR_NORM), 1, 0.0, stream);
+    launch_max_abs(3 * mesh.nV, d_searchDir.p, slot(S_DIR_NORM), stream);
 }
 
 void HipOptimizer::computeSearchDir()
@@ -1442,13 +1446,13 @@ void HipOptimizer::computeSearchDir()
         if (lin.factorizeSolve(rhs, d_searchDir.p, /*wait=*/false, signInSolver)) {
             // ten launches (fifteen before round 4: the resets, the copy + step-size + step and the two read-backs are one launch each now)
             launch_iter_reset(d_scalar.p, d_flag.p, stream); // (zeroes the slot of |p|_inf with the others: no enqueueDirNorm(), whose fill would be one launch more)
-            launch_max_abs(3 * mesh.nV, d_searchDir.p, d_scalar.p + 3, stream);
-            if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
-            enqueueElasticEnergy(true, d_scalar.p);
-            launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, mesh.needElemInvSafeGuard(), d_scalar.p + 6, stream);
+            launch_max_abs(3 * mesh.nV, d_searchDir.p, slot(S_DIR_NORM), stream);
+            if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, slot(S_STEP_FILTER), stream); // (the trial step starts at 1)
+            enqueueElasticEnergy(true, slot(S_E_ITERATE));
+            launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, slot(S_STEP_FILTER), mesh.needElemInvSafeGuard(), slot(S_TRIAL_ALPHA), stream);
             if (mesh.needElemInvSafeGuard()) launch_check_inversion(view(), d_flag.p, stream);
-            enqueueElasticEnergy(true, d_scalar.p + 1);
-            launch_publish2(d_flag.p, h_flag.dev, 1, d_scalar.p, h_scalar.dev, 14, stream); // the inversion flag + 7 doubles
+            enqueueElasticEnergy(true, slot(S_E_TRIAL));
+            launch_publish2(d_flag.p, h_flag.dev, 1, slot(S_E_ITERATE), slotMapped(S_E_ITERATE), slotSpan(S_E_ITERATE, S_TRIAL_ALPHA), stream); // the inversion flag + the scalars
             // the ONE synchronisation waits for the read-back, not for the stream: behind it runs the next pass's assembly at the trial point, enqueued ahead
             if (!evTail) HIP_CHECK(hipEventCreateWithFlags(&evTail, hipEventDisableTiming));
             HIP_CHECK(hipEventRecord(evTail, stream));
@@ -1456,11 +1460,11 @@ void HipOptimizer::computeSearchDir()
             HIP_CHECK(hipEventSynchronize(evTail));
             t.nosync = specAsmValid;
             if (lin.lastPivotsOk()) {
-                cachedE0 = h_scalar.p[0];
-                cachedTrialE = h_scalar.p[1];
-                cachedFilter = h_scalar.p[2];
-                cachedDist = h_scalar.p[3];
-                cachedAlpha = h_scalar.p[6];
+                cachedE0 = published(S_E_ITERATE);
+                cachedTrialE = published(S_E_TRIAL);
+                cachedFilter = published(S_STEP_FILTER);
+                cachedDist = published(S_DIR_NORM);
+                cachedAlpha = published(S_TRIAL_ALPHA);
                 cachedTrialInverted = mesh.needElemInvSafeGuard() && h_flag.p[0] != 0;
                 cachedDistValid = cachedE0Valid = cachedTrialValid = true;
                 return;
@@ -1482,11 +1486,11 @@ void HipOptimizer::computeSearchDir()
             if (ok) {
                 chamberGasCorrect(elasticCoef(), projDBC, d_searchDir.p); // (enqueued behind the sweeps; a bad pivot ends in the diagonal fallback below, which ignores the rank-k term)
                 enqueueDirNorm();
-                launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
+                publish(S_DIR_NORM);
                 HIP_CHECK(hipStreamSynchronize(stream));
                 ok = lin.lastPivotsOk();
                 if (ok) {
-                    cachedDist = h_scalar.p[3];
+                    cachedDist = published(S_DIR_NORM);
                     cachedDistValid = true;
                 }
             }
@@ -1504,14 +1508,14 @@ void HipOptimizer::computeSearchDir()
         // (convergence test of the next pass, Optimizer.cpp:1869-1879), the inversion step filter (:1887) and E at the current iterate
         // (line search entry, :2681)
         enqueueDirNorm();
-        launch_fill(d_scalar.p + 2, 1, 1e20, stream);
-        if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // (the trial step starts at 1)
-        enqueueElasticEnergy(true, d_scalar.p);
-        launch_publish(d_scalar.p, h_scalar.dev, 8, stream); // 4 doubles = 8 words
+        launch_fill(slot(S_STEP_FILTER), 1, 1e20, stream);
+        if (mesh.needElemInvSafeGuard()) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, slot(S_STEP_FILTER), stream); // (the trial step starts at 1)
+        enqueueElasticEnergy(true, slot(S_E_ITERATE));
+        publish(S_E_ITERATE, slotSpan(S_E_ITERATE, S_DIR_NORM));
         HIP_CHECK(hipStreamSynchronize(stream));
-        cachedE0 = h_scalar.p[0];
-        cachedFilter = h_scalar.p[2];
-        cachedDist = h_scalar.p[3];
+        cachedE0 = published(S_E_ITERATE);
+        cachedFilter = published(S_STEP_FILTER);
+        cachedDist = published(S_DIR_NORM);
         cachedDistValid = cachedE0Valid = true;
     }
     else {
@@ -1519,9 +1523,9 @@ void HipOptimizer::computeSearchDir()
         // come back yet (several processes, or the diagonal fallback just replaced the direction)
         if (!cachedDistValid) {
             enqueueDirNorm();
-            launch_publish(d_scalar.p + 3, h_scalar.dev + 3, 2, stream);
+            publish(S_DIR_NORM);
             HIP_CHECK(hipStreamSynchronize(stream));
-            cachedDist = h_scalar.p[3];
+            cachedDist = published(S_DIR_NORM);
             cachedDistValid = true;
         }
         if (selfCollision) contact->takeHessianError();
@@ -1606,11 +1610,11 @@ void HipOptimizer::lineSearch(double& stepSize)
                 launch_check_inversion(view(), d_flag.p, stream);
                 launch_publish(d_flag.p, h_flag.dev, 1, stream);
             }
-            enqueueElasticEnergy(true, d_scalar.p);
-            launch_publish(d_scalar.p, h_scalar.dev, 2, stream);
+            enqueueElasticEnergy(true, slot(S_E_ITERATE));
+            publish(S_E_ITERATE);
             HIP_CHECK(hipStreamSynchronize(stream));
             if (mesh.needElemInvSafeGuard()) inverted = h_flag.p[0];
-            testingE = h_scalar.p[0];
+            testingE = published(S_E_ITERATE);
             done = !inverted && !(testingE > lastEnergyVal);
         }
         if (done) {
@@ -1722,16 +1726,16 @@ void HipOptimizer::beginTimestep()
         setDBCVertices();
         launch_twist_dir(nHandles, d_handleIds.p, d_handleAng.p, rotCenter[1], rotCenter[2], mesh.d_x.p, d_searchDir.p, stream);
         buildTargetPositions(/*deferTolerance=*/true);
-        launch_fill(d_scalar.p + 2, 1, 1e20, stream);
-        if (guard) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, d_scalar.p + 2, stream); // filterStepSize(p, 1.0) ...
-        launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, d_scalar.p + 2, guard, d_scalar.p + 6, stream); // ... applied by its rule; x0 = x, x += step p
+        launch_fill(slot(S_STEP_FILTER), 1, 1e20, stream);
+        if (guard) launch_inversion_step(view(), d_searchDir.p, 0.2, 1.0, slot(S_STEP_FILTER), stream); // filterStepSize(p, 1.0) ...
+        launch_trial_step_fused(3 * mesh.nV, mesh.d_x.p, d_x0.p, d_searchDir.p, slot(S_STEP_FILTER), guard, slot(S_TRIAL_ALPHA), stream); // ... applied by its rule; x0 = x, x += step p
         if (guard) launch_check_inversion(view(), d_flag.p + 1, stream);
-        enqueueElasticEnergy(true, d_scalar.p); // computeEnergyVal() of this configuration: elasticity + inertia
-        launch_publish2(d_flag.p, h_flag.dev, 2, d_scalar.p, h_scalar.dev, 14, stream);
+        enqueueElasticEnergy(true, slot(S_E_ITERATE)); // computeEnergyVal() of this configuration: elasticity + inertia
+        launch_publish2(d_flag.p, h_flag.dev, 2, slot(S_E_ITERATE), slotMapped(S_E_ITERATE), slotSpan(S_E_ITERATE, S_TRIAL_ALPHA), stream);
         HIP_CHECK(hipStreamSynchronize(stream));
         if (h_flag.p[0]) throw StateError("element inversion before scripted motion (Optimizer.cpp:517-522)");
         finishTolerance();
-        double stepSize = h_scalar.p[6];
+        double stepSize = published(S_TRIAL_ALPHA);
         bool energyKnown = true;
         if (h_flag.p[1]) { // inverted behind the filtered step: the halving loop (AnimScripter.cpp:2172-2180) from here
             energyKnown = false;
@@ -1742,7 +1746,7 @@ void HipOptimizer::beginTimestep()
         completedStep = stepSize;
         d_searchDir.zero(stream);
         initSubProblem();
-        lastEnergyVal = energyKnown ? h_scalar.p[0] : computeEnergyVal(); // Optimizer.cpp:1609
+        lastEnergyVal = energyKnown ? published(S_E_ITERATE) : computeEnergyVal(); // Optimizer.cpp:1609
         k = 0;
         return;
     }
@@ -1871,8 +1875,8 @@ void HipOptimizer::finishTolerance()
 double HipOptimizer::computeCompletedStepSize()
 {
     if (dist2Tol == 0.0 || tpIds.empty()) return completedStep = 1.0;
-    launch_mdbc_reduce(mdbc(), mesh.d_x.p, 0.0, 1, d_scalar.p + 5, stream);
-    const double sqNorm = readScalar(d_scalar.p + 5);
+    launch_mdbc_reduce(mdbc(), mesh.d_x.p, 0.0, 1, slot(S_SCRATCH), stream);
+    const double sqNorm = readScalar(S_SCRATCH);
     return completedStep = 1.0 - std::sqrt(sqNorm / (dist2Tol * 1.0e6));
 }
 
@@ -1891,7 +1895,7 @@ void HipOptimizer::dirichletPenaltyUpdate()
     else if (completed < lastMove && rhoDBC < 1.0e8) rhoDBC *= 2.0;
     else {
         enqueueDirNorm();
-        if (readScalar(d_scalar.p + 3) < CN_MBC) { // safeToPull
+        if (readScalar(S_DIR_NORM) < CN_MBC) { // safeToPull
             if (completed < 0.99 && rhoDBC < 1.0e8) rhoDBC *= 2.0;
             else launch_mdbc_lambda(mdbc(), mesh.d_x.p, rhoDBC, stream); // updateLambda (AnimScripter.cpp:2339-2346)
         }
@@ -1905,7 +1909,7 @@ bool HipOptimizer::newtonIter()
     if (k && cachedDistValid) distToOpt_PN = cachedDist; // read back with the last solve
     else if (k) {
         enqueueDirNorm();
-        distToOpt_PN = readScalar(d_scalar.p + 3);
+        distToOpt_PN = readScalar(S_DIR_NORM);
     }
     else distToOpt_PN = 0.0; // (the test needs k > 0: nothing to measure in the first pass of a time step)
     cachedDistValid = false;
@@ -1970,10 +1974,10 @@ bool HipOptimizer::newtonIter()
                 // inversion filter, partial CCD and surface speed in one batch: the filter's root stays on the device and bounds the CCD there
                 const bool filter = mesh.needElemInvSafeGuard(); // Energy.cpp:567 needElemInvSafeGuard
                 if (filter) {
-                    launch_fill(d_scalar.p + 2, 1, 1e20, stream);
-                    launch_inversion_step(view(), d_searchDir.p, 0.2, alpha, d_scalar.p + 2, stream);
+                    launch_fill(slot(S_STEP_FILTER), 1, 1e20, stream);
+                    launch_inversion_step(view(), d_searchDir.p, 0.2, alpha, slot(S_STEP_FILTER), stream);
                 }
-                contact->stepBounds(mesh.d_x.p, d_searchDir.p, slackness_m, alpha, filter ? d_scalar.p + 2 : nullptr, &alpha, lastCCDPair, &pMax);
+                contact->stepBounds(mesh.d_x.p, d_searchDir.p, slackness_m, alpha, filter ? slot(S_STEP_FILTER) : nullptr, &alpha, lastCCDPair, &pMax);
             }
             else {
                 alpha = contact->ccdPartial(mesh.d_x.p, d_searchDir.p, slackness_m, alpha, lastCCDPair);

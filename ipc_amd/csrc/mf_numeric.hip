@@ -24,6 +24,7 @@
 // No vendor BLAS is involved: rocSOLVER's potrf / rocBLAS' trsm+syrk cost ~150 tiny launches per front.
 #include <climits>
 #include "mf_kernels.h"
+#include "device_prims.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -35,7 +36,6 @@ namespace ipcgpu {
 
 namespace {
 
-__global__ void k_publish_flag(const int* __restrict__ flag, int* __restrict__ mapped) { mapped[0] = flag[0]; }
 // (only behind a factorisation that launched no fused front, whose workgroup 0 clears the next factorisation's flag otherwise)
 __global__ void k_clear_flag(int* __restrict__ flag) { flag[0] = 0; }
 
@@ -1859,7 +1859,7 @@ bool MfNumeric::factorize(const double* a_dev)
         // forest that was not cut (several bodies, world > number of roots) lives on one rank alone -- one double
         allreduceFlag();
     }
-    hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(1), 0, stream_, curFlag(), hflag_.dev); // mapped pinned memory: no blit
+    prims::launch_publish(curFlag(), hflag_.dev, 1, stream_); // mapped pinned memory: no blit
     HIP_CHECK(hipStreamSynchronize(stream_));
 #ifdef MF_FUSED_PROBE
     {
@@ -1914,7 +1914,7 @@ bool MfNumeric::factorizeSolve(const double* a_dev, const double* rhs_dev, doubl
     if (!fwdJoined_) HIP_CHECK(hipEventRecord(evFwdDone_, fwd_));
     // the backward sweep follows the root's forward result; enqueued before the flag is looked at (a failed pivot makes x meaningless,
     // the caller falls back to the diagonal preconditioner as after factorize() == false).  The pivot flag is final here: the first launch of the
-    // sweep carries it to its mapped slot (a launch of its own, k_publish_flag, used to sit between the two sweeps)
+    // sweep carries it to its mapped slot (a launch of its own used to sit between the two sweeps)
     if (!fwdJoined_) HIP_CHECK(hipStreamWaitEvent(stream_, evFwdDone_, 0));
     enqueueBackward(x_dev, /*publishFlag=*/true);
     if (!wait) return true;

@@ -1,6 +1,7 @@
 // GPU multifrontal Cholesky: the triangular sweeps (forward level by level up the assembly tree, backward down it) on the factor mf_numeric.hip leaves in HBM.
 // Split out of mf_numeric.hip in round 5; the kernels and their launch order are unchanged.
 #include "mf_kernels.h"
+#include "device_prims.h"
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -30,8 +31,6 @@ __global__ void k_permute_rhs(int nn, const int* __restrict__ newOf, const doubl
         bp[3 * newOf[v] + d] = negate ? -b[i] : b[i];
     }
 }
-// (only where the backward sweep launches nothing that could carry the flag: an empty tree)
-__global__ void k_publish_flag_late(const int* __restrict__ flag, int* __restrict__ mapped) { mapped[0] = flag[0]; }
 // (sharded runs only: there the solution is summed over the ranks in elimination order first)
 __global__ void k_unpermute_x(int nn, const int* __restrict__ newOf, const double* __restrict__ xp, double* __restrict__ x)
 {
@@ -680,7 +679,7 @@ void MfNumeric::enqueueBackward(double* x_dev, bool publishFlag)
         }
     }
 #endif
-    if (!published) hipLaunchKernelGGL(k_publish_flag_late, dim3(1), dim3(1), 0, stream_, out.flag, hflag_.dev); // (a tree without a single front)
+    if (!published) prims::launch_publish(out.flag, hflag_.dev, 1, stream_); // (a tree without a single front: the backward sweep launches nothing that could carry the flag)
     if (!direct) {
         if (world_ > 1) reduceSolution(); // every rank holds the solution of the fronts it executed: sum of the masked parts (mf_exchange.hip; nodeExec_ exists on sharded runs only)
         hipLaunchKernelGGL(k_unpermute_x, dim3((n3 + 255) / 256), dim3(256), 0, stream_, sym.nn, newOf_.p, xsol_.p, x_dev);

@@ -1,6 +1,7 @@
 // Launchers of the per-tetrahedron neo-Hookean kernels and the nodal helper kernels (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "common.h"
 
 namespace ipcgpu {
 
@@ -64,12 +65,24 @@ void launch_trial_step(int n3, const double* x0, const double* p, const double* 
 void launch_max_abs(int n, const double* v, double* out /*preset 0*/, hipStream_t s);
 // round 4: the small launches of a contact-free iteration's tail, fused (x -> x0 + alpha + step; scalar resets; the two read-backs)
 void launch_trial_step_fused(int n3, double* x, double* x0, const double* p, const double* filterMin, bool useFilter, double* alphaOut, hipStream_t s);
-void launch_iter_reset(double* scalar, int* flag, hipStream_t s);
-void launch_publish2(const void* a, void* da, int na, const void* b, void* db, int nb, hipStream_t s);
+void launch_iter_reset(double* scalar, int* flag, hipStream_t s); // scalar: the board's base (scalar_slots.h); resets S_DIR_NORM and S_STEP_FILTER
 void launch_fill(double* p, size_t n, double v, hipStream_t s);
 void launch_negate(int n, const double* in, double* out, hipStream_t s);
-// copies nWords 4-byte words from device memory into mapped pinned host memory (a ~24 us blit per scalar read-back otherwise)
-void launch_publish(const void* src_dev, void* dst_mapped, int nWords, hipStream_t s);
+// Read-backs through mapped pinned host memory (a ~24 us blit per scalar read-back otherwise): `count` elements of T from device memory to their
+// mapped place, as 32-bit words by one wave (prims::k_publish_words).  The typed forms work out the word count.
+void launch_publish_words(const void* src_dev, void* dst_mapped, int nWords, hipStream_t s);
+// the same for two ranges in one launch (the inversion flags and the scalars of the contact-free tails)
+void launch_publish2_words(const void* a, void* da, int na, const void* b, void* db, int nb, hipStream_t s);
+template <class T>
+inline void launch_publish(const T* src_dev, T* dst_mapped, int count, hipStream_t s)
+{
+    launch_publish_words(src_dev, dst_mapped, publish_words<T>(count), s);
+}
+template <class A, class B>
+inline void launch_publish2(const A* a, A* da, int na, const B* b, B* db, int nb, hipStream_t s)
+{
+    launch_publish2_words(a, da, publish_words<A>(na), b, db, publish_words<B>(nb), s);
+}
 void launch_colmajor_to_aos(int nV, const double* src, double* dst, hipStream_t s);
 void launch_aos_to_colmajor(int nV, const double* src, double* dst, hipStream_t s);
 // symmetric-upper CSR times vector and diagonal preconditioner (LinSysSolver.hpp:238-253, 411-420)

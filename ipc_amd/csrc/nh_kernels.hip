@@ -13,6 +13,7 @@
 // the sigma-space A block (3x3, PSD-clamped) and the three 2x2 B blocks (makePD2d-clamped)
 // -- the same numbers, ~2.5 kflop instead of ~7 kflop per element.
 #include "nh_device.h"
+#include "scalar_slots.h"
 #include <algorithm>
 #include <cfloat>
 #include <cstdlib>
@@ -516,8 +517,8 @@ __global__ void k_trial_step_fused(int n, double* __restrict__ x, double* __rest
 // the scalars a contact-free Newton iteration accumulates into behind the solve, reset by one launch: |p|_inf = 0, the step filter's minimum = 1e20, inversion flag = 0
 __global__ void k_iter_reset(double* __restrict__ scalar, int* __restrict__ flag)
 {
-    scalar[3] = 0.0;
-    scalar[2] = 1e20;
+    scalar[S_DIR_NORM] = 0.0;
+    scalar[S_STEP_FILTER] = 1e20;
     flag[0] = 0;
 }
 // the inversion flag and the scalars to their mapped host buffers in one launch
@@ -934,7 +935,7 @@ void launch_trial_step_fused(int n3, double* x, double* x0, const double* p, con
     hipLaunchKernelGGL(k_trial_step_fused, dim3(std::max(nblk(n3, BLOCK), 1)), dim3(BLOCK), 0, s, n3, x, x0, p, filterMin, useFilter ? 1 : 0, alphaOut);
 }
 void launch_iter_reset(double* scalar, int* flag, hipStream_t s) { hipLaunchKernelGGL(k_iter_reset, dim3(1), dim3(1), 0, s, scalar, flag); }
-void launch_publish2(const void* a, void* da, int na, const void* b, void* db, int nb, hipStream_t s)
+void launch_publish2_words(const void* a, void* da, int na, const void* b, void* db, int nb, hipStream_t s)
 {
     hipLaunchKernelGGL(k_publish2, dim3(1), dim3(64), 0, s, (const unsigned*)a, (unsigned*)da, na, (const unsigned*)b, (unsigned*)db, nb);
 }
@@ -1076,14 +1077,9 @@ void launch_dbc_targets(int n, const int* ids, const double* target, const doubl
     if (n) hipLaunchKernelGGL(k_dbc_targets, dim3(nblk(3LL * n, BLOCK)), dim3(BLOCK), 0, s, n, ids, target, x, p);
 }
 
-__global__ void k_publish(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int n)
+void launch_publish_words(const void* src_dev, void* dst_mapped, int nWords, hipStream_t s)
 {
-    const int i = threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-void launch_publish(const void* src_dev, void* dst_mapped, int nWords, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, s, (const unsigned*)src_dev, (unsigned*)dst_mapped, nWords);
+    prims::launch_publish((const unsigned*)src_dev, (unsigned*)dst_mapped, nWords, s);
 }
 
 } // namespace ipcgpu

@@ -2,7 +2,8 @@
     python tools/device_bits.py            (on the GPU; run it at two commits and compare the lines)
 Every case runs twice on fresh contexts.  A case whose two runs differ (or that raises) is reported and left out of the final digest: only paths without
 fp64 atomics are listed, so that should not happen.  Sizes: a 14 x 14 x 2 mat stack and a 6 x 6 x 6 bar (item counts between 257 and a few thousand, no
-multiples of 64), and one bar of 65 856 tets for elastic_energy alone, whose reduction strides over more than 256 partial sums."""
+multiples of 64), and one bar of 65 856 tets for elastic_energy alone, whose reduction strides over more than 256 partial sums.  The step3_* cases run three
+time steps of the stepper and hash positions, energy, step sizes, iteration counts and the contact state after each."""
 import hashlib
 import os
 import sys
@@ -201,11 +202,90 @@ def case_newton_steps():
     return out
 
 
+# ---- three time steps through the stepper: every read-back of the scalar board and of the contact handler --------------------------------------------------
+def stepped(c, steps=3, max_iter=100, extra=None, contact=False):
+    out = []
+    for _ in range(steps):
+        n = c.solve_timestep(max_iter)
+        s = c.state()
+        out += [s["V"].copy(), s["E"], s["stepSize"], s["alphaFeasible"], n, s["innerIterAmt"]]
+        if contact:  # (the entry point refuses a context without self-collision and half-spaces)
+            out.append(c.contact_state())
+        if extra:
+            out.append(extra(c))
+    c.close()
+    return out
+
+
+def step_bar(energy="NH", twist=True, setup=None):
+    V, F = scene.make_bar(6, 6, 6, size=(3.0, 1.0, 1.0))
+    left, right = scene.border_verts(V, 0.01)
+    c = ipc_amd.Context(0)
+    c.set_mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+    c.set_energy_type(energy)
+    c.opt_init(0.025, False)
+    if twist:
+        c.set_twist(left, right)
+    if setup:
+        setup(c, V, left, right)
+    c.precompute()
+    return c
+
+
+def case_step_bar(energy):
+    return lambda: stepped(step_bar(energy))  # the fast path: k_iter_reset, k_publish2, alpha and both energies (FCR: no inversion guard, the filter slot unused)
+
+
+def case_step_damping_neumann():
+    def setup(c, V, left, right):
+        c.set_damping(0.1)
+        c.add_neumann(np.nonzero(np.abs(V[:, 0] - V[:, 0].mean()) < 0.3)[0].astype(np.int32), [0.0, -20.0, 0.0])
+    return stepped(step_bar(setup=setup))
+
+
+def case_step_mdbc():
+    # the right end moves 0.6 (more than a cell) per step against the held left end: the inversion guard cuts the scripted step short, the rest goes the penalty route
+    seen = []
+
+    def setup(c, V, left, right):
+        c.add_dirichlet(left)
+        c.add_dirichlet(right, lin_vel=(-24.0, 0.0, 0.0))
+
+    def extra(c):
+        d = c.dbc_state()
+        seen.append(d["rho"] > 0.0 or not d["projectDBC"])
+        return d
+    out = stepped(step_bar(twist=False, setup=setup), max_iter=40, extra=extra)
+    assert any(seen), "the penalty route was not taken"
+    return out
+
+
+def case_step_mats(ccd_mode):
+    def run():
+        V, F, nA = scene.make_mat_stack(14, 2, gap=1.2e-3)
+        c = ipc_amd.Context(0)
+        c.set_mesh(V, F, YM=2e4, PR=0.4, density=1000.0)
+        c.set_positions(scene.jitter(V, F, rel=2e-3))
+        c.opt_init(DT, True)
+        c.set_surface(scene.surface_tris(F))
+        c.enable_self_collision(1e-3)
+        c.set_friction(0.3, 1, 1e-3)
+        c.set_ccd_mode(ccd_mode)  # 0: the swept-box sweep, 1: the reference's sweep
+        c.precompute()
+        full = []
+        out = stepped(c, contact=True, extra=lambda c: full.append(c.contact_state()["nFullCCD"]) or full[-1])
+        assert full[-1] > 0, "the stepper never ran its full CCD: the sweep's read-backs are not covered"
+        return out
+    return run
+
+
 CASES = [("elastic_energy+incremental_potential+check_inversion+filter_step_size", case_elastic), ("elastic_energy_65k_tets", case_elastic_energy_large),
          ("contact_energy+gradient_add+hessian_add", case_contact), ("friction_energy+gradient+hessian+contact_report", case_friction_and_report),
          ("ccd_full", case_ccd_full), ("halfspace_energy+hessian_add+step_bound+move", case_halfspace), ("pcg_block_jacobi", case_pcg(0)),
          ("pcg_lagged_factor", case_pcg(1)), ("pcg_two_level", case_pcg(2)), ("chamber_energy+gas_state", case_chamber), ("shell_stretch", case_shell_stretch),
-         ("newton_12_steps_friction_halfspace", case_newton_steps)]
+         ("newton_12_steps_friction_halfspace", case_newton_steps), ("step3_bar_NH_fast_path", case_step_bar("NH")), ("step3_bar_FCR", case_step_bar("FCR")),
+         ("step3_bar_damping_neumann", case_step_damping_neumann), ("step3_bar_moving_dirichlet_penalty", case_step_mdbc),
+         ("step3_mats_self_collision_friction", case_step_mats(0)), ("step3_mats_reference_ccd", case_step_mats(1))]
 
 
 def main():

@@ -35,6 +35,14 @@ enum BuildCounter : int { C_PT = 0, C_EE = 1, C_STALE = 2 }; // buildConstraintS
 enum HessianCounter : int { C_MISS = 0, C_SWEEPS = 1, C_BIN0 = 4 }; // hessianAdd, patternCovers: a node pair outside the CSR pattern, Jacobi sweeps of the projections, the first of the NBINS stencil-kind bin counts (k_bin_stencils)
 enum CcdCounter : int { C_QUERIED = 0, C_HITS = 1 }; // ccdFull, ccdFullReference: queried pairs, pairs that returned a time inside the step (the hit list)
 enum CloseCounter : int { C_CLOSE = 0, C_CLOSE_MISS = 2, C_CLOSE_END = 4 }; // closeStencils: stencils closer than dTol, the pattern check's miss flag riding along; [0, C_CLOSE_END) come back
+// ccdOut_ (HipContact): the 64-bit words a step-bound pass leaves its result in, set by k_step_bounds_init at its head; non-negative doubles as bits, which order like integers
+enum CcdSlot : int {
+    CCD_MIN = 0, // the smallest time a pair returned; all ones: none
+    CCD_ARG = 1, // the smallest order key (pair_key, ref_key) among the pairs that attain it; all ones: none
+    CCD_AUX = 2, // stepBounds, maxSurfaceSpeed, makeGrid: the largest |p| (k_max_speed).  ccdFullReference: the bound the vertex sweeps left
+    CCD_STEP = 3, // the step the pass is bounded by (stepBounds: cut by the inversion filter's root)
+    CCD_SLOTS = 4
+};
 
 // what the host needs between the stages of a build, written to mapped host memory by one thread (three blits of 12, 4 and 48 bytes before)
 struct BuildReadback {
@@ -49,20 +57,21 @@ struct BuildReadback {
 // calls in between (energy, stepBounds, both CCDs, builds): no other member may share its bytes.
 struct ContactReadback {
     BuildReadback build; // buildConstraintSet (k_publish_narrow, then k_dup_emit: totals, nUnique), isIntersected (k_publish_narrow)
-    unsigned long long stepBounds[4]; // stepBounds: minimum time, its pair, largest surface speed, the step the CCD was bounded by (ccdOut_)
+    unsigned long long stepBounds[CCD_SLOTS]; // stepBounds, maxSurfaceSpeed: ccdOut_, by CcdSlot
     double energy; // energy(): the barrier energy behind energyEnqueue
     double refBox[7]; // ccdFullReference, first wait: the capped step, lower and upper corner of the hash (k_ref_box_final)
-    unsigned long long refCcd[2]; // ccdFullReference, third wait: minimum time, its pair ...
+    unsigned long long refCcd[2]; // ccdFull, ccdFullReference, last wait: ccdOut_[CCD_MIN], [CCD_ARG] ...
     int refCount[2]; // ... and C_QUERIED, C_HITS
-    int refItems; // ccdFullReference, second wait: total number of cell entries
+    int refItems; // ccdFull, ccdFullReference, second wait: total number of cell entries
     int hessError; // C_MISS of a hessianAdd(deferCheck): see above
     int close[C_CLOSE_END]; // closeStencils: counters [0, C_CLOSE_END)
+    double sweptBox[7]; // ccdFull, first wait: lower and upper corner of the positions' box, the largest |p| (makeGrid)
 };
 static_assert(sizeof(BuildReadback) == 80 && offsetof(BuildReadback, box) % 8 == 0 && offsetof(BuildReadback, totals) % 8 == 0, "k_publish_narrow and k_dup_emit write this record");
 static_assert(offsetof(ContactReadback, build) == 0 && offsetof(ContactReadback, stepBounds) % 8 == 0 && offsetof(ContactReadback, energy) % 8 == 0
-        && offsetof(ContactReadback, refBox) % 8 == 0 && offsetof(ContactReadback, refCcd) % 8 == 0,
+        && offsetof(ContactReadback, refBox) % 8 == 0 && offsetof(ContactReadback, refCcd) % 8 == 0 && offsetof(ContactReadback, sweptBox) % 8 == 0,
     "the kernels store the 8-byte members whole");
-static_assert(sizeof(ContactReadback) == 224, "members are added at the end; every publish stays inside its own member");
+static_assert(sizeof(ContactReadback) == 280, "members are added at the end; every publish stays inside its own member");
 
 class HipContact {
 public:
@@ -209,13 +218,17 @@ private:
         PinnedBuf<int> hostI;
         PinnedBuf<double> hostD;
     } report_;
-    // host side of the grids: the swept grid of ccdFull (own bounding box, two synchronisations), the grid of a build or check over box_ padded by two cells
-    // of size h (grown until the grid has at most 2^26 cells), and the box of the positions measured synchronously (first build or check of a surface)
+    // host side of the grids: the swept grid of ccdFull (over the positions' own box grown by the step's reach, read back with the largest |p| in one wait: box_ is
+    // not touched), the grid of a build or check over box_ padded by two cells of size h (grown until the grid has at most 2^26 cells), and the box of the
+    // positions measured synchronously (first build or check of a surface)
     Grid makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells);
     Grid gridOverBox(double h, long long& nCells) const;
+    double* enqueueBox(int nV, const double* x_dev); // the box of the positions, six doubles on the device (k_bbox_partial, k_bbox_final without the stale check)
     void measureBox(int nV, const double* x_dev);
-    void buildCells(const Grid& g, long long nCells, int nPrim, int nv, const int* prim_dev, const double* x_dev, const double* p_dev, double alpha,
-        DevBuf<int>& cnt, DevBuf<int>& start, DevBuf<int>& items);
+    void buildCells(const Grid& g, long long nCells, const double* x_dev, const double* p_dev, double alpha);
+    unsigned long long* ccdOutBegin(double stepSize, const double* filterDev = nullptr); // ccdOut_ allocated and set for a pass (k_step_bounds_init)
+    void readSweep(); // ccdFull, ccdFullReference: ccdOut_[CCD_MIN], [CCD_ARG], C_QUERIED and C_HITS into readback_ (refCcd, refCount), waited for
+    void enqueueMaxSpeed(int n, const int* ids_dev, const double* p_dev, CcdSlot slot); // ccdOut_[slot] = max(itself, largest |p| of the n nodes; ids null: 0 .. n - 1)
     void* scanTmp(size_t bytes); // temporary storage of a hipcub call, grown on demand
     template <class T>
     void exclusiveSum(const T* in, T* out, int count);
@@ -223,13 +236,14 @@ private:
     DevBuf<double> d_vals_;
     DevBuf<unsigned long long> ccdOut_, ccdHits_;
     DevBuf<int> d_codimPoints;
-    DevBuf<int> cellCountT_, cellCountE_, cellStartT_, cellStartE_, cellItemsT_, cellItemsE_, outPT_, outEE_, counters_;
+    DevBuf<int> outPT_, outEE_, counters_;
     DevBuf<int> d_v2sv, refVbox_, refStart_, refItems_; // reference-mode sweep: node -> surface index, index boxes, the three cell structures in one
     ZeroKeptCounters refCount_;
     DevBuf<double> bboxPartial_;
     bool haveBox_ = false; // box_: the bounding box the last constraint-set build or intersection check measured (the next grid is laid over it)
     double box_[6] = { 0, 0, 0, 0, 0, 0 };
-    // the narrow phase's grids, triangles and edges in one array of 2 nCells + 1 cells (k_grid_insert_both); the intersection check uses nCells + 1 of them
+    // the narrow phase's grids, triangles and edges in one array of 2 nCells + 1 cells (k_grid_insert_both); the intersection check uses nCells + 1 of them,
+    // the swept grid of ccdFull 2 (nCells + 1) with bare indices as items (buildCells).  One pass at a time; gridItems_ never shrinks
     ZeroKeptCounters gridCount_;
     DevBuf<int> gridStart_, gridItems_;
     // on-device assembly of the sets (buildConstraintSet)

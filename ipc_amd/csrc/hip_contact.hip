@@ -1276,11 +1276,36 @@ __device__ __forceinline__ unsigned long long pair_key(int kind, int i, int j)
 {
     return ((unsigned long long)(kind == K_PT ? 0 : 1) << 62) | ((unsigned long long)(unsigned)i << 31) | (unsigned long long)(unsigned)j;
 }
+inline void unpack_pair_key(unsigned long long key, int* pair2) // (-svI - 1, sfI) or (eI, eJ)
+{
+    const int i = (int)((key >> 31) & 0x7FFFFFFF);
+    pair2[0] = (key >> 62) ? i : -i - 1;
+    pair2[1] = (int)(key & 0x7FFFFFFF);
+}
+// What a pass left in ccdOut_[CCD_MIN] and [CCD_ARG], read against the step it was bounded by.  No pair limits the step when none returned a time below it:
+// t is then the step itself and the key means nothing.
+inline double double_of_bits(unsigned long long bits)
+{
+    double v;
+    std::memcpy(&v, &bits, sizeof(v));
+    return v;
+}
+struct StepBound {
+    double t;
+    unsigned long long key;
+    bool limited;
+    StepBound(unsigned long long minBits, unsigned long long argKey, double step) : t(double_of_bits(minBits)), key(argKey)
+    {
+        limited = key != ~0ull && t < step;
+        if (!limited) t = step;
+    }
+};
 struct CcdOut {
     unsigned long long* minBits; // bit pattern of the smallest time (positive doubles order like integers)
     unsigned long long* argKey; // smallest order key among the pairs that attain it
     // pairs that returned a time below the step (few: most candidates of a sweep do not meet inside it) as (time bits, order key): the pair
-    // that attains the minimum is then found by one small pass over this list instead of a second run of the whole sweep
+    // that attains the minimum is then found by one small pass over this list instead of a second run of the whole sweep (what rounds 1-2 did:
+    // profiles/r03m_contact_bench_lds_jacobi_two_pass_ccd.json)
     unsigned long long* hits = nullptr;
     int* hitCount = nullptr;
     int hitCap = 0;
@@ -1348,35 +1373,7 @@ __global__ __launch_bounds__(BLOCK) void k_ccd_list(int nPairs, const int* __res
     else ccd_record_arg(t, pair_key(kind, ki, kj), o);
 }
 
-// swept boxes over [x, x + alpha p]
-__global__ __launch_bounds__(BLOCK) void k_grid_insert_swept(int nPrim, int nv, const int* __restrict__ prim, const double* __restrict__ x,
-    const double* __restrict__ p, double alpha, Grid g, int mode, int* __restrict__ cellCount, const int* __restrict__ cellStart,
-    int* __restrict__ cellItems)
-{
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nPrim) return;
-    double bl[3] = { 1e300, 1e300, 1e300 }, bh[3] = { -1e300, -1e300, -1e300 };
-    for (int k = 0; k < nv; ++k) {
-        const int v = prim[nv * (size_t)i + k];
-        for (int c = 0; c < 3; ++c) {
-            const double a = x[3 * (size_t)v + c], b = a + alpha * p[3 * (size_t)v + c];
-            bl[c] = fmin(bl[c], fmin(a, b));
-            bh[c] = fmax(bh[c], fmax(a, b));
-        }
-    }
-    int a[3], b[3];
-    for (int c = 0; c < 3; ++c) {
-        a[c] = cell_of(g, bl[c], c);
-        b[c] = cell_of(g, bh[c], c);
-    }
-    for (int z = a[2]; z <= b[2]; ++z)
-        for (int y = a[1]; y <= b[1]; ++y)
-            for (int xx = a[0]; xx <= b[0]; ++xx) {
-                const int cell = xx + g.dim[0] * (y + g.dim[1] * z);
-                const int slot = atomicAdd(&cellCount[cell], 1);
-                if (mode == 1) cellItems[cellStart[cell] + slot] = i;
-            }
-}
+// box of n nodes swept over [x, x + alpha p]
 __device__ __forceinline__ void swept_box(const int* node, int n, const double* x, const double* p, double alpha, double* lo, double* hi)
 {
     for (int c = 0; c < 3; ++c) {
@@ -1390,77 +1387,53 @@ __device__ __forceinline__ void swept_box(const int* node, int n, const double* 
             hi[c] = fmax(hi[c], fmax(a, b));
         }
 }
-// full CCD: every (surface vertex, triangle) and (edge, edge) pair with overlapping swept boxes (SelfCollisionHandler.cpp:982-1366)
-__global__ __launch_bounds__(BLOCK) void k_ccd_full_pt(int nSVI, const int* __restrict__ SVI, const int* __restrict__ SF, const double* __restrict__ x,
-    const double* __restrict__ p, const int* __restrict__ dbc, Grid g, const int* __restrict__ cellStart, const int* __restrict__ cellItems,
-    double alpha, double slackness, int pass, CcdOut o, int* __restrict__ nCand)
+// primitives of nv nodes into the cells their swept boxes touch, bare indices as items; mode 0 counts, mode 1 fills and counts the cells back down (k_grid_insert_both)
+__global__ __launch_bounds__(BLOCK) void k_grid_insert_swept(int nPrim, int nv, const int* __restrict__ prim, const double* __restrict__ x,
+    const double* __restrict__ p, double alpha, Grid g, int mode, int* __restrict__ cellCount, const int* __restrict__ cellStart,
+    int* __restrict__ cellItems)
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nSVI) return;
-    const int vI = SVI[i];
-    double lo[3], hi[3];
-    swept_box(&vI, 1, x, p, alpha, lo, hi);
-    int ca[3], cb[3];
+    if (i >= nPrim) return;
+    double bl[3], bh[3];
+    swept_box(prim + nv * (size_t)i, nv, x, p, alpha, bl, bh);
+    int a[3], b[3];
     for (int c = 0; c < 3; ++c) {
-        ca[c] = cell_of(g, lo[c], c);
-        cb[c] = cell_of(g, hi[c], c);
+        a[c] = cell_of(g, bl[c], c);
+        b[c] = cell_of(g, bh[c], c);
     }
-    const bool vDbc = (dbc[vI] & 1) != 0;
-    for (int z = ca[2]; z <= cb[2]; ++z)
-        for (int y = ca[1]; y <= cb[1]; ++y)
-            for (int xx = ca[0]; xx <= cb[0]; ++xx) {
+    for (int z = a[2]; z <= b[2]; ++z)
+        for (int y = a[1]; y <= b[1]; ++y)
+            for (int xx = a[0]; xx <= b[0]; ++xx) {
                 const int cell = xx + g.dim[0] * (y + g.dim[1] * z);
-                for (int k = cellStart[cell]; k < cellStart[cell + 1]; ++k) {
-                    const int f = cellItems[k];
-                    int node[4] = { vI, SF[3 * (size_t)f], SF[3 * (size_t)f + 1], SF[3 * (size_t)f + 2] };
-                    if (vI == node[1] || vI == node[2] || vI == node[3]) continue;
-                    if (vDbc && (dbc[node[1]] & 1) && (dbc[node[2]] & 1) && (dbc[node[3]] & 1)) continue;
-                    if (pair_filtered(dbc[vI], dbc[node[1]])) continue;
-                    double tl[3], th[3];
-                    swept_box(node + 1, 3, x, p, alpha, tl, th);
-                    bool ok = true;
-                    int canon[3];
-                    for (int c = 0; c < 3; ++c) {
-                        if (lo[c] > th[c] || tl[c] > hi[c]) ok = false;
-                        canon[c] = cell_of(g, fmax(lo[c], tl[c]), c);
-                    }
-                    if (!ok || canon[0] != xx || canon[1] != y || canon[2] != z) continue;
-                    if (pass == 0) atomicAdd(nCand, 1);
-                    const double t = pair_toc(K_PT, node, x, p, slackness, alpha);
-                    if (pass == 0) ccd_record_min(t, alpha, o);
-                    else ccd_record_arg(t, pair_key(K_PT, i, f), o);
-                }
+                if (mode == 0) atomicAdd(&cellCount[cell], 1);
+                else cellItems[cellStart[cell + 1] - atomicSub(&cellCount[cell], 1)] = i; // (from the cell's front: the order of arrival, as a counter counting up gives it)
             }
 }
-__global__ __launch_bounds__(BLOCK) void k_ccd_full_ee(int nE, const int* __restrict__ SFE, const double* __restrict__ x, const double* __restrict__ p,
-    const int* __restrict__ dbc, Grid g, const int* __restrict__ cellStart, const int* __restrict__ cellItems, double alpha, double slackness,
-    int pass, CcdOut o, int* __restrict__ nCand)
+// full CCD: every (surface vertex, triangle) and (edge, edge) pair with overlapping swept boxes (SelfCollisionHandler.cpp:982-1366)
+// The walk of one query primitive i of a sweep of kind K_PT / K_EE: the cells its swept box touches and their lists.  node[] holds the query's nodes (one
+// or two); keep(j) puts the nodes of candidate j behind them, false: the pair is filtered.  A pair whose swept boxes overlap is handled in the one cell that
+// holds the low corner of the overlap.  pass 0: candidate count and minimum time; pass 1: first pair attaining it.
+template <int KIND, class Keep>
+__device__ __forceinline__ void swept_walk(int i, int* node, const double* __restrict__ x, const double* __restrict__ p, const Grid& g,
+    const int* __restrict__ cellStart, const int* __restrict__ cellItems, double alpha, double slackness, int pass, CcdOut o, int* __restrict__ nCand, Keep keep)
 {
-    const int eI = blockIdx.x * BLOCK + threadIdx.x;
-    if (eI >= nE) return;
-    int node[4] = { SFE[2 * (size_t)eI], SFE[2 * (size_t)eI + 1], 0, 0 };
+    constexpr int NQ = KIND == K_PT ? 1 : 2;
     double lo[3], hi[3];
-    swept_box(node, 2, x, p, alpha, lo, hi);
+    swept_box(node, NQ, x, p, alpha, lo, hi);
     int ca[3], cb[3];
     for (int c = 0; c < 3; ++c) {
         ca[c] = cell_of(g, lo[c], c);
         cb[c] = cell_of(g, hi[c], c);
     }
-    const bool aDbc = (dbc[node[0]] & 1) && (dbc[node[1]] & 1);
     for (int z = ca[2]; z <= cb[2]; ++z)
         for (int y = ca[1]; y <= cb[1]; ++y)
             for (int xx = ca[0]; xx <= cb[0]; ++xx) {
                 const int cell = xx + g.dim[0] * (y + g.dim[1] * z);
                 for (int k = cellStart[cell]; k < cellStart[cell + 1]; ++k) {
-                    const int eJ = cellItems[k];
-                    if (eJ <= eI) continue;
-                    node[2] = SFE[2 * (size_t)eJ];
-                    node[3] = SFE[2 * (size_t)eJ + 1];
-                    if (node[0] == node[2] || node[0] == node[3] || node[1] == node[2] || node[1] == node[3]) continue;
-                    if (aDbc && (dbc[node[2]] & 1) && (dbc[node[3]] & 1)) continue;
-                    if (pair_filtered(dbc[node[0]], dbc[node[2]])) continue;
+                    const int j = cellItems[k];
+                    if (!keep(j)) continue;
                     double jl[3], jh[3];
-                    swept_box(node + 2, 2, x, p, alpha, jl, jh);
+                    swept_box(node + NQ, 4 - NQ, x, p, alpha, jl, jh);
                     bool ok = true;
                     int canon[3];
                     for (int c = 0; c < 3; ++c) {
@@ -1469,11 +1442,44 @@ __global__ __launch_bounds__(BLOCK) void k_ccd_full_ee(int nE, const int* __rest
                     }
                     if (!ok || canon[0] != xx || canon[1] != y || canon[2] != z) continue;
                     if (pass == 0) atomicAdd(nCand, 1);
-                    const double t = pair_toc(K_EE, node, x, p, slackness, alpha);
+                    const double t = pair_toc(KIND, node, x, p, slackness, alpha);
                     if (pass == 0) ccd_record_min(t, alpha, o);
-                    else ccd_record_arg(t, pair_key(K_EE, eI, eJ), o);
+                    else ccd_record_arg(t, pair_key(KIND, i, j), o);
                 }
             }
+}
+__global__ __launch_bounds__(BLOCK) void k_ccd_full_pt(int nSVI, const int* __restrict__ SVI, const int* __restrict__ SF, const double* __restrict__ x,
+    const double* __restrict__ p, const int* __restrict__ dbc, Grid g, const int* __restrict__ cellStart, const int* __restrict__ cellItems,
+    double alpha, double slackness, int pass, CcdOut o, int* __restrict__ nCand)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nSVI) return;
+    const int vI = SVI[i];
+    int node[4] = { vI, 0, 0, 0 };
+    const bool vDbc = (dbc[vI] & 1) != 0;
+    swept_walk<K_PT>(i, node, x, p, g, cellStart, cellItems, alpha, slackness, pass, o, nCand, [&](int f) {
+        for (int k = 0; k < 3; ++k) node[1 + k] = SF[3 * (size_t)f + k];
+        if (vI == node[1] || vI == node[2] || vI == node[3]) return false;
+        if (vDbc && (dbc[node[1]] & 1) && (dbc[node[2]] & 1) && (dbc[node[3]] & 1)) return false;
+        return !pair_filtered(dbc[vI], dbc[node[1]]);
+    });
+}
+__global__ __launch_bounds__(BLOCK) void k_ccd_full_ee(int nE, const int* __restrict__ SFE, const double* __restrict__ x, const double* __restrict__ p,
+    const int* __restrict__ dbc, Grid g, const int* __restrict__ cellStart, const int* __restrict__ cellItems, double alpha, double slackness,
+    int pass, CcdOut o, int* __restrict__ nCand)
+{
+    const int eI = blockIdx.x * BLOCK + threadIdx.x;
+    if (eI >= nE) return;
+    int node[4] = { SFE[2 * (size_t)eI], SFE[2 * (size_t)eI + 1], 0, 0 };
+    const bool aDbc = (dbc[node[0]] & 1) && (dbc[node[1]] & 1);
+    swept_walk<K_EE>(eI, node, x, p, g, cellStart, cellItems, alpha, slackness, pass, o, nCand, [&](int eJ) {
+        if (eJ <= eI) return false;
+        node[2] = SFE[2 * (size_t)eJ];
+        node[3] = SFE[2 * (size_t)eJ + 1];
+        if (node[0] == node[2] || node[0] == node[3] || node[1] == node[2] || node[1] == node[3]) return false;
+        if (aDbc && (dbc[node[2]] & 1) && (dbc[node[3]] & 1)) return false;
+        return !pair_filtered(dbc[node[0]], dbc[node[2]]);
+    });
 }
 
 // ---- full CCD as the reference sweeps it (SelfCollisionHandler.cpp:982-1366 over SpatialHash.hpp:589-832) ------------------------
@@ -1703,6 +1709,12 @@ __device__ inline double ref_pair_bound(int kind, const int* node, const double*
 __device__ __forceinline__ unsigned long long ref_key(int isEE, int i, int rank, int j)
 {
     return ((unsigned long long)isEE << 63) | ((unsigned long long)(unsigned)i << 33) | ((unsigned long long)rank << 31) | (unsigned long long)(unsigned)j;
+}
+inline void unpack_ref_key(unsigned long long key, int* arg3) // (kind, i, j); rank 0 / 1 / 2 = K_PP / K_PE / K_PT
+{
+    arg3[0] = (key >> 63) ? K_EE : (int)((key >> 31) & 3);
+    arg3[1] = (int)((key >> 33) & 0x3FFFFFFF);
+    arg3[2] = (int)(key & 0x7FFFFFFF);
 }
 struct RefLists {
     const int *startV, *itemsV, *startE, *itemsE, *startT, *itemsT;
@@ -2194,17 +2206,17 @@ __global__ void k_publish_narrow(const int* __restrict__ counters, const int* __
     out->cnt[3] = gridTotal[0];
     for (int c = 0; c < 6; ++c) out->box[c] = box[c];
 }
-// ccdOut of HipContact::stepBounds: [0] minimum time, [1] its pair (both "none"), [2] largest surface speed, [3] the step the CCD is bounded by
+// ccdOut_ at the head of a step-bound pass (CcdSlot): no time, no pair, speed zero, the step cut by the inversion filter's root where there is one
 __global__ void k_step_bounds_init(double stepSize, const double* __restrict__ filterRoot, unsigned long long* __restrict__ out)
 {
-    out[0] = ~0ull;
-    out[1] = ~0ull;
-    out[2] = 0ull;
+    out[CCD_MIN] = ~0ull;
+    out[CCD_ARG] = ~0ull;
+    out[CCD_AUX] = 0ull;
     if (filterRoot) {
         const double t = filterRoot[0];
         if (t > 0.0 && t < stepSize) stepSize = t; // Energy.cpp:565-581
     }
-    out[3] = (unsigned long long)__double_as_longlong(stepSize);
+    out[CCD_STEP] = (unsigned long long)__double_as_longlong(stepSize);
 }
 // stencils of the active set closer than dTol (closeMConstraint bookkeeping, Optimizer.cpp:2365-2440): index + distance
 __global__ void k_close_stencils(int n, const int* __restrict__ ids, const double* __restrict__ x, double dTol, int cap, int* __restrict__ outIdx,
@@ -2400,14 +2412,18 @@ static Grid layGrid(const double* lo, const double* hi, double h, double pad, lo
 }
 Grid HipContact::gridOverBox(double h, long long& nCells) const { return layGrid(box_, box_ + 3, h, 2.0, nCells); }
 
-void HipContact::measureBox(int nV, const double* x_dev)
+double* HipContact::enqueueBox(int nV, const double* x_dev)
 {
     const int nb = nblk(nV, BLOCK);
     bboxPartial_.ensure(6 * (size_t)nb + 6);
     double* box_dev = bboxPartial_.p + 6 * (size_t)nb;
     hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
     hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(BLOCK), 0, stream, nb, bboxPartial_.p, box_dev, Grid{}, 0, (int*)nullptr);
-    HIP_CHECK(hipMemcpyAsync(box_, box_dev, sizeof(box_), hipMemcpyDeviceToHost, stream));
+    return box_dev;
+}
+void HipContact::measureBox(int nV, const double* x_dev)
+{
+    HIP_CHECK(hipMemcpyAsync(box_, enqueueBox(nV, x_dev), sizeof(box_), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     haveBox_ = true;
 }
@@ -2967,86 +2983,82 @@ __global__ void k_max_speed(int n, const int* __restrict__ ids, const double* __
 }
 } // namespace
 
-double HipContact::maxSurfaceSpeed(const double* p_dev)
+unsigned long long* HipContact::ccdOutBegin(double stepSize, const double* filterDev)
 {
-    ccdOut_.alloc(4);
-    ccdOut_.zero(stream);
-    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p);
-    unsigned long long bits = 0;
-    HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
+    ccdOut_.alloc(CCD_SLOTS);
+    readbackInit();
+    hipLaunchKernelGGL(k_step_bounds_init, dim3(1), dim3(1), 0, stream, stepSize, filterDev, ccdOut_.p);
+    return ccdOut_.p;
+}
+void HipContact::enqueueMaxSpeed(int n, const int* ids_dev, const double* p_dev, CcdSlot slot)
+{
+    if (n) hipLaunchKernelGGL(k_max_speed, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, ids_dev, p_dev, ccdOut_.p + slot);
+}
+// minimum, pair and the two counters of a full sweep in one read-back through mapped memory
+void HipContact::readSweep()
+{
+    static_assert(CCD_MIN == 0 && CCD_ARG == 1 && C_QUERIED == 0 && C_HITS == 1, "published as pairs");
+    prims::launch_publish(ccdOut_.p + CCD_MIN, readback_.dev->refCcd, 2, stream);
+    prims::launch_publish(counters_.p + C_QUERIED, readback_.dev->refCount, 2, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    double v;
-    std::memcpy(&v, &bits, sizeof(v));
-    return v;
+}
+// what a pass hands back: the bound, and the limiting pair or (0, 0)
+static double boundAndPair(const StepBound& b, int* pair2)
+{
+    if (pair2) pair2[0] = pair2[1] = 0;
+    if (pair2 && b.limited) unpack_pair_key(b.key, pair2);
+    return b.t;
 }
 
-// the grid of the swept-box sweep (ccdFull): the box of the positions grown by what the step can reach, cells at least that large
+double HipContact::maxSurfaceSpeed(const double* p_dev)
+{
+    const unsigned long long* out = ccdOutBegin(0.0);
+    enqueueMaxSpeed(nSVI, d_SVI.p, p_dev, CCD_AUX);
+    prims::launch_publish(out + CCD_AUX, readback_.dev->stepBounds + CCD_AUX, 1, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    return double_of_bits(readback_.p->stepBounds[CCD_AUX]);
+}
+
+// the grid of the swept-box sweep (ccdFull, behind its ccdOutBegin): the box of the positions grown by what the step can reach, cells at least that large
 Grid HipContact::makeGrid(const HipMesh& mesh, const double* x_dev, const double* p_dev, double alpha, double minCell, long long& nCells)
 {
-    const int nV = mesh.nV;
-    const int nb = nblk(nV, BLOCK);
-    bboxPartial_.ensure(6 * (size_t)nb);
-    hipLaunchKernelGGL(k_bbox_partial, dim3(nb), dim3(BLOCK), 0, stream, nV, x_dev, bboxPartial_.p);
-    std::vector<double> part(6 * (size_t)nb);
-    bboxPartial_.download(part.data(), part.size(), stream);
-    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
-    for (int b = 0; b < nb; ++b)
-        for (int c = 0; c < 3; ++c) {
-            lo[c] = std::min(lo[c], part[6 * (size_t)b + c]);
-            hi[c] = std::max(hi[c], part[6 * (size_t)b + 3 + c]);
-        }
-    // swept boxes reach at most alpha * max |p| beyond the current bounding box
-    ccdOut_.alloc(4);
-    ccdOut_.zero(stream);
-    hipLaunchKernelGGL(k_max_speed, dim3(nblk(nV, BLOCK)), dim3(BLOCK), 0, stream, nV, (const int*)nullptr, p_dev, ccdOut_.p);
-    unsigned long long bits = 0;
-    HIP_CHECK(hipMemcpyAsync(&bits, ccdOut_.p, sizeof(bits), hipMemcpyDeviceToHost, stream));
+    const double* box_dev = enqueueBox(mesh.nV, x_dev);
+    enqueueMaxSpeed(mesh.nV, nullptr, p_dev, CCD_AUX);
+    prims::launch_publish(box_dev, readback_.dev->sweptBox, 6, stream);
+    prims::launch_publish(reinterpret_cast<const double*>(ccdOut_.p + CCD_AUX), readback_.dev->sweptBox + 6, 1, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    double pm;
-    std::memcpy(&pm, &bits, sizeof(pm));
-    const double reach = alpha * pm;
+    const double* h = readback_.p->sweptBox;
+    const double reach = alpha * h[6]; // swept boxes reach at most alpha * max |p| beyond the current bounding box
+    double lo[3], hi[3];
     for (int c = 0; c < 3; ++c) {
-        lo[c] -= reach;
-        hi[c] += reach;
+        lo[c] = h[c] - reach;
+        hi[c] = h[3 + c] + reach;
     }
     return layGrid(lo, hi, std::max(minCell, reach), 0.0, nCells);
 }
 
-// cell lists of primitive indices over swept boxes: count, scan, wait for the total, fill
-void HipContact::buildCells(const Grid& g, long long nCells, int nPrim, int nv, const int* prim, const double* x_dev, const double* p_dev, double alpha,
-    DevBuf<int>& cnt, DevBuf<int>& start, DevBuf<int>& items)
+// Cell lists of primitive indices over swept boxes, as ccdFullReference builds its three: triangles in counters [0, nCells], edges in the nCells + 1 behind
+// them, the last of each half left at zero; one scan makes the edges' offsets absolute, the host waits once, for the total, and the fill counts back down.
+void HipContact::buildCells(const Grid& g, long long nCells, const double* x_dev, const double* p_dev, double alpha)
 {
-    cnt.ensure((size_t)nCells + 1);
-    start.ensure((size_t)nCells + 1);
+    const size_t nC1 = (size_t)nCells + 1;
+    int* count = gridCount_.begin(2 * nC1, stream);
+    gridStart_.ensure(2 * nC1);
+    const int nPrims[2] = { nSF, nSFE }, nvs[2] = { 3, 2 };
+    const int* prims[2] = { d_SF.p, d_SFE.p };
     auto insert = [&](int mode) {
-        cnt.zeroN((size_t)nCells + 1, stream);
-        hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrim, BLOCK)), dim3(BLOCK), 0, stream, nPrim, nv, prim, x_dev, p_dev, alpha, g, mode, cnt.p, start.p,
-            items.p);
+        for (int q = 0; q < 2; ++q)
+            if (nPrims[q])
+                hipLaunchKernelGGL(k_grid_insert_swept, dim3(nblk(nPrims[q], BLOCK)), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], x_dev, p_dev, alpha, g, mode,
+                    count + q * nC1, (const int*)(gridStart_.p + q * nC1), gridItems_.p);
     };
     insert(0);
-    exclusiveSum(cnt.p, start.p, (int)nCells + 1);
-    int total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, start.p + nCells, sizeof(int), hipMemcpyDeviceToHost, stream));
+    exclusiveSum(count, gridStart_.p, (int)(2 * nC1));
+    prims::launch_publish(gridStart_.p + 2 * nC1 - 1, &readback_.dev->refItems, 1, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    items.ensure((size_t)std::max(1, total));
+    gridItems_.ensure((size_t)std::max(1, readback_.p->refItems));
     insert(1);
-}
-
-static void decodeCcdOut(const unsigned long long* h, double stepSize, double* outStep, int* pair2)
-{
-    double t;
-    std::memcpy(&t, &h[0], sizeof(t));
-    if (h[1] == ~0ull || !(t < stepSize)) { // no pair limits the step
-        *outStep = stepSize;
-        if (pair2) pair2[0] = pair2[1] = 0;
-        return;
-    }
-    *outStep = t;
-    if (pair2) {
-        const int isEE = (int)(h[1] >> 62), i = (int)((h[1] >> 31) & 0x7FFFFFFF), j = (int)(h[1] & 0x7FFFFFFF);
-        pair2[0] = isEE ? i : -i - 1;
-        pair2[1] = j;
-    }
+    gridCount_.done();
 }
 
 double HipContact::ccdPartial(const double* x_dev, const double* p_dev, double slackness, double stepSize, int* pair2)
@@ -3054,19 +3066,15 @@ double HipContact::ccdPartial(const double* x_dev, const double* p_dev, double s
     const int n = nCand_;
     if (pair2) pair2[0] = pair2[1] = 0;
     if (!n) return stepSize;
-    ccdOut_.alloc(4);
-    const unsigned long long init[2] = { ~0ull, ~0ull };
-    HIP_CHECK(hipMemcpyAsync(ccdOut_.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
-    CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
+    unsigned long long* out = ccdOutBegin(stepSize);
+    CcdOut o{ out + CCD_MIN, out + CCD_ARG };
     for (int pass = 0; pass < 2; ++pass)
         hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
             o, (const unsigned long long*)nullptr);
-    unsigned long long h[2];
-    HIP_CHECK(hipMemcpyAsync(h, ccdOut_.p, sizeof(h), hipMemcpyDeviceToHost, stream));
+    unsigned long long h[CCD_ARG + 1];
+    HIP_CHECK(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    double out;
-    decodeCcdOut(h, stepSize, &out, pair2);
-    return out;
+    return boundAndPair(StepBound(h[CCD_MIN], h[CCD_ARG], stepSize), pair2);
 }
 
 // The step bounds a Newton iteration of a contact scene asks for one after the other (Optimizer.cpp:1884-1953): the inversion filter's root (already on the
@@ -3075,22 +3083,18 @@ double HipContact::ccdPartial(const double* x_dev, const double* p_dev, double s
 void HipContact::stepBounds(const double* x_dev, const double* p_dev, double slackness, double stepSize, const double* filterDev, double* alphaOut, int* pair2,
     double* pMaxOut)
 {
-    ccdOut_.alloc(4);
-    readbackInit();
-    hipLaunchKernelGGL(k_step_bounds_init, dim3(1), dim3(1), 0, stream, stepSize, filterDev, ccdOut_.p);
+    unsigned long long* out = ccdOutBegin(stepSize, filterDev);
     const int n = nCand_;
-    CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
+    CcdOut o{ out + CCD_MIN, out + CCD_ARG };
     for (int pass = 0; pass < 2 && n; ++pass)
         hipLaunchKernelGGL(k_ccd_list, dim3(nblk(n, BLOCK)), dim3(BLOCK), 0, stream, n, d_csPTEE.p, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, slackness, stepSize, pass,
-            o, (const unsigned long long*)(ccdOut_.p + 3));
-    if (nSVI) hipLaunchKernelGGL(k_max_speed, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, p_dev, ccdOut_.p + 2);
-    prims::launch_publish(ccdOut_.p, readback_.dev->stepBounds, 4, stream);
+            o, (const unsigned long long*)(out + CCD_STEP));
+    enqueueMaxSpeed(nSVI, d_SVI.p, p_dev, CCD_AUX);
+    prims::launch_publish(out, readback_.dev->stepBounds, CCD_SLOTS, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
     const unsigned long long* h = readback_.p->stepBounds;
-    double filtered;
-    std::memcpy(&filtered, &h[3], sizeof(filtered));
-    std::memcpy(pMaxOut, &h[2], sizeof(double));
-    decodeCcdOut(h, filtered, alphaOut, pair2);
+    *pMaxOut = double_of_bits(h[CCD_AUX]);
+    *alphaOut = boundAndPair(StepBound(h[CCD_MIN], h[CCD_ARG], double_of_bits(h[CCD_STEP])), pair2);
 }
 
 double HipContact::ccdFull(const HipMesh& mesh, const double* x_dev, const double* p_dev, const int* dbc_dev, double slackness, double stepSize,
@@ -3098,30 +3102,25 @@ double HipContact::ccdFull(const HipMesh& mesh, const double* x_dev, const doubl
 {
     if (!surfaceSet) throw StateError("ccd before set_surface");
     const int* pf = pairFlags(mesh.nV, dbc_dev);
+    unsigned long long* out = ccdOutBegin(stepSize);
     long long nCells;
     const Grid g = makeGrid(mesh, x_dev, p_dev, stepSize, mesh.avgEdgeLen, nCells);
-    buildCells(g, nCells, nSF, 3, d_SF.p, x_dev, p_dev, stepSize, cellCountT_, cellStartT_, cellItemsT_);
-    buildCells(g, nCells, nSFE, 2, d_SFE.p, x_dev, p_dev, stepSize, cellCountE_, cellStartE_, cellItemsE_);
-    ccdOut_.alloc(4);
-    const unsigned long long init[2] = { ~0ull, ~0ull };
-    HIP_CHECK(hipMemcpyAsync(ccdOut_.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    buildCells(g, nCells, x_dev, p_dev, stepSize);
     counters_.alloc(C_COUNT);
     counters_.zero(stream);
-    CcdOut o{ ccdOut_.p, ccdOut_.p + 1 };
+    const CcdOut o{ out + CCD_MIN, out + CCD_ARG };
+    const int *startT = gridStart_.p, *startE = gridStart_.p + nCells + 1;
     for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(k_ccd_full_pt, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, p_dev, pf, g, cellStartT_.p,
-            cellItemsT_.p, stepSize, slackness, pass, o, counters_.p);
-        hipLaunchKernelGGL(k_ccd_full_ee, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, g, cellStartE_.p, cellItemsE_.p,
-            stepSize, slackness, pass, o, counters_.p);
+        if (nSVI)
+            hipLaunchKernelGGL(k_ccd_full_pt, dim3(nblk(nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, x_dev, p_dev, pf, g, startT, (const int*)gridItems_.p,
+                stepSize, slackness, pass, o, counters_.p + C_QUERIED);
+        if (nSFE)
+            hipLaunchKernelGGL(k_ccd_full_ee, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, g, startE, (const int*)gridItems_.p, stepSize,
+                slackness, pass, o, counters_.p + C_QUERIED);
     }
-    unsigned long long h[2];
-    int cnt[2];
-    HIP_CHECK(hipMemcpyAsync(h, ccdOut_.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-    counters_.download(cnt, 2, stream);
-    if (nCand) *nCand = cnt[0];
-    double out;
-    decodeCcdOut(h, stepSize, &out, pair2);
-    return out;
+    readSweep();
+    if (nCand) *nCand = readback_.p->refCount[C_QUERIED];
+    return boundAndPair(StepBound(readback_.p->refCcd[CCD_MIN], readback_.p->refCcd[CCD_ARG], stepSize), pair2);
 }
 
 double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, const double* p_dev, const int* dbc_dev, double slackness, double alpha,
@@ -3207,69 +3206,45 @@ double HipContact::ccdFullReference(const HipMesh& mesh, const double* x_dev, co
             hipLaunchKernelGGL(k_ref_insert, dim3(nblk(nPrims[q], BLOCK)), dim3(BLOCK), 0, stream, nPrims[q], nvs[q], prims[q], d_v2sv.p, refVbox_.p, g, 1,
                 refCount + q * nC1, (const int*)(refStart_.p + q * nC1), refItems_.p);
     refCount_.done();
-    ccdOut_.alloc(4);
+    unsigned long long* out = ccdOutBegin(alpha);
     counters_.alloc(C_COUNT);
     constexpr int HIT_CAP = 1 << 20;
-    const bool twoPass = false; // (true: the limiting pair by a second run of the sweep, rounds 1-2; profiles/r03m_contact_bench_lds_jacobi_two_pass_ccd.json)
-    if (!twoPass) ccdHits_.ensure(2 * (size_t)HIT_CAP);
-    HIP_CHECK(hipMemsetAsync(ccdOut_.p, 0xFF, 3 * sizeof(unsigned long long), stream)); // "no time yet" = all ones
+    ccdHits_.ensure(2 * (size_t)HIT_CAP);
     counters_.zero(stream);
-    CcdOut o{ ccdOut_.p, ccdOut_.p + 1, twoPass ? nullptr : ccdHits_.p, counters_.p + C_HITS, twoPass ? 0 : HIT_CAP };
+    CcdOut o{ out + CCD_MIN, out + CCD_ARG, ccdHits_.p, counters_.p + C_HITS, HIT_CAP };
     const RefLists L{ refStart_.p, refItems_.p, refStart_.p + nC1, refItems_.p, refStart_.p + 2 * nC1, refItems_.p };
     auto sweep = [&](int pass) {
         hipLaunchKernelGGL(k_ref_sweep_vertex, dim3(nblk(SWEEP_COOP * (long long)nSVI, BLOCK)), dim3(BLOCK), 0, stream, nSVI, d_SVI.p, d_SF.p, d_SFE.p, x_dev, p_dev, pf,
             d_v2sv.p, refVbox_.p, g, L, alpha, slackness, pass, o, counters_.p);
         // the bound the vertex sweeps left is what the edge pairs' boxes are swept over (SelfCollisionHandler.cpp:1189, 1219)
-        if (pass == 0) HIP_CHECK(hipMemcpyAsync(ccdOut_.p + 2, ccdOut_.p, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+        if (pass == 0) HIP_CHECK(hipMemcpyAsync(out + CCD_AUX, out + CCD_MIN, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
         if (nSFE)
             hipLaunchKernelGGL(k_ref_sweep_edge, dim3(nblk(SWEEP_COOP * (long long)nSFE, BLOCK)), dim3(BLOCK), 0, stream, nSFE, d_SFE.p, x_dev, p_dev, pf, d_v2sv.p,
-                refVbox_.p, g, L.startE, L.itemsE, alpha, ccdOut_.p + 2, slackness, pass, o, counters_.p);
+                refVbox_.p, g, L.startE, L.itemsE, alpha, out + CCD_AUX, slackness, pass, o, counters_.p);
     };
     sweep(0);
-    if (twoPass) sweep(1);
-    else hipLaunchKernelGGL(k_ccd_hits_arg, dim3(64), dim3(BLOCK), 0, stream, o);
-    unsigned long long h[2];
-    int cnt[2];
-    // minimum, pair and the two counters in one read-back through mapped memory
-    static_assert(C_QUERIED == 0 && C_HITS == 1, "published as a pair");
-    prims::launch_publish(ccdOut_.p, readback_.dev->refCcd, 2, stream);
-    prims::launch_publish(counters_.p + C_QUERIED, readback_.dev->refCount, 2, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
-    h[0] = readback_.p->refCcd[0];
-    h[1] = readback_.p->refCcd[1];
-    cnt[C_QUERIED] = readback_.p->refCount[C_QUERIED];
-    cnt[C_HITS] = readback_.p->refCount[C_HITS];
-    if (!twoPass && cnt[C_HITS] > HIT_CAP) { // more hits than the list holds (never seen): the limiting pair by the second run after all
+    hipLaunchKernelGGL(k_ccd_hits_arg, dim3(64), dim3(BLOCK), 0, stream, o);
+    readSweep();
+    if (readback_.p->refCount[C_HITS] > HIT_CAP) { // more hits than the list holds (never seen): the limiting pair by a second run of the sweep
         sweep(1);
-        HIP_CHECK(hipMemcpyAsync(h, ccdOut_.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        readSweep();
     }
-    if (nCand) *nCand = cnt[C_QUERIED];
-    double t;
-    std::memcpy(&t, &h[0], sizeof(t));
-    if (h[1] == ~0ull || !(t < alpha)) return alpha;
-    if (arg3) {
-        const int isEE = (int)(h[1] >> 63);
-        arg3[0] = isEE ? K_EE : (int)((h[1] >> 31) & 3); // rank 0 / 1 / 2 = K_PP / K_PE / K_PT
-        arg3[1] = (int)((h[1] >> 33) & 0x3FFFFFFF);
-        arg3[2] = (int)(h[1] & 0x7FFFFFFF);
-    }
-    return t;
+    if (nCand) *nCand = readback_.p->refCount[C_QUERIED];
+    const StepBound b(readback_.p->refCcd[CCD_MIN], readback_.p->refCcd[CCD_ARG], alpha);
+    if (arg3 && b.limited) unpack_ref_key(b.key, arg3);
+    return b.t;
 }
 
 bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const int* dbc_dev)
 {
     if (!surfaceSet) throw StateError("is_intersected before set_surface");
     const int* pf = pairFlags(mesh.nV, dbc_dev);
+    auto byPredicates = [&](auto* exact, auto* plain) { return exactPredicates ? exact : plain; }; // the kernel's instantiation (see seg_tri_intersect)
     auto pointsInTets = [&]() {
         if (codimPoints.empty() || !mesh.nT) return;
         const dim3 grid(nblk((long long)codimPoints.size() * mesh.nT, BLOCK));
-        if (exactPredicates)
-            hipLaunchKernelGGL(k_points_in_tets<true>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
-                pf, counters_.p);
-        else
-            hipLaunchKernelGGL(k_points_in_tets<false>, grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT, mesh.d_tet.p, x_dev,
-                pf, counters_.p);
+        hipLaunchKernelGGL(byPredicates(k_points_in_tets<true>, k_points_in_tets<false>), grid, dim3(BLOCK), 0, stream, (int)codimPoints.size(), d_codimPoints.p, mesh.nT,
+            mesh.d_tet.p, x_dev, pf, counters_.p);
     };
     counters_.alloc(C_COUNT);
     if (nSF == 0 || nSFE == 0) {
@@ -3309,12 +3284,8 @@ bool HipContact::isIntersected(const HipMesh& mesh, const double* x_dev, const i
         hipLaunchKernelGGL(k_grid_insert_both, dim3(nblk(nSFE, BLOCK)), dim3(BLOCK), 0, stream, 0, (const int*)nullptr, nSFE, d_SFE.p, x_dev, g, 0, 0.0, 1, capItems, stale,
             gridCount, gridStart_.p, gridItems_.p);
         gridCount_.done();
-        if (exactPredicates)
-            hipLaunchKernelGGL(k_intersect<true>, dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
-                gridItems_.p, counters_.p, capItems);
-        else
-            hipLaunchKernelGGL(k_intersect<false>, dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev, pf, g, gridStart_.p,
-                gridItems_.p, counters_.p, capItems);
+        hipLaunchKernelGGL(byPredicates(k_intersect<true>, k_intersect<false>), dim3(nblk(COOP * (long long)nSF, BLOCK)), dim3(BLOCK), 0, stream, nSF, d_SF.p, d_SFE.p, x_dev,
+            pf, g, gridStart_.p, gridItems_.p, counters_.p, capItems);
         pointsInTets();
         hipLaunchKernelGGL(k_publish_narrow, dim3(1), dim3(1), 0, stream, counters_.p, gridStart_.p + nCells, box_dev, &readback_.dev->build);
         HIP_CHECK(hipStreamSynchronize(stream));

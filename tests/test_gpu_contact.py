@@ -132,6 +132,77 @@ def test_ccd_step_bounds_and_intersection_check(orc, pair):
     assert not c.is_intersected()
 
 
+def test_swept_grid_shares_counters_and_item_list_with_the_other_grids(orc, gpu_lib):
+    """ccd_full builds its cell lists in the counters, offsets and item list of the build's and the check's grids, and reads back through the record the
+    reference sweep uses.  A sequence that changes cell size, cell count and item total between the passes (a step 20 times as long, then none at all:
+    cells of the mean edge length) and puts a build, a check and the reference sweep in between returns, call by call, the bits a fresh context returns,
+    and what the oracle returns (bound to 1e-12, same pair, same candidate count)."""
+    V, F = two_blocks(0.004, n=3)
+    V = scene.jitter(V, F, rel=3e-3)
+    SF = scene.surface_tris(F)
+    nA = V.shape[0] // 2
+    dbc = np.nonzero(V[:, 1] < 1e-3 + V[:, 1].min())[0].astype(np.int32)
+    m = orc.Mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+    m.set_surface(SF)
+    m.set_dbc(dbc, 1)
+    dHat = 1e-3 ** 2 * m.features()["bboxDiag2"] * 40
+
+    def fresh():
+        c = gpu_lib.Context(0)
+        c.set_mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+        c.opt_init(0.025, False)
+        c.set_surface(SF)
+        c.set_dbc(dbc, 1)
+        c.enable_self_collision(1e-3)  # (contact_state asks for it; the calls below take their dHat as an argument)
+        return c
+
+    def alone(call):
+        c = fresh()
+        out = call(c)
+        c.close()
+        return out
+
+    p1 = 0.002 * np.random.default_rng(21).normal(size=V.shape)
+    p1[nA:, 1] -= 0.02  # upper slab pushed into the lower one
+    p1 = p1.reshape(-1)
+    p2, p0 = 20.0 * p1, 0.0 * p1
+    full = {k: (lambda c, p=p: c.ccd_full(p, 0.8, 1.0)) for k, p in (("p1", p1), ("p2", p2), ("p0", p0))}
+    want = {k: orc.ccd_full(m, p, 0.8, 1.0) for k, p in (("p1", p1), ("p2", p2), ("p0", p0))}
+    print("oracle ccd_full (bound, pair, candidates):", want)
+    assert want["p1"][2] > 0 and want["p2"][2] > 0 and want["p1"][2] != want["p2"][2]  # no empty sweeps, and the item total changes
+    assert want["p1"][0] < 1.0 and want["p2"][0] < want["p1"][0]
+
+    def same_full(got, k):
+        ref = alone(full[k])
+        print(k, "sequence", got, "fresh", ref)
+        assert np.float64(got[0]).view(np.uint64) == np.float64(ref[0]).view(np.uint64) and got[1:] == ref[1:], (k, got, ref)
+        fo, pfo, no = want[k]
+        assert abs(got[0] - fo) <= 1e-12 * fo and got[1] == pfo and got[2] == no, (k, got, want[k])
+
+    c = fresh()
+    same_full(full["p1"](c), "p1")
+    assert c.is_intersected() == alone(lambda f: f.is_intersected()) == orc.is_intersected(m) == False  # noqa: E712
+    same_full(full["p2"](c), "p2")
+    built, built_fresh = c.contact_build(dHat), alone(lambda f: f.contact_build(dHat))
+    assert len(built["active"]) > 10
+    for k in ("active", "para", "para_eiej", "cs_ptee"):
+        assert np.array_equal(built[k], built_fresh[k]), k
+    same_full(full["p1"](c), "p1")
+    same_full(full["p0"](c), "p0")
+    ref_sweep = lambda f: f.ccd_full_reference(p1, 0.8, 1.0)  # noqa: E731
+    got, ref = ref_sweep(c), alone(ref_sweep)
+    assert [np.float64(v).view(np.uint64) for v in got[:2]] == [np.float64(v).view(np.uint64) for v in ref[:2]] and got[2:] == ref[2:] and got[3] > 0, (got, ref)
+    same_full(full["p1"](c), "p1")
+
+    def after_build(f):
+        f.contact_build(dHat)
+        return f.ccd_partial(p1, 0.8, 1.0), f.contact_state()
+    (sg, pg), state = c.ccd_partial(p1, 0.8, 1.0), c.contact_state()
+    (sf, pf), state_fresh = alone(after_build)
+    assert np.float64(sg).view(np.uint64) == np.float64(sf).view(np.uint64) and sg < 1.0 and pg == pf and state == state_fresh, (sg, sf, pg, pf, state, state_fresh)
+    c.close()
+
+
 def test_grid_over_the_last_measured_box_survives_a_mesh_that_moves_away(orc, pair):
     """Constraint-set build and intersection check lay their grid over the bounding box the LAST build or check measured and read everything back with one
     synchronisation (round 6).  A mesh that has left that box is noticed on the device (stale flag: nothing runs) and the pass repeats on the fresh box;

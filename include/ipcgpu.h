@@ -582,6 +582,54 @@ int ipcgpu_chamber_gas_get(ipcgpu_ctx*, int* isGas_nCh, double* ambient_nCh, dou
 int ipcgpu_chamber_gas_state(ipcgpu_ctx*, double* volume_nCh, double* gauge_nCh, double* beta_nCh);
 int ipcgpu_chamber_volume_gradient(ipcgpu_ctx*, int chamber, int projectDBC, double* u_3nV);
 int ipcgpu_chamber_gas_solve(ipcgpu_ctx*, double coef, const double* rhs_3nV, double* x_3nV);
+/* Wind and air drag on shells and body surfaces: a load that depends on how a surface faces the air and how fast it moves through it (a sheet that sinks
+ * instead of dropping, a flag, a parachute, a balloon that slows down).  A project extension: the reference has none, and gravity or ipcgpu_opt_add_neumann
+ * (a constant acceleration) cannot stand in for it.
+ *   An aerodynamic surface is a list of triangles over any nodes of the mesh -- shell triangles, boundary faces of tetrahedral components --; it need not be
+ *   closed.  Surface s has a normal coefficient Cn >= 0, a tangential coefficient Ct >= 0 and a flag oneSided; globally there is a wind velocity w, uniform
+ *   in space, and an air density rho_a > 0 (defaults: still air, 1.225).
+ *   lagging     Per triangle the unit normal n (right-hand rule), the area A and the centroid c^n are taken at the positions the time step starts from:
+ *               ipcgpu_set_aero computes them at the rest positions, ipcgpu_opt_begin_timestep refreshes them on the device before any scripted move, and
+ *               they stay fixed through that step's Newton iterations and line searches.  ipcgpu_set_positions does not move them.
+ *   energy      at positions x, with c = (x0 + x1 + x2) / 3:  u = (c - c^n) / dt - w,  u_n = u . n,  u_t = u - u_n n,  s_n = u_n (two-sided) or
+ *               max(0, u_n) (one-sided: only the face that pushes into the air is loaded);  the dissipative potential
+ *               D_t = dt (rho_a A / 6) (Cn |s_n|^3 + Ct |u_t|^3);  the force on the centroid -dD_t/dc = -(rho_a A / 2) (Cn |s_n| s_n n + Ct |u_t| u_t), a
+ *               third of it on each node;  the exact Hessian K = (rho_a A / (2 dt)) (2 Cn |s_n| n n^T + Ct (|u_t| (I - n n^T) + u_t u_t^T / |u_t|)), PSD as it
+ *               stands (no projection), K / 9 in each of the nine nodal blocks.  At |u_t| = 0 the tangential part is exactly zero, at s_n = 0 the normal
+ *               part, a triangle of zero lagged area contributes nothing; nothing is written for a part that vanishes, and no NaN or Inf is produced.
+ *   D enters the stepper and the building blocks (ipcgpu_assemble_newton, ipcgpu_incremental_potential, ipcgpu_gradient) wherever the elastic
+ *   codimensional terms do, with the same coefficient.  Under Newmark the velocity the term sees is still (x - x^n) / dt, as the lagged friction's: the load
+ *   is then first order in time.  Rows, columns and gradient entries of projected Dirichlet nodes are dropped; their motion still counts in c.  The term is no
+ *   stiffness: it does not enter the lagged stiffness damping (ipcgpu_opt_set_damping), whose matrix is to the bit what it is without surfaces.  Contact is
+ *   NOT changed.  Both exact solvers and the iterative solver work (the term is sparse).
+ * Not modelled: lift other than the normal component of flat-plate drag; shading of one surface by another; wind that varies in space; rods; sharded
+ * contexts (IPCGPU_ERR_UNSUPPORTED, both ways: ipcgpu_ctx_set_shard refuses a context with surfaces); ipcgpu_opt_system_report returns
+ * IPCGPU_ERR_UNSUPPORTED while surfaces are set.
+ * ipcgpu_set_aero: surface s owns the triangles [triEnd_nSurf[s - 1], triEnd_nSurf[s]) (from 0 for s = 0) of tri_colmajor (nTri x 3, nTri =
+ * triEnd_nSurf[nSurf - 1]); cn, ct, oneSided per surface.  After ipcgpu_set_mesh, before ipcgpu_opt_init (else IPCGPU_ERR_STATE) and before
+ * ipcgpu_linsys_set_pattern: the three edges of every triangle join vNeighbor (a node pattern that exists already is rebuilt by this call).  It changes no
+ * mass and marks no node.  IPCGPU_ERR_ARG, with a message that names the surface and the triangle: a node id out of range, a triangle that repeats a node,
+ * zero rest area, a triangle listed twice (in one surface or in two, in any rotation or orientation), a coefficient that is negative or not finite, an
+ * empty surface, triEnd not ascending.  nSurf == 0 removes the surfaces (no-op without any; wind and density return to their defaults), a second call
+ * replaces them (wind and density stay).  ipcgpu_set_mesh drops them.  Without a surface no aero kernel is ever launched.
+ * ipcgpu_aero_set_wind: the wind velocity and the air density, at any time, also between time steps: the next step sees them.  IPCGPU_ERR_ARG for a wind
+ * that is not finite or a density that is not positive and finite.
+ * ipcgpu_aero_get: counts2 = {nSurf, nTri}; the lists and coefficients as given; the wind and the density.  Any pointer may be null.
+ * ipcgpu_aero_state: at the current positions the force -dD_t/dc on every triangle (force_3nTri, xyz interleaved); lagged_8nTri, the records the
+ * evaluations use now (n, A, c^n, 0 per triangle); total5 = the total force (3), the dissipated power sum -f . u (>= 0) and the loaded area (the lagged area
+ * of the triangles that carry a force).  The totals are summed in two passes in a fixed order on the device: bit-reproducible.  Any pointer may be null;
+ * force and total5 need ipcgpu_opt_init (it supplies dt).
+ * ipcgpu_aero_energy / _energy_per_elem / _gradient_add / _hessian_add: the semantics of their ipcgpu_chamber_* namesakes (per-triangle terms unscaled;
+ * projected Dirichlet entries dropped; a block the pattern lacks: IPCGPU_ERR_STATE; fp64 atomics), all after ipcgpu_opt_init (IPCGPU_ERR_STATE before).
+ * Without a surface every one of these calls returns IPCGPU_OK and does nothing. */
+int ipcgpu_set_aero(ipcgpu_ctx*, int nSurf, const int* triEnd_nSurf, const int* tri_colmajor, const double* cn_nSurf, const double* ct_nSurf, const int* oneSided_nSurf);
+int ipcgpu_aero_set_wind(ipcgpu_ctx*, const double* wind3, double density);
+int ipcgpu_aero_get(ipcgpu_ctx*, int* counts2, int* triEnd_nSurf, int* tri_colmajor, double* cn_nSurf, double* ct_nSurf, int* oneSided_nSurf, double* wind3, double* density);
+int ipcgpu_aero_state(ipcgpu_ctx*, double* force_3nTri, double* lagged_8nTri, double* total5);
+int ipcgpu_aero_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_aero_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
+int ipcgpu_aero_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_aero_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

@@ -113,15 +113,16 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
 // `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its rubber membrane and its limit, ipcgpu_shell_limit_* the limit alone,
-// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers.
+// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers, ipcgpu_aero_* wind and air drag.
 constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_RUBBER | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT,
                    RUBBER_ALONE = HipOptimizer::CODIM_SHELL_RUBBER, ROD = HipOptimizer::CODIM_ROD,
-                   ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER;
+                   ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER, AERO = HipOptimizer::CODIM_AERO;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
 const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hessian: build it after ipcgpu_set_attachments";
 const char* const CHAMBER_MISS = "the pattern lacks a block of the chamber Hessian: build it after ipcgpu_set_chambers";
-// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle.
+const char* const AERO_MISS = "the pattern lacks a block of the air-drag Hessian: build it after ipcgpu_set_aero";
+// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle, no aerodynamic triangle.
 int codimCount(const HipMesh& m, unsigned which)
 {
     return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
@@ -129,7 +130,8 @@ int codimCount(const HipMesh& m, unsigned which)
         : (which & HipOptimizer::CODIM_SHELL_RUBBER) ? m.shell.nRubber()
         : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
         : (which & HipOptimizer::CODIM_ATTACH)      ? m.attach.n()
-                                                    : m.chamber.nTri();
+        : (which & HipOptimizer::CODIM_CHAMBER)     ? m.chamber.nTri()
+                                                    : m.aero.nTri();
 }
 int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
 {
@@ -176,21 +178,22 @@ int codimHessianAdd(ipcgpu_ctx* c, unsigned which, double coef, int projectDBC, 
     }
     return IPCGPU_OK;
 }
-// ipcgpu_set_shell / ipcgpu_set_rod / ipcgpu_set_attachments / ipcgpu_set_chambers (which: CODIM_SHELL / CODIM_ROD / CODIM_ATTACH / CODIM_CHAMBER): n elements,
-// set(mesh) the call that differs
+// ipcgpu_set_shell / ipcgpu_set_rod / ipcgpu_set_attachments / ipcgpu_set_chambers / ipcgpu_set_aero (which: CODIM_SHELL / CODIM_ROD / CODIM_ATTACH /
+// CODIM_CHAMBER / CODIM_AERO): n elements, set(mesh) the call that differs
 template <class Set>
 int setCodimBody(ipcgpu_ctx* c, unsigned which, bool argsOk, int n, Set&& set)
 {
     specChanged(c);
     return guarded([&] {
-        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : which == HipOptimizer::CODIM_ROD ? "rod" : which == HipOptimizer::CODIM_ATTACH ? "attachment" : "chamber";
+        const bool aero = which == HipOptimizer::CODIM_AERO;
+        const std::string what = which == HipOptimizer::CODIM_SHELL ? "shell" : which == HipOptimizer::CODIM_ROD ? "rod" : which == HipOptimizer::CODIM_ATTACH ? "attachment" : aero ? "aerodynamic surface" : "chamber";
         const bool plural = which == HipOptimizer::CODIM_ATTACH || which == HipOptimizer::CODIM_CHAMBER;
         HipMesh& m = M(c);
         bind(c);
         needArg(argsOk, ("bad " + what + " arguments").c_str());
         if (n == 0 && codimCount(m, which) == 0) return IPCGPU_OK; // nothing to remove
         if (c->worldSize > 1) throw UnsupportedError(what + "s on a sharded context");
-        need(!c->opt->initialised, ("ipcgpu_set_" + what + (plural ? "s" : "") + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
+        need(!c->opt->initialised, ("ipcgpu_set_" + (aero ? std::string("aero") : what) + (plural ? "s" : "") + " must come before ipcgpu_opt_init (masses, dHat and kappa derive from it) and before the pattern is built").c_str());
         set(m);
         if (!c->lin->rowBase.empty()) c->lin->set_pattern(m, 0, nullptr); // (a pattern built before this call lacks the new body's node pairs)
         return IPCGPU_OK;
@@ -268,6 +271,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->rod.nSeg()) throw UnsupportedError("rods on a sharded context");
         if (world > 1 && c->mesh->attach.n()) throw UnsupportedError("attachments on a sharded context");
         if (world > 1 && c->mesh->chamber.n()) throw UnsupportedError("chambers on a sharded context");
+        if (world > 1 && c->mesh->aero.n()) throw UnsupportedError("aerodynamic surfaces on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -1506,6 +1510,104 @@ int ipcgpu_chamber_gas_solve(ipcgpu_ctx* c, double coef, const double* rhs, doub
         return ok ? IPCGPU_OK : IPCGPU_NOT_PD;
     });
 }
+// ---- Wind and air drag -----------------------------------------------------------------------------------
+int ipcgpu_set_aero(ipcgpu_ctx* c, int nSurf, const int* triEnd, const int* tri, const double* cn, const double* ct, const int* oneSided)
+{
+    // (setCodimBody counts triangles: nSurf == 0 with no surface set is "nothing to remove"; it rebuilds a pattern built before this call)
+    return setCodimBody(c, HipOptimizer::CODIM_AERO, nSurf >= 0 && ((triEnd && tri && cn && ct && oneSided) || !nSurf), nSurf,
+        [&](HipMesh& m) { m.setAero(nSurf, triEnd, tri, cn, ct, oneSided, c->stream); });
+}
+int ipcgpu_aero_set_wind(ipcgpu_ctx* c, const double* wind3, double density)
+{
+    specChanged(c);
+    return guarded([&] {
+        M(c).setAeroWind(wind3, density);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_aero_get(ipcgpu_ctx* c, int* counts2, int* triEnd, int* tri, double* cn, double* ct, int* oneSided, double* wind3, double* density)
+{
+    return guarded([&] {
+        const HipAero& h = M(c).aero;
+        const AeroPlan& p = h.plan;
+        if (counts2) {
+            counts2[0] = p.n;
+            counts2[1] = p.nTri;
+        }
+        if (triEnd) std::copy(p.triEnd.begin(), p.triEnd.end(), triEnd);
+        if (tri) std::copy(p.tri.begin(), p.tri.end(), tri);
+        if (cn) std::copy(p.cn.begin(), p.cn.end(), cn);
+        if (ct) std::copy(p.ct.begin(), p.ct.end(), ct);
+        if (oneSided) std::copy(p.oneSided.begin(), p.oneSided.end(), oneSided);
+        if (wind3) std::copy(h.wind, h.wind + 3, wind3);
+        if (density) *density = h.density;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_aero_state(ipcgpu_ctx* c, double* force, double* lagged, double* total5)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        HipAero& h = c->mesh->aero;
+        const size_t n = (size_t)h.nTri();
+        if (!n) return IPCGPU_OK;
+        if (force || total5) {
+            need(o.initialised, "call ipcgpu_opt_init first (it supplies dt)");
+            const AeroView v = o.aeroView(c->mesh->d_x.p);
+            if (force) h.d_force.alloc(3 * n);
+            h.d_statePartial.ensure(5 * (size_t)aero_energy_blocks(v));
+            h.d_stateOut.alloc(5);
+            launch_aero_state(v, force ? h.d_force.p : nullptr, h.d_statePartial.p, total5 ? h.d_stateOut.p : nullptr, c->stream);
+            HIP_CHECK(hipGetLastError());
+            if (force) h.d_force.download(force, 3 * n, c->stream);
+            if (total5) h.d_stateOut.download(total5, 5, c->stream);
+        }
+        if (lagged) h.d_lagged.download(lagged, 8 * n, c->stream); // the records the evaluations use now, not those of the current positions
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_aero_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] {
+        if (E && !M(c).aero.n()) { // without a surface: nothing, whatever the state
+            *E = 0.0;
+            return (int)IPCGPU_OK;
+        }
+        return codimEnergy(c, AERO, coef, E);
+    });
+}
+int ipcgpu_aero_energy_per_elem(ipcgpu_ctx* c, double* perTri)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const int n = c->mesh->aero.nTri();
+        if (!n || !perTri) return IPCGPU_OK;
+        need(o.initialised, "call ipcgpu_opt_init first (it supplies dt)");
+        DevBuf<double> e;
+        e.alloc(n);
+        launch_aero_energy_per_elem(o.aeroView(c->mesh->d_x.p), e.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        e.download(perTri, n, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_aero_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] {
+        need(!M(c).aero.n() || O(c).initialised, "call ipcgpu_opt_init first (it supplies dt)");
+        return codimGradientAdd(c, AERO, coef, projectDBC, g);
+    });
+}
+int ipcgpu_aero_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] {
+        need(!M(c).aero.n() || O(c).initialised, "call ipcgpu_opt_init first (it supplies dt)");
+        return codimHessianAdd(c, AERO, coef, projectDBC, AERO_MISS);
+    });
+}
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)
 {
     specChanged(c);
@@ -2296,6 +2398,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         if (c->mesh->rod.nSeg()) throw UnsupportedError("system report with a rod set (the report's slices do not know the rod energy)");
         if (c->mesh->attach.n()) throw UnsupportedError("system report with attachments set (their energy belongs to no single component)");
         if (c->mesh->chamber.n()) throw UnsupportedError("system report with chambers set (the report's slices do not know the pressure energy)");
+        if (c->mesh->aero.n()) throw UnsupportedError("system report with aerodynamic surfaces set (the report's slices do not know the dissipation of the air drag)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

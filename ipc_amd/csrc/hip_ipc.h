@@ -7,6 +7,8 @@
 // one-line forwards.  Everything here is reached through the C ABI of include/ipcgpu.h.
 #pragma once
 #include "common.h"
+#include "aero_kernels.h"
+#include "aero_plan.h"
 #include "attach_kernels.h"
 #include "attach_plan.h"
 #include "chamber_kernels.h"
@@ -122,6 +124,26 @@ struct HipChamber {
     }
 };
 
+// Aerodynamic surfaces of the mesh (ipcgpu_set_aero): the host plan and its device copy.  n() == 0: none, and then nothing below is ever read.
+struct HipAero {
+    AeroPlan plan;
+    DevBuf<int> d_tri, d_surfOf;
+    DevBuf<double> d_coef, d_lagged; // d_lagged: the lagged records, the rest values until the first time step refreshes them (aero_kernels.h)
+    DevBuf<double> d_statePartial, d_stateOut, d_force; // ipcgpu_aero_state
+    double wind[3] = { 0.0, 0.0, 0.0 }, density = 1.225; // ipcgpu_aero_set_wind; back to these defaults when the surfaces are removed
+    // vNeighbor as it was before this set's pairs joined it, and HipMesh::nbVersion right after they did (setAero)
+    std::vector<int> nbPtrBefore, nbBefore;
+    unsigned nbVersionAfter = 0;
+    int n() const { return plan.n; }
+    int nTri() const { return plan.nTri; }
+    void drop()
+    {
+        plan = AeroPlan();
+        wind[0] = wind[1] = wind[2] = 0.0;
+        density = 1.225;
+    }
+};
+
 class HipMesh {
 public:
     int nV = 0, nT = 0;
@@ -187,6 +209,12 @@ public:
     // again.  setChambers and computeFeatures drop it too.
     void setChamberGas(const int* isGas, const double* ambient, const double* gamma, const double* fillVolume, hipStream_t s);
     void uploadChamberGasPressures(hipStream_t s); // d_pConst and d_pEff from plan.pressure
+    // Aerodynamic surfaces (aero_plan.h): validates, adds the plan's node pairs to vNeighbor and uploads the lists, the coefficients and the rest records.
+    // nSurf = 0 removes them, a second call replaces them (their neighbour pairs leave vNeighbor again unless something else has extended it since);
+    // computeFeatures drops them.  Touches no mass and no inMesh mark: a load is no body.  Wind and density survive a replacement, not a removal.
+    HipAero aero;
+    void setAero(int nSurf, const int* triEnd, const int* tri_colmajor, const double* cn, const double* ct, const int* oneSided, hipStream_t s);
+    void setAeroWind(const double* wind3, double density); // finite wind, finite density > 0; nothing without surfaces
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -344,11 +372,14 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h) enter wherever the tetrahedral elastic term does, with the same
-    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, limit, rod, attachments, chambers (the energy sum
-    // is (((((E + shell) + rubber) + limit) + rod) + attach) + chamber) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri()); none of them is ever sharded.
-    // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness.
-    enum : unsigned { CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_ALL = 63, CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER };
+    // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h, aero_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, limit, rod, attachments, chambers, air drag (the energy sum
+    // is ((((((E + shell) + rubber) + limit) + rod) + attach) + chamber) + aero) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri(), aero.nTri()); none of them is ever sharded.
+    // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness, and neither is air drag.
+    enum : unsigned {
+        CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_AERO = 64, CODIM_ALL = 127,
+        CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER & ~CODIM_AERO
+    };
     CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
     ShellLimitView shellLimitView(const double* x_dev) const;
@@ -360,6 +391,8 @@ public:
     enum { CHAMBER_P_EFFECTIVE = 0, CHAMBER_P_CONSTANT = 1 };
     ChamberView chamberView(const double* x_dev, int pressure = CHAMBER_P_EFFECTIVE) const;
     void refreshChamberRef(); // r_c of every chamber from the current positions, on the device (beginTimestep)
+    AeroView aeroView(const double* x_dev) const; // (with the wind, the density and dt as they are now)
+    void refreshAeroLagged(); // n, A and c^n of every aerodynamic triangle from the current positions, on the device (beginTimestep)
     // The gas chambers' dense rank-k Hessian term, coef sum_c beta_c u_c u_c^T, as a correction around the solver's retained factor (chamber_kernels.h):
     // y_dev holds A^-1 r on entry and (A + coef sum beta_c u_c u_c^T)^-1 r on return, with beta and u at the mesh's current positions.  k further solves,
     // everything on the stream, no synchronisation.  Nothing without a gas chamber.  The stepper (computeSearchDir) and ipcgpu_chamber_gas_solve both call it.

@@ -39,6 +39,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
     if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
     chamber.gas = ChamberGas(); // ... with their gas law
+    if (aero.n()) aero.drop(); // ... and the aerodynamic surfaces
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -365,6 +366,48 @@ void HipMesh::setChambers(int nCh, const int* triEnd, const int* tri, const doub
         d_codimErr.zero(s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setAero(int nSurf, const int* triEnd, const int* tri, const double* cn, const double* ct, const int* oneSided, hipStream_t s)
+{
+    if (nSurf == 0 && aero.n() == 0) return; // nothing to remove: no state changes at all
+    AeroPlan plan;
+    std::string err;
+    if (!buildAeroPlan(nV, V_rest.data(), nSurf, triEnd, tri, cn, ct, oneSided, plan, err)) throw ArgError(err);
+    // The plan's pairs (the triangle edges) join vNeighbor; those of the set this call replaces or removes leave it again where nothing else has touched
+    // vNeighbor since (setChambers)
+    if (aero.n() && aero.nbVersionAfter == nbVersion) {
+        nbPtr = aero.nbPtrBefore;
+        nb = aero.nbBefore;
+    }
+    aero.nbPtrBefore = nbPtr;
+    aero.nbBefore = nb;
+    addNeighbourPairs(plan.pairs);
+    aero.nbVersionAfter = nbVersion;
+    if (!plan.n) {
+        aero.drop();
+        return;
+    }
+    aero.plan = std::move(plan);
+    const AeroPlan& p = aero.plan;
+    aero.d_tri.upload(p.tri, s);
+    aero.d_surfOf.upload(p.surfOf, s);
+    aero.d_coef.upload(p.coef, s);
+    aero.d_lagged.upload(p.restRecord, s);
+    if (!d_codimErr.n) { // the first codimensional term of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setAeroWind(const double* wind3, double density)
+{
+    if (!wind3 || !std::isfinite(wind3[0]) || !std::isfinite(wind3[1]) || !std::isfinite(wind3[2])) throw ArgError("aero_set_wind: the wind is not finite");
+    if (!(density > 0.0) || !std::isfinite(density)) throw ArgError("aero_set_wind: the air density must be positive and finite");
+    if (!aero.n()) return;
+    for (int a = 0; a < 3; ++a) aero.wind[a] = wind3[a];
+    aero.density = density;
 }
 
 void HipMesh::setChamberPressure(const double* pressure, hipStream_t s)

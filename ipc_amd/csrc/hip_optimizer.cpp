@@ -85,6 +85,7 @@ CODIM_VIEW_LAYOUT(ShellRubberView, ShellRubberFields, nTri);
 CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
 CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
 CODIM_VIEW_LAYOUT(ChamberView, ChamberFields, nTri);
+CODIM_VIEW_LAYOUT(AeroView, AeroFields, nTri);
 #pragma clang diagnostic pop
 #undef CODIM_VIEW_LAYOUT
 
@@ -209,6 +210,30 @@ void HipOptimizer::refreshChamberRef()
     HIP_CHECK(hipGetLastError());
 }
 
+AeroView HipOptimizer::aeroView(const double* x_dev) const
+{
+    const HipAero& h = mesh.aero;
+    AeroView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nTri = h.nTri();
+    v.n = h.n();
+    v.tri = h.d_tri.p;
+    v.surfOf = h.d_surfOf.p;
+    v.coef = h.d_coef.p;
+    v.lagged = h.d_lagged.p;
+    for (int a = 0; a < 3; ++a) v.wind[a] = h.wind[a];
+    v.density = h.density;
+    v.dt = dt;
+    return v;
+}
+
+void HipOptimizer::refreshAeroLagged()
+{
+    if (!mesh.aero.n()) return;
+    launch_aero_refresh(aeroView(mesh.d_x.p), mesh.aero.d_lagged.p, stream);
+    HIP_CHECK(hipGetLastError());
+}
+
 // The codimensional terms, one row each, in launch order.  A new term is a kernel file, a view builder and a row here.
 namespace {
 struct CodimTerm {
@@ -249,6 +274,9 @@ const CodimTerm CODIM_TERMS[] = {
             if (h.nGas()) launch_chamber_gas_update(o.chamberView(x), h.gasView(), 0.0, nullptr, false, o.stream);
             launch_chamber_assemble(o.chamberView(x), coef, proj, g, a, err, o.stream);
         } },
+    { HipOptimizer::CODIM_AERO, [](const HipMesh& m) { return m.aero.nTri(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_aero_energy(o.aeroView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_aero_assemble(o.aeroView(x), coef, proj, g, a, err, o.stream); } },
 };
 } // namespace
 
@@ -627,7 +655,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness)
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness, nor is air drag)
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -1704,6 +1732,7 @@ void HipOptimizer::beginTimestep()
     if (!initialised) throw StateError("opt_begin_timestep before opt_init");
     if (!lin.analyzed()) throw StateError("opt_begin_timestep before opt_precompute");
     Tic t(timers[11], stream);
+    refreshAeroLagged(); // normals, areas and centroids of the aerodynamic triangles: from the positions this step starts from, before any scripted move (aero_kernels.h)
     refreshChamberRef(); // r_c of the pressure chambers follows the body: from the positions this step starts from, fixed until the next step (chamber_kernels.h)
     // The contact-free twist (BASELINE configs[1]; round 6): everything the set-up of a time step asks the device -- inverted before the motion? the filter's bound
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each

@@ -813,6 +813,64 @@ class Context:
         """the sparse part only: a gas chamber's rank-one term beta gradV gradV^T lives in chamber_gas_solve and the stepper"""
         self._codim_hessian_add("chamber", coef, projectDBC)
 
+    # ---- wind and air drag (ipcgpu_set_aero: a drag load on triangle surfaces that depends on their normal and their velocity against the air)
+    def set_aero(self, tri_lists, cn=1.28, ct=0.0, one_sided=False):
+        """tri_lists: one m x 3 array of node ids per surface (shell triangles or boundary faces, open or closed); cn, ct, one_sided: a scalar or one value
+        per surface.  D = dt (rho_a A / 6) (cn |s_n|^3 + ct |u_t|^3) per triangle, normal, area and start centroid lagged per time step.  After set_mesh,
+        before opt_init and set_pattern; changes no mass.  An empty list removes the surfaces."""
+        lists = [np.asarray(t, dtype=np.int32).reshape(-1, 3) for t in tri_lists]
+        if len(lists) == 0:
+            self._chk(self._L.ipcgpu_set_aero(self.h, C.c_int(0), None, None, None, None, None))
+            return
+        n = len(lists)
+        a = _f64(np.broadcast_to(np.asarray(cn, dtype=np.float64), (n,)))
+        b = _f64(np.broadcast_to(np.asarray(ct, dtype=np.float64), (n,)))
+        o = _i32(np.broadcast_to(np.asarray(one_sided), (n,)).astype(bool))
+        end = _i32(np.cumsum([len(t) for t in lists]))
+        tri = np.asfortranarray(np.vstack(lists), dtype=np.int32)
+        self._chk(self._L.ipcgpu_set_aero(self.h, C.c_int(n), _ip(end), _ip(tri), _dp(a), _dp(b), _ip(o)))
+
+    def aero_set_wind(self, wind=(0.0, 0.0, 0.0), density=1.225):
+        """the wind velocity (uniform in space) and the air density, at any time, also between time steps"""
+        w = _f64(np.asarray(wind, dtype=np.float64).reshape(3))
+        self._chk(self._L.ipcgpu_aero_set_wind(self.h, _dp(w), C.c_double(density)))
+
+    def _aero_counts(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_aero_get(self.h, _ip(cnt), None, None, None, None, None, None, None))
+        return int(cnt[0]), int(cnt[1])
+
+    def aero_get(self):
+        """dict: n (surfaces), nTri, triEnd, tri (nTri x 3, as given), cn, ct, oneSided, wind, density"""
+        n, nTri = self._aero_counts()
+        cnt, end, tri = np.zeros(2, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((nTri, 3), dtype=np.int32, order="F")
+        cn, ct, one, w, rho = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(3), C.c_double()
+        self._chk(self._L.ipcgpu_aero_get(self.h, _ip(cnt), _ip(end), _ip(tri), _dp(cn), _dp(ct), _ip(one), _dp(w), C.byref(rho)))
+        return {"n": n, "nTri": nTri, "triEnd": end, "tri": np.ascontiguousarray(tri), "cn": cn, "ct": ct, "oneSided": one.astype(bool), "wind": w, "density": rho.value}
+
+    def aero_state(self, with_force=True):
+        """(force nTri x 3, lagged nTri x 8, total5): the force on every triangle at the current positions, the lagged records (n, A, c^n, 0) the evaluations
+        use now, and the total force (3), the dissipated power and the loaded area.  with_force=False: the lagged records alone (allowed before opt_init)."""
+        nTri = self._aero_counts()[1]
+        f, lag, tot = np.zeros((nTri, 3)), np.zeros((nTri, 8)), np.zeros(5)
+        self._chk(self._L.ipcgpu_aero_state(self.h, _dp(f) if with_force else None, _dp(lag), _dp(tot) if with_force else None))
+        return f, lag, tot
+
+    def aero_energy(self, coef=1.0):
+        return self._codim_energy("aero", coef)
+
+    def aero_energy_per_elem(self):
+        e = np.zeros(self._aero_counts()[1])
+        self._chk(self._L.ipcgpu_aero_energy_per_elem(self.h, _dp(e)))
+        return e
+
+    def aero_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * air-drag gradient; returns it"""
+        return self._codim_gradient_add("aero", coef, projectDBC, grad)
+
+    def aero_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("aero", coef, projectDBC)
+
     # ---- the gas law of the chambers (ipcgpu_chamber_set_gas)
     def chamber_set_gas(self, is_gas, ambient=0.0, gamma=1.0, fill_volume=None):
         """per chamber (scalars broadcast): is_gas (False: constant pressure), the ambient absolute pressure, the exponent gamma (1 isothermal, 1.4 adiabatic

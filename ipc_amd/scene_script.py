@@ -13,7 +13,8 @@ Keywords of this project beside the reference's: `shell`, `limit`, `rod`, `conta
 `contactIgnore`, `contactFric`, `attach <shapeA> <nodeA> <shapeB> <nodeB> <k> [<L>]` and `stitch <shapeA> <shapeB> <radius> <k> [rest]` (see SceneConfig):
 the last two tie nodes of two shapes by springs (Context.set_attachments); barycentric points stay an API feature.  `pressure <p> [ramp <seconds>]
 [gas <ambient> [gamma <g>]]` on a shape line (a `shell` shape or a tetrahedral shape) makes the shape's closed surface one pressure chamber, constant or
-following the ideal-gas law (Context.set_chambers, Context.chamber_set_gas; see Shape).
+following the ideal-gas law (Context.set_chambers, Context.chamber_set_gas; see Shape).  `aero [cn <C>] [ct <C>] [onesided]` on such a shape line makes its
+surface an aerodynamic surface (Context.set_aero; see Shape) in the wind of the top-level line `wind <wx> <wy> <wz> [density <rho>]` (see SceneConfig).
 """
 from dataclasses import dataclass, field
 import math
@@ -80,6 +81,14 @@ class Shape:
     # adiabatic air), filled at the rest volume; p is then the gauge pressure at the rest volume, ambient + p > 0, and a `ramp` pumps the gas in
     pressure: float = None
     pressure_ramp: float = 0.0
+    # `aero [cn <C>] [ct <C>] [onesided]` (this project's keyword, on a `shell` shape or a tetrahedral shape): the shape's surface triangles are ONE
+    # aerodynamic surface with the normal and tangential drag coefficients cn >= 0 (default 1.28, a flat plate) and ct >= 0 (default 0) in the scene's
+    # `wind` (Context.set_aero).  On a `shell` shape the triangles are the shell's own, two-sided unless `onesided` is given; on a tetrahedral shape they are
+    # the outward boundary faces, always one-sided (only the face that pushes into the air is loaded)
+    aero: bool = False
+    aero_cn: float = 1.28
+    aero_ct: float = 0.0
+    aero_onesided: bool = False
     pressure_gas: bool = False
     pressure_ambient: float = 0.0
     pressure_gamma: float = 1.0
@@ -137,6 +146,10 @@ class SceneConfig:
     # an error.  Contact between the two shapes is not changed: mask it with contactGroup / contactIgnore, or give a rest length.
     attach: list = field(default_factory=list)  # (shapeA, nodeA, shapeB, nodeB, k, L)
     stitch: list = field(default_factory=list)  # (shapeA, shapeB, radius, k, rest)
+    # `wind <wx> <wy> <wz> [density <rho>]` (this project's keyword, a top-level line): the wind velocity, uniform in space, and the air density the `aero`
+    # shapes see (Context.aero_set_wind).  Default: still air of density 1.225
+    wind: tuple = (0.0, 0.0, 0.0)
+    air_density: float = 1.225
 
     def uses_contact_groups(self):
         return bool(self.contact_ignore or self.contact_fric or any(sh.contact_group for sh in self.shapes))
@@ -383,6 +396,14 @@ class SceneConfig:
                 if not (math.isfinite(radius) and radius >= 0 and math.isfinite(kk) and kk > 0):
                     raise ValueError("stitch: the radius must not be negative and k must be positive")
                 cfg.stitch.append((int(a[0]), int(a[1]), radius, kk, len(a) == 5))
+            elif k == "wind":  # this project's keyword: the wind the `aero` shapes see
+                if len(a) not in (3, 5) or (len(a) == 5 and a[3] != "density"):
+                    raise ValueError("wind needs <wx> <wy> <wz> [density <rho>]")
+                cfg.wind = (float(a[0]), float(a[1]), float(a[2]))
+                if len(a) == 5:
+                    cfg.air_density = float(a[4])
+                if not all(math.isfinite(v) for v in cfg.wind) or not (0.0 < cfg.air_density < math.inf):
+                    raise ValueError("wind: the velocity must be finite and the density positive and finite")
             elif k in VIEWER_KEYWORDS:
                 pass  # viewer / logging only
             elif k in ("resolution", "inexactSolve"):
@@ -511,6 +532,21 @@ def _parse_shape(st, resolve):
                 # (with a ramp the pressure starts near 0: the ambient pressure alone must then carry the gas)
                 if not sh.pressure_ambient + min(sh.pressure, 0.0 if sh.pressure_ramp > 0.0 else sh.pressure) > 0.0:
                     raise ValueError("gas needs ambient + pressure > 0 (the absolute pressure at the rest volume)")
+        elif e == "aero":
+            sh.aero = True
+            while j < len(st) and st[j] in ("cn", "ct", "onesided"):
+                if st[j] == "onesided":
+                    sh.aero_onesided = True
+                    j += 1
+                    continue
+                if j + 1 >= len(st):
+                    raise ValueError(f"{st[j]} needs a coefficient")
+                setattr(sh, "aero_" + st[j], float(st[j + 1]))
+                j += 2
+            if not (0.0 <= sh.aero_cn < float("inf")) or not (0.0 <= sh.aero_ct < float("inf")):
+                raise ValueError("aero needs finite coefficients cn >= 0 and ct >= 0")
+        elif e in ("cn", "ct", "onesided"):
+            raise ValueError(f"{e} is valid behind aero only")
         elif e == "initVel":
             v = [float(x) for x in st[j:j + 6]]
             sh.init_vel = (tuple(v[:3]), tuple(v[3:]))
@@ -545,6 +581,12 @@ def _parse_shape(st, resolve):
         raise ValueError("shell is valid on a triangle-mesh shape only (not on a tetrahedral, segment or point shape)")
     if sh.rod_radius is not None and os.path.splitext(sh.path.lower())[1] != ".seg":
         raise ValueError("rod is valid on a segment shape only (not on a tetrahedral, triangle-mesh or point shape)")
+    if sh.aero:
+        ext = os.path.splitext(sh.path.lower())[1]
+        if ext in (".seg", ".pt") or (ext == ".obj" and sh.shell_thickness is None):
+            raise ValueError("aero is valid on a shell shape or a tetrahedral shape only (not on a segment, point or kinematic triangle-mesh shape)")
+        if ext != ".obj":
+            sh.aero_onesided = True  # the boundary faces of a solid have one side in the air
     if sh.pressure is not None:
         ext = os.path.splitext(sh.path.lower())[1]
         if ext in (".seg", ".pt") or (ext == ".obj" and sh.shell_thickness is None):
@@ -648,6 +690,10 @@ class AssembledScene:
     # pressure, ramp (seconds per chamber, 0: none)}, or None.  Where a shape carries `gas` the dictionary also holds gas (bool), ambient and gamma per chamber,
     # as Context.chamber_set_gas takes them
     chambers: dict = None
+    # the shapes that carry `aero`, one aerodynamic surface each in script order, as Context.set_aero takes them: {tri_lists (global node ids), cn, ct,
+    # one_sided (per surface)}, or None.  Set by assemble(); a plain attribute, not a field, so that the fields of a scene without the keyword are what
+    # they were.  The wind itself is the scene's (cfg.wind, cfg.air_density)
+    aero = None
 
     def chamber_pressures(self, t):
         """the pressures of the chambers for the time step that ends at time t: p min(1, t / ramp) where a shape gives `ramp`, p elsewhere; None when no
@@ -746,6 +792,7 @@ class _Parts:
     shells: list = field(default_factory=list)  # (triangles, thickness, bend scale, (rho, E, nu), (limit or 0, onset, stiffness), (model, alpha)) per `shell` shape
     rods: list = field(default_factory=list)  # (segments, radius, bend scale, (rho, E, nu)) per `rod` shape
     chambers: list = field(default_factory=list)  # (triangle list, pressure, ramp, (gas, ambient, gamma)) per `pressure` shape
+    aero: list = field(default_factory=list)  # (triangle list, cn, ct, one-sided) per `aero` shape
 
 
 def _read_shape(sh, read_mesh):
@@ -764,8 +811,25 @@ def _read_shape(sh, read_mesh):
     return ext, V, T, SF, E
 
 
-def _codim_keywords(cfg, sh, name, V, SF, E, off, p):
-    """the `shell`, `rod` and `pressure` keywords of one shape (transformed nodes V, first node `off`) as records of p"""
+def _outward_faces(SF, T, V):
+    """the boundary faces SF of the tetrahedra T (node ids into V), each turned so that its normal (right-hand rule) points away from the fourth node of its
+    tetrahedron: outward, piece by piece, on the transformed shape (a mirroring scale flips the file's orientation)"""
+    apex = {}
+    for t in np.asarray(T):
+        for k in range(4):
+            apex[tuple(sorted(int(v) for v in np.delete(t, k)))] = int(t[k])
+    tri = np.array(SF, dtype=np.int32).reshape(-1, 3)
+    for i, f in enumerate(tri):
+        a = apex.get(tuple(sorted(int(v) for v in f)))
+        if a is None:
+            raise ValueError(f"aero: surface triangle {i} is no face of a tetrahedron")
+        if np.dot(np.cross(V[f[1]] - V[f[0]], V[f[2]] - V[f[0]]), V[a] - V[f[0]]) > 0.0:
+            tri[i] = f[::-1]
+    return tri
+
+
+def _codim_keywords(cfg, sh, name, V, T, SF, E, off, p):
+    """the `shell`, `rod`, `pressure` and `aero` keywords of one shape (transformed nodes V, first node `off`) as records of p"""
     mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
     if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
         p.shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat, (0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff),
@@ -774,6 +838,11 @@ def _codim_keywords(cfg, sh, name, V, SF, E, off, p):
         p.rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
     if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
         p.chambers.append((_chamber_list(SF, V, name) + off, sh.pressure, sh.pressure_ramp, (sh.pressure_gas, sh.pressure_ambient, sh.pressure_gamma)))
+    if sh.aero:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other): the shell's own triangles as they are, or the outward boundary faces
+        if len(SF) == 0:
+            raise ValueError(f"aero: {name} has no surface triangle")
+        tri = np.array(SF, dtype=np.int32).reshape(-1, 3) if sh.shell_thickness is not None else _outward_faces(SF, T, V)
+        p.aero.append((tri + off, sh.aero_cn, sh.aero_ct, sh.aero_onesided))
 
 
 def _assemble_shapes(cfg, read_mesh):
@@ -809,7 +878,7 @@ def _assemble_shapes(cfg, read_mesh):
             ids = np.arange(V.shape[0], dtype=np.int32) + off
             p.given.dirichlet.append((ids, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, float("inf")))
             p.given.seqs.append({"ids": ids, "folder": sh.mesh_seq, "ext": ext})  # (the very array of the Dirichlet row: assemble() finds the row by it)
-        _codim_keywords(cfg, sh, f"shape {s_index} ({os.path.basename(sh.path)})", V, SF, E, off, p)
+        _codim_keywords(cfg, sh, f"shape {s_index} ({os.path.basename(sh.path)})", V, T, SF, E, off, p)
         if is_codim:  # (an elastic shell or rod needs nobody to hold it: it counts as moved)
             elastic = sh.shell_thickness is not None or sh.rod_radius is not None
             p.codim.append((np.arange(off, off + V.shape[0], dtype=np.int32), SF + off,
@@ -902,8 +971,8 @@ def _per(records, value, dtype=np.float64):
 
 
 def _codim_payloads(p, attachments, V):
-    """-> (shell, rod, attachments, chambers) as AssembledScene holds them and apply() hands them on, None where no shape asks for one"""
-    shell = rod = chambers = None
+    """-> (shell, rod, attachments, chambers, aero) as AssembledScene holds them and apply() hands them on, None where no shape asks for one"""
+    shell = rod = chambers = aero = None
     if p.shells:
         if len({r[2] for r in p.shells}) > 1:
             raise ValueError("one bend scale per scene: the shell shapes give different ones")
@@ -930,7 +999,10 @@ def _codim_payloads(p, attachments, V):
         if any(q[3][0] for q in p.chambers):
             chambers.update(gas=np.array([q[3][0] for q in p.chambers], dtype=bool), ambient=np.array([q[3][1] for q in p.chambers], dtype=np.float64),
                             gamma=np.array([q[3][2] for q in p.chambers], dtype=np.float64))
-    return shell, rod, attachments, chambers
+    if p.aero:
+        aero = {"tri_lists": [q[0].astype(np.int32) for q in p.aero], "cn": np.array([q[1] for q in p.aero], dtype=np.float64),
+                "ct": np.array([q[2] for q in p.aero], dtype=np.float64), "one_sided": np.array([q[3] for q in p.aero], dtype=bool)}
+    return shell, rod, attachments, chambers, aero
 
 
 def assemble(cfg, read_mesh):
@@ -951,7 +1023,9 @@ def assemble(cfg, read_mesh):
                         codim_nodes, codim_mass, st.codim_fixed, model.V0)
     sc.motions, sc.mesh_i = st.motions, st.mesh_i
     sc.codim_edges = np.vstack(p.CEs).astype(np.int32) if p.CEs else np.zeros((0, 2), dtype=np.int32)
-    sc.shell, sc.rod, sc.attachments, sc.chambers = _codim_payloads(p, attachments, V)
+    sc.shell, sc.rod, sc.attachments, sc.chambers, aero = _codim_payloads(p, attachments, V)
+    if aero is not None:
+        sc.aero = aero
     for q in st.seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(st.dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = st.seqs
@@ -988,6 +1062,9 @@ def apply(sc, be):
         be.set_chambers(sc.chambers["tri_lists"], sc.chambers["pressure"])
         if "gas" in sc.chambers:
             be.chamber_set_gas(sc.chambers["gas"], sc.chambers["ambient"], sc.chambers["gamma"])
+    if sc.aero is not None:  # every `aero` shape in one call, behind set_shell, before opt_init and the pattern; then the scene's `wind` line
+        be.set_aero(sc.aero["tri_lists"], sc.aero["cn"], sc.aero["ct"], sc.aero["one_sided"])
+        be.aero_set_wind(cfg.wind, cfg.air_density)
     be.set_energy_type(cfg.energy)
     for s, sh in enumerate(cfg.shapes):
         # (a shell shape's `material` went into set_shell, which sets the masses of its nodes itself: the component call would scale them by rho / density

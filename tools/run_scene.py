@@ -38,7 +38,9 @@ if args.precond is not None:
     if cfg.linear_solver != lib.SOLVER_PCG:
         sys.exit("--precond needs a scene with `linearSolver AMGCL`")
     ctx.set_iterative(precond=args.precond)
-c = ss.apply(sc, ctx)
+c = ss.apply(sc, ctx)  # (the `aero` shapes and the `wind` line included: set_aero, aero_set_wind)
+if sc.aero is not None:
+    print(f"{len(sc.aero['tri_lists'])} aerodynamic surfaces, {sum(len(t) for t in sc.aero['tri_lists'])} triangles, wind {cfg.wind}, air density {cfg.air_density}")
 report = ss.ReportWriter(args.report) if args.report else None
 if report:
     report.write(c)

@@ -744,6 +744,41 @@ int ipcgpu_halfspace_hessian_add(ipcgpu_ctx*, int id, double dHat, double kappa,
  * stepSizeLeft = 1 - that fraction. */
 int ipcgpu_halfspace_move(ipcgpu_ctx*, int id, const double* delta3, double slackness, double* stepSizeLeft);
 int ipcgpu_halfspace_step_bound(ipcgpu_ctx*, int id, const double* searchDir_3nV, double slackness, double* stepSize_inout);
+
+/* ---- round colliders: analytic spheres and capsules beside the half-space (a project extension; model in ipc_amd/csrc/round_collider_kernels.h) ----
+ * A round collider is the segment [p0, p1] with radius R > 0: a sphere where p0 == p1 (exactly), a capsule otherwise.  hollow = 1 (spheres only):
+ * the bodies live inside, as in a bowl; it needs R^2 > dHat.  With q the closest point of the segment, r = |x - q|, the signed distance is
+ * s = side (r - R), side = +1 / -1 (solid / hollow); the barrier is kappa b(s^2, dHat) on the surface vertices with dbc == 0 and s^2 < dHat.  The
+ * Hessian touches only the diagonal 3 x 3 block of a node, so the matrix pattern never changes.  Needs ipcgpu_set_surface; shares the context's one
+ * dHatEps; refused with IPCGPU_ERR_UNSUPPORTED on a sharded context, and IPCGPU_ERR_STATE where a node with dbc == 0 lies on or inside the collider
+ * at the current positions (ipcgpu_opt_begin_timestep asks again).  Returns its index in *id (round colliders count separately from half-spaces).
+ * The stepper visits the round colliders right after the half-spaces: constraint set, barrier energy / gradient / Hessian, step bound with slackness
+ * 0.9, intersection check, kappa adaptation, lagged friction.  ipcgpu_opt_system_report is refused while one is set, and ipcgpu_contact_report does
+ * not list them: ipcgpu_round_state serves that purpose. */
+int ipcgpu_opt_add_round_collider(ipcgpu_ctx*, const double* p0_3, const double* p1_3, double R, int hollow, double dHatEps, int* id);
+/* the same pieces one by one, as the ipcgpu_halfspace_* list.  verts: the active set in ascending surface order. */
+int ipcgpu_round_build(ipcgpu_ctx*, int id, double dHat, int cap, int* verts, int* n);
+int ipcgpu_round_set(ipcgpu_ctx*, int id, int n, const int* verts);
+int ipcgpu_round_energy(ipcgpu_ctx*, int id, double dHat, double kappa, double* E);
+int ipcgpu_round_gradient_add(ipcgpu_ctx*, int id, double dHat, double kappa, double* grad_3nV_inout);
+int ipcgpu_round_hessian_add(ipcgpu_ctx*, int id, double dHat, double kappa, int projectDBC);
+/* the first t in (0, *stepSize_inout] at which some surface vertex with dbc == 0 has s(x + t p) = (1 - slackness) s(x); unchanged where no ray gets there */
+int ipcgpu_round_step_bound(ipcgpu_ctx*, int id, const double* searchDir_3nV, double slackness, double* stepSize_inout);
+/* translate the collider by the largest fraction <= 1 of delta that keeps `slackness` of every surface node's gap (Dirichlet nodes included);
+ * stepSizeLeft = 1 - that fraction, like ipcgpu_halfspace_move */
+int ipcgpu_round_move(ipcgpu_ctx*, int id, const double* delta3, double slackness, double* stepSizeLeft);
+int ipcgpu_round_get(ipcgpu_ctx*, int id, double* p0_3, double* p1_3, double* R, int* hollow); /* any pointer may be null */
+/* lagged friction piece by piece: lambda and the unit normal of every entry of the current set are stored (the lagged tangent plane); energy,
+ * gradient and Hessian are the half-space's with that per-entry normal, Vt = x^t (3 nV), eps2 = the squared velocity threshold times h^2 */
+int ipcgpu_round_lag_update(ipcgpu_ctx*, int id, double dHat, double kappa, int* nLagged);
+int ipcgpu_round_friction_energy(ipcgpu_ctx*, int id, const double* Vt, double eps2, double* E);
+int ipcgpu_round_friction_gradient_add(ipcgpu_ctx*, int id, const double* Vt, double eps2, double* grad_3nV_inout);
+int ipcgpu_round_friction_hessian_add(ipcgpu_ctx*, int id, const double* Vt, double eps2, int projectDBC);
+/* State of one collider at the current positions and set.  *nSet: the set size.  out10[0]: the smallest s over the surface nodes (Dirichlet nodes
+ * included; +infinity without a surface node); out10[1..3]: the total barrier force on the bodies (minus the barrier gradient over the set);
+ * out10[4..6]: its torque about p0; out10[7..9]: the total lagged friction force (zero while nothing is lagged), with x^t and the velocity threshold
+ * of the stepper.  dHat, kappa <= 0: the stepper's current values.  Summed in a fixed order: two calls on one state agree to the bit. */
+int ipcgpu_round_state(ipcgpu_ctx*, int id, double dHat, double kappa, int* nSet, double* out10);
 /* ---- lagged smoothed Coulomb friction (FrictionUtils.hpp, SelfCollisionHandler.cpp:2481-2988, HalfSpace.cpp:272-381)
  * `selfFric mu` / `fricIterAmt n` / eps_v = tuning[4] (Config.cpp:482-488, 550-551, 45).  Self friction needs self collision. */
 /* NOTE on eps_v: the smoothing distance the friction terms use is eps_v^2 * h^2 * (bounding-box diagonal)^2 with h = 0.025 -- the step size of the
@@ -776,6 +811,7 @@ int ipcgpu_opt_set_friction_scales(ipcgpu_ctx*, double scaleSelf, double scaleOb
  * then runs after every converged sub-problem.  on != 0 switches that loop on without any frictional pair. */
 int ipcgpu_opt_force_friction_loop(ipcgpu_ctx*, int on);
 int ipcgpu_opt_set_half_space_friction(ipcgpu_ctx*, int id, double mu); /* CollisionObject::friction of half-space `id` */
+int ipcgpu_opt_set_round_collider_friction(ipcgpu_ctx*, int id, double mu); /* the same for round collider `id` */
 /* Lagged stiffness-proportional damping: `dampingStiff s` (Config.cpp:141-147; `dampingRatio r` is s = r * dt^3 * 3 / 4, :148-157,
  * 614-616).  The damping matrix is the PSD-projected elastic Hessian at the end of the last time step times s / dt
  * (Optimizer.cpp:593-595, 3723-3735); 1/2 dx^T D dx joins the energy (:3381-3400), D dx the gradient (:3519-3540), D the Hessian

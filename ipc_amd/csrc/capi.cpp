@@ -2,6 +2,7 @@
 #include "../../include/ipcgpu.h"
 #include "hip_ipc.h"
 #include "msh_io.h"
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -272,6 +273,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->attach.n()) throw UnsupportedError("attachments on a sharded context");
         if (world > 1 && c->mesh->chamber.n()) throw UnsupportedError("chambers on a sharded context");
         if (world > 1 && c->mesh->aero.n()) throw UnsupportedError("aerodynamic surfaces on a sharded context");
+        if (world > 1 && !c->opt->rounds.empty()) throw UnsupportedError("round colliders on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -300,6 +302,7 @@ int ipcgpu_set_mesh(ipcgpu_ctx* c, int nV, int nT, const double* Vr, const int* 
         c->opt->selfCollision = false; // surface + contact state belong to the previous mesh
         c->opt->contact = nullptr;
         c->opt->planes.clear();
+        c->opt->rounds.clear();
         c->contact.reset();
         c->stress.reset(); // the incidence list belongs to the previous mesh
         return IPCGPU_OK;
@@ -2057,6 +2060,199 @@ int ipcgpu_halfspace_step_bound(ipcgpu_ctx* c, int id, const double* p, double s
         return IPCGPU_OK;
     });
 }
+// ---- round colliders (round_collider_kernels.h): the half-space's list, piece by piece, plus the state query ---------------------------------------
+int ipcgpu_opt_add_round_collider(ipcgpu_ctx* c, const double* p0, const double* p1, double R, int hollow, double dHatEps, int* id)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        need(o.initialised, "call ipcgpu_opt_init first");
+        needArg(p0 && p1 && dHatEps > 0, "bad round-collider argument");
+        const int k = o.addRoundCollider(&CT(c), p0, p1, R, hollow, dHatEps);
+        if (id) *id = k;
+        return IPCGPU_OK;
+    });
+}
+static HipRoundCollider& RC(ipcgpu_ctx* c, int id)
+{
+    HipOptimizer& o = O(c);
+    needArg(id >= 0 && id < (int)o.rounds.size(), "round-collider index out of range");
+    return *o.rounds[id];
+}
+int ipcgpu_round_build(ipcgpu_ctx* c, int id, double dHat, int cap, int* verts, int* n)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        const int cnt = h.build(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, dHat);
+        if (n) *n = cnt;
+        needArg(!verts || cap >= cnt, "verts buffer too small");
+        if (verts) std::memcpy(verts, h.set.data(), sizeof(int) * cnt);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_set(ipcgpu_ctx* c, int id, int n, const int* verts)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        needArg(n >= 0 && (verts || !n), "bad vertex list");
+        for (int i = 0; i < n; ++i) needArg(verts[i] >= 0 && verts[i] < c->mesh->nV, "vertex id out of range");
+        h.setSet(n, verts);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_energy(ipcgpu_ctx* c, int id, double dHat, double kappa, double* E)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        needArg(E != nullptr, "null result");
+        *E = h.energy(c->mesh->d_x.p, dHat, kappa);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_gradient_add(ipcgpu_ctx* c, int id, double dHat, double kappa, double* g)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(g != nullptr, "null gradient");
+        const size_t n3 = 3 * (size_t)c->mesh->nV;
+        HIP_CHECK(hipMemcpyAsync(o.d_gradient.p, g, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        h.gradientAdd(c->mesh->d_x.p, dHat, kappa, o.d_gradient.p);
+        o.d_gradient.download(g, n3, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_hessian_add(ipcgpu_ctx* c, int id, double dHat, double kappa, int projectDBC)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        need(c->lin->numRows == 3 * c->mesh->nV, "call ipcgpu_linsys_set_pattern first");
+        h.hessianAdd(c->mesh->d_x.p, c->mesh->d_dbc.p, c->lin->d_rowBase.p, c->lin->d_rowLen.p, dHat, kappa, projectDBC, c->lin->d_a.p);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_move(ipcgpu_ctx* c, int id, const double* delta3, double slackness, double* stepSizeLeft)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        needArg(delta3 && slackness > 0.0 && slackness <= 1.0, "bad round-collider move");
+        for (int k = 0; k < 3; ++k) needArg(std::isfinite(delta3[k]), "bad round-collider move");
+        const double left = h.move(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, delta3, slackness);
+        if (stepSizeLeft) *stepSizeLeft = left;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_step_bound(ipcgpu_ctx* c, int id, const double* p, double slackness, double* step)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(p && step && slackness > 0 && slackness <= 1, "bad step-bound argument");
+        HIP_CHECK(hipMemcpyAsync(o.d_searchDir.p, p, 3 * (size_t)c->mesh->nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        *step = h.stepBound(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, o.d_searchDir.p, slackness, *step);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_get(ipcgpu_ctx* c, int id, double* p0, double* p1, double* R, int* hollow)
+{
+    return guarded([&] {
+        const RoundShape& s = RC(c, id).shape;
+        for (int k = 0; k < 3; ++k) {
+            if (p0) p0[k] = s.p0[k];
+            if (p1) p1[k] = s.p1[k];
+        }
+        if (R) *R = s.R;
+        if (hollow) *hollow = s.side < 0.0 ? 1 : 0;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_opt_set_round_collider_friction(ipcgpu_ctx* c, int id, double mu)
+{
+    specChanged(c);
+    return guarded([&] {
+        needArg(mu >= 0.0, "negative friction coefficient");
+        RC(c, id).friction = mu;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_lag_update(ipcgpu_ctx* c, int id, double dHat, double kappa, int* nLagged)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        h.lagUpdate(c->mesh->d_x.p, dHat, kappa);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (nLagged) *nLagged = (int)h.lagSet.size();
+        return IPCGPU_OK;
+    });
+}
+// x^t of the friction pieces: the caller's Vt in d_x0, as ipcgpu_friction_energy takes it
+static const double* roundXt(ipcgpu_ctx* c, const double* Vt)
+{
+    HipOptimizer& o = O(c);
+    needArg(Vt != nullptr, "null Vt");
+    HIP_CHECK(hipMemcpyAsync(o.d_x0.p, Vt, 3 * (size_t)c->mesh->nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return o.d_x0.p;
+}
+int ipcgpu_round_friction_energy(ipcgpu_ctx* c, int id, const double* Vt, double eps2, double* E)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        needArg(E && eps2 > 0.0, "bad friction argument");
+        *E = h.frictionEnergy(c->mesh->d_x.p, roundXt(c, Vt), eps2);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_friction_gradient_add(ipcgpu_ctx* c, int id, const double* Vt, double eps2, double* g)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(g && eps2 > 0.0, "bad friction argument");
+        const size_t n3 = 3 * (size_t)c->mesh->nV;
+        const double* xt = roundXt(c, Vt);
+        HIP_CHECK(hipMemcpyAsync(o.d_gradient.p, g, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        h.frictionGradientAdd(c->mesh->d_x.p, xt, eps2, o.d_gradient.p);
+        o.d_gradient.download(g, n3, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_friction_hessian_add(ipcgpu_ctx* c, int id, const double* Vt, double eps2, int projectDBC)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        bind(c);
+        needArg(eps2 > 0.0, "bad friction argument");
+        need(c->lin->numRows == 3 * c->mesh->nV, "call ipcgpu_linsys_set_pattern first");
+        h.frictionHessianAdd(c->mesh->d_x.p, roundXt(c, Vt), c->mesh->d_dbc.p, c->lin->d_rowBase.p, c->lin->d_rowLen.p, eps2, projectDBC, c->lin->d_a.p);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_round_state(ipcgpu_ctx* c, int id, double dHat, double kappa, int* nSet, double* out10)
+{
+    return guarded([&] {
+        HipRoundCollider& h = RC(c, id);
+        HipOptimizer& o = O(c);
+        bind(c);
+        needArg(out10 != nullptr, "null result");
+        const int n = h.state(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, o.d_xPrev.p, dHat > 0.0 ? dHat : o.dHat, kappa > 0.0 ? kappa : o.kappa, o.fricDHat, out10);
+        if (nSet) *nSet = n;
+        return IPCGPU_OK;
+    });
+}
 int ipcgpu_opt_set_friction(ipcgpu_ctx* c, double selfFric, int fricIterAmt, double epsV)
 {
     specChanged(c);
@@ -2399,6 +2595,7 @@ int ipcgpu_opt_system_report(ipcgpu_ctx* c, double* sysE, double* sysM, double* 
         if (c->mesh->attach.n()) throw UnsupportedError("system report with attachments set (their energy belongs to no single component)");
         if (c->mesh->chamber.n()) throw UnsupportedError("system report with chambers set (the report's slices do not know the pressure energy)");
         if (c->mesh->aero.n()) throw UnsupportedError("system report with aerodynamic surfaces set (the report's slices do not know the dissipation of the air drag)");
+        if (!o.rounds.empty()) throw UnsupportedError("system report with a round collider set (the report's slices do not know its barrier and friction energy)");
         o.systemReport(sysE, sysM, sysL);
         return IPCGPU_OK;
     });

@@ -20,6 +20,7 @@
 #include "patch_assembly.h"
 #include "hip_contact.h"
 #include "hip_halfspace.h"
+#include "round_collider_kernels.h"
 #include "pcg.h"
 #include "pcg_coarse.h"
 #include "report_plan.h"
@@ -588,7 +589,9 @@ public:
     double lookahead() const { return patternPad >= 0.0 ? patternPad : (mesh.nV > 150000 ? 2.25 : 4.0); }
     // analytic half-space obstacles (animConfig.collisionObjects) and their close-constraint list (Optimizer.cpp:2364-2374)
     std::vector<std::unique_ptr<HipHalfSpace>> planes;
-    std::vector<std::pair<int, int>> closeHS;
+    // analytic round colliders (spheres, capsules: round_collider_kernels.h), visited right after the planes wherever those are walked
+    std::vector<std::unique_ptr<HipRoundCollider>> rounds;
+    std::vector<std::pair<int, int>> closeHS; // (object, vertex): objects count through the planes, then the rounds
     std::vector<double> closeHSVal;
     // lagged friction: Optimizer.cpp:286-304, 1525-1600, 1615-1790; the lagged sets live in HipContact /
     // HipHalfSpace, x^t is d_xPrev
@@ -601,9 +604,11 @@ public:
     bool solveFric() const;
     void updateFrictionLag();
     bool nextSubproblem(); // tail of the fullyImplicit_IP loop body after a converged solveSub_IP; true = run another one
-    bool ipOn() const { return selfCollision || !planes.empty(); }
+    bool ipOn() const { return selfCollision || !planes.empty() || !rounds.empty(); }
     size_t nConstraints() const;
     int addHalfSpace(HipContact* c, const double* origin3, const double* normal3, double dHatEps);
+    int addRoundCollider(HipContact* c, const double* p0, const double* p1, double R, int hollow, double dHatEps);
+    void requireRoundsFeasible(); // throws where dHat has outgrown a hollow sphere, or a node with dbc == 0 lies on or inside a collider
     bool anyIntersection();
     void elasticInertiaGradient(bool projectDBC, bool finish = true); // finish = false: owner-computes callers that exchange the sum themselves
     void barrierGradientAdd(bool projectDBC, double kappa, bool activeOnly, double* grad_dev, int part = 0);

@@ -609,9 +609,12 @@ double HipOptimizer::computeEnergyVal()
     if (!nbcGroups.empty()) E += neumannEnergy();
     // barrier terms over the current constraint sets (Optimizer.cpp:3252-3353); replicated on every rank
     for (auto& h : planes) E += h->energy(mesh.d_x.p, dHat, kappa);
+    for (auto& h : rounds) E += h->energy(mesh.d_x.p, dHat, kappa);
     if (selfCollision) E += Econtact;
     if (fricDHat > 0.0) { // lagged friction (Optimizer.cpp:3357-3377)
         for (auto& h : planes)
+            if (h->friction > 0.0) E += h->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat);
+        for (auto& h : rounds)
             if (h->friction > 0.0) E += h->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat);
         if (selfCollision && selfFric > 0.0) E += contact->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, d_partial, slot(S_FRICTION_E));
     }
@@ -691,6 +694,8 @@ bool HipOptimizer::solveFric() const
     if (selfCollision && selfFric > 0.0) return true;
     for (const auto& h : planes)
         if (h->friction > 0.0) return true;
+    for (const auto& h : rounds)
+        if (h->friction > 0.0) return true;
     return false;
 }
 
@@ -699,6 +704,8 @@ void HipOptimizer::updateFrictionLag()
     // multipliers, closest points and tangent bases of the current constraint sets (Optimizer.cpp:1553-1600 / 1620-1675)
     if (!solveFric()) return;
     for (auto& h : planes)
+        if (h->friction > 0.0) h->lagUpdate(mesh.d_x.p, dHat, kappa);
+    for (auto& h : rounds)
         if (h->friction > 0.0) h->lagUpdate(mesh.d_x.p, dHat, kappa);
     if (selfCollision && selfFric > 0.0) contact->frictionLagUpdate(mesh.d_x.p, dHat, kappa);
 }
@@ -719,6 +726,13 @@ bool HipOptimizer::nextSubproblem()
         double dMax = 0.0, dMin = 1.0e300;
         std::vector<double> d;
         for (auto& h : planes) {
+            h->evalDist2(h->set, mesh.d_x.p, d);
+            for (size_t i = 0; i < h->set.size(); ++i) {
+                dMax = std::max(dMax, d[i]);
+                dMin = std::min(dMin, d[i]);
+            }
+        }
+        for (auto& h : rounds) {
             h->evalDist2(h->set, mesh.d_x.p, d);
             for (size_t i = 0; i < h->set.size(); ++i) {
                 dMax = std::max(dMax, d[i]);
@@ -765,6 +779,7 @@ size_t HipOptimizer::nConstraints() const
 {
     size_t n = selfCollision ? (size_t)contact->nActive() : 0;
     for (const auto& h : planes) n += h->set.size();
+    for (const auto& h : rounds) n += h->set.size();
     return n;
 }
 
@@ -774,7 +789,7 @@ int HipOptimizer::addHalfSpace(HipContact* c, const double* origin3, const doubl
     if (!c || !c->surfaceSet) throw StateError("opt_add_half_space before set_surface");
     // one dHat for the whole interior-point problem, as in the reference (a single `dHat` script keyword, Config.cpp:41-45):
     // a second object registered with another value would silently change the first one's activation distance
-    if ((selfCollision || !planes.empty()) && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
+    if (ipOn() && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
     contact = c;
     planes.emplace_back(new HipHalfSpace(stream, origin3, normal3));
     dHatEps = eps;
@@ -783,10 +798,40 @@ int HipOptimizer::addHalfSpace(HipContact* c, const double* origin3, const doubl
     return (int)planes.size() - 1;
 }
 
+int HipOptimizer::addRoundCollider(HipContact* c, const double* p0, const double* p1, double R, int hollow, double eps)
+{
+    // sphere / capsule obstacle (round_collider_kernels.h): registered like a half-space, one dHat for the whole context
+    if (!c || !c->surfaceSet) throw StateError("opt_add_round_collider before set_surface");
+    if (worldSize > 1) throw UnsupportedError("round colliders on a sharded context");
+    if (ipOn() && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
+    RoundShape shape;
+    std::string err;
+    if (!planRoundCollider(p0, p1, R, hollow, eps * eps * lenScale2(), shape, err)) throw ArgError(err);
+    std::unique_ptr<HipRoundCollider> h(new HipRoundCollider(stream, shape));
+    if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) throw StateError("round collider: a node lies on or inside the collider at the current positions (an intersecting start state)");
+    contact = c;
+    rounds.push_back(std::move(h));
+    dHatEps = eps;
+    dHat = eps * eps * lenScale2();
+    dTol = dTolRel * dTolRel * lenScale2();
+    return (int)rounds.size() - 1;
+}
+
+void HipOptimizer::requireRoundsFeasible()
+{
+    std::string err;
+    for (auto& h : rounds) {
+        if (!checkRoundColliderDHat(h->shape, dHatEps * dHatEps * lenScale2(), err)) throw ArgError(err);
+        if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) throw StateError("round collider: a node lies on or inside the collider at the current positions (an intersecting start state)");
+    }
+}
+
 bool HipOptimizer::anyIntersection()
 {
     // isIntersected (Optimizer.cpp:2626-2659): analytic objects first, then the mesh against itself
     for (auto& h : planes)
+        if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) return true;
+    for (auto& h : rounds)
         if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) return true;
     return selfCollision && isIntersected();
 }
@@ -796,7 +841,7 @@ void HipOptimizer::enableSelfCollision(HipContact* c, double eps)
 {
     // `selfCollisionOn` + interior point; dHat = dHatEps^2 * bbox diagonal^2 (Optimizer.cpp:1534-1537, Config.cpp:41-45)
     if (!c || !c->surfaceSet) throw StateError("opt_enable_self_collision before set_surface");
-    if (!planes.empty() && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
+    if ((!planes.empty() || !rounds.empty()) && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
     contact = c;
     selfCollision = true;
     dHatEps = eps;
@@ -938,6 +983,7 @@ void HipOptimizer::computeConstraintSets()
     if (!ipOn()) return;
     Tic t(timers[14], stream);
     for (auto& h : planes) h->build(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, dHat); // Optimizer.cpp:2460-2462
+    for (auto& h : rounds) h->build(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, dHat);
     if (selfCollision) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, dHat); // Optimizer.cpp:2448-2470
 }
 
@@ -999,6 +1045,18 @@ void HipOptimizer::postLineSearch()
         for (size_t i = 0; i < verts.size(); ++i)
             if (d[i] <= was[i]) updateKappa = true;
     }
+    for (size_t ri = 0; ri < rounds.size() && !updateKappa; ++ri) {
+        std::vector<int> verts;
+        std::vector<double> was;
+        for (size_t i = 0; i < closeHS.size(); ++i)
+            if (closeHS[i].first == (int)(planes.size() + ri)) {
+                verts.push_back(closeHS[i].second);
+                was.push_back(closeHSVal[i]);
+            }
+        rounds[ri]->evalDist2(verts, mesh.d_x.p, d);
+        for (size_t i = 0; i < verts.size(); ++i)
+            if (d[i] <= was[i]) updateKappa = true;
+    }
     if (!updateKappa && selfCollision) {
         contact->evalStencils(closeID, mesh.d_x.p, d);
         for (size_t i = 0; i < closeID.size(); ++i)
@@ -1021,6 +1079,14 @@ void HipOptimizer::postLineSearch()
         for (size_t i = 0; i < planes[pi]->set.size(); ++i)
             if (d[i] < dTol) {
                 closeHS.push_back({ (int)pi, planes[pi]->set[i] });
+                closeHSVal.push_back(d[i]);
+            }
+    }
+    for (size_t ri = 0; ri < rounds.size(); ++ri) {
+        rounds[ri]->evalDist2(rounds[ri]->set, mesh.d_x.p, d);
+        for (size_t i = 0; i < rounds[ri]->set.size(); ++i)
+            if (d[i] < dTol) {
+                closeHS.push_back({ (int)(planes.size() + ri), rounds[ri]->set[i] });
                 closeHSVal.push_back(d[i]);
             }
     }
@@ -1110,8 +1176,11 @@ void HipOptimizer::barrierGradientAdd(bool projectDBC, double kappa_, bool activ
         return;
     }
     for (auto& h : planes) h->gradientAdd(mesh.d_x.p, dHat, kappa_, grad_dev);
+    for (auto& h : rounds) h->gradientAdd(mesh.d_x.p, dHat, kappa_, grad_dev);
     if (!activeOnly && fricDHat > 0.0) { // Optimizer.cpp:3474-3478, 3504-3506
         for (auto& h : planes)
+            if (h->friction > 0.0) h->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, grad_dev);
+        for (auto& h : rounds)
             if (h->friction > 0.0) h->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, grad_dev);
         if (selfCollision && selfFric > 0.0) contact->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, grad_dev);
     }
@@ -1349,10 +1418,15 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
         // (half-spaces and lagged friction: vertex-wise diagonal blocks / one set, evaluated alike on every rank and added to the rows each rank holds)
         for (auto& h : planes)
             h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
+        for (auto& h : rounds)
+            h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
         if (selfCollision) // owner-computes: the stencils that touch a row this rank needs
             contact->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin, dHat, kappa, projectDBC, lin.d_a.p, owner ? d_need.p : nullptr, /*deferCheck=*/true);
         if (fricDHat > 0.0) { // Optimizer.cpp:3677-3702
             for (auto& h : planes)
+                if (h->friction > 0.0)
+                    h->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, fricDHat, projectDBC, lin.d_a.p);
+            for (auto& h : rounds)
                 if (h->friction > 0.0)
                     h->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, fricDHat, projectDBC, lin.d_a.p);
             if (selfCollision && selfFric > 0.0)
@@ -1738,13 +1812,14 @@ void HipOptimizer::beginTimestep()
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.
     // (a strain limit or a rubber membrane takes the general sequence: its scripted step is shortened by stepFeasible)
-    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && !(warmStart >= 1 && warmStart <= 5)
+    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && rounds.empty() && !(warmStart >= 1 && warmStart <= 5)
         && !mesh.shell.nLimited() && !mesh.shell.nRubber();
     // With a strain limit the stepper never accepts a state with a stretch at or over it, so a time step may only start from a feasible one.  The energy the
     // stepper holds on the host tells: it is +infinity exactly then (or at the fold of a rod node, which the count below tells apart) -- no device query on
     // the usual path.  Positions or a limit set from outside since then are asked for once.  Nothing has been changed yet when this throws.
     if (mesh.shell.nLimited() && (mesh.shell.limitUnchecked || !(lastEnergyVal < INFINITY))) requireShellLimitFeasible();
     if (mesh.shell.nRubber() && (mesh.shell.rubberUnchecked || !(lastEnergyVal < INFINITY))) requireShellRubberFeasible(); // the same for a degenerate rubber triangle
+    if (!rounds.empty()) requireRoundsFeasible(); // a start state on or inside a round collider is refused; nothing has been changed yet
     if (batched) {
         const bool guard = mesh.needElemInvSafeGuard(); // Optimizer.cpp:252, 517: only under getNeedElemInvSafeGuard()
         d_flag.zero(stream);
@@ -1821,6 +1896,7 @@ void HipOptimizer::beginTimestep()
         double stepSize = filterStepSize(d_searchDir.p, 1.0);
         if (ipOn()) {
             for (auto& h : planes) stepSize = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, stepSize);
+            for (auto& h : rounds) stepSize = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, stepSize);
             if (selfCollision) stepSize = fullCcd(0.8, stepSize);
         }
         HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, 3 * (size_t)mesh.nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -1841,6 +1917,7 @@ void HipOptimizer::beginTimestep()
         // friction: lagged sets reset, eps_v^2 h^2 (Optimizer.cpp:1525-1533, 286-304), then lagged at x^n (:1553-1600)
         if (contact) contact->frictionLagClear();
         for (auto& h : planes) h->lagClear();
+        for (auto& h : rounds) h->lagClear();
         fricDHat0 = epsV * epsV * (ctorDt * ctorDt) * lenScale2(); // Optimizer.cpp:290-303: set once in the constructor, see (ctorDt * ctorDt)
         fricDHatTarget = epsVTarget > 0.0 ? epsVTarget * epsVTarget * (ctorDt * ctorDt) * lenScale2() : fricDHat0;
         fricDHat = solveFric() ? fricDHat0 : -1.0;
@@ -1985,7 +2062,7 @@ bool HipOptimizer::newtonIter()
         Tic t(timers[13], stream);
         t.nosync = specAsmValid && cachedTrialValid; // nothing is enqueued in here on that path, and the stream carries the assembly enqueued ahead
         // (one process, self-contact, no half-spaces between the filter and the CCD: the three bounds come back with one synchronisation, HipContact::stepBounds)
-        const bool batchedBounds = !cachedTrialValid && !cachedE0Valid && selfCollision && planes.empty() && worldSize == 1;
+        const bool batchedBounds = !cachedTrialValid && !cachedE0Valid && selfCollision && planes.empty() && rounds.empty() && worldSize == 1;
         if (cachedTrialValid) alpha = cachedAlpha; // decided on the device by the same rule, the trial step is already taken with it
         else if (cachedE0Valid) { // Optimizer.cpp:1887 with the value the solve's batch brought back
             if (mesh.needElemInvSafeGuard() && cachedFilter > 0.0 && cachedFilter < alpha) alpha = cachedFilter;
@@ -1993,6 +2070,8 @@ bool HipOptimizer::newtonIter()
         else if (!batchedBounds)
         alpha = filterStepSize(d_searchDir.p, alpha); // Optimizer.cpp:1887
         for (auto& h : planes) // slackness_a = 0.9 (:1886-1890)
+            alpha = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, alpha);
+        for (auto& h : rounds)
             alpha = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, alpha);
         if (selfCollision) {
             // step-size pipeline of Optimizer.cpp:1884-2040: partial CCD over the candidates of the current

@@ -1172,6 +1172,88 @@ class Context:
         self._chk(self._L.ipcgpu_halfspace_step_bound(self.h, C.c_int(idx), _dp(p), C.c_double(slackness), C.byref(s)))
         return s.value
 
+    # ---- round colliders (spheres, capsules; ipc_amd/csrc/round_collider_kernels.h) ----
+    def add_round_collider(self, p0, p1, R, hollow=False, dHatEps=1e-3):
+        """segment [p0, p1] with radius R: a sphere where p0 == p1, a capsule otherwise; hollow: the bodies live inside (spheres only)"""
+        a, b = _f64(np.asarray(p0, dtype=np.float64).reshape(3)), _f64(np.asarray(p1, dtype=np.float64).reshape(3))
+        idx = C.c_int()
+        self._chk(self._L.ipcgpu_opt_add_round_collider(self.h, _dp(a), _dp(b), C.c_double(R), C.c_int(int(hollow)), C.c_double(dHatEps), C.byref(idx)))
+        return idx.value
+
+    def add_sphere_collider(self, centre, R, hollow=False, dHatEps=1e-3):
+        return self.add_round_collider(centre, centre, R, hollow, dHatEps)
+
+    def round_build(self, idx, dHat):
+        verts = np.zeros(self.nV, dtype=np.int32)
+        n = C.c_int()
+        self._chk(self._L.ipcgpu_round_build(self.h, C.c_int(idx), C.c_double(dHat), C.c_int(self.nV), _ip(verts), C.byref(n)))
+        return verts[:n.value].copy()
+
+    def round_set(self, idx, verts):
+        verts = _i32(verts)
+        self._chk(self._L.ipcgpu_round_set(self.h, C.c_int(idx), C.c_int(len(verts)), _ip(verts)))
+
+    def round_energy(self, idx, dHat, kappa):
+        E = C.c_double()
+        self._chk(self._L.ipcgpu_round_energy(self.h, C.c_int(idx), C.c_double(dHat), C.c_double(kappa), C.byref(E)))
+        return E.value
+
+    def round_gradient_add(self, idx, dHat, kappa, grad=None):
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(self._L.ipcgpu_round_gradient_add(self.h, C.c_int(idx), C.c_double(dHat), C.c_double(kappa), _dp(g)))
+        return g
+
+    def round_hessian_add(self, idx, dHat, kappa, projectDBC=True):
+        self._chk(self._L.ipcgpu_round_hessian_add(self.h, C.c_int(idx), C.c_double(dHat), C.c_double(kappa), C.c_int(int(projectDBC))))
+
+    def round_step_bound(self, idx, p, slackness=0.9, step=1.0):
+        p = _f64(np.asarray(p).reshape(-1))
+        s = C.c_double(step)
+        self._chk(self._L.ipcgpu_round_step_bound(self.h, C.c_int(idx), _dp(p), C.c_double(slackness), C.byref(s)))
+        return s.value
+
+    def round_move(self, idx, delta, slackness=0.5):
+        """translate round collider `idx` by (the feasible fraction of) delta; returns the fraction left"""
+        d = _f64(np.asarray(delta, dtype=np.float64).reshape(3))
+        left = C.c_double()
+        self._chk(self._L.ipcgpu_round_move(self.h, C.c_int(idx), _dp(d), C.c_double(slackness), C.byref(left)))
+        return left.value
+
+    def round_get(self, idx):
+        p0, p1, R, hollow = np.zeros(3), np.zeros(3), C.c_double(), C.c_int()
+        self._chk(self._L.ipcgpu_round_get(self.h, C.c_int(idx), _dp(p0), _dp(p1), C.byref(R), C.byref(hollow)))
+        return dict(p0=p0, p1=p1, R=R.value, hollow=bool(hollow.value))
+
+    def set_round_collider_friction(self, idx, mu):
+        self._chk(self._L.ipcgpu_opt_set_round_collider_friction(self.h, C.c_int(idx), C.c_double(mu)))
+
+    def round_lag_update(self, idx, dHat, kappa):
+        n = C.c_int()
+        self._chk(self._L.ipcgpu_round_lag_update(self.h, C.c_int(idx), C.c_double(dHat), C.c_double(kappa), C.byref(n)))
+        return n.value
+
+    def round_friction_energy(self, idx, Vt, eps2):
+        Vt = _f64(np.asarray(Vt).reshape(-1))
+        E = C.c_double()
+        self._chk(self._L.ipcgpu_round_friction_energy(self.h, C.c_int(idx), _dp(Vt), C.c_double(eps2), C.byref(E)))
+        return E.value
+
+    def round_friction_gradient_add(self, idx, Vt, eps2, grad=None):
+        Vt = _f64(np.asarray(Vt).reshape(-1))
+        g = np.zeros(3 * self.nV) if grad is None else _f64(grad).copy()
+        self._chk(self._L.ipcgpu_round_friction_gradient_add(self.h, C.c_int(idx), _dp(Vt), C.c_double(eps2), _dp(g)))
+        return g
+
+    def round_friction_hessian_add(self, idx, Vt, eps2, projectDBC=True):
+        Vt = _f64(np.asarray(Vt).reshape(-1))
+        self._chk(self._L.ipcgpu_round_friction_hessian_add(self.h, C.c_int(idx), _dp(Vt), C.c_double(eps2), C.c_int(int(projectDBC))))
+
+    def round_state(self, idx, dHat=0.0, kappa=0.0):
+        """set size, smallest signed distance over the surface nodes, total barrier force on the bodies, its torque about p0, total lagged friction force"""
+        n, out = C.c_int(), np.zeros(10)
+        self._chk(self._L.ipcgpu_round_state(self.h, C.c_int(idx), C.c_double(dHat), C.c_double(kappa), C.byref(n), _dp(out)))
+        return dict(n=n.value, min_s=float(out[0]), force=out[1:4].copy(), torque=out[4:7].copy(), friction=out[7:10].copy())
+
     def set_friction_target(self, eps_v_target):
         """eps_v homotopy target (`tuning`'s sixth entry); <= 0: the same as eps_v"""
         self._chk(self._L.ipcgpu_opt_set_friction_target(self.h, C.c_double(eps_v_target)))

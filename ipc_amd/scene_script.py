@@ -94,6 +94,55 @@ class Shape:
     pressure_gamma: float = 1.0
 
 
+def _parse_round_collider(k, a):
+    """sphereCollider cx cy cz R [hollow] [friction mu] [velocity vx vy vz]  /  capsuleCollider ax ay az bx by bz R [friction mu] [velocity vx vy vz]
+    -> {p0, p1, R, hollow, friction, velocity (None: at rest)}"""
+    sphere = k == "sphereCollider"
+    usage = (k + " needs <cx> <cy> <cz> <R> [hollow] [friction <mu>] [velocity <vx> <vy> <vz>]") if sphere else (
+        k + " needs <ax> <ay> <az> <bx> <by> <bz> <R> [friction <mu>] [velocity <vx> <vy> <vz>]")
+    nNum = 4 if sphere else 7
+    try:
+        v = [float(x) for x in a[:nNum]]
+    except ValueError:
+        raise ValueError(usage) from None
+    if len(v) < nNum:
+        raise ValueError(usage)
+    out = {"p0": np.array(v[0:3]), "p1": np.array(v[0:3] if sphere else v[3:6]), "R": v[nNum - 1], "hollow": False, "friction": 0.0, "velocity": None}
+    j, seen = nNum, set()
+    while j < len(a):
+        word = a[j]
+        if word in seen:
+            raise ValueError(f"{k}: {word} is given twice")
+        seen.add(word)
+        try:
+            if word == "hollow" and sphere:
+                out["hollow"] = True
+                j += 1
+            elif word == "friction" and j + 1 < len(a):
+                out["friction"] = float(a[j + 1])
+                j += 2
+            elif word == "velocity" and j + 3 < len(a):
+                out["velocity"] = np.array([float(x) for x in a[j + 1:j + 4]])
+                j += 4
+            elif word == "hollow":
+                raise ValueError(f"{k}: only a sphere may be hollow")
+            else:
+                raise ValueError(usage)
+        except ValueError as e:
+            raise ValueError(str(e) if str(e).startswith(k) else usage) from None
+    if not all(math.isfinite(x) for x in v):
+        raise ValueError(f"{k}: the coordinates and the radius must be finite")
+    if not out["R"] > 0.0:
+        raise ValueError(f"{k}: the radius must be positive")
+    if not sphere and np.array_equal(out["p0"], out["p1"]):
+        raise ValueError(f"{k}: the two end points coincide (that is a sphereCollider)")
+    if not (math.isfinite(out["friction"]) and out["friction"] >= 0.0):
+        raise ValueError(f"{k}: the friction coefficient must be finite and not negative")
+    if out["velocity"] is not None and not np.all(np.isfinite(out["velocity"])):
+        raise ValueError(f"{k}: the velocity must be finite")
+    return out
+
+
 @dataclass
 class SceneConfig:
     energy: str = "NH"
@@ -133,6 +182,7 @@ class SceneConfig:
     warm_start: int = 0  # initX option
     restart: str = None
     half_spaces: list = field(default_factory=list)  # (origin, normal, friction)
+    round_colliders = ()  # `sphereCollider` / `capsuleCollider` lines, see _parse_round_collider (a plain attribute, not a field: a scene without them has the fields it had)
     mesh_cos: list = field(default_factory=list)  # (obj path, origin, scale, friction, rotate_deg) -- kinematic mesh obstacles (MeshCO)
     shapes: list = field(default_factory=list)
     # contact groups (this project's keywords, not the reference's): `contactIgnore g h` -- groups g and h form no contact pair --, `contactFric g h mu` -- the
@@ -404,6 +454,10 @@ class SceneConfig:
                     cfg.air_density = float(a[4])
                 if not all(math.isfinite(v) for v in cfg.wind) or not (0.0 < cfg.air_density < math.inf):
                     raise ValueError("wind: the velocity must be finite and the density positive and finite")
+            elif k in ("sphereCollider", "capsuleCollider"):  # this project's keywords: analytic round colliders (round_collider_kernels.h)
+                if cfg.round_colliders == ():
+                    cfg.round_colliders = []
+                cfg.round_colliders.append(_parse_round_collider(k, a))
             elif k in VIEWER_KEYWORDS:
                 pass  # viewer / logging only
             elif k in ("resolution", "inexactSolve"):
@@ -694,6 +748,21 @@ class AssembledScene:
     # one_sided (per surface)}, or None.  Set by assemble(); a plain attribute, not a field, so that the fields of a scene without the keyword are what
     # they were.  The wind itself is the scene's (cfg.wind, cfg.air_density)
     aero = None
+
+    def move_round_colliders(self, be):
+        """Before a time step: every `sphereCollider` / `capsuleCollider` with a `velocity` moves by v dt through Context.round_move; the fraction a
+        move leaves over is carried into the next step's, as the half-space scripts do.  Returns the fractions left (one per moving collider)."""
+        if not hasattr(self, "_round_carry"):
+            self._round_carry = {}
+        left = []
+        for idx, rc in enumerate(self.cfg.round_colliders):
+            if rc["velocity"] is None:
+                continue
+            delta = np.asarray(rc["velocity"], dtype=np.float64) * self.cfg.dt + self._round_carry.get(idx, 0.0)
+            f = be.round_move(idx, delta, 0.5)
+            self._round_carry[idx] = f * delta
+            left.append(f)
+        return left
 
     def chamber_pressures(self, t):
         """the pressures of the chambers for the time step that ends at time t: p min(1, t / ramp) where a shape gives `ramp`, p elsewhere; None when no
@@ -1104,7 +1173,11 @@ def apply(sc, be):
         idx = be.add_half_space(origin, normal, cfg.dHat_eps)
         if mu > 0:
             be.set_half_space_friction(idx, mu)
-    plane_fric = any(mu > 0 for *_, mu in cfg.half_spaces)
+    for rc in cfg.round_colliders:  # analytic spheres and capsules, right after the planes
+        idx = be.add_round_collider(rc["p0"], rc["p1"], rc["R"], rc["hollow"], cfg.dHat_eps)
+        if rc["friction"] > 0:
+            be.set_round_collider_friction(idx, rc["friction"])
+    plane_fric = any(mu > 0 for *_, mu in cfg.half_spaces) or any(rc["friction"] > 0 for rc in cfg.round_colliders)
     # Optimizer.cpp:146-166: solveFric is true as soon as ANY collision object -- a mesh collision object included -- or selfFric carries a
     # coefficient: the lagging loop with its tangent-space convergence solve then runs even when no pair carries friction
     loop_only = any(mc[3] > 0 for mc in cfg.mesh_cos) and not (self_fric > 0 or plane_fric)

@@ -55,6 +55,7 @@ steps = args.steps if args.steps is not None else int(round(cfg.duration / cfg.d
 timestep = c.state()["timestep"] if fields else 0  # not 0 after `restart`
 for step in range(steps):
     t0 = time.time()
+    sc.move_round_colliders(c)  # `sphereCollider` / `capsuleCollider` with a `velocity`: v dt plus what the last move left over
     sc.before_step(c, step * cfg.dt)  # state-dependent script decisions (AnimScripter::stepAnimScript)
     ramped = sc.chamber_pressures((step + 1) * cfg.dt)  # `pressure <p> ramp <seconds>`: p min(1, t / ramp) at the time this step ends; None without a ramp
     if ramped is not None:
@@ -66,6 +67,9 @@ for step in range(steps):
     timestep = st["timestep"]
     cs = c.contact_state() if cfg.self_collision or cfg.half_spaces else {}
     print(f"step {st['timestep']:5d}  {it:4d} Newton iterations  {1e3 * (time.time() - t0):8.1f} ms  E = {st['E']:.6e}  active = {cs.get('nActive', 0)}", flush=True)
+    for k in range(len(cfg.round_colliders)):
+        rs = c.round_state(k)
+        print(f"            round collider {k}: {rs['n']} active, min s = {rs['min_s']:.3e}, force on the bodies {rs['force'] / cfg.dt ** 2}", flush=True)
     if report:
         report.write(c)
     if contact_report:  # (before the fields writer, which rebuilds the constraint set)

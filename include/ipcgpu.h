@@ -106,7 +106,8 @@ int ipcgpu_set_positions(ipcgpu_ctx*, const double* V_colmajor);
 int ipcgpu_get_positions(ipcgpu_ctx*, double* V_colmajor);
 /* Optimizer::xTilta (Optimizer.cpp:1236-1257) */
 int ipcgpu_set_xtilde(ipcgpu_ctx*, const double* xTilta_colmajor);
-/* read back derived per-element / per-node data (any pointer may be NULL) */
+/* read back derived per-element / per-node data (any pointer may be NULL).  restTriInv is the CURRENT one: once ipcgpu_set_plasticity was called it is
+ * downloaded from the device, where the plastic flow rewrites it. */
 int ipcgpu_get_features(ipcgpu_ctx*, double* restTriInv_9nT, double* triArea_nT, double* mass_nV,
     double* mu_nT, double* lambda_nT);
 /* nV = nT = 0 until ipcgpu_set_mesh was called */
@@ -115,7 +116,8 @@ int ipcgpu_get_mesh_dims(ipcgpu_ctx*, int* nV, int* nT);
    (Mesh.hpp:163, one 3x3 per tet, column-major inside the 9), triArea (:151), the diagonal of massMatrix (:148, lumped),
    u / lambda (:150, per tet).  Any pointer may be NULL (that array keeps what ipcgpu_set_mesh computed).  Call after
    ipcgpu_set_mesh; lets per-element state the reference modified after construction (component materials, rescaled
-   masses) reach the device unchanged. */
+   masses) reach the device unchanged.  A restTriInv argument resets the plastic history (ipcgpu_set_plasticity): it becomes
+   both the current rest shape and the one ipcgpu_plastic_reset restores, and the accumulated plastic strain is zero again. */
 int ipcgpu_set_mesh_features(ipcgpu_ctx*, const double* restTriInv_9nT, const double* triArea_nT, const double* mass_nV,
     const double* mu_nT, const double* lambda_nT);
 /* Mesh::checkInversion (Mesh.cpp:715-764): *ok = 1 when no element has det < 0 */
@@ -630,6 +632,34 @@ int ipcgpu_aero_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_aero_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_aero_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_aero_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+/* ---- Plastic flow of tetrahedral elements: yield, creep, isotropic hardening.  No counterpart in the reference (every body of it is elastic).
+ * The model is stated in ipc_amd/csrc/plastic_kernels.h.  Per element with a finite yield strain, at the end of every time step (after the BE / Newmark
+ * update, before the lagged damping matrix): F = Ds(x) restTriInv = U diag(s) V^T; skipped and counted where s2 <= 0; e = ln s, d = e - mean(e), n = |d|;
+ * y = yield + harden alpha; where n > y: Delta = -expm1(-creep dt) (n - y) / (1 + harden), restTriInv <- restTriInv V diag(exp(-Delta d_i / n)) V^T,
+ * alpha += Delta.  Isochoric (volumes and masses do not change).  For small strains the von Mises stress of ipcgpu_elastic_stress is sqrt(6) mu n, so a yield
+ * stress sigma_y corresponds to yield = sigma_y / (sqrt(6) mu).
+ * ipcgpu_set_plasticity (no counterpart in the reference): elements [tetBegin, tetEnd) get (yield, creep, harden); ranges as in ipcgpu_set_component_material,
+ *   later calls overwrite.  yield >= 0 or +inf (+inf switches the range off), creep > 0 or +inf (+inf: the rate-independent return onto the yield
+ *   surface), harden >= 0 and finite, nothing NaN: IPCGPU_ERR_ARG otherwise, and nothing is changed.  Touches neither the pattern nor the masses: allowed any
+ *   time after ipcgpu_set_mesh, before or after ipcgpu_opt_init, between time steps.  The first call keeps a copy A0 of the current restTriInv.  With no
+ *   element switched on the stepper launches nothing and every result is bit-identical to a context that never called this.  IPCGPU_ERR_UNSUPPORTED on a
+ *   sharded context; ipcgpu_ctx_set_shard with world > 1 on a context with plastic elements returns the same.
+ * ipcgpu_plastic_get (no counterpart): the parameters, the accumulated plastic strain alpha and A0 (layout of ipcgpu_get_features); any pointer may be NULL.
+ * ipcgpu_plastic_update (no counterpart): ONE flow at the held positions with the given dt, outside the stepper -- the kernel's test entry, like the
+ *   *_hessian_add calls.  nYielded / nSkipped (nullable): elements rewritten / found flat or inverted.
+ * ipcgpu_plastic_state (no counterpart): read-only.  perElem (nullable, column-major nT x 3): n, the current y, alpha; n = NaN for an element the flow would
+ *   skip, y = +inf where plasticity is off.  totals4 (nullable): yielded and skipped in the last flow, max alpha, sum of rest volume times alpha.
+ *   Deterministic: fixed summation order, no floating-point atomics.
+ * ipcgpu_plastic_set_state (no counterpart): restTriInv (layout of ipcgpu_get_features) and / or alpha from the caller (either may be NULL); needs
+ *   ipcgpu_set_plasticity first.  ipcgpu_plastic_reset (no counterpart): restTriInv = A0, alpha = 0.
+ * ipcgpu_opt_save_status appends a section `plastic <nT> 10` (nine entries of restTriInv, then alpha, per element) when an element is plastic -- the file is
+ * otherwise byte for byte what it was, and the reference's reader skips the tokens; ipcgpu_opt_load_status reads it (a file without it leaves both untouched). */
+int ipcgpu_set_plasticity(ipcgpu_ctx*, int tetBegin, int tetEnd, double yield, double creep, double harden);
+int ipcgpu_plastic_get(ipcgpu_ctx*, double* yield_nT, double* creep_nT, double* harden_nT, double* alpha_nT, double* restTriInv0_9nT);
+int ipcgpu_plastic_update(ipcgpu_ctx*, double dt, int* nYielded, int* nSkipped);
+int ipcgpu_plastic_state(ipcgpu_ctx*, double* perElem_nTx3, double* totals4);
+int ipcgpu_plastic_set_state(ipcgpu_ctx*, const double* restTriInv_9nT, const double* alpha_nT);
+int ipcgpu_plastic_reset(ipcgpu_ctx*);
 /* SelfCollisionHandler::computeConstraintSet (SelfCollisionHandler.cpp:2149-2478) at the current positions:
  * MMActiveSet (PP / PE duplicates merged, multiplicity in slot 3), paraEEMMCVIDSet + paraEEeIeJSet, and the
  * candidate list for the partial CCD.  counts3 = {nActive, nParaEE, nCandidates}. */

@@ -274,6 +274,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->chamber.n()) throw UnsupportedError("chambers on a sharded context");
         if (world > 1 && c->mesh->aero.n()) throw UnsupportedError("aerodynamic surfaces on a sharded context");
         if (world > 1 && !c->opt->rounds.empty()) throw UnsupportedError("round colliders on a sharded context");
+        if (world > 1 && c->mesh->plastic.on()) throw UnsupportedError("plasticity on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -447,6 +448,10 @@ int ipcgpu_get_features(ipcgpu_ctx* c, double* A, double* vol, double* mass, dou
 {
     return guarded([&] {
         HipMesh& m = M(c);
+        if (A && m.plastic.allocated()) { // the flow rewrites d_A on the device: the host copy is stale from the first flow on
+            bind(c);
+            m.d_A.download(m.restTriInv.data(), m.restTriInv.size(), c->stream);
+        }
         if (A)
             for (int t = 0; t < m.nT; ++t)
                 for (int k = 0; k < 9; ++k) A[9 * (size_t)t + k] = m.restTriInv[(size_t)k * m.nT + t];
@@ -477,6 +482,7 @@ int ipcgpu_set_mesh_features(ipcgpu_ctx* c, const double* A, const double* vol, 
             for (int t = 0; t < m.nT; ++t)
                 for (int k = 0; k < 9; ++k) m.restTriInv[(size_t)k * m.nT + t] = A[9 * (size_t)t + k];
             m.d_A.upload(m.restTriInv, c->stream);
+            m.resetPlasticHistory(c->stream); // a new rest shape has no plastic history: A0 = A, alpha = 0
         }
         if (vol) {
             m.triArea.assign(vol, vol + m.nT);
@@ -1609,6 +1615,144 @@ int ipcgpu_aero_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
     return guarded([&] {
         need(!M(c).aero.n() || O(c).initialised, "call ipcgpu_opt_init first (it supplies dt)");
         return codimHessianAdd(c, AERO, coef, projectDBC, AERO_MISS);
+    });
+}
+// ---- Plastic flow (plastic_kernels.h; the reference has no counterpart) -------------------------------------------------------------------------
+int ipcgpu_set_plasticity(ipcgpu_ctx* c, int tetBegin, int tetEnd, double yield, double creep, double harden)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (c->worldSize > 1) throw UnsupportedError("plasticity on a sharded context");
+        m.setPlasticity(tetBegin, tetEnd, yield, creep, harden, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_plastic_get(ipcgpu_ctx* c, double* yield, double* creep, double* harden, double* alpha, double* restTriInv0)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        const HipPlastic& h = m.plastic;
+        const size_t nT = (size_t)m.nT;
+        if (!h.allocated()) { // never set: every element elastic, no history, A0 is the mesh's restTriInv
+            for (size_t t = 0; t < nT; ++t) {
+                if (yield) yield[t] = INFINITY;
+                if (creep) creep[t] = INFINITY;
+                if (harden) harden[t] = 0.0;
+                if (alpha) alpha[t] = 0.0;
+            }
+            if (restTriInv0)
+                for (size_t t = 0; t < nT; ++t)
+                    for (int k = 0; k < 9; ++k) restTriInv0[9 * t + k] = m.restTriInv[k * nT + t];
+            return IPCGPU_OK;
+        }
+        if (yield) std::memcpy(yield, h.plan.yield.data(), sizeof(double) * nT);
+        if (creep) std::memcpy(creep, h.plan.creep.data(), sizeof(double) * nT);
+        if (harden) std::memcpy(harden, h.plan.harden.data(), sizeof(double) * nT);
+        if (alpha) h.d_alpha.download(alpha, nT, c->stream);
+        if (restTriInv0) {
+            std::vector<double> soa(9 * nT);
+            h.d_A0.download(soa.data(), soa.size(), c->stream);
+            for (size_t t = 0; t < nT; ++t)
+                for (int k = 0; k < 9; ++k) restTriInv0[9 * t + k] = soa[k * nT + t];
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_plastic_update(ipcgpu_ctx* c, double dt, int* nYielded, int* nSkipped)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        needArg(dt > 0.0 && std::isfinite(dt), "plastic_update: the time step must be positive and finite");
+        int cnt[PC_COUNT] = { 0, 0 };
+        if (m.plastic.on()) {
+            c->opt->plasticFlow(m.d_x.p, dt);
+            HIP_CHECK(hipGetLastError());
+            m.plastic.d_count.download(cnt, PC_COUNT, c->stream);
+        }
+        if (nYielded) *nYielded = cnt[PC_YIELDED];
+        if (nSkipped) *nSkipped = cnt[PC_SKIPPED];
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_plastic_state(ipcgpu_ctx* c, double* perElem, double* totals4)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        const size_t nT = (size_t)m.nT;
+        HipPlastic& h = m.plastic;
+        if (totals4) totals4[0] = totals4[1] = totals4[2] = totals4[3] = 0.0;
+        if (!h.allocated()) {
+            if (perElem)
+                for (size_t t = 0; t < nT; ++t) {
+                    perElem[t] = NAN; // (n is not evaluated without the state arrays)
+                    perElem[nT + t] = INFINITY;
+                    perElem[2 * nT + t] = 0.0;
+                }
+            return IPCGPU_OK;
+        }
+        if (!perElem && !totals4) return IPCGPU_OK;
+        const PlasticView v = c->opt->plasticView(m.d_x.p, 1.0);
+        if (perElem) h.d_state.ensure(3 * nT);
+        h.d_partial.ensure(2 * (size_t)plastic_state_blocks(v));
+        launch_plastic_state(v, perElem ? h.d_state.p : nullptr, h.d_partial.p, totals4 ? h.d_totals.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (perElem) h.d_state.download(perElem, 3 * nT, c->stream);
+        if (totals4) {
+            int cnt[PC_COUNT];
+            double tot[PT_COUNT];
+            h.d_count.download(cnt, PC_COUNT, c->stream);
+            h.d_totals.download(tot, PT_COUNT, c->stream);
+            totals4[0] = cnt[PC_YIELDED];
+            totals4[1] = cnt[PC_SKIPPED];
+            totals4[2] = tot[PT_MAX_ALPHA];
+            totals4[3] = tot[PT_VOL_ALPHA];
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_plastic_set_state(ipcgpu_ctx* c, const double* restTriInv, const double* alpha)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        need(m.plastic.allocated(), "call ipcgpu_set_plasticity first");
+        const size_t nT = (size_t)m.nT;
+        if (alpha)
+            for (size_t t = 0; t < nT; ++t) needArg(alpha[t] >= 0.0 && std::isfinite(alpha[t]), "plastic_set_state: the accumulated plastic strain must be finite and not negative");
+        if (restTriInv) {
+            std::vector<double> soa(9 * nT);
+            for (size_t t = 0; t < nT; ++t)
+                for (int k = 0; k < 9; ++k) {
+                    needArg(std::isfinite(restTriInv[9 * t + k]), "plastic_set_state: restTriInv is not finite");
+                    soa[k * nT + t] = restTriInv[9 * t + k];
+                }
+            HIP_CHECK(hipMemcpyAsync(m.d_A.p, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream)); // (soa leaves scope)
+        }
+        if (alpha) HIP_CHECK(hipMemcpyAsync(m.plastic.d_alpha.p, alpha, nT * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_plastic_reset(ipcgpu_ctx* c)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (!m.plastic.allocated()) return IPCGPU_OK; // no history to forget
+        HIP_CHECK(hipMemcpyAsync(m.d_A.p, m.plastic.d_A0.p, 9 * (size_t)m.nT * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        m.plastic.d_alpha.zero(c->stream);
+        m.plastic.d_count.zero(c->stream);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        return IPCGPU_OK;
     });
 }
 int ipcgpu_set_obstacle_nodes(ipcgpu_ctx* c, int n, const int* ids, int only)

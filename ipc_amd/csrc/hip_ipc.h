@@ -23,6 +23,8 @@
 #include "round_collider_kernels.h"
 #include "pcg.h"
 #include "pcg_coarse.h"
+#include "plastic_kernels.h"
+#include "plastic_plan.h"
 #include "report_plan.h"
 #include "rod_kernels.h"
 #include "rod_plan.h"
@@ -145,6 +147,20 @@ struct HipAero {
     }
 };
 
+// Plastic flow of the tetrahedral elements (ipcgpu_set_plasticity; plastic_kernels.h): the host plan and the device state.  plan.nT == 0: never set, and
+// then nothing below is allocated or read.  on(): some element has a finite yield strain -- only then does the stepper launch the flow and does
+// saveStatus write the section.  While allocated, d_A (HipMesh) is the truth and the host copy HipMesh::restTriInv may be stale.
+struct HipPlastic {
+    PlasticPlan plan;
+    DevBuf<double> d_yield, d_creep, d_harden, d_alpha;
+    DevBuf<double> d_A0; // restTriInv as it was when plasticity was first set (ipcgpu_plastic_reset puts it back), SoA [9][nT]
+    DevBuf<int> d_count; // PC_COUNT (scalar_slots.h)
+    DevBuf<double> d_totals, d_partial, d_state; // PT_COUNT; ipcgpu_plastic_state's scratch
+    bool allocated() const { return plan.nT > 0; }
+    bool on() const { return plan.nOn > 0; }
+    void drop() { plan = PlasticPlan(); }
+};
+
 class HipMesh {
 public:
     int nV = 0, nT = 0;
@@ -216,6 +232,12 @@ public:
     HipAero aero;
     void setAero(int nSurf, const int* triEnd, const int* tri_colmajor, const double* cn, const double* ct, const int* oneSided, hipStream_t s);
     void setAeroWind(const double* wind3, double density); // finite wind, finite density > 0; nothing without surfaces
+    // Plastic flow (plastic_plan.h): validates, uploads the three parameter arrays; the first call allocates alpha = 0 and keeps the copy A0 of d_A.
+    // Touches no mass, no neighbour pair and no pattern; computeFeatures drops it.
+    HipPlastic plastic;
+    void setPlasticity(int tetBegin, int tetEnd, double yield, double creep, double harden, hipStream_t s);
+    void ensurePlastic(hipStream_t s); // the state arrays with every element elastic, unless they exist (loadStatus of a file with a plastic section)
+    void resetPlasticHistory(hipStream_t s); // A0 = the current d_A, alpha = 0 (ipcgpu_set_mesh_features with a restTriInv)
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -393,6 +415,8 @@ public:
     ChamberView chamberView(const double* x_dev, int pressure = CHAMBER_P_EFFECTIVE) const;
     void refreshChamberRef(); // r_c of every chamber from the current positions, on the device (beginTimestep)
     AeroView aeroView(const double* x_dev) const; // (with the wind, the density and dt as they are now)
+    PlasticView plasticView(const double* x_dev, double dt_) const;
+    void plasticFlow(const double* x_dev, double dt_); // zeroes the two counters and launches one flow on the stream: no synchronisation
     void refreshAeroLagged(); // n, A and c^n of every aerodynamic triangle from the current positions, on the device (beginTimestep)
     // The gas chambers' dense rank-k Hessian term, coef sum_c beta_c u_c u_c^T, as a correction around the solver's retained factor (chamber_kernels.h):
     // y_dev holds A^-1 r on entry and (A + coef sum beta_c u_c u_c^T)^-1 r on return, with beta and u at the mesh's current positions.  k further solves,

@@ -40,6 +40,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
     chamber.gas = ChamberGas(); // ... with their gas law
     if (aero.n()) aero.drop(); // ... and the aerodynamic surfaces
+    if (plastic.allocated()) plastic.drop(); // ... and the plastic parameters and history
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -408,6 +409,48 @@ void HipMesh::setAeroWind(const double* wind3, double density)
     if (!aero.n()) return;
     for (int a = 0; a < 3; ++a) aero.wind[a] = wind3[a];
     aero.density = density;
+}
+
+void HipMesh::ensurePlastic(hipStream_t s)
+{
+    if (plastic.allocated()) return;
+    std::string err;
+    if (!setPlasticRange(plastic.plan, nT, 0, 0, INFINITY, INFINITY, 0.0, err)) throw ArgError(err); // every element elastic
+    const size_t n = (size_t)nT;
+    plastic.d_yield.upload(plastic.plan.yield, s);
+    plastic.d_creep.upload(plastic.plan.creep, s);
+    plastic.d_harden.upload(plastic.plan.harden, s);
+    plastic.d_alpha.alloc(n);
+    plastic.d_alpha.zero(s);
+    plastic.d_count.alloc(PC_COUNT);
+    plastic.d_count.zero(s);
+    plastic.d_totals.alloc(PT_COUNT);
+    plastic.d_totals.zero(s);
+    plastic.d_A0.alloc(9 * n);
+    HIP_CHECK(hipMemcpyAsync(plastic.d_A0.p, d_A.p, 9 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setPlasticity(int tetBegin, int tetEnd, double yield, double creep, double harden, hipStream_t s)
+{
+    PlasticPlan next = plastic.plan; // a refused call changes nothing
+    std::string err;
+    if (!setPlasticRange(next, nT, tetBegin, tetEnd, yield, creep, harden, err)) throw ArgError(err);
+    ensurePlastic(s);
+    plastic.plan = std::move(next);
+    plastic.d_yield.upload(plastic.plan.yield, s);
+    plastic.d_creep.upload(plastic.plan.creep, s);
+    plastic.d_harden.upload(plastic.plan.harden, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::resetPlasticHistory(hipStream_t s)
+{
+    if (!plastic.allocated()) return;
+    HIP_CHECK(hipMemcpyAsync(plastic.d_A0.p, d_A.p, 9 * (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));
+    plastic.d_alpha.zero(s);
+    plastic.d_count.zero(s);
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
 void HipMesh::setChamberPressure(const double* pressure, hipStream_t s)

@@ -227,6 +227,19 @@ AeroView HipOptimizer::aeroView(const double* x_dev) const
     return v;
 }
 
+PlasticView HipOptimizer::plasticView(const double* x_dev, double dt_) const
+{
+    const HipPlastic& h = mesh.plastic;
+    return PlasticView{ mesh.nT, tetBegin, tetEnd, x_dev, mesh.d_tet.p, mesh.d_A.p, mesh.d_vol.p, h.d_yield.p, h.d_creep.p, h.d_harden.p, h.d_alpha.p, dt_ };
+}
+
+void HipOptimizer::plasticFlow(const double* x_dev, double dt_)
+{
+    specAsmValid = false; // an assembly enqueued ahead read the rest shapes this flow rewrites
+    mesh.plastic.d_count.zero(stream);
+    launch_plastic_flow(plasticView(x_dev, dt_), mesh.plastic.d_count.p, stream);
+}
+
 void HipOptimizer::refreshAeroLagged()
 {
     if (!mesh.aero.n()) return;
@@ -916,6 +929,17 @@ void HipOptimizer::saveStatus(const std::string& path)
     rows("acceleration", acc);
     out << "\n";
     rows("dx_Elastic", dx);
+    if (mesh.plastic.on()) { // a project extension (the reference's reader skips the tokens): restTriInv (nine entries, column-major) and alpha per element
+        const size_t nT = (size_t)mesh.nT;
+        std::vector<double> A(9 * nT), alpha(nT);
+        mesh.d_A.download(A.data(), A.size(), stream);
+        mesh.plastic.d_alpha.download(alpha.data(), nT, stream);
+        out << "\nplastic " << mesh.nT << " 10\n";
+        for (size_t t = 0; t < nT; ++t) {
+            for (int k = 0; k < 9; ++k) out << A[k * nT + t] << " ";
+            out << alpha[t] << "\n";
+        }
+    }
     if (!out.good()) throw StateError("write error on status file " + path);
 }
 
@@ -940,6 +964,7 @@ void HipOptimizer::loadStatus(const std::string& path)
         // partly read (or stale) arrays
         if (in.fail()) throw StateError("truncated or malformed section in status file " + path);
     };
+    std::vector<double> plasticA, plasticAlpha; // the plastic section, where the file has one
     std::string line;
     while (std::getline(in, line)) {
         std::stringstream ss(line);
@@ -957,6 +982,20 @@ void HipOptimizer::loadStatus(const std::string& path)
         }
         else if (token == "acceleration") readRows(ss, acc, true);
         else if (token == "dx_Elastic") readRows(ss, dx, true);
+        else if (token == "plastic") {
+            int rowsIn = 0, dimIn = 0;
+            ss >> rowsIn >> dimIn;
+            if (ss.fail()) throw StateError("malformed section header in status file " + path);
+            if (rowsIn != mesh.nT || dimIn != 10) throw StateError("status file does not match the mesh");
+            const size_t nT = (size_t)mesh.nT;
+            plasticA.assign(9 * nT, 0.0);
+            plasticAlpha.assign(nT, 0.0);
+            for (size_t t = 0; t < nT; ++t) {
+                for (int k = 0; k < 9; ++k) in >> plasticA[k * nT + t];
+                in >> plasticAlpha[t];
+            }
+            if (in.fail()) throw StateError("truncated or malformed plastic section in status file " + path);
+        }
     }
     if (in.bad()) throw StateError("read error on status file " + path);
     mesh.d_x.upload(x, stream);
@@ -967,6 +1006,11 @@ void HipOptimizer::loadStatus(const std::string& path)
     d_vel.upload(vel, stream);
     d_acc.upload(acc, stream);
     d_dxElastic.upload(dx, stream);
+    if (!plasticA.empty()) { // (a file without the section leaves A and alpha untouched)
+        mesh.ensurePlastic(stream);
+        HIP_CHECK(hipMemcpyAsync(mesh.d_A.p, plasticA.data(), plasticA.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(mesh.plastic.d_alpha.p, plasticAlpha.data(), plasticAlpha.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
     HIP_CHECK(hipStreamSynchronize(stream));
     computeXTilta();
 }
@@ -2122,6 +2166,9 @@ void HipOptimizer::endTimestep()
     else
         launch_be_update(mesh.nV, mesh.d_dbc.p, mesh.d_x.p, d_xStepStart.p, d_xPrev.p, d_vel.p, d_acc.p, d_dxElastic.p, mesh.d_xTilde.p, dt, gravity[0],
             gravity[1], gravity[2], stream);
+    // plastic flow at the end-of-step positions (plastic_kernels.h): before the lagged damping matrix, which is then the stiffness of the rest shape the
+    // next step sees.  Nothing derived from A outlives it: specAsmValid is cleared above, the patch plan and the stress plan hold topology only.
+    if (mesh.plastic.on()) plasticFlow(mesh.d_x.p, dt);
     computeDampingMtr(); // Optimizer.cpp:593-595
     globalIterNum++;
 }

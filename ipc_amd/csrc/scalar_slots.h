@@ -21,6 +21,19 @@ enum ScalarSlot : int {
     S_COUNT
 };
 
+// The plastic flow's own two small boards (HipPlastic, hip_ipc.h; plastic_kernels.h): the stepper's launch adds to the integer one and never reads it on
+// the fast path; ipcgpu_plastic_update and ipcgpu_plastic_state read them.
+enum PlasticCount : int {
+    PC_YIELDED = 0, // elements the last flow rewrote.  Zeroed before every flow, added to by k_plastic_flow (integer atomics).
+    PC_SKIPPED, // elements the last flow found flat or inverted (s2 <= 0) and left alone
+    PC_COUNT
+};
+enum PlasticTotal : int {
+    PT_MAX_ALPHA = 0, // the largest accumulated plastic strain.  Written by launch_plastic_state's reduction, read by ipcgpu_plastic_state behind it.
+    PT_VOL_ALPHA, // sum of rest volume times accumulated plastic strain
+    PT_COUNT
+};
+
 // how many slots first .. last are: the count of a publish
 constexpr int slotSpan(ScalarSlot first, ScalarSlot last) { return last - first + 1; }
 

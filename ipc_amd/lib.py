@@ -871,6 +871,42 @@ class Context:
     def aero_hessian_add(self, coef=1.0, projectDBC=True):
         self._codim_hessian_add("aero", coef, projectDBC)
 
+    # ---- plastic flow of tetrahedral elements (ipcgpu_set_plasticity: yield, creep, isotropic hardening; ipc_amd/csrc/plastic_kernels.h)
+    def set_plasticity(self, tet_range, yield_strain, creep=np.inf, harden=0.0):
+        """elements [tet_range[0], tet_range[1]) yield where the deviatoric Hencky strain norm n exceeds yield_strain + harden alpha (for small strains the von
+        Mises stress is sqrt(6) mu n); the excess decays like exp(-creep t) (inf: returned at once); yield_strain = inf switches the range off.  Any time
+        after set_mesh, also between time steps; later calls overwrite."""
+        self._chk(self._L.ipcgpu_set_plasticity(self.h, C.c_int(tet_range[0]), C.c_int(tet_range[1]), C.c_double(yield_strain), C.c_double(creep), C.c_double(harden)))
+
+    def plastic_get(self):
+        """dict: yield, creep, harden, alpha (nT each), restTriInv0 (nT x 9: the rest shapes plastic_reset restores)"""
+        y, cr, K, al, A0 = np.zeros(self.nT), np.zeros(self.nT), np.zeros(self.nT), np.zeros(self.nT), np.zeros((self.nT, 9))
+        self._chk(self._L.ipcgpu_plastic_get(self.h, _dp(y), _dp(cr), _dp(K), _dp(al), _dp(A0)))
+        return {"yield": y, "creep": cr, "harden": K, "alpha": al, "restTriInv0": A0}
+
+    def plastic_update(self, dt):
+        """one flow at the held positions, outside the stepper: (elements that yielded, elements skipped as flat or inverted)"""
+        ny, ns = C.c_int(), C.c_int()
+        self._chk(self._L.ipcgpu_plastic_update(self.h, C.c_double(dt), C.byref(ny), C.byref(ns)))
+        return ny.value, ns.value
+
+    def plastic_state(self, per_elem=True):
+        """(perElem nT x 3: n, current yield strain y, alpha -- n is NaN where the flow would skip the element; totals: yielded and skipped in the last flow,
+        max alpha, sum of rest volume x alpha).  Read-only."""
+        pe, tot = np.zeros((self.nT, 3), order="F"), np.zeros(4)
+        self._chk(self._L.ipcgpu_plastic_state(self.h, _dp(pe) if per_elem else None, _dp(tot)))
+        return (pe if per_elem else None), tot
+
+    def plastic_set_state(self, restTriInv=None, alpha=None):
+        """the current rest shapes (nT x 9, as features()['restTriInv']) and / or the accumulated plastic strain (nT) from the caller"""
+        A = None if restTriInv is None else _f64(np.asarray(restTriInv, dtype=np.float64).reshape(self.nT, 9))
+        al = None if alpha is None else _f64(np.asarray(alpha, dtype=np.float64).reshape(self.nT))
+        self._chk(self._L.ipcgpu_plastic_set_state(self.h, _dp(A), _dp(al)))
+
+    def plastic_reset(self):
+        """forget the plastic history: the rest shapes of the first set_plasticity call, alpha = 0"""
+        self._chk(self._L.ipcgpu_plastic_reset(self.h))
+
     # ---- the gas law of the chambers (ipcgpu_chamber_set_gas)
     def chamber_set_gas(self, is_gas, ambient=0.0, gamma=1.0, fill_volume=None):
         """per chamber (scalars broadcast): is_gas (False: constant pressure), the ambient absolute pressure, the exponent gamma (1 isothermal, 1.4 adiabatic

@@ -67,6 +67,10 @@ class Shape:
     # `shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]`: this shape's triangles carry the incompressible Mooney-Rivlin membrane in place of
     # the StVK one (Context.set_shell_membrane); alpha in [0, 1) is the I2 fraction, default 0 = neo-Hookean; per shape, shapes may differ
     shell_rubber: bool = False
+    # `plastic <yield> [creep <rate>] [harden <K>]` (this project's keyword, tetrahedral shapes only): the shape's elements flow plastically where the deviatoric
+    # Hencky strain norm exceeds yield + K alpha (Context.set_plasticity; for small strains the von Mises stress is sqrt(6) mu n); creep: the rate at which the
+    # excess decays (default inf: returned within the step), harden: isotropic hardening (default 0).  (yield, creep, harden), or None
+    plastic: tuple = None
     shell_alpha: float = 0.0
     # `rod <radius> [bend <scale>]` (this project's keyword, `.seg` shapes only): the component is an elastic rod -- stretching and bending energy with the
     # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
@@ -499,6 +503,19 @@ def _parse_shape(st, resolve):
                 raise ValueError("contactGroup needs a group")
             sh.contact_group = _contact_group(st[j])
             j += 1
+        elif e == "plastic":
+            if j >= len(st):
+                raise ValueError("plastic needs a yield strain")
+            par = {"yield": float(st[j]), "creep": math.inf, "harden": 0.0}
+            j += 1
+            while j < len(st) and st[j] in ("creep", "harden"):
+                if j + 1 >= len(st):
+                    raise ValueError(st[j] + " needs a number")
+                par[st[j]] = float(st[j + 1])
+                j += 2
+            if not (par["yield"] >= 0.0 and par["creep"] > 0.0 and 0.0 <= par["harden"] < math.inf):
+                raise ValueError("plastic needs a yield strain >= 0, a creep rate > 0 and a finite hardening modulus >= 0")
+            sh.plastic = (par["yield"], par["creep"], par["harden"])
         elif e == "shell":
             if j >= len(st):
                 raise ValueError("shell needs a thickness")
@@ -635,6 +652,8 @@ def _parse_shape(st, resolve):
         raise ValueError("shell is valid on a triangle-mesh shape only (not on a tetrahedral, segment or point shape)")
     if sh.rod_radius is not None and os.path.splitext(sh.path.lower())[1] != ".seg":
         raise ValueError("rod is valid on a segment shape only (not on a tetrahedral, triangle-mesh or point shape)")
+    if sh.plastic is not None and os.path.splitext(sh.path.lower())[1] in (".obj", ".seg", ".pt"):
+        raise ValueError("plastic is valid on a tetrahedral shape only (not on a shell, rod, point or surface-only shape)")
     if sh.aero:
         ext = os.path.splitext(sh.path.lower())[1]
         if ext in (".seg", ".pt") or (ext == ".obj" and sh.shell_thickness is None):
@@ -1141,6 +1160,9 @@ def apply(sc, be):
         # (the same holds for a rod shape and set_rod)
         if sh.material is not None and all(np.isfinite(sh.material)) and sh.shell_thickness is None and sh.rod_radius is None:
             be.set_component_material((sc.node_ranges[s], sc.node_ranges[s + 1]), (sc.tet_ranges[s], sc.tet_ranges[s + 1]), *sh.material)
+    for s, sh in enumerate(cfg.shapes):  # per component, behind the materials
+        if sh.plastic is not None and sc.tet_ranges[s + 1] > sc.tet_ranges[s]:
+            be.set_plasticity((sc.tet_ranges[s], sc.tet_ranges[s + 1]), *sh.plastic)
     if sc.V0 is not None:
         be.set_positions(sc.V0)
     be.opt_init(cfg.dt, cfg.gravity)
@@ -1268,7 +1290,7 @@ class ContactReportWriter:
 
 class FieldsWriter:
     """`fields<N>.vtu` files in `folder` (tools/run_scene.py --fields): an ASCII VTK unstructured grid of the tetrahedra at the state the backend holds.
-    Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()`.  Point data: the nodal
+    Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()` -- and, only when a shape carries `plastic`, `plasticStrain` (the accumulated plastic strain alpha).  Point data: the nodal
     `stress` (rest-volume-weighted mean of the incident elements), `von_mises` of that mean, `velocity`; with self-contact on, `contact_force` -- minus the
     barrier gradient of the constraint set rebuilt at these positions with the step's dHat and kappa, Dirichlet rows kept -- and, when the lagged friction
     set is not empty, `friction_force` -- minus the lagged friction gradient of the step from `x_prev` to here.  The reference writes no such file.
@@ -1288,6 +1310,8 @@ class FieldsWriter:
         nV = X.shape[0]
         cell = {"stress": elem[:, :6], "von_mises": elem[:, 6], "J": elem[:, 7]}
         point = {"stress": node[:, :6], "von_mises": node[:, 6], "velocity": be.kinematics()["velocity"].reshape(nV, 3)}
+        if any(sh.plastic is not None for sh in self.sc.cfg.shapes):  # the accumulated plastic strain, only where a shape is plastic: other files are what they were
+            cell["plasticStrain"] = be.plastic_get()["alpha"]
         if self.contact:
             fs = be.friction_state()  # (the lagged set first: rebuilding the constraint set below is not to touch what it is read from)
             fric = np.zeros((nV, 3))

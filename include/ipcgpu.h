@@ -144,7 +144,8 @@ int ipcgpu_elastic_energy_per_elem(ipcgpu_ctx*, double* perElem_nT);
  * an element (surface-only and codimensional nodes) gets zeros; a NaN element makes the seven stress entries of its four nodes NaN (the volume sum stays).
  * Any pointer may be null; the nodal pass is skipped when perNode is null.  Valid after ipcgpu_set_mesh (positions: ipcgpu_set_positions) and at
  * any point between time steps after ipcgpu_opt_init (before a mesh is set: IPCGPU_ERR_STATE); changes no state.  fp64, a fixed summation order, no
- * floating-point atomics: the same state gives the same bits.  On a sharded context (ipcgpu_ctx_set_shard, world > 1): IPCGPU_ERR_UNSUPPORTED. */
+ * floating-point atomics: the same state gives the same bits.  On a sharded context (ipcgpu_ctx_set_shard, world > 1): IPCGPU_ERR_UNSUPPORTED.
+ * The stress is the ISOTROPIC part alone: the fibre term of ipcgpu_set_fibers is not in it (ipcgpu_fiber_state gives the fibre tension per element). */
 int ipcgpu_elastic_stress(ipcgpu_ctx*, double* perElem_nTx8, double* perNode_nVx8, int* n_invalid);
 /* Energy::computeGradient (Energy.hpp:47, Energy.cpp:245-289) */
 int ipcgpu_elastic_gradient(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
@@ -632,6 +633,37 @@ int ipcgpu_aero_energy(ipcgpu_ctx*, double coef, double* energy);
 int ipcgpu_aero_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_aero_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_aero_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+/* ---- Fibre reinforcement and active contraction of tetrahedral elements.  No counterpart in the reference (every body of it is isotropic).  The model, its
+ * degenerate states and what is not modelled are stated in ipc_amd/csrc/fiber_kernels.h.  Per fibred element with rest volume vol, unit rest direction a and
+ * b = restTriInv a: d = b1 (x1 - x0) + b2 (x2 - x0) + b3 (x3 - x0) = F a, l = |d| the fibre stretch, W = vol psi(l); the Hessian blocks are the closed-form
+ * PSD projection.  The term is one of the codimensional energies of the stepper (it enters the lagged stiffness damping) and adds no pair to the pattern.
+ * ipcgpu_set_fibers: elements [tetBegin, tetEnd) get one fibre family; ranges as in ipcgpu_set_component_material, a later call overwrites, k == 0 removes.
+ *   dir: 3 doubles in the frame of the rest positions (dirPerElement != 0: 3 per element of the range, element-major); normalised by the call.
+ *   law 0 (spring): psi = k (l - l0)^2 / 2 with l0 = 1 - act(group); tensionOnly != 0: psi = 0 for l <= l0.  law 1 (exp): psi = k / (2 k2) (exp(k2 (l^2 - 1)^2) - 1)
+ *   for l > 1, 0 otherwise; k2 is read under law 1 alone.  k is a stress (Pa), the caller's: no material scales it.  group: 0 .. 63.
+ *   IPCGPU_ERR_ARG, and nothing is changed: a range outside [0, nT), a null, zero or non-finite direction, k < 0 or not finite, an unknown law, law 1 with
+ *   k2 <= 0, a group outside [0, 64), law 1 on a group whose activation is not 0.  IPCGPU_ERR_UNSUPPORTED: an element of the range is plastic
+ *   (ipcgpu_set_plasticity on a fibred element returns the same), or the context is sharded (ipcgpu_ctx_set_shard with world > 1 on a context with fibres
+ *   returns the same).  Allowed any time after ipcgpu_set_mesh, before or after ipcgpu_opt_init, between time steps.  With no fibred element the stepper
+ *   launches nothing and every result is bit-identical to a context that never called this.  ipcgpu_set_mesh_features with a restTriInv or a volume
+ *   recomputes b and vol k; ipcgpu_set_mesh drops the fibres.
+ * ipcgpu_fiber_set_activation: act < 1 of one group (0: passive; 0.3: the fibres want to be 30 % shorter); uploads 64 doubles and nothing per element.
+ *   IPCGPU_ERR_ARG: act >= 1 or not finite, a group out of range, act != 0 on a group that holds a law-1 element.  IPCGPU_ERR_STATE before ipcgpu_set_fibers.
+ * ipcgpu_fiber_get: the number of fibred elements, per element k, k2, the law, tension-only (1 under law 1), the group and the unit direction (nT x 3,
+ *   element-major; zeros without a fibre), and the 64 activations.  Any pointer may be NULL.
+ * ipcgpu_fiber_energy / _energy_per_elem (nT, 0 without a fibre) / _gradient_add / _hessian_add: as the ipcgpu_attach_* calls of the same names.
+ * ipcgpu_fiber_state: read-only.  perElem (nullable, column-major nT x 5): l, the tension psi'(l) (a stress), the current direction t; an element without
+ *   fibres gets 1, 0 and 0 0 0.  totals3 (nullable): min l and max l over the fibred elements (1 and 1 without any) and the sum of W.  Deterministic.
+ * ipcgpu_opt_save_status appends a section `fiber <nT> 7 64` (the activations, then k, k2, flag word, group and direction per element) when an element is
+ *   fibred -- the file is otherwise byte for byte what it was; ipcgpu_opt_load_status reads it and replaces the context's fibres with it. */
+int ipcgpu_set_fibers(ipcgpu_ctx*, int tetBegin, int tetEnd, const double* dir, int dirPerElement, double k, int law, double k2, int tensionOnly, int group);
+int ipcgpu_fiber_set_activation(ipcgpu_ctx*, int group, double act);
+int ipcgpu_fiber_get(ipcgpu_ctx*, int* nFibred, double* k_nT, double* k2_nT, int* law_nT, int* tensionOnly_nT, int* group_nT, double* dir_3nT, double* act_64);
+int ipcgpu_fiber_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_fiber_energy_per_elem(ipcgpu_ctx*, double* perTet_nT);
+int ipcgpu_fiber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_fiber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_fiber_state(ipcgpu_ctx*, double* perElem_nTx5, double* totals3);
 /* ---- Plastic flow of tetrahedral elements: yield, creep, isotropic hardening.  No counterpart in the reference (every body of it is elastic).
  * The model is stated in ipc_amd/csrc/plastic_kernels.h.  Per element with a finite yield strain, at the end of every time step (after the BE / Newmark
  * update, before the lagged damping matrix): F = Ds(x) restTriInv = U diag(s) V^T; skipped and counted where s2 <= 0; e = ln s, d = e - mean(e), n = |d|;

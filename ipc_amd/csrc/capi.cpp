@@ -114,16 +114,17 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
 // `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its rubber membrane and its limit, ipcgpu_shell_limit_* the limit alone,
-// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers, ipcgpu_aero_* wind and air drag.
+// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers, ipcgpu_aero_* wind and air drag, ipcgpu_fiber_* the fibres of the tetrahedra.
 constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_RUBBER | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT,
                    RUBBER_ALONE = HipOptimizer::CODIM_SHELL_RUBBER, ROD = HipOptimizer::CODIM_ROD,
-                   ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER, AERO = HipOptimizer::CODIM_AERO;
+                   ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER, AERO = HipOptimizer::CODIM_AERO, FIBER = HipOptimizer::CODIM_FIBER;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
 const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hessian: build it after ipcgpu_set_attachments";
 const char* const CHAMBER_MISS = "the pattern lacks a block of the chamber Hessian: build it after ipcgpu_set_chambers";
 const char* const AERO_MISS = "the pattern lacks a block of the air-drag Hessian: build it after ipcgpu_set_aero";
-// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle, no aerodynamic triangle.
+const char* const FIBER_MISS = "the pattern lacks a block of the fibre Hessian: it does not hold the node pairs of the tetrahedra";
+// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle, no aerodynamic triangle, no fibred element.
 int codimCount(const HipMesh& m, unsigned which)
 {
     return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
@@ -132,7 +133,8 @@ int codimCount(const HipMesh& m, unsigned which)
         : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
         : (which & HipOptimizer::CODIM_ATTACH)      ? m.attach.n()
         : (which & HipOptimizer::CODIM_CHAMBER)     ? m.chamber.nTri()
-                                                    : m.aero.nTri();
+        : (which & HipOptimizer::CODIM_AERO)        ? m.aero.nTri()
+                                                    : m.fiber.n();
 }
 int codimEnergy(ipcgpu_ctx* c, unsigned which, double coef, double* E)
 {
@@ -275,6 +277,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->aero.n()) throw UnsupportedError("aerodynamic surfaces on a sharded context");
         if (world > 1 && !c->opt->rounds.empty()) throw UnsupportedError("round colliders on a sharded context");
         if (world > 1 && c->mesh->plastic.on()) throw UnsupportedError("plasticity on a sharded context");
+        if (world > 1 && c->mesh->fiber.n()) throw UnsupportedError("fibres on a sharded context");
         c->rank = rank;
         c->worldSize = world;
         c->opt->rank = rank;
@@ -488,6 +491,7 @@ int ipcgpu_set_mesh_features(ipcgpu_ctx* c, const double* A, const double* vol, 
             m.triArea.assign(vol, vol + m.nT);
             m.d_vol.upload(m.triArea, c->stream);
         }
+        if (A || vol) m.uploadFibers(c->stream); // b = A_t a and vol k of the fibred elements follow (fiber_plan.h)
         if (mass) {
             m.mass.assign(mass, mass + m.nV);
             m.d_mass.upload(m.mass, c->stream);
@@ -1615,6 +1619,117 @@ int ipcgpu_aero_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
     return guarded([&] {
         need(!M(c).aero.n() || O(c).initialised, "call ipcgpu_opt_init first (it supplies dt)");
         return codimHessianAdd(c, AERO, coef, projectDBC, AERO_MISS);
+    });
+}
+// ---- Fibre reinforcement (fiber_kernels.h; the reference has no counterpart) ---------------------------------------------------------------------
+int ipcgpu_set_fibers(ipcgpu_ctx* c, int tetBegin, int tetEnd, const double* dir, int dirPerElement, double k, int law, double k2, int tensionOnly, int group)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (c->worldSize > 1) throw UnsupportedError("fibres on a sharded context");
+        m.setFibers(tetBegin, tetEnd, dir, dirPerElement != 0, k, law, k2, tensionOnly != 0, group, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_fiber_set_activation(ipcgpu_ctx* c, int group, double act)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        m.setFiberActivation(group, act, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_fiber_get(ipcgpu_ctx* c, int* nFibred, double* k, double* k2, int* law, int* tensionOnly, int* group, double* dir, double* act)
+{
+    return guarded([&] {
+        const HipMesh& m = M(c);
+        const FiberPlan& p = m.fiber.plan;
+        const size_t nT = (size_t)m.nT;
+        const bool set = p.nT > 0;
+        if (nFibred) *nFibred = p.nF;
+        for (size_t t = 0; t < nT; ++t) {
+            if (k) k[t] = set ? p.k[t] : 0.0;
+            if (k2) k2[t] = set ? p.k2[t] : 0.0;
+            if (law) law[t] = set && (p.flags[t] & FIBER_FLAG_EXP) ? FIBER_LAW_EXP : FIBER_LAW_SPRING;
+            if (tensionOnly) tensionOnly[t] = set && p.flags[t] != 0 ? 1 : 0; // (the exp law is always tension only)
+            if (group) group[t] = set ? p.group[t] : 0;
+            if (dir)
+                for (int r = 0; r < 3; ++r) dir[3 * t + r] = set ? p.dir[r * nT + t] : 0.0;
+        }
+        if (act)
+            for (int g = 0; g < FIBER_MAX_GROUPS; ++g) act[g] = set ? p.act[g] : 0.0;
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_fiber_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] { return codimEnergy(c, FIBER, coef, E); });
+}
+int ipcgpu_fiber_energy_per_elem(ipcgpu_ctx* c, double* perTet)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        if (!perTet) return IPCGPU_OK;
+        const HipFiber& f = c->mesh->fiber;
+        std::fill(perTet, perTet + c->mesh->nT, 0.0);
+        const int n = f.n();
+        if (!n) return IPCGPU_OK;
+        DevBuf<double> e;
+        e.alloc(n);
+        launch_fiber_energy_per_elem(o.fiberView(c->mesh->d_x.p), e.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        std::vector<double> h(n);
+        e.download(h.data(), n, c->stream);
+        for (int i = 0; i < n; ++i) perTet[f.plan.fibTet[i]] = h[i];
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_fiber_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] { return codimGradientAdd(c, FIBER, coef, projectDBC, g); });
+}
+int ipcgpu_fiber_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] { return codimHessianAdd(c, FIBER, coef, projectDBC, FIBER_MISS); });
+}
+int ipcgpu_fiber_state(ipcgpu_ctx* c, double* perElem, double* totals3)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        HipMesh& m = *c->mesh;
+        HipFiber& f = m.fiber;
+        const size_t nT = (size_t)m.nT, n = (size_t)f.n();
+        if (perElem) // an element without fibres: stretch 1, no tension, no direction
+            for (size_t t = 0; t < nT; ++t) {
+                perElem[t] = 1.0;
+                for (int q = 1; q < FIBER_STATE_COLS; ++q) perElem[q * nT + t] = 0.0;
+            }
+        if (totals3) {
+            totals3[0] = totals3[1] = 1.0;
+            totals3[2] = 0.0;
+        }
+        if (!n || (!perElem && !totals3)) return IPCGPU_OK;
+        const FiberView v = o.fiberView(m.d_x.p);
+        if (perElem) f.d_state.ensure(FIBER_STATE_COLS * n);
+        f.d_partial.ensure(3 * (size_t)fiber_energy_blocks(v));
+        f.d_totals.ensure(3);
+        launch_fiber_state(v, m.d_vol.p, perElem ? f.d_state.p : nullptr, f.d_partial.p, totals3 ? f.d_totals.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (perElem) {
+            std::vector<double> h(FIBER_STATE_COLS * n);
+            f.d_state.download(h.data(), h.size(), c->stream);
+            for (size_t i = 0; i < n; ++i)
+                for (int q = 0; q < FIBER_STATE_COLS; ++q) perElem[q * nT + (size_t)f.plan.fibTet[i]] = h[q * n + i];
+        }
+        if (totals3) f.d_totals.download(totals3, 3, c->stream);
+        return IPCGPU_OK;
     });
 }
 // ---- Plastic flow (plastic_kernels.h; the reference has no counterpart) -------------------------------------------------------------------------

@@ -14,6 +14,8 @@
 #include "chamber_kernels.h"
 #include "chamber_plan.h"
 #include "contact_pattern.h"
+#include "fiber_kernels.h"
+#include "fiber_plan.h"
 #include "mf_numeric.h"
 #include "mf_symbolic.h"
 #include "nh_kernels.h"
@@ -161,6 +163,17 @@ struct HipPlastic {
     void drop() { plan = PlasticPlan(); }
 };
 
+// Fibre reinforcement of the tetrahedral elements (ipcgpu_set_fibers; fiber_kernels.h): the host plan and its device copy.  n() == 0: no fibred element,
+// and then nothing below is ever read and the stepper launches nothing.
+struct HipFiber {
+    FiberPlan plan;
+    DevBuf<int> d_fibTet, d_flags, d_groupOf;
+    DevBuf<double> d_b, d_volK, d_k2, d_l0;
+    DevBuf<double> d_state, d_partial, d_totals; // ipcgpu_fiber_state's scratch
+    int n() const { return plan.nF; }
+    void drop() { plan = FiberPlan(); }
+};
+
 class HipMesh {
 public:
     int nV = 0, nT = 0;
@@ -238,6 +251,13 @@ public:
     void setPlasticity(int tetBegin, int tetEnd, double yield, double creep, double harden, hipStream_t s);
     void ensurePlastic(hipStream_t s); // the state arrays with every element elastic, unless they exist (loadStatus of a file with a plastic section)
     void resetPlasticHistory(hipStream_t s); // A0 = the current d_A, alpha = 0 (ipcgpu_set_mesh_features with a restTriInv)
+    // Fibre reinforcement (fiber_plan.h): validates, merges the range into the specification, rebuilds the compact lists from the current restTriInv and
+    // rest volumes and uploads them.  Refuses a range that holds a plastic element.  Touches no mass, no neighbour pair and no pattern (the six node
+    // pairs of a tetrahedron are in every pattern); computeFeatures drops it.
+    HipFiber fiber;
+    void setFibers(int tetBegin, int tetEnd, const double* dir, bool dirPerElement, double k, int law, double k2, bool tensionOnly, int group, hipStream_t s);
+    void setFiberActivation(int group, double act, hipStream_t s); // uploads l0 (FIBER_MAX_GROUPS doubles) and nothing per element
+    void uploadFibers(hipStream_t s); // the compact lists again from the current restTriInv and volumes (ipcgpu_set_mesh_features, loadStatus)
     void meshBBox(); // bounding box and node count over inMesh (Mesh::matSpaceBBoxSize2(dim) / avgNodeMass(dim): tetrahedral components only)
     void uploadDBC(hipStream_t s);
     int energyType = 0; // Config `energy NH|FCR` (Config.cpp:23-24): 0 neo-Hookean, 1 fixed corotated; 2 stable neo-Hookean (no counterpart in the reference)
@@ -397,10 +417,10 @@ public:
     ElemView view() const;
     // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h, aero_kernels.h) enter wherever the tetrahedral elastic term does, with the same
     // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, limit, rod, attachments, chambers, air drag (the energy sum
-    // is ((((((E + shell) + rubber) + limit) + rod) + attach) + chamber) + aero) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri(), aero.nTri()); none of them is ever sharded.
-    // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness, and neither is air drag.
+    // is (((((((E + shell) + rubber) + limit) + rod) + attach) + chamber) + aero) + fiber) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri(), aero.nTri(), fiber.n()); none of them is ever sharded.
+    // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness, and neither is air drag; the fibre term is one.
     enum : unsigned {
-        CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_AERO = 64, CODIM_ALL = 127,
+        CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_AERO = 64, CODIM_FIBER = 128, CODIM_ALL = 255,
         CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER & ~CODIM_AERO
     };
     CodimBase codimBase(const double* x_dev) const;
@@ -409,6 +429,7 @@ public:
     ShellRubberView shellRubberView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
     AttachView attachView(const double* x_dev) const;
+    FiberView fiberView(const double* x_dev) const;
     // pressure: which array the kernels read as the pressure -- d_pressure without a gas chamber, whatever is asked; with one, the effective pressure
     // (CHAMBER_P_EFFECTIVE, what the assembly wants) or the constant chambers' alone (CHAMBER_P_CONSTANT, what the per-triangle energy wants)
     enum { CHAMBER_P_EFFECTIVE = 0, CHAMBER_P_CONSTANT = 1 };

@@ -41,6 +41,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     chamber.gas = ChamberGas(); // ... with their gas law
     if (aero.n()) aero.drop(); // ... and the aerodynamic surfaces
     if (plastic.allocated()) plastic.drop(); // ... and the plastic parameters and history
+    if (fiber.plan.nT) fiber.drop(); // ... and the fibres
     nV = nV_;
     nT = nT_;
     V_rest.assign(Vr, Vr + 3 * (size_t)nV);
@@ -436,6 +437,9 @@ void HipMesh::setPlasticity(int tetBegin, int tetEnd, double yield, double creep
     PlasticPlan next = plastic.plan; // a refused call changes nothing
     std::string err;
     if (!setPlasticRange(next, nT, tetBegin, tetEnd, yield, creep, harden, err)) throw ArgError(err);
+    if (fiber.n() && yield < INFINITY) // (fiber_kernels.h: the rest shape of a fibred element must not flow under b = A_t a)
+        for (int t = tetBegin; t < tetEnd; ++t)
+            if (fiber.plan.k[t] > 0.0) throw UnsupportedError("plasticity on a fibred element (element " + std::to_string(t) + "): its rest shape would flow under the fibre direction");
     ensurePlastic(s);
     plastic.plan = std::move(next);
     plastic.d_yield.upload(plastic.plan.yield, s);
@@ -450,6 +454,55 @@ void HipMesh::resetPlasticHistory(hipStream_t s)
     HIP_CHECK(hipMemcpyAsync(plastic.d_A0.p, d_A.p, 9 * (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));
     plastic.d_alpha.zero(s);
     plastic.d_count.zero(s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::uploadFibers(hipStream_t s)
+{
+    if (!fiber.plan.nT) return;
+    std::vector<double> A;
+    const double* Ap = restTriInv.data();
+    if (plastic.allocated()) { // (the host copy may be stale: HipPlastic)
+        A.resize(9 * (size_t)nT);
+        d_A.download(A.data(), A.size(), s);
+        Ap = A.data();
+    }
+    buildFiberLists(fiber.plan, Ap, triArea.data());
+    const FiberPlan& p = fiber.plan;
+    fiber.d_fibTet.upload(p.fibTet, s);
+    fiber.d_flags.upload(p.flagsF, s);
+    fiber.d_groupOf.upload(p.groupOf, s);
+    fiber.d_b.upload(p.b, s);
+    fiber.d_volK.upload(p.volK, s);
+    fiber.d_k2.upload(p.k2F, s);
+    fiber.d_l0.upload(p.l0, s);
+    if (!d_codimErr.n) { // the first codimensional term of this mesh
+        d_codimErr.alloc(1);
+        d_codimErr.zero(s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setFibers(int tetBegin, int tetEnd, const double* dir, bool dirPerElement, double k, int law, double k2, bool tensionOnly, int group, hipStream_t s)
+{
+    FiberPlan next = fiber.plan; // a refused call changes nothing
+    std::string err;
+    if (!setFiberRange(next, nT, tetBegin, tetEnd, dir, dirPerElement, k, law, k2, tensionOnly, group, err)) throw ArgError(err);
+    if (k > 0.0 && plastic.on()) // (fiber_kernels.h)
+        for (int t = tetBegin; t < tetEnd; ++t)
+            if (plastic.plan.yield[t] < INFINITY) throw UnsupportedError("fibres on a plastic element (element " + std::to_string(t) + "): its rest shape would flow under the fibre direction");
+    fiber.plan = std::move(next);
+    uploadFibers(s);
+}
+
+void HipMesh::setFiberActivation(int group, double act, hipStream_t s)
+{
+    std::string err;
+    if (!ipcgpu::setFiberActivation(fiber.plan, group, act, err)) { // (the plan's function, fiber_plan.h)
+        if (!fiber.plan.nT) throw StateError("ipcgpu_fiber_set_activation without fibres: call ipcgpu_set_fibers first");
+        throw ArgError(err);
+    }
+    fiber.d_l0.upload(fiber.plan.l0, s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 

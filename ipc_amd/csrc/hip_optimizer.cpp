@@ -12,6 +12,7 @@
 #include <limits>
 #include <sstream>
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <thread>
 #include <iterator>
@@ -86,6 +87,7 @@ CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
 CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
 CODIM_VIEW_LAYOUT(ChamberView, ChamberFields, nTri);
 CODIM_VIEW_LAYOUT(AeroView, AeroFields, nTri);
+CODIM_VIEW_LAYOUT(FiberView, FiberFields, nF);
 #pragma clang diagnostic pop
 #undef CODIM_VIEW_LAYOUT
 
@@ -160,6 +162,23 @@ AttachView HipOptimizer::attachView(const double* x_dev) const
     v.node = t.d_node.p;
     v.coef = t.d_coef.p;
     v.kL = t.d_kL.p;
+    return v;
+}
+
+FiberView HipOptimizer::fiberView(const double* x_dev) const
+{
+    const HipFiber& f = mesh.fiber;
+    FiberView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nF = f.n();
+    v.fibTet = f.d_fibTet.p;
+    v.tet = mesh.d_tet.p;
+    v.b = f.d_b.p;
+    v.volK = f.d_volK.p;
+    v.k2 = f.d_k2.p;
+    v.flags = f.d_flags.p;
+    v.groupOf = f.d_groupOf.p;
+    v.l0 = f.d_l0.p;
     return v;
 }
 
@@ -290,6 +309,9 @@ const CodimTerm CODIM_TERMS[] = {
     { HipOptimizer::CODIM_AERO, [](const HipMesh& m) { return m.aero.nTri(); },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_aero_energy(o.aeroView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_aero_assemble(o.aeroView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_FIBER, [](const HipMesh& m) { return m.fiber.n(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_fiber_energy(o.fiberView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_fiber_assemble(o.fiberView(x), coef, proj, g, a, err, o.stream); } },
 };
 } // namespace
 
@@ -671,7 +693,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod and attachment Hessians at the damping positions (a chamber's pressure is no stiffness, nor is air drag)
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod, attachment and fibre Hessians at the damping positions (a chamber's pressure is no stiffness, nor is air drag)
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;
@@ -940,6 +962,14 @@ void HipOptimizer::saveStatus(const std::string& path)
             out << alpha[t] << "\n";
         }
     }
+    if (mesh.fiber.n()) { // a project extension, beside `plastic`: the activations per group, then k, k2, the flag word, the group and the unit direction per element
+        const FiberPlan& p = mesh.fiber.plan;
+        const size_t nT = (size_t)mesh.nT;
+        out << "\nfiber " << mesh.nT << " 7 " << FIBER_MAX_GROUPS << "\n";
+        for (int g = 0; g < FIBER_MAX_GROUPS; ++g) out << p.act[g] << (g + 1 < FIBER_MAX_GROUPS ? " " : "\n");
+        for (size_t t = 0; t < nT; ++t)
+            out << p.k[t] << " " << p.k2[t] << " " << p.flags[t] << " " << p.group[t] << " " << p.dir[t] << " " << p.dir[nT + t] << " " << p.dir[2 * nT + t] << "\n";
+    }
     if (!out.good()) throw StateError("write error on status file " + path);
 }
 
@@ -965,6 +995,7 @@ void HipOptimizer::loadStatus(const std::string& path)
         if (in.fail()) throw StateError("truncated or malformed section in status file " + path);
     };
     std::vector<double> plasticA, plasticAlpha; // the plastic section, where the file has one
+    FiberPlan fiberIn; // the fiber section, where the file has one
     std::string line;
     while (std::getline(in, line)) {
         std::stringstream ss(line);
@@ -996,6 +1027,40 @@ void HipOptimizer::loadStatus(const std::string& path)
             }
             if (in.fail()) throw StateError("truncated or malformed plastic section in status file " + path);
         }
+        else if (token == "fiber") {
+            int rowsIn = 0, dimIn = 0, groupsIn = 0;
+            ss >> rowsIn >> dimIn >> groupsIn;
+            if (ss.fail()) throw StateError("malformed section header in status file " + path);
+            if (rowsIn != mesh.nT || dimIn != 7 || groupsIn != FIBER_MAX_GROUPS) throw StateError("status file does not match the mesh");
+            const size_t nT = (size_t)mesh.nT;
+            std::vector<double> act(FIBER_MAX_GROUPS), k(nT), k2(nT), dir(3 * nT);
+            std::vector<int> flags(nT), group(nT);
+            for (double& v : act) in >> v;
+            for (size_t t = 0; t < nT; ++t) in >> k[t] >> k2[t] >> flags[t] >> group[t] >> dir[3 * t] >> dir[3 * t + 1] >> dir[3 * t + 2];
+            if (in.fail()) throw StateError("truncated or malformed fiber section in status file " + path);
+            // the rows go through the plan's own calls, in the order a caller would make them: one set of rules (fiber_plan.h).  The plan normalises the
+            // direction again; the file's own is kept where it is that unit vector to rounding, so that a restart continues to the bit
+            std::string err;
+            auto bad = [&](const std::string& what) { return StateError("fiber section of status file " + path + ": " + what); };
+            const double none[3] = { 1.0, 0.0, 0.0 };
+            if (!setFiberRange(fiberIn, mesh.nT, 0, 0, none, false, 0.0, 0, 0.0, false, 0, err)) throw bad(err); // no fibre anywhere
+            for (int g = 0; g < FIBER_MAX_GROUPS; ++g)
+                if (!setFiberActivation(fiberIn, g, act[g], err)) throw bad(err);
+            for (size_t t = 0; t < nT; ++t) {
+                if (k[t] == 0.0) continue;
+                if (worldSize > 1) throw UnsupportedError("fibres on a sharded context");
+                if (flags[t] != 0 && flags[t] != FIBER_FLAG_EXP && flags[t] != FIBER_FLAG_TENSION_ONLY) throw bad("element " + std::to_string(t) + ": unknown flag word");
+                const bool isExp = flags[t] == FIBER_FLAG_EXP;
+                if (!setFiberRange(fiberIn, mesh.nT, (int)t, (int)t + 1, &dir[3 * t], false, k[t], isExp ? FIBER_LAW_EXP : FIBER_LAW_SPRING, k2[t], flags[t] == FIBER_FLAG_TENSION_ONLY,
+                        group[t], err))
+                    throw bad("element " + std::to_string(t) + ": " + err);
+                for (int r = 0; r < 3; ++r) {
+                    if (!(std::fabs(fiberIn.dir[r * nT + t] - dir[3 * t + r]) <= 4.0 * DBL_EPSILON)) throw bad("element " + std::to_string(t) + ": the direction is no unit vector");
+                    fiberIn.dir[r * nT + t] = dir[3 * t + r];
+                }
+                if (mesh.plastic.on() && mesh.plastic.plan.yield[t] < INFINITY) throw bad("element " + std::to_string(t) + " is plastic in this context");
+            }
+        }
     }
     if (in.bad()) throw StateError("read error on status file " + path);
     mesh.d_x.upload(x, stream);
@@ -1012,6 +1077,10 @@ void HipOptimizer::loadStatus(const std::string& path)
         HIP_CHECK(hipMemcpyAsync(mesh.plastic.d_alpha.p, plasticAlpha.data(), plasticAlpha.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     }
     HIP_CHECK(hipStreamSynchronize(stream));
+    if (fiberIn.nT) { // (a file without the section leaves the fibres untouched)
+        mesh.fiber.plan = std::move(fiberIn);
+        mesh.uploadFibers(stream);
+    }
     computeXTilta();
 }
 

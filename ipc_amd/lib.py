@@ -871,6 +871,56 @@ class Context:
     def aero_hessian_add(self, coef=1.0, projectDBC=True):
         self._codim_hessian_add("aero", coef, projectDBC)
 
+    # ---- fibre reinforcement and active contraction of tetrahedral elements (ipcgpu_set_fibers; ipc_amd/csrc/fiber_kernels.h)
+    FIBER_LAWS = {"spring": 0, "exp": 1}
+    FIBER_MAX_GROUPS = 64
+
+    def set_fibers(self, tet_range, direction, k, law="spring", k2=0.0, tension_only=False, group=0):
+        """elements [tet_range[0], tet_range[1]) get one fibre family along `direction` (3 numbers, or one row per element of the range; rest frame, normalised
+        by the call) with stiffness k (a stress; 0 removes the fibres).  law "spring": k (l - l0)^2 / 2 with l0 = 1 - activation of `group`, tension_only
+        switches it off for l <= l0; law "exp": k / (2 k2) (exp(k2 (l^2 - 1)^2) - 1) for l > 1.  Any time after set_mesh; later calls overwrite."""
+        d = _f64(np.asarray(direction, dtype=np.float64))
+        per = d.ndim == 2
+        if per and d.shape != (tet_range[1] - tet_range[0], 3) or not per and d.shape != (3,):
+            raise ValueError("direction: 3 numbers, or one row of 3 per element of the range")
+        self._chk(self._L.ipcgpu_set_fibers(self.h, C.c_int(tet_range[0]), C.c_int(tet_range[1]), _dp(d), C.c_int(int(per)), C.c_double(k),
+                                            C.c_int(self.FIBER_LAWS.get(law, law)), C.c_double(k2), C.c_int(int(tension_only)), C.c_int(group)))
+
+    def fiber_set_activation(self, group, act):
+        """the activation of one group: the spring fibres of it want the stretch 1 - act (act < 1; 0 is passive)"""
+        self._chk(self._L.ipcgpu_fiber_set_activation(self.h, C.c_int(group), C.c_double(act)))
+
+    def fiber_get(self):
+        """dict: n (fibred elements), k, k2, law, tensionOnly, group (nT each), dir (nT x 3, unit; zeros without a fibre), act (64)"""
+        nT = self.nT
+        n = C.c_int()
+        k, k2, d, act = np.zeros(nT), np.zeros(nT), np.zeros((nT, 3)), np.zeros(self.FIBER_MAX_GROUPS)
+        law, to, grp = np.zeros(nT, dtype=np.int32), np.zeros(nT, dtype=np.int32), np.zeros(nT, dtype=np.int32)
+        self._chk(self._L.ipcgpu_fiber_get(self.h, C.byref(n), _dp(k), _dp(k2), _ip(law), _ip(to), _ip(grp), _dp(d), _dp(act)))
+        return {"n": n.value, "k": k, "k2": k2, "law": law, "tensionOnly": to, "group": grp, "dir": d, "act": act}
+
+    def fiber_energy(self, coef=1.0):
+        return self._codim_energy("fiber", coef)
+
+    def fiber_energy_per_elem(self):
+        """W per element (nT; 0 without a fibre)"""
+        e = np.zeros(self.nT)
+        self._chk(self._L.ipcgpu_fiber_energy_per_elem(self.h, _dp(e)))
+        return e
+
+    def fiber_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * fibre gradient; returns it"""
+        return self._codim_gradient_add("fiber", coef, projectDBC, grad)
+
+    def fiber_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("fiber", coef, projectDBC)
+
+    def fiber_state(self, per_elem=True):
+        """(perElem nT x 5: stretch l, tension psi'(l), current direction t -- 1, 0 and 0 0 0 without a fibre; totals: min l, max l, sum of W).  Read-only."""
+        pe, tot = np.zeros((self.nT, 5), order="F"), np.zeros(3)
+        self._chk(self._L.ipcgpu_fiber_state(self.h, _dp(pe) if per_elem else None, _dp(tot)))
+        return (pe if per_elem else None), tot
+
     # ---- plastic flow of tetrahedral elements (ipcgpu_set_plasticity: yield, creep, isotropic hardening; ipc_amd/csrc/plastic_kernels.h)
     def set_plasticity(self, tet_range, yield_strain, creep=np.inf, harden=0.0):
         """elements [tet_range[0], tet_range[1]) yield where the deviatoric Hencky strain norm n exceeds yield_strain + harden alpha (for small strains the von

@@ -71,6 +71,12 @@ class Shape:
     # Hencky strain norm exceeds yield + K alpha (Context.set_plasticity; for small strains the von Mises stress is sqrt(6) mu n); creep: the rate at which the
     # excess decays (default inf: returned within the step), harden: isotropic hardening (default 0).  (yield, creep, harden), or None
     plastic: tuple = None
+    # `fiber <k> dir <x> <y> <z> [exp <k2>] [tensiononly] [activate <act> [ramp <seconds>]]` (this project's keyword, tetrahedral shapes only): one fibre family
+    # in the shape's elements (Context.set_fibers; ipc_amd/csrc/fiber_kernels.h).  k is a stress; dir is in the mesh file's frame and turns (and scales) with
+    # the shape line's transform; `exp <k2>` picks the exponential law (no activation with it), `tensiononly` lets spring fibres buckle; `activate` makes
+    # them want the stretch 1 - act, with `ramp` reached linearly over that many seconds (tools/run_scene.py sets act min(1, t / ramp) before each step).
+    # {k, dir, law, k2, tension_only, act, ramp}, or None
+    fiber: dict = None
     shell_alpha: float = 0.0
     # `rod <radius> [bend <scale>]` (this project's keyword, `.seg` shapes only): the component is an elastic rod -- stretching and bending energy with the
     # shape's `material` or the scene's density / stiffness (Context.set_rod; Poisson's ratio is unused) -- and may be free or partly held by `DBC` boxes
@@ -516,6 +522,42 @@ def _parse_shape(st, resolve):
             if not (par["yield"] >= 0.0 and par["creep"] > 0.0 and 0.0 <= par["harden"] < math.inf):
                 raise ValueError("plastic needs a yield strain >= 0, a creep rate > 0 and a finite hardening modulus >= 0")
             sh.plastic = (par["yield"], par["creep"], par["harden"])
+        elif e == "fiber":
+            if j + 4 >= len(st) or st[j + 1] != "dir":
+                raise ValueError("fiber needs <k> dir <x> <y> <z>")
+            fb = {"k": float(st[j]), "dir": tuple(float(x) for x in st[j + 2:j + 5]), "law": "spring", "k2": 0.0, "tension_only": False, "act": 0.0, "ramp": 0.0}
+            j += 5
+            while j < len(st) and st[j] in ("exp", "tensiononly", "activate"):
+                if st[j] == "tensiononly":
+                    fb["tension_only"] = True
+                    j += 1
+                    continue
+                if j + 1 >= len(st):
+                    raise ValueError(st[j] + " needs a number")
+                if st[j] == "exp":
+                    fb["law"], fb["k2"] = "exp", float(st[j + 1])
+                    j += 2
+                else:
+                    fb["act"] = float(st[j + 1])
+                    j += 2
+                    if j < len(st) and st[j] == "ramp":
+                        if j + 1 >= len(st):
+                            raise ValueError("ramp needs a time")
+                        fb["ramp"] = float(st[j + 1])
+                        j += 2
+                        if not (0.0 < fb["ramp"] < math.inf):
+                            raise ValueError("ramp needs a positive, finite time")
+            if not (0.0 < fb["k"] < math.inf):
+                raise ValueError("fiber needs a positive, finite stiffness")
+            if not all(math.isfinite(x) for x in fb["dir"]) or not any(x != 0.0 for x in fb["dir"]):
+                raise ValueError("fiber needs a finite direction that is not zero")
+            if fb["law"] == "exp" and not (0.0 < fb["k2"] < math.inf):
+                raise ValueError("exp needs a positive, finite k2")
+            if not (math.isfinite(fb["act"]) and fb["act"] < 1.0):
+                raise ValueError("activate needs an activation below 1")
+            if fb["law"] == "exp" and fb["act"] != 0.0:
+                raise ValueError("activate is not defined for exp fibres")
+            sh.fiber = fb
         elif e == "shell":
             if j >= len(st):
                 raise ValueError("shell needs a thickness")
@@ -654,6 +696,10 @@ def _parse_shape(st, resolve):
         raise ValueError("rod is valid on a segment shape only (not on a tetrahedral, triangle-mesh or point shape)")
     if sh.plastic is not None and os.path.splitext(sh.path.lower())[1] in (".obj", ".seg", ".pt"):
         raise ValueError("plastic is valid on a tetrahedral shape only (not on a shell, rod, point or surface-only shape)")
+    if sh.fiber is not None and os.path.splitext(sh.path.lower())[1] in (".obj", ".seg", ".pt"):
+        raise ValueError("fiber is valid on a tetrahedral shape only (not on a shell, rod, point or surface-only shape)")
+    if sh.fiber is not None and sh.plastic is not None:
+        raise ValueError("fiber and plastic exclude each other on a shape (the rest shape would flow under the fibre direction)")
     if sh.aero:
         ext = os.path.splitext(sh.path.lower())[1]
         if ext in (".seg", ".pt") or (ext == ".obj" and sh.shell_thickness is None):
@@ -767,6 +813,17 @@ class AssembledScene:
     # one_sided (per surface)}, or None.  Set by assemble(); a plain attribute, not a field, so that the fields of a scene without the keyword are what
     # they were.  The wind itself is the scene's (cfg.wind, cfg.air_density)
     aero = None
+    # the shapes that carry `fiber`, in script order, as Context.set_fibers takes them: a list of {tet_range, dir (turned and scaled with the shape), k, law,
+    # k2, tension_only, group (the index in this list), act, ramp}, or None.  A plain attribute like `aero`
+    fibers = None
+
+    def fiber_activations(self, t):
+        """(group, activation) of every `fiber ... activate <act> ramp <seconds>` shape for the time step that ends at time t: act min(1, t / ramp); None when
+        no shape has a ramp (then the activations set by apply() stay)"""
+        q = [f for f in (self.fibers or []) if f["ramp"] > 0.0]
+        if not q:
+            return None
+        return [(f["group"], f["act"] * min(1.0, t / f["ramp"])) for f in q]
 
     def move_round_colliders(self, be):
         """Before a time step: every `sphereCollider` / `capsuleCollider` with a `velocity` moves by v dt through Context.round_move; the fraction a
@@ -998,6 +1055,21 @@ def _add_mesh_obstacles(cfg, p):
     return obstacles
 
 
+def _fiber_payload(cfg, tet_ranges):
+    """the `fiber` keywords of the shapes as SceneData.fibers holds them: the direction follows the shape line's transform R (p * scale), as a material
+    line of the mesh file does; one activation group per fibred shape"""
+    out = []
+    for s, sh in enumerate(cfg.shapes):
+        if sh.fiber is None or tet_ranges[s + 1] <= tet_ranges[s]:
+            continue
+        if len(out) >= 64:
+            raise ValueError("fiber: at most 64 shapes may carry fibres (one activation group each)")
+        d = _rot(sh.rotate_deg) @ (np.asarray(sh.fiber["dir"], dtype=np.float64) * sh.scale)
+        out.append({"tet_range": (tet_ranges[s], tet_ranges[s + 1]), "dir": d / np.linalg.norm(d), "k": sh.fiber["k"], "law": sh.fiber["law"], "k2": sh.fiber["k2"],
+                    "tension_only": sh.fiber["tension_only"], "group": len(out), "act": sh.fiber["act"], "ramp": sh.fiber["ramp"]})
+    return out or None
+
+
 def _start_positions(cfg, V, nSim):
     """`rotateModel` and `size` on the simulated mesh V[:nSim] (in place) -> the start positions where they differ from the rest shape, else None"""
     V0 = None
@@ -1114,6 +1186,9 @@ def assemble(cfg, read_mesh):
     sc.shell, sc.rod, sc.attachments, sc.chambers, aero = _codim_payloads(p, attachments, V)
     if aero is not None:
         sc.aero = aero
+    fibers = _fiber_payload(cfg, sc.tet_ranges)
+    if fibers is not None:
+        sc.fibers = fibers
     for q in st.seqs:  # the group a sequence drives = the entry of `dirichlet` that holds its nodes
         q["group"] = next(g for g, d in enumerate(st.dirichlet) if d[0] is q["ids"])
     sc.mesh_seqs = st.seqs
@@ -1163,6 +1238,10 @@ def apply(sc, be):
     for s, sh in enumerate(cfg.shapes):  # per component, behind the materials
         if sh.plastic is not None and sc.tet_ranges[s + 1] > sc.tet_ranges[s]:
             be.set_plasticity((sc.tet_ranges[s], sc.tet_ranges[s + 1]), *sh.plastic)
+    for f in sc.fibers or []:  # per component, behind the materials; a ramped activation starts at 0 (tools/run_scene.py raises it before each step)
+        be.set_fibers(f["tet_range"], f["dir"], f["k"], law=f["law"], k2=f["k2"], tension_only=f["tension_only"], group=f["group"])
+        if f["act"] != 0.0 and not f["ramp"] > 0.0:
+            be.fiber_set_activation(f["group"], f["act"])
     if sc.V0 is not None:
         be.set_positions(sc.V0)
     be.opt_init(cfg.dt, cfg.gravity)
@@ -1290,7 +1369,7 @@ class ContactReportWriter:
 
 class FieldsWriter:
     """`fields<N>.vtu` files in `folder` (tools/run_scene.py --fields): an ASCII VTK unstructured grid of the tetrahedra at the state the backend holds.
-    Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()` -- and, only when a shape carries `plastic`, `plasticStrain` (the accumulated plastic strain alpha).  Point data: the nodal
+    Cell data: `stress` (Cauchy, six components XX YY ZZ XY YZ XZ), `von_mises`, `J` -- the element records of `elastic_stress()` -- and, only when a shape carries `plastic`, `plasticStrain` (the accumulated plastic strain alpha); only when a shape carries `fiber`, `fiberStretch` (l; 1 without a fibre) and `fiberDir` (the current direction t; 0 0 0 without one).  Point data: the nodal
     `stress` (rest-volume-weighted mean of the incident elements), `von_mises` of that mean, `velocity`; with self-contact on, `contact_force` -- minus the
     barrier gradient of the constraint set rebuilt at these positions with the step's dHat and kappa, Dirichlet rows kept -- and, when the lagged friction
     set is not empty, `friction_force` -- minus the lagged friction gradient of the step from `x_prev` to here.  The reference writes no such file.
@@ -1312,6 +1391,9 @@ class FieldsWriter:
         point = {"stress": node[:, :6], "von_mises": node[:, 6], "velocity": be.kinematics()["velocity"].reshape(nV, 3)}
         if any(sh.plastic is not None for sh in self.sc.cfg.shapes):  # the accumulated plastic strain, only where a shape is plastic: other files are what they were
             cell["plasticStrain"] = be.plastic_get()["alpha"]
+        if self.sc.fibers:  # the fibre stretch and the current fibre direction, only where a shape carries `fiber`: other files are what they were
+            fs = be.fiber_state()[0]
+            cell["fiberStretch"], cell["fiberDir"] = fs[:, 0], fs[:, 2:5]
         if self.contact:
             fs = be.friction_state()  # (the lagged set first: rebuilding the constraint set below is not to touch what it is read from)
             fric = np.zeros((nV, 3))

@@ -3,7 +3,7 @@ usage: python tools/run_scene.py <scene.txt> [--root DIR] [--steps N] [--status-
 `--root` is the directory the script's relative mesh paths are resolved against (the reference resolves them against its
 repository root).  `--precond` chooses the preconditioner of a `linearSolver AMGCL` scene (0 block Jacobi, the default; 1 lagged Cholesky; 2 two-level).  `--report DIR` writes the reference's system report, `DIR/sysE.txt`, `sysM.txt` and `sysL.txt`: energy, linear and angular momentum per mesh component, one line
 after precompute() and one per time step (17 significant digits).  `--fields DIR` writes `DIR/fields<N>.vtu` after every K-th time step (K = 1 unless
-`--fields-every` says otherwise): an ASCII VTK unstructured grid with the Cauchy stress, von Mises stress and J per element (and the accumulated plastic strain `plasticStrain` when a shape carries `plastic`), the nodal mean stress, its von
+`--fields-every` says otherwise): an ASCII VTK unstructured grid with the Cauchy stress, von Mises stress and J per element (and the accumulated plastic strain `plasticStrain` when a shape carries `plastic`, the fibre stretch `fiberStretch` and direction `fiberDir` when one carries `fiber`), the nodal mean stress, its von
 Mises stress and the velocity per node, and -- when the scene has contact -- the contact and friction forces per node (ipc_amd/scene_script.py FieldsWriter).
 `--contact-report DIR` writes `DIR/contact.txt`: after every time step one line per pair of components (or component and half-space) in contact -- smallest
 squared distance, constraint counts by kind, barrier forces and torques on either side, friction forces and work (ipc_amd/scene_script.py
@@ -60,6 +60,8 @@ for step in range(steps):
     ramped = sc.chamber_pressures((step + 1) * cfg.dt)  # `pressure <p> ramp <seconds>`: p min(1, t / ramp) at the time this step ends; None without a ramp
     if ramped is not None:
         c.chamber_set_pressure(ramped)
+    for group, act in sc.fiber_activations((step + 1) * cfg.dt) or ():  # `fiber ... activate <act> ramp <seconds>`: act min(1, t / ramp) at the time this step ends
+        c.fiber_set_activation(group, act)
     writes_fields = fields is not None and (timestep + 1) % max(args.fields_every, 1) == 0
     x_prev = c.get_positions() if writes_fields or contact_report else None  # the friction field / columns need the positions the step started from
     it = c.solve_timestep(1000)

@@ -429,6 +429,45 @@ int ipcgpu_shell_rubber_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_shell_rubber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_shell_rubber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 int ipcgpu_shell_thickness(ipcgpu_ctx*, double* h_nTri);
+/* ---- Plastic flow of the shell: permanent stretch, creases and dents.  No counterpart in the reference (it has no shell and no plasticity).  The model is
+ * stated in ipc_amd/csrc/shell_plastic_kernels.h.  Every shell kernel reads the rest shape of a triangle from B = Dm^-1 (rows 0-3 of its constants) and of a
+ * hinge from thetaBar, so at the end of every time step (after the BE / Newmark update, before the lagged damping matrix) two kernels rewrite those records:
+ *   membrane, per triangle with a finite yield: C = F^T F = V diag(l1, l2) V^T, skipped and counted where l2 <= 0; e_i = ln(l_i) / 2, e3 = -nu / (1 - nu)
+ *     (e1 + e2), n = |dev(e1, e2, e3)|; y = yield + harden alpha; where n > y: Delta = -expm1(-creep dt) (n - y) / (1 + harden), B <- B V diag(exp(-Delta e_i
+ *     / n)) V^T, alpha += Delta.  h A mu, h A lambda_ps, masses and the strain-limit scale do not change (the thickness takes up det G).  For small strains
+ *     the von Mises stress is sqrt(6) mu n, as for the tetrahedra.
+ *   hinges, per hinge whose two triangles both have a finite bendYield (its parameters are the means of theirs): eps = g |theta - thetaBar|, g = h_m w_e /
+ *     (2 |eBar|), skipped and counted where n1, n2 or e has zero length; where eps > y = bendYield + harden alphaB: Delta as above, thetaBar += sign(theta -
+ *     thetaBar) Delta / g, alphaB += Delta.
+ * ipcgpu_shell_set_plasticity (no counterpart in the reference): triangles [triBegin, triEnd) get (yield, bendYield, creep, harden); later calls overwrite.
+ *   yield, bendYield >= 0 or +inf (+inf switches that flow off), creep > 0 or +inf (+inf: the rate-independent return), harden >= 0 and finite, nothing NaN,
+ *   0 <= triBegin <= triEnd <= nTri: IPCGPU_ERR_ARG otherwise, and nothing is changed.  Without a shell: IPCGPU_ERR_STATE.  Touches neither the pattern nor
+ *   the masses: allowed before or after ipcgpu_opt_init, between time steps.  The first call keeps copies B0 and thetaBar0 of the current records.  With
+ *   nothing switched on the stepper launches nothing and every result is bit-identical to a context that never called this.  IPCGPU_ERR_UNSUPPORTED on a
+ *   rubber triangle (ipcgpu_shell_set_membrane on a plastic triangle returns the same) and on a sharded context (ipcgpu_ctx_set_shard with world > 1 on a
+ *   context with a plastic shell returns the same).  ipcgpu_set_shell and ipcgpu_set_mesh drop parameters and history.  ipcgpu_shell_set_membrane keeps a
+ *   flowed B.  ipcgpu_shell_get keeps returning the plan's rest angle; the current thetaBar comes from the calls below.
+ * ipcgpu_shell_plastic_get (no counterpart): yield, bendYield, creep, harden, alpha per triangle; triConst_nTrix6 column-major, the CURRENT six constants of
+ *   every triangle as the kernels read them (B in columns 0-3, h A mu, h A lambda_ps); B0_nTrix4 column-major; hinge_nHingex4 column-major: mean bendYield
+ *   (+inf: the hinge does not flow), mean creep, mean harden, g; alphaB, the CURRENT thetaBar and thetaBar0 per hinge.  Any pointer may be NULL.
+ * ipcgpu_shell_plastic_update (no counterpart): ONE flow of both kinds at the held positions with the given dt, outside the stepper -- the kernels' test
+ *   entry, like the *_hessian_add calls.  counts4 (nullable): triangles rewritten, triangles skipped, hinges rewritten, hinges skipped.
+ * ipcgpu_shell_plastic_state (no counterpart): read-only.  perTri (nullable, column-major nTri x 4): n, the current y, alpha, the rest-area ratio det B0 /
+ *   det B; n = NaN for a triangle the flow would skip, y = +inf where the membrane flow is off.  perHinge (nullable, column-major nHinge x 4): eps, the
+ *   current y, alphaB, thetaBar - thetaBar0.  totals7 (nullable): counts4 of the last flow, max alpha, max alphaB, sum of h A alpha.  Deterministic: fixed
+ *   summation order, no floating-point atomics.
+ * ipcgpu_shell_plastic_set_state (no counterpart): B (nTri x 4 column-major), alpha, thetaBar, alphaB from the caller (any may be NULL); needs
+ *   ipcgpu_shell_set_plasticity first.  ipcgpu_shell_plastic_reset (no counterpart): B = B0, thetaBar = thetaBar0, alpha = alphaB = 0.
+ * ipcgpu_opt_save_status appends a section `shellplastic <nTri> 5 <nHinge> 2` (B and alpha per triangle, then thetaBar and alphaB per hinge) when something
+ * is plastic -- the file is otherwise byte for byte what it was; ipcgpu_opt_load_status reads it (a file without it leaves the records untouched; a
+ * truncated section is refused with a message that names it). */
+int ipcgpu_shell_set_plasticity(ipcgpu_ctx*, int triBegin, int triEnd, double yield, double bendYield, double creep, double harden);
+int ipcgpu_shell_plastic_get(ipcgpu_ctx*, double* yield_nTri, double* bendYield_nTri, double* creep_nTri, double* harden_nTri, double* alpha_nTri,
+    double* triConst_nTrix6, double* B0_nTrix4, double* hinge_nHingex4, double* alphaB_nHinge, double* thetaBar_nHinge, double* thetaBar0_nHinge);
+int ipcgpu_shell_plastic_update(ipcgpu_ctx*, double dt, int* counts4);
+int ipcgpu_shell_plastic_state(ipcgpu_ctx*, double* perTri_nTrix4, double* perHinge_nHingex4, double* totals7);
+int ipcgpu_shell_plastic_set_state(ipcgpu_ctx*, const double* B_nTrix4, const double* alpha_nTri, const double* thetaBar_nHinge, const double* alphaB_nHinge);
+int ipcgpu_shell_plastic_reset(ipcgpu_ctx*);
 /* Elastic rods (no counterpart in the reference): stretching and bending energy on segment components.
  *   stretching  per segment (a, b): rest length L, length l, radius r, Young's modulus E, A = pi r^2, k_s = E A / L, W_s = k_s (l - L)^2 / 2.  Exact gradient.
  *               With t = (x_b - x_a) / l the 3 x 3 block is B = k_s [t t^T + max(0, 1 - L / l) (I - t t^T)], the 6 x 6 Hessian [[B, -B], [-B, B]]: the clamp

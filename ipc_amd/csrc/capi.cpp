@@ -277,6 +277,7 @@ int ipcgpu_ctx_set_shard(ipcgpu_ctx* c, int rank, int world)
         if (world > 1 && c->mesh->aero.n()) throw UnsupportedError("aerodynamic surfaces on a sharded context");
         if (world > 1 && !c->opt->rounds.empty()) throw UnsupportedError("round colliders on a sharded context");
         if (world > 1 && c->mesh->plastic.on()) throw UnsupportedError("plasticity on a sharded context");
+        if (world > 1 && c->mesh->shell.plastic.on()) throw UnsupportedError("shell plasticity on a sharded context");
         if (world > 1 && c->mesh->fiber.n()) throw UnsupportedError("fibres on a sharded context");
         c->rank = rank;
         c->worldSize = world;
@@ -1209,6 +1210,167 @@ int ipcgpu_shell_thickness(ipcgpu_ctx* c, double* h)
         std::vector<double> sigma(2 * (size_t)sh.nTri());
         o.shellStretch(sigma.data(), nullptr, nullptr);
         for (int t : sh.rubber.tri) h[t] = sh.plan.thickness[(size_t)t] / (sigma[2 * (size_t)t] * sigma[2 * (size_t)t + 1]); // incompressible: lambda_3 = 1 / (sigma1 sigma2)
+        return IPCGPU_OK;
+    });
+}
+// ---- Plastic flow of the shells (shell_plastic_kernels.h; the reference has no counterpart) ------------------------------------------------------
+int ipcgpu_shell_set_plasticity(ipcgpu_ctx* c, int triBegin, int triEnd, double yield, double bendYield, double creep, double harden)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        if (c->worldSize > 1) throw UnsupportedError("shell plasticity on a sharded context"); // (first: a sharded context cannot hold a shell at all)
+        need(m.shell.nTri() > 0, "shell_set_plasticity: no shell is set (call ipcgpu_set_shell first)");
+        m.setShellPlasticity(triBegin, triEnd, yield, bendYield, creep, harden, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_plastic_get(ipcgpu_ctx* c, double* yield, double* bendYield, double* creep, double* harden, double* alpha, double* triConst, double* B0,
+    double* hingePar, double* alphaB, double* thetaBar, double* thetaBar0)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        const HipShell& sh = m.shell;
+        const HipShellPlastic& h = sh.plastic;
+        const size_t nTri = (size_t)sh.nTri(), nH = (size_t)sh.nHinge();
+        if (!nTri) return IPCGPU_OK;
+        if (triConst) sh.d_triConst.download(triConst, 6 * nTri, c->stream);
+        if (thetaBar) sh.d_hingeConst.download(thetaBar, nH, c->stream);
+        if (!h.allocated()) { // never set: everything elastic, no history, the rest records are the device's own
+            for (size_t t = 0; t < nTri; ++t) {
+                if (yield) yield[t] = INFINITY;
+                if (bendYield) bendYield[t] = INFINITY;
+                if (creep) creep[t] = INFINITY;
+                if (harden) harden[t] = 0.0;
+                if (alpha) alpha[t] = 0.0;
+            }
+            if (B0) sh.d_triConst.download(B0, 4 * nTri, c->stream);
+            if (thetaBar0) sh.d_hingeConst.download(thetaBar0, nH, c->stream);
+            for (size_t i = 0; i < nH; ++i) {
+                if (hingePar) {
+                    hingePar[i] = hingePar[nH + i] = INFINITY;
+                    hingePar[2 * nH + i] = 0.0;
+                    hingePar[3 * nH + i] = NAN; // (g is computed with the plan)
+                }
+                if (alphaB) alphaB[i] = 0.0;
+            }
+            return IPCGPU_OK;
+        }
+        if (yield) std::memcpy(yield, h.plan.yield.data(), sizeof(double) * nTri);
+        if (bendYield) std::memcpy(bendYield, h.plan.bendYield.data(), sizeof(double) * nTri);
+        if (creep) std::memcpy(creep, h.plan.creep.data(), sizeof(double) * nTri);
+        if (harden) std::memcpy(harden, h.plan.harden.data(), sizeof(double) * nTri);
+        if (alpha) h.d_alpha.download(alpha, nTri, c->stream);
+        if (B0) h.d_B0.download(B0, 4 * nTri, c->stream);
+        if (hingePar && nH) {
+            std::memcpy(hingePar, h.plan.hingeYield.data(), sizeof(double) * nH);
+            std::memcpy(hingePar + nH, h.plan.hingeCreep.data(), sizeof(double) * nH);
+            std::memcpy(hingePar + 2 * nH, h.plan.hingeHarden.data(), sizeof(double) * nH);
+            std::memcpy(hingePar + 3 * nH, h.plan.hingeG.data(), sizeof(double) * nH);
+        }
+        if (alphaB) h.d_alphaB.download(alphaB, nH, c->stream);
+        if (thetaBar0) h.d_thetaBar0.download(thetaBar0, nH, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_plastic_update(ipcgpu_ctx* c, double dt, int* counts4)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        needArg(dt > 0.0 && std::isfinite(dt), "shell_plastic_update: the time step must be positive and finite");
+        int cnt[SPC_COUNT] = { 0, 0, 0, 0 };
+        if (m.shell.plastic.on()) {
+            c->opt->shellPlasticFlow(m.d_x.p, dt);
+            HIP_CHECK(hipGetLastError());
+            m.shell.plastic.d_count.download(cnt, SPC_COUNT, c->stream);
+        }
+        if (counts4) std::copy(cnt, cnt + SPC_COUNT, counts4);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_plastic_state(ipcgpu_ctx* c, double* perTri, double* perHinge, double* totals7)
+{
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        HipShell& sh = m.shell;
+        HipShellPlastic& h = sh.plastic;
+        const size_t nTri = (size_t)sh.nTri(), nH = (size_t)sh.nHinge();
+        if (totals7) std::fill(totals7, totals7 + 7, 0.0);
+        if (!h.allocated()) {
+            for (size_t t = 0; t < nTri && perTri; ++t) {
+                perTri[t] = NAN; // (n is not evaluated without the state arrays)
+                perTri[nTri + t] = INFINITY;
+                perTri[2 * nTri + t] = 0.0;
+                perTri[3 * nTri + t] = 1.0;
+            }
+            for (size_t i = 0; i < nH && perHinge; ++i) {
+                perHinge[i] = NAN;
+                perHinge[nH + i] = INFINITY;
+                perHinge[2 * nH + i] = perHinge[3 * nH + i] = 0.0;
+            }
+            return IPCGPU_OK;
+        }
+        if (!perTri && !perHinge && !totals7) return IPCGPU_OK;
+        const ShellPlasticView v = c->opt->shellPlasticView(m.d_x.p, 1.0);
+        if (perTri) h.d_stateTri.ensure(4 * nTri);
+        if (perHinge) h.d_stateHinge.ensure(4 * nH);
+        h.d_partial.ensure(SPT_COUNT * (size_t)shell_plastic_state_blocks(v));
+        launch_shell_plastic_state(v, perTri ? h.d_stateTri.p : nullptr, perHinge && nH ? h.d_stateHinge.p : nullptr, h.d_partial.p, totals7 ? h.d_totals.p : nullptr, c->stream);
+        HIP_CHECK(hipGetLastError());
+        if (perTri) h.d_stateTri.download(perTri, 4 * nTri, c->stream);
+        if (perHinge) h.d_stateHinge.download(perHinge, 4 * nH, c->stream);
+        if (totals7) {
+            int cnt[SPC_COUNT];
+            double tot[SPT_COUNT];
+            h.d_count.download(cnt, SPC_COUNT, c->stream);
+            h.d_totals.download(tot, SPT_COUNT, c->stream);
+            for (int k = 0; k < SPC_COUNT; ++k) totals7[k] = cnt[k];
+            for (int k = 0; k < SPT_COUNT; ++k) totals7[SPC_COUNT + k] = tot[k];
+        }
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_plastic_set_state(ipcgpu_ctx* c, const double* B, const double* alpha, const double* thetaBar, const double* alphaB)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        HipShell& sh = m.shell;
+        need(sh.plastic.allocated(), "call ipcgpu_shell_set_plasticity first");
+        const size_t nTri = (size_t)sh.nTri(), nH = (size_t)sh.nHinge();
+        for (size_t t = 0; t < nTri && alpha; ++t) needArg(alpha[t] >= 0.0 && std::isfinite(alpha[t]), "shell_plastic_set_state: the accumulated plastic strain must be finite and not negative");
+        for (size_t i = 0; i < nH && alphaB; ++i) needArg(alphaB[i] >= 0.0 && std::isfinite(alphaB[i]), "shell_plastic_set_state: the accumulated plastic strain must be finite and not negative");
+        for (size_t k = 0; k < 4 * nTri && B; ++k) needArg(std::isfinite(B[k]), "shell_plastic_set_state: B is not finite");
+        for (size_t i = 0; i < nH && thetaBar; ++i) needArg(std::isfinite(thetaBar[i]), "shell_plastic_set_state: thetaBar is not finite");
+        if (B) HIP_CHECK(hipMemcpyAsync(sh.d_triConst.p, B, 4 * nTri * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (alpha) HIP_CHECK(hipMemcpyAsync(sh.plastic.d_alpha.p, alpha, nTri * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (thetaBar && nH) HIP_CHECK(hipMemcpyAsync(sh.d_hingeConst.p, thetaBar, nH * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (alphaB && nH) HIP_CHECK(hipMemcpyAsync(sh.plastic.d_alphaB.p, alphaB, nH * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_plastic_reset(ipcgpu_ctx* c)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        HipShell& sh = m.shell;
+        if (!sh.plastic.allocated()) return IPCGPU_OK; // no history to forget
+        const size_t nTri = (size_t)sh.nTri(), nH = (size_t)sh.nHinge();
+        HIP_CHECK(hipMemcpyAsync(sh.d_triConst.p, sh.plastic.d_B0.p, 4 * nTri * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (nH) HIP_CHECK(hipMemcpyAsync(sh.d_hingeConst.p, sh.plastic.d_thetaBar0.p, nH * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        sh.plastic.d_alpha.zero(c->stream);
+        sh.plastic.d_alphaB.zero(c->stream);
+        sh.plastic.d_count.zero(c->stream);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
         return IPCGPU_OK;
     });
 }

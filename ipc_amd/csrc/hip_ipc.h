@@ -35,6 +35,8 @@
 #include "shell_limit_kernels.h"
 #include "shell_limit_plan.h"
 #include "shell_plan.h"
+#include "shell_plastic_kernels.h"
+#include "shell_plastic_plan.h"
 #include "shell_rubber_kernels.h"
 #include "shell_rubber_plan.h"
 #include "stress_plan.h"
@@ -47,6 +49,22 @@ typedef int (*ipcgpu_allreduce_fn_t)(void* user, void* buf_dev, long long count,
 typedef int (*ipcgpu_allreduce_stream_fn_t)(void* user, void* buf_dev, long long count, int op, void* hipStream);
 
 namespace ipcgpu {
+
+// Plastic flow of the shell (ipcgpu_shell_set_plasticity; shell_plastic_kernels.h): the host plan and the device state.  plan.nTri == 0: never set, and then
+// nothing below is allocated or read.  on(): some triangle has a finite yield strain or some hinge flows -- only then does the stepper launch a flow and
+// does saveStatus write the section.  While allocated, rows 0-3 of d_triConst and row 0 of d_hingeConst (HipShell) are the truth about the rest shape.
+struct HipShellPlastic {
+    ShellPlasticPlan plan;
+    DevBuf<double> d_yield, d_creep, d_harden, d_alpha; // nTri
+    DevBuf<double> d_hYield, d_hCreep, d_hHarden, d_hG, d_alphaB; // nHinge
+    DevBuf<double> d_hA; // nTri rest volumes h A
+    DevBuf<double> d_B0, d_thetaBar0; // SoA [4][nTri], nHinge: the records as they were at the first call (ipcgpu_shell_plastic_reset puts them back)
+    DevBuf<int> d_count; // SPC_COUNT (scalar_slots.h)
+    DevBuf<double> d_totals, d_partial, d_stateTri, d_stateHinge; // SPT_COUNT; ipcgpu_shell_plastic_state's scratch
+    bool allocated() const { return plan.nTri > 0; }
+    bool on() const { return plan.nOn > 0 || plan.nHingeOn > 0; }
+    void drop() { plan = ShellPlasticPlan(); }
+};
 
 // Elastic shell of the mesh (ipcgpu_set_shell): the host plan and its device copy.  nTri() == 0: no shell, and then nothing below is ever read.
 struct HipShell {
@@ -76,6 +94,7 @@ struct HipShell {
     DevBuf<double> d_rubConst, d_rubCount;
     bool rubberUnchecked = false;
     int nRubber() const { return rubber.nRubber; }
+    HipShellPlastic plastic; // (its own struct above)
 };
 
 // Elastic rod of the mesh (ipcgpu_set_rod): the host plan and its device copy.  nSeg() == 0: no rod, and then nothing below is ever read.
@@ -212,6 +231,11 @@ public:
     // shell's triConst with the StVK constants of those triangles zeroed (the plan's own where none is rubber).  All models zero (or null) removes the term;
     // setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair (the blocks are the membrane's).
     void setShellMembrane(const int* model, const double* alpha, hipStream_t s);
+    // Plastic flow of the shell (shell_plastic_plan.h): validates, uploads the parameter arrays; the first call allocates alpha = alphaB = 0 and keeps the
+    // copies B0 and thetaBar0 of the device records.  Touches no mass, no neighbour pair and no pattern; setShell and computeFeatures drop it.
+    void setShellPlasticity(int triBegin, int triEnd, double yield, double bendYield, double creep, double harden, hipStream_t s);
+    void ensureShellPlastic(hipStream_t s); // the state arrays with everything elastic, unless they exist (loadStatus of a file with a shellplastic section)
+    void uploadShellPlasticParams(hipStream_t s);
     // Elastic rod on segment components (rod_plan.h): as setShell -- validates, sets the lumped masses of the rod nodes, marks them as element nodes, adds
     // the plan's node pairs to vNeighbor and uploads the constants.  nSeg = 0 removes the rod, a second call replaces it: the nodes of the old rod get back
     // the masses they had before it and lose the mark; the neighbour pairs stay.  With neither a tetrahedron nor a shell in the mesh avgEdgeLen is the mean
@@ -438,6 +462,8 @@ public:
     AeroView aeroView(const double* x_dev) const; // (with the wind, the density and dt as they are now)
     PlasticView plasticView(const double* x_dev, double dt_) const;
     void plasticFlow(const double* x_dev, double dt_); // zeroes the two counters and launches one flow on the stream: no synchronisation
+    ShellPlasticView shellPlasticView(const double* x_dev, double dt_) const;
+    void shellPlasticFlow(const double* x_dev, double dt_); // zeroes the four counters and launches the flows that are on: no synchronisation
     void refreshAeroLagged(); // n, A and c^n of every aerodynamic triangle from the current positions, on the device (beginTimestep)
     // The gas chambers' dense rank-k Hessian term, coef sum_c beta_c u_c u_c^T, as a correction around the solver's retained factor (chamber_kernels.h):
     // y_dev holds A^-1 r on entry and (A + coef sum beta_c u_c u_c^T)^-1 r on return, with beta and u at the mesh's current positions.  k further solves,

@@ -35,6 +35,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
     shell.limit = ShellLimitPlan(); // ... and its strain limit with it
     shell.rubber = ShellRubberPlan(); // ... and its rubber membrane
+    shell.plastic.drop(); // ... and its plastic parameters and history
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
     if (chamber.n()) chamber.plan = ChamberPlan(); // ... and the pressure chambers
@@ -213,6 +214,7 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     shell.plan = std::move(plan);
     shell.limit = ShellLimitPlan(); // a strain limit belongs to the shell it was set on
     shell.rubber = ShellRubberPlan(); // ... and so does a rubber membrane (d_triConst below is the new plan's own)
+    shell.plastic.drop(); // ... and the plastic parameters and history (d_triConst and d_hingeConst below are the new plan's own)
     shell.bendScale = bendScale;
     const ShellPlan& p = shell.plan;
     d_mass.upload(mass, s);
@@ -256,15 +258,73 @@ void HipMesh::setShellMembrane(const int* model, const double* alpha, hipStream_
     std::string err;
     if (!buildShellRubberPlan(shell.nTri(), model, alpha, shell.plan.membraneK.data(), plan, err)) throw ArgError(err);
     if (!plan.nRubber && !shell.rubber.nRubber) return; // StVK before and after: nothing is touched
+    for (int t : plan.tri) // (shell_plastic_kernels.h: rows 4 and 5 of a rubber triangle are zero, its strain norm has no meaning)
+        if (shellPlasticTriOn(shell.plastic.plan, t)) throw UnsupportedError("shell_set_membrane: rubber on a plastic triangle (triangle " + std::to_string(t) + ")");
     shell.rubber = std::move(plan);
     shell.rubberUnchecked = shell.rubber.nRubber > 0;
-    const std::vector<double> triConst = shellTriConstWithoutRubber(shell.plan.triConst, shell.rubber); // (the plan's own once the last rubber triangle is gone)
+    std::vector<double> triConst = shellTriConstWithoutRubber(shell.plan.triConst, shell.rubber); // (the plan's own once the last rubber triangle is gone)
+    if (shell.plastic.allocated()) // rows 0-3 on the device may have flowed: they stay what they are, rows 4-5 alone are new
+        shell.d_triConst.download(triConst.data(), 4 * (size_t)shell.nTri(), s);
     shell.d_triConst.upload(triConst, s);
     if (shell.rubber.nRubber) {
         shell.d_rubTri.upload(shell.rubber.tri, s);
         shell.d_rubConst.upload(shell.rubber.rubConst, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::uploadShellPlasticParams(hipStream_t s)
+{
+    HipShellPlastic& h = shell.plastic;
+    h.d_yield.upload(h.plan.yield, s);
+    h.d_creep.upload(h.plan.creep, s);
+    h.d_harden.upload(h.plan.harden, s);
+    h.d_hYield.upload(h.plan.hingeYield, s);
+    h.d_hCreep.upload(h.plan.hingeCreep, s);
+    h.d_hHarden.upload(h.plan.hingeHarden, s);
+    h.d_hG.upload(h.plan.hingeG, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::ensureShellPlastic(hipStream_t s)
+{
+    HipShellPlastic& h = shell.plastic;
+    if (h.allocated()) return;
+    if (!shell.nTri()) throw StateError("shell_set_plasticity: no shell is set (call ipcgpu_set_shell first)");
+    std::string err;
+    if (!setShellPlasticRange(h.plan, shell.plan, nV, V_rest.data(), nullptr, 0, 0, INFINITY, INFINITY, INFINITY, 0.0, err)) throw ArgError(err); // everything elastic
+    const size_t nTri = (size_t)shell.nTri(), nH = (size_t)shell.nHinge();
+    uploadShellPlasticParams(s);
+    std::vector<double> hA(nTri);
+    for (size_t t = 0; t < nTri; ++t) hA[t] = shell.plan.thickness[t] * shell.plan.area[t];
+    h.d_hA.upload(hA, s);
+    h.d_alpha.alloc(nTri);
+    h.d_alpha.zero(s);
+    h.d_alphaB.alloc(nH);
+    h.d_alphaB.zero(s);
+    h.d_count.alloc(SPC_COUNT);
+    h.d_count.zero(s);
+    h.d_totals.alloc(SPT_COUNT);
+    h.d_totals.zero(s);
+    h.d_B0.alloc(4 * nTri);
+    HIP_CHECK(hipMemcpyAsync(h.d_B0.p, shell.d_triConst.p, 4 * nTri * sizeof(double), hipMemcpyDeviceToDevice, s));
+    h.d_thetaBar0.alloc(nH);
+    if (nH) HIP_CHECK(hipMemcpyAsync(h.d_thetaBar0.p, shell.d_hingeConst.p, nH * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s)); // (hA leaves scope)
+}
+
+void HipMesh::setShellPlasticity(int triBegin, int triEnd, double yield, double bendYield, double creep, double harden, hipStream_t s)
+{
+    if (!shell.nTri()) throw StateError("shell_set_plasticity: no shell is set (call ipcgpu_set_shell first)");
+    ShellPlasticPlan next = shell.plastic.plan; // a refused call changes nothing
+    std::string err;
+    if (!setShellPlasticRange(next, shell.plan, nV, V_rest.data(), nullptr, triBegin, triEnd, yield, bendYield, creep, harden, err)) throw ArgError(err);
+    if (shell.nRubber() && (yield < INFINITY || bendYield < INFINITY)) // (the plan refuses a rubber triangle too when handed the models; here it is its own error class)
+        for (int t = triBegin; t < triEnd; ++t)
+            if (shell.rubber.model[t]) throw UnsupportedError("shell_set_plasticity: triangle " + std::to_string(t) + " carries the rubber membrane");
+    ensureShellPlastic(s);
+    shell.plastic.plan = std::move(next);
+    uploadShellPlasticParams(s);
 }
 
 void HipMesh::setRod(int nSeg, const int* seg, const double* radius, const double* YM, const double* rho, double bendScale, hipStream_t s)

@@ -259,6 +259,42 @@ void HipOptimizer::plasticFlow(const double* x_dev, double dt_)
     launch_plastic_flow(plasticView(x_dev, dt_), mesh.plastic.d_count.p, stream);
 }
 
+ShellPlasticView HipOptimizer::shellPlasticView(const double* x_dev, double dt_) const
+{
+    const HipShell& sh = mesh.shell;
+    const HipShellPlastic& h = sh.plastic;
+    ShellPlasticView v;
+    v.nTri = sh.nTri();
+    v.nHinge = sh.nHinge();
+    v.x = x_dev;
+    v.tri = sh.d_tri.p;
+    v.triConst = sh.d_triConst.p;
+    v.hinge = sh.d_hinge.p;
+    v.hingeConst = sh.d_hingeConst.p;
+    v.yield = h.d_yield.p;
+    v.creep = h.d_creep.p;
+    v.harden = h.d_harden.p;
+    v.alpha = h.d_alpha.p;
+    v.hYield = h.d_hYield.p;
+    v.hCreep = h.d_hCreep.p;
+    v.hHarden = h.d_hHarden.p;
+    v.hG = h.d_hG.p;
+    v.alphaB = h.d_alphaB.p;
+    v.hA = h.d_hA.p;
+    v.B0 = h.d_B0.p;
+    v.thetaBar0 = h.d_thetaBar0.p;
+    v.dt = dt_;
+    return v;
+}
+
+void HipOptimizer::shellPlasticFlow(const double* x_dev, double dt_)
+{
+    specAsmValid = false; // an assembly enqueued ahead read the rest records these flows rewrite
+    HipShellPlastic& h = mesh.shell.plastic;
+    h.d_count.zero(stream);
+    launch_shell_plastic_flow(shellPlasticView(x_dev, dt_), h.plan.nOn > 0, h.plan.nHingeOn > 0, h.d_count.p, stream);
+}
+
 void HipOptimizer::refreshAeroLagged()
 {
     if (!mesh.aero.n()) return;
@@ -970,6 +1006,21 @@ void HipOptimizer::saveStatus(const std::string& path)
         for (size_t t = 0; t < nT; ++t)
             out << p.k[t] << " " << p.k2[t] << " " << p.flags[t] << " " << p.group[t] << " " << p.dir[t] << " " << p.dir[nT + t] << " " << p.dir[2 * nT + t] << "\n";
     }
+    if (mesh.shell.plastic.on()) { // a project extension, beside `plastic`: B (b00 b10 b01 b11) and alpha per shell triangle, then thetaBar and alphaB per hinge
+        const HipShell& sh = mesh.shell;
+        const size_t nTri = (size_t)sh.nTri(), nH = (size_t)sh.nHinge();
+        std::vector<double> B(4 * nTri), alpha(nTri), thetaBar(nH), alphaB(nH);
+        sh.d_triConst.download(B.data(), B.size(), stream);
+        sh.plastic.d_alpha.download(alpha.data(), nTri, stream);
+        sh.d_hingeConst.download(thetaBar.data(), nH, stream);
+        sh.plastic.d_alphaB.download(alphaB.data(), nH, stream);
+        out << "\nshellplastic " << sh.nTri() << " 5 " << sh.nHinge() << " 2\n";
+        for (size_t t = 0; t < nTri; ++t) {
+            for (int k = 0; k < 4; ++k) out << B[k * nTri + t] << " ";
+            out << alpha[t] << "\n";
+        }
+        for (size_t i = 0; i < nH; ++i) out << thetaBar[i] << " " << alphaB[i] << "\n";
+    }
     if (!out.good()) throw StateError("write error on status file " + path);
 }
 
@@ -996,6 +1047,8 @@ void HipOptimizer::loadStatus(const std::string& path)
     };
     std::vector<double> plasticA, plasticAlpha; // the plastic section, where the file has one
     FiberPlan fiberIn; // the fiber section, where the file has one
+    std::vector<double> shellB, shellAlpha, shellThetaBar, shellAlphaB; // the shellplastic section, where the file has one
+    bool shellPlasticIn = false;
     std::string line;
     while (std::getline(in, line)) {
         std::stringstream ss(line);
@@ -1026,6 +1079,24 @@ void HipOptimizer::loadStatus(const std::string& path)
                 in >> plasticAlpha[t];
             }
             if (in.fail()) throw StateError("truncated or malformed plastic section in status file " + path);
+        }
+        else if (token == "shellplastic") {
+            int rowsIn = 0, dimIn = 0, hingesIn = 0, hdimIn = 0;
+            ss >> rowsIn >> dimIn >> hingesIn >> hdimIn;
+            if (ss.fail()) throw StateError("malformed section header in status file " + path);
+            if (!mesh.shell.nTri() || rowsIn != mesh.shell.nTri() || dimIn != 5 || hingesIn != mesh.shell.nHinge() || hdimIn != 2) throw StateError("status file does not match the shell");
+            const size_t nTri = (size_t)rowsIn, nH = (size_t)hingesIn;
+            shellB.assign(4 * nTri, 0.0);
+            shellAlpha.assign(nTri, 0.0);
+            shellThetaBar.assign(nH, 0.0);
+            shellAlphaB.assign(nH, 0.0);
+            for (size_t t = 0; t < nTri; ++t) {
+                for (int k = 0; k < 4; ++k) in >> shellB[k * nTri + t];
+                in >> shellAlpha[t];
+            }
+            for (size_t i = 0; i < nH; ++i) in >> shellThetaBar[i] >> shellAlphaB[i];
+            if (in.fail()) throw StateError("truncated or malformed shellplastic section in status file " + path);
+            shellPlasticIn = true;
         }
         else if (token == "fiber") {
             int rowsIn = 0, dimIn = 0, groupsIn = 0;
@@ -1075,6 +1146,17 @@ void HipOptimizer::loadStatus(const std::string& path)
         mesh.ensurePlastic(stream);
         HIP_CHECK(hipMemcpyAsync(mesh.d_A.p, plasticA.data(), plasticA.size() * sizeof(double), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemcpyAsync(mesh.plastic.d_alpha.p, plasticAlpha.data(), plasticAlpha.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
+    if (shellPlasticIn) { // (a file without the section leaves the shell's records and history untouched)
+        if (worldSize > 1) throw UnsupportedError("shell plasticity on a sharded context");
+        mesh.ensureShellPlastic(stream);
+        HipShell& sh = mesh.shell;
+        HIP_CHECK(hipMemcpyAsync(sh.d_triConst.p, shellB.data(), shellB.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(sh.plastic.d_alpha.p, shellAlpha.data(), shellAlpha.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (!shellThetaBar.empty()) {
+            HIP_CHECK(hipMemcpyAsync(sh.d_hingeConst.p, shellThetaBar.data(), shellThetaBar.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(sh.plastic.d_alphaB.p, shellAlphaB.data(), shellAlphaB.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        }
     }
     HIP_CHECK(hipStreamSynchronize(stream));
     if (fiberIn.nT) { // (a file without the section leaves the fibres untouched)
@@ -2238,6 +2320,7 @@ void HipOptimizer::endTimestep()
     // plastic flow at the end-of-step positions (plastic_kernels.h): before the lagged damping matrix, which is then the stiffness of the rest shape the
     // next step sees.  Nothing derived from A outlives it: specAsmValid is cleared above, the patch plan and the stress plan hold topology only.
     if (mesh.plastic.on()) plasticFlow(mesh.d_x.p, dt);
+    if (mesh.shell.plastic.on()) shellPlasticFlow(mesh.d_x.p, dt); // (shell_plastic_kernels.h: the same place, for the same reason)
     computeDampingMtr(); // Optimizer.cpp:593-595
     globalIterNum++;
 }

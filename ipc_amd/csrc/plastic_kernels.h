@@ -21,8 +21,8 @@
 // CHOOSING THE YIELD STRAIN.  For small strains the von Mises stress (ipcgpu_elastic_stress) is sqrt(6) mu n, so a material with yield stress sigma_y and
 //   shear modulus mu = E / (2 (1 + nu)) has yield = sigma_y / (sqrt(6) mu).  harden is dimensionless (yield strain gained per unit of plastic strain);
 //   creep is 1 / time: the excess decays like exp(-creep t) under a held deformation.
-// NOT modelled: volumetric (pressure-dependent) yield;  kinematic hardening;  a cap on the plastic strain;  plastic work as heat;  shells, rods and
-//   attachments (their rest records do not flow);  sharded contexts (refused both ways round, as for aero).
+// NOT modelled: volumetric (pressure-dependent) yield;  kinematic hardening;  a cap on the plastic strain;  plastic work as heat;  rods and attachments
+//   (their rest records do not flow; the shells have a flow of their own, shell_plastic_kernels.h);  sharded contexts (refused both ways round, as for aero).
 //
 // k_plastic_flow: one lane per tetrahedron of [tetBegin, tetEnd).  Coalesced SoA loads of A, the three parameters and alpha, the four-node gather of the
 // element kernels, svd3, three log, three exp, two 3 x 3 products; nine coalesced stores plus alpha from the lanes that yielded and from no other.  fp64

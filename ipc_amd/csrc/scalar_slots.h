@@ -34,6 +34,23 @@ enum PlasticTotal : int {
     PT_COUNT
 };
 
+// The shells' plastic flow keeps the same two boards (HipShellPlastic, hip_ipc.h; shell_plastic_kernels.h): the stepper's launches add to the integer one
+// and never read it; ipcgpu_shell_plastic_update and ipcgpu_shell_plastic_state read them.
+enum ShellPlasticCount : int {
+    SPC_TRI_YIELDED = 0, // triangles the last flow rewrote.  Zeroed before every flow, added to by k_shell_plastic_flow_tri (integer atomics).
+    SPC_TRI_SKIPPED, // triangles the last flow found collapsed (l2 <= 0 or not finite) and left alone.  (Stays behind SPC_TRI_YIELDED: the kernel adds to the pair.)
+    SPC_HINGE_YIELDED, // hinges the last flow rewrote.  Added to by k_shell_plastic_flow_hinge.
+    SPC_HINGE_SKIPPED, // hinges the last flow found with a zero-length n1, n2 or e and left alone.  (Stays behind SPC_HINGE_YIELDED.)
+    SPC_COUNT
+};
+enum ShellPlasticTotal : int {
+    SPT_MAX_ALPHA = 0, // the largest accumulated membrane plastic strain.  Written by launch_shell_plastic_state's reduction, read by ipcgpu_shell_plastic_state behind it.
+    SPT_MAX_ALPHA_B, // the largest accumulated outer-fibre plastic strain of a hinge
+    SPT_HA_ALPHA, // sum of rest volume h A times alpha over the triangles
+    SPT_COUNT
+};
+static_assert(SPC_TRI_SKIPPED == SPC_TRI_YIELDED + 1 && SPC_HINGE_SKIPPED == SPC_HINGE_YIELDED + 1, "a flow kernel adds to a pair of neighbours");
+
 // how many slots first .. last are: the count of a publish
 constexpr int slotSpan(ScalarSlot first, ScalarSlot last) { return last - first + 1; }
 

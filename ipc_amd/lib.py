@@ -652,6 +652,58 @@ class Context:
         self._chk(self._L.ipcgpu_shell_thickness(self.h, _dp(h)))
         return h
 
+    # ---- plastic flow of the shell (ipcgpu_shell_set_plasticity: permanent stretch, creases and dents; ipc_amd/csrc/shell_plastic_kernels.h)
+    def _shell_counts(self):
+        cnt = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.ipcgpu_shell_get(self.h, _ip(cnt), None, None, None, None, None))
+        return int(cnt[0]), int(cnt[1])
+
+    def shell_set_plasticity(self, tri_range, yield_strain, bend_yield=None, creep=np.inf, harden=0.0):
+        """shell triangles [tri_range[0], tri_range[1]): the membrane flows where the deviatoric Hencky strain norm n exceeds yield_strain + harden alpha, a hinge
+        between two such triangles where its outer-fibre strain g |theta - thetaBar| exceeds bend_yield + harden alphaB (None: yield_strain); the excess decays like
+        exp(-creep t) (inf: returned at once); inf switches a flow off.  After set_shell, also between time steps; later calls overwrite."""
+        yb = yield_strain if bend_yield is None else bend_yield
+        self._chk(self._L.ipcgpu_shell_set_plasticity(self.h, C.c_int(tri_range[0]), C.c_int(tri_range[1]), C.c_double(yield_strain), C.c_double(yb), C.c_double(creep), C.c_double(harden)))
+
+    def shell_plastic_get(self):
+        """dict: yield, bendYield, creep, harden, alpha (nTri each), triConst (nTri x 6, the current constants the kernels read: B = columns 0-3 as b00 b10 b01
+        b11, then h A mu, h A lambda_ps), B0 (nTri x 4), hingeYield, hingeCreep, hingeHarden, g, alphaB, thetaBar (current), thetaBar0 (nHinge each)"""
+        nT, nH = self._shell_counts()
+        y, yb, cr, K, al = (np.zeros(nT) for _ in range(5))
+        tc, B0, hp = np.zeros((nT, 6), order="F"), np.zeros((nT, 4), order="F"), np.zeros((nH, 4), order="F")
+        alB, th, th0 = np.zeros(nH), np.zeros(nH), np.zeros(nH)
+        self._chk(self._L.ipcgpu_shell_plastic_get(self.h, _dp(y), _dp(yb), _dp(cr), _dp(K), _dp(al), _dp(tc), _dp(B0), _dp(hp), _dp(alB), _dp(th), _dp(th0)))
+        return {"yield": y, "bendYield": yb, "creep": cr, "harden": K, "alpha": al, "triConst": tc, "B": tc[:, :4].copy(), "B0": B0, "hingeYield": hp[:, 0].copy(),
+                "hingeCreep": hp[:, 1].copy(), "hingeHarden": hp[:, 2].copy(), "g": hp[:, 3].copy(), "alphaB": alB, "thetaBar": th, "thetaBar0": th0}
+
+    def shell_plastic_update(self, dt):
+        """one flow of the membrane and of the hinges at the held positions, outside the stepper: (triangles that yielded, triangles skipped as collapsed,
+        hinges that yielded, hinges skipped as degenerate)"""
+        cnt = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.ipcgpu_shell_plastic_update(self.h, C.c_double(dt), _ip(cnt)))
+        return tuple(int(v) for v in cnt)
+
+    def shell_plastic_state(self):
+        """(perTri nTri x 4: n, current yield strain y, alpha, det B0 / det B -- n is NaN where the flow would skip the triangle; perHinge nHinge x 4: eps, y,
+        alphaB, thetaBar - thetaBar0; totals 7: the four counts of the last flow, max alpha, max alphaB, sum of h A alpha).  Read-only."""
+        nT, nH = self._shell_counts()
+        pt, ph, tot = np.zeros((nT, 4), order="F"), np.zeros((nH, 4), order="F"), np.zeros(7)
+        self._chk(self._L.ipcgpu_shell_plastic_state(self.h, _dp(pt), _dp(ph), _dp(tot)))
+        return pt, ph, tot
+
+    def shell_plastic_set_state(self, B=None, alpha=None, thetaBar=None, alphaB=None):
+        """the current B (nTri x 4: b00 b10 b01 b11 per row), alpha (nTri), thetaBar and alphaB (nHinge) from the caller; None leaves a part as it is"""
+        nT, nH = self._shell_counts()
+        Bf = None if B is None else np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(nT, 4))
+        al = None if alpha is None else _f64(np.asarray(alpha, dtype=np.float64).reshape(nT))
+        th = None if thetaBar is None else _f64(np.asarray(thetaBar, dtype=np.float64).reshape(nH))
+        ab = None if alphaB is None else _f64(np.asarray(alphaB, dtype=np.float64).reshape(nH))
+        self._chk(self._L.ipcgpu_shell_plastic_set_state(self.h, _dp(Bf), _dp(al), _dp(th), _dp(ab)))
+
+    def shell_plastic_reset(self):
+        """forget the shell's plastic history: B and thetaBar of the first shell_set_plasticity call, alpha = alphaB = 0"""
+        self._chk(self._L.ipcgpu_shell_plastic_reset(self.h))
+
     # ---- elastic rods (ipcgpu_set_rod: stretching + bending energy on segment components)
     def set_rod(self, seg, radius, YM, rho, bend_scale=1.0):
         """seg: nSeg x 2 node ids; radius, YM, rho: scalars or one value per segment.  After set_mesh, before opt_init and set_pattern; sets the masses of

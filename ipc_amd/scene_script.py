@@ -67,6 +67,10 @@ class Shape:
     # `shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]`: this shape's triangles carry the incompressible Mooney-Rivlin membrane in place of
     # the StVK one (Context.set_shell_membrane); alpha in [0, 1) is the I2 fraction, default 0 = neo-Hookean; per shape, shapes may differ
     shell_rubber: bool = False
+    # `shell <thickness> [bend <s>] [limit ...] yield <y> [bendyield <yb>] [creep <rate>] [harden <K>]`: this shape's triangles flow plastically -- the membrane
+    # where the deviatoric Hencky strain norm exceeds y + K alpha, a hinge where its outer-fibre strain exceeds yb + K alphaB (Context.shell_set_plasticity);
+    # bendyield defaults to yield, creep to inf (returned within the step), harden to 0; not with `rubber`.  (yield, bendyield, creep, harden), or None
+    shell_plastic: tuple = None
     # `plastic <yield> [creep <rate>] [harden <K>]` (this project's keyword, tetrahedral shapes only): the shape's elements flow plastically where the deviatoric
     # Hencky strain norm exceeds yield + K alpha (Context.set_plasticity; for small strains the von Mises stress is sqrt(6) mu n); creep: the rate at which the
     # excess decays (default inf: returned within the step), harden: isotropic hardening (default 0).  (yield, creep, harden), or None
@@ -599,6 +603,28 @@ def _parse_shape(st, resolve):
                     raise ValueError("limit needs 1 <= onset < limit and a stiffness > 0")
             elif j < len(st) and st[j] in ("onset", "stiff"):
                 raise ValueError(st[j] + " belongs behind limit")
+            if j < len(st) and st[j] == "yield":
+                if sh.shell_rubber:
+                    raise ValueError("yield is not valid behind rubber: a rubber membrane has no plastic flow")
+                if j + 1 >= len(st):
+                    raise ValueError("yield needs a strain")
+                par = {"yield": float(st[j + 1]), "bendyield": None, "creep": math.inf, "harden": 0.0}
+                j += 2
+                for word in ("bendyield", "creep", "harden"):
+                    if j < len(st) and st[j] == word:
+                        if j + 1 >= len(st):
+                            raise ValueError(word + " needs a number")
+                        par[word] = float(st[j + 1])
+                        j += 2
+                if par["bendyield"] is None:
+                    par["bendyield"] = par["yield"]
+                if not (par["yield"] >= 0.0 and par["bendyield"] >= 0.0 and par["creep"] > 0.0 and 0.0 <= par["harden"] < math.inf):
+                    raise ValueError("yield needs strains >= 0, a creep rate > 0 and a finite hardening modulus >= 0")
+                sh.shell_plastic = (par["yield"], par["bendyield"], par["creep"], par["harden"])
+                if j < len(st) and st[j] in ("yield", "bendyield", "creep", "harden", "limit", "onset", "stiff"):
+                    raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <s>] [limit ...] yield <y> [bendyield <yb>] [creep <rate>] [harden <K>]")
+            elif j < len(st) and st[j] in ("bendyield", "creep", "harden"):
+                raise ValueError(st[j] + " belongs behind yield")
             if j < len(st) and st[j] in ("rubber", "mr", "bend"):
                 raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]")
         elif e == "rod":
@@ -978,7 +1004,7 @@ def _codim_keywords(cfg, sh, name, V, T, SF, E, off, p):
     mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
     if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
         p.shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat, (0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff),
-                         (1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0)))
+                         (1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0), sh.shell_plastic))
     if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
         p.rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
     if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
@@ -1145,6 +1171,9 @@ def _codim_payloads(p, attachments, V):
         if any(r[5][0] for r in p.shells):  # per triangle, as Context.set_shell_membrane takes them; a shape without `rubber` stays StVK (0)
             shell["model"] = _per(p.shells, lambda r: r[5][0], dtype=np.int32)
             shell["alpha"] = _per(p.shells, lambda r: float(r[5][1]))
+        if any(r[6] is not None for r in p.shells):  # per plastic shape its triangle range within the shell and the four parameters, as Context.shell_set_plasticity takes them
+            ends = np.cumsum([len(r[0]) for r in p.shells])
+            shell["plastic"] = [((int(e - len(r[0])), int(e)),) + tuple(r[6]) for r, e in zip(p.shells, ends) if r[6] is not None]
     if p.rods:
         if len({r[2] for r in p.rods}) > 1:
             raise ValueError("one bend scale per scene: the rod shapes give different ones")
@@ -1215,6 +1244,8 @@ def apply(sc, be):
             be.set_shell_membrane(q["model"], q["alpha"])
         if "limit" in q:
             be.set_shell_strain_limit(q["limit"], q["onset"], q["stiff"])
+        for rng, y, yb, creep, harden in q.get("plastic", ()):  # one call per plastic shape, over its triangle range
+            be.shell_set_plasticity(rng, y, yb, creep, harden)
     if sc.rod is not None:  # after set_codim_nodes and set_shell (it replaces the segment masses of its nodes), before opt_init and the pattern
         q = sc.rod
         be.set_rod(q["seg"], q["radius"], q["YM"], q["rho"], q["bend"])

@@ -308,6 +308,7 @@ int ipcgpu_set_mesh(ipcgpu_ctx* c, int nV, int nT, const double* Vr, const int* 
         c->opt->contact = nullptr;
         c->opt->planes.clear();
         c->opt->rounds.clear();
+        c->opt->listColliders();
         c->contact.reset();
         c->stress.reset(); // the incidence list belongs to the previous mesh
         return IPCGPU_OK;
@@ -2384,6 +2385,69 @@ int ipcgpu_opt_set_pattern_lookahead(ipcgpu_ctx* c, double pad)
         return IPCGPU_OK;
     });
 }
+// ---- what the half-space and the round collider entry points share: one body each, the caller supplies the obstacle ------------------------------------
+static int colliderBuild(ipcgpu_ctx* c, HipVertexCollider& h, double dHat, int cap, int* verts, int* n)
+{
+    bind(c);
+    const int cnt = h.build(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, dHat);
+    if (n) *n = cnt;
+    needArg(!verts || cap >= cnt, "verts buffer too small");
+    if (verts) std::memcpy(verts, h.set.data(), sizeof(int) * cnt);
+    return IPCGPU_OK;
+}
+static int colliderSet(ipcgpu_ctx* c, HipVertexCollider& h, int n, const int* verts)
+{
+    bind(c);
+    needArg(n >= 0 && (verts || !n), "bad vertex list");
+    for (int i = 0; i < n; ++i) needArg(verts[i] >= 0 && verts[i] < c->mesh->nV, "vertex id out of range");
+    h.setSet(n, verts);
+    return IPCGPU_OK;
+}
+static int colliderEnergy(ipcgpu_ctx* c, HipVertexCollider& h, double dHat, double kappa, double* E)
+{
+    bind(c);
+    needArg(E != nullptr, "null result");
+    *E = h.energy(c->mesh->d_x.p, dHat, kappa);
+    return IPCGPU_OK;
+}
+static int colliderGradientAdd(ipcgpu_ctx* c, HipVertexCollider& h, double dHat, double kappa, double* g)
+{
+    HipOptimizer& o = O(c);
+    bind(c);
+    needArg(g != nullptr, "null gradient");
+    const size_t n3 = 3 * (size_t)c->mesh->nV;
+    HIP_CHECK(hipMemcpyAsync(o.d_gradient.p, g, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    h.gradientAdd(c->mesh->d_x.p, dHat, kappa, o.d_gradient.p);
+    o.d_gradient.download(g, n3, c->stream);
+    return IPCGPU_OK;
+}
+static int colliderHessianAdd(ipcgpu_ctx* c, HipVertexCollider& h, double dHat, double kappa, int projectDBC)
+{
+    bind(c);
+    need(c->lin->numRows == 3 * c->mesh->nV, "call ipcgpu_linsys_set_pattern first");
+    h.hessianAdd(c->mesh->d_x.p, c->mesh->d_dbc.p, c->lin->d_rowBase.p, c->lin->d_rowLen.p, dHat, kappa, projectDBC, c->lin->d_a.p);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return IPCGPU_OK;
+}
+// (the caller has announced the change with specChanged)
+static int colliderMove(ipcgpu_ctx* c, HipVertexCollider& h, const double* delta3, double slackness, double* stepSizeLeft, const char* bad)
+{
+    bind(c);
+    needArg(delta3 && slackness > 0.0 && slackness <= 1.0, bad);
+    for (int k = 0; k < 3; ++k) needArg(std::isfinite(delta3[k]), bad);
+    const double left = h.move(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, delta3, slackness);
+    if (stepSizeLeft) *stepSizeLeft = left;
+    return IPCGPU_OK;
+}
+static int colliderStepBound(ipcgpu_ctx* c, HipVertexCollider& h, const double* p, double slackness, double* step)
+{
+    HipOptimizer& o = O(c);
+    bind(c);
+    needArg(p && step && slackness > 0 && slackness <= 1, "bad step-bound argument");
+    HIP_CHECK(hipMemcpyAsync(o.d_searchDir.p, p, 3 * (size_t)c->mesh->nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    *step = h.stepBound(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, o.d_searchDir.p, slackness, *step);
+    return IPCGPU_OK;
+}
 int ipcgpu_opt_add_half_space(ipcgpu_ctx* c, const double* origin, const double* normal, double dHatEps, int* id)
 {
     specChanged(c);
@@ -2405,83 +2469,34 @@ static HipHalfSpace& HS(ipcgpu_ctx* c, int id)
 }
 int ipcgpu_halfspace_build(ipcgpu_ctx* c, int id, double dHat, int cap, int* verts, int* n)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        bind(c);
-        const int cnt = h.build(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, dHat);
-        if (n) *n = cnt;
-        needArg(!verts || cap >= cnt, "verts buffer too small");
-        if (verts) std::memcpy(verts, h.set.data(), sizeof(int) * cnt);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderBuild(c, HS(c, id), dHat, cap, verts, n); });
 }
 int ipcgpu_halfspace_set(ipcgpu_ctx* c, int id, int n, const int* verts)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        bind(c);
-        for (int i = 0; i < n; ++i) needArg(verts[i] >= 0 && verts[i] < c->mesh->nV, "vertex id out of range");
-        h.setSet(n, verts);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderSet(c, HS(c, id), n, verts); });
 }
 int ipcgpu_halfspace_energy(ipcgpu_ctx* c, int id, double dHat, double kappa, double* E)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        bind(c);
-        *E = h.energy(c->mesh->d_x.p, dHat, kappa);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderEnergy(c, HS(c, id), dHat, kappa, E); });
 }
 int ipcgpu_halfspace_gradient_add(ipcgpu_ctx* c, int id, double dHat, double kappa, double* g)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        HipOptimizer& o = O(c);
-        bind(c);
-        const size_t n3 = 3 * (size_t)c->mesh->nV;
-        HIP_CHECK(hipMemcpyAsync(o.d_gradient.p, g, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        h.gradientAdd(c->mesh->d_x.p, dHat, kappa, o.d_gradient.p);
-        o.d_gradient.download(g, n3, c->stream);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderGradientAdd(c, HS(c, id), dHat, kappa, g); });
 }
 int ipcgpu_halfspace_hessian_add(ipcgpu_ctx* c, int id, double dHat, double kappa, int projectDBC)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        bind(c);
-        need(c->lin->numRows == 3 * c->mesh->nV, "call ipcgpu_linsys_set_pattern first");
-        h.hessianAdd(c->mesh->d_x.p, c->mesh->d_dbc.p, c->lin->d_rowBase.p, c->lin->d_rowLen.p, dHat, kappa, projectDBC, c->lin->d_a.p);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderHessianAdd(c, HS(c, id), dHat, kappa, projectDBC); });
 }
 int ipcgpu_halfspace_move(ipcgpu_ctx* c, int id, const double* delta3, double slackness, double* stepSizeLeft)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        bind(c);
-        needArg(delta3 && slackness > 0.0 && slackness <= 1.0, "bad half-space move");
-        const double left = h.move(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, delta3, slackness);
-        if (stepSizeLeft) *stepSizeLeft = left;
-        return IPCGPU_OK;
-    });
+    specChanged(c);
+    return guarded([&] { return colliderMove(c, HS(c, id), delta3, slackness, stepSizeLeft, "bad half-space move"); });
 }
 int ipcgpu_halfspace_step_bound(ipcgpu_ctx* c, int id, const double* p, double slackness, double* step)
 {
-    return guarded([&] {
-        HipHalfSpace& h = HS(c, id);
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(p && step && slackness > 0 && slackness <= 1, "bad step-bound argument");
-        HIP_CHECK(hipMemcpyAsync(o.d_searchDir.p, p, 3 * (size_t)c->mesh->nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        *step = h.stepBound(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, o.d_searchDir.p, slackness, *step);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderStepBound(c, HS(c, id), p, slackness, step); });
 }
-// ---- round colliders (round_collider_kernels.h): the half-space's list, piece by piece, plus the state query ---------------------------------------
+// ---- round colliders (round_collider_kernels.h): the half-space's list through the same bodies, plus the friction pieces and the state query ---------------------------------------
 int ipcgpu_opt_add_round_collider(ipcgpu_ctx* c, const double* p0, const double* p1, double R, int hollow, double dHatEps, int* id)
 {
     specChanged(c);
@@ -2503,86 +2518,32 @@ static HipRoundCollider& RC(ipcgpu_ctx* c, int id)
 }
 int ipcgpu_round_build(ipcgpu_ctx* c, int id, double dHat, int cap, int* verts, int* n)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        bind(c);
-        const int cnt = h.build(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, dHat);
-        if (n) *n = cnt;
-        needArg(!verts || cap >= cnt, "verts buffer too small");
-        if (verts) std::memcpy(verts, h.set.data(), sizeof(int) * cnt);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderBuild(c, RC(c, id), dHat, cap, verts, n); });
 }
 int ipcgpu_round_set(ipcgpu_ctx* c, int id, int n, const int* verts)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        bind(c);
-        needArg(n >= 0 && (verts || !n), "bad vertex list");
-        for (int i = 0; i < n; ++i) needArg(verts[i] >= 0 && verts[i] < c->mesh->nV, "vertex id out of range");
-        h.setSet(n, verts);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderSet(c, RC(c, id), n, verts); });
 }
 int ipcgpu_round_energy(ipcgpu_ctx* c, int id, double dHat, double kappa, double* E)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        bind(c);
-        needArg(E != nullptr, "null result");
-        *E = h.energy(c->mesh->d_x.p, dHat, kappa);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderEnergy(c, RC(c, id), dHat, kappa, E); });
 }
 int ipcgpu_round_gradient_add(ipcgpu_ctx* c, int id, double dHat, double kappa, double* g)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(g != nullptr, "null gradient");
-        const size_t n3 = 3 * (size_t)c->mesh->nV;
-        HIP_CHECK(hipMemcpyAsync(o.d_gradient.p, g, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        h.gradientAdd(c->mesh->d_x.p, dHat, kappa, o.d_gradient.p);
-        o.d_gradient.download(g, n3, c->stream);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderGradientAdd(c, RC(c, id), dHat, kappa, g); });
 }
 int ipcgpu_round_hessian_add(ipcgpu_ctx* c, int id, double dHat, double kappa, int projectDBC)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        bind(c);
-        need(c->lin->numRows == 3 * c->mesh->nV, "call ipcgpu_linsys_set_pattern first");
-        h.hessianAdd(c->mesh->d_x.p, c->mesh->d_dbc.p, c->lin->d_rowBase.p, c->lin->d_rowLen.p, dHat, kappa, projectDBC, c->lin->d_a.p);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderHessianAdd(c, RC(c, id), dHat, kappa, projectDBC); });
 }
 int ipcgpu_round_move(ipcgpu_ctx* c, int id, const double* delta3, double slackness, double* stepSizeLeft)
 {
     specChanged(c);
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        bind(c);
-        needArg(delta3 && slackness > 0.0 && slackness <= 1.0, "bad round-collider move");
-        for (int k = 0; k < 3; ++k) needArg(std::isfinite(delta3[k]), "bad round-collider move");
-        const double left = h.move(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, delta3, slackness);
-        if (stepSizeLeft) *stepSizeLeft = left;
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderMove(c, RC(c, id), delta3, slackness, stepSizeLeft, "bad round-collider move"); });
 }
 int ipcgpu_round_step_bound(ipcgpu_ctx* c, int id, const double* p, double slackness, double* step)
 {
-    return guarded([&] {
-        HipRoundCollider& h = RC(c, id);
-        HipOptimizer& o = O(c);
-        bind(c);
-        needArg(p && step && slackness > 0 && slackness <= 1, "bad step-bound argument");
-        HIP_CHECK(hipMemcpyAsync(o.d_searchDir.p, p, 3 * (size_t)c->mesh->nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        *step = h.stepBound(CT(c).nSVI, CT(c).d_SVI.p, c->mesh->d_x.p, c->mesh->d_dbc.p, o.d_searchDir.p, slackness, *step);
-        return IPCGPU_OK;
-    });
+    return guarded([&] { return colliderStepBound(c, RC(c, id), p, slackness, step); });
 }
 int ipcgpu_round_get(ipcgpu_ctx* c, int id, double* p0, double* p1, double* R, int* hollow)
 {

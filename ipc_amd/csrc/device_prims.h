@@ -4,11 +4,12 @@
 // the SAME reduction tree, hence one definition.
 // Everything is __forceinline__ and takes the including unit's -ffp-contract setting; nothing here multiplies and adds, so that setting cannot
 // change a bit -- keep arithmetic beyond add / min / max out of the helpers.  For .hip files only.
-//   nh_kernels, hip_contact, hip_halfspace, pcg          include this header
+//   nh_kernels, hip_contact, vertex_collider, pcg        include this header
 //   shell*, rod, attach, chamber kernels                 get it through csr_scatter_device.h (the atomic block scatter)
 //   mf_numeric, mf_sweeps                                include it for the publish kernel alone
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstring>
 #include "common.h"
 
 namespace ipcgpu {
@@ -106,7 +107,28 @@ inline void launch_reduce_partials(const double* partial, int n, double scale, b
     hipLaunchKernelGGL(k_reduce_partials<BLOCK>, dim3(1), dim3(BLOCK), 0, s, partial, n, scale, accumulate ? 1 : 0, out);
 }
 
-// ---- read-backs through mapped host memory ------------------------------------------------------------------------------------------------------------------
+// ---- minimum of doubles through atomicMin ---------------------------------------------------------------------------------------------------------------------
+// order-preserving map double -> uint64, so that atomicMin works for either sign; the cell starts at ~0ull
+__device__ __forceinline__ unsigned long long ordered_bits(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+inline double from_ordered_bits(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+    double v;
+    std::memcpy(&v, &b, sizeof(v));
+    return v;
+}
+// the tail of a minimum kernel: the wave tree, then one atomic per wave
+__device__ __forceinline__ void atomic_min_wave(double best, unsigned long long* __restrict__ out)
+{
+    best = wave_min(best);
+    if ((threadIdx.x & 63) == 0) atomicMin(out, ordered_bits(best));
+}
+
+// ---- read-backs through mapped host memory------------------------------------------------------------------------------------------------------------------
 // dst[i] = src[i] for the nWords <= 64 32-bit words of a small result, one lane each: THE kernel that carries flags, counters and scalars from device memory
 // to their mapped place on the host.  (k_publish2, k_publish_narrow and the tail of k_reduce_scaled stay where they are: two sources, or a gather.)
 template <int WAVE = 64> // (a template, like k_reduce_partials: a unit that never launches it gets no kernel)
@@ -127,6 +149,17 @@ inline void launch_publish(const T* src, T* dst, int count, hipStream_t s)
 // L entries starting at base, row 3 v + 1 starts at base + L and has L - 1, row 3 v + 2 starts at base + 2 L - 1 and has L - 2.  The six entries of
 // the diagonal block are base, base + 1, base + 2, base + L, base + L + 1, base + 2 L - 1; they stay written out at their sites, and so does the search in
 // scatter::add_off: in the code-object diff against the parent commit every helper form tried for them changed the instruction stream of the kernels.
+// (The vertex colliders, whose kernels write nothing but this block, do share the write.)
+// a[the diagonal block of the node whose row starts at p0 with L entries] += h6, the upper triangle row by row: 00 01 02 11 12 22
+__device__ __forceinline__ void add_diag_block(double* __restrict__ a, int p0, int L, const double* h6)
+{
+    a[p0] += h6[0];
+    a[p0 + 1] += h6[1];
+    a[p0 + 2] += h6[2];
+    a[p0 + L] += h6[3];
+    a[p0 + L + 1] += h6[4];
+    a[p0 + 2 * L - 1] += h6[5];
+}
 // row r of an off-diagonal block whose first entry is at p0 starts at p0 + block_row_off(r, L)
 __device__ __forceinline__ int block_row_off(int r, int L) { return r == 0 ? 0 : (r == 1 ? L - 1 : 2 * L - 3); }
 // Binary search for the block of neighbour cn in ja[lo, hi): lo = base + 3 (behind the diagonal block's entries) and hi = base + L of the node row.

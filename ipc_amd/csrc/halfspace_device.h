@@ -1,4 +1,4 @@
-// Device functions of the half-space obstacle that more than one translation unit uses: the kernels of hip_halfspace.hip and the contact report of
+// Device functions of the half-space obstacle that more than one translation unit uses: the kernels of vertex_collider.hip and the contact report of
 // hip_contact.hip (both compiled with -ffp-contract=off, so the signed distance has the same bits in both).
 #pragma once
 #include <hip/hip_runtime.h>

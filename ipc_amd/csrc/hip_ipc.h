@@ -660,9 +660,13 @@ public:
     double lookahead() const { return patternPad >= 0.0 ? patternPad : (mesh.nV > 150000 ? 2.25 : 4.0); }
     // analytic half-space obstacles (animConfig.collisionObjects) and their close-constraint list (Optimizer.cpp:2364-2374)
     std::vector<std::unique_ptr<HipHalfSpace>> planes;
-    // analytic round colliders (spheres, capsules: round_collider_kernels.h), visited right after the planes wherever those are walked
+    // analytic round colliders (spheres, capsules: round_collider_kernels.h)
     std::vector<std::unique_ptr<HipRoundCollider>> rounds;
-    std::vector<std::pair<int, int>> closeHS; // (object, vertex): objects count through the planes, then the rounds
+    // THE walk over the analytic obstacles: all planes in registration order, then all rounds in registration order, whatever the order of the add calls
+    // (the energy sums and the object index of closeHS are positions in it).  listColliders() after every change of `planes` or `rounds`.
+    std::vector<HipVertexCollider*> colliders;
+    void listColliders();
+    std::vector<std::pair<int, int>> closeHS; // (object, vertex): the object's position in `colliders`
     std::vector<double> closeHSVal;
     // lagged friction: Optimizer.cpp:286-304, 1525-1600, 1615-1790; the lagged sets live in HipContact /
     // HipHalfSpace, x^t is d_xPrev
@@ -675,7 +679,7 @@ public:
     bool solveFric() const;
     void updateFrictionLag();
     bool nextSubproblem(); // tail of the fullyImplicit_IP loop body after a converged solveSub_IP; true = run another one
-    bool ipOn() const { return selfCollision || !planes.empty() || !rounds.empty(); }
+    bool ipOn() const { return selfCollision || !colliders.empty(); }
     size_t nConstraints() const;
     int addHalfSpace(HipContact* c, const double* origin3, const double* normal3, double dHatEps);
     int addRoundCollider(HipContact* c, const double* p0, const double* p1, double R, int hollow, double dHatEps);

@@ -679,13 +679,10 @@ double HipOptimizer::computeEnergyVal()
     const double Econtact = contactQueued ? published(S_CONTACT_E) : 0.0;
     if (!nbcGroups.empty()) E += neumannEnergy();
     // barrier terms over the current constraint sets (Optimizer.cpp:3252-3353); replicated on every rank
-    for (auto& h : planes) E += h->energy(mesh.d_x.p, dHat, kappa);
-    for (auto& h : rounds) E += h->energy(mesh.d_x.p, dHat, kappa);
+    for (auto* h : colliders) E += h->energy(mesh.d_x.p, dHat, kappa);
     if (selfCollision) E += Econtact;
     if (fricDHat > 0.0) { // lagged friction (Optimizer.cpp:3357-3377)
-        for (auto& h : planes)
-            if (h->friction > 0.0) E += h->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat);
-        for (auto& h : rounds)
+        for (auto* h : colliders)
             if (h->friction > 0.0) E += h->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat);
         if (selfCollision && selfFric > 0.0) E += contact->frictionEnergy(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, d_partial, slot(S_FRICTION_E));
     }
@@ -763,9 +760,7 @@ bool HipOptimizer::solveFric() const
 {
     if (fricLoopForced) return true;
     if (selfCollision && selfFric > 0.0) return true;
-    for (const auto& h : planes)
-        if (h->friction > 0.0) return true;
-    for (const auto& h : rounds)
+    for (const auto* h : colliders)
         if (h->friction > 0.0) return true;
     return false;
 }
@@ -774,9 +769,7 @@ void HipOptimizer::updateFrictionLag()
 {
     // multipliers, closest points and tangent bases of the current constraint sets (Optimizer.cpp:1553-1600 / 1620-1675)
     if (!solveFric()) return;
-    for (auto& h : planes)
-        if (h->friction > 0.0) h->lagUpdate(mesh.d_x.p, dHat, kappa);
-    for (auto& h : rounds)
+    for (auto* h : colliders)
         if (h->friction > 0.0) h->lagUpdate(mesh.d_x.p, dHat, kappa);
     if (selfCollision && selfFric > 0.0) contact->frictionLagUpdate(mesh.d_x.p, dHat, kappa);
 }
@@ -796,14 +789,7 @@ bool HipOptimizer::nextSubproblem()
     { // discrete complementarity slackness on the distances of the active sets (:1706-1713); once per sub-problem, on the host
         double dMax = 0.0, dMin = 1.0e300;
         std::vector<double> d;
-        for (auto& h : planes) {
-            h->evalDist2(h->set, mesh.d_x.p, d);
-            for (size_t i = 0; i < h->set.size(); ++i) {
-                dMax = std::max(dMax, d[i]);
-                dMin = std::min(dMin, d[i]);
-            }
-        }
-        for (auto& h : rounds) {
+        for (auto* h : colliders) {
             h->evalDist2(h->set, mesh.d_x.p, d);
             for (size_t i = 0; i < h->set.size(); ++i) {
                 dMax = std::max(dMax, d[i]);
@@ -849,8 +835,7 @@ bool HipOptimizer::nextSubproblem()
 size_t HipOptimizer::nConstraints() const
 {
     size_t n = selfCollision ? (size_t)contact->nActive() : 0;
-    for (const auto& h : planes) n += h->set.size();
-    for (const auto& h : rounds) n += h->set.size();
+    for (const auto* h : colliders) n += h->set.size();
     return n;
 }
 
@@ -862,7 +847,8 @@ int HipOptimizer::addHalfSpace(HipContact* c, const double* origin3, const doubl
     // a second object registered with another value would silently change the first one's activation distance
     if (ipOn() && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
     contact = c;
-    planes.emplace_back(new HipHalfSpace(stream, origin3, normal3));
+    planes.push_back(HipHalfSpace::create(stream, origin3, normal3));
+    listColliders();
     dHatEps = eps;
     dHat = eps * eps * lenScale2();
     dTol = dTolRel * dTolRel * lenScale2();
@@ -878,14 +864,22 @@ int HipOptimizer::addRoundCollider(HipContact* c, const double* p0, const double
     RoundShape shape;
     std::string err;
     if (!planRoundCollider(p0, p1, R, hollow, eps * eps * lenScale2(), shape, err)) throw ArgError(err);
-    std::unique_ptr<HipRoundCollider> h(new HipRoundCollider(stream, shape));
+    std::unique_ptr<HipRoundCollider> h = HipRoundCollider::create(stream, shape);
     if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) throw StateError("round collider: a node lies on or inside the collider at the current positions (an intersecting start state)");
     contact = c;
     rounds.push_back(std::move(h));
+    listColliders();
     dHatEps = eps;
     dHat = eps * eps * lenScale2();
     dTol = dTolRel * dTolRel * lenScale2();
     return (int)rounds.size() - 1;
+}
+
+void HipOptimizer::listColliders()
+{
+    colliders.clear();
+    for (const auto& h : planes) colliders.push_back(h.get());
+    for (const auto& h : rounds) colliders.push_back(h.get());
 }
 
 void HipOptimizer::requireRoundsFeasible()
@@ -900,9 +894,7 @@ void HipOptimizer::requireRoundsFeasible()
 bool HipOptimizer::anyIntersection()
 {
     // isIntersected (Optimizer.cpp:2626-2659): analytic objects first, then the mesh against itself
-    for (auto& h : planes)
-        if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) return true;
-    for (auto& h : rounds)
+    for (auto* h : colliders)
         if (h->intersected(mesh.nV, mesh.d_x.p, mesh.d_dbc.p)) return true;
     return selfCollision && isIntersected();
 }
@@ -912,7 +904,7 @@ void HipOptimizer::enableSelfCollision(HipContact* c, double eps)
 {
     // `selfCollisionOn` + interior point; dHat = dHatEps^2 * bbox diagonal^2 (Optimizer.cpp:1534-1537, Config.cpp:41-45)
     if (!c || !c->surfaceSet) throw StateError("opt_enable_self_collision before set_surface");
-    if ((!planes.empty() || !rounds.empty()) && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
+    if (!colliders.empty() && eps != dHatEps) throw ArgError("all collision objects of a context share one dHat (Config.cpp:41-45): got a different dHatEps");
     contact = c;
     selfCollision = true;
     dHatEps = eps;
@@ -1177,8 +1169,7 @@ void HipOptimizer::computeConstraintSets()
 {
     if (!ipOn()) return;
     Tic t(timers[14], stream);
-    for (auto& h : planes) h->build(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, dHat); // Optimizer.cpp:2460-2462
-    for (auto& h : rounds) h->build(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, dHat);
+    for (auto* h : colliders) h->build(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, dHat); // Optimizer.cpp:2460-2462
     if (selfCollision) contact->buildConstraintSet(mesh, mesh.d_x.p, mesh.d_dbc.p, dHat); // Optimizer.cpp:2448-2470
 }
 
@@ -1228,27 +1219,15 @@ void HipOptimizer::postLineSearch()
     }
     std::vector<double> d;
     bool updateKappa = false;
-    for (size_t pi = 0; pi < planes.size() && !updateKappa; ++pi) {
+    for (size_t ci = 0; ci < colliders.size() && !updateKappa; ++ci) {
         std::vector<int> verts;
         std::vector<double> was;
         for (size_t i = 0; i < closeHS.size(); ++i)
-            if (closeHS[i].first == (int)pi) {
+            if (closeHS[i].first == (int)ci) {
                 verts.push_back(closeHS[i].second);
                 was.push_back(closeHSVal[i]);
             }
-        planes[pi]->evalDist2(verts, mesh.d_x.p, d);
-        for (size_t i = 0; i < verts.size(); ++i)
-            if (d[i] <= was[i]) updateKappa = true;
-    }
-    for (size_t ri = 0; ri < rounds.size() && !updateKappa; ++ri) {
-        std::vector<int> verts;
-        std::vector<double> was;
-        for (size_t i = 0; i < closeHS.size(); ++i)
-            if (closeHS[i].first == (int)(planes.size() + ri)) {
-                verts.push_back(closeHS[i].second);
-                was.push_back(closeHSVal[i]);
-            }
-        rounds[ri]->evalDist2(verts, mesh.d_x.p, d);
+        colliders[ci]->evalDist2(verts, mesh.d_x.p, d);
         for (size_t i = 0; i < verts.size(); ++i)
             if (d[i] <= was[i]) updateKappa = true;
     }
@@ -1269,19 +1248,12 @@ void HipOptimizer::postLineSearch()
     closeVal.clear();
     closeHS.clear();
     closeHSVal.clear();
-    for (size_t pi = 0; pi < planes.size(); ++pi) {
-        planes[pi]->evalDist2(planes[pi]->set, mesh.d_x.p, d);
-        for (size_t i = 0; i < planes[pi]->set.size(); ++i)
+    for (size_t ci = 0; ci < colliders.size(); ++ci) {
+        const std::vector<int>& set = colliders[ci]->set;
+        colliders[ci]->evalDist2(set, mesh.d_x.p, d);
+        for (size_t i = 0; i < set.size(); ++i)
             if (d[i] < dTol) {
-                closeHS.push_back({ (int)pi, planes[pi]->set[i] });
-                closeHSVal.push_back(d[i]);
-            }
-    }
-    for (size_t ri = 0; ri < rounds.size(); ++ri) {
-        rounds[ri]->evalDist2(rounds[ri]->set, mesh.d_x.p, d);
-        for (size_t i = 0; i < rounds[ri]->set.size(); ++i)
-            if (d[i] < dTol) {
-                closeHS.push_back({ (int)(planes.size() + ri), rounds[ri]->set[i] });
+                closeHS.push_back({ (int)ci, set[i] });
                 closeHSVal.push_back(d[i]);
             }
     }
@@ -1370,12 +1342,9 @@ void HipOptimizer::barrierGradientAdd(bool projectDBC, double kappa_, bool activ
             contact->gradientAdd(mesh.d_x.p, mesh.d_dbc.p, mesh.nV, dHat, kappa_, 0, grad_dev, true, !activeOnly, d_need.p);
         return;
     }
-    for (auto& h : planes) h->gradientAdd(mesh.d_x.p, dHat, kappa_, grad_dev);
-    for (auto& h : rounds) h->gradientAdd(mesh.d_x.p, dHat, kappa_, grad_dev);
+    for (auto* h : colliders) h->gradientAdd(mesh.d_x.p, dHat, kappa_, grad_dev);
     if (!activeOnly && fricDHat > 0.0) { // Optimizer.cpp:3474-3478, 3504-3506
-        for (auto& h : planes)
-            if (h->friction > 0.0) h->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, grad_dev);
-        for (auto& h : rounds)
+        for (auto* h : colliders)
             if (h->friction > 0.0) h->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, grad_dev);
         if (selfCollision && selfFric > 0.0) contact->frictionGradientAdd(mesh.d_x.p, d_xPrev.p, fricDHat, selfFric, grad_dev);
     }
@@ -1611,17 +1580,12 @@ void HipOptimizer::assembleSystem(bool projectDBC, bool withGradient)
     }
     if (ipOn()) { // barrier blocks, PSD-projected per stencil (Optimizer.cpp:3625-3636, 3670-3676)
         // (half-spaces and lagged friction: vertex-wise diagonal blocks / one set, evaluated alike on every rank and added to the rows each rank holds)
-        for (auto& h : planes)
-            h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
-        for (auto& h : rounds)
+        for (auto* h : colliders)
             h->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, dHat, kappa, projectDBC, lin.d_a.p);
         if (selfCollision) // owner-computes: the stencils that touch a row this rank needs
             contact->hessianAdd(mesh.d_x.p, mesh.d_dbc.p, lin, dHat, kappa, projectDBC, lin.d_a.p, owner ? d_need.p : nullptr, /*deferCheck=*/true);
         if (fricDHat > 0.0) { // Optimizer.cpp:3677-3702
-            for (auto& h : planes)
-                if (h->friction > 0.0)
-                    h->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, fricDHat, projectDBC, lin.d_a.p);
-            for (auto& h : rounds)
+            for (auto* h : colliders)
                 if (h->friction > 0.0)
                     h->frictionHessianAdd(mesh.d_x.p, d_xPrev.p, mesh.d_dbc.p, lin.d_rowBase.p, lin.d_rowLen.p, fricDHat, projectDBC, lin.d_a.p);
             if (selfCollision && selfFric > 0.0)
@@ -2007,7 +1971,7 @@ void HipOptimizer::beginTimestep()
     // on the scripted step, the step, inverted after it? the energy there -- is enqueued as ONE batch and read back with one synchronisation (seven before: each
     // question waited for its answer).  Any answer but the usual one ("no", "no") falls back to the general sequence below from the state it left off.
     // (a strain limit or a rubber membrane takes the general sequence: its scripted step is shortened by stepFeasible)
-    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && planes.empty() && rounds.empty() && !(warmStart >= 1 && warmStart <= 5)
+    const bool batched = BEGIN_BATCHED && fastPath() && nHandles && dbcGroups.empty() && !selfCollision && colliders.empty() && !(warmStart >= 1 && warmStart <= 5)
         && !mesh.shell.nLimited() && !mesh.shell.nRubber();
     // With a strain limit the stepper never accepts a state with a stretch at or over it, so a time step may only start from a feasible one.  The energy the
     // stepper holds on the host tells: it is +infinity exactly then (or at the fold of a rod node, which the count below tells apart) -- no device query on
@@ -2090,8 +2054,7 @@ void HipOptimizer::beginTimestep()
         }
         double stepSize = filterStepSize(d_searchDir.p, 1.0);
         if (ipOn()) {
-            for (auto& h : planes) stepSize = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, stepSize);
-            for (auto& h : rounds) stepSize = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, stepSize);
+            for (auto* h : colliders) stepSize = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, stepSize);
             if (selfCollision) stepSize = fullCcd(0.8, stepSize);
         }
         HIP_CHECK(hipMemcpyAsync(d_x0.p, mesh.d_x.p, 3 * (size_t)mesh.nV * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -2111,8 +2074,7 @@ void HipOptimizer::beginTimestep()
         closeVal.clear();
         // friction: lagged sets reset, eps_v^2 h^2 (Optimizer.cpp:1525-1533, 286-304), then lagged at x^n (:1553-1600)
         if (contact) contact->frictionLagClear();
-        for (auto& h : planes) h->lagClear();
-        for (auto& h : rounds) h->lagClear();
+        for (auto* h : colliders) h->lagClear();
         fricDHat0 = epsV * epsV * (ctorDt * ctorDt) * lenScale2(); // Optimizer.cpp:290-303: set once in the constructor, see (ctorDt * ctorDt)
         fricDHatTarget = epsVTarget > 0.0 ? epsVTarget * epsVTarget * (ctorDt * ctorDt) * lenScale2() : fricDHat0;
         fricDHat = solveFric() ? fricDHat0 : -1.0;
@@ -2257,16 +2219,14 @@ bool HipOptimizer::newtonIter()
         Tic t(timers[13], stream);
         t.nosync = specAsmValid && cachedTrialValid; // nothing is enqueued in here on that path, and the stream carries the assembly enqueued ahead
         // (one process, self-contact, no half-spaces between the filter and the CCD: the three bounds come back with one synchronisation, HipContact::stepBounds)
-        const bool batchedBounds = !cachedTrialValid && !cachedE0Valid && selfCollision && planes.empty() && rounds.empty() && worldSize == 1;
+        const bool batchedBounds = !cachedTrialValid && !cachedE0Valid && selfCollision && colliders.empty() && worldSize == 1;
         if (cachedTrialValid) alpha = cachedAlpha; // decided on the device by the same rule, the trial step is already taken with it
         else if (cachedE0Valid) { // Optimizer.cpp:1887 with the value the solve's batch brought back
             if (mesh.needElemInvSafeGuard() && cachedFilter > 0.0 && cachedFilter < alpha) alpha = cachedFilter;
         }
         else if (!batchedBounds)
         alpha = filterStepSize(d_searchDir.p, alpha); // Optimizer.cpp:1887
-        for (auto& h : planes) // slackness_a = 0.9 (:1886-1890)
-            alpha = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, alpha);
-        for (auto& h : rounds)
+        for (auto* h : colliders) // slackness_a = 0.9 (:1886-1890)
             alpha = h->stepBound(contact->nSVI, contact->d_SVI.p, mesh.d_x.p, mesh.d_dbc.p, d_searchDir.p, 0.9, alpha);
         if (selfCollision) {
             // step-size pipeline of Optimizer.cpp:1884-2040: partial CCD over the candidates of the current

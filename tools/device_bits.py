@@ -3,7 +3,10 @@
 Every case runs twice on fresh contexts.  A case whose two runs differ (or that raises) is reported and left out of the final digest: only paths without
 fp64 atomics are listed, so that should not happen.  Sizes: a 14 x 14 x 2 mat stack and a 6 x 6 x 6 bar (item counts between 257 and a few thousand, no
 multiples of 64), and one bar of 65 856 tets for elastic_energy alone, whose reduction strides over more than 256 partial sums.  The step3_* cases run three
-time steps of the stepper and hash positions, energy, step sizes, iteration counts and the contact state after each."""
+time steps of the stepper and hash positions, energy, step sizes, iteration counts and the contact state after each.  The analytic obstacles: the
+half-space on the mat stack and its lagged friction inside the potential, gradient and matrix of a begun time step; a solid sphere, a hollow sphere and
+a capsule on the bar and on a finer bar whose sets span several workgroups (every entry point, the friction pieces and the state query); and a stepper
+case with a plane and a capsule, both with friction, the capsule registered first."""
 import hashlib
 import os
 import sys
@@ -114,7 +117,7 @@ def case_ccd_full():
     return out
 
 
-# ---- hip_halfspace ------------------------------------------------------------------------------------------------------------------------------------------
+# ---- vertex_collider: the half-space ------------------------------------------------------------------------------------------------------------------------
 def case_halfspace():
     c, V, F, Vs, dHat = mat_ctx()
     y0 = float(Vs[:, 1].min())
@@ -128,6 +131,86 @@ def case_halfspace():
     out.append(c.get_a())
     out.append(c.halfspace_step_bound(h, direction(len(V), 9), 0.9, 1.0))
     out.append(c.half_space_move(h, [0.0, 2e-3, 0.0], 0.5))
+    c.close()
+    return out
+
+
+def case_halfspace_friction():
+    # the plane's lagged friction terms at entry-point level.  No entry point takes a half-space's friction alone, so: begin_timestep lags the plane at x^n
+    # (self-contact is off, the plane is the only obstacle), the nodes are then displaced along and off the plane, and the incremental potential, the
+    # Newton gradient and the matrix are taken with the plane's friction and again without it; both enter the digest and have to differ
+    V, F = scene.make_bar(6, 6, 6, size=(3.0, 1.0, 1.0))
+    c = ipc_amd.Context(0)
+    c.set_mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+    c.opt_init(DT, True)
+    c.set_surface(scene.surface_tris(F))
+    h = c.add_half_space([0.0, float(V[:, 1].min()) - 2e-3, 0.0], [1e-3, 1.0, -5e-4])  # (tilted a little: no component of the normal is zero)
+    c.set_half_space_friction(h, 0.3)
+    c.precompute()
+    c.begin_timestep()
+    fs = c.friction_state()
+    assert fs["n_half_space_lagged"] > 16 and fs["n_lagged"] == 0 and fs["fricDHat"] > 0.0, fs
+    d = 100.0 * direction(len(V), 7) * np.sqrt(fs["fricDHat"])  # displacements of the order of eps_v h: sticking and sliding entries
+    d[:, 1] = np.abs(d[:, 1])
+    c.set_positions(c.state()["V"] + d)
+    out = [fs]
+    for mu in (0.3, 0.0):
+        c.set_half_space_friction(h, mu)
+        out += [c.incremental_potential(DT * DT), c.assemble_newton(DT * DT, True), c.get_a()]
+    assert out[1] != out[4] and not np.array_equal(out[2], out[5]) and not np.array_equal(out[3], out[6]), "the plane's friction terms did not act"
+    c.close()
+    return out
+
+
+# ---- round colliders: a solid sphere under the 6 x 6 x 6 bar, a hollow sphere around it, a capsule along its bottom face -----------------------------------
+ROUNDS = [dict(p0=[0.1, -1.6, 0.05], p1=[0.1, -1.6, 0.05], R=1.0, hollow=False, dHat=0.25, delta=[0.0, 0.2, 0.0]),
+          dict(p0=[0.05, 0.02, -0.03], p1=[0.05, 0.02, -0.03], R=1.8, hollow=True, dHat=1.0, delta=[0.3, 0.0, 0.0]),
+          dict(p0=[-1.0, -0.8, 0.02], p1=[1.1, -0.78, -0.04], R=0.25, hollow=False, dHat=0.16, delta=[0.0, 0.1, 0.0])]
+
+
+def round_ctx(n=(6, 6, 6)):
+    V, F = scene.make_bar(*n, size=(3.0, 1.0, 1.0))
+    Vs = scene.jitter(V, F, rel=2e-3)
+    left, _ = scene.border_verts(V, 0.01)
+    c = ipc_amd.Context(0)
+    c.set_mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+    c.set_dbc(left, 1)
+    c.set_positions(Vs)
+    c.opt_init(DT, True)
+    c.set_surface(scene.surface_tris(F))
+    c.set_pattern()
+    ids = [c.add_round_collider(r["p0"], r["p1"], r["R"], r["hollow"]) for r in ROUNDS]
+    return c, V, Vs, ids
+
+
+def case_round_barrier(n=(6, 6, 6), at_least=(16, 16, 16)):
+    c, V, Vs, ids = round_ctx(n)
+    out = []
+    for k, (i, r) in enumerate(zip(ids, ROUNDS)):
+        verts = c.round_build(i, r["dHat"])
+        assert len(verts) > at_least[k] and len(verts) % 64, (k, len(verts))
+        out += [verts, c.round_energy(i, r["dHat"], KAPPA), c.round_gradient_add(i, r["dHat"], KAPPA)]
+        c.set_zero()
+        c.round_hessian_add(i, r["dHat"], KAPPA, True)
+        out += [c.get_a(), c.round_step_bound(i, 10.0 * direction(len(V), 9 + k), 0.9, 1.0)]
+    for i, r in zip(ids, ROUNDS):  # (the moves last: the three share one set of positions)
+        out += [c.round_move(i, r["delta"], 0.5), c.round_get(i)]
+    c.close()
+    return out
+
+
+def case_round_friction(n=(6, 6, 6), which=2, at_least=16):
+    c, V, Vs, ids = round_ctx(n)
+    i, r = ids[which], ROUNDS[which]
+    c.set_round_collider_friction(i, 0.4)
+    out = [c.round_build(i, r["dHat"]), c.round_lag_update(i, r["dHat"], KAPPA)]
+    assert out[1] > at_least and out[1] % 64, out[1]
+    Vprev = Vs + direction(len(V), 7) * 0.05
+    eps2 = 1e-8
+    out += [c.round_friction_energy(i, Vprev, eps2), c.round_friction_gradient_add(i, Vprev, eps2)]
+    c.set_zero()
+    c.round_friction_hessian_add(i, Vprev, eps2, True)
+    out += [c.get_a(), c.round_state(i, r["dHat"], KAPPA)]
     c.close()
     return out
 
@@ -279,13 +362,46 @@ def case_step_mats(ccd_mode):
     return run
 
 
+def case_step_plane_capsule():
+    # the 6 x 6 x 6 bar sliding along +x under gravity on a plane and a capsule that lies in it, both with friction; the capsule is registered BEFORE the
+    # plane (the stepper walks the planes first whatever the order of registration)
+    V, F = scene.make_bar(6, 6, 6, size=(3.0, 1.0, 1.0))
+    c = ipc_amd.Context(0)
+    c.set_mesh(V, F, YM=1e5, PR=0.4, density=1000.0)
+    c.opt_init(DT, True)
+    c.set_surface(scene.surface_tris(F))
+    y0 = float(V[:, 1].min()) - 2e-3
+    r = c.add_round_collider([-1.0, y0 - 0.2, 0.0], [1.0, y0 - 0.2, 0.0], 0.2)
+    h = c.add_half_space([0.0, y0, 0.0], [0.0, 1.0, 0.0])
+    c.set_round_collider_friction(r, 0.4)
+    c.set_half_space_friction(h, 0.3)
+    c.set_velocity(np.tile([0.5, 0.0, 0.0], (len(V), 1)))
+    c.precompute()
+    seen = []
+
+    def extra(c):
+        s = c.round_state(r)
+        seen.append((s["n"], c.friction_state()["n_half_space_lagged"]))
+        return [s, c.round_get(r)]
+    out = stepped(c, contact=True, extra=extra)
+    assert all(a > 0 and b > 0 for a, b in seen), seen  # both obstacles act in every step
+    return out
+
+
 CASES = [("elastic_energy+incremental_potential+check_inversion+filter_step_size", case_elastic), ("elastic_energy_65k_tets", case_elastic_energy_large),
          ("contact_energy+gradient_add+hessian_add", case_contact), ("friction_energy+gradient+hessian+contact_report", case_friction_and_report),
          ("ccd_full", case_ccd_full), ("halfspace_energy+hessian_add+step_bound+move", case_halfspace), ("pcg_block_jacobi", case_pcg(0)),
          ("pcg_lagged_factor", case_pcg(1)), ("pcg_two_level", case_pcg(2)), ("chamber_energy+gas_state", case_chamber), ("shell_stretch", case_shell_stretch),
          ("newton_12_steps_friction_halfspace", case_newton_steps), ("step3_bar_NH_fast_path", case_step_bar("NH")), ("step3_bar_FCR", case_step_bar("FCR")),
          ("step3_bar_damping_neumann", case_step_damping_neumann), ("step3_bar_moving_dirichlet_penalty", case_step_mdbc),
-         ("step3_mats_self_collision_friction", case_step_mats(0)), ("step3_mats_reference_ccd", case_step_mats(1))]
+         ("step3_mats_self_collision_friction", case_step_mats(0)), ("step3_mats_reference_ccd", case_step_mats(1)),
+         ("round_build+energy+gradient+hessian+step_bound+move+get_x3", case_round_barrier),
+         ("round_lag_update+friction_energy+gradient+hessian+state", case_round_friction),
+         # (the same on a 24 x 10 x 10 bar, 1 162 surface vertices: sets of more than one workgroup, the friction pieces on the hollow sphere)
+         ("round_barrier_x3_fine_bar", lambda: case_round_barrier((24, 10, 10), (64, 512, 256))),
+         ("round_friction+state_fine_bar", lambda: case_round_friction((24, 10, 10), 1, 512)),
+         ("halfspace_lagged_friction_in_potential+gradient+matrix", case_halfspace_friction),
+         ("step3_bar_capsule_then_plane_friction", case_step_plane_capsule)]
 
 
 def main():

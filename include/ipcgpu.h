@@ -429,6 +429,40 @@ int ipcgpu_shell_rubber_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
 int ipcgpu_shell_rubber_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
 int ipcgpu_shell_rubber_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
 int ipcgpu_shell_thickness(ipcgpu_ctx*, double* h_nTri);
+/* Woven cloth of the shell (no counterpart in the reference): an orthotropic St. Venant-Kirchhoff membrane on chosen triangles, in place of their isotropic
+ * one, and direction-dependent bending.  The model is stated in ipc_amd/csrc/shell_weave_kernels.h.  With F and G = (F^T F - I) / 2 the membrane's, a the unit
+ * warp direction in the triangle's rest plane and b the weft at right angles to it:  Eww = a^T G a, Eff = b^T G b, Ewf = a^T G b,
+ *   W = h A (C11 Eww^2 / 2 + C12 Eww Eff + C22 Eff^2 / 2 + 2 G12 Ewf^2),  C11 = E1 / (1 - nu12 nu21),  C22 = E2 / (1 - nu12 nu21),  C12 = nu12 E2 / (1 - nu12 nu21),
+ *   nu21 = nu12 E2 / E1.  Exact gradient; the exact Hessian with its eigenvalues clamped at 0 per triangle.  A polynomial in F: finite at every finite state.
+ *   With E1 = E2 = E, nu12 = nu, G12 = E / (2 (1 + nu)) it is the StVK membrane for every direction.  The E and nu given to ipcgpu_set_shell are not read by
+ *   this term on a woven triangle (they still enter the bending constant k_b of its hinges).
+ *   Bending: the stiffness of a hinge whose rest edge makes the angle phi with the warp is multiplied by the mean over its two triangles of
+ *   bendWarp sin^2 phi + bendWeft cos^2 phi (a triangle that is not woven counts 1): an edge along the weft curves the warp yarns.
+ * ipcgpu_shell_set_weave: woven per triangle, 0 = as without this call, 1 = woven; dir: 3 per triangle (x, y, z of triangle t at 3 t), a vector of rest space,
+ *   projected into the triangle's rest plane and normalised; E1 (warp), E2 (weft), G12 (shear), nu12 (null: 0), bendWarp, bendWeft (null: 1) per triangle; all
+ *   read where woven is 1.  All selectors zero, or a null woven, removes the term.  After ipcgpu_set_shell (without a shell: IPCGPU_ERR_STATE), at any time
+ *   between steps, before or after ipcgpu_opt_init: it changes no mass and adds no node pair.  ipcgpu_set_shell and ipcgpu_set_mesh drop it.  IPCGPU_ERR_ARG,
+ *   the message naming the triangle and nothing changed: a selector other than 0 or 1; a value that is not finite; E1, E2 or G12 <= 0; nu12^2 >= E1 / E2; a bend
+ *   factor <= 0; a direction of zero length, or one normal to the triangle (its projection shorter than 1e-6 of its length).  A woven triangle can be neither
+ *   rubber nor plastic (flow rewrites the rest metric, in which a and b would stop being orthonormal): IPCGPU_ERR_UNSUPPORTED naming the triangle from this call
+ *   on a rubber or plastic triangle, from ipcgpu_shell_set_membrane with rubber on a woven triangle and from ipcgpu_shell_set_plasticity on a woven triangle.
+ *   A strain limit on the same triangle composes unchanged; ipcgpu_shell_thickness returns the rest h there; ipcgpu_shell_get keeps returning the plan's values.
+ * With woven triangles the term is part of the shell energy everywhere: ipcgpu_shell_energy, ipcgpu_shell_gradient_add and ipcgpu_shell_hessian_add include it,
+ *   and so do the time stepper and the stiffness damping.  Without one none of its kernels is launched and every result is bit-identical to a context that
+ *   never made this call.
+ * ipcgpu_shell_weave_get: woven (nTri), a (nTri x 2, row-major: a_x, a_y in the rest frame whose first axis runs along X1 - X0), const4 (nTri x 4, row-major:
+ *   C11, C12, C22, G12, without h A) -- zeros on a triangle that is not woven -- and the factor per hinge (1 without the term); any pointer may be null.
+ * ipcgpu_shell_weave_energy / _energy_per_elem / _gradient_add / _hessian_add: the term alone, with the semantics of the ipcgpu_shell_rubber_* namesakes (any
+ *   coef).  ipcgpu_shell_weave_state: column-major nTri x 6 -- Eww, Eff, the shear angle asin((F a) . (F b) / (|F a| |F b|)) and the current unit warp direction
+ *   F a / |F a| (x, y, z); NaN where a length it divides by is 0, zeros on a triangle that is not woven.  Without a shell these return IPCGPU_OK and do nothing. */
+int ipcgpu_shell_set_weave(ipcgpu_ctx*, const int* woven_nTri, const double* dir_3nTri, const double* E1_nTri, const double* E2_nTri, const double* G12_nTri,
+                           const double* nu12_nTri, const double* bendWarp_nTri, const double* bendWeft_nTri);
+int ipcgpu_shell_weave_get(ipcgpu_ctx*, int* woven_nTri, double* a_2nTri, double* const4_nTri, double* hingeFactor_nHinge);
+int ipcgpu_shell_weave_energy(ipcgpu_ctx*, double coef, double* energy);
+int ipcgpu_shell_weave_energy_per_elem(ipcgpu_ctx*, double* perTri_nTri);
+int ipcgpu_shell_weave_gradient_add(ipcgpu_ctx*, double coef, int projectDBC, double* grad_3nV);
+int ipcgpu_shell_weave_hessian_add(ipcgpu_ctx*, double coef, int projectDBC);
+int ipcgpu_shell_weave_state(ipcgpu_ctx*, double* perTri_nTrix6);
 /* ---- Plastic flow of the shell: permanent stretch, creases and dents.  No counterpart in the reference (it has no shell and no plasticity).  The model is
  * stated in ipc_amd/csrc/shell_plastic_kernels.h.  Every shell kernel reads the rest shape of a triangle from B = Dm^-1 (rows 0-3 of its constants) and of a
  * hinge from thetaBar, so at the end of every time step (after the BE / Newmark update, before the lagged damping matrix) two kernels rewrite those records:

@@ -17,9 +17,9 @@ LIB = os.path.join(HERE, "libipcgpu.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
-SOURCES = ["nh_kernels.hip", "patch_assembly.hip", "hip_contact.hip", "vertex_collider.hip", "mf_numeric.hip", "mf_sweeps.hip", "mf_exchange.hip", "hip_linsys.hip", "pcg.hip", "shell_kernels.hip", "shell_limit_kernels.hip", "shell_rubber_kernels.hip", "rod_kernels.hip", "attach_kernels.hip", "chamber_kernels.hip", "aero_kernels.hip", "plastic_kernels.hip", "fiber_kernels.hip", "shell_plastic_kernels.hip", "mf_symbolic.cpp", "mf_plan.cpp", "report_plan.cpp", "contact_report_plan.cpp", "stress_plan.cpp", "contact_groups.cpp", "shell_plan.cpp", "shell_limit_plan.cpp", "shell_rubber_plan.cpp", "rod_plan.cpp", "attach_plan.cpp", "chamber_plan.cpp", "aero_plan.cpp", "plastic_plan.cpp", "fiber_plan.cpp", "shell_plastic_plan.cpp", "round_collider_plan.cpp", "contact_pattern.cpp", "pcg_coarse.cpp", "hip_mesh.cpp",
+SOURCES = ["nh_kernels.hip", "patch_assembly.hip", "hip_contact.hip", "vertex_collider.hip", "mf_numeric.hip", "mf_sweeps.hip", "mf_exchange.hip", "hip_linsys.hip", "pcg.hip", "shell_kernels.hip", "shell_limit_kernels.hip", "shell_rubber_kernels.hip", "shell_weave_kernels.hip", "rod_kernels.hip", "attach_kernels.hip", "chamber_kernels.hip", "aero_kernels.hip", "plastic_kernels.hip", "fiber_kernels.hip", "shell_plastic_kernels.hip", "mf_symbolic.cpp", "mf_plan.cpp", "report_plan.cpp", "contact_report_plan.cpp", "stress_plan.cpp", "contact_groups.cpp", "shell_plan.cpp", "shell_limit_plan.cpp", "shell_rubber_plan.cpp", "shell_weave_plan.cpp", "rod_plan.cpp", "attach_plan.cpp", "chamber_plan.cpp", "aero_plan.cpp", "plastic_plan.cpp", "fiber_plan.cpp", "shell_plastic_plan.cpp", "round_collider_plan.cpp", "contact_pattern.cpp", "pcg_coarse.cpp", "hip_mesh.cpp",
            "hip_optimizer.cpp", "msh_io.cpp", "capi.cpp"]
-FMA_OK = {"nh_kernels.hip", "patch_assembly.hip", "shell_kernels.hip", "shell_limit_kernels.hip", "shell_rubber_kernels.hip", "rod_kernels.hip", "attach_kernels.hip", "chamber_kernels.hip", "aero_kernels.hip", "fiber_kernels.hip", "mf_numeric.hip", "mf_sweeps.hip", "mf_exchange.hip"}
+FMA_OK = {"nh_kernels.hip", "patch_assembly.hip", "shell_kernels.hip", "shell_limit_kernels.hip", "shell_rubber_kernels.hip", "shell_weave_kernels.hip", "rod_kernels.hip", "attach_kernels.hip", "chamber_kernels.hip", "aero_kernels.hip", "fiber_kernels.hip", "mf_numeric.hip", "mf_sweeps.hip", "mf_exchange.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", f"-I{ROCM}/include", f"-I{os.path.join(HERE, '..', 'include')}"]
 

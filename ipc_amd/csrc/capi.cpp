@@ -113,10 +113,10 @@ void downloadColMajor(ipcgpu_ctx* c, const DevBuf<double>& src, double* Vcm)
 }
 
 // ---- what the entry points of the codimensional energies (shells, their strain limit, rods) share -------------------------------------------
-// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its rubber membrane and its limit, ipcgpu_shell_limit_* the limit alone,
-// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers, ipcgpu_aero_* wind and air drag, ipcgpu_fiber_* the fibres of the tetrahedra.
-constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_RUBBER | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT,
-                   RUBBER_ALONE = HipOptimizer::CODIM_SHELL_RUBBER, ROD = HipOptimizer::CODIM_ROD,
+// `which` is a mask of HipOptimizer::CODIM_*: ipcgpu_shell_* mean the shell with its rubber membrane, its woven cloth and its limit, ipcgpu_shell_limit_* the limit alone,
+// ipcgpu_shell_rubber_* the rubber membrane alone, ipcgpu_shell_weave_* the woven cloth alone, ipcgpu_rod_* the rod, ipcgpu_attach_* the attachments, ipcgpu_chamber_* the pressure chambers, ipcgpu_aero_* wind and air drag, ipcgpu_fiber_* the fibres of the tetrahedra.
+constexpr unsigned SHELL_AND_LIMIT = HipOptimizer::CODIM_SHELL | HipOptimizer::CODIM_SHELL_RUBBER | HipOptimizer::CODIM_SHELL_WEAVE | HipOptimizer::CODIM_SHELL_LIMIT, LIMIT_ALONE = HipOptimizer::CODIM_SHELL_LIMIT,
+                   RUBBER_ALONE = HipOptimizer::CODIM_SHELL_RUBBER, WEAVE_ALONE = HipOptimizer::CODIM_SHELL_WEAVE, ROD = HipOptimizer::CODIM_ROD,
                    ATTACH = HipOptimizer::CODIM_ATTACH, CHAMBER = HipOptimizer::CODIM_CHAMBER, AERO = HipOptimizer::CODIM_AERO, FIBER = HipOptimizer::CODIM_FIBER;
 const char* const SHELL_MISS = "the pattern lacks a block of the shell Hessian: build it after ipcgpu_set_shell";
 const char* const ROD_MISS = "the pattern lacks a block of the rod Hessian: build it after ipcgpu_set_rod";
@@ -124,12 +124,13 @@ const char* const ATTACH_MISS = "the pattern lacks a block of the attachment Hes
 const char* const CHAMBER_MISS = "the pattern lacks a block of the chamber Hessian: build it after ipcgpu_set_chambers";
 const char* const AERO_MISS = "the pattern lacks a block of the air-drag Hessian: build it after ipcgpu_set_aero";
 const char* const FIBER_MISS = "the pattern lacks a block of the fibre Hessian: it does not hold the node pairs of the tetrahedra";
-// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no segment, no attachment, no chamber triangle, no aerodynamic triangle, no fibred element.
+// What an entry point returns early on: no triangle, no limited triangle, no rubber triangle, no woven triangle, no segment, no attachment, no chamber triangle, no aerodynamic triangle, no fibred element.
 int codimCount(const HipMesh& m, unsigned which)
 {
     return (which & HipOptimizer::CODIM_SHELL) ? m.shell.nTri()
         : (which & HipOptimizer::CODIM_SHELL_LIMIT) ? m.shell.nLimited()
         : (which & HipOptimizer::CODIM_SHELL_RUBBER) ? m.shell.nRubber()
+        : (which & HipOptimizer::CODIM_SHELL_WEAVE) ? m.shell.nWoven()
         : (which & HipOptimizer::CODIM_ROD)         ? m.rod.nSeg()
         : (which & HipOptimizer::CODIM_ATTACH)      ? m.attach.n()
         : (which & HipOptimizer::CODIM_CHAMBER)     ? m.chamber.nTri()
@@ -1211,6 +1212,77 @@ int ipcgpu_shell_thickness(ipcgpu_ctx* c, double* h)
         std::vector<double> sigma(2 * (size_t)sh.nTri());
         o.shellStretch(sigma.data(), nullptr, nullptr);
         for (int t : sh.rubber.tri) h[t] = sh.plan.thickness[(size_t)t] / (sigma[2 * (size_t)t] * sigma[2 * (size_t)t + 1]); // incompressible: lambda_3 = 1 / (sigma1 sigma2)
+        return IPCGPU_OK;
+    });
+}
+// ---- Woven cloth of the shells (shell_weave_kernels.h; the reference has no counterpart) ----------------------------------------------------------
+int ipcgpu_shell_set_weave(ipcgpu_ctx* c, const int* woven, const double* dir, const double* E1, const double* E2, const double* G12, const double* nu12,
+    const double* bendWarp, const double* bendWeft)
+{
+    specChanged(c);
+    return guarded([&] {
+        HipMesh& m = M(c);
+        bind(c);
+        m.setShellWeave(woven, dir, E1, E2, G12, nu12, bendWarp, bendWeft, c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_weave_get(ipcgpu_ctx* c, int* woven, double* a, double* const4, double* hingeFactor)
+{
+    return guarded([&] {
+        const HipShell& sh = M(c).shell;
+        if (woven) std::fill(woven, woven + sh.nTri(), 0);
+        if (a) std::fill(a, a + 2 * (size_t)sh.nTri(), 0.0);
+        if (const4) std::fill(const4, const4 + 4 * (size_t)sh.nTri(), 0.0);
+        if (hingeFactor) std::fill(hingeFactor, hingeFactor + sh.nHinge(), 1.0);
+        if (!sh.nWoven()) return IPCGPU_OK;
+        if (woven) std::copy(sh.weave.woven.begin(), sh.weave.woven.end(), woven);
+        if (a) std::copy(sh.weave.a.begin(), sh.weave.a.end(), a);
+        if (const4) std::copy(sh.weave.const4.begin(), sh.weave.const4.end(), const4);
+        if (hingeFactor) std::copy(sh.weave.hingeFactor.begin(), sh.weave.hingeFactor.end(), hingeFactor);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_weave_energy(ipcgpu_ctx* c, double coef, double* E)
+{
+    return guarded([&] { return codimEnergy(c, WEAVE_ALONE, coef, E); });
+}
+int ipcgpu_shell_weave_energy_per_elem(ipcgpu_ctx* c, double* perTri)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri() || !perTri) return IPCGPU_OK;
+        DevBuf<double> t;
+        t.alloc(sh.nTri());
+        launch_shell_weave_energy_per_elem(o.shellWeaveView(c->mesh->d_x.p), t.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        t.download(perTri, sh.nTri(), c->stream);
+        return IPCGPU_OK;
+    });
+}
+int ipcgpu_shell_weave_gradient_add(ipcgpu_ctx* c, double coef, int projectDBC, double* g)
+{
+    return guarded([&] { return codimGradientAdd(c, WEAVE_ALONE, coef, projectDBC, g); });
+}
+int ipcgpu_shell_weave_hessian_add(ipcgpu_ctx* c, double coef, int projectDBC)
+{
+    specChanged(c);
+    return guarded([&] { return codimHessianAdd(c, WEAVE_ALONE, coef, projectDBC, SHELL_MISS); });
+}
+int ipcgpu_shell_weave_state(ipcgpu_ctx* c, double* perTri6)
+{
+    return guarded([&] {
+        HipOptimizer& o = O(c);
+        bind(c);
+        const HipShell& sh = c->mesh->shell;
+        if (!sh.nTri() || !perTri6) return IPCGPU_OK;
+        DevBuf<double> t;
+        t.alloc(6 * (size_t)sh.nTri());
+        launch_shell_weave_state(o.shellWeaveView(c->mesh->d_x.p), t.p, c->stream);
+        HIP_CHECK(hipGetLastError());
+        t.download(perTri6, 6 * (size_t)sh.nTri(), c->stream);
         return IPCGPU_OK;
     });
 }

@@ -39,6 +39,8 @@
 #include "shell_plastic_plan.h"
 #include "shell_rubber_kernels.h"
 #include "shell_rubber_plan.h"
+#include "shell_weave_kernels.h"
+#include "shell_weave_plan.h"
 #include "stress_plan.h"
 #include <map>
 #include <memory>
@@ -94,6 +96,13 @@ struct HipShell {
     DevBuf<double> d_rubConst, d_rubCount;
     bool rubberUnchecked = false;
     int nRubber() const { return rubber.nRubber; }
+    // woven cloth (ipcgpu_shell_set_weave; shell_weave_plan.h): arrays of its own beside the shell's.  nWoven() == 0: no triangle is woven, none of the weave
+    // kernels is launched, d_triConst holds no zeros of this term and row 1 of d_hingeConst is the plan's bendScale k_b w_e; otherwise d_triConst holds zeros
+    // for the two StVK constants of the woven triangles and row 1 of d_hingeConst carries the plan's hinge factors
+    ShellWeavePlan weave;
+    DevBuf<int> d_wovTri;
+    DevBuf<double> d_wovConst;
+    int nWoven() const { return weave.nWoven; }
     HipShellPlastic plastic; // (its own struct above)
 };
 
@@ -231,6 +240,12 @@ public:
     // shell's triConst with the StVK constants of those triangles zeroed (the plan's own where none is rubber).  All models zero (or null) removes the term;
     // setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair (the blocks are the membrane's).
     void setShellMembrane(const int* model, const double* alpha, hipStream_t s);
+    // Woven cloth of the shell's triangles (shell_weave_plan.h): validates, uploads the compact list of the woven triangles with their constants, the shell's
+    // triConst with the StVK constants of those triangles zeroed, and row 1 of hingeConst times the plan's hinge factors (both the shell plan's own once no
+    // triangle is woven).  All selectors zero (or null) removes the term; setShell and computeFeatures drop it.  Changes no mass and adds no neighbour pair.
+    void setShellWeave(const int* woven, const double* dir, const double* E1, const double* E2, const double* G12, const double* nu12, const double* bendWarp,
+        const double* bendWeft, hipStream_t s);
+    void uploadShellTriConst(hipStream_t s); // rows 4 and 5 of d_triConst from the shell plan, zeroed where the rubber or the weave plan says so; rows 0-3 kept where they may have flowed
     // Plastic flow of the shell (shell_plastic_plan.h): validates, uploads the parameter arrays; the first call allocates alpha = alphaB = 0 and keeps the
     // copies B0 and thetaBar0 of the device records.  Touches no mass, no neighbour pair and no pattern; setShell and computeFeatures drop it.
     void setShellPlasticity(int triBegin, int triEnd, double yield, double bendYield, double creep, double harden, hipStream_t s);
@@ -439,18 +454,19 @@ public:
     double fullCcd(double slackness, double stepSize); // the full sweep of the search direction in the mode of the contact handler
     bool checkInversion(bool meshQuery = false); // true: no element has det < 0; without meshQuery also whenever the energy has no inversion safeguard
     ElemView view() const;
-    // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h, aero_kernels.h) enter wherever the tetrahedral elastic term does, with the same
-    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, limit, rod, attachments, chambers, air drag (the energy sum
-    // is (((((((E + shell) + rubber) + limit) + rod) + attach) + chamber) + aero) + fiber) and launch a term only where the mesh has it (nTri(), nRubber(), nLimited(), nSeg(), attach.n(), chamber.nTri(), aero.nTri(), fiber.n()); none of them is ever sharded.
+    // The codimensional terms (shell_kernels.h, shell_rubber_kernels.h, shell_weave_kernels.h, shell_limit_kernels.h, rod_kernels.h, attach_kernels.h, chamber_kernels.h, aero_kernels.h) enter wherever the tetrahedral elastic term does, with the same
+    // coefficient, through the two members below and nowhere else.  Both walk the terms in the fixed order shell, rubber, weave, limit, rod, attachments, chambers, air drag (the energy sum
+    // is ((((((((E + shell) + rubber) + weave) + limit) + rod) + attach) + chamber) + aero) + fiber) and launch a term only where the mesh has it (nTri(), nRubber(), nWoven(), nLimited(), nSeg(), attach.n(), chamber.nTri(), aero.nTri(), fiber.n()); none of them is ever sharded.
     // CODIM_STIFFNESS: the terms that enter the lagged stiffness damping -- a pressure load is no stiffness, and neither is air drag; the fibre term is one.
     enum : unsigned {
-        CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_AERO = 64, CODIM_FIBER = 128, CODIM_ALL = 255,
+        CODIM_SHELL = 1, CODIM_SHELL_LIMIT = 2, CODIM_ROD = 4, CODIM_ATTACH = 8, CODIM_CHAMBER = 16, CODIM_SHELL_RUBBER = 32, CODIM_AERO = 64, CODIM_FIBER = 128, CODIM_SHELL_WEAVE = 256, CODIM_ALL = 511,
         CODIM_STIFFNESS = CODIM_ALL & ~CODIM_CHAMBER & ~CODIM_AERO
     };
     CodimBase codimBase(const double* x_dev) const;
     ShellView shellView(const double* x_dev) const;
     ShellLimitView shellLimitView(const double* x_dev) const;
     ShellRubberView shellRubberView(const double* x_dev) const;
+    ShellWeaveView shellWeaveView(const double* x_dev) const;
     RodView rodView(const double* x_dev) const;
     AttachView attachView(const double* x_dev) const;
     FiberView fiberView(const double* x_dev) const;

@@ -35,6 +35,7 @@ void HipMesh::computeFeatures(int nV_, int nT_, const double* Vr, const int* Fc,
     if (shell.nTri()) shell.plan = ShellPlan(); // the shell belongs to the previous mesh
     shell.limit = ShellLimitPlan(); // ... and its strain limit with it
     shell.rubber = ShellRubberPlan(); // ... and its rubber membrane
+    shell.weave = ShellWeavePlan(); // ... and its woven cloth
     shell.plastic.drop(); // ... and its plastic parameters and history
     if (rod.nSeg()) rod.plan = RodPlan(); // ... and so does the rod
     if (attach.n()) attach.plan = AttachPlan(); // ... and so do the attachments
@@ -214,6 +215,7 @@ void HipMesh::setShell(int nTri, const int* tri, const double* thickness, const 
     shell.plan = std::move(plan);
     shell.limit = ShellLimitPlan(); // a strain limit belongs to the shell it was set on
     shell.rubber = ShellRubberPlan(); // ... and so does a rubber membrane (d_triConst below is the new plan's own)
+    shell.weave = ShellWeavePlan(); // ... and a woven cloth (d_triConst and row 1 of d_hingeConst below are the new plan's own)
     shell.plastic.drop(); // ... and the plastic parameters and history (d_triConst and d_hingeConst below are the new plan's own)
     shell.bendScale = bendScale;
     const ShellPlan& p = shell.plan;
@@ -251,6 +253,15 @@ void HipMesh::setShellStrainLimit(const double* limit, const double* onset, cons
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
+void HipMesh::uploadShellTriConst(hipStream_t s)
+{
+    // (the shell plan's own once the last rubber and the last woven triangle are gone)
+    std::vector<double> triConst = shellTriConstWithoutWeave(shellTriConstWithoutRubber(shell.plan.triConst, shell.rubber), shell.weave);
+    if (shell.plastic.allocated()) // rows 0-3 on the device may have flowed: they stay what they are, rows 4-5 alone are new
+        shell.d_triConst.download(triConst.data(), 4 * (size_t)shell.nTri(), s);
+    shell.d_triConst.upload(triConst, s);
+}
+
 void HipMesh::setShellMembrane(const int* model, const double* alpha, hipStream_t s)
 {
     if (!shell.nTri()) throw StateError("shell_set_membrane: no shell is set (call ipcgpu_set_shell first)");
@@ -260,17 +271,42 @@ void HipMesh::setShellMembrane(const int* model, const double* alpha, hipStream_
     if (!plan.nRubber && !shell.rubber.nRubber) return; // StVK before and after: nothing is touched
     for (int t : plan.tri) // (shell_plastic_kernels.h: rows 4 and 5 of a rubber triangle are zero, its strain norm has no meaning)
         if (shellPlasticTriOn(shell.plastic.plan, t)) throw UnsupportedError("shell_set_membrane: rubber on a plastic triangle (triangle " + std::to_string(t) + ")");
+    if (shell.nWoven())
+        for (int t : plan.tri)
+            if (shell.weave.woven[(size_t)t]) throw UnsupportedError("shell_set_membrane: rubber on a woven triangle (triangle " + std::to_string(t) + ")");
     shell.rubber = std::move(plan);
     shell.rubberUnchecked = shell.rubber.nRubber > 0;
-    std::vector<double> triConst = shellTriConstWithoutRubber(shell.plan.triConst, shell.rubber); // (the plan's own once the last rubber triangle is gone)
-    if (shell.plastic.allocated()) // rows 0-3 on the device may have flowed: they stay what they are, rows 4-5 alone are new
-        shell.d_triConst.download(triConst.data(), 4 * (size_t)shell.nTri(), s);
-    shell.d_triConst.upload(triConst, s);
+    uploadShellTriConst(s);
     if (shell.rubber.nRubber) {
         shell.d_rubTri.upload(shell.rubber.tri, s);
         shell.d_rubConst.upload(shell.rubber.rubConst, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void HipMesh::setShellWeave(const int* woven, const double* dir, const double* E1, const double* E2, const double* G12, const double* nu12, const double* bendWarp,
+    const double* bendWeft, hipStream_t s)
+{
+    if (!shell.nTri()) throw StateError("shell_set_weave: no shell is set (call ipcgpu_set_shell first)");
+    ShellWeavePlan plan;
+    std::string err;
+    if (!buildShellWeavePlan(shell.plan, nV, V_rest.data(), woven, dir, E1, E2, G12, nu12, bendWarp, bendWeft, plan, err)) throw ArgError(err);
+    if (!plan.nWoven && !shell.weave.nWoven) return; // no woven triangle before and after: nothing is touched
+    // (flow rewrites Dm^-1, and a, b would stop being orthonormal in the new rest metric; a rubber triangle has its own membrane law)
+    for (int t : plan.tri) {
+        if (shell.nRubber() && shell.rubber.model[(size_t)t]) throw UnsupportedError("shell_set_weave: triangle " + std::to_string(t) + " carries the rubber membrane");
+        if (shellPlasticTriOn(shell.plastic.plan, t)) throw UnsupportedError("shell_set_weave: triangle " + std::to_string(t) + " is plastic");
+    }
+    shell.weave = std::move(plan);
+    uploadShellTriConst(s);
+    const std::vector<double> k = shellHingeStiffnessWithWeave(shell.plan, shell.bendScale, shell.weave); // (the plan's own once the last woven triangle is gone)
+    if (!k.empty()) // row 1 alone: row 0, the rest angles, may have flowed
+        HIP_CHECK(hipMemcpyAsync(shell.d_hingeConst.p + k.size(), k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (shell.weave.nWoven) {
+        shell.d_wovTri.upload(shell.weave.tri, s);
+        shell.d_wovConst.upload(shell.weave.wovConst, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s)); // (k leaves scope)
 }
 
 void HipMesh::uploadShellPlasticParams(hipStream_t s)
@@ -322,6 +358,9 @@ void HipMesh::setShellPlasticity(int triBegin, int triEnd, double yield, double 
     if (shell.nRubber() && (yield < INFINITY || bendYield < INFINITY)) // (the plan refuses a rubber triangle too when handed the models; here it is its own error class)
         for (int t = triBegin; t < triEnd; ++t)
             if (shell.rubber.model[t]) throw UnsupportedError("shell_set_plasticity: triangle " + std::to_string(t) + " carries the rubber membrane");
+    if (shell.nWoven() && (yield < INFINITY || bendYield < INFINITY)) // (flow rewrites Dm^-1: the warp and weft directions would stop being orthonormal in the new rest metric)
+        for (int t = triBegin; t < triEnd; ++t)
+            if (shell.weave.woven[t]) throw UnsupportedError("shell_set_plasticity: triangle " + std::to_string(t) + " is woven");
     ensureShellPlastic(s);
     shell.plastic.plan = std::move(next);
     uploadShellPlasticParams(s);

@@ -83,6 +83,7 @@ ElemView HipOptimizer::view() const
 CODIM_VIEW_LAYOUT(ShellView, ShellFields, nTri);
 CODIM_VIEW_LAYOUT(ShellLimitView, ShellLimitFields, nTri);
 CODIM_VIEW_LAYOUT(ShellRubberView, ShellRubberFields, nTri);
+CODIM_VIEW_LAYOUT(ShellWeaveView, ShellWeaveFields, nTri);
 CODIM_VIEW_LAYOUT(RodView, RodFields, nSeg);
 CODIM_VIEW_LAYOUT(AttachView, AttachFields, n);
 CODIM_VIEW_LAYOUT(ChamberView, ChamberFields, nTri);
@@ -136,6 +137,20 @@ ShellRubberView HipOptimizer::shellRubberView(const double* x_dev) const
     v.triConst = sh.d_triConst.p;
     v.rubTri = sh.d_rubTri.p;
     v.rubConst = sh.d_rubConst.p;
+    return v;
+}
+
+ShellWeaveView HipOptimizer::shellWeaveView(const double* x_dev) const
+{
+    const HipShell& sh = mesh.shell;
+    ShellWeaveView v;
+    static_cast<CodimBase&>(v) = codimBase(x_dev);
+    v.nTri = sh.nTri();
+    v.nWoven = sh.nWoven();
+    v.tri = sh.d_tri.p;
+    v.triConst = sh.d_triConst.p;
+    v.wovTri = sh.d_wovTri.p;
+    v.wovConst = sh.d_wovConst.p;
     return v;
 }
 
@@ -317,6 +332,9 @@ const CodimTerm CODIM_TERMS[] = {
     { HipOptimizer::CODIM_SHELL_RUBBER, [](const HipMesh& m) { return m.shell.nRubber(); },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_rubber_energy(o.shellRubberView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_rubber_assemble(o.shellRubberView(x), coef, proj, g, a, err, o.stream); } },
+    { HipOptimizer::CODIM_SHELL_WEAVE, [](const HipMesh& m) { return m.shell.nWoven(); },
+        [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_weave_energy(o.shellWeaveView(x), coef, partial, out, acc, o.stream); },
+        [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_weave_assemble(o.shellWeaveView(x), coef, proj, g, a, err, o.stream); } },
     { HipOptimizer::CODIM_SHELL_LIMIT, [](const HipMesh& m) { return m.shell.nLimited(); },
         [](const HipOptimizer& o, const double* x, double coef, double* partial, double* out, bool acc) { launch_shell_limit_energy(o.shellLimitView(x), coef, partial, out, acc, o.stream); },
         [](const HipOptimizer& o, const double* x, double coef, int proj, double* g, double* a, int* err) { launch_shell_limit_assemble(o.shellLimitView(x), coef, proj, g, a, err, o.stream); } },
@@ -726,7 +744,7 @@ void HipOptimizer::assembleDampingMtr()
     if (worldSize > 1) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream));
     if (shellOnly()) HIP_CHECK(hipMemsetAsync(d_damp.p, 0, sizeof(double) * nnz, stream)); // (no patch plan without tetrahedra: nothing else writes the values)
     launch_assemble_patches(v, patch, pb, pe, dampingStiff / dt, 1, nullptr, d_damp.p, stream);
-    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, limit, rod, attachment and fibre Hessians at the damping positions (a chamber's pressure is no stiffness, nor is air drag)
+    codimAssembleAdd(dampingStiff / dt, true, nullptr, d_damp.p, d_xDamp.p, CODIM_STIFFNESS); // the shell, rubber, weave, limit, rod, attachment and fibre Hessians at the damping positions (a chamber's pressure is no stiffness, nor is air drag)
     if (worldSize > 1) reduceSum(d_damp.p, (long long)nnz);
     launch_damp_clear_diag(mesh.nV, mesh.d_dbc.p, lin.d_ia.p, d_damp.p, stream);
     dampPatternVersion = lin.patternVersion;

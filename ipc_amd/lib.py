@@ -652,6 +652,48 @@ class Context:
         self._chk(self._L.ipcgpu_shell_thickness(self.h, _dp(h)))
         return h
 
+    # ---- woven cloth of the shell (ipcgpu_shell_set_weave: an orthotropic StVK membrane and direction-dependent bending on the chosen triangles)
+    def set_shell_weave(self, woven, direction=None, E1=None, E2=None, G12=None, nu12=None, bend_warp=None, bend_weft=None):
+        """woven: 0 or 1; direction: one 3-vector of rest space or one per shell triangle (projected into each triangle's rest plane: the warp); E1 (warp), E2
+        (weft), G12 (shear), nu12 (None: 0), bend_warp, bend_weft (None: 1): scalars or one value per shell triangle; woven None or all zeros removes the term.
+        After set_shell, also between time steps; set_shell and set_mesh drop it."""
+        n = self._shell_ntri()
+        w = None if woven is None else np.ascontiguousarray(np.broadcast_to(np.asarray(woven, dtype=np.int32), (n,)))
+        d = None if direction is None else _f64(np.broadcast_to(np.asarray(direction, dtype=np.float64), (n, 3)))
+        per = [None if a is None else _f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))) for a in (E1, E2, G12, nu12, bend_warp, bend_weft)]
+        self._chk(self._L.ipcgpu_shell_set_weave(self.h, _ip(w), _dp(d), *[_dp(a) for a in per]))
+
+    def shell_weave_get(self):
+        """dict: woven (nTri, int32), a (nTri x 2: the unit warp direction in each triangle's rest frame), const4 (nTri x 4: C11, C12, C22, G12), hingeFactor
+        (nHinge); zeros (ones for hingeFactor) without a woven triangle"""
+        n, nH = self._shell_counts()
+        w, a, c4, hf = np.zeros(n, dtype=np.int32), np.zeros((n, 2)), np.zeros((n, 4)), np.ones(nH)
+        self._chk(self._L.ipcgpu_shell_weave_get(self.h, _ip(w), _dp(a), _dp(c4), _dp(hf)))
+        return {"woven": w, "a": a, "const4": c4, "hingeFactor": hf}
+
+    def shell_weave_energy(self, coef=1.0):
+        return self._codim_energy("shell_weave", coef)
+
+    def shell_weave_energy_per_elem(self):
+        """the unscaled woven energy per shell triangle (0 for one that is not woven)"""
+        t = np.zeros(self._shell_ntri())
+        self._chk(self._L.ipcgpu_shell_weave_energy_per_elem(self.h, _dp(t)))
+        return t
+
+    def shell_weave_gradient_add(self, coef=1.0, projectDBC=True, grad=None):
+        """grad (3 nV, xyz interleaved; zeros when None) += coef * gradient of the woven term; returns it"""
+        return self._codim_gradient_add("shell_weave", coef, projectDBC, grad)
+
+    def shell_weave_hessian_add(self, coef=1.0, projectDBC=True):
+        self._codim_hessian_add("shell_weave", coef, projectDBC)
+
+    def shell_weave_state(self):
+        """nTri x 6 per shell triangle: the warp strain Eww, the weft strain Eff, the shear angle between the yarns (radians) and the current unit warp direction
+        (x, y, z); NaN where a yarn direction has length 0, zeros on a triangle that is not woven"""
+        s = np.zeros((6, self._shell_ntri()))
+        self._chk(self._L.ipcgpu_shell_weave_state(self.h, _dp(s)))
+        return np.ascontiguousarray(s.T)
+
     # ---- plastic flow of the shell (ipcgpu_shell_set_plasticity: permanent stretch, creases and dents; ipc_amd/csrc/shell_plastic_kernels.h)
     def _shell_counts(self):
         cnt = np.zeros(2, dtype=np.int32)

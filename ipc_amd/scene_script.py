@@ -67,6 +67,12 @@ class Shape:
     # `shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]`: this shape's triangles carry the incompressible Mooney-Rivlin membrane in place of
     # the StVK one (Context.set_shell_membrane); alpha in [0, 1) is the I2 fraction, default 0 = neo-Hookean; per shape, shapes may differ
     shell_rubber: bool = False
+    # `shell <thickness> [bend <scale>] weave <E1> <E2> <G12> dir <x> <y> <z> [nu12 <v>] [bendwarp <s>] [bendweft <s>] [limit ...]`: this shape's triangles are woven
+    # cloth -- an orthotropic StVK membrane with Young's moduli E1 along the warp and E2 along the weft, the shear modulus G12 and Poisson's ratio nu12 (default
+    # 0), and bending factors about the two yarn directions (default 1 1) -- in place of the isotropic one (Context.set_shell_weave;
+    # ipc_amd/csrc/shell_weave_kernels.h).  dir is the warp in the mesh file's frame; it turns (and scales) with the shape line's transform and is projected into
+    # every triangle.  Stands where `rubber` does; not with `rubber` or `yield`.  {E1, E2, G12, dir, nu12, bendwarp, bendweft}, or None
+    shell_weave: dict = None
     # `shell <thickness> [bend <s>] [limit ...] yield <y> [bendyield <yb>] [creep <rate>] [harden <K>]`: this shape's triangles flow plastically -- the membrane
     # where the deviatoric Hencky strain norm exceeds y + K alpha, a hinge where its outer-fibre strain exceeds yb + K alphaB (Context.shell_set_plasticity);
     # bendyield defaults to yield, creep to inf (returned within the step), harden to 0; not with `rubber`.  (yield, bendyield, creep, harden), or None
@@ -588,6 +594,35 @@ def _parse_shape(st, resolve):
                     raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]")
             elif j < len(st) and st[j] == "mr":
                 raise ValueError("mr belongs behind rubber")
+            if j < len(st) and st[j] == "weave":
+                if sh.shell_rubber:
+                    raise ValueError("weave is not valid behind rubber: a triangle carries one membrane law, the rubber one or the woven one")
+                if j + 7 >= len(st) or st[j + 4] != "dir":
+                    raise ValueError("weave needs <E1> <E2> <G12> dir <x> <y> <z>")
+                wv = {"E1": float(st[j + 1]), "E2": float(st[j + 2]), "G12": float(st[j + 3]), "dir": tuple(float(x) for x in st[j + 5:j + 8]),
+                      "nu12": 0.0, "bendwarp": 1.0, "bendweft": 1.0}
+                j += 8
+                for word in ("nu12", "bendwarp", "bendweft"):
+                    if j < len(st) and st[j] == word:
+                        if j + 1 >= len(st):
+                            raise ValueError(word + " needs a number")
+                        wv[word] = float(st[j + 1])
+                        j += 2
+                if not all(0.0 < wv[k] < math.inf for k in ("E1", "E2", "G12")):
+                    raise ValueError("weave needs positive, finite moduli E1, E2 and G12")
+                if not all(math.isfinite(x) for x in wv["dir"]) or not any(x != 0.0 for x in wv["dir"]):
+                    raise ValueError("weave needs a finite direction that is not zero")
+                if not (math.isfinite(wv["nu12"]) and wv["nu12"] ** 2 < wv["E1"] / wv["E2"]):
+                    raise ValueError("nu12 needs nu12^2 < E1 / E2: the law is not positive definite otherwise")
+                if not all(0.0 < wv[k] < math.inf for k in ("bendwarp", "bendweft")):
+                    raise ValueError("bendwarp and bendweft need positive, finite factors")
+                sh.shell_weave = wv
+                if j < len(st) and st[j] in ("bend", "weave", "dir", "nu12", "bendwarp", "bendweft", "mr"):
+                    raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] weave <E1> <E2> <G12> dir <x> <y> <z> [nu12 <v>] [bendwarp <s>] [bendweft <s>] [limit ...]")
+                if j < len(st) and st[j] == "rubber":
+                    raise ValueError("rubber is not valid behind weave: a triangle carries one membrane law, the woven one or the rubber one")
+            elif j < len(st) and st[j] in ("dir", "nu12", "bendwarp", "bendweft"):
+                raise ValueError(st[j] + " belongs behind weave")
             if j < len(st) and st[j] == "limit":
                 if j + 1 >= len(st):
                     raise ValueError("limit needs a stretch")
@@ -606,6 +641,8 @@ def _parse_shape(st, resolve):
             if j < len(st) and st[j] == "yield":
                 if sh.shell_rubber:
                     raise ValueError("yield is not valid behind rubber: a rubber membrane has no plastic flow")
+                if sh.shell_weave is not None:
+                    raise ValueError("yield is not valid behind weave: plastic flow rewrites the rest metric, in which warp and weft would stop being orthonormal")
                 if j + 1 >= len(st):
                     raise ValueError("yield needs a strain")
                 par = {"yield": float(st[j + 1]), "bendyield": None, "creep": math.inf, "harden": 0.0}
@@ -625,6 +662,8 @@ def _parse_shape(st, resolve):
                     raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <s>] [limit ...] yield <y> [bendyield <yb>] [creep <rate>] [harden <K>]")
             elif j < len(st) and st[j] in ("bendyield", "creep", "harden"):
                 raise ValueError(st[j] + " belongs behind yield")
+            if j < len(st) and st[j] == "weave":
+                raise ValueError("weave is misplaced: shell <thickness> [bend <scale>] weave <E1> <E2> <G12> dir <x> <y> <z> [nu12 <v>] [bendwarp <s>] [bendweft <s>] [limit ...]")
             if j < len(st) and st[j] in ("rubber", "mr", "bend"):
                 raise ValueError(st[j] + " is misplaced: shell <thickness> [bend <scale>] [rubber [mr <alpha>]] [limit ...]")
         elif e == "rod":
@@ -999,12 +1038,20 @@ def _outward_faces(SF, T, V):
     return tri
 
 
+def _weave_record(sh):
+    """the `weave` part of a shell shape with the warp turned and scaled like the shape (as a fibre direction is: _fiber_payload), or None"""
+    if sh.shell_weave is None:
+        return None
+    d = _rot(sh.rotate_deg) @ (np.asarray(sh.shell_weave["dir"], dtype=np.float64) * sh.scale)
+    return dict(sh.shell_weave, dir=d / np.linalg.norm(d))
+
+
 def _codim_keywords(cfg, sh, name, V, T, SF, E, off, p):
     """the `shell`, `rod`, `pressure` and `aero` keywords of one shape (transformed nodes V, first node `off`) as records of p"""
     mat = sh.material if sh.material is not None and all(np.isfinite(sh.material)) else (cfg.rho, cfg.YM, cfg.PR)
     if sh.shell_thickness is not None:  # (a triangle mesh: _parse_shape refuses the keyword on any other shape)
         p.shells.append((SF + off, sh.shell_thickness, sh.shell_bend, mat, (0.0, 1.0, 1.0) if sh.shell_limit is None else (sh.shell_limit, sh.shell_onset, sh.shell_stiff),
-                         (1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0), sh.shell_plastic))
+                         (1, sh.shell_alpha) if sh.shell_rubber else (0, 0.0), sh.shell_plastic, _weave_record(sh)))
     if sh.rod_radius is not None:  # (a segment mesh: _parse_shape refuses the keyword on any other shape)
         p.rods.append((E + off, sh.rod_radius, sh.rod_bend, mat))
     if sh.pressure is not None:  # (a shell or a tetrahedral shape: _parse_shape refuses the keyword on any other); on the transformed shape: a mirroring scale flips it
@@ -1171,6 +1218,12 @@ def _codim_payloads(p, attachments, V):
         if any(r[5][0] for r in p.shells):  # per triangle, as Context.set_shell_membrane takes them; a shape without `rubber` stays StVK (0)
             shell["model"] = _per(p.shells, lambda r: r[5][0], dtype=np.int32)
             shell["alpha"] = _per(p.shells, lambda r: float(r[5][1]))
+        if any(r[7] is not None for r in p.shells):  # per triangle, as Context.set_shell_weave takes them; a shape without `weave` stays as it is (0; the rest is not read there)
+            wv = lambda k, none: (lambda r: none if r[7] is None else float(r[7][k]))
+            shell["weave"] = {"woven": _per(p.shells, lambda r: int(r[7] is not None), dtype=np.int32),
+                              "dir": np.vstack([np.tile(np.zeros(3) if r[7] is None else r[7]["dir"], (len(r[0]), 1)) for r in p.shells]),
+                              "E1": _per(p.shells, wv("E1", 0.0)), "E2": _per(p.shells, wv("E2", 0.0)), "G12": _per(p.shells, wv("G12", 0.0)),
+                              "nu12": _per(p.shells, wv("nu12", 0.0)), "bend_warp": _per(p.shells, wv("bendwarp", 1.0)), "bend_weft": _per(p.shells, wv("bendweft", 1.0))}
         if any(r[6] is not None for r in p.shells):  # per plastic shape its triangle range within the shell and the four parameters, as Context.shell_set_plasticity takes them
             ends = np.cumsum([len(r[0]) for r in p.shells])
             shell["plastic"] = [((int(e - len(r[0])), int(e)),) + tuple(r[6]) for r, e in zip(p.shells, ends) if r[6] is not None]
@@ -1242,6 +1295,9 @@ def apply(sc, be):
         be.set_shell(q["tri"], q["thickness"], q["YM"], q["PR"], q["rho"], q["bend"])
         if "model" in q:
             be.set_shell_membrane(q["model"], q["alpha"])
+        if "weave" in q:
+            w = q["weave"]
+            be.set_shell_weave(w["woven"], w["dir"], w["E1"], w["E2"], w["G12"], w["nu12"], w["bend_warp"], w["bend_weft"])
         if "limit" in q:
             be.set_shell_strain_limit(q["limit"], q["onset"], q["stiff"])
         for rng, y, yb, creep, harden in q.get("plastic", ()):  # one call per plastic shape, over its triangle range
